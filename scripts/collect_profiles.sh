@@ -11,7 +11,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # (the program goes directly after `--`: no env / bash -c hop under rocprofv3)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -- python3 $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extra-config > $OUT/${TAG}_stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -- python3 $ROOT/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-extra-config > $OUT/${TAG}_stats.log 2>&1
 for cfg in 1 2; do
   for c in FETCH_SIZE WRITE_SIZE; do
     rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/${TAG}_pmc${cfg}_$c -- python3 $ROOT/bench.py --steps 3 --warmup 1 --config $cfg --no-cpu-baseline --no-extra-config > $OUT/${TAG}_pmc${cfg}_$c.log 2>&1
@@ -101,6 +101,6 @@ print(open(f"gpurun_out/{tag}_sq_counters.txt").read())
 PY
 # the bench lines LAST: they attach the traffic capture just taken on this build (profiles/traffic_latest.json on this box)
 cp $OUT/traffic_latest.json $ROOT/profiles/traffic_latest.json
-python3 $ROOT/bench.py --steps 20 --warmup 3 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
-python3 $ROOT/bench.py --steps 10 --warmup 3 --config 2 --no-cpu-baseline --no-extra-config > $OUT/${TAG}_bench_config2.json 2>> $OUT/${TAG}_bench.err
+python3 $ROOT/bench.py --steps 20 --warmup 3 --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python3 $ROOT/bench.py --steps 10 --warmup 3 --config 2 --full --no-cpu-baseline --no-extra-config > $OUT/${TAG}_bench_config2.json 2>> $OUT/${TAG}_bench.err
 cat $OUT/${TAG}_bench.json

@@ -500,7 +500,7 @@ def test_bench_two_ranks_gloo_on_one_gpu():
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
-    common = ["--steps", "3", "--warmup", "1", "--frames", "16384"]
+    common = ["--steps", "3", "--warmup", "1", "--frames", "16384", "--full"]   # (--full: roofline and the config2 key)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo"] + common
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
@@ -522,3 +522,36 @@ def test_bench_two_ranks_gloo_on_one_gpu():
     c2, c21 = j["config2"], j1["config2_single_gpu"]
     assert c2["n_bins"] == c21["n_bins"] == 288 and "configs[2]" in c2["workload"] and c2["n_gpus"] == 2 and c21["n_gpus"] == 1
     assert abs(c2["value"] - 2 * 16384 * 3 / (c2["ms_per_step"] * 3e-3)) / c2["value"] < 1e-3
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """bench.py without --full: the headline line alone, and --dump-outputs writes what the timed path computed — the same bits this
+    process gets from one call of the path on the same seeded input."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    from pitchvis_amd.sharding import stream_slice
+    F = 16384
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--frames", str(F),
+                        "--settle-ms", "0", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert j["metric"] == "vqt_frames_per_sec" and j["unit"] == "frames/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+    assert j["steps"] == 3 and j["value"] > 0 and abs(j["value"] - F * 3 / (j["ms_per_step"] * 3e-3)) / j["value"] < 1e-3
+    assert not {"roofline", "alt_gemm", "cold_start", "config2_single_gpu", "cpu_baseline"} & set(j)
+    got = {n[:-4]: np.load(os.path.join(tmp_path, n)) for n in os.listdir(tmp_path)}
+    assert set(got) == {"frames", "db", "peaks", "peak_count", "peak_center", "peak_size"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert np.array_equal(got["frames"], np.arange(F))   # (F <= the sample size: every frame)
+    # the same step in this process: the bench's workload, its shard, its settings
+    W = bench.WORKLOADS[1]
+    v = P.Vqt.new(P.VqtParameters(sr=bench.SR, range=P.VqtRange(55.0, W["octaves"], 36)), 0)
+    v.set_algo(P.ALGO_AUTO); v.set_gemm_precision(P.GEMM_F32)
+    s = plan_shard(F, bench.HOP, v.window_union, 0, 1)
+    d_pcm = stream_slice(W["seed"], s.sample_begin, s.sample_end, "cuda")
+    db, mask, cnt, ctr, sz = _run(v, d_pcm.cpu().numpy(), bench.HOP, F, n_lead=s.n_lead)
+    peaks = np.unpackbits(mask.view(np.uint8), axis=1, bitorder="little")[:, :v.n_bins]
+    for name, want in (("db", db), ("peaks", peaks), ("peak_count", cnt), ("peak_center", ctr), ("peak_size", sz)):
+        assert np.array_equal(got[name], want.astype(np.float32)), name
+    assert int(cnt.sum()) > 0
