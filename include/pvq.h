@@ -132,6 +132,12 @@ pvq_status pvq_vqt_calculate_batch_db(pvq_vqt *v, const float *pcm, size_t n_lea
  * Device-pointer form: d_pcm, d_out_db (and optional d_out_cplx: [n_frames][n_bins][2], the
  * complex coefficients before power_to_db, may be NULL) are device memory on the handle's GPU.
  * Enqueued on `stream` (a hipStream_t; NULL = default stream); returns without synchronising.
+ *
+ * Bin counts.  pvq_vqt_create takes any geometry; what a call can compute depends on the path.  The block-DFT path takes
+ * 3..1024 bins, as do peak detection (pvq_analyze_batch*, pvq_vqt_analyze_batch*) and the batched AnalysisState; above 1024 they
+ * return PVQ_ERR_UNSUPPORTED with a message and leave their outputs untouched.  The FFT path (PVQ_ALGO_AUTO above 1024 bins, and
+ * pvq_vqt_calculate_instant_db) takes up to 4096 bins while a frame's largest FFT and its bins fit 160 KB of LDS (about 3000 bins
+ * beside a 32 768-sample window); beyond that the call returns PVQ_ERR_UNSUPPORTED with a message, before anything is launched.
  */
 pvq_status pvq_vqt_calculate_batch_db_device(pvq_vqt *v, const float *d_pcm, size_t n_lead,
                                              size_t hop, size_t n_frames, float *d_out_db,

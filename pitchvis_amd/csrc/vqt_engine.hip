@@ -20,6 +20,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <type_traits>
 
 #include "device_tables.hpp"
@@ -276,7 +277,7 @@ __device__ __forceinline__ void db_epilogue(const float2* xv, float* red, int n_
                                             float* lds_out, int tid, unsigned* status, bool live = true) {
     const float ref_db = 10.0f * log10f(PVQ_REF_POWER);
     constexpr int NW = T / 64;
-    constexpr int PER = 1024 / T < 4 ? 4 : 1024 / T;  // supports n_bins <= 1024 (and <= 4 T)
+    constexpr int PER = 1024 / T < 4 ? 4 : 1024 / T;  // supports n_bins <= max(1024, 4 T): fft_db_threads() picks T
     float d[PER];
     float mx = -3.40282347e+38f, mn = 3.40282347e+38f;
     bool bad = false;
@@ -320,6 +321,15 @@ __device__ __forceinline__ void db_epilogue(const float2* xv, float* red, int n_
             if (lds_out) lds_out[k] = r;
         }
     }
+}
+
+// threads per frame the dB epilogue needs for n_bins (PER * T >= n_bins): the forms up to 1024 bins keep their own T; beyond, 512
+// threads cover 2 048 bins and 1 024 threads 4 096 (FFT_MAX_BINS, the most any form covers).  Same bits for every T: a bin's dB is
+// computed alone, the frame's max / min are exact.
+constexpr int FFT_MAX_BINS = 4096;
+constexpr size_t FFT_MAX_LDS = 160 * 1024;   // a workgroup's LDS on gfx950
+__host__ __device__ constexpr int fft_db_threads(int T, int n_bins) {
+    return n_bins <= (1024 / T < 4 ? 4 * T : 1024) ? T : n_bins <= 2048 ? (T > 512 ? T : 512) : 1024;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -526,7 +536,7 @@ __global__ __launch_bounds__(BLOCK, 4) void vqt_fft_frames(FftArgs a) {   // fou
 // pass chain is unrolled, and a workgroup serves one window group (the launch is per group, as the few-frames form of the kernel
 // above already is: rows of x_vqt through `xv_split`, db_rows finishes the frames).  The arithmetic is the walk's — the same twiddle
 // table entries, the same cmul and RegFft<R>, the same pass radices and pruning, the same real split and row dots with the same
-// lanes-per-row — so a frame's bits are what vqt_fft_frames gives (tests/test_parity_gpu.py::test_fft_batch_kernels_equal_the_walk).
+// lanes-per-row — so a frame's bits are what vqt_fft_frames gives (tests/test_configs_gpu.py::test_fft_batch_kernels_equal_the_walk_in_subprocesses).
 // ------------------------------------------------------------------------------------------------
 template <int R, int N, int P, int T>
 __device__ __forceinline__ void stockham_pass_ct(float2* __restrict__ Z, const float2* __restrict__ tw, int n_tw, int tl) {
@@ -1259,10 +1269,17 @@ pvq_status Vqt::launch_fft_streams(const void* st_table, size_t n_st, const floa
     // threads per frame: one radix-16 butterfly per thread and pass for the largest window; 512-thread workgroups hold
     // 512 / T frames side by side (a single frame, e.g. the streaming front end's, keeps the whole workgroup)
     const int n_tw = dev_->n_tw;
-    const int T = n_frames < 4 ? (n_tw <= 8192 ? 512 : 1024) : n_tw <= 2048 ? 128 : n_tw <= 4096 ? 256 : n_tw <= 8192 ? 512 : 1024;
+    // (more than 1 024 bins: at least as many threads as the dB epilogue needs for them, fft_db_threads)
+    const int T = fft_db_threads(n_frames < 4 ? (n_tw <= 8192 ? 512 : 1024) : n_tw <= 2048 ? 128 : n_tw <= 4096 ? 256 : n_tw <= 8192 ? 512 : 1024,
+                                 a.n_bins);
     const int BLOCK = T == 1024 ? 1024 : 512;
     const int F = BLOCK / T;
     const size_t lds = (size_t)F * (sizeof(float2) * ((size_t)(n_tw + (n_tw >> 4)) + 1 + a.n_bins) + sizeof(float) * 2 * (T / 64));
+    if (a.n_bins > FFT_MAX_BINS || lds > FFT_MAX_LDS) {   // (up to 1 024 bins every form fits: 147 KB at most, 16 384-point FFTs)
+        set_last_error("unsupported: the FFT path takes up to 4096 bins, and a frame's largest FFT and its bins must fit 160 KB of LDS (" +
+                       std::to_string(a.n_bins) + " bins, " + std::to_string(lds) + " bytes)");
+        return PVQ_ERR_UNSUPPORTED;
+    }
     int grid = (int)std::min<size_t>((n_frames + F - 1) / F, 1u << 20);
     // few frames of one stream: a workgroup per window group (FftArgs::xv_split).  Measured against the walk (profiles/r04_fft_split.txt):
     // 1 frame 47 -> 19 us at 48 kHz / 252 bins (77 -> 27 at 96 kHz / 360), ahead up to ~400 frames there (~200 at 96 kHz, ~750 at
@@ -1311,8 +1328,12 @@ pvq_status Vqt::launch_fft_streams(const void* st_table, size_t n_st, const floa
                 }
                 if (ls != PVQ_OK) return ls;
             }
-            hipLaunchKernelGGL(db_rows_batch<256>, dim3((unsigned)nf), dim3(256), 0, stream, static_cast<const float2*>(ws_split_), nf, (int)f0, a.n_bins, a.streams, a.n_streams,
-                               a.out_db, a.out_cplx, a.status);
+            if (fft_db_threads(256, a.n_bins) == 256)
+                hipLaunchKernelGGL(db_rows_batch<256>, dim3((unsigned)nf), dim3(256), 0, stream, static_cast<const float2*>(ws_split_), nf, (int)f0, a.n_bins, a.streams,
+                                   a.n_streams, a.out_db, a.out_cplx, a.status);
+            else   // more than 1 024 bins
+                hipLaunchKernelGGL(db_rows_batch<1024>, dim3((unsigned)nf), dim3(1024), 0, stream, static_cast<const float2*>(ws_split_), nf, (int)f0, a.n_bins, a.streams,
+                                   a.n_streams, a.out_db, a.out_cplx, a.status);
         }
         slot_end(SLOT_FFT_FRAMES, stream);
         if (pk) {
