@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PVQ_ABI_VERSION 4   /* 4: + pvq_vqt_calculate_batch_db_streams, pvq_vqt_analyze_batch_streams (many streams per call).  3: + pvq_vqt_set_workspace_limit, pvq_plan_shard, pvq_vqt_analyze_batch_multi, pvq_analysis_batch_*, profiling mode 2; per-call NaN flag semantics of the synchronous entry points */
+#define PVQ_ABI_VERSION 4   /* (pvq_agc_batch_* came later and left the number alone: new symbols only, nothing that existed changed.)  4: + pvq_vqt_calculate_batch_db_streams, pvq_vqt_analyze_batch_streams (many streams per call).  3: + pvq_vqt_set_workspace_limit, pvq_plan_shard, pvq_vqt_analyze_batch_multi, pvq_analysis_batch_*, profiling mode 2; per-call NaN flag semantics of the synchronous entry points */
 
 /* replaces VqtParameters + VqtRange (vqt.rs:238-262, 278-331), flattened POD */
 typedef struct pvq_vqt_params {
@@ -412,6 +412,29 @@ size_t pvq_train_chunk_samples(const pvq_vqt *v);
  * [n_chunks * chunk]; gain_out [n_chunks] (may be NULL) = agc.gain() after each chunk. */
 pvq_status pvq_train_condition_stream(pvq_mono_agc *a, const float *left, const float *right, size_t n_chunks,
                                       size_t chunk, float *mono_out, float *gain_out);
+/* The same conditioning for MANY streams on the device (the trainer's par_iter over files, train.rs:146-163): one MonoAgc per
+ * stream, a lane per stream for the recurrence, nothing leaves the device between conditioning and transform.  Every sample and
+ * every gain carries the bits pvq_train_condition_stream gives that stream.
+ * create: n_streams dagc::MonoAgc::new(desired_output_rms, distortion_factor) (dagc_fork/src/lib.rs:35-53) on device_id; the
+ * argument checks and texts of pvq_mono_agc_create, PVQ_ERR_INVALID_ARG before any device is touched; device_id < 0: a host-only
+ * handle whose condition call returns PVQ_ERR_NO_DEVICE. */
+typedef struct pvq_agc_batch pvq_agc_batch;
+pvq_status pvq_agc_batch_create(int device_id, uint32_t n_streams, float desired_output_rms, float distortion_factor,
+                                pvq_agc_batch **out);
+void pvq_agc_batch_destroy(pvq_agc_batch *b);
+/* train.rs:286-301 for every stream: d_left / d_right / d_mono_out are HOST arrays of n_streams DEVICE pointers (d_right NULL,
+ * or an entry NULL: that stream is mono); stream s has n_chunks[s] chunks of `chunk` samples and nothing past them is written.
+ * d_gain_out (device, may be NULL): [n_streams][gain_stride], agc.gain() after each chunk; entries past a stream's n_chunks are
+ * left alone.  In place is allowed (d_mono_out[s] == d_left[s]); rows that overlap in any other way are not.  Every stream's gain
+ * persists between calls, like one MonoAgc per stream on the host.  PVQ_ERR_INVALID_ARG (chunk == 0, a null table, a null left or
+ * output pointer of a stream with chunks, gain_stride smaller than a stream's n_chunks) before anything is launched.  Asynchronous
+ * on `stream`; the calls of one handle go to one stream.  d_mono_out is what pvq_vqt_calculate_batch_db_streams takes as d_pcm
+ * with hop = chunk * step, n_lead = NULL, n_frames[s] = n_chunks[s] / step: the many-streams form of pvq_train_frames_db. */
+pvq_status pvq_agc_batch_condition_device(pvq_agc_batch *b, const float *const *d_left, const float *const *d_right,
+                                          const size_t *n_chunks, size_t chunk, float *const *d_mono_out,
+                                          float *d_gain_out, size_t gain_stride, void *stream);
+/* lib.rs:72 for every stream after the last call: gains [n_streams] (synchronises) */
+pvq_status pvq_agc_batch_get_gains(pvq_agc_batch *b, float *gains);
 /* train.rs:341 for every step-th chunk (STEP_SIZE_IN_CHUNKS = 3, train.rs:44), on the GPU: frame f = VQT dB of
  * the last n_fft conditioned samples after chunk (f+1)*step (zeros before the stream, the ring buffer of
  * train.rs:268-269).  out_db [n_chunks / step][n_bins]. */

@@ -31,6 +31,7 @@ EXPORTS = [
     "pvq_analysis_state_tuning_grid_inaccuracy",
     "pvq_mono_agc_create", "pvq_mono_agc_destroy", "pvq_mono_agc_freeze_gain", "pvq_mono_agc_is_gain_frozen",
     "pvq_mono_agc_gain", "pvq_mono_agc_process", "pvq_train_chunk_samples", "pvq_train_condition_stream",
+    "pvq_agc_batch_create", "pvq_agc_batch_destroy", "pvq_agc_batch_condition_device", "pvq_agc_batch_get_gains",
     "pvq_train_frames_db", "pvq_train_rows", "pvq_npy_write_f32", "pvq_stream_create", "pvq_stream_destroy",
     "pvq_stream_push", "pvq_stream_gain", "pvq_stream_chunk_size_ms", "pvq_stream_frame_db", "pvq_stream_read",
     "pvq_calculate_color", "pvq_led_frame", "pvq_host_alloc", "pvq_host_free",
@@ -215,6 +216,11 @@ def load():
     L.pvq_train_chunk_samples.argtypes = [vp]; L.pvq_train_chunk_samples.restype = C.c_size_t
     L.pvq_train_condition_stream.argtypes = [vp, fp, fp, C.c_size_t, C.c_size_t, fp, fp]
     L.pvq_train_condition_stream.restype = C.c_int
+    L.pvq_agc_batch_create.argtypes = [C.c_int, C.c_uint32, C.c_float, C.c_float, C.POINTER(vp)]; L.pvq_agc_batch_create.restype = C.c_int
+    L.pvq_agc_batch_destroy.argtypes = [vp]
+    L.pvq_agc_batch_condition_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), szp, C.c_size_t, C.POINTER(vp), vp, C.c_size_t, vp]
+    L.pvq_agc_batch_condition_device.restype = C.c_int
+    L.pvq_agc_batch_get_gains.argtypes = [vp, fp]; L.pvq_agc_batch_get_gains.restype = C.c_int
     L.pvq_train_frames_db.argtypes = [vp, fp, C.c_size_t, C.c_size_t, C.c_size_t, fp]; L.pvq_train_frames_db.restype = C.c_int
     L.pvq_train_rows.argtypes = [fp, C.c_size_t, C.c_uint32, up, ip, fp, fp, fp, fp]; L.pvq_train_rows.restype = C.c_int
     L.pvq_npy_write_f32.argtypes = [C.c_char_p, fp, C.c_uint64]; L.pvq_npy_write_f32.restype = C.c_int

@@ -2,6 +2,7 @@
 
 * ``MonoAgc``                        — dagc_fork/src/lib.rs:19-87
 * ``train_dataset`` / ``write_npy``  — pitchvis_train/src/train.rs:252-351, 443-460, 192-208 (frames on the GPU)
+* ``AgcBatch`` / ``train_dataset_streams`` — the same for many rendered streams at once (train.rs:146-163), conditioned on the device
 * ``Stream``                         — the pitchvis_audio RingBuffer contract with a device-resident ring
 * ``calculate_color`` / ``led_frame``— pitchvis_colors/src/lib.rs:86-117, pitchvis_serial/src/main.rs:122-175
 """
@@ -89,6 +90,12 @@ def train_dataset(vqt, left: np.ndarray, right: Optional[np.ndarray], voices: Se
     n_frames = n_chunks // step
     db = np.empty((n_frames, vqt.n_bins), np.float32)
     _check(L.pvq_train_frames_db(vqt._h, _f(mono), n_chunks, chunk, step, _f(db)))
+    return _train_rows(L, vqt.n_bins, db, gains, voices, step)
+
+
+def _train_rows(L, n_bins: int, db: np.ndarray, gains: np.ndarray, voices, step: int) -> np.ndarray:
+    """train.rs:317-337, 347, 443-460 for one stream: db [n_frames][n_bins], gains [n_chunks] -> flat rows"""
+    n_frames = db.shape[0]
     assert len(voices) == n_frames
     ptr = np.zeros(n_frames + 1, np.uint32)
     keys, gl, gr = [], [], []
@@ -100,10 +107,97 @@ def train_dataset(vqt, left: np.ndarray, right: Optional[np.ndarray], voices: Se
     gl = np.asarray(gl if gl else [0], np.float32)
     gr = np.asarray(gr if gr else [0], np.float32)
     agc_gain = np.ascontiguousarray(gains[step - 1::step][:n_frames])   # agc.gain() at the analysed chunks (train.rs:326)
-    rows = np.empty((n_frames, vqt.n_bins + 128), np.float32)
-    _check(L.pvq_train_rows(_f(db), n_frames, vqt.n_bins, ptr.ctypes.data_as(C.POINTER(C.c_uint32)),
+    rows = np.empty((n_frames, n_bins + 128), np.float32)
+    _check(L.pvq_train_rows(_f(db), n_frames, n_bins, ptr.ctypes.data_as(C.POINTER(C.c_uint32)),
                             keys.ctypes.data_as(C.POINTER(C.c_int32)), _f(gl), _f(gr), _f(agc_gain), _f(rows)))
     return rows.reshape(-1)
+
+
+class AgcBatch:
+    """One dagc::MonoAgc per stream for MANY streams on the GPU (pvq_agc_batch_*): the trainer's conditioning (train.rs:286-301:
+    downmix, silence gate, AGC) with a lane per stream, the bits of ``pvq_train_condition_stream``; gains kept between calls.
+    ``device=None``: a host-only handle (the argument checks work; conditioning raises: no CPU fallback)."""
+
+    def __init__(self, n_streams: int, desired_output_rms: float, distortion_factor: float, device: Optional[int] = 0):
+        self._L = _lib.load()
+        self.n_streams = int(n_streams)
+        self._h = C.c_void_p()
+        st = self._L.pvq_agc_batch_create(-1 if device is None else int(device), self.n_streams, desired_output_rms, distortion_factor,
+                                          C.byref(self._h))
+        if st == _lib.PVQ_ERR_INVALID_ARG:
+            raise ValueError((self._L.pvq_last_error() or b"").decode())
+        _check(st)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._L.pvq_agc_batch_destroy(h)
+            self._h = None
+
+    def condition_device(self, d_lefts, d_rights, n_chunks, chunk: int, d_outs=None, d_gain_out=None, gain_stride: Optional[int] = None,
+                         stream=None) -> None:
+        """d_lefts / d_rights / d_outs: sequences of device tensors (or raw pointers), one per stream; d_rights None, or an entry
+        None: mono; d_outs None: in place over d_lefts.  d_gain_out: device tensor [n_streams][gain_stride] (default stride: its
+        second dimension).  Asynchronous on `stream`."""
+        from . import _ptr, _stream_handle
+        n = self.n_streams
+        if len(d_lefts) != n or len(n_chunks) != n or (d_rights is not None and len(d_rights) != n) or (d_outs is not None and len(d_outs) != n):
+            raise ValueError("one entry per stream of the batch")
+        tab = lambda ts: (C.c_void_p * n)(*[_ptr(t) for t in ts])
+        lefts = tab(d_lefts)
+        if gain_stride is None:
+            gain_stride = int(d_gain_out.shape[1]) if d_gain_out is not None else 0
+        _check(self._L.pvq_agc_batch_condition_device(self._h, lefts, tab(d_rights) if d_rights is not None else None,
+                                                      (C.c_size_t * n)(*[int(x) for x in n_chunks]), int(chunk),
+                                                      tab(d_outs) if d_outs is not None else lefts, _ptr(d_gain_out), int(gain_stride),
+                                                      _stream_handle(stream)))
+
+    def gains(self) -> np.ndarray:
+        """MonoAgc::gain of every stream after the last call (synchronises)"""
+        out = np.empty(self.n_streams, np.float32)
+        _check(self._L.pvq_agc_batch_get_gains(self._h, _f(out)))
+        return out
+
+
+def train_dataset_streams(vqt, lefts, rights, voices, step: int = STEP_SIZE_IN_CHUNKS):
+    """``train_dataset`` for MANY rendered streams at once, the trainer's par_iter over files (train.rs:146-163): every stream is
+    uploaded once, conditioned on the device (one MonoAgc(0.07, 0.001) each, train.rs:265), all frames of all streams come from ONE
+    many-streams transform call, and only dB rows and per-chunk gains come back.  ``lefts[s]`` / ``rights[s]`` (``rights`` or an
+    entry None: mono) / ``voices[s]`` as ``train_dataset``'s arguments.  Returns one flat row array per stream, laid out as
+    ``train_dataset``'s."""
+    import torch
+    L = _lib.load()
+    n = len(lefts)
+    if n == 0:
+        return []
+    chunk = train_chunk_samples(vqt)
+    dev = torch.device("cuda", vqt.device)
+    n_chunks, d_l, d_r = [], [], []
+    for s in range(n):
+        left = np.ascontiguousarray(lefts[s], np.float32)
+        nc = left.size // chunk
+        assert nc * chunk == left.size, "every stream must be a whole number of chunks"
+        n_chunks.append(nc)
+        d_l.append(torch.from_numpy(left).to(dev))
+        right = rights[s] if rights is not None else None
+        if right is not None:
+            right = np.ascontiguousarray(right, np.float32)
+            assert right.size == left.size
+            d_r.append(torch.from_numpy(right).to(dev))
+        else:
+            d_r.append(None)
+    n_frames = [nc // step for nc in n_chunks]
+    max_chunks, max_frames = max(max(n_chunks), 1), max(max(n_frames), 1)
+    with torch.cuda.device(dev):
+        agc = AgcBatch(n, 0.07, 0.001, device=vqt.device)   # train.rs:265
+        d_gain = torch.zeros((n, max_chunks), dtype=torch.float32, device=dev)
+        agc.condition_device(d_l, d_r, n_chunks, chunk, d_gain_out=d_gain)   # in place: d_l now holds the conditioned mono streams
+        d_db = torch.empty((n, max_frames, vqt.n_bins), dtype=torch.float32, device=dev)
+        vqt.batch_streams_device(d_l, chunk * step, n_frames, d_db, out_stride_frames=max_frames)   # the ring buffer of train.rs:268-269: zeros before the stream
+        vqt.input_status()   # (waits; raises on a non-finite sample like pvq_train_frames_db)
+        db = d_db.cpu().numpy()
+        gains = d_gain.cpu().numpy()
+    return [_train_rows(L, vqt.n_bins, np.ascontiguousarray(db[s, :n_frames[s]]), gains[s, :n_chunks[s]], voices[s], step) for s in range(n)]
 
 
 def write_npy(path: str, data: np.ndarray) -> None:

@@ -12,6 +12,7 @@
 
 #include "analysis_batch.hpp"
 #include "analysis_host.hpp"
+#include "condition_batch.hpp"
 #include "consumers_host.hpp"
 #include "multi_host.hpp"
 #include "vqt_engine.hpp"
@@ -27,6 +28,9 @@ struct pvq_analysis_batch {
 };
 struct pvq_mono_agc {
     pvq::MonoAgc impl;
+};
+struct pvq_agc_batch {
+    std::unique_ptr<pvq::AgcBatch> impl;
 };
 // device-resident ring: the newest buf_size samples are d_ring[w - buf_size, w); compacted when the linear
 // buffer (4 x buf_size) runs out
@@ -806,6 +810,37 @@ pvq_status pvq_train_condition_stream(pvq_mono_agc* a, const float* left, const 
         if (!a || !left || !mono_out) return null_handle();
         pvq::train_condition_stream(a->impl, left, right, n_chunks, chunk, mono_out, gain_out);
         return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+// train.rs:146-163 + 286-301: the conditioning of many files side by side, on the device (condition_batch.hpp)
+pvq_status pvq_agc_batch_create(int device_id, uint32_t n_streams, float desired_output_rms, float distortion_factor, pvq_agc_batch** out) {
+    try {
+        if (!out) return null_handle();
+        *out = nullptr;
+        std::unique_ptr<pvq::AgcBatch> impl;
+        const pvq_status st = pvq::AgcBatch::create(device_id, n_streams, desired_output_rms, distortion_factor, impl);   // lib.rs:35-53
+        if (st != PVQ_OK) return st;
+        *out = new pvq_agc_batch{std::move(impl)};
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+void pvq_agc_batch_destroy(pvq_agc_batch* b) {
+    try {
+        delete b;
+    } catch (...) { (void)translate_exception(); }
+}
+pvq_status pvq_agc_batch_condition_device(pvq_agc_batch* b, const float* const* d_left, const float* const* d_right, const size_t* n_chunks,
+                                          size_t chunk, float* const* d_mono_out, float* d_gain_out, size_t gain_stride, void* stream) {
+    try {
+        if (!b) return null_handle();
+        return b->impl->condition_device(d_left, d_right, n_chunks, chunk, d_mono_out, d_gain_out, gain_stride,
+                                         static_cast<hipStream_t>(stream));   // train.rs:286-301
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_agc_batch_get_gains(pvq_agc_batch* b, float* gains) {
+    try {
+        if (!b) return null_handle();
+        return b->impl->get_gains(gains);   // lib.rs:72
     } catch (...) { return translate_exception(); }
 }
 pvq_status pvq_train_frames_db(pvq_vqt* v, const float* mono, size_t n_chunks, size_t chunk, size_t step, float* out_db) {
