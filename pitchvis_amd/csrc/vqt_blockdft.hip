@@ -14,14 +14,18 @@
 // log2(Nb)-level tree  A_{l+1}[j] = A_l[j] + phi^(2^l) A_l[j+2^l]  evaluated in LDS, then the
 // banded complex row dots (vqt.rs:889-910) and power_to_db (vqt.rs:922-954) as in the FFT path.
 //
-// Kernels:  blockdft_gemm_tree[_bf16x3] (MFMA GEMM + combine tree fused; windows of <= 64 hop blocks)
-//           blockdft_gemm + blockdft_combine (the same two stages unfused, for longer windows)
-//           blockdft_banddots_db (kernel product as a banded MFMA GEMM + power_to_db)
+// Kernels:  blockdft_gemm_tree[_bf16x3] (MFMA GEMM + combine tree fused; the first 64 hop blocks of a window)
+//           blockdft_tree_finish (the last one or two tree levels of windows of more than 64 hop blocks)
+//           blockdft_gemm_gen (hops that do not divide the windows: whole hop blocks + the window's remainder)
+//           blockdft_gemm_rows + blockdft_combine (the same two stages unfused: more than 8 window groups)
+//           blockdft_banddots4c_db / blockdft_banddots_db[_bf16x3] (kernel product as a banded MFMA GEMM + power_to_db)
+// Host planning (tables, run packing, tile lists) is blockdft_plan.cpp; this file uploads what it builds and launches.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <type_traits>
 
+#include "blockdft_plan.hpp"
 #include "device_tables.hpp"
 #include "peaks_device.hpp"
 #include "vqt_engine.hpp"
@@ -37,10 +41,11 @@ namespace pvq {
         }                                                                                          \
     } while (0)
 
-constexpr int GM_BN = 64;   // granularity of the column tiling: 64 floats = 32 complex spectrum columns
+static_assert(sizeof(Float2) == sizeof(float2) && alignof(Float2) == alignof(float2), "blockdft_plan.hpp: Float2 must match float2");
+static_assert(sizeof(Float4) == sizeof(float4) && alignof(Float4) == alignof(float4), "blockdft_plan.hpp: Float4 must match float4");
+static_assert(sizeof(Int4) == sizeof(int4) && alignof(Int4) == alignof(int4), "blockdft_plan.hpp: Int4 must match int4");
+
 constexpr int CB_T = 128;    // frames per combine workgroup
-constexpr int CB_C = GM_BN / 2;  // complex columns per combine workgroup
-constexpr int CB_MAX_NB = 256;  // hop blocks per window the combine tree supports (<= 64: 32-column tiles, else 16)
 // Frames per sub-batch: the X (+ Y) workspace is sized for one.  As many as the handle's workspace limit holds (default 1 GiB:
 // 131 072 frames at 48 kHz / 252 bins = 0.74 GB; wide geometries — 840 bins: 15 KB per frame — take fewer), a multiple of 64,
 // at most 147 456 (BASELINE configs[2]'s 131 072 per rank is one sub-batch; against two of 65 536 the step is 4 % shorter: one ramp and
@@ -51,40 +56,6 @@ static size_t chunk_frames(size_t limit_bytes, size_t bytes_per_frame) {
     size_t f = limit_bytes / std::max<size_t>(bytes_per_frame, 1) / 64 * 64;
     return std::min<size_t>(std::max<size_t>(f, 64), 147456);   // (131 072 + an eighth: 64 staged streams of 2 048 frames with their gaps are 135 168 frames — one launch, not one and a 4 000-frame tail)
 }
-
-struct BlockGroup {
-    int nb;         // hop blocks per window
-    int levels;     // log2(nb)
-    int n_cols;     // spectrum columns used
-    int tile0;      // first GEMM column tile of this group
-    int n_tiles;    // column tiles (of 32 complex columns)
-    int tw_off;     // into d_comb_tw: levels x (n_tiles*32) entries
-    long long s_rel;  // window begin relative to the end of the n_fft buffer: w0 - n_fft
-    int nb_f;       // blocks summed inside the fused kernel: min(nb, 64); the remaining levels run in blockdft_tree_finish
-    int levels_f;   // log2(nb_f)
-    // general hops (a multiple of 64 that does not divide the window, blockdft_gemm_gen): window = nq whole hop blocks + rem samples
-    int nq, rem;
-    int e16r_off;   // float4 index of the group's slices of E16R (the DFT matrix of the first rem samples of a block)
-    int gtw_off;    // float2 index into gen_tw: phi (n_tiles * 32 columns), then tau
-};
-
-// 16 output bins (rows of one window group's kernel) and the contiguous range of X columns they read
-struct BandBlock {
-    int x0;      // first X column
-    int kb;      // columns walked (multiple of BD_KU; coefficients beyond the true range are zero)
-    int boff;    // first column of this block in d_band_B (units of 64 floats)
-    int bin0;    // first output bin
-    int nrows;   // 1..16
-    int kg;      // 8-column groups walked by the split-bf16 form
-    int boff3;   // first group of this block in d_band_B3 (units of 3 planes x 64 lanes x 8 bf16)
-};
-constexpr int BD_RB = 16;   // bins per block: 32 MFMA columns = 16 x (re, im)
-constexpr int BD_KU = 4;    // columns per software-pipeline stage
-constexpr int BD_NS = 4;    // pipeline stages
-constexpr int BD8_RB = 8;   // bins per block of the 16x16x4 form
-constexpr int BD8_KU = 4;   // columns per stage (two column pairs = two MFMAs per 16-frame tile)
-constexpr int BD8_NS = 4;   // stages in the operand ring
-constexpr int X_PAD_COLS = 32;   // zeroed columns after the last X column (the operand prefetch runs past a block's range)
 
 struct BlockDftTables {
     size_t hop = 0;
@@ -115,18 +86,7 @@ struct BlockDftTables {
     float* d_P = nullptr;  size_t p_cap = 0;   // workspace
     float2* d_X = nullptr; size_t x_cap = 0;
     float2* d_Y = nullptr; size_t y_cap = 0;   // 64-block partial sums (windows of more than 64 blocks)
-    // frame-stripe tile order of the fused kernels, built per (frames, tile rows) and kept for the next launch
-    struct SegKey {   // one run of a launch: what decides its tiles, where its frames go
-        long long pcm_off, base, out_row0;
-        unsigned pcm_bytes;
-        int nf, x_tile0, y_tile0, row_step;
-        unsigned long long slot_hash;   // a run over a staged buffer of many streams: hash of its slots (0: none), its grid offset and first frame
-        long long grid_i, fbeg;
-        bool operator==(const SegKey& o) const {
-            return pcm_off == o.pcm_off && base == o.base && out_row0 == o.out_row0 && pcm_bytes == o.pcm_bytes && nf == o.nf && x_tile0 == o.x_tile0 && y_tile0 == o.y_tile0 &&
-                   row_step == o.row_step && slot_hash == o.slot_hash && grid_i == o.grid_i && fbeg == o.fbeg;
-        }
-    };
+    // frame-stripe tile order of the fused kernels, built per launch shape and kept for the next launch
     struct TileList {
         int4* d = nullptr; size_t cap = 0;            // device: the list, then the launch's segment table and X-tile map
         const struct SegDev* d_segs = nullptr;
@@ -148,28 +108,12 @@ struct BlockDftTables {
 
 void free_blockdft_tables(BlockDftTables* t) {
     if (!t) return;
-    if (t->d_E) (void)hipFree(t->d_E);
-    if (t->d_Et) (void)hipFree(t->d_Et);
-    if (t->d_tile_group) (void)hipFree(t->d_tile_group);
-    if (t->d_tile_s) (void)hipFree(t->d_tile_s);
-    if (t->d_groups) (void)hipFree(t->d_groups);
-    if (t->d_comb_tw) (void)hipFree(t->d_comb_tw);
-    if (t->d_band) (void)hipFree(t->d_band);
-    if (t->d_band_B) (void)hipFree(t->d_band_B);
-    if (t->d_band8) (void)hipFree(t->d_band8);
-    if (t->d_band_B4) (void)hipFree(t->d_band_B4);
-    if (t->d_band_list8) (void)hipFree(t->d_band_list8);
-    if (t->d_band_B3) (void)hipFree(t->d_band_B3);
-    if (t->d_band_list) (void)hipFree(t->d_band_list);
-    if (t->d_P) (void)hipFree(t->d_P);
-    if (t->d_X) (void)hipFree(t->d_X);
-    if (t->d_Y) (void)hipFree(t->d_Y);
+    for (void* p : {(void*)t->d_E, (void*)t->d_Et, (void*)t->d_tile_group, (void*)t->d_tile_s, (void*)t->d_groups, (void*)t->d_comb_tw, (void*)t->d_band, (void*)t->d_band_B,
+                    (void*)t->d_band8, (void*)t->d_band_B4, (void*)t->d_band_list8, (void*)t->d_band_B3, (void*)t->d_band_list, (void*)t->d_P, (void*)t->d_X, (void*)t->d_Y,
+                    (void*)t->d_clk, (void*)t->d_E16, (void*)t->d_E16R, (void*)t->d_gen_tw})
+        if (p) (void)hipFree(p);
     for (auto& tl : t->tile_lists)
         if (tl.d) (void)hipFree(tl.d);
-    if (t->d_clk) (void)hipFree(t->d_clk);
-    if (t->d_E16) (void)hipFree(t->d_E16);
-    if (t->d_E16R) (void)hipFree(t->d_E16R);
-    if (t->d_gen_tw) (void)hipFree(t->d_gen_tw);
     delete t;
 }
 
@@ -218,24 +162,8 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // +20 % MFMA work at 48 kHz / hop 256) in exchange for dropping the P round trip through memory
 // (172 MB written + ~200 MB read per 32 768 frames) and the separate combine launch.
 // ------------------------------------------------------------------------------------------------
-// MANY streams in one launch (pvq_vqt_*_streams: the trainer's shape, pitchvis_train/src/train.rs:146-163 — many files side by side).
-// A launch covers a list of SEGMENTS, each a contiguous run of frames of one stream; a tile list entry names its segment
-// (.x bits 16..31), the segment table gives the tile its stream (offset from the launch's base pointer, readable bytes, where
-// frame 0 of the run ends) and the run's first 64-frame tile in X / Y; XTile maps an X tile back to the output rows it holds.
-// segs == nullptr: one segment described by the kernel arguments themselves (the single-stream entry points: unchanged).
-struct alignas(16) SegDev {
-    long long pcm_off;    // samples from GemmTreeArgs::pcm_base to the segment's rebased stream pointer
-    long long base;       // index, relative to that pointer, of the end of the segment's frame 0
-    unsigned pcm_bytes;   // bytes readable from that pointer
-    int n_frames;         // frames of the segment
-    int x_tile0, y_tile0; // its first 64-frame tile in X / in Y
-};
-struct XTile {
-    long long out_row0;   // output row (of out_db, masks, ...) of the tile's frame 0
-    int live_step;        // bits 0..7: frames of the tile that exist (<= 64); bits 8..: output rows between consecutive frames (1, or r
-                          // for a run that holds every r-th frame of its stream: Vqt::run_batch's interleaved block grids)
-    int y_tile;           // the Y tile that holds the same frames' 64-block partial sums
-};
+// Many streams in one launch: SegDev / XTile (blockdft_plan.hpp).  segs == nullptr: one segment described by the kernel arguments
+// themselves (the single-stream entry points).
 
 struct GemmTreeArgs {
     const float* pcm_base;
@@ -985,6 +913,7 @@ __global__ __launch_bounds__(2 * BM, 4) void blockdft_gemm_tree(GemmTreeArgs a) 
     PVQ_END_STAMPS
 }
 
+#ifdef PVQ_DEV_KNOBS   // developer library only: measured, not adopted (PVQ_TREE3=1)
 // ------------------------------------------------------------------------------------------------
 // THREE workgroups per CU (round 5; DESIGN.md 5.2 "(i)").  The 256 x 32 tile's life is a serial chain of latencies of which the K loop
 // is about a third; two such lives per CU leave the matrix pipe idle whenever both are outside their K loops.  This form buys a third
@@ -1264,6 +1193,7 @@ __global__ __launch_bounds__(2 * BM, 6) void blockdft_gemm_tree3(GemmTreeArgs a)
     }
     PVQ_END_STAMPS
 }
+#endif   // PVQ_DEV_KNOBS
 
 // ------------------------------------------------------------------------------------------------
 // General hops: a multiple of 64 samples that does NOT divide the windows (1 600 samples = 30 analyses per second at 48 kHz, the
@@ -1281,7 +1211,6 @@ __global__ __launch_bounds__(2 * BM, 6) void blockdft_gemm_tree3(GemmTreeArgs a)
 // the Q tiles (257 - nq frames per tile), which add tau Y on their way out.  Same K loop, same P tile, same X layout as
 // blockdft_gemm_tree: the kernel-product and peak stages do not know the difference.
 // ------------------------------------------------------------------------------------------------
-constexpr int GEN_MAX_NQ = 16;   // whole blocks per window the combine takes (the P tile's 15 spare rows are its halo)
 template <int BM>
 __device__ __forceinline__ void gen_horner(float* smem, const float2* phi, int nq, int tid) {
     float2 (*A)[FT_LDP] = reinterpret_cast<float2 (*)[FT_LDP]>(smem);  // [BM + 15][33]
@@ -1422,7 +1351,6 @@ __global__ __launch_bounds__(2 * BM, 2) void blockdft_gemm_rows(GemmArgs a) {
 // bf16 = 36 KB of staging, swizzled instead of padded (4 workgroups per CU), aliased by the P tile.  Measured
 // accuracy equals the fp32 MFMA form (6e-7 of the frame peak); the K loop runs at ~35 % of the bf16 matrix peak,
 // bounded by the LDS staging and barrier structure of a 128 x 64 tile, not by the matrix pipe.
-constexpr int FB_BK = 32;
 template <int BM> struct FbGeom {
     static constexpr int PLANE = (BM + FT_BN) * FB_BK;            // bf16 elements of one plane: BM PCM rows, then 64 E^T rows
     static constexpr int STAGE_BYTES = 3 * PLANE * 2;             // 36 864 B at BM = 128
@@ -2132,7 +2060,6 @@ __global__ __launch_bounds__(64 * NW, NU == 2 || NW == 8 ? NW / 2 : NW) void blo
 // spectrum columns (16 real k) go through six v_mfma_f32_32x32x16_bf16: 6 x 32 cycles instead of 8 x 64.  A lane
 // (frame m, half kh) loads (Re, Im) of columns 4 kh .. 4 kh + 3 of its frame — the same bytes per lane as the fp32
 // form — and splits them in registers; the coefficient planes come pre-split in B-operand order.
-constexpr int B3_NS = 3;   // 8-column stages in flight
 
 template <int MT, int NW>
 __global__ __launch_bounds__(64 * NW, NW / 2) void blockdft_banddots_db_bf16x3(BandArgs a) {
@@ -2248,20 +2175,6 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void blockdft_banddots_db_bf16x3(B
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-// round-to-nearest-even bf16 of a finite float (host)
-static inline uint16_t host_to_bf16(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static inline float host_from_bf16(uint16_t h) {
-    uint32_t u = (uint32_t)h << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-}
-
 // median over the sampled workgroups of the last profiled fused-GEMM launch: shader clock (MHz) held inside the K loop
 float Vqt::last_sclk_mhz() {
     if (!dev_ || !dev_->block || !dev_->block->d_clk || dev_->block->clk_n <= 0) return 0.0f;
@@ -2297,30 +2210,14 @@ bool Vqt::blockdft_takes_streams(size_t hop) const {
     return !dev_knob("PVQ_NO_FUSE", 0) && nb_max <= (size_t)CB_MAX_NB && groups.size() <= 8 && hop % (use_bf ? FB_BK : 64) == 0;
 }
 
-bool Vqt::blockdft_applicable(size_t hop) const {
-    if (!has_device() || hop < 64 || hop % 64 != 0 || hop > 4096) return false;   // the mirrored K loop walks hop / 2 in stages of 32
-    if (n_bins() > 1024) return false;
-    bool divides = (hop & (hop - 1)) == 0;
-    for (const WindowGroup& g : plan_.kernel.window_groups) divides = divides && g.window_size() % hop == 0;
-    if (divides) {   // power-of-two hop dividing every window: hop-block GEMM + doubling tree
-        for (const WindowGroup& g : plan_.kernel.window_groups)
-            if (g.window_size() / hop > (size_t)CB_MAX_NB) return false;
-        return true;
-    }
-    // general hop (a multiple of 64): whole hop blocks + the window's remainder, combined by Horner's rule over at most GEN_MAX_NQ blocks;
-    // the fused kernel only (at most 8 window groups), windows a multiple of 64 samples
-    if (plan_.kernel.window_groups.size() > 8) return false;
-    for (const WindowGroup& g : plan_.kernel.window_groups) {
-        const size_t ws = g.window_size();
-        if (ws % 64 != 0 || ws / hop > (size_t)GEN_MAX_NQ) return false;
-    }
-    return true;
-}
+bool Vqt::blockdft_applicable(size_t hop) const { return has_device() && blockdft_plan_applicable(plan_, hop); }
 
-template <typename T>
-static bool up(T** dst, const std::vector<T>& src) {
-    if (hipMalloc(reinterpret_cast<void**>(dst), sizeof(T) * std::max<size_t>(src.size(), 1)) != hipSuccess) return false;
-    if (!src.empty() && hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice) != hipSuccess) return false;
+// a host table to the device; D is the HIP type the kernels read, H the planner's plain struct of the same layout
+template <typename D, typename H>
+static bool up(D** dst, const std::vector<H>& src) {
+    static_assert(sizeof(D) == sizeof(H) && alignof(D) == alignof(H), "device and host element types differ");
+    if (hipMalloc(reinterpret_cast<void**>(dst), sizeof(H) * std::max<size_t>(src.size(), 1)) != hipSuccess) return false;
+    if (!src.empty() && hipMemcpy(*dst, src.data(), sizeof(H) * src.size(), hipMemcpyHostToDevice) != hipSuccess) return false;
     return true;
 }
 
@@ -2331,374 +2228,32 @@ pvq_status Vqt::prepare_blockdft(size_t hop) {
         free_blockdft_tables(dev_->block);
         dev_->block = nullptr;
     }
-    auto* t = new BlockDftTables();
-    t->hop = hop;
-    const auto& groups = plan_.kernel.window_groups;
-    t->n_groups = (int)groups.size();
-    const double pi = 3.14159265358979323846;
-    int tile = 0, tw_off = 0;
-    // Only the spectrum columns some kernel row actually reads are computed (e.g. 602 of 871 at
-    // 48 kHz / 7x36): col_of[g][i] is the i-th used column of group g, idx_of[g][c] its compressed index.
-    std::vector<std::vector<uint32_t>> col_of(groups.size());
-    std::vector<std::vector<int>> idx_of(groups.size());
-    for (size_t g = 0; g < groups.size(); ++g) {
-        std::vector<char> used(groups[g].filter_bank.cols + 1, 0);
-        for (uint32_t c : groups[g].filter_bank.col_idx) used[c] = 1;
-        for (uint32_t c : groups[g].negative_filter_bank.col_idx) used[c] = 1;
-        idx_of[g].assign(used.size(), -1);
-        for (uint32_t c = 0; c < used.size(); ++c)
-            if (used[c]) {
-                idx_of[g][c] = (int)col_of[g].size();
-                col_of[g].push_back(c);
-            }
-    }
-    {
-        bool divides = (hop & (hop - 1)) == 0;
-        for (const WindowGroup& g : groups) divides = divides && g.window_size() % hop == 0;
-        t->general = !divides;
-    }
-    int e16r_off = 0, gtw_off = 0;
-    for (size_t g = 0; g < groups.size(); ++g) {
-        BlockGroup B{};
-        if (t->general) {   // window = nq whole hop blocks + rem samples; no tree
-            B.nq = (int)(groups[g].window_size() / hop);
-            B.rem = (int)(groups[g].window_size() % hop);
-            B.nb = B.nb_f = 1;
-            B.levels = B.levels_f = 0;
-        } else {
-            B.nb = (int)(groups[g].window_size() / hop);
-            B.levels = 0;
-            while ((1 << B.levels) < B.nb) ++B.levels;
-            B.nb_f = std::min(B.nb, 64);
-            B.levels_f = std::min(B.levels, 6);
-        }
-        B.n_cols = (int)col_of[g].size();
-        B.tile0 = tile;
-        B.n_tiles = (B.n_cols + CB_C - 1) / CB_C;
-        B.tw_off = tw_off;
-        B.s_rel = (long long)groups[g].window_begin - (long long)plan_.params.n_fft;  // + n_lead + hop at launch
-        B.e16r_off = e16r_off;
-        B.gtw_off = gtw_off;
-        e16r_off += B.n_tiles * (B.rem / 2) * 16;
-        gtw_off += 2 * B.n_tiles * CB_C;
-        tile += B.n_tiles;
-        tw_off += B.levels * B.n_tiles * CB_C;
-        t->nb_max = std::max(t->nb_max, B.nb);
-        t->groups.push_back(B);
-    }
-    t->n_tiles = tile;
-    const int ntot = tile * GM_BN;
-    auto tq = [&](double v) { const float f = (float)v; return twiddle_fp16_ ? round_to_half(f) : f; };   // config 4: fp16 twiddles
-    // The hop DFT is taken about the centre of the hop block (see blockdft_gemm_tree): E[m][c] = e^{-i th_c u_m},
-    // u_m = m - (hop-1)/2, th_c = 2 pi c / W.  Every GEMM form therefore yields P' = P / rho_c, rho_c = e^{-i th_c (hop-1)/2},
-    // and the tree X' = X / rho_c; rho_c goes into the kernel-product coefficients below.
-    //   E [hop][Ntot], (cos, sin) interleaved per column; the mirrored fp32 form reads its first hop/2 rows
-    std::vector<float> E((size_t)hop * ntot, 0.0f);
-    std::vector<std::vector<std::pair<double, double>>> rho(groups.size());
-    std::vector<int> tile_group(tile);
-    std::vector<float2> comb_tw((size_t)std::max(tw_off, 1), make_float2(0.0f, 0.0f));
-    for (size_t g = 0; g < groups.size(); ++g) {
-        const BlockGroup& B = t->groups[g];
-        const double W = (double)groups[g].window_size();
-        const long long W2 = 2ll * (long long)groups[g].window_size();
-        for (int tt = 0; tt < B.n_tiles; ++tt) tile_group[B.tile0 + tt] = (int)g;
-        rho[g].resize(B.n_cols);
-        for (int ci = 0; ci < B.n_cols; ++ci) {
-            const long long c = (long long)col_of[g][ci];  // actual spectrum column
-            {   // the phase of the centred block DFT whose results the kernel product sees: the hop block's, or — a window shorter than a
-                // general hop, where the transform is the remainder GEMM alone — the window's
-                const long long D = t->general && B.nq == 0 ? (long long)B.rem : (long long)hop;
-                const long long prod = (c * (D - 1)) % W2;
-                const double ang = -2.0 * pi * (double)prod / (double)W2;
-                rho[g][ci] = {std::cos(ang), std::sin(ang)};
-            }
-            for (size_t m = 0; m < hop; ++m) {
-                // reduce the angle exactly: c * (2m - hop + 1) mod 2W in integers
-                long long prod = (c * (2ll * (long long)m - (long long)hop + 1ll)) % W2;
-                if (prod < 0) prod += W2;
-                const double ang = -2.0 * pi * (double)prod / (double)W2;
-                const float er = tq(std::cos(ang)), ei = tq(std::sin(ang));
-                E[m * ntot + (size_t)B.tile0 * GM_BN + 2 * ci] = er;
-                E[m * ntot + (size_t)B.tile0 * GM_BN + 2 * ci + 1] = ei;
-            }
-            for (int l = 0; l < B.levels; ++l) {
-                const long long prod = (c * (1ll << l)) % (long long)B.nb;
-                const double ang = -2.0 * pi * (double)prod / (double)B.nb;
-                comb_tw[B.tw_off + l * (B.n_tiles * CB_C) + ci] = make_float2(tq(std::cos(ang)), tq(std::sin(ang)));
-            }
-        }
-        (void)W;
-    }
-    // Banded kernel product tables: per window group, blocks of BD_RB consecutive bins; a block walks the
-    // union of its rows' (compressed) columns.  B operand of column c, lane l (n = l & 31, k = l >> 5):
-    // output n = part * 16 + row, k = 0 multiplies Re X, k = 1 multiplies Im X:
-    //     y += v X        : re += vr Xr - vi Xi,  im += vi Xr + vr Xi      (filter_bank, vqt.rs:889-895)
-    //     y += conj(w X)  : re += wr Xr - wi Xi,  im += -wi Xr - wr Xi     (negative_filter_bank, vqt.rs:896-910)
-    // with v, w the reference's coefficients times rho_c (the GEMM stages deliver X' = X / rho_c, see above).
-    const int nb = (int)n_bins();
-    t->n_bins_pad = (nb + 63) / 64 * 64;
-    std::vector<BandBlock> band;
-    std::vector<float> band_B;
-    // columns are stored in pairs: element (column c, lane l) lives at [(c / 2) * 64 + l] * 2 + (c & 1)
-    auto at = [](float* Bp, int c, int l) -> float& { return Bp[((size_t)(c >> 1) * 64 + l) * 2 + (c & 1)]; };
-    for (size_t g = 0; g < groups.size(); ++g) {
-        const CsrMatrix& A = groups[g].filter_bank;
-        const CsrMatrix& Bm = groups[g].negative_filter_bank;
-        const int xoff = t->groups[g].tile0 * CB_C;
-        for (uint32_t r0 = 0; r0 < A.rows; r0 += BD_RB) {
-            const uint32_t r1 = std::min<uint32_t>(A.rows, r0 + BD_RB);
-            int lo = 1 << 30, hi = -1;
-            for (uint32_t r = r0; r < r1; ++r) {
-                for (uint32_t q = A.row_ptr[r]; q < A.row_ptr[r + 1]; ++q) {
-                    lo = std::min(lo, idx_of[g][A.col_idx[q]]);
-                    hi = std::max(hi, idx_of[g][A.col_idx[q]]);
-                }
-                if (Bm.nnz() > 0)
-                    for (uint32_t q = Bm.row_ptr[r]; q < Bm.row_ptr[r + 1]; ++q) {
-                        lo = std::min(lo, idx_of[g][Bm.col_idx[q]]);
-                        hi = std::max(hi, idx_of[g][Bm.col_idx[q]]);
-                    }
-            }
-            BandBlock bb{};
-            bb.bin0 = (int)(groups[g].first_bin + r0);
-            bb.nrows = (int)(r1 - r0);
-            bb.boff = (int)(band_B.size() / 64);
-            if (hi < 0) {   // rows without coefficients: one all-zero stage
-                lo = 0;
-                hi = 0;
-            }
-            bb.x0 = xoff + lo;
-            bb.kb = ((hi - lo + 1) + BD_KU - 1) / BD_KU * BD_KU;
-            band_B.resize(band_B.size() + (size_t)bb.kb * 64, 0.0f);
-            float* Bp = band_B.data() + (size_t)bb.boff * 64;
-            for (uint32_t r = r0; r < r1; ++r) {
-                const int row = (int)(r - r0);
-                for (uint32_t q = A.row_ptr[r]; q < A.row_ptr[r + 1]; ++q) {
-                    const int ci = idx_of[g][A.col_idx[q]];
-                    const int cc = ci - lo;
-                    // v * rho_c, in double, rounded once
-                    const double ar_ = A.values[q].re, ai_ = A.values[q].im;
-                    const float vr = (float)(ar_ * rho[g][ci].first - ai_ * rho[g][ci].second);
-                    const float vi = (float)(ar_ * rho[g][ci].second + ai_ * rho[g][ci].first);
-                    at(Bp, cc, 0 * 32 + row) += vr;        // k = 0 (Re X) -> re
-                    at(Bp, cc, 1 * 32 + row) += -vi;       // k = 1 (Im X) -> re
-                    at(Bp, cc, 0 * 32 + 16 + row) += vi;   // k = 0 -> im
-                    at(Bp, cc, 1 * 32 + 16 + row) += vr;   // k = 1 -> im
-                }
-                if (Bm.nnz() > 0)
-                    for (uint32_t q = Bm.row_ptr[r]; q < Bm.row_ptr[r + 1]; ++q) {
-                        const int ci = idx_of[g][Bm.col_idx[q]];
-                        const int cc = ci - lo;
-                        const double br_ = Bm.values[q].re, bi_ = Bm.values[q].im;
-                        const float wr = (float)(br_ * rho[g][ci].first - bi_ * rho[g][ci].second);
-                        const float wi = (float)(br_ * rho[g][ci].second + bi_ * rho[g][ci].first);
-                        at(Bp, cc, 0 * 32 + row) += wr;
-                        at(Bp, cc, 1 * 32 + row) += -wi;
-                        at(Bp, cc, 0 * 32 + 16 + row) += -wi;
-                        at(Bp, cc, 1 * 32 + 16 + row) += -wr;
-                    }
-            }
-            band.push_back(bb);
-        }
-    }
-    // The same coefficients for the 16x16x4 MFMA form: blocks of BD8_RB = 8 bins (16 output columns = 8 x (re, im)) walk the
-    // union of 8 rows' columns — about 35 instead of 57 columns per block, so 39 % fewer matrix operations for the same
-    // products.  B operand of a column pair, lane l (n = l & 15: part = n >> 3, row = n & 7; k = l >> 4: column k >> 1 of
-    // the pair, k & 1 = 0 multiplies Re X, 1 multiplies Im X).
-    std::vector<BandBlock> band8;
-    std::vector<float> band_B8, band_B4;
-    for (size_t g = 0; g < groups.size(); ++g) {
-        const CsrMatrix& A = groups[g].filter_bank;
-        const CsrMatrix& Bm = groups[g].negative_filter_bank;
-        const int xoff = t->groups[g].tile0 * CB_C;
-        for (uint32_t r0 = 0; r0 < A.rows; r0 += BD8_RB) {
-            const uint32_t r1 = std::min<uint32_t>(A.rows, r0 + BD8_RB);
-            int lo = 1 << 30, hi = -1;
-            for (uint32_t r = r0; r < r1; ++r) {
-                for (uint32_t q = A.row_ptr[r]; q < A.row_ptr[r + 1]; ++q) {
-                    lo = std::min(lo, idx_of[g][A.col_idx[q]]);
-                    hi = std::max(hi, idx_of[g][A.col_idx[q]]);
-                }
-                if (Bm.nnz() > 0)
-                    for (uint32_t q = Bm.row_ptr[r]; q < Bm.row_ptr[r + 1]; ++q) {
-                        lo = std::min(lo, idx_of[g][Bm.col_idx[q]]);
-                        hi = std::max(hi, idx_of[g][Bm.col_idx[q]]);
-                    }
-            }
-            if (hi < 0) {
-                lo = 0;
-                hi = 0;
-            }
-            BandBlock bb{};
-            bb.bin0 = (int)(groups[g].first_bin + r0);
-            bb.nrows = (int)(r1 - r0);
-            bb.boff = (int)(band_B8.size() / 64);   // in column pairs
-            bb.x0 = xoff + lo;
-            bb.kb = ((hi - lo + 1) + BD8_KU - 1) / BD8_KU * BD8_KU;
-            band_B8.resize(band_B8.size() + (size_t)(bb.kb / 2) * 64, 0.0f);
-            float* Bp = band_B8.data() + (size_t)bb.boff * 64;
-            // element (column cc, kk = Re / Im input, part = re / im output, row)
-            // pairs are stored two by two (one 8-byte load per lane and stage): pair p, lane l at ((p >> 1) * 64 + l) * 2 + (p & 1)
-            auto at8 = [&](int cc, int kk, int part, int row) -> float& {
-                const int pr = cc >> 1, l = ((cc & 1) * 2 + kk) * 16 + part * 8 + row;
-                return Bp[((size_t)(pr >> 1) * 64 + l) * 2 + (pr & 1)];
-            };
-            for (uint32_t r = r0; r < r1; ++r) {
-                const int row = (int)(r - r0);
-                for (uint32_t q = A.row_ptr[r]; q < A.row_ptr[r + 1]; ++q) {
-                    const int ci = idx_of[g][A.col_idx[q]];
-                    const int cc = ci - lo;
-                    const double ar_ = A.values[q].re, ai_ = A.values[q].im;
-                    const float vr = (float)(ar_ * rho[g][ci].first - ai_ * rho[g][ci].second);
-                    const float vi = (float)(ar_ * rho[g][ci].second + ai_ * rho[g][ci].first);
-                    at8(cc, 0, 0, row) += vr;
-                    at8(cc, 1, 0, row) += -vi;
-                    at8(cc, 0, 1, row) += vi;
-                    at8(cc, 1, 1, row) += vr;
-                }
-                if (Bm.nnz() > 0)
-                    for (uint32_t q = Bm.row_ptr[r]; q < Bm.row_ptr[r + 1]; ++q) {
-                        const int ci = idx_of[g][Bm.col_idx[q]];
-                        const int cc = ci - lo;
-                        const double br_ = Bm.values[q].re, bi_ = Bm.values[q].im;
-                        const float wr = (float)(br_ * rho[g][ci].first - bi_ * rho[g][ci].second);
-                        const float wi = (float)(br_ * rho[g][ci].second + bi_ * rho[g][ci].first);
-                        at8(cc, 0, 0, row) += wr;
-                        at8(cc, 1, 0, row) += -wi;
-                        at8(cc, 0, 1, row) += -wi;
-                        at8(cc, 1, 1, row) += -wr;
-                    }
-            }
-            // the same block in the order of blockdft_banddots4c_db: per 4 columns (group gq) and lane (kq = column of the group, n = part * 8 + row)
-            // a float2 (coefficient of Re X, coefficient of Im X)
-            bb.boff3 = (int)(band_B4.size() / 128);   // in groups of 4 columns
-            band_B4.resize(band_B4.size() + (size_t)(bb.kb / 4) * 128, 0.0f);
-            {
-                float* B4 = band_B4.data() + (size_t)bb.boff3 * 128;
-                for (int cc = 0; cc < bb.kb; ++cc)
-                    for (int kk = 0; kk < 2; ++kk)
-                        for (int part = 0; part < 2; ++part)
-                            for (int row = 0; row < 8; ++row)
-                                B4[((size_t)(cc >> 2) * 64 + (cc & 3) * 16 + part * 8 + row) * 2 + kk] = at8(cc, kk, part, row);
-            }
-            band8.push_back(bb);
-        }
-    }
-    band_B4.resize(band_B4.size() + (size_t)8 * 128, 0.0f);   // the prefetch of the last block runs on past it
-    band_B8.resize(band_B8.size() + (size_t)8 * (BD8_KU / 2) * 64, 0.0f);   // the prefetch of the last block runs on past it
-    t->band_per_wave8 = (int)band8.size() + 2;
-    std::vector<int> band_list8((size_t)8 * t->band_per_wave8, 0);
-    {
-        std::vector<std::vector<int>> per_wave(8);
-        for (size_t i = 0; i < band8.size(); ++i) per_wave[i % 8].push_back((int)i);
-        for (int w = 0; w < 8; ++w) {
-            int* row = band_list8.data() + (size_t)w * t->band_per_wave8;
-            row[0] = (int)per_wave[w].size();
-            for (size_t i = 0; i < per_wave[w].size(); ++i) row[1 + i] = per_wave[w][i];
-        }
-    }
-    band_B.resize(band_B.size() + (size_t)BD_NS * BD_KU * 64, 0.0f);   // the prefetch of the last block runs on past it
-    // split-bf16 planes of the same coefficients, 8 columns (16 real k) per MFMA: lane (n = l & 31, kh = l >> 5)
-    // holds k = 8 kh + t, t = 0..7  <->  column 4 kh + t / 2, Re / Im row t & 1
-    std::vector<uint16_t> band_B3;
-    for (BandBlock& bb : band) {
-        bb.kg = (bb.kb + 7) / 8;
-        bb.boff3 = (int)(band_B3.size() / (3 * 64 * 8));
-        band_B3.resize(band_B3.size() + (size_t)bb.kg * 3 * 64 * 8, 0);
-        float* Bp = band_B.data() + (size_t)bb.boff * 64;
-        for (int g = 0; g < bb.kg; ++g)
-            for (int l = 0; l < 64; ++l)
-                for (int tt = 0; tt < 8; ++tt) {
-                    const int col = 8 * g + 4 * (l >> 5) + (tt >> 1);
-                    const float x = col < bb.kb ? at(Bp, col, (tt & 1) * 32 + (l & 31)) : 0.0f;
-                    const uint16_t h = host_to_bf16(x);
-                    const float r1 = x - host_from_bf16(h);
-                    const uint16_t m = host_to_bf16(r1);
-                    const uint16_t lo = host_to_bf16(r1 - host_from_bf16(m));
-                    const size_t base = ((size_t)(bb.boff3 + g) * 3) * 64 * 8 + (size_t)l * 8 + tt;
-                    band_B3[base] = h;
-                    band_B3[base + 64 * 8] = m;
-                    band_B3[base + 2 * 64 * 8] = lo;
-                }
-    }
-    band_B3.resize(band_B3.size() + (size_t)B3_NS * 3 * 64 * 8, 0);
-    // blocks to waves: round robin in bin order, so that the four waves of a workgroup walk neighbouring blocks
-    // (whose column ranges overlap) at the same time and share the X columns through L1 / L2
-    // two sets of lists: for `band_waves` waves per workgroup (fp32 form) and for 4 (split-bf16 form, whose register
-    // budget does not fit four waves per SIMD)
-    t->band_waves = 8;   // fp32 forms: 8 waves per workgroup (4 waves per SIMD when two workgroups fit a CU)
-    t->band_per_wave = (int)band.size() + 2;
-    std::vector<int> band_list((size_t)(t->band_waves + 4) * t->band_per_wave, 0);
-    auto deal = [&](int first_row, int waves) {
-        // dealt round robin in bin order: the waves of a workgroup walk neighbouring blocks (overlapping column ranges)
-        // at the same time and share the X columns through L1 / L2 (balancing by cost instead was measured no faster)
-        std::vector<std::vector<int>> per_wave(waves);
-        for (size_t i = 0; i < band.size(); ++i) per_wave[i % waves].push_back((int)i);
-        for (int w = 0; w < waves; ++w) {
-            int* row = band_list.data() + (size_t)(first_row + w) * t->band_per_wave;
-            row[0] = (int)per_wave[w].size();
-            for (size_t i = 0; i < per_wave[w].size(); ++i) row[1 + i] = per_wave[w][i];
-        }
-    };
-    deal(0, t->band_waves);
-    deal(t->band_waves, 4);
-    if (tile * CB_C >= 0x8000) {
-        free_blockdft_tables(t);
-        set_last_error("unsupported: too many spectrum columns for the block-DFT path");
+    BlockDftHostTables h;
+    std::string err;
+    if (!build_blockdft_tables(plan_, hop, twiddle_fp16_, h, &err)) {
+        set_last_error(err);
         return PVQ_ERR_UNSUPPORTED;
     }
-    std::vector<long long> tile_s(tile, 0);
-    for (size_t g = 0; g < groups.size(); ++g)
-        for (int tt = 0; tt < t->groups[g].n_tiles; ++tt) tile_s[t->groups[g].tile0 + tt] = t->groups[g].s_rel;
-    std::vector<float4> E16;
-    {   // E in the B-operand order of the 16x16x4 GEMM: [column tile][k < hop / 2][n < 16]: (cos c_n, cos c_{n+16}, -sin c_n, -sin c_{n+16})
-        const size_t K2 = hop / 2;
-        E16.resize((size_t)tile * K2 * 16);
-        for (int tt = 0; tt < tile; ++tt)
-            for (size_t m = 0; m < K2; ++m)
-                for (int n = 0; n < 16; ++n) {
-                    const float* e = E.data() + m * ntot + (size_t)tt * GM_BN;
-                    E16[((size_t)tt * K2 + m) * 16 + n] = make_float4(e[2 * n], e[2 * (n + 16)], e[2 * n + 1], e[2 * (n + 16) + 1]);
-                }
-    }
-    std::vector<float4> E16R((size_t)std::max(e16r_off, 1), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    std::vector<float2> gen_tw((size_t)std::max(gtw_off, 1), make_float2(1.0f, 0.0f));
-    if (t->general) {
-        for (size_t g = 0; g < groups.size(); ++g) {
-            const BlockGroup& B = t->groups[g];
-            const long long W = (long long)groups[g].window_size(), W2 = 2 * W;
-            auto cs = [&](long long num, long long den) {   // e^{-2 pi i num / den}, the angle reduced exactly
-                long long r = num % den;
-                if (r < 0) r += den;
-                const double ang = -2.0 * pi * (double)r / (double)den;
-                return make_float2(tq(std::cos(ang)), tq(std::sin(ang)));
-            };
-            for (int ci = 0; ci < B.n_cols; ++ci) {
-                const long long c = (long long)col_of[g][ci];
-                const int tt = ci / CB_C, n32 = ci % CB_C;
-                // E_R[m][c] = e^{-i th_c (m - (rem - 1) / 2)}, m < rem / 2 (the mirrored form reads the first half), B-operand order of E16
-                for (int m = 0; m < B.rem / 2; ++m) {
-                    const float2 e = cs(c * (2ll * m - (long long)B.rem + 1ll), W2);
-                    float4& dst = E16R[(size_t)B.e16r_off + ((size_t)tt * (B.rem / 2) + m) * 16 + (n32 & 15)];
-                    if (n32 < 16) { dst.x = e.x; dst.z = e.y; } else { dst.y = e.x; dst.w = e.y; }
-                }
-                // phi_c = e^{-2 pi i c hop / W};  tau_c = phi_c^nq rho_R / rho_Q = e^{-i th_c (nq hop + (rem - hop) / 2)}
-                gen_tw[(size_t)B.gtw_off + ci] = cs(c * (long long)hop, W);
-                gen_tw[(size_t)B.gtw_off + B.n_tiles * CB_C + ci] = B.nq > 0 ? cs(c * (2ll * B.nq * (long long)hop + (long long)B.rem - (long long)hop), W2) : make_float2(1.0f, 0.0f);
-            }
-        }
-    }
-    t->h_E = E;  // kept for the lazily built bf16 planes
-    bool ok = up(&t->d_E16R, E16R) && up(&t->d_gen_tw, gen_tw) && up(&t->d_E, E) && up(&t->d_tile_group, tile_group) && up(&t->d_tile_s, tile_s) && up(&t->d_groups, t->groups) &&
-              up(&t->d_comb_tw, comb_tw) && up(&t->d_band, band) && up(&t->d_band_B, band_B) && up(&t->d_band_list, band_list) && up(&t->d_band8, band8) &&
-              up(&t->d_band_B4, band_B4) && up(&t->d_band_list8, band_list8) &&
-              up(reinterpret_cast<uint16_t**>(&t->d_band_B3), band_B3) &&
-              up(&t->d_E16, E16);
+    auto* t = new BlockDftTables();
+    t->hop = hop;
+    t->n_groups = (int)h.groups.size();
+    t->n_tiles = h.n_tiles;
+    t->nb_max = h.nb_max;
+    t->n_bins_pad = h.n_bins_pad;
+    t->general = h.general;
+    t->band_per_wave = h.band_per_wave;
+    t->band_waves = h.band_waves;
+    t->band_per_wave8 = h.band_per_wave8;
+    const bool ok = up(&t->d_E16R, h.E16R) && up(&t->d_gen_tw, h.gen_tw) && up(&t->d_E, h.E) && up(&t->d_tile_group, h.tile_group) && up(&t->d_tile_s, h.tile_s) &&
+                    up(&t->d_groups, h.groups) && up(&t->d_comb_tw, h.comb_tw) && up(&t->d_band, h.band) && up(&t->d_band_B, h.band_B) && up(&t->d_band_list, h.band_list) &&
+                    up(&t->d_band8, h.band8) && up(&t->d_band_B4, h.band_B4) && up(&t->d_band_list8, h.band_list8) && up(&t->d_band_B3, h.band_B3) && up(&t->d_E16, h.E16);
     if (!ok) {
         free_blockdft_tables(t);
         set_last_error("hipMalloc/hipMemcpy failed while building block-DFT tables");
         return PVQ_ERR_DEVICE;
     }
+    t->groups = std::move(h.groups);
+    t->h_E = std::move(h.E);  // kept for the lazily built bf16 planes
     dev_->block = t;
     return PVQ_OK;
 }
@@ -2712,6 +2267,410 @@ pvq_status Vqt::launch_blockdft_path(const float* d_pcm, size_t n_lead, size_t h
     return launch_blockdft_streams(&one, 1, hop, d_out_db, d_out_cplx, n_frames, pk, stream);
 }
 
+// grow-only device buffer: freed and allocated anew when `bytes` exceed its capacity
+template <typename T>
+static pvq_status grow(T** ptr, size_t* cap, size_t bytes, bool* grown = nullptr) {
+    if (grown) *grown = false;
+    if (*cap >= bytes) return PVQ_OK;
+    if (*ptr) PVQ_HIP(hipFree(*ptr));
+    *ptr = nullptr;
+    *cap = 0;
+    PVQ_HIP(hipMalloc(reinterpret_cast<void**>(ptr), bytes));
+    *cap = bytes;
+    if (grown) *grown = true;
+    return PVQ_OK;
+}
+
+// What the stages of one launch share.  X is blocked by 64-frame tiles: [tile][column][64 frames], so the kernel-product workgroup
+// of a tile streams one contiguous region (and a column step is a constant 512 bytes); X_PAD_COLS zeroed columns close every tile.
+struct BlockLaunch {
+    const LaunchShape* shape;
+    const std::vector<BdRun>* runs;
+    const BdStream* streams;
+    bool use_bf;               // the split-bf16 GEMM
+    bool multi;                // several runs, or one whose rows go through the X-tile map: the launch reads the segment table
+    const float* pcm_base;     // the launch's base pointer (a launch of one run: that run's rebased stream pointer, as the single-stream entry point always did)
+    size_t nf;                 // frames the per-frame stages of the launch cover
+    size_t rows_cap;           // row capacity of the unfused stages' P
+    int ntot, xcp;             // floats per row of E; columns per frame tile of X (incl. the zeroed pad columns)
+    const XTile* d_xmap;       // set by the fused GEMM stage: the X-tile map of a multi launch (else nullptr)
+};
+
+// the X (+ Y, P) workspaces for the largest of the call's launches, and the split-bf16 GEMM's E^T planes on first use
+pvq_status Vqt::grow_blockdft_workspaces(const std::vector<LaunchShape>& shapes, size_t rows_cap, bool fused, bool use_bf, hipStream_t stream) {
+    BlockDftTables* t = dev_->block;
+    const int ntot = t->n_tiles * GM_BN, xcp = t->n_tiles * CB_C + X_PAD_COLS;
+    size_t x_tiles = 1, y_tiles = 1;
+    for (const LaunchShape& s : shapes) {
+        x_tiles = std::max(x_tiles, s.x_tiles);
+        y_tiles = std::max(y_tiles, s.y_tiles);
+    }
+    const size_t x_bytes = x_tiles * (size_t)xcp * 64 * sizeof(float2);
+    bool grown = false;
+    pvq_status s = grow(&t->d_X, &t->x_cap, x_bytes, &grown);
+    if (s != PVQ_OK) return s;
+    if (grown) PVQ_HIP(hipMemsetAsync(t->d_X, 0, x_bytes, stream));   // (the pad columns stay zero: no kernel writes them)
+    if (fused && (t->nb_max > 64 || t->general))   // (general hops: the remainder GEMM's results, laid out like X)
+        if ((s = grow(&t->d_Y, &t->y_cap, y_tiles * (size_t)xcp * 64 * sizeof(float2))) != PVQ_OK) return s;
+    if (!fused)
+        if ((s = grow(&t->d_P, &t->p_cap, rows_cap * ntot * sizeof(float))) != PVQ_OK) return s;
+    if (use_bf && fused && !t->d_Et) {
+        const std::vector<uint16_t> Et = build_Et_bf16x3(t->h_E, ntot, t->hop);
+        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_Et), Et.size() * 2));
+        PVQ_HIP(hipMemcpy(t->d_Et, Et.data(), Et.size() * 2, hipMemcpyHostToDevice));
+    }
+    return PVQ_OK;
+}
+
+// The launch's tile list of one kind, from the cache or built and uploaded with its segment table and X-tile map (one allocation:
+// list | segments | map).  The list is cached per (tile rows, kernel family, the runs' stream geometry): which tiles lie wholly
+// inside their stream — 16-byte loads, wide entries — is decided by the planner with the kernel's own test (tile_inside_stream), so a
+// list built for one geometry must never be used for another (round 3: a list keyed on the frame count alone let a launch read past
+// a shorter stream's end).  A launch of one run hands its stream pointer and output rows over in the kernel arguments: they are not
+// part of its key, so the middle sub-batches of a long stream share one list, and so do different buffers of one geometry.
+static pvq_status get_tile_list(BlockDftTables* t, const BlockLaunch& L, int kind, int bm, int wide_mode, const TileListOptions& opt,
+                                hipStream_t stream, BlockDftTables::TileList** out) {
+    const LaunchShape& sh = *L.shape;
+    std::vector<SegKey> key = sh.segs;
+    if (!L.multi) key[0].pcm_off = key[0].out_row0 = key[0].fbeg = 0;
+    for (auto& c : t->tile_lists)
+        if (c.bm == bm && c.wide == wide_mode && c.multi == L.multi && c.kind == kind && c.key == key && c.slot_data == sh.slot_data) {
+            *out = &c;
+            return PVQ_OK;
+        }
+    BlockDftTables::TileList* tl = &t->tile_lists[t->tile_list_next];
+    t->tile_list_next = (t->tile_list_next + 1) & 7;
+    const HostTileList h = build_tile_list(t->groups, sh.segs, t->hop, bm, wide_mode, kind, opt);
+    std::vector<SegDev> hsegs;
+    std::vector<XTile> hmap;
+    build_segment_map(L.streams, *L.runs, sh, hsegs, hmap);
+    const size_t b_list = h.list.size() * sizeof(int4), b_segs = (hsegs.size() * sizeof(SegDev) + 15) / 16 * 16, b_map = hmap.size() * sizeof(XTile);
+    pvq_status s = grow(&tl->d, &tl->cap, b_list + b_segs + b_map);
+    if (s != PVQ_OK) return s;
+    PVQ_HIP(hipStreamSynchronize(stream));   // an earlier launch may still read this slot
+    char* dbase = reinterpret_cast<char*>(tl->d);
+    PVQ_HIP(hipMemcpy(dbase, h.list.data(), b_list, hipMemcpyHostToDevice));
+    PVQ_HIP(hipMemcpy(dbase + b_list, hsegs.data(), hsegs.size() * sizeof(SegDev), hipMemcpyHostToDevice));
+    PVQ_HIP(hipMemcpy(dbase + b_list + b_segs, hmap.data(), b_map, hipMemcpyHostToDevice));
+    tl->d_segs = reinterpret_cast<const SegDev*>(dbase + b_list);
+    tl->d_xmap = reinterpret_cast<const XTile*>(dbase + b_list + b_segs);
+    tl->key = key;
+    tl->slot_data = sh.slot_data;
+    tl->bm = bm;
+    tl->wide = wide_mode;
+    tl->multi = L.multi;
+    tl->kind = kind;
+    tl->blocks = (int)h.list.size();
+    tl->eff_tiles = h.eff_tiles;
+    tl->eff_flop = h.eff_flop;
+    *out = tl;
+    return PVQ_OK;
+}
+
+// developer knobs PVQ_STAMPS / PVQ_STAMPS_DOTS: the phase stamps of one launch to a file, once the launch has finished
+static pvq_status dump_stamps(const char* path, unsigned long long* d_stamps, size_t n_words, hipStream_t stream) {
+    std::vector<unsigned long long> h(n_words);
+    PVQ_HIP(hipStreamSynchronize(stream));
+    PVQ_HIP(hipMemcpy(h.data(), d_stamps, h.size() * 8, hipMemcpyDeviceToHost));
+    PVQ_HIP(hipFree(d_stamps));
+    if (FILE* fp = fopen(path, "wb")) {
+        fwrite(h.data(), 8, h.size(), fp);
+        fclose(fp);
+    }
+    return PVQ_OK;
+}
+
+// GEMM + tree fused: picks the tile shape, fetches the launch's tile list(s) and runs the kernel family of the hop and arithmetic
+pvq_status Vqt::launch_blockdft_gemm_fused(BlockLaunch& L, hipStream_t stream) {
+    BlockDftTables* t = dev_->block;
+    const std::vector<SegKey>& segs = L.shape->segs;
+    const size_t hop = t->hop;
+    const bool use_bf = L.use_bf;
+    if (segs.size() > 0xFFFFu) {
+        set_last_error("too many streams in one launch");
+        return PVQ_ERR_INTERNAL;
+    }
+    // 256-row tiles: 257 - Nb complete frames per tile (1.08x row recomputation instead of 1.2x with 128 rows) — for a launch that
+    // fills the chip's 512 workgroup slots a few times over.  A smaller one (fewer than FUSED_SMALL 256-row tiles: up to ~12 000
+    // frames at 48 kHz / 252 bins) takes 128-row tiles: twice the workgroups, each half as long — what such a launch lacks is
+    // parallelism, not efficiency (hop 1 600: 4 096 frames 294 -> 216 us, 8 192: 324 -> 292; hop 256: 2 048 frames 61 -> 54;
+    // profiles/r04_small_tiles.txt).  Same bits either way (a frame's values do not depend on its tile: tests/test_tile_shapes).
+    constexpr double FUSED_SMALL = 1400.0;
+    static const int bm_env = dev_knob("PVQ_FUSED_BM", 0);          // 128: 128-row tiles (the tile-shape bit-identity test)
+    int fused_bm = 256;
+    if (!use_bf && (bm_env == 128 || (bm_env == 0 && fused_tile_count(t->groups, segs, 256, use_bf) < FUSED_SMALL))) fused_bm = 128;
+    // the tile order's knobs (blockdft_plan.hpp: build_tile_list)
+    static const TileListOptions opt = [] {
+        TileListOptions o;
+        o.fs = dev_knob("PVQ_TILE_FS", 2048);
+        o.balance = dev_knob("PVQ_BALANCE", 1);
+        o.tail = dev_knob("PVQ_TAIL", 128);
+        return o;
+    }();
+    static const int wide_env = dev_knob("PVQ_WIDE", 1);         // 0: narrow tiles only; 2: wide tiles to the very end of every queue
+#ifdef PVQ_DEV_KNOBS
+    static const int tree3_env = dev_knob("PVQ_TREE3", 0);       // 1: blockdft_gemm_tree3 (three workgroups per CU, 32-column tiles, P' in 16-column quarters)
+    const bool tree3 = tree3_env && !use_bf && fused_bm == 256 && !t->general;
+#else
+    const bool tree3 = false;
+#endif
+    const int wide_mode = !use_bf && fused_bm == 256 && !t->general && !tree3 ? wide_env : 0;   // (the split-bf16 kernel, the 128-row form and the general-hop kernel take 32-column tiles only)
+    BlockDftTables::TileList* tl = nullptr;
+    BlockDftTables::TileList* tl_r = nullptr;   // general hops: the remainder tiles
+    pvq_status ls;
+    if (t->general) {
+        if ((ls = get_tile_list(t, L, 1, fused_bm, wide_mode, opt, stream, &tl_r)) != PVQ_OK) return ls;
+        if ((ls = get_tile_list(t, L, 2, fused_bm, wide_mode, opt, stream, &tl)) != PVQ_OK) return ls;
+        // (the second lookup may have evicted the first — the slots are handed out round robin — look it up again)
+        if ((ls = get_tile_list(t, L, 1, fused_bm, wide_mode, opt, stream, &tl_r)) != PVQ_OK) return ls;
+    } else if ((ls = get_tile_list(t, L, 0, fused_bm, wide_mode, opt, stream, &tl)) != PVQ_OK)
+        return ls;
+    L.d_xmap = L.multi ? tl->d_xmap : nullptr;
+    const int n_wg = tl->blocks;   // list entries = workgroups of the non-persistent forms = rows of the stamp dump
+    GemmTreeArgs fa;
+    fa.pcm_base = L.pcm_base;
+    fa.pcm_bytes = segs[0].pcm_bytes;
+    fa.E = t->d_E;
+    fa.ld = L.ntot;
+    fa.X = t->d_X;
+    fa.Y = t->d_Y;
+    fa.xcp = L.xcp;
+    fa.n_frames = (int)segs[0].nf;
+    fa.K = (int)hop;
+    fa.base = segs[0].base;
+    fa.n_groups = t->n_groups;
+    fa.tile_list = tl->d;
+    fa.segs = L.multi ? tl->d_segs : nullptr;
+    fa.groups = t->d_groups;
+    for (int g = 0; g < 8; ++g) fa.gv[g] = t->groups[std::min(g, t->n_groups - 1)];
+    fa.comb_tw = t->d_comb_tw;
+    fa.Et = t->d_Et;
+    fa.E16 = t->d_E16;
+    fa.E16R = t->d_E16R;
+    fa.gen_tw = t->d_gen_tw;
+    fa.gen_kind = 0;
+    static const char* stamps_env = dev_knob_str("PVQ_STAMPS");   // dump per-tile phase stamps of the first launch
+    static bool stamps_done = false;
+    static int stamps_skip = dev_knob("PVQ_STAMPS_SKIP", 0);         // ... of launch n + 1 (a warm one)
+    const bool do_stamps = stamps_env && !stamps_done && stamps_skip-- <= 0;
+    fa.stamps = nullptr;
+    if (do_stamps) PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&fa.stamps), (size_t)n_wg * 12 * 8 + 8));   // rows of 8, then rows of 4 (PVQ_END_STAMPS)
+    if (do_stamps) PVQ_HIP(hipMemset(fa.stamps, 0, (size_t)n_wg * 12 * 8 + 8));
+    // flop the GEMM's matrix instructions issue in this launch: tiles x rows x 64 real columns x depth x 2
+    // (depth hop / 2 in the mirrored fp32 form, hop in the split-bf16 form, where it counts fp32-equivalent products; fp32: what the
+    // list's entries issue: a wide entry two whole tiles, a lone half tile half a tile)
+    const double eff_tiles = use_bf ? fused_tile_count(t->groups, segs, fused_bm, use_bf) : tl->eff_tiles;
+    last_gemm_flop_ = eff_tiles * fused_bm * (2 * CB_C) * (use_bf ? (double)hop : (double)hop / 2) * 2.0;
+    fa.clk = nullptr;
+    if (profiling_ && !use_bf) {
+        const size_t need = ((size_t)n_wg / 64 + 1) * 4 * sizeof(unsigned long long);
+        bool grown = false;
+        if ((ls = grow(&t->d_clk, &t->clk_cap, need, &grown)) != PVQ_OK) return ls;
+        if (grown) PVQ_HIP(hipMemset(t->d_clk, 0, need));   // once: every sampled workgroup rewrites its slot at every launch (a fill per launch cost the stream 3 us)
+        t->clk_n = n_wg / 64 + 1;
+        fa.clk = t->d_clk;
+    }
+    slot_begin(SLOT_BLOCKDFT_GEMM, stream);
+    if (t->general) {
+        // the remainder tiles first (their results wait in Y), then the whole-block tiles; flop: both launches' K loops
+        double flop = 0.0;
+        for (int kind = 1; kind <= 2; ++kind) {
+            const BlockDftTables::TileList* list = kind == 1 ? tl_r : tl;
+            if (list->blocks == 0 || list->eff_tiles == 0.0) continue;
+            GemmTreeArgs ga = fa;
+            ga.tile_list = list->d;
+            ga.segs = L.multi ? list->d_segs : nullptr;
+            ga.gen_kind = kind;
+            ga.stamps = nullptr;
+            ga.clk = nullptr;
+            if (fused_bm == 256)
+                hipLaunchKernelGGL(blockdft_gemm_gen<256>, dim3(list->blocks), dim3(512), 0, stream, ga);
+            else
+                hipLaunchKernelGGL(blockdft_gemm_gen<128>, dim3(list->blocks), dim3(256), 0, stream, ga);
+            flop += list->eff_flop;
+        }
+        last_gemm_flop_ = flop;
+    } else if (use_bf)
+        hipLaunchKernelGGL(blockdft_gemm_tree_bf16x3<256>, dim3(n_wg), dim3(512), 0, stream, fa);
+#ifdef PVQ_DEV_KNOBS
+    else if (tree3)
+        hipLaunchKernelGGL(blockdft_gemm_tree3<256>, dim3(n_wg), dim3(512), 0, stream, fa);
+#endif
+    else if (fused_bm == 256 && fa.K == 256 && dev_knob("PVQ_KFIX", 1))   // the instantiations that know the hop: 2 % fewer cycles (its strides and trip counts fold)
+        hipLaunchKernelGGL((blockdft_gemm_tree<256, 256>), dim3(n_wg), dim3(512), 0, stream, fa);
+    else if (fused_bm == 256)
+        hipLaunchKernelGGL(blockdft_gemm_tree<256>, dim3(n_wg), dim3(512), 0, stream, fa);
+    else
+        hipLaunchKernelGGL(blockdft_gemm_tree<128>, dim3(n_wg), dim3(256), 0, stream, fa);
+    slot_end(SLOT_BLOCKDFT_GEMM, stream);
+    if (do_stamps) {
+        stamps_done = true;
+        return dump_stamps(stamps_env, fa.stamps, (size_t)n_wg * 12, stream);
+    }
+    return PVQ_OK;
+}
+
+// the last one or two tree levels of the windows of more than 64 hop blocks: Y (64-block partial sums) -> X
+void Vqt::launch_blockdft_tree_finish(const BlockLaunch& L, hipStream_t stream) {
+    BlockDftTables* t = dev_->block;
+    slot_begin(SLOT_BLOCKDFT_COMBINE, stream);
+    for (int g = 0; g < t->n_groups; ++g) {
+        const BlockGroup& G = t->groups[g];
+        if (G.nb <= G.nb_f) continue;
+        FinishArgs fin;
+        fin.Y = t->d_Y;
+        fin.X = t->d_X;
+        fin.xcp = L.xcp;
+        fin.n_frames = (int)L.nf;
+        fin.col0 = G.tile0 * CB_C;
+        fin.n_cols = G.n_tiles * CB_C;
+        fin.n_real = G.n_cols;
+        fin.levels_f = G.levels_f;
+        fin.levels = G.levels;
+        fin.tw = t->d_comb_tw + G.tw_off;
+        fin.xmap = L.d_xmap;
+        hipLaunchKernelGGL(blockdft_tree_finish, dim3((unsigned)((L.nf + 63) / 64), (unsigned)((fin.n_real + 3) / 4)), dim3(256), 0,
+                           stream, fin);
+    }
+    slot_end(SLOT_BLOCKDFT_COMBINE, stream);
+}
+
+// GEMM and tree as two kernels with P in memory (more than 8 window groups, or PVQ_NO_FUSE in the developer library): one stream
+void Vqt::launch_blockdft_gemm_unfused(const BlockLaunch& L, hipStream_t stream) {
+    BlockDftTables* t = dev_->block;
+    const size_t hop = t->hop, nf = L.nf;
+    const int n_rows = (int)(nf + t->nb_max - 1);
+    GemmArgs ga;
+    ga.pcm_base = L.pcm_base;
+    ga.pcm_bytes = L.shape->segs[0].pcm_bytes;
+    ga.E = t->d_E;
+    ga.ld = L.ntot;
+    ga.P = t->d_P;
+    ga.n_rows = n_rows;
+    ga.K = (int)hop;
+    ga.tile_s = t->d_tile_s;
+    ga.base = L.shape->segs[0].base;
+    ga.n_col_tiles = t->n_tiles;
+    ga.p_rows = (int)L.rows_cap;
+    const int m_tiles8 = (((n_rows + 255) / 256) + 7) / 8 * 8;
+    last_gemm_flop_ = (double)ga.n_col_tiles * ((n_rows + 255) / 256) * 256.0 * FT_BN * ((double)hop / 2) * 2.0;
+    slot_begin(SLOT_BLOCKDFT_GEMM, stream);
+    hipLaunchKernelGGL(blockdft_gemm_rows<256>, dim3(ga.n_col_tiles * m_tiles8), dim3(512), 0, stream, ga);
+    slot_end(SLOT_BLOCKDFT_GEMM, stream);
+    CombineArgs ca;
+    ca.P = t->d_P;
+    ca.p_rows = (int)L.rows_cap;
+    ca.X = t->d_X;
+    ca.xcp = L.xcp;
+    ca.n_frames = (int)nf;
+    ca.n_rows = n_rows;
+    ca.tile_group = t->d_tile_group;
+    ca.groups = t->d_groups;
+    ca.comb_tw = t->d_comb_tw;
+    slot_begin(SLOT_BLOCKDFT_COMBINE, stream);
+    if (t->nb_max <= 64)
+        hipLaunchKernelGGL((blockdft_combine<128, 16, 64>), dim3(t->n_tiles * 2, (unsigned)((nf + 127) / 128)), dim3(256), 0,
+                           stream, ca);
+    else
+        hipLaunchKernelGGL((blockdft_combine<CB_T, 16, 256>), dim3(t->n_tiles * 2, (unsigned)((nf + CB_T - 1) / CB_T)), dim3(256),
+                           0, stream, ca);
+    slot_end(SLOT_BLOCKDFT_COMBINE, stream);
+}
+
+// kernel product + power_to_db over the launch's X tiles: the form follows the bin count and the GEMM arithmetic
+pvq_status Vqt::launch_blockdft_dots(const BlockLaunch& L, float* d_out_db, float* d_out_cplx, hipStream_t stream) {
+    BlockDftTables* t = dev_->block;
+    const int nb = (int)n_bins();
+    const size_t nf = L.nf;
+    BandArgs da;
+    da.X = reinterpret_cast<const float*>(t->d_X);
+    da.xcp = L.xcp;
+    da.n_frames = (int)nf;
+    da.n_bins = nb;
+    // 4 rows apart (the two lane halves of a C tile) land 16 banks apart; the 64-frame form has the stride compiled in
+    // more than 256 bins (32-frame tiles): the smallest stride >= n_bins that is 4 mod 16, so that up to 596 bins still fit two workgroups per CU
+    // 64-frame tiles while two 64-row tiles fit a CU: up to 256 bins (stride 260) or up to 304 (stride 308; fp32 8-bin form only)
+    const bool wide308 = !gemm_split_bf16_ && t->n_bins_pad > 256 && nb <= BAND_LDB3 - 4;
+    const bool wide = t->n_bins_pad <= 256 || wide308;
+    da.ldb = wide308 ? BAND_LDB3 : wide ? BAND_LDB2 : ((nb + 11) / 16 * 16 + 4);
+    da.blocks = t->d_band;
+    da.B = t->d_band_B;
+    da.B3 = t->d_band_B3;
+    da.list = t->d_band_list;
+    da.per_wave = t->band_per_wave;
+    // one run: its rows follow each other from its first output row; several: the X-tile map names every tile's rows
+    da.xmap = L.d_xmap;
+    const size_t row_first = L.multi ? 0 : (size_t)L.shape->segs[0].out_row0;
+    da.out_db = d_out_db + row_first * nb;
+    da.out_cplx = d_out_cplx ? reinterpret_cast<float2*>(d_out_cplx) + row_first * nb : nullptr;
+    da.status = dev_->d_status;
+    static const char* dstamps_env = dev_knob_str("PVQ_STAMPS_DOTS");   // dump per-workgroup phase stamps of the first launch
+    static bool dstamps_done = false;
+    const bool do_dstamps = dstamps_env && !dstamps_done;
+    da.stamps = nullptr;
+    const size_t n_wg = (nf + 63) / 32;   // upper bound of the grid
+    if (do_dstamps) PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&da.stamps), n_wg * 8 * 8));
+    if (do_dstamps) PVQ_HIP(hipMemset(da.stamps, 0, n_wg * 8 * 8));
+    slot_begin(SLOT_BLOCKDFT_DOTS, stream);
+    const int mt = wide ? 2 : 1;
+    static const int dots_f32_env = dev_knob("PVQ_DOTS_F32", 0);
+    const bool dots_split = gemm_split_bf16_ && !dots_f32_env;   // the kernel product follows the GEMM arithmetic
+#ifdef PVQ_DEV_KNOBS
+    static const int dots16_env = dev_knob("PVQ_DOTS_16BIN", 0);   // the 16-bin 32x32x2 form wherever it fits
+#else
+    constexpr int dots16_env = 0;
+#endif
+    const size_t lds = sizeof(float) * 32 * mt * da.ldb;
+    const dim3 grid((unsigned)((nf + 32 * mt - 1) / (32 * mt)));
+    auto use_8bin_blocks = [&] {   // 8-bin blocks, 16x16x4 MFMAs, the no-swap coefficient order
+        da.blocks = t->d_band8;
+        da.list = t->d_band_list8;
+        da.per_wave = t->band_per_wave8;
+        da.B = t->d_band_B4;
+    };
+    if (dots_split) {
+        da.list = t->d_band_list + (size_t)t->band_waves * t->band_per_wave;   // the 4-wave lists
+        if (mt == 2)
+            hipLaunchKernelGGL((blockdft_banddots_db_bf16x3<2, 4>), grid, dim3(256), lds, stream, da);
+        else
+            hipLaunchKernelGGL((blockdft_banddots_db_bf16x3<1, 4>), grid, dim3(256), lds, stream, da);
+#ifdef PVQ_DEV_KNOBS
+    } else if (mt == 2 && dots16_env && !wide308) {
+        hipLaunchKernelGGL((blockdft_banddots_db<2, 8>), grid, dim3(512), lds, stream, da);
+#endif
+    } else if (mt == 2) {
+        use_8bin_blocks();
+        if (wide308)
+            hipLaunchKernelGGL((blockdft_banddots4c_db<8, BD8_NS, BAND_LDB3, 2>), grid, dim3(512), lds, stream, da);
+        else
+            hipLaunchKernelGGL((blockdft_banddots4c_db<8, BD8_NS, BAND_LDB2, 2>), grid, dim3(512), lds, stream, da);
+    } else if (dots16_env || nb > 1024 - 4) {
+        hipLaunchKernelGGL((blockdft_banddots_db<1, 8>), grid, dim3(512), lds, stream, da);
+    } else {
+        // more than 304 bins (the reference's default 588, 360, 840): the 8-bin / 16x16x4 / no-swap form on HALF tiles (32 frames x all bins
+        // per workgroup, 8 waves), its LDS row stride compiled in per class of bin counts — round 5; before, these geometries ran the
+        // 16-bin 32x32x2 form (PVQ_DOTS_16BIN=1 in the developer library)
+        use_8bin_blocks();
+        const int ldb_c = nb <= 368 ? 372 : nb <= 592 ? 596 : nb <= 848 ? 852 : 1028;
+        da.ldb = ldb_c;
+        const size_t lds_c = sizeof(float) * 32 * ldb_c;
+        auto launch_c = [&](auto kern) -> pvq_status {
+            if (lds_c > 64 * 1024) PVQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
+            hipLaunchKernelGGL(kern, grid, dim3(512), lds_c, stream, da);
+            return PVQ_OK;
+        };
+        pvq_status lcs = ldb_c == 372 ? launch_c(blockdft_banddots4c_db<8, BD8_NS, 372, 1>) : ldb_c == 596 ? launch_c(blockdft_banddots4c_db<8, BD8_NS, 596, 1>)
+                         : ldb_c == 852 ? launch_c(blockdft_banddots4c_db<8, BD8_NS, 852, 1>) : launch_c(blockdft_banddots4c_db<8, BD8_NS, 1028, 1>);
+        if (lcs != PVQ_OK) return lcs;
+    }
+    slot_end(SLOT_BLOCKDFT_DOTS, stream);
+    if (do_dstamps) {
+        dstamps_done = true;
+        return dump_stamps(dstamps_env, da.stamps, n_wg * 8, stream);
+    }
+    return PVQ_OK;
+}
+
 // The same path over MANY streams (pvq_vqt_*_streams).  Every stream is cut into runs of at most one sub-batch; runs are packed
 // into launches up to the sub-batch size (the workspace limit), so 64 streams of 2 048 frames are ONE launch per stage where a
 // loop over single-stream calls pays 64 ramps and tails per stage; a long stream still runs sub-batch by sub-batch, alone in
@@ -2721,14 +2680,18 @@ pvq_status Vqt::launch_blockdft_streams(const StreamIn* st, size_t n_st, size_t 
     pvq_status pst = prepare_blockdft(hop);
     if (pst != PVQ_OK) return pst;
     BlockDftTables* t = dev_->block;
-    const int ntot = t->n_tiles * GM_BN, xc = t->n_tiles * CB_C;
-    // X is blocked by 64-frame tiles: [tile][column][64 frames], so the kernel-product workgroup of a tile streams one
-    // contiguous region (and a column step is a constant 512 bytes); X_PAD_COLS zeroed columns close every tile
-    const int xcp = xc + X_PAD_COLS;
+    const int ntot = t->n_tiles * GM_BN, xcp = t->n_tiles * CB_C + X_PAD_COLS;
+    // the launches' base pointer: the lowest stream pointer (segment offsets are counted from it, in samples)
+    const float* pcm_min = st[0].d_pcm;
+    for (size_t i = 1; i < n_st; ++i)
+        if (st[i].d_pcm < pcm_min) pcm_min = st[i].d_pcm;
+    std::vector<BdStream> streams(n_st);
     size_t longest = 0, total_frames = 0;
     for (size_t i = 0; i < n_st; ++i) {
-        longest = std::max(longest, st[i].n_frames);
-        total_frames += st[i].n_frames;
+        const StreamIn& S = st[i];
+        streams[i] = BdStream{(long long)(S.d_pcm - pcm_min), S.first_end, S.n_samples, S.n_frames, S.out_row0, S.row_step, S.slots, S.n_slots, S.grid_i, S.slot_hash};
+        longest = std::max(longest, S.n_frames);
+        total_frames += S.n_frames;
     }
     const size_t chunk = std::min(n_st == 1 ? longest : std::max<size_t>((total_frames + 63) / 64 * 64, 64),
                                   chunk_frames(workspace_limit_, (size_t)xcp * sizeof(float2) * (t->nb_max > 64 ? 2 : 1)));
@@ -2739,625 +2702,23 @@ pvq_status Vqt::launch_blockdft_streams(const StreamIn* st, size_t n_st, size_t 
         set_last_error("internal: the unfused block-DFT stages take one stream per call");
         return PVQ_ERR_INTERNAL;
     }
-    // runs -> launches: a launch holds runs of whole 64-frame tiles up to the sub-batch size
-    struct Run { size_t stream, fbeg, nf; };
-    std::vector<std::vector<Run>> launches;
-    {
-        const size_t budget = (chunk + 63) / 64;   // tiles per launch
-        size_t used = 0;
-        for (size_t i = 0; i < n_st; ++i) {
-            size_t fbeg = 0, left = st[i].n_frames;
-            while (left > 0) {
-                const size_t nf = std::min(left, chunk);
-                const size_t tiles = (nf + 63) / 64;
-                if (launches.empty() || used + tiles > budget || launches.back().size() >= 0xFFFFu) {   // (a tile-list entry names its run in 16 bits)
-                    launches.emplace_back();
-                    used = 0;
-                }
-                launches.back().push_back(Run{i, fbeg, nf});
-                used += tiles;
-                fbeg += nf;
-                left -= nf;
-            }
-        }
-    }
-    size_t x_tiles = 1, y_tiles = 1;
-    for (const auto& L : launches) {
-        size_t xt = 0, yt = 0;
-        for (const Run& r : L) {
-            xt += (r.nf + 63) / 64;
-            yt += (r.nf + (size_t)std::max(t->nb_max - 64, 0) + 63) / 64;
-        }
-        x_tiles = std::max(x_tiles, xt);
-        y_tiles = std::max(y_tiles, yt);
-    }
+    const std::vector<std::vector<BdRun>> launches = pack_runs(streams.data(), n_st, chunk);
+    std::vector<LaunchShape> shapes;
+    for (const auto& runs : launches) shapes.push_back(launch_shape(streams.data(), runs, hop, plan_.params.n_fft, t->nb_max));
     const size_t rows_cap = chunk + t->nb_max - 1;
-    const size_t x_bytes = x_tiles * (size_t)xcp * 64 * sizeof(float2);
-    if (t->x_cap < x_bytes) {
-        if (t->d_X) PVQ_HIP(hipFree(t->d_X));
-        t->d_X = nullptr; t->x_cap = 0;
-        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_X), x_bytes));
-        PVQ_HIP(hipMemsetAsync(t->d_X, 0, x_bytes, stream));
-        t->x_cap = x_bytes;
-    }
-    if (fused && (t->nb_max > 64 || t->general)) {   // (general hops: the remainder GEMM's results, laid out like X)
-        const size_t y_bytes = y_tiles * (size_t)xcp * 64 * sizeof(float2);
-        if (t->y_cap < y_bytes) {
-            if (t->d_Y) PVQ_HIP(hipFree(t->d_Y));
-            t->d_Y = nullptr; t->y_cap = 0;
-            PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_Y), y_bytes));
-            t->y_cap = y_bytes;
-        }
-    }
-    if (!fused) {
-        const size_t p_bytes = rows_cap * ntot * sizeof(float);
-        if (t->p_cap < p_bytes) {
-            if (t->d_P) PVQ_HIP(hipFree(t->d_P));
-            t->d_P = nullptr; t->p_cap = 0;
-            PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_P), p_bytes));
-            t->p_cap = p_bytes;
-        }
-    }
-    if (use_bf && fused && !t->d_Et) {
-        // bf16 split of E^T (round-to-nearest-even on the bit patterns), built on first use
-        std::vector<uint16_t> Et((size_t)3 * ntot * hop);
-        for (int n = 0; n < ntot; ++n)
-            for (size_t m = 0; m < hop; ++m) {
-                const float x = t->h_E[m * ntot + n];
-                const uint16_t h = host_to_bf16(x);
-                const float r1 = x - host_from_bf16(h);
-                const uint16_t mid = host_to_bf16(r1);
-                Et[((size_t)0 * ntot + n) * hop + m] = h;
-                Et[((size_t)1 * ntot + n) * hop + m] = mid;
-                Et[((size_t)2 * ntot + n) * hop + m] = host_to_bf16(r1 - host_from_bf16(mid));
-            }
-        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_Et), Et.size() * 2));
-        PVQ_HIP(hipMemcpy(t->d_Et, Et.data(), Et.size() * 2, hipMemcpyHostToDevice));
-    }
-    const int nb = (int)n_bins();
-    float2* X = t->d_X;
-    // the launch's base pointer: the lowest stream pointer (segment offsets are counted from it, in samples)
-    const float* pcm_min = st[0].d_pcm;
-    for (size_t i = 1; i < n_st; ++i)
-        if (st[i].d_pcm < pcm_min) pcm_min = st[i].d_pcm;
-    for (const auto& L : launches) {
-        // per run: rebase its stream so that every byte offset of the launch fits 32 bits
-        bool strided = false;   // a run that holds every r-th frame of its stream: its rows go through the X-tile map too
-        std::vector<BlockDftTables::SegKey> segs(L.size());
-        size_t xt_n = 0, yt_n = 0, nf_launch = 0;
-        for (size_t u = 0; u < L.size(); ++u) {
-            const Run& r = L[u];
-            const StreamIn& S = st[r.stream];
-            const long long n_samples = (long long)S.n_samples;
-            const long long first_needed = (long long)S.first_end + (long long)r.fbeg * (long long)hop - (long long)plan_.params.n_fft;
-            const long long rebase = std::max<long long>(0, std::min<long long>(first_needed, n_samples));
-            const long long extent = std::min<long long>(n_samples - rebase, (long long)(r.nf + 2) * (long long)hop + (long long)plan_.params.n_fft + 4096);
-            BlockDftTables::SegKey& k = segs[u];
-            k.pcm_off = (long long)(S.d_pcm - pcm_min) + rebase;
-            k.pcm_bytes = (unsigned)std::min<long long>(extent * 4, 0xFFFFF000ll);
-            k.base = (long long)S.first_end + (long long)r.fbeg * (long long)hop - rebase;
-            k.nf = (int)r.nf;
-            k.x_tile0 = (int)xt_n;
-            k.y_tile0 = (int)yt_n;
-            k.out_row0 = (long long)(S.out_row0 + r.fbeg * S.row_step);
-            k.row_step = (int)S.row_step;
-            k.slot_hash = S.slots ? (S.slot_hash | 1ull) : 0ull;
-            k.grid_i = (long long)S.grid_i;
-            k.fbeg = (long long)r.fbeg;
-            strided |= S.row_step != 1 || S.slots != nullptr;
-            xt_n += (r.nf + 63) / 64;
-            yt_n += (r.nf + (size_t)std::max(t->nb_max - 64, 0) + 63) / 64;
-            nf_launch += r.nf;
-        }
-        // a launch of one run goes through the kernel arguments (segs == nullptr), as the single-stream entry point always did
-        const bool multi = L.size() > 1 || strided;
-        const float* pcm_base = multi ? pcm_min : pcm_min + segs[0].pcm_off;
-        const unsigned pcm_bytes = segs[0].pcm_bytes;
-        const long long base = segs[0].base;
-        const size_t nf = multi ? xt_n * 64 : (size_t)segs[0].nf;   // frames the per-frame stages of the launch cover
-        const SegDev* d_segs = nullptr;
-        const XTile* d_xmap = nullptr;
+    if ((pst = grow_blockdft_workspaces(shapes, rows_cap, fused, use_bf, stream)) != PVQ_OK) return pst;
+    for (size_t i = 0; i < launches.size(); ++i) {
+        const LaunchShape& sh = shapes[i];
+        const bool multi = launches[i].size() > 1 || sh.strided;
+        BlockLaunch L{&sh, &launches[i], streams.data(), use_bf, multi, multi ? pcm_min : pcm_min + sh.segs[0].pcm_off,
+                      multi ? sh.x_tiles * 64 : (size_t)sh.segs[0].nf, rows_cap, ntot, xcp, nullptr};
         if (fused) {
-            GemmTreeArgs fa;
-            fa.pcm_base = pcm_base;
-            fa.pcm_bytes = pcm_bytes;
-            fa.E = t->d_E;
-            fa.ld = ntot;
-            fa.X = X;
-            fa.Y = t->d_Y;
-            fa.xcp = xcp;
-            fa.n_frames = (int)segs[0].nf;
-            fa.K = (int)hop;
-            fa.base = base;
-            fa.n_groups = t->n_groups;
-            static const int dyn_lds_env = dev_knob("PVQ_DYN_LDS", 0);      // extra LDS -> one workgroup per CU
-            static const int bm_env = dev_knob("PVQ_FUSED_BM", 0);          // 128: 128-row tiles (the tile-shape bit-identity test)
-            // matrix work of the launch in whole-tile units, for tiles of bm rows
-            auto count_tiles = [&](int bm) {
-                double n = 0.0;
-                for (const auto& k : segs)
-                    for (int g = 0; g < t->n_groups; ++g) {
-                        const int S = bm - t->groups[g].nb_f + 1;
-                        const int rows_g = k.nf + t->groups[g].nb - t->groups[g].nb_f;
-                        // a last tile of at most 16 columns runs half the MFMAs (fp32 kernel; the few tiles at the stream's ends run the full
-                        // loop: counted as half all the same)
-                        const bool half_last = !use_bf && t->groups[g].n_cols - (t->groups[g].n_tiles - 1) * CB_C <= 16;
-                        n += (t->groups[g].n_tiles - (half_last ? 0.5 : 0.0)) * ((rows_g + S - 1) / S);
-                    }
-                return n;
-            };
-            // 256-row tiles: 257 - Nb complete frames per tile (1.08x row recomputation instead of 1.2x with 128 rows) — for a launch that
-            // fills the chip's 512 workgroup slots a few times over.  A smaller one (fewer than FUSED_SMALL 256-row tiles: up to ~12 000
-            // frames at 48 kHz / 252 bins) takes 128-row tiles: twice the workgroups, each half as long — what such a launch lacks is
-            // parallelism, not efficiency (hop 1 600: 4 096 frames 294 -> 216 us, 8 192: 324 -> 292; hop 256: 2 048 frames 61 -> 54;
-            // profiles/r04_small_tiles.txt).  Same bits either way (a frame's values do not depend on its tile: tests/test_tile_shapes).
-            constexpr double FUSED_SMALL = 1400.0;
-            int fused_bm = 256;
-            if (!use_bf && (bm_env == 128 || (bm_env == 0 && count_tiles(256) < FUSED_SMALL))) fused_bm = 128;
-            double eff_tiles = count_tiles(fused_bm);
-            // Frame-stripe tile order: the launch's frames are cut into stripes of 2 048, stripe s belongs to XCD queue s & 7 (workgroup b
-            // runs on the XCD of all b' = b mod 8), and a queue takes its stripes in order, within a stripe every group's row tiles with
-            // all their column tiles.  All window groups then read a stripe's PCM rows from that XCD's L2 while they are resident (once
-            // per stripe, not once per group).  Entry: (group | wide << 8 | segment << 16, column tile, first frame, position i * 8 + queue).
-            static const int FS = dev_knob("PVQ_TILE_FS", 2048);
-            static const int balance_env = dev_knob("PVQ_BALANCE", 1);   // 0: queues as the stripes fall
-            static const int order_env = dev_knob("PVQ_ORDER", 1);       // 0: wide and narrow tiles of a stripe interleaved
-            static const int pair_half_env = dev_knob("PVQ_PAIR_HALF", 0); // 1: a group's last tile of at most 16 columns pairs up too (measured: same time, more MFMAs)
-            static const int tail_env = dev_knob("PVQ_TAIL", 128);       // narrow entries at the end of every queue
-            static const int wide_env = dev_knob("PVQ_WIDE", 1);         // 0: narrow tiles only; 2: wide tiles to the very end of every queue; 3: none in a queue's last stripe
-            static const int tree3_env = dev_knob("PVQ_TREE3", 0);       // 1: blockdft_gemm_tree3 (three workgroups per CU, 32-column tiles, P' in 16-column quarters)
-            const bool tree3 = tree3_env && !use_bf && fused_bm == 256 && !t->general;
-            const int wide_mode = !use_bf && fused_bm == 256 && !t->general && !tree3 ? wide_env : 0;   // (the split-bf16 kernel, the 128-row form and the general-hop kernel take 32-column tiles only)
-            if (segs.size() > 0xFFFFu) {
-                set_last_error("too many streams in one launch");
-                return PVQ_ERR_INTERNAL;
-            }
-            // The list is cached per (tile rows, kernel family, the runs' stream geometry): which tiles lie wholly inside their stream —
-            // 16-byte loads, wide entries — is decided here with the kernel's own test, so a list built for one geometry must never be
-            // used for another (round 3: a list keyed on the frame count alone let a launch read past a shorter stream's end)
-            // (a launch of one run hands its stream pointer and output rows over in the kernel arguments: they are not part of its key,
-            // so the middle sub-batches of a long stream share one list, and so do different buffers of one geometry)
-            std::vector<BlockDftTables::SegKey> key = segs;
-            if (!multi) key[0].pcm_off = key[0].out_row0 = key[0].fbeg = 0;
-            std::vector<size_t> slot_data;   // runs over a staged buffer: their slots by content (runs of one buffer share one slot list: taken once)
-            {
-                const Slot* seen = nullptr;
-                for (const Run& r : L) {
-                    const StreamIn& S = st[r.stream];
-                    if (!S.slots || S.slots == seen) continue;
-                    seen = S.slots;
-                    slot_data.push_back(S.n_slots);
-                    for (size_t i = 0; i < S.n_slots; ++i) {
-                        slot_data.push_back(S.slots[i].vframe0);
-                        slot_data.push_back(S.slots[i].n_frames);
-                        slot_data.push_back(S.slots[i].out_row0);
-                    }
-                }
-            }
-            // kind 0: the tiles of a power-of-two hop (GEMM + tree); 1 / 2: the remainder / whole-block tiles of a general hop
-            auto get_list = [&](int kind, BlockDftTables::TileList*& tl) -> pvq_status {
-            tl = nullptr;
-            for (auto& c : t->tile_lists)
-                if (c.bm == fused_bm && c.wide == wide_mode && c.multi == multi && c.kind == kind && c.key == key && c.slot_data == slot_data) tl = &c;
-            if (!tl) {
-                tl = &t->tile_lists[t->tile_list_next];
-                t->tile_list_next = (t->tile_list_next + 1) & 7;
-                auto grp = [](const int4& e) { return e.x & 255; };
-                auto is_wide = [](const int4& e) { return ((e.x >> 8) & 1) != 0; };
-                auto seg_of = [](const int4& e) { return (int)((unsigned)e.x >> 16); };
-                auto inside_of = [&](int g, int seg, int f0) {   // the kernel's own test
-                    const BlockGroup& G = t->groups[g];
-                    if (kind == 0) {
-                        const long long tile_lo = segs[seg].base + G.s_rel + (long long)f0 * (long long)hop, tile_hi = tile_lo + (long long)fused_bm * (long long)hop;
-                        return tile_lo >= 0 && tile_hi * 4ll <= (long long)segs[seg].pcm_bytes;
-                    }
-                    const long long depth = kind == 1 ? G.rem : (long long)hop;
-                    const long long tile_lo = segs[seg].base + G.s_rel + (long long)(f0 + (kind == 1 ? G.nq : 0)) * (long long)hop;
-                    const long long tile_hi = tile_lo + (long long)(fused_bm - 1) * (long long)hop + depth;
-                    return tile_lo >= 0 && tile_hi * 4ll <= (long long)segs[seg].pcm_bytes;
-                };
-                std::vector<std::vector<int4>> q(8);
-                for (size_t u = 0; u < segs.size(); ++u)
-                    for (int g = 0; g < t->n_groups; ++g) {
-                        const BlockGroup& G = t->groups[g];
-                        if ((kind == 1 && G.rem == 0) || (kind == 2 && G.nq == 0)) continue;
-                        const int S = kind == 0 ? fused_bm - G.nb_f + 1 : kind == 1 ? fused_bm : fused_bm - (G.nq > 1 ? G.nq - 1 : 0);
-                        const int rows_g = kind == 0 ? segs[u].nf + G.nb - G.nb_f : segs[u].nf;
-                        const bool half_last = G.n_cols - (G.n_tiles - 1) * CB_C <= 16;
-                        for (int f0 = 0; f0 < rows_g; f0 += S)
-                            for (int ntl = 0; ntl < G.n_tiles; ++ntl) {
-                                // two neighbouring column tiles as one WIDE entry (.x bit 8; fp32 kernel, 256-row tiles)
-                                // (a last tile of at most 16 columns keeps its own entry and its half-depth loop)
-                                const bool pair = wide_mode && inside_of(g, (int)u, f0) && ntl + 1 < G.n_tiles && (pair_half_env || !(half_last && ntl + 1 == G.n_tiles - 1));
-                                const int stripe = (segs[u].x_tile0 * 64 + f0) / FS;   // position in the launch's frame order
-                                q[stripe & 7].push_back(make_int4(g | (pair ? 256 : 0) | (int)((unsigned)u << 16), ntl, f0, stripe));
-                                if (pair) ++ntl;
-                            }
-                    }
-                size_t Lq = 0;
-                // what a tile costs its workgroup, roughly in us: K loop (half for a last tile of at most 16 columns) + tree levels
-                auto tile_cost = [&](const int4& e) {
-                    const BlockGroup& G = t->groups[grp(e)];
-                    const bool half = e.y == G.n_tiles - 1 && G.n_cols - e.y * CB_C <= 16;
-                    if (kind != 0) {   // a general hop's tiles: the K loop's depth decides
-                        const int depth = kind == 1 ? G.rem : (int)hop;
-                        return (inside_of(grp(e), seg_of(e), e.z) ? (half ? 1 : 2) : 4) * (depth / 32) + 8 + (kind == 2 ? G.nq : 0);
-                    }
-                    if (!inside_of(grp(e), seg_of(e), e.z)) return 2 * 16 + G.levels_f;   // the range-checked loop: dword loads
-                    return ((half ? 8 : 16) + G.levels_f) * (is_wide(e) ? 2 : 1);
-                };
-                for (auto& v : q)   // by stripe; (segment, group, row tile, column tile) order kept
-                    std::stable_sort(v.begin(), v.end(), [&](const int4& x, const int4& y) {
-                        if (x.w != y.w) return x.w < y.w;
-                        return order_env ? is_wide(x) > is_wide(y) : false;   // wide tiles of a stripe before its narrow ones (see below)
-                    });
-                // Even queues: stripes are dealt round robin, but the stream's first and last stripe carry extra tiles (the range-checked
-                // ones at the ends, which do not pair up, and the long windows' partial-sum rows past the last frame) — queue 0 ran 28 us
-                // longer than the rest of a 290 us launch.  The heaviest queue hands entries of its last stripe to the lightest until they
-                // differ by less than a tile (those read their PCM rows through another XCD's L2: a few dozen tiles per launch).
-                if (balance_env) {
-                    long long cost[8];
-                    for (int x = 0; x < 8; ++x) {
-                        cost[x] = 0;
-                        for (const int4& e : q[x]) cost[x] += tile_cost(e);
-                    }
-                    for (int it = 0; it < 4096; ++it) {
-                        int h = 0, l = 0;
-                        for (int x = 1; x < 8; ++x) {
-                            if (cost[x] > cost[h]) h = x;
-                            if (cost[x] < cost[l]) l = x;
-                        }
-                        if (q[h].empty()) break;
-                        int4 e = q[h].back();
-                        const int c = tile_cost(e);
-                        if (cost[h] - cost[l] <= c) break;
-                        q[h].pop_back();
-                        if (!q[l].empty()) e.w = q[l].back().w;   // it joins the receiving queue's last stripe
-                        q[l].push_back(e);
-                        cost[h] -= c;
-                        cost[l] += c;
-                    }
-                }
-                for (auto& v : q) {
-                    // the queue's last stripe: long tiles first, so that what is still running when the queues run dry is short
-                    if (!v.empty()) {
-                        const int last = v.back().w;
-                        auto first_of_last = std::find_if(v.begin(), v.end(), [&](const int4& e) { return e.w == last; });
-                        std::stable_sort(first_of_last, v.end(), [&](const int4& x, const int4& y) { return tile_cost(x) > tile_cost(y); });
-                        if (wide_mode == 1 || wide_mode == 3) {
-                            // ... and the queue's last entries narrow again (two per workgroup slot of the XCD; 3: the whole stripe): what is
-                            // still running when the queues run dry sets the launch's tail
-                            const size_t n_tail = wide_mode == 3 ? v.size() : (size_t)tail_env;
-                            const size_t lo = first_of_last - v.begin();
-                            std::vector<int4> tail;
-                            while (v.size() > lo && tail.size() < n_tail) {
-                                const int4 e = v.back();
-                                v.pop_back();
-                                if (is_wide(e)) {
-                                    tail.push_back(make_int4(e.x & ~256, e.y, e.z, e.w));
-                                    tail.push_back(make_int4(e.x & ~256, e.y + 1, e.z, e.w));
-                                } else
-                                    tail.push_back(e);
-                            }
-                            std::stable_sort(tail.begin(), tail.end(), [&](const int4& x, const int4& y) { return tile_cost(x) > tile_cost(y); });
-                            v.insert(v.end(), tail.begin(), tail.end());
-                        }
-                    }
-                    Lq = std::max(Lq, v.size());
-                }
-                tl->eff_tiles = 0.0;
-                tl->eff_flop = 0.0;
-                for (auto& v : q)
-                    for (const int4& e : v) {
-                        const BlockGroup& G = t->groups[grp(e)];
-                        const bool half = e.y == G.n_tiles - 1 && G.n_cols - e.y * CB_C <= 16;
-                        const double et = is_wide(e) ? 2.0 : (half ? 0.5 : 1.0);   // (the few range-checked tiles run the full loop: counted as half all the same)
-                        tl->eff_tiles += et;
-                        tl->eff_flop += et * fused_bm * (2 * CB_C) * ((kind == 1 ? (double)G.rem : (double)hop) / 2) * 2.0;   // (mirrored fp32 form: half depth)
-                    }
-                std::vector<int4> list(8 * std::max<size_t>(Lq, 1), make_int4(0, 0, 0x3FFFFFFF, 0));   // padding entries: past every group's rows
-                for (int x = 0; x < 8; ++x) {
-                    for (size_t i = 0; i < q[x].size(); ++i) {
-                        list[i * 8 + x] = q[x][i];
-                        list[i * 8 + x].w = (int)(i * 8 + x);
-                    }
-                }
-                // the segment table and the X-tile map travel with the list (one allocation: list | segments | map)
-                std::vector<SegDev> hsegs(segs.size());
-                std::vector<XTile> hmap(xt_n);
-                for (size_t u = 0; u < segs.size(); ++u) {
-                    hsegs[u] = SegDev{segs[u].pcm_off, segs[u].base, segs[u].pcm_bytes, segs[u].nf, segs[u].x_tile0, segs[u].y_tile0};
-                    const int tiles = (segs[u].nf + 63) / 64;
-                    const StreamIn& S = st[L[u].stream];
-                    for (int i = 0; i < tiles; ++i) {
-                        XTile xt{segs[u].out_row0 + 64ll * i * segs[u].row_step, std::min(64, segs[u].nf - 64 * i) | (segs[u].row_step << 8), segs[u].y_tile0 + i};
-                        if (S.slots) {   // frame t of the run = frame grid_i + row_step * t of the staged buffer: the slot it falls into names its rows
-                            const size_t rs = S.row_step, t0 = L[u].fbeg + 64 * (size_t)i, v0 = S.grid_i + rs * t0;
-                            const Slot* lo = S.slots;   // the last slot that starts at or before v0 (slots ascend; they start on multiples of 64 row_step frames)
-                            size_t n = S.n_slots;
-                            while (n > 1) {
-                                const size_t h = n / 2;
-                                if (lo[h].vframe0 <= v0) { lo += h; n -= h; } else n = h;
-                            }
-                            long long live = 0;
-                            if (S.n_slots && lo->vframe0 <= v0 && v0 < lo->vframe0 + lo->n_frames)
-                                live = std::min<long long>((long long)((lo->vframe0 + lo->n_frames - v0 + rs - 1) / rs), std::min(64, segs[u].nf - 64 * i));
-                            xt.out_row0 = S.n_slots ? (long long)(lo->out_row0 + (v0 - std::min(v0, lo->vframe0))) : 0;
-                            xt.live_step = (int)live | ((int)rs << 8);
-                        }
-                        hmap[segs[u].x_tile0 + i] = xt;
-                    }
-                }
-                const size_t b_list = list.size() * sizeof(int4), b_segs = (hsegs.size() * sizeof(SegDev) + 15) / 16 * 16, b_map = hmap.size() * sizeof(XTile);
-                if (tl->cap < b_list + b_segs + b_map) {
-                    if (tl->d) PVQ_HIP(hipFree(tl->d));
-                    tl->d = nullptr; tl->cap = 0;
-                    PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&tl->d), b_list + b_segs + b_map));
-                    tl->cap = b_list + b_segs + b_map;
-                }
-                PVQ_HIP(hipStreamSynchronize(stream));   // an earlier launch may still read this slot
-                char* dbase = reinterpret_cast<char*>(tl->d);
-                PVQ_HIP(hipMemcpy(dbase, list.data(), b_list, hipMemcpyHostToDevice));
-                PVQ_HIP(hipMemcpy(dbase + b_list, hsegs.data(), hsegs.size() * sizeof(SegDev), hipMemcpyHostToDevice));
-                PVQ_HIP(hipMemcpy(dbase + b_list + b_segs, hmap.data(), b_map, hipMemcpyHostToDevice));
-                tl->d_segs = reinterpret_cast<const SegDev*>(dbase + b_list);
-                tl->d_xmap = reinterpret_cast<const XTile*>(dbase + b_list + b_segs);
-                tl->key = key;
-                tl->slot_data = slot_data;
-                tl->bm = fused_bm;
-                tl->wide = wide_mode;
-                tl->multi = multi;
-                tl->kind = kind;
-                tl->blocks = (int)list.size();
-            }
-            return PVQ_OK;
-            };   // get_list
-            BlockDftTables::TileList* tl = nullptr;
-            BlockDftTables::TileList* tl_r = nullptr;
-            if (t->general) {
-                pvq_status ls = get_list(1, tl_r);
-                if (ls != PVQ_OK) return ls;
-                ls = get_list(2, tl);
-                if (ls != PVQ_OK) return ls;
-                // (the second lookup may have evicted the first — the slots are handed out round robin — look it up again)
-                ls = get_list(1, tl_r);
-                if (ls != PVQ_OK) return ls;
-            } else {
-                pvq_status ls = get_list(0, tl);
-                if (ls != PVQ_OK) return ls;
-            }
-            fa.tile_list = tl->d;
-            d_segs = multi ? tl->d_segs : nullptr;
-            d_xmap = multi ? tl->d_xmap : nullptr;
-            fa.segs = d_segs;
-            const int off = tl->blocks;   // list entries = workgroups of the non-persistent forms = rows of the stamp dump
-            fa.groups = t->d_groups;
-            for (int g = 0; g < 8; ++g) fa.gv[g] = t->groups[std::min(g, t->n_groups - 1)];
-            fa.comb_tw = t->d_comb_tw;
-            fa.Et = t->d_Et;
-            fa.E16 = t->d_E16;
-            static const char* stamps_env = dev_knob_str("PVQ_STAMPS");   // dump per-tile phase stamps of the first launch
-            static bool stamps_done = false;
-            static int stamps_skip = dev_knob("PVQ_STAMPS_SKIP", 0);         // ... of launch n + 1 (a warm one)
-            const bool do_stamps = stamps_env && !stamps_done && stamps_skip-- <= 0;
-            fa.stamps = nullptr;
-            if (do_stamps) PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&fa.stamps), (size_t)off * 12 * 8 + 8));   // rows of 8, then rows of 4 (PVQ_END_STAMPS)
-            if (do_stamps) PVQ_HIP(hipMemset(fa.stamps, 0, (size_t)off * 12 * 8 + 8));
-            // flop the GEMM's matrix instructions issue in this launch: tiles x rows x 64 real columns x depth x 2
-            // (depth hop / 2 in the mirrored fp32 form, hop in the split-bf16 form, where it counts fp32-equivalent products)
-            if (!use_bf) eff_tiles = tl->eff_tiles;   // (what the list's entries issue: a wide entry two whole tiles, a lone half tile half a tile)
-            last_gemm_flop_ = eff_tiles * fused_bm * (2 * CB_C) * (use_bf ? (double)hop : (double)hop / 2) * 2.0;
-            fa.E16R = t->d_E16R;
-            fa.gen_tw = t->d_gen_tw;
-            fa.gen_kind = 0;
-            fa.clk = nullptr;
-            if (profiling_ && !use_bf) {
-                const size_t need = ((size_t)off / 64 + 1) * 4 * sizeof(unsigned long long);
-                if (t->clk_cap < need) {
-                    if (t->d_clk) PVQ_HIP(hipFree(t->d_clk));
-                    t->d_clk = nullptr; t->clk_cap = 0;
-                    PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_clk), need));
-                    PVQ_HIP(hipMemset(t->d_clk, 0, need));   // once: every sampled workgroup rewrites its slot at every launch (a fill per launch cost the stream 3 us)
-                    t->clk_cap = need;
-                }
-                t->clk_n = off / 64 + 1;
-                fa.clk = t->d_clk;
-            }
-            slot_begin(SLOT_BLOCKDFT_GEMM, stream);
-            if (t->general) {
-                // the remainder tiles first (their results wait in Y), then the whole-block tiles; flop: both launches' K loops
-                double flop = 0.0;
-                for (int kind = 1; kind <= 2; ++kind) {
-                    const BlockDftTables::TileList* L = kind == 1 ? tl_r : tl;
-                    if (L->blocks == 0 || L->eff_tiles == 0.0) continue;
-                    GemmTreeArgs ga = fa;
-                    ga.tile_list = L->d;
-                    ga.segs = multi ? L->d_segs : nullptr;
-                    ga.gen_kind = kind;
-                    ga.stamps = nullptr;
-                    ga.clk = nullptr;
-                    if (fused_bm == 256)
-                        hipLaunchKernelGGL(blockdft_gemm_gen<256>, dim3(L->blocks), dim3(512), 0, stream, ga);
-                    else
-                        hipLaunchKernelGGL(blockdft_gemm_gen<128>, dim3(L->blocks), dim3(256), 0, stream, ga);
-                    flop += L->eff_flop;
-                }
-                last_gemm_flop_ = flop;
-                d_xmap = multi ? tl->d_xmap : nullptr;
-            } else if (use_bf)
-                hipLaunchKernelGGL(blockdft_gemm_tree_bf16x3<256>, dim3(off), dim3(512), 0, stream, fa);
-            else if (tree3)
-                hipLaunchKernelGGL(blockdft_gemm_tree3<256>, dim3(off), dim3(512), 0, stream, fa);
-            else if (fused_bm == 256 && fa.K == 256 && dev_knob("PVQ_KFIX", 1))   // the instantiations that know the hop: 2 % fewer cycles (its strides and trip counts fold)
-                hipLaunchKernelGGL((blockdft_gemm_tree<256, 256>), dim3(off), dim3(512), dyn_lds_env, stream, fa);
-            else if (fused_bm == 256)
-                hipLaunchKernelGGL(blockdft_gemm_tree<256>, dim3(off), dim3(512), dyn_lds_env, stream, fa);
-            else
-                hipLaunchKernelGGL(blockdft_gemm_tree<128>, dim3(off), dim3(256), 0, stream, fa);
-            slot_end(SLOT_BLOCKDFT_GEMM, stream);
-            if (do_stamps) {
-                stamps_done = true;
-                std::vector<unsigned long long> h((size_t)off * 12);
-                PVQ_HIP(hipStreamSynchronize(stream));
-                PVQ_HIP(hipMemcpy(h.data(), fa.stamps, h.size() * 8, hipMemcpyDeviceToHost));
-                PVQ_HIP(hipFree(fa.stamps));
-                if (FILE* fp = fopen(stamps_env, "wb")) {
-                    fwrite(h.data(), 8, h.size(), fp);
-                    fclose(fp);
-                }
-            }
-            if (t->nb_max > 64) {   // the last one or two tree levels of the long windows
-                slot_begin(SLOT_BLOCKDFT_COMBINE, stream);
-                for (int g = 0; g < t->n_groups; ++g) {
-                    const BlockGroup& G = t->groups[g];
-                    if (G.nb <= G.nb_f) continue;
-                    FinishArgs fin;
-                    fin.Y = t->d_Y;
-                    fin.X = X;
-                    fin.xcp = xcp;
-                    fin.n_frames = (int)nf;
-                    fin.col0 = G.tile0 * CB_C;
-                    fin.n_cols = G.n_tiles * CB_C;
-                    fin.n_real = G.n_cols;
-                    fin.levels_f = G.levels_f;
-                    fin.levels = G.levels;
-                    fin.tw = t->d_comb_tw + G.tw_off;
-                    fin.xmap = d_xmap;
-                    hipLaunchKernelGGL(blockdft_tree_finish, dim3((unsigned)((nf + 63) / 64), (unsigned)((fin.n_real + 3) / 4)), dim3(256), 0,
-                                       stream, fin);
-                }
-                slot_end(SLOT_BLOCKDFT_COMBINE, stream);
-            }
-        } else {
-            const int n_rows = (int)(nf + t->nb_max - 1);
-            GemmArgs ga;
-            ga.pcm_base = pcm_base;
-            ga.pcm_bytes = pcm_bytes;
-            ga.E = t->d_E;
-            ga.ld = ntot;
-            ga.P = t->d_P;
-            ga.n_rows = n_rows;
-            ga.K = (int)hop;
-            ga.tile_s = t->d_tile_s;
-            ga.base = base;
-            ga.n_col_tiles = t->n_tiles;
-            ga.p_rows = (int)rows_cap;
-            const int m_tiles8 = (((n_rows + 255) / 256) + 7) / 8 * 8;
-            last_gemm_flop_ = (double)ga.n_col_tiles * ((n_rows + 255) / 256) * 256.0 * FT_BN * ((double)hop / 2) * 2.0;
-            slot_begin(SLOT_BLOCKDFT_GEMM, stream);
-            hipLaunchKernelGGL(blockdft_gemm_rows<256>, dim3(ga.n_col_tiles * m_tiles8), dim3(512), 0, stream, ga);
-            slot_end(SLOT_BLOCKDFT_GEMM, stream);
-            CombineArgs ca;
-            ca.P = t->d_P;
-            ca.p_rows = (int)rows_cap;
-            ca.X = X;
-            ca.xcp = xcp;
-            ca.n_frames = (int)nf;
-            ca.n_rows = n_rows;
-            ca.tile_group = t->d_tile_group;
-            ca.groups = t->d_groups;
-            ca.comb_tw = t->d_comb_tw;
-            slot_begin(SLOT_BLOCKDFT_COMBINE, stream);
-            if (t->nb_max <= 64)
-                hipLaunchKernelGGL((blockdft_combine<128, 16, 64>), dim3(t->n_tiles * 2, (unsigned)((nf + 127) / 128)), dim3(256), 0,
-                                   stream, ca);
-            else
-                hipLaunchKernelGGL((blockdft_combine<CB_T, 16, 256>), dim3(t->n_tiles * 2, (unsigned)((nf + CB_T - 1) / CB_T)), dim3(256),
-                                   0, stream, ca);
-            slot_end(SLOT_BLOCKDFT_COMBINE, stream);
-        }
-        BandArgs da;
-        da.X = reinterpret_cast<const float*>(X);
-        da.xcp = xcp;
-        da.n_frames = (int)nf;
-        da.n_bins = nb;
-        // 4 rows apart (the two lane halves of a C tile) land 16 banks apart; the 64-frame form has the stride compiled in
-        // more than 256 bins (32-frame tiles): the smallest stride >= n_bins that is 4 mod 16, so that up to 596 bins still fit two workgroups per CU
-        // 64-frame tiles while two 64-row tiles fit a CU: up to 256 bins (stride 260) or up to 304 (stride 308; fp32 8-bin form only)
-        const bool wide308 = !gemm_split_bf16_ && t->n_bins_pad > 256 && nb <= BAND_LDB3 - 4;
-        const bool wide = t->n_bins_pad <= 256 || wide308;
-        da.ldb = wide308 ? BAND_LDB3 : wide ? BAND_LDB2 : ((nb + 11) / 16 * 16 + 4);
-        da.blocks = t->d_band;
-        da.B = t->d_band_B;
-        da.B3 = t->d_band_B3;
-        da.list = t->d_band_list;
-        da.per_wave = t->band_per_wave;
-        // one run: its rows follow each other from its first output row; several: the X-tile map names every tile's rows
-        da.xmap = d_xmap;
-        const size_t row_first = multi ? 0 : (size_t)segs[0].out_row0;
-        da.out_db = d_out_db + row_first * nb;
-        da.out_cplx = d_out_cplx ? reinterpret_cast<float2*>(d_out_cplx) + row_first * nb : nullptr;
-        da.status = dev_->d_status;
-        static const char* dstamps_env = dev_knob_str("PVQ_STAMPS_DOTS");   // dump per-workgroup phase stamps of the first launch
-        static bool dstamps_done = false;
-        const bool do_dstamps = dstamps_env && !dstamps_done;
-        da.stamps = nullptr;
-        const size_t n_wg = (nf + 63) / 32;   // upper bound of the grid
-        if (do_dstamps) PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&da.stamps), n_wg * 8 * 8));
-        if (do_dstamps) PVQ_HIP(hipMemset(da.stamps, 0, n_wg * 8 * 8));
-        slot_begin(SLOT_BLOCKDFT_DOTS, stream);
-        const int mt = wide ? 2 : 1;
-        static const int dots16_env = dev_knob("PVQ_DOTS_16BIN", 0);   // the 32x32x2 form
-        static const int dots_f32_env = dev_knob("PVQ_DOTS_F32", 0);
-        const bool dots_split = gemm_split_bf16_ && !dots_f32_env;   // the kernel product follows the GEMM arithmetic
-        const size_t lds = sizeof(float) * 32 * mt * da.ldb;
-        const dim3 grid((unsigned)((nf + 32 * mt - 1) / (32 * mt)));
-        if (mt == 2) {
-            if (dots_split) {
-                da.list = t->d_band_list + (size_t)t->band_waves * t->band_per_wave;   // the 4-wave lists
-                hipLaunchKernelGGL((blockdft_banddots_db_bf16x3<2, 4>), grid, dim3(256), lds, stream, da);
-            } else if (dots16_env && !wide308) {
-                hipLaunchKernelGGL((blockdft_banddots_db<2, 8>), grid, dim3(512), lds, stream, da);
-            } else {   // 8-bin blocks, 16x16x4 MFMAs
-                da.blocks = t->d_band8;
-                da.list = t->d_band_list8;
-                da.per_wave = t->band_per_wave8;
-                da.B = t->d_band_B4;
-                if (wide308)
-                    hipLaunchKernelGGL((blockdft_banddots4c_db<8, BD8_NS, BAND_LDB3, 2>), grid, dim3(512), lds, stream, da);
-                else
-                    hipLaunchKernelGGL((blockdft_banddots4c_db<8, BD8_NS, BAND_LDB2, 2>), grid, dim3(512), lds, stream, da);
-            }
-        } else {
-            if (dots_split) {
-                da.list = t->d_band_list + (size_t)t->band_waves * t->band_per_wave;   // the 4-wave lists
-                hipLaunchKernelGGL((blockdft_banddots_db_bf16x3<1, 4>), grid, dim3(256), lds, stream, da);
-            } else if (dots16_env || nb > 1024 - 4) {
-                hipLaunchKernelGGL((blockdft_banddots_db<1, 8>), grid, dim3(512), lds, stream, da);
-            } else {
-                // more than 304 bins (the reference's default 588, 360, 840): the 8-bin / 16x16x4 / no-swap form on HALF tiles (32 frames x all bins
-                // per workgroup, 8 waves), its LDS row stride compiled in per class of bin counts — round 5; before, these geometries ran the
-                // 16-bin 32x32x2 form (PVQ_DOTS_16BIN=1 in the developer library)
-                da.blocks = t->d_band8;
-                da.list = t->d_band_list8;
-                da.per_wave = t->band_per_wave8;
-                da.B = t->d_band_B4;
-                const int ldb_c = nb <= 368 ? 372 : nb <= 592 ? 596 : nb <= 848 ? 852 : 1028;
-                da.ldb = ldb_c;
-                const size_t lds_c = sizeof(float) * 32 * ldb_c;
-                auto launch_c = [&](auto kern) -> pvq_status {
-                    if (lds_c > 64 * 1024) PVQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
-                    hipLaunchKernelGGL(kern, grid, dim3(512), lds_c, stream, da);
-                    return PVQ_OK;
-                };
-                pvq_status lcs = ldb_c == 372 ? launch_c(blockdft_banddots4c_db<8, BD8_NS, 372, 1>) : ldb_c == 596 ? launch_c(blockdft_banddots4c_db<8, BD8_NS, 596, 1>)
-                                 : ldb_c == 852 ? launch_c(blockdft_banddots4c_db<8, BD8_NS, 852, 1>) : launch_c(blockdft_banddots4c_db<8, BD8_NS, 1028, 1>);
-                if (lcs != PVQ_OK) return lcs;
-            }
-        }
-        slot_end(SLOT_BLOCKDFT_DOTS, stream);
-        if (do_dstamps) {
-            dstamps_done = true;
-            std::vector<unsigned long long> h(n_wg * 8);
-            PVQ_HIP(hipStreamSynchronize(stream));
-            PVQ_HIP(hipMemcpy(h.data(), da.stamps, h.size() * 8, hipMemcpyDeviceToHost));
-            PVQ_HIP(hipFree(da.stamps));
-            if (FILE* fp = fopen(dstamps_env, "wb")) {
-                fwrite(h.data(), 8, h.size(), fp);
-                fclose(fp);
-            }
-        }
-        last_frames_per_launch_ = (uint32_t)nf_launch;
+            if ((pst = launch_blockdft_gemm_fused(L, stream)) != PVQ_OK) return pst;
+            if (t->nb_max > 64) launch_blockdft_tree_finish(L, stream);
+        } else
+            launch_blockdft_gemm_unfused(L, stream);
+        if ((pst = launch_blockdft_dots(L, d_out_db, d_out_cplx, stream)) != PVQ_OK) return pst;
+        last_frames_per_launch_ = (uint32_t)sh.n_frames;
     }
     if (pk) {
         slot_begin(SLOT_PEAKS, stream);

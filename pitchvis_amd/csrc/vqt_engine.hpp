@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/pvq.h"
+#include "blockdft_plan.hpp"
 #include "multi_host.hpp"
 #include "vqt_host.hpp"
 
@@ -44,6 +45,7 @@ struct AnalysisParameters {
 
 struct DeviceTables;   // opaque (device_tables.hpp)
 struct PeakParamsDev;  // peaks_device.hpp
+struct BlockLaunch;    // vqt_blockdft.hip
 
 class Vqt {
    public:
@@ -135,7 +137,7 @@ class Vqt {
     // A run may also read a STAGED buffer that holds many short streams one behind the other, each in a slot of whole 64 r-frame tiles
     // followed by a gap that is the next stream's history (Vqt::batch_streams_device): then `slots` says which output rows the
     // run's frames are — frame t of the run is frame grid_i + row_step * t of the staged buffer — and out_row0 is unused.
-    struct Slot { size_t vframe0, n_frames, out_row0; };   // frames [vframe0, vframe0 + n_frames) of the staged buffer -> rows out_row0 ...
+    using Slot = BdSlot;   // frames [vframe0, vframe0 + n_frames) of the staged buffer -> rows out_row0 ...
     struct StreamIn {
         const float* d_pcm;
         size_t first_end, n_samples, n_frames, out_row0, row_step;
@@ -148,6 +150,12 @@ class Vqt {
     pvq_status launch_blockdft_streams(const StreamIn* st, size_t n_st, size_t hop, float* d_out_db, float* d_out_cplx, size_t rows_total,
                                        const PeakParamsDev* pk, hipStream_t stream);
     pvq_status prepare_blockdft(size_t hop);
+    // the stages of one launch of the block-DFT path (vqt_blockdft.hip)
+    pvq_status grow_blockdft_workspaces(const std::vector<LaunchShape>& shapes, size_t rows_cap, bool fused, bool use_bf, hipStream_t stream);
+    pvq_status launch_blockdft_gemm_fused(BlockLaunch& L, hipStream_t stream);
+    void launch_blockdft_gemm_unfused(const BlockLaunch& L, hipStream_t stream);
+    void launch_blockdft_tree_finish(const BlockLaunch& L, hipStream_t stream);
+    pvq_status launch_blockdft_dots(const BlockLaunch& L, float* d_out_db, float* d_out_cplx, hipStream_t stream);
     pvq_status launch_blockdft_path(const float* d_pcm, size_t n_lead, size_t hop, size_t n_frames,
                                     float* d_out_db, float* d_out_cplx, const PeakParamsDev* pk, hipStream_t stream);
     pvq_status ensure_workspace(void** ptr, size_t* cap, size_t bytes);

@@ -2,7 +2,8 @@
 // AddressSanitizer is not available on this pool).  Replays, through the instrumented objects, what tests/test_host_plan.py,
 // tests/test_analysis_state.py, tests/test_consumers.py and tests/test_multi_device.py feed them: kernel construction for every test
 // geometry (including the two constructor errors and a reference panic), the AnalysisState recurrence in three smoothing modes, the
-// peak helpers on crafted frames, the AGC / dataset / LED / .npy consumers and the shard planner.
+// peak helpers on crafted frames, the AGC / dataset / LED / .npy consumers, the shard planner and the block-DFT path's planner
+// (tables, run packing, tile lists, segment tables and X-tile maps: structural invariants over every test geometry and launch shape).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "analysis_host.hpp"
+#include "blockdft_plan.hpp"
 #include "consumers_host.hpp"
 #include "multi_host.hpp"
 #include "vqt_host.hpp"
@@ -25,6 +27,192 @@ static float frand() {   // xorshift64*, [0, 1)
     return (float)((rng_state * 2685821657736338717ull) >> 40) / 16777216.0f;
 }
 #define CHECK(c) do { if (!(c)) { std::fprintf(stderr, "CHECK failed: %s (line %d)\n", #c, __LINE__); std::exit(2); } } while (0)
+
+// ---- block-DFT planner (blockdft_plan.cpp) ---------------------------------------------------------------------------------------
+// One set of streams as Vqt::batch_streams_device / run_batch hand them to the path: `r` interleaved runs per stream (hop H = r * hop).
+struct StreamSet {
+    std::vector<BdStream> st;
+    std::vector<BdSlot> slots;
+    size_t rows_total = 0, chunk = 0;
+};
+static StreamSet plain_streams(const std::vector<size_t>& n_frames, size_t r, size_t hop, size_t lead, size_t chunk) {
+    StreamSet s;
+    s.chunk = chunk;
+    size_t stride = 0;
+    for (size_t n : n_frames) stride = std::max(stride, n);
+    long long off = 0;
+    for (size_t k = 0; k < n_frames.size(); ++k) {
+        for (size_t i = 0; i < r && i < n_frames[k]; ++i)
+            s.st.push_back(BdStream{off, lead + (i + 1) * hop, lead + n_frames[k] * hop, (n_frames[k] - i + r - 1) / r, k * stride + i, r, nullptr, 0, 0, 0});
+        off += (long long)(lead + n_frames[k] * hop) + 7;
+    }
+    s.rows_total = stride * n_frames.size();
+    return s;
+}
+static StreamSet staged_streams(const std::vector<size_t>& n_frames, size_t r, size_t hop, size_t window_union) {   // vqt_engine.hip: batch_streams_device
+    StreamSet s;
+    size_t stride = 0;
+    for (size_t n : n_frames) stride = std::max(stride, n);
+    const size_t G = window_union > hop ? (window_union - hop + hop - 1) / hop : 0, A = 64 * r;
+    size_t F = (G + A - 1) / A * A;
+    for (size_t k = 0; k < n_frames.size(); ++k) {
+        s.slots.push_back(BdSlot{F, n_frames[k], k * stride});
+        F += (n_frames[k] + G + A - 1) / A * A;
+    }
+    for (size_t i = 0; i < r; ++i)
+        s.st.push_back(BdStream{0, (i + 1) * hop, F * hop, (F - i + r - 1) / r, 0, r, s.slots.data(), s.slots.size(), i, 0x1234u + i});
+    s.rows_total = stride * n_frames.size();
+    s.chunk = (F + 63) / 64 * 64;
+    return s;
+}
+
+static void check_tables(const BlockDftHostTables& t, size_t hop, uint32_t n_bins) {
+    const size_t xcp = (size_t)t.n_tiles * CB_C + X_PAD_COLS, ntot = (size_t)t.n_tiles * GM_BN;
+    CHECK(t.E.size() == hop * ntot && t.E16.size() == (size_t)t.n_tiles * (hop / 2) * 16);
+    CHECK(t.tile_group.size() == (size_t)t.n_tiles && t.tile_s.size() == (size_t)t.n_tiles);
+    int tiles = 0;
+    for (const BlockGroup& G : t.groups) {
+        CHECK(G.tile0 == tiles && G.n_tiles * CB_C >= G.n_cols && G.nb <= t.nb_max && G.nb_f <= 64 && (1 << G.levels_f) == G.nb_f);
+        tiles += G.n_tiles;
+        CHECK((size_t)G.tw_off + (size_t)G.levels * G.n_tiles * CB_C <= t.comb_tw.size());
+        CHECK((size_t)G.e16r_off + (size_t)G.n_tiles * (G.rem / 2) * 16 <= t.E16R.size());
+        CHECK((size_t)G.gtw_off + 2 * (size_t)G.n_tiles * CB_C <= t.gen_tw.size());
+        if (t.general) CHECK((size_t)G.nq * hop + G.rem > 0 && G.nq <= GEN_MAX_NQ && G.nb == 1); else CHECK(G.nq == 0 && G.rem == 0 && (1 << G.levels) == G.nb);
+    }
+    CHECK(tiles == t.n_tiles);
+    for (int g : t.tile_group) CHECK(g >= 0 && (size_t)g < t.groups.size());
+    // kernel-product blocks: every bin once, in order; the columns a block walks (with the operand ring's prefetch past its range: the
+    // stages in flight x columns per stage) lie inside a frame tile of X incl. its zeroed pad columns, its coefficients inside their arrays
+    auto check_blocks = [&](const std::vector<BandBlock>& band, int rb, int ku, int ns) {
+        int bin = 0;
+        for (const BandBlock& b : band) {
+            CHECK(b.bin0 == bin && b.nrows >= 1 && b.nrows <= rb && b.kb > 0 && b.kb % ku == 0 && b.x0 >= 0);
+            bin += b.nrows;
+            CHECK((size_t)b.x0 + b.kb + (size_t)ns * ku <= xcp);
+        }
+        CHECK(bin == (int)n_bins);
+    };
+    check_blocks(t.band, BD_RB, BD_KU, BD_NS);
+    check_blocks(t.band8, BD8_RB, BD8_KU, BD8_NS);
+    for (const BandBlock& b : t.band) {
+        CHECK(((size_t)b.boff + b.kb + BD_NS * BD_KU) * 64 <= t.band_B.size());
+        CHECK(b.kg * 8 >= b.kb && ((size_t)b.boff3 + b.kg + B3_NS) * 3 * 64 * 8 <= t.band_B3.size() && (size_t)b.x0 + 8 * (size_t)(b.kg + B3_NS) <= xcp);
+    }
+    for (const BandBlock& b : t.band8) CHECK(((size_t)b.boff3 + b.kb / 4 + 8) * 128 <= t.band_B4.size() && b.boff == 2 * b.boff3);
+    // block lists: per set of waves, every block in exactly one wave's row
+    auto check_lists = [&](const int* rows, int waves, int per_wave, size_t n_blocks) {
+        std::vector<int> seen(n_blocks, 0);
+        for (int w = 0; w < waves; ++w) {
+            const int* row = rows + (size_t)w * per_wave;
+            CHECK(row[0] >= 0 && row[0] < per_wave);
+            for (int i = 0; i < row[0]; ++i) {
+                CHECK(row[1 + i] >= 0 && (size_t)row[1 + i] < n_blocks);
+                ++seen[row[1 + i]];
+            }
+        }
+        for (int c : seen) CHECK(c == 1);
+    };
+    CHECK(t.band_list.size() == (size_t)(t.band_waves + 4) * t.band_per_wave && t.band_list8.size() == (size_t)8 * t.band_per_wave8);
+    check_lists(t.band_list.data(), t.band_waves, t.band_per_wave, t.band.size());
+    check_lists(t.band_list.data() + (size_t)t.band_waves * t.band_per_wave, 4, t.band_per_wave, t.band.size());
+    check_lists(t.band_list8.data(), 8, t.band_per_wave8, t.band8.size());
+}
+
+// every (segment, group, row tile, column tile) the launch needs exactly once, wide entries only where the kernel may take them
+static void check_tile_list(const BlockDftHostTables& t, const LaunchShape& sh, size_t hop, int bm, int wide_mode, int kind, const HostTileList& tl) {
+    CHECK(!tl.list.empty() && tl.list.size() % 8 == 0);
+    std::vector<std::vector<std::vector<int>>> seen(sh.segs.size(), std::vector<std::vector<int>>(t.groups.size()));
+    auto stride_of = [&](const BlockGroup& G) { return kind == 0 ? bm - G.nb_f + 1 : kind == 1 ? bm : bm - (G.nq > 1 ? G.nq - 1 : 0); };
+    auto skipped = [&](const BlockGroup& G) { return (kind == 1 && G.rem == 0) || (kind == 2 && G.nq == 0); };
+    for (size_t u = 0; u < sh.segs.size(); ++u)
+        for (size_t g = 0; g < t.groups.size(); ++g) {
+            const BlockGroup& G = t.groups[g];
+            const int rows = kind == 0 ? sh.segs[u].nf + G.nb - G.nb_f : sh.segs[u].nf, S = stride_of(G);
+            CHECK(S > 0);
+            seen[u][g].assign(skipped(G) ? 0 : (size_t)((rows + S - 1) / S) * G.n_tiles, 0);
+        }
+    double eff = 0.0;
+    for (size_t i = 0; i < tl.list.size(); ++i) {
+        const Int4& e = tl.list[i];
+        if (e.z == 0x3FFFFFFF) {   // padding: past every group's rows
+            CHECK(e.x == 0 && e.y == 0);
+            continue;
+        }
+        CHECK(e.w == (int)i);
+        const size_t u = (unsigned)e.x >> 16, g = e.x & 255;
+        const bool wide = (e.x >> 8) & 1;
+        CHECK(u < sh.segs.size() && g < t.groups.size() && (e.x & 0xFE00) == 0);
+        const BlockGroup& G = t.groups[g];
+        const int S = stride_of(G);
+        CHECK(e.z >= 0 && e.z % S == 0 && e.y >= 0 && e.y + (wide ? 1 : 0) < G.n_tiles);
+        const size_t slot = (size_t)(e.z / S) * G.n_tiles + e.y;
+        CHECK(slot + (wide ? 1 : 0) < seen[u][g].size());
+        ++seen[u][g][slot];
+        if (wide) {
+            ++seen[u][g][slot + 1];
+            const bool half_last = G.n_cols - (G.n_tiles - 1) * CB_C <= 16;
+            CHECK(wide_mode != 0 && tile_inside_stream(G, sh.segs[u], e.z, hop, bm, kind) && !(half_last && e.y + 1 == G.n_tiles - 1));
+        }
+        eff += wide ? 2.0 : (e.y == G.n_tiles - 1 && G.n_cols - e.y * CB_C <= 16) ? 0.5 : 1.0;
+    }
+    for (const auto& per_seg : seen)
+        for (const auto& per_group : per_seg)
+            for (int c : per_group) CHECK(c == 1);
+    CHECK(eff == tl.eff_tiles && tl.eff_flop >= 0.0);
+}
+
+static void check_blockdft_plan(const HostPlan& plan) {
+    const struct { size_t hop, r; } hops[] = {{64, 1}, {256, 1}, {1024, 1}, {800, 2}, {1600, 1}};
+    const uint32_t n_bins = plan.params.range.n_buckets();
+    for (const auto& hr : hops) {
+        const size_t H = hr.hop * hr.r, r = hr.r;
+        if (!blockdft_plan_applicable(plan, H)) continue;
+        BlockDftHostTables t;
+        std::string err;
+        CHECK(build_blockdft_tables(plan, H, hr.hop == 256 && n_bins == 252, t, &err));
+        check_tables(t, H, n_bins);
+        if (!t.general && H % FB_BK == 0 && H <= 256) CHECK(build_Et_bf16x3(t.E, t.n_tiles * GM_BN, H).size() == 3 * t.E.size());
+        std::vector<size_t> shorts(64);
+        for (size_t k = 0; k < shorts.size(); ++k) shorts[k] = 1 + (k * 37) % 300 + (k % 7 == 0 ? 700 : 0);
+        // one long stream in sub-batches (first / middle / last), 64 short unequal streams side by side, the same streams staged into one
+        // buffer with slots; r = 2: every stream as two interleaved (strided) runs
+        const StreamSet sets[] = {plain_streams({20011}, r, hr.hop, plan.window_union, 8192), plain_streams(shorts, r, hr.hop, plan.window_union, 1 << 17),
+                                  staged_streams(shorts, r, hr.hop, plan.window_union)};
+        for (const StreamSet& set : sets) {
+            const auto launches = pack_runs(set.st.data(), set.st.size(), set.chunk);
+            size_t frames = 0;
+            for (const auto& runs : launches) {
+                CHECK(!runs.empty() && runs.size() <= 0xFFFFu);
+                const LaunchShape sh = launch_shape(set.st.data(), runs, H, plan.params.n_fft, t.nb_max);
+                CHECK(sh.segs.size() == runs.size() && sh.x_tiles * 64 <= (set.chunk + 63) / 64 * 64 && sh.strided == (r != 1 || set.st[0].slots != nullptr));
+                frames += sh.n_frames;
+                std::vector<SegDev> segs;
+                std::vector<XTile> xmap;
+                build_segment_map(set.st.data(), runs, sh, segs, xmap);
+                CHECK(segs.size() == runs.size() && xmap.size() == sh.x_tiles);
+                for (const SegDev& s : segs)
+                    CHECK(s.n_frames > 0 && s.x_tile0 >= 0 && (size_t)s.x_tile0 + (s.n_frames + 63) / 64 <= sh.x_tiles && s.y_tile0 >= 0 && (size_t)s.y_tile0 < sh.y_tiles && s.pcm_off >= 0);
+                for (const XTile& x : xmap) {   // the rows a tile's live frames go to lie inside the output
+                    const int live = x.live_step & 255, step = x.live_step >> 8;
+                    CHECK(live <= 64 && step == (int)r && x.y_tile >= 0 && (size_t)x.y_tile < sh.y_tiles);
+                    if (live > 0) CHECK(x.out_row0 >= 0 && (size_t)x.out_row0 + (size_t)(live - 1) * step < set.rows_total);
+                }
+                for (int bm : {128, 256})
+                    for (int wide : {0, 1, 2})
+                        for (int kind = t.general ? 1 : 0; kind <= (t.general ? 2 : 0); ++kind)
+                            for (int balance = 0; balance < 2; ++balance) {
+                                TileListOptions opt;
+                                opt.balance = balance;
+                                check_tile_list(t, sh, H, bm, wide, kind, build_tile_list(t.groups, sh.segs, H, bm, wide, kind, opt));
+                            }
+                (void)fused_tile_count(t.groups, sh.segs, 256, false);
+            }
+            size_t want = 0;
+            for (const BdStream& s : set.st) want += s.n_frames;
+            CHECK(frames == want);
+        }
+    }
+}
 
 int main() {
     // ---- kernel construction: the six test geometries ----------------------------------------------------------------------
@@ -50,6 +238,7 @@ int main() {
         std::vector<float> lnf;
         bin_log_frequencies(p, lnf);
         CHECK(lnf.size() == rows);
+        check_blockdft_plan(plan);
     }
     CHECK(neg_default == 379);                       // VQT_REVIEW.md:369
     CHECK(nnz_default > 15000 && nnz_default < 20000);

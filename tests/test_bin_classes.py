@@ -147,7 +147,7 @@ def _ints(m):
 
 
 def test_kernel_product_thresholds_match_the_restatement():
-    s = _src("vqt_blockdft.hip")
+    s = _src("vqt_blockdft.hip") + _src("blockdft_plan.cpp") + _src("blockdft_plan.hpp")   # (the launches; the path's host planning)
     ldb2 = int(re.search(r"constexpr int BAND_LDB2 = (\d+);", s).group(1))
     ldb3 = int(re.search(r"constexpr int BAND_LDB3 = (\d+);", s).group(1))
     assert (ldb2, ldb3) == (260, 308)
@@ -156,7 +156,7 @@ def test_kernel_product_thresholds_match_the_restatement():
     assert m and (int(m.group(1)), ldb3 - int(m.group(2))) == (256, 304)
     m = re.search(r"const bool wide = t->n_bins_pad <= (\d+) \|\| wide308;", s)
     assert m and int(m.group(1)) == 256
-    assert re.search(r"t->n_bins_pad = \(nb \+ 63\) / 64 \* 64;", s)
+    assert re.search(r"t\.n_bins_pad = \(nb \+ 63\) / 64 \* 64;", s)
     m = re.search(r"const int ldb_c = nb <= (\d+) \? (\d+) : nb <= (\d+) \? (\d+) : nb <= (\d+) \? (\d+) : (\d+);", s)
     assert m, "the kernel product's LDS stride classes moved"
     v = _ints(m)
@@ -170,9 +170,10 @@ def test_kernel_product_thresholds_match_the_restatement():
     for (hi, c) in KP_FP32[:-1]:
         assert int(c[3:]) >= hi + 4, c
     assert re.search(r"hipLaunchKernelGGL\(\(blockdft_banddots_db_bf16x3<2, 4>\)", s) and re.search(r"hipLaunchKernelGGL\(\(blockdft_banddots_db_bf16x3<1, 4>\)", s)
-    m = re.search(r"if \(n_bins\(\) > (\d+)\) return false;", s)
+    m = re.search(r"if \(plan\.params\.range\.n_buckets\(\) > (\d+)\) return false;", s)
     assert m and int(m.group(1)) == BLOCKDFT_MAX_BINS
-    m = re.search(r"if \(!has_device\(\) \|\| hop < (\d+) \|\| hop % (\d+) != 0 \|\| hop > (\d+)\) return false;", s)
+    assert "bool Vqt::blockdft_applicable(size_t hop) const { return has_device() && blockdft_plan_applicable(plan_, hop); }" in s
+    m = re.search(r"if \(hop < (\d+) \|\| hop % (\d+) != 0 \|\| hop > (\d+)\) return false;", s)
     assert m and _ints(m) == (HOP_MIN, 64, HOP_MAX)
     m = re.search(r"constexpr int CB_MAX_NB = (\d+);", s)
     assert m and int(m.group(1)) == CB_MAX_NB

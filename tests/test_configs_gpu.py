@@ -344,7 +344,7 @@ def test_tile_shapes_bit_identical_in_subprocesses():
     res = {}
     for tag, env in (("base", {}), ("dev", {"PVQ_DEV_LIB": "1"}), ("bm128", {"PVQ_DEV_LIB": "1", "PVQ_FUSED_BM": "128"}), ("bm256", {"PVQ_DEV_LIB": "1", "PVQ_FUSED_BM": "256"}),
                      ("narrow", {"PVQ_DEV_LIB": "1", "PVQ_WIDE": "0", "PVQ_BALANCE": "0"}), ("wide_all", {"PVQ_DEV_LIB": "1", "PVQ_WIDE": "2"}),
-                     ("tree3", {"PVQ_DEV_LIB": "1", "PVQ_FUSED_BM": "256", "PVQ_TREE3": "1"})):   # three workgroups per CU, P' in 16-column quarters (blockdft_gemm_tree3: measured, not adopted)   # three workgroups per CU, P' in 16-column quarters (blockdft_gemm_tree3)
+                     ("tree3", {"PVQ_DEV_LIB": "1", "PVQ_FUSED_BM": "256", "PVQ_TREE3": "1"})):   # three workgroups per CU, P' in 16-column quarters (blockdft_gemm_tree3: measured, not adopted)
         f = os.path.join(root, "gpurun_out", f"forms_{tag}.npz")
         r = subprocess.run([sys.executable, "-c", code, f], env=dict(os.environ, **env), capture_output=True, text=True, timeout=300, cwd=root)
         assert r.returncode == 0 and "FORM_OK" in r.stdout, tag + r.stdout[-2000:] + r.stderr[-2000:]
@@ -360,7 +360,7 @@ def test_fft_batch_kernels_equal_the_walk_in_subprocesses():
     developer library keeps for batches too with PVQ_FFT_CT=0): the same bits on every test geometry, at a power-of-two hop and at an odd one
     (735 = pitchvis_serial's cadence at 22 050 Hz), stream start included.  Both forms share every arithmetic helper and vqt_engine.hip
     compiles with FMA contraction off (fused multiply-adds are written where wanted), so this holds by construction; the test keeps it so.
-    (tests/test_parity_gpu.py::test_few_frames_on_the_fft_path_equal_the_same_frames_of_a_batch compares the few-frames forms of the walk with
+    (tests/test_handles_gpu.py::test_few_frames_on_the_fft_path_equal_the_same_frames_of_a_batch compares the few-frames forms of the walk with
     the batch form in one process.)"""
     import os, subprocess, sys, textwrap
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -53,6 +53,24 @@ def test_register_budgets_of_the_block_dft_kernels(tmp_path):
             inside = None
         elif inside:
             body[inside].append(line)
+    # The product build holds exactly the kernels its dispatch can reach (vqt_blockdft.hip: launch_blockdft_gemm_fused / _gemm_unfused /
+    # _tree_finish / _dots): the forms that only a developer knob selects — blockdft_gemm_tree3, the 16-bin kernel product on 64-frame
+    # tiles (blockdft_banddots_db<MT = 2, NW = 8>) — compile under -DPVQ_DEV_KNOBS alone.
+    reachable = {
+        "_ZN3pvq18blockdft_gemm_treeILi256ELi256EEEvNS_12GemmTreeArgsE", "_ZN3pvq18blockdft_gemm_treeILi256ELi0EEEvNS_12GemmTreeArgsE",
+        "_ZN3pvq18blockdft_gemm_treeILi128ELi0EEEvNS_12GemmTreeArgsE", "_ZN3pvq25blockdft_gemm_tree_bf16x3ILi256EEEvNS_12GemmTreeArgsE",
+        "_ZN3pvq17blockdft_gemm_genILi256EEEvNS_12GemmTreeArgsE", "_ZN3pvq17blockdft_gemm_genILi128EEEvNS_12GemmTreeArgsE",
+        "_ZN3pvq20blockdft_tree_finishENS_10FinishArgsE",
+        "_ZN3pvq18blockdft_gemm_rowsILi256EEEvNS_8GemmArgsE",
+        "_ZN3pvq16blockdft_combineILi128ELi16ELi64EEEvNS_11CombineArgsE", "_ZN3pvq16blockdft_combineILi128ELi16ELi256EEEvNS_11CombineArgsE",
+        "_ZN3pvq22blockdft_banddots4c_dbILi8ELi4ELi260ELi2EEEvNS_8BandArgsE", "_ZN3pvq22blockdft_banddots4c_dbILi8ELi4ELi308ELi2EEEvNS_8BandArgsE",
+        "_ZN3pvq22blockdft_banddots4c_dbILi8ELi4ELi372ELi1EEEvNS_8BandArgsE", "_ZN3pvq22blockdft_banddots4c_dbILi8ELi4ELi596ELi1EEEvNS_8BandArgsE",
+        "_ZN3pvq22blockdft_banddots4c_dbILi8ELi4ELi852ELi1EEEvNS_8BandArgsE", "_ZN3pvq22blockdft_banddots4c_dbILi8ELi4ELi1028ELi1EEEvNS_8BandArgsE",
+        "_ZN3pvq20blockdft_banddots_dbILi1ELi8EEEvNS_8BandArgsE",   # above 1 020 bins
+        "_ZN3pvq27blockdft_banddots_db_bf16x3ILi2ELi4EEEvNS_8BandArgsE", "_ZN3pvq27blockdft_banddots_db_bf16x3ILi1ELi4EEEvNS_8BandArgsE",
+    }
+    assert set(body) == reachable, (sorted(set(body) - reachable), sorted(reachable - set(body)))
+    assert not any("tree3" in k or "blockdft_banddots_dbILi2ELi8E" in k for k in body)
     checked = 0
     for name, lines in body.items():
         if "blockdft_gemm_treeILi" not in name and "blockdft_gemm_tree_bf16x3" not in name:   # the shipped kernels (not the opt-in experiments)
