@@ -127,7 +127,7 @@ std::vector<uint16_t> build_Et_bf16x3(const std::vector<float>& E, int ntot, siz
 
 // ---- streams -> runs -> launches -------------------------------------------------------------------------------------------------
 struct BdSlot { size_t vframe0, n_frames, out_row0; };   // frames [vframe0, vframe0 + n_frames) of a staged buffer -> rows out_row0 ...
-// One run of frames as the planner sees it (Vqt::StreamIn with the stream pointer as a sample offset from the launch's base pointer)
+// One run of frames as the planner sees it (StreamRun, batch_plan.hpp, with the stream pointer as a sample offset from the launch's base pointer)
 struct BdStream {
     long long pcm_off;
     size_t first_end, n_samples, n_frames, out_row0, row_step;

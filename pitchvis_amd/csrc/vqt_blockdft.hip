@@ -2263,7 +2263,7 @@ pvq_status Vqt::prepare_blockdft(size_t hop) {
 // the streams contend for the same CUs.)
 pvq_status Vqt::launch_blockdft_path(const float* d_pcm, size_t n_lead, size_t hop, size_t n_frames, float* d_out_db,
                                      float* d_out_cplx, const PeakParamsDev* pk, hipStream_t stream) {
-    const StreamIn one{d_pcm, n_lead + hop, n_lead + n_frames * hop, n_frames, 0, 1};
+    const StreamRun one{d_pcm, n_lead + hop, n_lead + n_frames * hop, n_frames, 0, 1};
     return launch_blockdft_streams(&one, 1, hop, d_out_db, d_out_cplx, n_frames, pk, stream);
 }
 
@@ -2675,21 +2675,17 @@ pvq_status Vqt::launch_blockdft_dots(const BlockLaunch& L, float* d_out_db, floa
 // into launches up to the sub-batch size (the workspace limit), so 64 streams of 2 048 frames are ONE launch per stage where a
 // loop over single-stream calls pays 64 ramps and tails per stage; a long stream still runs sub-batch by sub-batch, alone in
 // its launches, exactly as through the single-stream entry point.  Stream s writes its rows to out rows st[s].out_row0 ...
-pvq_status Vqt::launch_blockdft_streams(const StreamIn* st, size_t n_st, size_t hop, float* d_out_db, float* d_out_cplx, size_t rows_total,
+pvq_status Vqt::launch_blockdft_streams(const StreamRun* st, size_t n_st, size_t hop, float* d_out_db, float* d_out_cplx, size_t rows_total,
                                         const PeakParamsDev* pk, hipStream_t stream) {
     pvq_status pst = prepare_blockdft(hop);
     if (pst != PVQ_OK) return pst;
     BlockDftTables* t = dev_->block;
     const int ntot = t->n_tiles * GM_BN, xcp = t->n_tiles * CB_C + X_PAD_COLS;
     // the launches' base pointer: the lowest stream pointer (segment offsets are counted from it, in samples)
-    const float* pcm_min = st[0].d_pcm;
-    for (size_t i = 1; i < n_st; ++i)
-        if (st[i].d_pcm < pcm_min) pcm_min = st[i].d_pcm;
-    std::vector<BdStream> streams(n_st);
+    const float* pcm_min = nullptr;
+    const std::vector<BdStream> streams = rebase_runs(st, n_st, &pcm_min);
     size_t longest = 0, total_frames = 0;
-    for (size_t i = 0; i < n_st; ++i) {
-        const StreamIn& S = st[i];
-        streams[i] = BdStream{(long long)(S.d_pcm - pcm_min), S.first_end, S.n_samples, S.n_frames, S.out_row0, S.row_step, S.slots, S.n_slots, S.grid_i, S.slot_hash};
+    for (const BdStream& S : streams) {
         longest = std::max(longest, S.n_frames);
         total_frames += S.n_frames;
     }
@@ -2721,9 +2717,7 @@ pvq_status Vqt::launch_blockdft_streams(const StreamIn* st, size_t n_st, size_t 
         last_frames_per_launch_ = (uint32_t)sh.n_frames;
     }
     if (pk) {
-        slot_begin(SLOT_PEAKS, stream);
-        pvq_status ps = launch_peaks_kernel(d_out_db, rows_total, *pk, stream);
-        slot_end(SLOT_PEAKS, stream);
+        pvq_status ps = peaks_stage(d_out_db, rows_total, *pk, stream);
         if (ps != PVQ_OK) return ps;
     }
     PVQ_HIP(hipGetLastError());

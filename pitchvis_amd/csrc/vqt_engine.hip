@@ -1022,17 +1022,10 @@ __global__ __launch_bounds__(PK_WAVES * 64) void peaks_frames_generic(const floa
 }
 
 // ------------------------------------------------------------------------------------------------
-// Many SHORT streams, staged one behind the other (Vqt::batch_streams_device): piece p copies `count` samples from its stream to
+// Many SHORT streams, staged one behind the other (plan_stream_staging, batch_plan.hpp): piece p copies `count` samples from its stream to
 // position dst_off of the staging buffer (zeroed before: the gaps between the streams are the zeros / the history each stream's
 // first frames see).  grid: (chunks, pieces).
 // ------------------------------------------------------------------------------------------------
-struct StagePiece {
-    const float* src;     // first sample to copy (the stream's pointer + what of its lead does not fit the gap)
-    long long count;
-    long long dst_off;    // samples from the start of the staging buffer
-    long long zero_from;  // the gap before the piece, [zero_from, dst_off), is zeroed by it (the previous piece's end; 0 for the first)
-    long long zero_to;    // ... and [dst_off + count, zero_to) behind it (the buffer's end for the last piece, nothing otherwise)
-};
 __global__ __launch_bounds__(256) void stage_streams(float* __restrict__ dst, const StagePiece* __restrict__ pieces) {
     const StagePiece p = pieces[blockIdx.y];
     const long long t0 = (long long)blockIdx.x * 256 + threadIdx.x, step = (long long)gridDim.x * 256;
@@ -1054,6 +1047,12 @@ const char* Vqt::slot_name(uint32_t s) {
         case SLOT_PEAKS: return "peaks_frames";
         default: return "";
     }
+}
+
+pvq_status Vqt::require_device() const {
+    if (has_device()) return PVQ_OK;
+    set_last_error("handle was created without a device; there is no CPU fallback");
+    return PVQ_ERR_NO_DEVICE;
 }
 
 pvq_status Vqt::create(const VqtParameters& p, int device_id, std::unique_ptr<Vqt>& out, VqtError& err) {
@@ -1272,15 +1271,14 @@ pvq_status Vqt::launch_fft_streams(const void* st_table, size_t n_st, const floa
     // (more than 1 024 bins: at least as many threads as the dB epilogue needs for them, fft_db_threads)
     const int T = fft_db_threads(n_frames < 4 ? (n_tw <= 8192 ? 512 : 1024) : n_tw <= 2048 ? 128 : n_tw <= 4096 ? 256 : n_tw <= 8192 ? 512 : 1024,
                                  a.n_bins);
-    const int BLOCK = T == 1024 ? 1024 : 512;
-    const int F = BLOCK / T;
+    const int F = (T == 1024 ? 1024 : 512) / T;
     const size_t lds = (size_t)F * (sizeof(float2) * ((size_t)(n_tw + (n_tw >> 4)) + 1 + a.n_bins) + sizeof(float) * 2 * (T / 64));
     if (a.n_bins > FFT_MAX_BINS || lds > FFT_MAX_LDS) {   // (up to 1 024 bins every form fits: 147 KB at most, 16 384-point FFTs)
         set_last_error("unsupported: the FFT path takes up to 4096 bins, and a frame's largest FFT and its bins must fit 160 KB of LDS (" +
                        std::to_string(a.n_bins) + " bins, " + std::to_string(lds) + " bytes)");
         return PVQ_ERR_UNSUPPORTED;
     }
-    int grid = (int)std::min<size_t>((n_frames + F - 1) / F, 1u << 20);
+    const int grid = (int)std::min<size_t>((n_frames + F - 1) / F, 1u << 20);
     // few frames of one stream: a workgroup per window group (FftArgs::xv_split).  Measured against the walk (profiles/r04_fft_split.txt):
     // 1 frame 47 -> 19 us at 48 kHz / 252 bins (77 -> 27 at 96 kHz / 360), ahead up to ~400 frames there (~200 at 96 kHz, ~750 at
     // 22 050 Hz / 588 bins): up to ~1 500 workgroups, beyond which the chip is full either way and the walk's one pass over LDS wins
@@ -1296,85 +1294,10 @@ pvq_status Vqt::launch_fft_streams(const void* st_table, size_t n_st, const floa
         const int N = dev_->h_groups[g].n_cplx;
         ct = N >= 256 && N <= 16384 && (N & (N - 1)) == 0 && dev_->h_groups[g].n_cols > 1;
     }
-    if (ct) {
-        constexpr size_t PART = 16384;
-        pvq_status es = ensure_workspace(&ws_split_, &ws_split_cap_, std::min(PART, n_frames) * (size_t)a.n_bins * sizeof(float2));
-        if (es != PVQ_OK) return es;
-        a.xv_split = static_cast<float2*>(ws_split_);
-        slot_begin(SLOT_FFT_FRAMES, stream);
-        auto launch_group = [&](auto n_c, auto block_c, int g, int f0, int nf) -> pvq_status {
-            constexpr int N = decltype(n_c)::value, BLK = decltype(block_c)::value;
-            constexpr int Tg = N / 16, Fg = BLK / Tg;
-            const size_t lds_g = (size_t)Fg * (N + N / 16 + 1) * sizeof(float2);
-            auto kern = vqt_fft_group<N, BLK>;
-            PVQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g));
-            const int grid_g = (int)(((size_t)nf + Fg - 1) / Fg);   // a workgroup per Fg frames (the kernel makes one pass)
-            hipLaunchKernelGGL(kern, dim3(grid_g), dim3(BLK), lds_g, stream, a, g, f0, nf);
-            return PVQ_OK;
-        };
-        using std::integral_constant;
-        for (size_t f0 = 0; f0 < n_frames; f0 += PART) {
-            const int nf = (int)std::min(PART, n_frames - f0);
-            for (int g = 0; g < a.n_groups; ++g) {
-                pvq_status ls = PVQ_OK;
-                switch (dev_->h_groups[g].n_cplx) {
-                    case 16384: ls = launch_group(integral_constant<int, 16384>{}, integral_constant<int, 1024>{}, g, (int)f0, nf); break;
-                    case 8192: ls = launch_group(integral_constant<int, 8192>{}, integral_constant<int, 512>{}, g, (int)f0, nf); break;
-                    case 4096: ls = launch_group(integral_constant<int, 4096>{}, integral_constant<int, 512>{}, g, (int)f0, nf); break;
-                    case 2048: ls = launch_group(integral_constant<int, 2048>{}, integral_constant<int, 512>{}, g, (int)f0, nf); break;
-                    case 1024: ls = launch_group(integral_constant<int, 1024>{}, integral_constant<int, 512>{}, g, (int)f0, nf); break;
-                    case 512: ls = launch_group(integral_constant<int, 512>{}, integral_constant<int, 256>{}, g, (int)f0, nf); break;
-                    default: ls = launch_group(integral_constant<int, 256>{}, integral_constant<int, 128>{}, g, (int)f0, nf); break;
-                }
-                if (ls != PVQ_OK) return ls;
-            }
-            if (fft_db_threads(256, a.n_bins) == 256)
-                hipLaunchKernelGGL(db_rows_batch<256>, dim3((unsigned)nf), dim3(256), 0, stream, static_cast<const float2*>(ws_split_), nf, (int)f0, a.n_bins, a.streams,
-                                   a.n_streams, a.out_db, a.out_cplx, a.status);
-            else   // more than 1 024 bins
-                hipLaunchKernelGGL(db_rows_batch<1024>, dim3((unsigned)nf), dim3(1024), 0, stream, static_cast<const float2*>(ws_split_), nf, (int)f0, a.n_bins, a.streams,
-                                   a.n_streams, a.out_db, a.out_cplx, a.status);
-        }
-        slot_end(SLOT_FFT_FRAMES, stream);
-        if (pk) {
-            slot_begin(SLOT_PEAKS, stream);
-            pvq_status ps = launch_peaks_kernel(d_out_db, rows_total, *pk, stream);
-            slot_end(SLOT_PEAKS, stream);
-            if (ps != PVQ_OK) return ps;
-        }
-        PVQ_HIP(hipGetLastError());
-        last_algo_ = PVQ_ALGO_FFT;
-        last_frames_per_launch_ = (uint32_t)n_frames;
-        last_gemm_flop_ = 0.0;
-        return PVQ_OK;
-    }
-    if (split) {
-        pvq_status es = ensure_workspace(&ws_split_, &ws_split_cap_, n_frames * (size_t)a.n_bins * sizeof(float2));
-        if (es != PVQ_OK) return es;
-        a.xv_split = static_cast<float2*>(ws_split_);
-        grid *= a.n_groups;
-    }
-    slot_begin(SLOT_FFT_FRAMES, stream);
-    auto launch = [&](auto kern) -> pvq_status {
-        PVQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, stream, a);
-        return PVQ_OK;
-    };
-    pvq_status lst = T == 128 ? launch(vqt_fft_frames<512, 16, 128>) : T == 256 ? launch(vqt_fft_frames<512, 16, 256>)
-                     : T == 512 ? launch(vqt_fft_frames<512, 16, 512>) : launch(vqt_fft_frames<1024, 16, 1024>);
-    if (lst != PVQ_OK) return lst;
-    if (split) {
-        const float2* rows = static_cast<const float2*>(ws_split_);
-        if (T == 128) hipLaunchKernelGGL(db_rows<128>, dim3((unsigned)n_frames), dim3(128), 0, stream, rows, (int)n_frames, a.n_bins, a.out_db, a.out_cplx, a.status);
-        else if (T == 256) hipLaunchKernelGGL(db_rows<256>, dim3((unsigned)n_frames), dim3(256), 0, stream, rows, (int)n_frames, a.n_bins, a.out_db, a.out_cplx, a.status);
-        else if (T == 512) hipLaunchKernelGGL(db_rows<512>, dim3((unsigned)n_frames), dim3(512), 0, stream, rows, (int)n_frames, a.n_bins, a.out_db, a.out_cplx, a.status);
-        else hipLaunchKernelGGL(db_rows<1024>, dim3((unsigned)n_frames), dim3(1024), 0, stream, rows, (int)n_frames, a.n_bins, a.out_db, a.out_cplx, a.status);
-    }
-    slot_end(SLOT_FFT_FRAMES, stream);
+    const pvq_status fs = ct ? launch_fft_groups(a, n_frames, stream) : launch_fft_walk(a, T, grid, lds, split, n_frames, stream);
+    if (fs != PVQ_OK) return fs;
     if (pk) {  // peak / note detection as its own launch (one wavefront per frame)
-        slot_begin(SLOT_PEAKS, stream);
-        pvq_status ps = launch_peaks_kernel(d_out_db, rows_total, *pk, stream);
-        slot_end(SLOT_PEAKS, stream);
+        pvq_status ps = peaks_stage(d_out_db, rows_total, *pk, stream);
         if (ps != PVQ_OK) return ps;
     }
     PVQ_HIP(hipGetLastError());
@@ -1382,6 +1305,80 @@ pvq_status Vqt::launch_fft_streams(const void* st_table, size_t n_st, const floa
     last_frames_per_launch_ = (uint32_t)n_frames;
     last_gemm_flop_ = 0.0;
     return PVQ_OK;
+}
+
+// the per-window kernels: a launch per window group and 16 384-frame part, the parts' dB rows behind them
+pvq_status Vqt::launch_fft_groups(FftArgs& a, size_t n_frames, hipStream_t stream) {
+    constexpr size_t PART = 16384;
+    pvq_status es = ensure_workspace(&ws_split_, &ws_split_cap_, std::min(PART, n_frames) * (size_t)a.n_bins * sizeof(float2));
+    if (es != PVQ_OK) return es;
+    a.xv_split = static_cast<float2*>(ws_split_);
+    slot_begin(SLOT_FFT_FRAMES, stream);
+    auto launch_group = [&](auto n_c, auto block_c, int g, int f0, int nf) -> pvq_status {
+        constexpr int N = decltype(n_c)::value, BLK = decltype(block_c)::value;
+        constexpr int Tg = N / 16, Fg = BLK / Tg;
+        const size_t lds_g = (size_t)Fg * (N + N / 16 + 1) * sizeof(float2);
+        auto kern = vqt_fft_group<N, BLK>;
+        PVQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g));
+        const int grid_g = (int)(((size_t)nf + Fg - 1) / Fg);   // a workgroup per Fg frames (the kernel makes one pass)
+        hipLaunchKernelGGL(kern, dim3(grid_g), dim3(BLK), lds_g, stream, a, g, f0, nf);
+        return PVQ_OK;
+    };
+    using std::integral_constant;
+    for (size_t f0 = 0; f0 < n_frames; f0 += PART) {
+        const int nf = (int)std::min(PART, n_frames - f0);
+        for (int g = 0; g < a.n_groups; ++g) {
+            pvq_status ls = PVQ_OK;
+            switch (dev_->h_groups[g].n_cplx) {
+                case 16384: ls = launch_group(integral_constant<int, 16384>{}, integral_constant<int, 1024>{}, g, (int)f0, nf); break;
+                case 8192: ls = launch_group(integral_constant<int, 8192>{}, integral_constant<int, 512>{}, g, (int)f0, nf); break;
+                case 4096: ls = launch_group(integral_constant<int, 4096>{}, integral_constant<int, 512>{}, g, (int)f0, nf); break;
+                case 2048: ls = launch_group(integral_constant<int, 2048>{}, integral_constant<int, 512>{}, g, (int)f0, nf); break;
+                case 1024: ls = launch_group(integral_constant<int, 1024>{}, integral_constant<int, 512>{}, g, (int)f0, nf); break;
+                case 512: ls = launch_group(integral_constant<int, 512>{}, integral_constant<int, 256>{}, g, (int)f0, nf); break;
+                default: ls = launch_group(integral_constant<int, 256>{}, integral_constant<int, 128>{}, g, (int)f0, nf); break;
+            }
+            if (ls != PVQ_OK) return ls;
+        }
+        if (fft_db_threads(256, a.n_bins) == 256)
+            hipLaunchKernelGGL(db_rows_batch<256>, dim3((unsigned)nf), dim3(256), 0, stream, static_cast<const float2*>(ws_split_), nf, (int)f0, a.n_bins, a.streams,
+                               a.n_streams, a.out_db, a.out_cplx, a.status);
+        else   // more than 1 024 bins
+            hipLaunchKernelGGL(db_rows_batch<1024>, dim3((unsigned)nf), dim3(1024), 0, stream, static_cast<const float2*>(ws_split_), nf, (int)f0, a.n_bins, a.streams,
+                               a.n_streams, a.out_db, a.out_cplx, a.status);
+    }
+    slot_end(SLOT_FFT_FRAMES, stream);
+    return PVQ_OK;
+}
+
+// the walk (every workgroup its frames' window groups in turn), or its group-split launch with db_rows behind it
+pvq_status Vqt::launch_fft_walk(FftArgs& a, int T, int grid, size_t lds, bool split, size_t n_frames, hipStream_t stream) {
+    if (split) {
+        pvq_status es = ensure_workspace(&ws_split_, &ws_split_cap_, n_frames * (size_t)a.n_bins * sizeof(float2));
+        if (es != PVQ_OK) return es;
+        a.xv_split = static_cast<float2*>(ws_split_);
+        grid *= a.n_groups;
+    }
+    slot_begin(SLOT_FFT_FRAMES, stream);
+    auto launch = [&](auto kern, unsigned blocks, int threads, size_t dyn, auto... args) -> pvq_status {
+        if (dyn) PVQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), dyn, stream, args...);
+        return PVQ_OK;
+    };
+    const int BLOCK = T == 1024 ? 1024 : 512;
+    pvq_status lst = T == 128 ? launch(vqt_fft_frames<512, 16, 128>, grid, BLOCK, lds, a) : T == 256 ? launch(vqt_fft_frames<512, 16, 256>, grid, BLOCK, lds, a)
+                     : T == 512 ? launch(vqt_fft_frames<512, 16, 512>, grid, BLOCK, lds, a) : launch(vqt_fft_frames<1024, 16, 1024>, grid, BLOCK, lds, a);
+    if (lst != PVQ_OK) return lst;
+    if (split) {
+        const float2* rows = static_cast<const float2*>(ws_split_);
+        const unsigned nr = (unsigned)n_frames;
+        lst = T == 128 ? launch(db_rows<128>, nr, 128, 0, rows, (int)n_frames, a.n_bins, a.out_db, a.out_cplx, a.status)
+              : T == 256 ? launch(db_rows<256>, nr, 256, 0, rows, (int)n_frames, a.n_bins, a.out_db, a.out_cplx, a.status)
+              : T == 512 ? launch(db_rows<512>, nr, 512, 0, rows, (int)n_frames, a.n_bins, a.out_db, a.out_cplx, a.status)
+                         : launch(db_rows<1024>, nr, 1024, 0, rows, (int)n_frames, a.n_bins, a.out_db, a.out_cplx, a.status);
+    }
+    slot_end(SLOT_FFT_FRAMES, stream);
+    return lst;
 }
 
 pvq_status Vqt::calculate_batch_db_device(const float* d_pcm, size_t n_lead, size_t hop, size_t n_frames,
@@ -1393,10 +1390,7 @@ pvq_status Vqt::vqt_analyze_batch_device(const float* d_pcm, size_t n_lead, size
                                          const AnalysisParameters& ap, float* d_out_db, uint32_t* d_peak_mask,
                                          uint32_t* d_peak_count, float* d_center, float* d_size, uint32_t max_peaks,
                                          hipStream_t stream) {
-    if (!has_device()) {
-        set_last_error("handle was created without a device; there is no CPU fallback");
-        return PVQ_ERR_NO_DEVICE;
-    }
+    if (pvq_status ds = require_device(); ds != PVQ_OK) return ds;
     if ((d_center == nullptr) != (d_size == nullptr)) {
         set_last_error("analyze: only one of center/size given");
         return PVQ_ERR_INVALID_ARG;
@@ -1426,12 +1420,13 @@ pvq_status Vqt::order_on(hipStream_t s) {
     return PVQ_OK;
 }
 
+static const char kNoBlockHop[] =
+    "block-DFT path: no multiple r * hop (r = 1, 2, 4, 8, 16) is a multiple of 64 samples that the windows hold at most 16 times "
+    "(or a power of two dividing every window)";
+
 pvq_status Vqt::run_batch(const float* d_pcm, size_t n_lead, size_t hop, size_t n_frames, float* d_out_db,
                           float* d_out_cplx, const PeakParamsDev* pk, hipStream_t stream) {
-    if (!has_device()) {
-        set_last_error("handle was created without a device; there is no CPU fallback");
-        return PVQ_ERR_NO_DEVICE;
-    }
+    if (pvq_status ds = require_device(); ds != PVQ_OK) return ds;
     if (n_frames == 0) return PVQ_OK;
     if (!d_pcm || !d_out_db || hop == 0 || n_frames > (size_t)0x7fffffff) {
         set_last_error("calculate_batch: null pointer, zero hop or too many frames");
@@ -1444,88 +1439,34 @@ pvq_status Vqt::run_batch(const float* d_pcm, size_t n_lead, size_t hop, size_t 
     }
     // The block-DFT path takes the hop itself (r = 1), or — a hop it cannot take but whose r-fold it can, 800 -> 1 600 — r interleaved
     // block grids of hop r * hop: grid i holds the frames i, i + r, ... (each hop' block is then transformed once per grid)
-    const size_t r = blockdft_hop_factor(hop);
-    bool use_block = false;
-    if (algo_ == PVQ_ALGO_BLOCKDFT) {
-        if (r == 0) {
-            set_last_error("block-DFT path: no multiple r * hop (r = 1, 2, 4, 8, 16) is a multiple of 64 samples that the windows hold at most 16 times "
-                           "(or a power of two dividing every window)");
-            return PVQ_ERR_UNSUPPORTED;
-        }
-        use_block = true;
-    } else if (algo_ == PVQ_ALGO_AUTO) {
-        use_block = r != 0 && n_frames >= auto_block_min_frames(hop, r);
-    }
-    if (use_block && r > 1 && !blockdft_takes_streams(hop * r)) {
-        if (algo_ == PVQ_ALGO_BLOCKDFT) {
+    size_t r = 0;
+    switch (route(hop, n_frames, &r)) {
+        case BatchRoute::Fft: return launch_fft_path(d_pcm, n_lead, hop, n_frames, d_out_db, d_out_cplx, pk, stream);
+        case BatchRoute::RefuseNoHop: set_last_error(kNoBlockHop); return PVQ_ERR_UNSUPPORTED;
+        case BatchRoute::RefuseUnfusedHop:
             set_last_error("block-DFT path: this geometry runs the unfused stages, which take the hop only as it is");
             return PVQ_ERR_UNSUPPORTED;
-        }
-        use_block = false;
+        case BatchRoute::BlockStreams:
+        case BatchRoute::BlockPerStream: break;
     }
-    if (use_block && r == 1) return launch_blockdft_path(d_pcm, n_lead, hop, n_frames, d_out_db, d_out_cplx, pk, stream);
-    if (use_block) {
-        std::vector<StreamIn> st;
-        for (size_t i = 0; i < r && i < n_frames; ++i)
-            st.push_back(StreamIn{d_pcm, n_lead + (i + 1) * hop, n_lead + n_frames * hop, (n_frames - i + r - 1) / r, i, r});
-        return launch_blockdft_streams(st.data(), st.size(), hop * r, d_out_db, d_out_cplx, n_frames, pk, stream);
-    }
-    return launch_fft_path(d_pcm, n_lead, hop, n_frames, d_out_db, d_out_cplx, pk, stream);
+    if (r == 1) return launch_blockdft_path(d_pcm, n_lead, hop, n_frames, d_out_db, d_out_cplx, pk, stream);
+    std::vector<StreamRun> st;
+    append_interleaved_runs(st, d_pcm, n_lead, n_frames, hop, r, 0);
+    return launch_blockdft_streams(st.data(), st.size(), hop * r, d_out_db, d_out_cplx, n_frames, pk, stream);
+}
+
+// The one route decision (route_batch, batch_plan.hpp) under the handle's settings, for a call of n_frames frames in all.
+BatchRoute Vqt::route(size_t hop, size_t n_frames, size_t* r_out) const {
+    const size_t r = *r_out = blockdft_hop_factor(hop);
+    return route_batch(algo_, r, r != 0 && blockdft_takes_streams(hop * r), n_frames,
+                       algo_ == PVQ_ALGO_AUTO && r != 0 ? auto_block_min_frames(plan_, hop, r) : 0);
 }
 
 // which path run_batch takes for a batch of this shape (the multi-device driver decides once for the WHOLE stream, so that a shard of a
 // few frames runs the path the unsharded stream runs: the two paths agree to the parity bars, not bit for bit)
 pvq_algo Vqt::resolve_algo(size_t hop, size_t n_frames) const {
-    if (algo_ == PVQ_ALGO_FFT) return PVQ_ALGO_FFT;
-    const size_t r = blockdft_hop_factor(hop);
-    if (r == 0 || (r > 1 && !blockdft_takes_streams(hop * r))) return algo_ == PVQ_ALGO_BLOCKDFT ? PVQ_ALGO_BLOCKDFT : PVQ_ALGO_FFT;   // (forced: run_batch reports the error)
-    if (algo_ == PVQ_ALGO_BLOCKDFT) return PVQ_ALGO_BLOCKDFT;
-    return n_frames >= auto_block_min_frames(hop, r) ? PVQ_ALGO_BLOCKDFT : PVQ_ALGO_FFT;
-}
-
-// From how many frames on PVQ_ALGO_AUTO takes the block-DFT path (hop * r its block length).  A power-of-two hop: from 384 frames
-// (and at least one tile row per grid).  A general hop is different:
-// its tiles' K loops are hop * r / 2 deep, so a launch cannot end before ~180 us at 1 600 samples and ~300 us at 3 200 however few
-// frames it holds, while the FFT path — a workgroup per frame, 512 of them side by side — takes 53 us for up to ~420 frames and
-// 0.125 us per frame beyond (48 kHz / 252 bins; profiles/r04_small_batches.txt: 64 frames at hop 800 took 367 us on the block path
-// against 64 on the FFT path).  The estimate below — both paths' time as floor + frames x slope, the slopes scaled by the geometry's
-// FFT work and column count — puts the switch where the two lines cross: ~1 700 frames at hop 800 / 1 600, ~3 500 at 3 200.
-size_t Vqt::auto_block_min_frames(size_t hop, size_t r) const {
-    const size_t hop_eff = hop * r;
-    bool divides = (hop_eff & (hop_eff - 1)) == 0;
-    double fft_work = 0.0;   // sum over the window groups of W log2 W
-    size_t cols = 0;         // spectrum columns the kernel reads (upper bound: every group's highest column)
-    for (const WindowGroup& g : plan_.kernel.window_groups) {
-        const size_t w = g.window_size();
-        divides = divides && w % hop_eff == 0;
-        fft_work += (double)w * std::log2((double)w);
-        uint32_t top = 0;
-        for (uint32_t c : g.filter_bank.col_idx) top = c > top ? c : top;
-        for (uint32_t c : g.negative_filter_bank.col_idx) top = c > top ? c : top;
-        cols += top + 1;
-    }
-    // (a power-of-two hop: both paths' launches are short; the block path's two kernels cost 58-67 us up to ~1 000 frames at 48 kHz /
-    // 252 bins, the FFT path — group-split for few frames, launch_fft_streams — 19 us for one frame, 42 for 256, 56 for 400)
-    if (divides) return std::max<size_t>(64 * r, 384);
-    // Both paths' time for n frames, in us, as measured on one box (profiles/r05_auto_rule.txt):
-    //   FFT path     t_fft (n + 500): the per-window kernels (round 5: half the walk's time) ~ the FFT work + the row dots (bins)
-    //   block path   max(floor, floor / 2 + t_block n): a launch pair cannot end before `floor` however few frames it holds; per frame the K loops'
-    //                depth x columns + the kernel product (bins)
-    // and the switch sits at the first n (in steps of 64 r) where the block path is the faster one.  At the reference's default geometry
-    // (22 050 Hz, 588 bins) the per-window FFT kernels run level with the general-hop block path — 0.035 against 0.038 us per frame at hop 1 600 —
-    // and AUTO stays on the FFT path at every size.
-    double t_fft = 1.45e-7 * fft_work + 1.0e-5 * (double)n_bins();
-    if (plan_.params.n_fft > 0 && fft_work > 6.0e5) t_fft *= 1.15;                        // (a 32 768-sample window: 1 024 threads per frame, one workgroup per CU)
-    const double floor_block = 58.0 + 0.075 * ((double)hop_eff - 256.0) + 18.0;           // us: shortest launch pair of the general-hop kernels
-    const double t_block = 1.0e-5 * (double)hop_eff * ((double)cols / 871.0) + 3.2e-5 * (double)n_bins();   // (871: the column bound at 48 kHz / 252 bins, 602 of them read)
-    const size_t lo = 64 * r;
-    if (t_fft <= t_block) {   // the lines never cross beyond the floor: the switch, if any, lies where the FFT path reaches the block path's floor
-        const double n = floor_block / t_fft - 500.0;
-        return n > 0.0 && floor_block / 2 + t_block * n <= floor_block ? std::max(lo, (size_t)n) : ~(size_t)0 >> 1;
-    }
-    for (size_t n = lo; n < ((size_t)1 << 22); n += lo)
-        if (std::max(floor_block, floor_block / 2 + t_block * (double)n) < t_fft * ((double)n + 500.0)) return n;
-    return ~(size_t)0 >> 1;
+    size_t r = 0;
+    return route(hop, n_frames, &r) == BatchRoute::Fft ? PVQ_ALGO_FFT : PVQ_ALGO_BLOCKDFT;   // (a refusal: forced, the run functions report the error)
 }
 
 size_t Vqt::blockdft_hop_factor(size_t hop) const {
@@ -1537,10 +1478,7 @@ size_t Vqt::blockdft_hop_factor(size_t hop) const {
 pvq_status Vqt::batch_streams_device(const float* const* d_pcm, const size_t* n_lead, const size_t* n_frames, uint32_t n_streams, size_t hop,
                                      float* d_out_db, size_t stride, const AnalysisParameters* ap, uint32_t* d_peak_mask, uint32_t* d_peak_count,
                                      float* d_center, float* d_size, uint32_t max_peaks, hipStream_t stream) {
-    if (!has_device()) {
-        set_last_error("handle was created without a device; there is no CPU fallback");
-        return PVQ_ERR_NO_DEVICE;
-    }
+    if (pvq_status ds = require_device(); ds != PVQ_OK) return ds;
     if (n_streams == 0) return PVQ_OK;
     if (!d_pcm || !n_frames || !d_out_db || hop == 0) {
         set_last_error("batch_streams: null pointer or zero hop");
@@ -1584,150 +1522,73 @@ pvq_status Vqt::batch_streams_device(const float* const* d_pcm, const size_t* n_
     // rows a stream does not fill are zero frames: nothing reads uninitialised memory, their peak outputs say "no peaks"
     if (ragged) PVQ_HIP(hipMemsetAsync(d_out_db, 0, rows_total * nb * sizeof(float), stream));
     if (total == 0) return PVQ_OK;
-    const size_t r = blockdft_hop_factor(hop);   // 1: the hop itself; > 1: r interleaved block grids of hop r * hop (Vqt::run_batch)
-    bool use_block = false;
-    if (algo_ == PVQ_ALGO_BLOCKDFT) {
-        if (r == 0 || (r > 1 && !blockdft_takes_streams(hop * r))) {
-            set_last_error("block-DFT path: no multiple r * hop (r = 1, 2, 4, 8, 16) is a multiple of 64 samples that the windows hold at most 16 times "
-                           "(or a power of two dividing every window)");
-            return PVQ_ERR_UNSUPPORTED;
-        }
-        use_block = true;
-    } else if (algo_ == PVQ_ALGO_AUTO) {
-        use_block = r != 0 && total >= auto_block_min_frames(hop, r) && (r == 1 || blockdft_takes_streams(hop * r));
-    }
-    if (use_block && blockdft_takes_streams(hop * r)) {
-        // SHORT streams are staged one behind the other into ONE buffer — each in a slot of whole 64 r-frame tiles, the zeroed gap behind
-        // it holding the next stream's history — and analysed as one long stream: a tile of the GEMM then never stops at a stream's end,
-        // no stream's first tile is a range-checked one (dword loads: twice the time, no 64-column pairing), and a stream shorter than a
-        // tile does not leave the rest of it empty.  The price is one copy of the PCM (1 KB per frame at hop 256 against the 9.6 KB of X
-        // traffic) and the gap frames (63 per stream at hop 256, 9 at hop 1 600), which are computed and dropped.  Long streams go as
-        // they are (segments of the launch, no copy).  Same bits either way: a frame's values do not depend on its place in a tile.
-        static const int stage_max_env = dev_knob("PVQ_STAGE_MAX", 2048);   // streams of at most this many frames are staged (0: none; measured: 2 048 frames gain 2 %, 512 gain 42 %, 4 096 lose 9 %)
-        const size_t stage_max = (size_t)stage_max_env;
-        const size_t wu = plan_.window_union;
-        const size_t G = wu > hop ? (wu - hop + hop - 1) / hop : 0;     // frames of history a stream's first frame needs
-        const size_t A = 64 * r;                                         // slots start on whole tiles of every grid
-        std::vector<uint32_t> shorts;
-        std::vector<StreamIn> longs;
-        for (uint32_t s = 0; s < n_streams; ++s) {
-            if (n_frames[s] == 0) continue;
-            if (n_streams > 1 && n_frames[s] <= stage_max)
-                shorts.push_back(s);
-            else {
+    const PeakParamsDev* pkp = want_peaks ? &pk : nullptr;
+    size_t r = 0;   // 1: the hop itself; > 1: r interleaved block grids of hop r * hop (Vqt::run_batch)
+    switch (route(hop, total, &r)) {
+        case BatchRoute::RefuseNoHop:
+        case BatchRoute::RefuseUnfusedHop: set_last_error(kNoBlockHop); return PVQ_ERR_UNSUPPORTED;
+        case BatchRoute::Fft: {   // (any hop): all streams in ONE launch, the peaks over all rows behind it
+            std::vector<FftStream> tab;
+            long long f0 = 0;
+            for (uint32_t s = 0; s < n_streams; ++s) {
+                if (n_frames[s] == 0) continue;
                 const size_t lead = n_lead ? n_lead[s] : 0;
-                for (size_t i = 0; i < r && i < n_frames[s]; ++i) {
-                    StreamIn in{d_pcm[s], lead + (i + 1) * hop, lead + n_frames[s] * hop, (n_frames[s] - i + r - 1) / r, (size_t)s * stride + i, r};
-                    longs.push_back(in);
-                }
+                tab.push_back(FftStream{d_pcm[s], (long long)lead, (long long)(lead + n_frames[s] * hop), (long long)((size_t)s * stride), f0});
+                f0 += (long long)n_frames[s];
             }
+            return launch_fft_streams(tab.data(), tab.size(), nullptr, 0, hop, (size_t)f0, rows_total, d_out_db, nullptr, pkp, stream);
         }
-        if (shorts.size() == 1) {   // a single short stream gains nothing from a copy
-            const uint32_t s = shorts[0];
-            const size_t lead = n_lead ? n_lead[s] : 0;
-            for (size_t i = 0; i < r && i < n_frames[s]; ++i) {
-                StreamIn in{d_pcm[s], lead + (i + 1) * hop, lead + n_frames[s] * hop, (n_frames[s] - i + r - 1) / r, (size_t)s * stride + i, r};
-                longs.push_back(in);
+        case BatchRoute::BlockPerStream:   // one stream per call (the unfused block-DFT stages), the peaks once over all rows
+            for (uint32_t s = 0; s < n_streams; ++s) {
+                if (n_frames[s] == 0) continue;
+                pvq_status st = launch_blockdft_path(d_pcm[s], n_lead ? n_lead[s] : 0, hop, n_frames[s], d_out_db + (size_t)s * stride * nb, nullptr, nullptr, stream);
+                if (st != PVQ_OK) return st;
             }
-            shorts.clear();
-        }
-        // staged buffers of at most 144 K frames (one sub-batch of the block-DFT path) and 512 MiB each, filled and analysed one after the other on `stream`
-        const size_t vcap = std::max<size_t>(A * 4, std::min<size_t>((size_t)147456, ((size_t)512 << 20) / (hop * sizeof(float))) / A * A);
-        size_t at = 0;
-        while (at < shorts.size()) {
-            std::vector<Slot> slots;
-            std::vector<StagePiece> pieces;
-            size_t F = (G + A - 1) / A * A;   // the first slot leaves room for the first stream's history too
-            uint64_t hash = 1469598103934665603ull;
-            auto mix = [&](uint64_t x) { hash = (hash ^ x) * 1099511628211ull; };
-            long long longest = 0;
-            while (at < shorts.size()) {
-                const uint32_t s = shorts[at];
-                const size_t len = (n_frames[s] + G + A - 1) / A * A;
-                if (!slots.empty() && F + len > vcap) break;
-                const size_t lead = n_lead ? n_lead[s] : 0;
-                const size_t h = std::min(lead, std::min(G * hop, F * hop));   // what of the stream's own history the gap before its slot holds
-                slots.push_back(Slot{F, n_frames[s], (size_t)s * stride});
-                const long long prev_end = pieces.empty() ? 0ll : pieces.back().dst_off + pieces.back().count;
-                pieces.push_back(StagePiece{d_pcm[s] + (lead - h), (long long)(h + n_frames[s] * hop), (long long)(F * hop - h), prev_end, 0ll});
-                pieces.back().zero_to = pieces.back().dst_off + pieces.back().count;
-                longest = std::max(longest, pieces.back().count);
-                mix(F); mix(n_frames[s]); mix((uint64_t)s * stride);
-                F += len;
-                ++at;
+            break;
+        case BatchRoute::BlockStreams: {   // short streams staged into buffers (plan_stream_staging), then the long ones as they are
+            static const int stage_max_env = dev_knob("PVQ_STAGE_MAX", 2048);   // streams of at most this many frames are staged (0: none; measured: 2 048 frames gain 2 %, 512 gain 42 %, 4 096 lose 9 %)
+            const StreamStaging plan = plan_stream_staging(d_pcm, n_lead, n_frames, n_streams, stride, hop, r, plan_.window_union, (size_t)stage_max_env);
+            for (const StagedBuffer& b : plan.buffers) {   // filled and analysed one after the other on `stream`
+                pvq_status ls = stage_buffer(b, hop, stream);
+                if (ls != PVQ_OK) return ls;
+                std::vector<StreamRun> runs;
+                append_staged_runs(runs, b, static_cast<const float*>(ws_stage_), hop, r);
+                ls = launch_blockdft_streams(runs.data(), runs.size(), hop * r, d_out_db, nullptr, rows_total, nullptr, stream);
+                if (ls != PVQ_OK) return ls;
             }
-            const size_t FV = F, n_samp = FV * hop;
-            pvq_status es = ensure_workspace(&ws_stage_, &ws_stage_cap_, n_samp * sizeof(float));
-            if (es != PVQ_OK) return es;
-            es = ensure_workspace(&ws_stage_tab_, &ws_stage_tab_cap_, pieces.size() * sizeof(StagePiece));
-            if (es != PVQ_OK) return es;
-            pieces.back().zero_to = (long long)n_samp;   // (every sample of the buffer is written: a stream's data or a gap's zeros)
-            PVQ_HIP(hipMemcpyAsync(ws_stage_tab_, pieces.data(), pieces.size() * sizeof(StagePiece), hipMemcpyHostToDevice, stream));   // (pageable source: staged before the call returns)
-            // (the piece table holds at most 65 535 pieces per launch of the copy kernel: grid.y)
-            for (size_t p0 = 0; p0 < pieces.size(); p0 += 65535) {
-                const unsigned np = (unsigned)std::min<size_t>(65535, pieces.size() - p0);
-                const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((longest + 1023) / 1024, 64));
-                hipLaunchKernelGGL(stage_streams, dim3(gx, np), dim3(256), 0, stream, static_cast<float*>(ws_stage_), static_cast<const StagePiece*>(ws_stage_tab_) + p0);
+            if (!plan.longs.empty()) {
+                pvq_status ls = launch_blockdft_streams(plan.longs.data(), plan.longs.size(), hop * r, d_out_db, nullptr, rows_total, nullptr, stream);
+                if (ls != PVQ_OK) return ls;
             }
-            std::vector<StreamIn> runs;
-            for (size_t i = 0; i < r; ++i) {
-                StreamIn in{static_cast<const float*>(ws_stage_), (i + 1) * hop, n_samp, (FV - i + r - 1) / r, 0, r};
-                in.slots = slots.data();
-                in.n_slots = slots.size();
-                in.grid_i = i;
-                in.slot_hash = hash;
-                runs.push_back(in);
-            }
-            pvq_status ls = launch_blockdft_streams(runs.data(), runs.size(), hop * r, d_out_db, nullptr, rows_total, nullptr, stream);
-            if (ls != PVQ_OK) return ls;
+            break;
         }
-        if (!longs.empty()) {
-            pvq_status ls = launch_blockdft_streams(longs.data(), longs.size(), hop * r, d_out_db, nullptr, rows_total, nullptr, stream);
-            if (ls != PVQ_OK) return ls;
-        }
-        if (want_peaks) {
-            slot_begin(SLOT_PEAKS, stream);
-            pvq_status ps = launch_peaks_kernel(d_out_db, rows_total, pk, stream);
-            slot_end(SLOT_PEAKS, stream);
-            if (ps != PVQ_OK) return ps;
-            PVQ_HIP(hipGetLastError());
-        }
-        return PVQ_OK;
-    }
-    if (!use_block) {   // the FFT path (any hop): all streams in ONE launch, the peaks over all rows behind it
-        std::vector<FftStream> tab;
-        long long f0 = 0;
-        for (uint32_t s = 0; s < n_streams; ++s) {
-            if (n_frames[s] == 0) continue;
-            const size_t lead = n_lead ? n_lead[s] : 0;
-            tab.push_back(FftStream{d_pcm[s], (long long)lead, (long long)(lead + n_frames[s] * hop), (long long)((size_t)s * stride), f0});
-            f0 += (long long)n_frames[s];
-        }
-        return launch_fft_streams(tab.data(), tab.size(), nullptr, 0, hop, (size_t)f0, rows_total, d_out_db, nullptr, want_peaks ? &pk : nullptr, stream);
-    }
-    // one stream per call (the unfused block-DFT stages), the peaks once over all rows
-    for (uint32_t s = 0; s < n_streams; ++s) {
-        if (n_frames[s] == 0) continue;
-        float* out = d_out_db + (size_t)s * stride * nb;
-        pvq_status st = use_block ? launch_blockdft_path(d_pcm[s], n_lead ? n_lead[s] : 0, hop, n_frames[s], out, nullptr, nullptr, stream)
-                                  : launch_fft_path(d_pcm[s], n_lead ? n_lead[s] : 0, hop, n_frames[s], out, nullptr, nullptr, stream);
-        if (st != PVQ_OK) return st;
     }
     if (want_peaks) {
-        slot_begin(SLOT_PEAKS, stream);
-        pvq_status ps = launch_peaks_kernel(d_out_db, rows_total, pk, stream);
-        slot_end(SLOT_PEAKS, stream);
+        pvq_status ps = peaks_stage(d_out_db, rows_total, pk, stream);
         if (ps != PVQ_OK) return ps;
         PVQ_HIP(hipGetLastError());
     }
     return PVQ_OK;
 }
 
-pvq_status Vqt::calculate_batch_db(const float* pcm, size_t n_lead, size_t hop, size_t n_frames, float* out_db) {
-    if (!has_device()) {
-        set_last_error("handle was created without a device; there is no CPU fallback");
-        return PVQ_ERR_NO_DEVICE;
+// One staged buffer into ws_stage_: the piece table up, then the copy kernel (every sample of the buffer is written).
+pvq_status Vqt::stage_buffer(const StagedBuffer& b, size_t hop, hipStream_t stream) {
+    pvq_status es = ensure_workspace(&ws_stage_, &ws_stage_cap_, b.frames * hop * sizeof(float));
+    if (es != PVQ_OK) return es;
+    es = ensure_workspace(&ws_stage_tab_, &ws_stage_tab_cap_, b.pieces.size() * sizeof(StagePiece));
+    if (es != PVQ_OK) return es;
+    PVQ_HIP(hipMemcpyAsync(ws_stage_tab_, b.pieces.data(), b.pieces.size() * sizeof(StagePiece), hipMemcpyHostToDevice, stream));   // (pageable source: staged before the call returns)
+    // (the piece table holds at most 65 535 pieces per launch of the copy kernel: grid.y)
+    for (size_t p0 = 0; p0 < b.pieces.size(); p0 += 65535) {
+        const unsigned np = (unsigned)std::min<size_t>(65535, b.pieces.size() - p0);
+        const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((b.longest + 1023) / 1024, 64));
+        hipLaunchKernelGGL(stage_streams, dim3(gx, np), dim3(256), 0, stream, static_cast<float*>(ws_stage_), static_cast<const StagePiece*>(ws_stage_tab_) + p0);
     }
+    return PVQ_OK;
+}
+
+pvq_status Vqt::calculate_batch_db(const float* pcm, size_t n_lead, size_t hop, size_t n_frames, float* out_db) {
+    if (pvq_status ds = require_device(); ds != PVQ_OK) return ds;
     if (n_frames == 0) return PVQ_OK;
     if (!pcm || !out_db || hop == 0) {
         set_last_error("calculate_batch: null pointer or zero hop");
@@ -1817,10 +1678,7 @@ pvq_status Vqt::calculate_vqt_instant_in_db(const float* x, size_t len, float* o
         set_last_error("input must be exactly n_fft samples");
         return PVQ_ERR_BAD_LENGTH;
     }
-    if (!has_device()) {
-        set_last_error("handle was created without a device; there is no CPU fallback");
-        return PVQ_ERR_NO_DEVICE;
-    }
+    if (pvq_status ds = require_device(); ds != PVQ_OK) return ds;
     if (!x || !out_db) {
         set_last_error("calculate_vqt_instant_in_db: null pointer");
         return PVQ_ERR_INVALID_ARG;
@@ -1865,10 +1723,13 @@ pvq_status Vqt::calculate_vqt_instant_in_db(const float* x, size_t len, float* o
     return PVQ_OK;
 }
 
-pvq_status Vqt::launch_peaks_kernel(const float* d_db, size_t n_frames, const PeakParamsDev& a, hipStream_t stream) {
+// the peak kernels as one timed stage (SLOT_PEAKS); callers check hipGetLastError where they always did
+pvq_status Vqt::peaks_stage(const float* d_db, size_t n_frames, const PeakParamsDev& a, hipStream_t stream) {
+    slot_begin(SLOT_PEAKS, stream);
     pvq_status st = ensure_workspace(&ws_flags_, &ws_flags_cap_, n_frames);
-    if (st != PVQ_OK) return st;
-    return launch_peaks_frames(d_db, n_frames, a, static_cast<uint8_t*>(ws_flags_), stream);
+    if (st == PVQ_OK) st = launch_peaks_frames(d_db, n_frames, a, static_cast<uint8_t*>(ws_flags_), stream);
+    slot_end(SLOT_PEAKS, stream);
+    return st;
 }
 
 // find_peaks over n_frames independent dB rows (the lean kernel, then the generic one over the few frames it flags in `redo`, n_frames bytes
@@ -1927,10 +1788,7 @@ pvq_status launch_peaks_frames(const float* d_db, size_t n_frames, const PeakPar
 pvq_status Vqt::analyze_batch_device(const float* d_db, size_t n_frames, const AnalysisParameters& ap,
                                      uint32_t* d_peak_mask, uint32_t* d_peak_count, float* d_center, float* d_size,
                                      uint32_t max_peaks, hipStream_t stream) {
-    if (!has_device()) {
-        set_last_error("handle was created without a device; there is no CPU fallback");
-        return PVQ_ERR_NO_DEVICE;
-    }
+    if (pvq_status ds = require_device(); ds != PVQ_OK) return ds;
     if (n_frames == 0) return PVQ_OK;
     if (!d_db || ((d_center == nullptr) != (d_size == nullptr))) {
         set_last_error("analyze_batch: null dB pointer, or only one of center/size given");
@@ -1946,9 +1804,7 @@ pvq_status Vqt::analyze_batch_device(const float* d_db, size_t n_frames, const A
         pvq_status os = order_on(stream);
         if (os != PVQ_OK) return os;
     }
-    slot_begin(SLOT_PEAKS, stream);
-    pvq_status ps = launch_peaks_kernel(d_db, n_frames, a, stream);
-    slot_end(SLOT_PEAKS, stream);
+    pvq_status ps = peaks_stage(d_db, n_frames, a, stream);
     if (ps != PVQ_OK) return ps;
     PVQ_HIP(hipGetLastError());
     return PVQ_OK;
@@ -1956,10 +1812,7 @@ pvq_status Vqt::analyze_batch_device(const float* d_db, size_t n_frames, const A
 
 pvq_status Vqt::analyze_batch(const float* db, size_t n_frames, const AnalysisParameters& ap, uint32_t* peak_mask,
                               uint32_t* peak_count, float* center, float* size, uint32_t max_peaks) {
-    if (!has_device()) {
-        set_last_error("handle was created without a device; there is no CPU fallback");
-        return PVQ_ERR_NO_DEVICE;
-    }
+    if (pvq_status ds = require_device(); ds != PVQ_OK) return ds;
     if (n_frames == 0) return PVQ_OK;
     if (!db) {
         set_last_error("analyze_batch: null dB pointer");
@@ -2021,6 +1874,28 @@ pvq_status Vqt::multi_buffers(const size_t (&bytes)[6], void* (&out)[6], hipStre
     return PVQ_OK;
 }
 
+// every handle present, on a device, passed once, of the same parameters
+static pvq_status check_multi_handles(Vqt* const* handles, uint32_t n_handles) {
+    for (uint32_t g = 0; g < n_handles; ++g) {
+        if (!handles[g]) {
+            set_last_error("analyze_batch_multi: null handle");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        if (pvq_status ds = handles[g]->require_device(); ds != PVQ_OK) return ds;
+        for (uint32_t h = 0; h < g; ++h)
+            if (handles[h] == handles[g]) {
+                set_last_error("analyze_batch_multi: a handle is exclusive to one worker; the same handle was passed twice");
+                return PVQ_ERR_INVALID_ARG;
+            }
+        const VqtParameters &p0 = handles[0]->params(), &pg = handles[g]->params();
+        if (std::memcmp(&p0, &pg, sizeof(VqtParameters)) != 0) {
+            set_last_error("analyze_batch_multi: the handles were created with different parameters");
+            return PVQ_ERR_INVALID_ARG;
+        }
+    }
+    return PVQ_OK;
+}
+
 pvq_status analyze_batch_multi(Vqt* const* handles, uint32_t n_handles, const float* pcm, size_t n_lead, size_t hop, size_t n_frames,
                                const AnalysisParameters& ap, float* out_db, uint32_t* peak_mask, uint32_t* peak_count, float* center,
                                float* size, uint32_t max_peaks) {
@@ -2037,26 +1912,7 @@ pvq_status analyze_batch_multi(Vqt* const* handles, uint32_t n_handles, const fl
         set_last_error("analyze_batch_multi: center and size go together, with max_peaks > 0");
         return PVQ_ERR_INVALID_ARG;
     }
-    for (uint32_t g = 0; g < n_handles; ++g) {
-        if (!handles[g]) {
-            set_last_error("analyze_batch_multi: null handle");
-            return PVQ_ERR_INVALID_ARG;
-        }
-        if (!handles[g]->has_device()) {
-            set_last_error("handle was created without a device; there is no CPU fallback");
-            return PVQ_ERR_NO_DEVICE;
-        }
-        for (uint32_t h = 0; h < g; ++h)
-            if (handles[h] == handles[g]) {
-                set_last_error("analyze_batch_multi: a handle is exclusive to one worker; the same handle was passed twice");
-                return PVQ_ERR_INVALID_ARG;
-            }
-        const VqtParameters &p0 = handles[0]->params(), &pg = handles[g]->params();
-        if (std::memcmp(&p0, &pg, sizeof(VqtParameters)) != 0) {
-            set_last_error("analyze_batch_multi: the handles were created with different parameters");
-            return PVQ_ERR_INVALID_ARG;
-        }
-    }
+    if (pvq_status hs = check_multi_handles(handles, n_handles); hs != PVQ_OK) return hs;
     const size_t nb = handles[0]->n_bins(), words = (nb + 31) / 32;
     const size_t wu = handles[0]->plan().window_union;
     const bool want_peaks = peak_mask || peak_count || center;

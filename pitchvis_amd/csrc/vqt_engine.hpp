@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/pvq.h"
+#include "batch_plan.hpp"
 #include "blockdft_plan.hpp"
 #include "multi_host.hpp"
 #include "vqt_host.hpp"
@@ -46,6 +47,7 @@ struct AnalysisParameters {
 struct DeviceTables;   // opaque (device_tables.hpp)
 struct PeakParamsDev;  // peaks_device.hpp
 struct BlockLaunch;    // vqt_blockdft.hip
+struct FftArgs;        // vqt_engine.hip
 
 class Vqt {
    public:
@@ -59,6 +61,7 @@ class Vqt {
     double delay_seconds() const { return plan_.delay_seconds; }  // vqt.rs:449
     uint32_t n_bins() const { return plan_.params.range.n_buckets(); }
     bool has_device() const { return device_id_ >= 0; }
+    pvq_status require_device() const;   // PVQ_ERR_NO_DEVICE (and the text) for a handle created without a device: every compute entry point's first check
     int device() const { return device_id_; }
 
     // vqt.rs:866 (host pointers, synchronous)
@@ -128,27 +131,15 @@ class Vqt {
                                float* d_out_cplx, const PeakParamsDev* pk, hipStream_t stream);
     pvq_status launch_fft_streams(const void* st_table, size_t n_st, const float* d_pcm, size_t n_lead, size_t hop, size_t n_frames, size_t rows_total,
                                   float* d_out_db, float* d_out_cplx, const PeakParamsDev* pk, hipStream_t stream);   // st_table: FftStream[n_st] (vqt_engine.hip) or null
+    pvq_status launch_fft_groups(FftArgs& a, size_t n_frames, hipStream_t stream);   // the two forms of one launch of the FFT path
+    pvq_status launch_fft_walk(FftArgs& a, int T, int grid, size_t lds, bool split, size_t n_frames, hipStream_t stream);
     bool blockdft_applicable(size_t hop) const;
     bool blockdft_takes_streams(size_t hop) const;
-    // One run of frames for the block-DFT path: frame f' (of n_frames) ends at sample first_end + f' * hop of a buffer of n_samples
-    // valid samples (zeros before it and after it) and goes to output row out_row0 + f' * row_step.  A stream of a many-streams call is
-    // one run (first_end = n_lead + hop, row_step 1); a hop the path cannot take itself but whose r-fold it can (800 -> 1 600) is r
-    // interleaved runs of hop r * hop, run i holding the frames i, i + r, ... (first_end = n_lead + (i + 1) hop, row_step r).
-    // A run may also read a STAGED buffer that holds many short streams one behind the other, each in a slot of whole 64 r-frame tiles
-    // followed by a gap that is the next stream's history (Vqt::batch_streams_device): then `slots` says which output rows the
-    // run's frames are — frame t of the run is frame grid_i + row_step * t of the staged buffer — and out_row0 is unused.
-    using Slot = BdSlot;   // frames [vframe0, vframe0 + n_frames) of the staged buffer -> rows out_row0 ...
-    struct StreamIn {
-        const float* d_pcm;
-        size_t first_end, n_samples, n_frames, out_row0, row_step;
-        const Slot* slots = nullptr;
-        size_t n_slots = 0, grid_i = 0;
-        uint64_t slot_hash = 0;
-    };
     size_t blockdft_hop_factor(size_t hop) const;   // smallest r in {1, 2, 4, 8, 16} with blockdft_applicable(r * hop), 0 if none
-    size_t auto_block_min_frames(size_t hop, size_t r) const;   // PVQ_ALGO_AUTO: the block-DFT path from this many frames on
-    pvq_status launch_blockdft_streams(const StreamIn* st, size_t n_st, size_t hop, float* d_out_db, float* d_out_cplx, size_t rows_total,
+    BatchRoute route(size_t hop, size_t n_frames, size_t* r) const;   // route_batch for a call of n_frames frames in all under the handle's settings; *r: the hop factor
+    pvq_status launch_blockdft_streams(const StreamRun* st, size_t n_st, size_t hop, float* d_out_db, float* d_out_cplx, size_t rows_total,
                                        const PeakParamsDev* pk, hipStream_t stream);
+    pvq_status stage_buffer(const StagedBuffer& b, size_t hop, hipStream_t stream);   // the staged buffer into ws_stage_: piece table up, copy kernel
     pvq_status prepare_blockdft(size_t hop);
     // the stages of one launch of the block-DFT path (vqt_blockdft.hip)
     pvq_status grow_blockdft_workspaces(const std::vector<LaunchShape>& shapes, size_t rows_cap, bool fused, bool use_bf, hipStream_t stream);
@@ -159,7 +150,7 @@ class Vqt {
     pvq_status launch_blockdft_path(const float* d_pcm, size_t n_lead, size_t hop, size_t n_frames,
                                     float* d_out_db, float* d_out_cplx, const PeakParamsDev* pk, hipStream_t stream);
     pvq_status ensure_workspace(void** ptr, size_t* cap, size_t bytes);
-    pvq_status launch_peaks_kernel(const float* d_db, size_t n_frames, const PeakParamsDev& p, hipStream_t s);
+    pvq_status peaks_stage(const float* d_db, size_t n_frames, const PeakParamsDev& p, hipStream_t s);   // the peak kernels as the timed SLOT_PEAKS stage
     void slot_begin(int slot, hipStream_t s);
     // One handle's calls are ORDERED: the workspaces (X, the group-split rows, staging buffers, tile-list slots, the peak kernels' redo
     // flags) belong to the handle, so a call on another stream than the previous call's — the single-frame route's own stream after an

@@ -2,8 +2,9 @@
 // AddressSanitizer is not available on this pool).  Replays, through the instrumented objects, what tests/test_host_plan.py,
 // tests/test_analysis_state.py, tests/test_consumers.py and tests/test_multi_device.py feed them: kernel construction for every test
 // geometry (including the two constructor errors and a reference panic), the AnalysisState recurrence in three smoothing modes, the
-// peak helpers on crafted frames, the AGC / dataset / LED / .npy consumers, the shard planner and the block-DFT path's planner
-// (tables, run packing, tile lists, segment tables and X-tile maps: structural invariants over every test geometry and launch shape).
+// peak helpers on crafted frames, the AGC / dataset / LED / .npy consumers, the shard planner, the block-DFT path's planner
+// (tables, run packing, tile lists, segment tables and X-tile maps: structural invariants over every test geometry and launch shape)
+// and the batch planner above it (route, interleaved runs, staging of short streams), whose stream sets feed the former.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "analysis_host.hpp"
+#include "batch_plan.hpp"
 #include "blockdft_plan.hpp"
 #include "consumers_host.hpp"
 #include "multi_host.hpp"
@@ -28,44 +30,189 @@ static float frand() {   // xorshift64*, [0, 1)
 }
 #define CHECK(c) do { if (!(c)) { std::fprintf(stderr, "CHECK failed: %s (line %d)\n", #c, __LINE__); std::exit(2); } } while (0)
 
-// ---- block-DFT planner (blockdft_plan.cpp) ---------------------------------------------------------------------------------------
-// One set of streams as Vqt::batch_streams_device / run_batch hand them to the path: `r` interleaved runs per stream (hop H = r * hop).
+// ---- stream sets (batch_plan.cpp) ------------------------------------------------------------------------------------------------
+// A stream table as pvq_vqt_*_streams gets it.  The addresses are made up, each stream a region of its own: the planners measure
+// distances between them and never read through them.
+struct StreamTable {
+    std::vector<const float*> pcm;
+    std::vector<size_t> lead, n_frames;
+    size_t stride = 0;
+};
+static StreamTable stream_table(const std::vector<size_t>& n_frames, const std::vector<size_t>& leads, size_t hop) {
+    StreamTable t;
+    t.n_frames = n_frames;
+    uintptr_t at = 0x100000;
+    for (size_t k = 0; k < n_frames.size(); ++k) {
+        t.stride = std::max(t.stride, n_frames[k]);
+        t.lead.push_back(leads[k % leads.size()]);
+        t.pcm.push_back(reinterpret_cast<const float*>(at));
+        at += (t.lead[k] + n_frames[k] * hop + 7) * sizeof(float);
+    }
+    return t;
+}
+// One set of streams as Vqt::batch_streams_device / run_batch hand them to the block-DFT path, built by the planner they use:
+// `r` interleaved runs per stream (hop H = r * hop), or the r runs over ONE staged buffer.
 struct StreamSet {
-    std::vector<BdStream> st;
-    std::vector<BdSlot> slots;
+    StreamStaging plan;
+    std::vector<BdStream> st;      // the runs rebased on the lowest stream pointer, as launch_blockdft_streams hands them on
     size_t rows_total = 0, chunk = 0;
 };
-static StreamSet plain_streams(const std::vector<size_t>& n_frames, size_t r, size_t hop, size_t lead, size_t chunk) {
+static StreamSet stream_set(const StreamTable& t, size_t r, size_t hop, size_t window_union, bool staged, size_t chunk) {
     StreamSet s;
+    s.plan = plan_stream_staging(t.pcm.data(), t.lead.data(), t.n_frames.data(), (uint32_t)t.pcm.size(), t.stride, hop, r, window_union, staged ? ~(size_t)0 : 0);
+    std::vector<StreamRun> runs = s.plan.longs;
+    if (staged) {
+        CHECK(s.plan.longs.empty() && s.plan.buffers.size() == 1);
+        append_staged_runs(runs, s.plan.buffers[0], reinterpret_cast<const float*>((uintptr_t)0x40), hop, r);
+        CHECK(runs.size() == r);
+        chunk = (s.plan.buffers[0].frames + 63) / 64 * 64;
+    } else
+        CHECK(s.plan.buffers.empty());
+    const float* base = nullptr;
+    s.st = rebase_runs(runs.data(), runs.size(), &base);
+    for (size_t i = 0; i < runs.size(); ++i) CHECK(base <= runs[i].pcm && s.st[i].pcm_off >= 0 && s.st[i].n_frames == runs[i].n_frames && s.st[i].slots == runs[i].slots);
+    s.rows_total = t.stride * t.pcm.size();
     s.chunk = chunk;
-    size_t stride = 0;
-    for (size_t n : n_frames) stride = std::max(stride, n);
-    long long off = 0;
-    for (size_t k = 0; k < n_frames.size(); ++k) {
-        for (size_t i = 0; i < r && i < n_frames[k]; ++i)
-            s.st.push_back(BdStream{off, lead + (i + 1) * hop, lead + n_frames[k] * hop, (n_frames[k] - i + r - 1) / r, k * stride + i, r, nullptr, 0, 0, 0});
-        off += (long long)(lead + n_frames[k] * hop) + 7;
-    }
-    s.rows_total = stride * n_frames.size();
-    return s;
-}
-static StreamSet staged_streams(const std::vector<size_t>& n_frames, size_t r, size_t hop, size_t window_union) {   // vqt_engine.hip: batch_streams_device
-    StreamSet s;
-    size_t stride = 0;
-    for (size_t n : n_frames) stride = std::max(stride, n);
-    const size_t G = window_union > hop ? (window_union - hop + hop - 1) / hop : 0, A = 64 * r;
-    size_t F = (G + A - 1) / A * A;
-    for (size_t k = 0; k < n_frames.size(); ++k) {
-        s.slots.push_back(BdSlot{F, n_frames[k], k * stride});
-        F += (n_frames[k] + G + A - 1) / A * A;
-    }
-    for (size_t i = 0; i < r; ++i)
-        s.st.push_back(BdStream{0, (i + 1) * hop, F * hop, (F - i + r - 1) / r, 0, r, s.slots.data(), s.slots.size(), i, 0x1234u + i});
-    s.rows_total = stride * n_frames.size();
-    s.chunk = (F + 63) / 64 * 64;
     return s;
 }
 
+// the runs of one stream: its frames once each, run i the frames i, i + r, ... on the rows row0 + i + r t
+static void check_interleaved_runs(const StreamRun* runs, size_t n_runs, const float* pcm, size_t lead, size_t n_frames, size_t hop, size_t r, size_t row0) {
+    CHECK(n_runs == std::min(r, n_frames));
+    std::vector<int> seen(n_frames, 0);
+    for (size_t i = 0; i < n_runs; ++i) {
+        const StreamRun& S = runs[i];
+        CHECK(S.pcm == pcm && S.row_step == r && S.out_row0 == row0 + i && S.n_samples == lead + n_frames * hop && S.slots == nullptr && S.n_frames > 0);
+        for (size_t t = 0; t < S.n_frames; ++t) {
+            const size_t end = S.first_end + t * hop * r;   // (the run's hop is r * hop)
+            CHECK(end > lead && (end - lead) % hop == 0);
+            const size_t f = (end - lead) / hop - 1;
+            CHECK(f < n_frames && f == i + r * t && S.out_row0 + t * S.row_step == row0 + f);
+            ++seen[f];
+        }
+    }
+    for (int c : seen) CHECK(c == 1);
+}
+
+// plan_stream_staging over one stream table: every stream once, slots on whole tiles with their history gap, pieces that tile the buffer
+static std::vector<uint64_t> check_staging(const StreamTable& t, size_t hop, size_t r, size_t window_union, size_t stage_max) {
+    const StreamStaging plan = plan_stream_staging(t.pcm.data(), t.lead.data(), t.n_frames.data(), (uint32_t)t.pcm.size(), t.stride, hop, r, window_union, stage_max);
+    const size_t G = staging_history_frames(window_union, hop), A = 64 * r;
+    const size_t cap = std::min<size_t>(147456, ((size_t)512 << 20) / (hop * sizeof(float)));
+    CHECK(G * hop + hop >= window_union && (G == 0 || (G - 1) * hop + hop < window_union));
+    std::vector<int> seen(t.pcm.size(), 0);
+    size_t at = 0;
+    while (at < plan.longs.size()) {   // a long stream: its runs side by side
+        CHECK(t.stride > 0);
+        const size_t s = plan.longs[at].out_row0 / t.stride;
+        CHECK(s < t.pcm.size() && t.n_frames[s] > 0);
+        const size_t n_runs = std::min(r, t.n_frames[s]);
+        CHECK(at + n_runs <= plan.longs.size());
+        check_interleaved_runs(&plan.longs[at], n_runs, t.pcm[s], t.lead[s], t.n_frames[s], hop, r, s * t.stride);
+        ++seen[s];
+        at += n_runs;
+    }
+    std::vector<uint64_t> hashes;
+    for (const StagedBuffer& b : plan.buffers) {
+        CHECK(!b.slots.empty() && b.pieces.size() == b.slots.size() && (b.slots.size() == 1 || b.frames <= cap));
+        size_t prev_end = 0;       // frames: the end of the slot before
+        long long written = 0;     // samples: everything before is a stream's data or zeroed
+        long long longest = 0;
+        for (size_t i = 0; i < b.slots.size(); ++i) {
+            const BdSlot& sl = b.slots[i];
+            const StagePiece& pc = b.pieces[i];
+            const size_t s = sl.out_row0 / t.stride;
+            CHECK(s < t.pcm.size() && sl.out_row0 == s * t.stride && sl.n_frames == t.n_frames[s] && sl.n_frames > 0 && sl.n_frames <= stage_max);
+            ++seen[s];
+            CHECK(sl.vframe0 % A == 0 && sl.vframe0 >= prev_end + G);
+            prev_end = sl.vframe0 + sl.n_frames;
+            // the piece: the stream's frames from the slot's first sample on, before them what of its lead the gap holds
+            const long long h = (long long)(sl.vframe0 * hop) - pc.dst_off;
+            CHECK(h >= 0 && (size_t)h <= t.lead[s] && (size_t)h <= G * hop && pc.src == t.pcm[s] + (t.lead[s] - (size_t)h));
+            CHECK(pc.count == h + (long long)(sl.n_frames * hop) && pc.src + pc.count == t.pcm[s] + t.lead[s] + sl.n_frames * hop);
+            CHECK((size_t)h == std::min(t.lead[s], G * hop) || pc.dst_off == 0);   // (all the history a frame reads, unless the buffer begins there)
+            CHECK(pc.zero_from == written && pc.dst_off >= pc.zero_from && pc.zero_to >= pc.dst_off + pc.count);
+            CHECK(i + 1 == b.slots.size() ? pc.zero_to == (long long)(b.frames * hop) : pc.zero_to == pc.dst_off + pc.count);
+            written = pc.zero_to;
+            longest = std::max(longest, pc.count);
+        }
+        CHECK(written == (long long)(b.frames * hop) && b.frames % A == 0 && b.frames >= prev_end && longest == b.longest);
+        std::vector<StreamRun> runs;
+        append_staged_runs(runs, b, reinterpret_cast<const float*>((uintptr_t)0x40), hop, r);
+        CHECK(runs.size() == r);
+        size_t frames = 0;
+        for (size_t i = 0; i < r; ++i) {
+            CHECK(runs[i].grid_i == i && runs[i].row_step == r && runs[i].first_end == (i + 1) * hop && runs[i].n_samples == b.frames * hop);
+            CHECK(runs[i].slots == b.slots.data() && runs[i].n_slots == b.slots.size() && runs[i].slot_hash == b.hash);
+            frames += runs[i].n_frames;
+        }
+        CHECK(frames == b.frames);
+        hashes.push_back(b.hash);
+    }
+    for (size_t s = 0; s < seen.size(); ++s) CHECK(seen[s] == (t.n_frames[s] > 0 ? 1 : 0));
+    return hashes;
+}
+
+static void check_batch_plan(const HostPlan& plan, bool bench_geometry) {
+    const size_t wu = plan.window_union;
+    auto hop_factor = [&](size_t hop) -> size_t {   // Vqt::blockdft_hop_factor
+        for (size_t r = 1; r <= 16; r *= 2)
+            if (blockdft_plan_applicable(plan, hop * r)) return r;
+        return 0;
+    };
+    // ---- route: one function for the run functions and for Vqt::resolve_algo; what it may answer, per setting
+    const size_t counts[] = {1, 63, 64, 383, 384, 1700, 3500, 65536, (size_t)1 << 20};
+    for (size_t hop : {(size_t)64, (size_t)256, (size_t)1024, (size_t)800, (size_t)1600, (size_t)320, (size_t)735}) {
+        const size_t r = hop_factor(hop);
+        const size_t thr = r ? auto_block_min_frames(plan, hop, r) : 0;
+        CHECK(r == 0 || thr >= 64 * r);
+        for (int takes = 0; takes < 2; ++takes) {
+            if (r == 0 && takes) continue;
+            bool block_before = false;
+            for (size_t n : counts) {
+                CHECK(route_batch(PVQ_ALGO_FFT, r, takes != 0, n, thr) == BatchRoute::Fft);
+                const BatchRoute forced = route_batch(PVQ_ALGO_BLOCKDFT, r, takes != 0, n, thr), au = route_batch(PVQ_ALGO_AUTO, r, takes != 0, n, thr);
+                CHECK(forced == (r == 0 ? BatchRoute::RefuseNoHop : takes ? BatchRoute::BlockStreams : r == 1 ? BatchRoute::BlockPerStream : BatchRoute::RefuseUnfusedHop));
+                // AUTO never refuses; it takes the block-DFT path where the forced setting runs it, from the threshold on
+                const bool runs_forced = forced == BatchRoute::BlockStreams || forced == BatchRoute::BlockPerStream;
+                CHECK(au == (runs_forced && n >= thr ? forced : BatchRoute::Fft));
+                CHECK(!block_before || au != BatchRoute::Fft);
+                block_before = au != BatchRoute::Fft;
+            }
+        }
+    }
+    if (bench_geometry) {   // tests/test_handles_gpu.py: test_resolve_algo_is_a_pure_query (general hops: the fused kernels take streams)
+        CHECK(hop_factor(800) == 2 && hop_factor(735) == 0 && hop_factor(320) != 0);
+        CHECK(route_batch(PVQ_ALGO_AUTO, 2, true, 100000, auto_block_min_frames(plan, 800, 2)) == BatchRoute::BlockStreams);
+        CHECK(route_batch(PVQ_ALGO_AUTO, 2, true, 64, auto_block_min_frames(plan, 800, 2)) == BatchRoute::Fft);
+        CHECK(route_batch(PVQ_ALGO_AUTO, hop_factor(320), true, 100000, auto_block_min_frames(plan, 320, hop_factor(320))) == BatchRoute::BlockStreams);
+        CHECK(route_batch(PVQ_ALGO_AUTO, 0, false, 100000, 0) == BatchRoute::Fft);
+    }
+    // ---- runs and staging
+    const struct { size_t hop, r; } hops[] = {{64, 1}, {256, 1}, {1024, 1}, {800, 2}, {1600, 1}};
+    const size_t stage_max = 2048;
+    const std::vector<size_t> leads = {0, 777, wu, 3 * wu + 5};
+    std::vector<size_t> many(80);
+    for (size_t k = 0; k < many.size(); ++k) many[k] = stage_max - k % 3;   // more than one buffer's worth of frames
+    const std::vector<std::vector<size_t>> sets = {{300}, {0, 17}, {5, 0, stage_max, stage_max + 1, 63, 64, 65, 700, 1}, many, {0, 0}};
+    for (const auto& hr : hops) {
+        std::vector<uint64_t> hashes;
+        for (const auto& n_frames : sets) {
+            const StreamTable t = stream_table(n_frames, leads, hr.hop);
+            const std::vector<uint64_t> h = check_staging(t, hr.hop, hr.r, wu, stage_max);
+            size_t n_short = 0;
+            for (size_t n : n_frames) n_short += n > 0 && n <= stage_max && n_frames.size() > 1;
+            CHECK(h.empty() == (n_short < 2));   // (a single short stream goes as it is)
+            if (n_frames.size() == many.size()) CHECK(h.size() >= 2);
+            hashes.insert(hashes.end(), h.begin(), h.end());
+            CHECK(check_staging(t, hr.hop, hr.r, wu, 0).empty());
+        }
+        for (size_t i = 0; i < hashes.size(); ++i)   // different slot layouts, different hashes
+            for (size_t k = 0; k < i; ++k) CHECK(hashes[i] != hashes[k]);
+    }
+}
+
+// ---- block-DFT planner (blockdft_plan.cpp) ---------------------------------------------------------------------------------------
 static void check_tables(const BlockDftHostTables& t, size_t hop, uint32_t n_bins) {
     const size_t xcp = (size_t)t.n_tiles * CB_C + X_PAD_COLS, ntot = (size_t)t.n_tiles * GM_BN;
     CHECK(t.E.size() == hop * ntot && t.E16.size() == (size_t)t.n_tiles * (hop / 2) * 16);
@@ -176,8 +323,9 @@ static void check_blockdft_plan(const HostPlan& plan) {
         for (size_t k = 0; k < shorts.size(); ++k) shorts[k] = 1 + (k * 37) % 300 + (k % 7 == 0 ? 700 : 0);
         // one long stream in sub-batches (first / middle / last), 64 short unequal streams side by side, the same streams staged into one
         // buffer with slots; r = 2: every stream as two interleaved (strided) runs
-        const StreamSet sets[] = {plain_streams({20011}, r, hr.hop, plan.window_union, 8192), plain_streams(shorts, r, hr.hop, plan.window_union, 1 << 17),
-                                  staged_streams(shorts, r, hr.hop, plan.window_union)};
+        const StreamTable one = stream_table({20011}, {plan.window_union}, hr.hop), many = stream_table(shorts, {plan.window_union}, hr.hop);
+        const StreamSet sets[] = {stream_set(one, r, hr.hop, plan.window_union, false, 8192), stream_set(many, r, hr.hop, plan.window_union, false, 1 << 17),
+                                  stream_set(many, r, hr.hop, plan.window_union, true, 0)};
         for (const StreamSet& set : sets) {
             const auto launches = pack_runs(set.st.data(), set.st.size(), set.chunk);
             size_t frames = 0;
@@ -239,6 +387,7 @@ int main() {
         bin_log_frequencies(p, lnf);
         CHECK(lnf.size() == rows);
         check_blockdft_plan(plan);
+        check_batch_plan(plan, g.sr == 48000.0f && g.oct == 7);
     }
     CHECK(neg_default == 379);                       // VQT_REVIEW.md:369
     CHECK(nnz_default > 15000 && nnz_default < 20000);

@@ -1,6 +1,6 @@
 """CPU sanitizer runs ("compile CPU oracle with -fsanitize=address,undefined"; GPU AddressSanitizer is not available on
 this pool).  Two instrumented executables, built here with gcc / g++ and run once each:
-  * the product's host side — vqt_host.cpp, analysis_host.cpp, consumers_host.cpp, multi_host.cpp, blockdft_plan.cpp — behind tests/sanitize/host_main.cpp,
+  * the product's host side — vqt_host.cpp, analysis_host.cpp, consumers_host.cpp, multi_host.cpp, blockdft_plan.cpp, batch_plan.cpp — behind tests/sanitize/host_main.cpp,
     which replays the inputs of test_host_plan / test_analysis_state / test_consumers / test_multi_device and checks the
     structural invariants of the block-DFT planner's tables, tile lists and X-tile maps;
   * the oracle, oracle/pvq_oracle.c, behind tests/sanitize/oracle_main.c.
@@ -21,7 +21,7 @@ ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPT
 def test_host_side_under_asan_ubsan(tmp_path):
     csrc = os.path.join(ROOT, "pitchvis_amd", "csrc")
     exe = str(tmp_path / "host_san")
-    srcs = [os.path.join(csrc, f) for f in ("vqt_host.cpp", "analysis_host.cpp", "consumers_host.cpp", "multi_host.cpp", "blockdft_plan.cpp")]
+    srcs = [os.path.join(csrc, f) for f in ("vqt_host.cpp", "analysis_host.cpp", "consumers_host.cpp", "multi_host.cpp", "blockdft_plan.cpp", "batch_plan.cpp")]
     cmd = ["g++", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall", *SAN, "-I", csrc,
            os.path.join(ROOT, "tests", "sanitize", "host_main.cpp"), *srcs, "-o", exe]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
