@@ -475,6 +475,60 @@ void pvq_calculate_color(uint16_t buckets_per_octave, float bucket, const float 
 size_t pvq_led_frame(uint32_t n_buckets, uint16_t buckets_per_octave, const float *center, const float *size,
                      uint32_t n_peaks, const float *colors, float gray_level, float easing_pow, uint8_t *out);
 
+/* ---- what the viewer and the LED strip show, from AnalysisState alone ---------------------------------
+ * pitchvis_viewer/src/display_system/update.rs turns an AnalysisState into a spectrogram texture row (update_spectrogram_system,
+ * update.rs:929-1087, both SpectrogramModes) and twelve chroma strengths (update_chroma_system, update.rs:1090-1144);
+ * pitchvis_serial turns it into an LED frame (pvq_led_frame above).  Stateless: texture management (the ring of rows, its vertical
+ * flip, clearing the next line, the scroll offset) stays with the caller. */
+typedef enum pvq_spectrogram_mode {
+    PVQ_SPECTROGRAM_VQT = 0,   /* SpectrogramMode::VQT (update.rs:962-1004): x_vqt_smoothed, brightness against the row's maximum */
+    PVQ_SPECTROGRAM_PEAKS = 1  /* SpectrogramMode::Peaks (update.rs:1005-1065): peaks_continuous, a radius of 2 bins each */
+} pvq_spectrogram_mode;
+/* replaces the match of update_spectrogram_system (update.rs:961-1065): the RGBA row the reference writes at write_index,
+ * out_rgba [n_buckets][4].  PVQ_SPECTROGRAM_VQT reads x_vqt_smoothed [n_buckets] (center / size may be NULL); every channel is
+ * (x * 255 * 1.2).clamp(0, 255) as u8, alpha from (1 - (1 - v / (max + 0.001))^2) * 1.5 clamped to 0..1, RGB written whether or not
+ * the row has a positive maximum.  PVQ_SPECTROGRAM_PEAKS reads center / size [n_peaks] in the given order (x_vqt_smoothed may be
+ * NULL): the row starts as zeros, every peak overwrites all four bytes of the bins within 2 of its centre (floor(c - 2).max(0) ..
+ * ceil(c + 2).min(n_buckets), upper bound exclusive), alpha = brightness * exp(-d^2 / 2); the last writer wins; nothing is drawn
+ * unless the largest size is > 0.  A NaN gives bytes 0 (`as u8`), and f32::max ignores it.  colors: 12 RGB triples in [0, 1].
+ * PVQ_ERR_INVALID_ARG for an unknown mode, buckets_per_octave == 0 or a missing array. */
+pvq_status pvq_spectrogram_row(int mode, uint32_t n_buckets, uint16_t buckets_per_octave, const float *x_vqt_smoothed,
+                               const float *center, const float *size, uint32_t n_peaks, const float *colors, float gray_level,
+                               float easing_pow, uint8_t *out_rgba);
+/* replaces the chroma of update_chroma_system (update.rs:1102-1131): out12[class] = sum of 10^(x_vqt_smoothed[bin] / 10) over the
+ * bins of the pitch class ((round(bin * 12 / bpo) + bin_0_pitch_class) % 12, bin_0_pitch_class from round(12 log2(min_freq /
+ * 261.626))), summed in ascending bin order in f32, divided by the largest of the twelve when that is > 0. */
+pvq_status pvq_chroma_row(float min_freq, uint32_t n_buckets, uint16_t buckets_per_octave, const float *x_vqt_smoothed,
+                          float out12[12]);
+
+/* The same for MANY rows on the GPU: a row is one frame of one stream, the inputs are the arrays pvq_analysis_batch_outputs
+ * describes, flattened to n_rows = n_streams * n_frames, so PCM -> VQT -> AnalysisState::preprocess -> picture never leaves the
+ * device.  Same arithmetic in the same f32 operation order as the three host functions; the device's powf / expf / cosf / sinf
+ * are what may differ (a byte one level apart where a product sits on an integer, chroma to ~1e-6 relative). */
+typedef struct pvq_render_batch pvq_render_batch;
+/* per-row results, DEVICE pointers, any may be NULL */
+typedef struct pvq_render_outputs {
+    uint8_t *spectrogram_vqt;    /* [n_rows][n_bins][4]: pvq_spectrogram_row(PVQ_SPECTROGRAM_VQT); 4-byte aligned */
+    uint8_t *spectrogram_peaks;  /* [n_rows][n_bins][4]: pvq_spectrogram_row(PVQ_SPECTROGRAM_PEAKS); 4-byte aligned */
+    float *chroma;               /* [n_rows][12]: pvq_chroma_row */
+    uint8_t *led;                /* [n_rows][3 + 3 * n_bins]: the bytes of pvq_led_frame (0xFF hi lo, then triples <= 0xFE) */
+} pvq_render_outputs;
+/* One geometry (VqtRange) and one palette (update.rs:985-992 / pitchvis_serial/src/main.rs:155-160: colors NULL = pitchvis_colors::
+ * COLORS; the LED strip's own palette is SERIAL_COLORS with gray 5.0 and easing 2.3, on a handle of its own).  The arguments are
+ * checked before any device is touched; takes the bin counts pvq_analysis_batch_create takes (PVQ_ERR_UNSUPPORTED beyond);
+ * device_id < 0: a host-only handle whose rows call returns PVQ_ERR_NO_DEVICE after its argument checks. */
+pvq_status pvq_render_batch_create(int device_id, float min_freq, uint32_t octaves, uint32_t buckets_per_octave,
+                                   const float *colors, float gray_level, float easing_pow, pvq_render_batch **out);
+void pvq_render_batch_destroy(pvq_render_batch *r);
+/* update.rs:961-1065, :1102-1131 and pitchvis_serial/src/main.rs:122-175 for n_rows rows.  d_x_vqt_smoothed [n_rows][n_bins];
+ * d_center / d_size [n_rows][max_peaks] with d_peak_count [n_rows] (a count above max_peaks is taken as max_peaks) — device
+ * pointers.  Inputs an output does not read may be NULL; PVQ_ERR_INVALID_ARG for a requested output whose inputs are missing
+ * (spectrogram_vqt / chroma without x_vqt_smoothed; spectrogram_peaks / led without center, size, peak_count or with
+ * max_peaks == 0).  Asynchronous on `stream`; the handle keeps no state between calls, calls on several streams may overlap. */
+pvq_status pvq_render_batch_rows_device(pvq_render_batch *r, size_t n_rows, const float *d_x_vqt_smoothed, const float *d_center,
+                                        const float *d_size, const uint32_t *d_peak_count, uint32_t max_peaks,
+                                        const pvq_render_outputs *outs, void *stream);
+
 /* Page-locked host memory for the host-buffer entry points (pvq_vqt_calculate_batch_db, pvq_analyze_batch,
  * pvq_train_frames_db): with pageable buffers those calls are bound by staged PCIe copies (~16 GB/s); buffers from
  * here are DMA-able directly.  NULL on failure (pvq_last_error). */

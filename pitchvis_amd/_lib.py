@@ -35,6 +35,7 @@ EXPORTS = [
     "pvq_train_frames_db", "pvq_train_rows", "pvq_npy_write_f32", "pvq_stream_create", "pvq_stream_destroy",
     "pvq_stream_push", "pvq_stream_gain", "pvq_stream_chunk_size_ms", "pvq_stream_frame_db", "pvq_stream_read",
     "pvq_calculate_color", "pvq_led_frame", "pvq_host_alloc", "pvq_host_free",
+    "pvq_spectrogram_row", "pvq_chroma_row", "pvq_render_batch_create", "pvq_render_batch_destroy", "pvq_render_batch_rows_device",
     "pvq_vqt_input_status", "pvq_vqt_last_gemm_flop", "pvq_vqt_last_sclk_mhz",
     "pvq_vqt_bandwidths_3db", "pvq_vqt_warning_count", "pvq_vqt_warning",
 ]
@@ -52,6 +53,7 @@ PVQ_ERR_NONFINITE_INPUT = 9
 
 ALGO_AUTO, ALGO_FFT, ALGO_BLOCKDFT = 0, 1, 2
 GEMM_F32, GEMM_BF16X3 = 0, 1
+SPECTROGRAM_VQT, SPECTROGRAM_PEAKS = 0, 1
 
 
 class CParams(C.Structure):
@@ -82,6 +84,10 @@ class CAnalysisBatchOutputs(C.Structure):   # pvq_analysis_batch_outputs (device
     _fields_ = [(n, C.c_void_p) for n in ("x_vqt_smoothed", "x_vqt_peakfiltered", "x_vqt_afterglow", "calmness", "pitch_accuracy",
                                           "pitch_deviation", "peak_mask", "peak_count", "center", "size")] + \
                [("max_peaks", C.c_uint32), ("scene_calmness", C.c_void_p), ("tuning_grid_inaccuracy", C.c_void_p)]
+
+
+class CRenderOutputs(C.Structure):   # pvq_render_outputs (device pointers)
+    _fields_ = [(n, C.c_void_p) for n in ("spectrogram_vqt", "spectrogram_peaks", "chroma", "led")]
 
 
 class CShard(C.Structure):   # pvq_shard
@@ -234,6 +240,14 @@ def load():
     L.pvq_calculate_color.argtypes = [C.c_uint16, C.c_float, fp, C.c_float, C.c_float, fp]
     L.pvq_led_frame.argtypes = [C.c_uint32, C.c_uint16, fp, fp, C.c_uint32, fp, C.c_float, C.c_float, bp]
     L.pvq_led_frame.restype = C.c_size_t
+    L.pvq_spectrogram_row.argtypes = [C.c_int, C.c_uint32, C.c_uint16, fp, fp, fp, C.c_uint32, fp, C.c_float, C.c_float, bp]
+    L.pvq_spectrogram_row.restype = C.c_int
+    L.pvq_chroma_row.argtypes = [C.c_float, C.c_uint32, C.c_uint16, fp, fp]; L.pvq_chroma_row.restype = C.c_int
+    L.pvq_render_batch_create.argtypes = [C.c_int, C.c_float, C.c_uint32, C.c_uint32, fp, C.c_float, C.c_float, C.POINTER(vp)]
+    L.pvq_render_batch_create.restype = C.c_int
+    L.pvq_render_batch_destroy.argtypes = [vp]
+    L.pvq_render_batch_rows_device.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, C.c_uint32, C.POINTER(CRenderOutputs), vp]
+    L.pvq_render_batch_rows_device.restype = C.c_int
     L.pvq_host_alloc.argtypes = [C.c_size_t]; L.pvq_host_alloc.restype = C.c_void_p
     L.pvq_host_free.argtypes = [C.c_void_p]
     L.pvq_vqt_input_status.argtypes = [vp, vp]; L.pvq_vqt_input_status.restype = C.c_int

@@ -5,6 +5,8 @@
 * ``AgcBatch`` / ``train_dataset_streams`` — the same for many rendered streams at once (train.rs:146-163), conditioned on the device
 * ``Stream``                         — the pitchvis_audio RingBuffer contract with a device-resident ring
 * ``calculate_color`` / ``led_frame``— pitchvis_colors/src/lib.rs:86-117, pitchvis_serial/src/main.rs:122-175
+* ``spectrogram_row`` / ``chroma_row`` — pitchvis_viewer/src/display_system/update.rs:961-1065, 1102-1131 (one AnalysisState, host)
+* ``RenderBatch``                    — both, and the LED frame, for many rows at once on the device
 """
 from __future__ import annotations
 
@@ -299,3 +301,132 @@ def led_frame(n_buckets: int, buckets_per_octave: int, peaks_continuous: Sequenc
     n = _lib.load().pvq_led_frame(n_buckets, buckets_per_octave, _f(ctr), _f(sz), len(peaks_continuous), _f(colors), gray_level,
                                   easing_pow, out.ctypes.data_as(C.POINTER(C.c_uint8)))
     return out[:n].tobytes()
+
+
+SPECTROGRAM_VQT, SPECTROGRAM_PEAKS = _lib.SPECTROGRAM_VQT, _lib.SPECTROGRAM_PEAKS   # SpectrogramMode (update.rs:959-961)
+
+
+def spectrogram_row(mode: int, n_buckets: int, buckets_per_octave: int, x_vqt_smoothed=None,
+                    peaks_continuous: Sequence[Tuple[float, float]] = (), colors: np.ndarray = COLORS, gray_level: float = GRAY_LEVEL,
+                    easing_pow: float = EASING_POW) -> np.ndarray:
+    """update_spectrogram_system's match (update.rs:961-1065): the RGBA row written at write_index, uint8 ``[n_buckets][4]``.
+    SPECTROGRAM_VQT reads ``x_vqt_smoothed``, SPECTROGRAM_PEAKS ``peaks_continuous`` ((center, size) in list order).  The texture
+    ring, its flip and the clearing of the next line stay with the caller."""
+    colors = np.ascontiguousarray(colors, np.float32)
+    x = None if x_vqt_smoothed is None else np.ascontiguousarray(x_vqt_smoothed, np.float32)
+    if x is not None and x.size != n_buckets:
+        raise ValueError("x_vqt_smoothed must hold n_buckets values")
+    ctr = np.asarray([p[0] for p in peaks_continuous] or [0.0], np.float32)
+    sz = np.asarray([p[1] for p in peaks_continuous] or [0.0], np.float32)
+    out = np.zeros((n_buckets, 4), np.uint8)
+    L = _lib.load()
+    st = L.pvq_spectrogram_row(int(mode), n_buckets, buckets_per_octave, _f(x) if x is not None else None, _f(ctr), _f(sz),
+                               len(peaks_continuous), _f(colors), gray_level, easing_pow, out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if st == _lib.PVQ_ERR_INVALID_ARG:
+        raise ValueError((L.pvq_last_error() or b"").decode())
+    _check(st)
+    return out
+
+
+def chroma_row(min_freq: float, n_buckets: int, buckets_per_octave: int, x_vqt_smoothed) -> np.ndarray:
+    """update_chroma_system's chroma (update.rs:1102-1131): twelve strengths, the largest 1.0 (float32)"""
+    x = np.ascontiguousarray(x_vqt_smoothed, np.float32)
+    if x.size != n_buckets:
+        raise ValueError("x_vqt_smoothed must hold n_buckets values")
+    out = np.zeros(12, np.float32)
+    L = _lib.load()
+    st = L.pvq_chroma_row(min_freq, n_buckets, buckets_per_octave, _f(x), _f(out))
+    if st == _lib.PVQ_ERR_INVALID_ARG:
+        raise ValueError((L.pvq_last_error() or b"").decode())
+    _check(st)
+    return out
+
+
+class RenderBatch:
+    """The viewer's spectrogram row (both modes), its chroma strengths and the serial LED frame for MANY rows on the GPU
+    (pvq_render_batch_*): a row is one frame of one stream, a wavefront renders it from the fields ``AnalysisBatch`` leaves in device
+    memory.  Stateless; one geometry and one palette per object (the LED strip's own: ``colors=SERIAL_COLORS,
+    gray_level=SERIAL_GRAY_LEVEL, easing_pow=SERIAL_EASING_POW``).  ``device=None``: a host-only handle (the argument checks work;
+    rendering raises: no CPU fallback)."""
+
+    OUTPUTS = ("spectrogram_vqt", "spectrogram_peaks", "chroma", "led")
+
+    def __init__(self, range, colors: Optional[np.ndarray] = None, gray_level: float = GRAY_LEVEL, easing_pow: float = EASING_POW,
+                 device: Optional[int] = 0):
+        self._L = _lib.load()
+        self.range = range
+        self.n_bins = range.octaves * range.buckets_per_octave
+        self.device = device
+        self._h = C.c_void_p()
+        pal = None if colors is None else np.ascontiguousarray(colors, np.float32)
+        if pal is not None and pal.shape != (12, 3):
+            raise ValueError("colors: 12 RGB triples")
+        st = self._L.pvq_render_batch_create(-1 if device is None else int(device), range.min_freq, range.octaves, range.buckets_per_octave,
+                                             _f(pal) if pal is not None else None, gray_level, easing_pow, C.byref(self._h))
+        if st == _lib.PVQ_ERR_INVALID_ARG:
+            raise ValueError((self._L.pvq_last_error() or b"").decode())
+        _check(st)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._L.pvq_render_batch_destroy(h)
+            self._h = None
+
+    def output_shape(self, name: str, n_rows: int):
+        """(shape, numpy dtype) of an output for n_rows rows"""
+        return {"spectrogram_vqt": ((n_rows, self.n_bins, 4), np.uint8), "spectrogram_peaks": ((n_rows, self.n_bins, 4), np.uint8),
+                "chroma": ((n_rows, 12), np.float32), "led": ((n_rows, 3 + 3 * self.n_bins), np.uint8)}[name]
+
+    def rows_device(self, fields=None, outputs=None, *, x_vqt_smoothed=None, center=None, size=None, peak_count=None,
+                    n_rows: Optional[int] = None, max_peaks: Optional[int] = None, stream=None) -> dict:
+        """Render every row.  Inputs: torch device tensors, by keyword or as the dict ``AnalysisBatch.preprocess_device`` fills
+        (``fields``; keys ``x_vqt_smoothed``, ``center``, ``size``, ``peak_count``; leading dimensions are flattened to rows, nothing
+        is copied).  ``outputs``: a dict name -> device tensor to fill, or a sequence of names to allocate (default: every output the
+        given inputs allow).  ``n_rows`` / ``max_peaks`` default to what the tensors' shapes say (raw pointers need them).
+        Returns the dict of output tensors.  Asynchronous on ``stream``."""
+        from . import _ptr, _stream_handle
+        f = dict(fields or {})
+        x = x_vqt_smoothed if x_vqt_smoothed is not None else f.get("x_vqt_smoothed")
+        ctr = center if center is not None else f.get("center")
+        sz = size if size is not None else f.get("size")
+        cnt = peak_count if peak_count is not None else f.get("peak_count")
+        if max_peaks is None:
+            max_peaks = int(ctr.shape[-1]) if hasattr(ctr, "shape") else 0
+        if n_rows is None:
+            if hasattr(x, "numel"):
+                n_rows = x.numel() // self.n_bins
+            elif hasattr(cnt, "numel"):
+                n_rows = cnt.numel()
+            else:
+                raise ValueError("n_rows is needed with raw pointers")
+        for t, per_row in ((x, self.n_bins), (ctr, max_peaks), (sz, max_peaks), (cnt, 1)):
+            if hasattr(t, "numel"):
+                if t.numel() != n_rows * per_row or not t.is_contiguous() or t.element_size() != 4:
+                    raise ValueError("an input tensor is not contiguous 32-bit [n_rows][...]")
+        if outputs is None:
+            outputs = [n for n in self.OUTPUTS if (x is not None if n in ("spectrogram_vqt", "chroma") else
+                                                   (ctr is not None and sz is not None and cnt is not None))]
+        if not isinstance(outputs, dict):
+            import torch
+            dev = next(t.device for t in (x, ctr, cnt) if hasattr(t, "device"))
+            made = {}
+            for name in outputs:
+                shape, dt = self.output_shape(name, n_rows)
+                made[name] = torch.empty(shape, dtype=torch.uint8 if dt == np.uint8 else torch.float32, device=dev)
+            outputs = made
+        o = _lib.CRenderOutputs()
+        for name, t in outputs.items():
+            if name not in self.OUTPUTS:
+                raise ValueError(f"unknown output {name!r}")
+            if hasattr(t, "numel"):
+                shape, dt = self.output_shape(name, n_rows)
+                if t.numel() != int(np.prod(shape)) or not t.is_contiguous() or t.element_size() != np.dtype(dt).itemsize:
+                    raise ValueError(f"output {name!r} must be a contiguous {np.dtype(dt).name} tensor of shape {shape}")
+            setattr(o, name, _ptr(t))
+        st = self._L.pvq_render_batch_rows_device(self._h, int(n_rows), _ptr(x), _ptr(ctr), _ptr(sz), _ptr(cnt), int(max_peaks), C.byref(o),
+                                                  _stream_handle(stream))
+        if st == _lib.PVQ_ERR_INVALID_ARG:
+            raise ValueError((self._L.pvq_last_error() or b"").decode())
+        _check(st)
+        return outputs

@@ -15,6 +15,7 @@
 #include "condition_batch.hpp"
 #include "consumers_host.hpp"
 #include "multi_host.hpp"
+#include "render_batch.hpp"
 #include "vqt_engine.hpp"
 
 struct pvq_vqt {
@@ -31,6 +32,9 @@ struct pvq_mono_agc {
 };
 struct pvq_agc_batch {
     std::unique_ptr<pvq::AgcBatch> impl;
+};
+struct pvq_render_batch {
+    std::unique_ptr<pvq::RenderBatch> impl;
 };
 // device-resident ring: the newest buf_size samples are d_ring[w - buf_size, w); compacted when the linear
 // buffer (4 x buf_size) runs out
@@ -1027,6 +1031,64 @@ size_t pvq_led_frame(uint32_t n_buckets, uint16_t buckets_per_octave, const floa
         return pvq::led_frame(n_buckets, buckets_per_octave, center, size, n_peaks, reinterpret_cast<const float(*)[3]>(colors),
                               gray_level, easing_pow, out);
     } catch (...) { (void)translate_exception(); return 0; }
+}
+
+// pitchvis_viewer/src/display_system/update.rs:961-1065: the spectrogram row of one AnalysisState
+pvq_status pvq_spectrogram_row(int mode, uint32_t n_buckets, uint16_t buckets_per_octave, const float* x_vqt_smoothed, const float* center,
+                               const float* size, uint32_t n_peaks, const float* colors, float gray_level, float easing_pow, uint8_t* out_rgba) {
+    try {
+        if (mode != PVQ_SPECTROGRAM_VQT && mode != PVQ_SPECTROGRAM_PEAKS) {
+            pvq::set_last_error("unknown spectrogram mode");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        if (buckets_per_octave == 0 || !colors || (!out_rgba && n_buckets) || (mode == PVQ_SPECTROGRAM_VQT && !x_vqt_smoothed && n_buckets) ||
+            (mode == PVQ_SPECTROGRAM_PEAKS && n_peaks && (!center || !size))) {
+            pvq::set_last_error("spectrogram row: buckets_per_octave == 0 or a missing array");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        pvq::spectrogram_row(mode, n_buckets, buckets_per_octave, x_vqt_smoothed, center, size, n_peaks,
+                             reinterpret_cast<const float(*)[3]>(colors), gray_level, easing_pow, out_rgba);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+// update.rs:1102-1131: the chroma strengths of one AnalysisState
+pvq_status pvq_chroma_row(float min_freq, uint32_t n_buckets, uint16_t buckets_per_octave, const float* x_vqt_smoothed, float out12[12]) {
+    try {
+        if (buckets_per_octave == 0 || !out12 || (!x_vqt_smoothed && n_buckets)) {
+            pvq::set_last_error("chroma row: buckets_per_octave == 0 or a missing array");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        pvq::chroma_row(min_freq, n_buckets, buckets_per_octave, x_vqt_smoothed, out12);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+// update.rs:961-1065 + 1102-1131 and pitchvis_serial/src/main.rs:122-175 for many rows, on the device (render_batch.hpp)
+pvq_status pvq_render_batch_create(int device_id, float min_freq, uint32_t octaves, uint32_t buckets_per_octave, const float* colors,
+                                   float gray_level, float easing_pow, pvq_render_batch** out) {
+    try {
+        if (!out) return null_handle();
+        *out = nullptr;
+        std::unique_ptr<pvq::RenderBatch> impl;
+        const pvq_status st = pvq::RenderBatch::create(device_id, min_freq, octaves, buckets_per_octave, colors, gray_level, easing_pow, impl);
+        if (st != PVQ_OK) return st;
+        *out = new pvq_render_batch{std::move(impl)};
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+void pvq_render_batch_destroy(pvq_render_batch* r) {
+    try {
+        delete r;
+    } catch (...) { (void)translate_exception(); }
+}
+pvq_status pvq_render_batch_rows_device(pvq_render_batch* r, size_t n_rows, const float* d_x_vqt_smoothed, const float* d_center,
+                                        const float* d_size, const uint32_t* d_peak_count, uint32_t max_peaks, const pvq_render_outputs* outs,
+                                        void* stream) {
+    try {
+        if (!r) return null_handle();
+        const pvq_render_outputs none{};
+        return r->impl->rows_device(n_rows, d_x_vqt_smoothed, d_center, d_size, d_peak_count, max_peaks, outs ? *outs : none,
+                                    static_cast<hipStream_t>(stream));   // update.rs:961-1065, 1102-1131; main.rs:122-175
+    } catch (...) { return translate_exception(); }
 }
 
 }  // extern "C"

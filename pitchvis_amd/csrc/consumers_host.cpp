@@ -2,6 +2,8 @@
 // reference's f32 expression, operation for operation.
 #include "consumers_host.hpp"
 
+#include "color_math.hpp"
+
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -119,79 +121,35 @@ bool npy_write_f32(const char* path, const float* data, uint64_t n, std::string*
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// pitchvis_colors/src/lib.rs with the conversions of the `lab` crate (0.11.0, Cargo.lock:3985) restated:
-// sRGB (u8) <-> CIE XYZ (D65) <-> L*a*b* <-> LCh.  Not vendored in the reference tree; parity with the crate's
-// exact constants is unpinned.
+// pitchvis_colors/src/lib.rs; the conversions of the `lab` crate live in color_math.hpp (one copy for this unit and the
+// render kernels).
 // ---------------------------------------------------------------------------------------------------------
-namespace {
-constexpr float KAPPA = 24389.0f / 27.0f;
-constexpr float EPSILON = 216.0f / 24389.0f;
-constexpr float CBRT_EPSILON = 6.0f / 29.0f;
-constexpr float S_0 = 0.003130668442500564f;
-constexpr float E_0_255 = 3294.6f * S_0;
-constexpr float WHITE_X = 0.9504492182750991f;
-constexpr float WHITE_Z = 1.0889166484304715f;
+using color::sat_u8;
 
-inline float srgb_expand(float c) {   // c in 0..255
-    if (c > E_0_255) return std::pow((c + 0.055f * 255.0f) / (1.055f * 255.0f), 2.4f);
-    return c / (12.92f * 255.0f);
+void palette_lch(const float colors[12][3], float out_lch[12][3]) {
+    for (int t = 0; t < 12; ++t) {
+        uint8_t base[3];
+        for (int i = 0; i < 3; ++i) base[i] = sat_u8(colors[t][i] * 255.0f);                   // lib.rs:94-95
+        color::rgb_to_lch(base, out_lch[t][0], out_lch[t][1], out_lch[t][2]);                  // lib.rs:98
+    }
 }
-inline float srgb_compress(float c) {
-    const float v = (c > S_0) ? 1.055f * std::pow(c, 1.0f / 2.4f) - 0.055f : 12.92f * c;
-    return std::fmax(std::fmin(v, 1.0f), 0.0f);
-}
-inline float lab_map(float c) { return (c > EPSILON) ? std::pow(c, 1.0f / 3.0f) : (KAPPA * c + 16.0f) / 116.0f; }
 
-void rgb_to_lch(const uint8_t rgb[3], float& l, float& c, float& h) {
-    const float r = srgb_expand(static_cast<float>(rgb[0])), g = srgb_expand(static_cast<float>(rgb[1])),
-                b = srgb_expand(static_cast<float>(rgb[2]));
-    const float x = r * 0.4124108464885388f + g * 0.3575845678529519f + b * 0.18045380393360833f;
-    const float y = r * 0.21264934272065283f + g * 0.7151691357059038f + b * 0.07218152157344333f;
-    const float z = r * 0.019331758429150258f + g * 0.11919485595098397f + b * 0.9503900340503373f;
-    const float fx = lab_map(x / WHITE_X), fy = lab_map(y), fz = lab_map(z / WHITE_Z);
-    l = (116.0f * fy) - 16.0f;
-    const float a = 500.0f * (fx - fy), bb = 200.0f * (fy - fz);
-    c = std::hypot(a, bb);
-    h = std::atan2(bb, a);
+void calculate_color_u8(uint16_t buckets_per_octave, float bucket, const float colors[12][3], float gray_level, float easing_pow,
+                        uint8_t rgb[3]) {
+    uint32_t idx;
+    float inaccuracy_cents;
+    color::tone_of_bucket(buckets_per_octave, bucket, idx, inaccuracy_cents);                  // lib.rs:93-96
+    uint8_t base[3];
+    for (int i = 0; i < 3; ++i) base[i] = sat_u8(colors[idx][i] * 255.0f);                     // lib.rs:94-95
+    float l, c, h;
+    color::rgb_to_lch(base, l, c, h);                                                          // lib.rs:98
+    color::lch_color_u8(l, c, h, inaccuracy_cents, gray_level, easing_pow, rgb);               // lib.rs:104-108
 }
-void lch_to_rgb(float l, float c, float h, uint8_t rgb[3]) {
-    const float a = c * std::cos(h), bb = c * std::sin(h);
-    const float fy = (l + 16.0f) / 116.0f;
-    const float fx = (a / 500.0f) + fy;
-    const float fz = fy - (bb / 200.0f);
-    const float xr = (fx > CBRT_EPSILON) ? fx * fx * fx : ((fx * 116.0f) - 16.0f) / KAPPA;
-    const float yr = (l > EPSILON * KAPPA) ? fy * fy * fy : l / KAPPA;
-    const float zr = (fz > CBRT_EPSILON) ? fz * fz * fz : ((fz * 116.0f) - 16.0f) / KAPPA;
-    const float x = xr * WHITE_X, y = yr, z = zr * WHITE_Z;
-    const float r = x * 3.240812398895283f - y * 1.5373084456298136f - z * 0.4985865229069666f;
-    const float g = x * -0.9692430170086407f + y * 1.8759663029085742f + z * 0.04155503085668564f;
-    const float b = x * 0.055638398436112804f - y * 0.20400746093241362f + z * 1.0571295702861434f;
-    rgb[0] = static_cast<uint8_t>(std::round(srgb_compress(r) * 255.0f));
-    rgb[1] = static_cast<uint8_t>(std::round(srgb_compress(g) * 255.0f));
-    rgb[2] = static_cast<uint8_t>(std::round(srgb_compress(b) * 255.0f));
-}
-inline uint8_t sat_u8(float v) {   // Rust `as u8`: saturating, NaN -> 0, truncation toward zero
-    if (!(v > 0.0f)) return 0;
-    if (v >= 255.0f) return 255;
-    return static_cast<uint8_t>(v);
-}
-}  // namespace
 
 void calculate_color(uint16_t buckets_per_octave, float bucket, const float colors[12][3], float gray_level, float easing_pow,
                      float out_rgb[3]) {
-    const float pitch_continuous = 12.0f * bucket / static_cast<float>(buckets_per_octave);   // lib.rs:93
-    const float rounded = std::round(pitch_continuous);
-    const size_t idx = static_cast<size_t>(rounded < 0.0f ? 0.0f : rounded) % 12;             // `as usize` saturates at 0
-    uint8_t base[3];
-    for (int i = 0; i < 3; ++i) base[i] = sat_u8(colors[idx][i] * 255.0f);                     // lib.rs:94-95
-    const float inaccuracy_cents = std::fabs(pitch_continuous - rounded);                      // lib.rs:96
-    float l, c, h;
-    rgb_to_lch(base, l, c, h);                                                                 // lib.rs:98
-    const float saturation = 1.0f - std::pow(2.0f * inaccuracy_cents, easing_pow);             // lib.rs:104
-    c *= saturation;                                                                           // lib.rs:105
-    l = saturation * l + (1.0f - saturation) * gray_level;                                     // lib.rs:106
     uint8_t rgb[3];
-    lch_to_rgb(l, c, h, rgb);                                                                  // lib.rs:108
+    calculate_color_u8(buckets_per_octave, bucket, colors, gray_level, easing_pow, rgb);
     for (int i = 0; i < 3; ++i) out_rgb[i] = static_cast<float>(rgb[i]) / 255.0f;
 }
 
@@ -229,6 +187,85 @@ size_t led_frame(uint32_t n_buckets, uint16_t buckets_per_octave, const float* c
         for (int i = 0; i < 3; ++i) out[o++] = sat_u8((rgb[i] * color_coefficient) * 254.0f);   // main.rs:163-167
     }
     return o;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// pitchvis_viewer/src/display_system/update.rs: the per-frame products that depend on AnalysisState alone
+// ---------------------------------------------------------------------------------------------------------
+void spectrogram_row(int mode, uint32_t n_buckets, uint16_t buckets_per_octave, const float* x_vqt_smoothed, const float* center,
+                     const float* size, uint32_t n_peaks, const float colors[12][3], float gray_level, float easing_pow, uint8_t* out_rgba) {
+    using color::brightness_of;
+    using color::texel_u8;
+    const float bpo = static_cast<float>(buckets_per_octave);
+    const float semitone_offset = static_cast<float>(buckets_per_octave - 3u * (buckets_per_octave / 12u));   // update.rs:982-984
+    if (mode == 0) {   // SpectrogramMode::VQT, update.rs:962-1004
+        float max_val = 0.0f;
+        for (uint32_t i = 0; i < n_buckets; ++i) max_val = std::fmax(max_val, x_vqt_smoothed[i]);   // update.rs:967 (f32::max ignores a NaN)
+        for (uint32_t bin = 0; bin < n_buckets; ++bin) {
+            const float value_db = x_vqt_smoothed[bin];
+            float brightness = 0.0f;
+            if (max_val > 0.0f) {                                                   // update.rs:974-979
+                const float normalized = value_db / (max_val + 0.001f);
+                brightness = brightness_of(1.0f - normalized);
+            }
+            uint8_t rgb[3];
+            calculate_color_u8(buckets_per_octave, std::fmod(static_cast<float>(bin) + semitone_offset, bpo), colors, gray_level,
+                               easing_pow, rgb);                                    // update.rs:985-992
+            uint8_t* px = out_rgba + 4 * static_cast<size_t>(bin);
+            for (int i = 0; i < 3; ++i) px[i] = texel_u8(static_cast<float>(rgb[i]) / 255.0f);   // update.rs:998-1000
+            px[3] = texel_u8(brightness);                                           // update.rs:1001
+        }
+        return;
+    }
+    // SpectrogramMode::Peaks, update.rs:1005-1065
+    std::memset(out_rgba, 0, 4 * static_cast<size_t>(n_buckets));                   // (the line was cleared a frame ago, update.rs:1068-1078)
+    float max_size = 0.0f;
+    for (uint32_t p = 0; p < n_peaks; ++p) max_size = std::fmax(max_size, size[p]); // update.rs:1010-1014
+    if (!(max_size > 0.0f)) return;                                                 // update.rs:1016
+    const float width = static_cast<float>(n_buckets);
+    for (uint32_t p = 0; p < n_peaks; ++p) {
+        const float c = center[p];
+        const float brightness = brightness_of(1.0f - size[p] / max_size);          // update.rs:1022-1023
+        uint8_t rgb[3];
+        calculate_color_u8(buckets_per_octave, std::fmod(c + semitone_offset, bpo), colors, gray_level, easing_pow, rgb);   // update.rs:1029-1035
+        // update.rs:1038-1039; `as usize` saturates and maps NaN to 0, f32::max / min ignore a NaN
+        const float lo_f = std::fmax(std::floor(c - 2.0f), 0.0f), hi_f = std::fmin(std::ceil(c + 2.0f), width);
+        const uint32_t lo = lo_f >= width ? n_buckets : static_cast<uint32_t>(lo_f);
+        const uint32_t hi = hi_f > 0.0f ? static_cast<uint32_t>(hi_f) : 0u;
+        for (uint32_t bin = lo; bin < hi; ++bin) {                                  // update.rs:1041-1062
+            const float distance = std::fabs(static_cast<float>(bin) - c);
+            if (distance <= 2.0f) {
+                const float falloff = std::exp(-distance * distance / (2.0f * 2.0f * 0.5f));
+                uint8_t* px = out_rgba + 4 * static_cast<size_t>(bin);
+                for (int i = 0; i < 3; ++i) px[i] = texel_u8(static_cast<float>(rgb[i]) / 255.0f);
+                px[3] = texel_u8(brightness * falloff);
+            }
+        }
+    }
+}
+
+int chroma_bin_0_pitch_class(float min_freq) {   // update.rs:1108-1110
+    const float semitones_from_c4 = 12.0f * std::log2(min_freq / 261.626f);
+    const float r = std::round(semitones_from_c4);
+    const int ri = !(r == r) ? 0 : (r >= 2147483648.0f ? 2147483647 : (r <= -2147483648.0f ? -2147483647 - 1 : static_cast<int>(r)));   // `as i32`
+    return ((ri % 12) + 12) % 12;
+}
+
+uint32_t chroma_pitch_class(uint32_t bin, uint16_t buckets_per_octave, int bin_0_pitch_class) {   // update.rs:1115-1118
+    const float semitone = std::round(static_cast<float>(bin * 12u) / static_cast<float>(buckets_per_octave));
+    return static_cast<uint32_t>((static_cast<int>(semitone) + bin_0_pitch_class) % 12);
+}
+
+void chroma_row(float min_freq, uint32_t n_buckets, uint16_t buckets_per_octave, const float* x_vqt_smoothed, float out12[12]) {
+    const int bin_0 = chroma_bin_0_pitch_class(min_freq);
+    float chroma[12] = {0.0f};                                                      // update.rs:1103
+    for (uint32_t bin = 0; bin < n_buckets; ++bin) {                                // update.rs:1112-1123
+        const float power = std::pow(10.0f, x_vqt_smoothed[bin] / 10.0f);
+        chroma[chroma_pitch_class(bin, buckets_per_octave, bin_0)] += power;
+    }
+    float max_chroma = 0.0f;
+    for (int k = 0; k < 12; ++k) max_chroma = std::fmax(max_chroma, chroma[k]);     // update.rs:1126
+    for (int k = 0; k < 12; ++k) out12[k] = max_chroma > 0.0f ? chroma[k] / max_chroma : chroma[k];   // update.rs:1127-1131
 }
 
 }  // namespace pvq

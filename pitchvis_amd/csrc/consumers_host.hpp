@@ -61,4 +61,21 @@ void calculate_color(uint16_t buckets_per_octave, float bucket, const float colo
 size_t led_frame(uint32_t n_buckets, uint16_t buckets_per_octave, const float* center, const float* size, uint32_t n_peaks,
                  const float colors[12][3], float gray_level, float easing_pow, uint8_t* out);
 
+// the same with the u8 triple lch_to_rgb leaves (lib.rs:108), before the division by 255 of lib.rs:110-114
+void calculate_color_u8(uint16_t buckets_per_octave, float bucket, const float colors[12][3], float gray_level, float easing_pow,
+                        uint8_t rgb[3]);
+// lib.rs:94-98 for every palette entry: (L, C, h) of the entry as u8
+void palette_lch(const float colors[12][3], float out_lch[12][3]);
+
+// pitchvis_viewer/src/display_system/update.rs:961-1065: the RGBA row the viewer writes at write_index; the texture ring, its
+// vertical flip and the clearing of the next line stay with the caller.  mode 0: SpectrogramMode::VQT (reads x_vqt_smoothed),
+// 1: SpectrogramMode::Peaks (reads center / size, AnalysisState::peaks_continuous, in list order).  out_rgba [n_buckets][4].
+void spectrogram_row(int mode, uint32_t n_buckets, uint16_t buckets_per_octave, const float* x_vqt_smoothed, const float* center,
+                     const float* size, uint32_t n_peaks, const float colors[12][3], float gray_level, float easing_pow, uint8_t* out_rgba);
+
+// update.rs:1102-1131: per-pitch-class power of the smoothed row, summed in ascending bin order, divided by its maximum
+int chroma_bin_0_pitch_class(float min_freq);                                                          // update.rs:1108-1110
+uint32_t chroma_pitch_class(uint32_t bin, uint16_t buckets_per_octave, int bin_0_pitch_class);         // update.rs:1115-1118
+void chroma_row(float min_freq, uint32_t n_buckets, uint16_t buckets_per_octave, const float* x_vqt_smoothed, float out12[12]);
+
 }  // namespace pvq
