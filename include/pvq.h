@@ -529,6 +529,69 @@ pvq_status pvq_render_batch_rows_device(pvq_render_batch *r, size_t n_rows, cons
                                         const float *d_size, const uint32_t *d_peak_count, uint32_t max_peaks,
                                         const pvq_render_outputs *outs, void *stream);
 
+/* The note model the dataset of pitchvis_train exists for (pitchvis_train/train.py:67-99), which the viewer runs per rendered frame
+ * through TorchScript on a CUDA device (pitchvis_viewer/src/ml_system.rs:24-69): a window of t_frames consecutive dB frames,
+ * flattened to L = t_frames * n_bins values -> Conv1d(1, 16, kernel 5, stride 2, no padding) -> ReLU -> max_pool1d(2) -> flatten
+ * (channel-major: feature c * O_pool + p) -> Linear(n_features, mlp_size) -> ReLU -> mlp_layers x (Linear(mlp_size, mlp_size) ->
+ * ReLU) -> Linear(mlp_size, 128) -> sigmoid.  O_conv = (L - 5) / 2 + 1, O_pool = O_conv / 2 (integer divisions: an odd O_conv
+ * loses its last position, as max_pool1d does), n_features = 16 * O_pool.  All arithmetic is f32 (the reference's "TODO: Half"
+ * is not taken up). */
+typedef struct pvq_note_model pvq_note_model;
+/* replaces the constructor arguments of train.py:67-75 (kernel_size 5, stride 2, 16 channels, pool 2 and 128 outputs are fixed, as
+ * in train.py:75,90 and ml_system.rs:7).  n_bins 3 .. 1024; t_frames 1 .. 8 with t_frames * n_bins >= 8; mlp_size a multiple of 16
+ * in 16 .. 4096; mlp_layers 0 .. 8 */
+typedef struct pvq_note_model_params {
+    uint32_t n_bins;     /* train.py:14 n_bins / ml_system.rs: the VqtRange's bucket count */
+    uint32_t t_frames;   /* train.py:15 T (5); 3 in the viewer */
+    uint32_t mlp_size;   /* train.py:69 mlp_size (1024) */
+    uint32_t mlp_layers; /* train.py:69 mlp_layers (2) */
+} pvq_note_model_params;
+/* replaces the module's state_dict (train.py:205-208 saves it inside a TorchScript file): HOST pointers to f32 arrays in PyTorch's
+ * layout.  layer_weight / layer_bias are arrays of mlp_layers pointers (may be NULL when mlp_layers == 0) */
+typedef struct pvq_note_model_weights {
+    const float *conv_weight;          /* conv1.weight [16][1][5] */
+    const float *conv_bias;            /* conv1.bias [16] */
+    const float *fc1_weight;           /* fc1.weight [mlp_size][n_features] */
+    const float *fc1_bias;             /* fc1.bias [mlp_size] */
+    const float *const *layer_weight;  /* layers.i.weight [mlp_size][mlp_size] */
+    const float *const *layer_bias;    /* layers.i.bias [mlp_size] */
+    const float *output_weight;        /* output.weight [128][mlp_size] */
+    const float *output_bias;          /* output.bias [128] */
+} pvq_note_model_weights;
+/* per-row results of pvq_note_model_rows_device, DEVICE pointers, any may be NULL */
+typedef struct pvq_note_model_outputs {
+    float *d_prob;     /* [n_streams][stride_frames][128]: AnalysisState::ml_midi_base_pitches (ml_system.rs:56-59) */
+    float *d_logits;   /* [n_streams][stride_frames][128]: the same before the sigmoid */
+    uint32_t *d_mask;  /* [n_streams][stride_frames][4]: bit k (word k / 32, bit k % 32) set when logit_k > 0, the pitches
+                          ml_system.rs:61-65 reports (p > 0.5); 4-byte aligned */
+} pvq_note_model_outputs;
+/* replaces NoteModel.__init__ + load_state_dict (train.py:67-87) / tch::CModule::load_on_device (ml_system.rs:13-20).  The sizes
+ * are checked before any device is touched (PVQ_ERR_INVALID_ARG for a null pointer, a zero field or an mlp_size that is no
+ * multiple of 16, PVQ_ERR_UNSUPPORTED for a value beyond the ranges above).  The weights are copied; every dense matrix is
+ * repacked once on the host into the order the kernels' matrix instructions read.  device_id < 0: a host-only handle
+ * (pvq_note_model_infer works, pvq_note_model_rows_device returns PVQ_ERR_NO_DEVICE after its argument checks). */
+pvq_status pvq_note_model_create(int device_id, const pvq_note_model_params *params, const pvq_note_model_weights *weights,
+                                 pvq_note_model **out);
+void pvq_note_model_destroy(pvq_note_model *m);
+/* the derived sizes: out4 = { L, O_conv, O_pool, n_features } */
+pvq_status pvq_note_model_sizes(const pvq_note_model *m, uint32_t out4[4]);
+/* replaces ml_system.rs::infer (ml_system.rs:24-69) for one row, on the host in plain f32: window_host [L] (t_frames frames, oldest
+ * first) -> out_prob [128].  Works on a host-only handle.  The one-row face beside pvq_note_model_rows_device, as
+ * pvq_spectrogram_row is beside pvq_render_batch_rows_device. */
+pvq_status pvq_note_model_infer(const pvq_note_model *m, const float *window_host, float out_prob[128]);
+/* The same for MANY rows on the GPU.  d_db is [n_streams][stride_frames][n_bins] (DEVICE), exactly what
+ * pvq_vqt_calculate_batch_db_streams writes; n_frames is a HOST array of n_streams frame counts (each <= stride_frames; NULL: every
+ * stream has stride_frames).  Row (s, f) is the model on frames f - t_frames + 1 .. f of stream s, one contiguous run of L floats:
+ * train.py:120-131's window_data with the label aligned to the last frame.  Rows with f < t_frames - 1 or f >= n_frames[s] are
+ * written as zeros in every output.  A row whose window holds a non-finite dB value has unspecified values in that row only.
+ * Asynchronous on `stream`; hidden activations live in a grow-only workspace of the handle (no allocation on the call path once
+ * it has grown), so one handle serves one stream at a time. */
+pvq_status pvq_note_model_rows_device(pvq_note_model *m, const float *d_db, const size_t *n_frames, uint32_t n_streams,
+                                      size_t stride_frames, const pvq_note_model_outputs *outs, void *stream);
+/* Upper bound in bytes for that workspace (default 256 MiB): a call processes its rows in chunks of whole 128-row tiles that fit;
+ * results do not depend on the chunking.  One tile (1 KiB * mlp_size + its table entry) is the least a call works with. */
+pvq_status pvq_note_model_set_workspace_limit(pvq_note_model *m, uint64_t bytes);
+
 /* Page-locked host memory for the host-buffer entry points (pvq_vqt_calculate_batch_db, pvq_analyze_batch,
  * pvq_train_frames_db): with pageable buffers those calls are bound by staged PCIe copies (~16 GB/s); buffers from
  * here are DMA-able directly.  NULL on failure (pvq_last_error). */

@@ -36,6 +36,8 @@ EXPORTS = [
     "pvq_stream_push", "pvq_stream_gain", "pvq_stream_chunk_size_ms", "pvq_stream_frame_db", "pvq_stream_read",
     "pvq_calculate_color", "pvq_led_frame", "pvq_host_alloc", "pvq_host_free",
     "pvq_spectrogram_row", "pvq_chroma_row", "pvq_render_batch_create", "pvq_render_batch_destroy", "pvq_render_batch_rows_device",
+    "pvq_note_model_create", "pvq_note_model_destroy", "pvq_note_model_sizes", "pvq_note_model_infer", "pvq_note_model_rows_device",
+    "pvq_note_model_set_workspace_limit",
     "pvq_vqt_input_status", "pvq_vqt_last_gemm_flop", "pvq_vqt_last_sclk_mhz",
     "pvq_vqt_bandwidths_3db", "pvq_vqt_warning_count", "pvq_vqt_warning",
 ]
@@ -88,6 +90,21 @@ class CAnalysisBatchOutputs(C.Structure):   # pvq_analysis_batch_outputs (device
 
 class CRenderOutputs(C.Structure):   # pvq_render_outputs (device pointers)
     _fields_ = [(n, C.c_void_p) for n in ("spectrogram_vqt", "spectrogram_peaks", "chroma", "led")]
+
+
+class CNoteModelParams(C.Structure):   # pvq_note_model_params
+    _fields_ = [(n, C.c_uint32) for n in ("n_bins", "t_frames", "mlp_size", "mlp_layers")]
+
+
+class CNoteModelWeights(C.Structure):   # pvq_note_model_weights (host pointers)
+    _fields_ = [("conv_weight", C.POINTER(C.c_float)), ("conv_bias", C.POINTER(C.c_float)), ("fc1_weight", C.POINTER(C.c_float)),
+                ("fc1_bias", C.POINTER(C.c_float)), ("layer_weight", C.POINTER(C.POINTER(C.c_float))),
+                ("layer_bias", C.POINTER(C.POINTER(C.c_float))), ("output_weight", C.POINTER(C.c_float)),
+                ("output_bias", C.POINTER(C.c_float))]
+
+
+class CNoteModelOutputs(C.Structure):   # pvq_note_model_outputs (device pointers)
+    _fields_ = [(n, C.c_void_p) for n in ("d_prob", "d_logits", "d_mask")]
 
 
 class CShard(C.Structure):   # pvq_shard
@@ -248,6 +265,14 @@ def load():
     L.pvq_render_batch_destroy.argtypes = [vp]
     L.pvq_render_batch_rows_device.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, C.c_uint32, C.POINTER(CRenderOutputs), vp]
     L.pvq_render_batch_rows_device.restype = C.c_int
+    L.pvq_note_model_create.argtypes = [C.c_int, C.POINTER(CNoteModelParams), C.POINTER(CNoteModelWeights), C.POINTER(vp)]
+    L.pvq_note_model_create.restype = C.c_int
+    L.pvq_note_model_destroy.argtypes = [vp]
+    L.pvq_note_model_sizes.argtypes = [vp, up]; L.pvq_note_model_sizes.restype = C.c_int
+    L.pvq_note_model_infer.argtypes = [vp, fp, fp]; L.pvq_note_model_infer.restype = C.c_int
+    L.pvq_note_model_rows_device.argtypes = [vp, vp, szp, C.c_uint32, C.c_size_t, C.POINTER(CNoteModelOutputs), vp]
+    L.pvq_note_model_rows_device.restype = C.c_int
+    L.pvq_note_model_set_workspace_limit.argtypes = [vp, C.c_uint64]; L.pvq_note_model_set_workspace_limit.restype = C.c_int
     L.pvq_host_alloc.argtypes = [C.c_size_t]; L.pvq_host_alloc.restype = C.c_void_p
     L.pvq_host_free.argtypes = [C.c_void_p]
     L.pvq_vqt_input_status.argtypes = [vp, vp]; L.pvq_vqt_input_status.restype = C.c_int

@@ -15,6 +15,7 @@
 #include "condition_batch.hpp"
 #include "consumers_host.hpp"
 #include "multi_host.hpp"
+#include "note_model.hpp"
 #include "render_batch.hpp"
 #include "vqt_engine.hpp"
 
@@ -35,6 +36,9 @@ struct pvq_agc_batch {
 };
 struct pvq_render_batch {
     std::unique_ptr<pvq::RenderBatch> impl;
+};
+struct pvq_note_model {
+    std::unique_ptr<pvq::NoteModel> impl;
 };
 // device-resident ring: the newest buf_size samples are d_ring[w - buf_size, w); compacted when the linear
 // buffer (4 x buf_size) runs out
@@ -1088,6 +1092,58 @@ pvq_status pvq_render_batch_rows_device(pvq_render_batch* r, size_t n_rows, cons
         const pvq_render_outputs none{};
         return r->impl->rows_device(n_rows, d_x_vqt_smoothed, d_center, d_size, d_peak_count, max_peaks, outs ? *outs : none,
                                     static_cast<hipStream_t>(stream));   // update.rs:961-1065, 1102-1131; main.rs:122-175
+    } catch (...) { return translate_exception(); }
+}
+
+// pitchvis_train/train.py:67-99 as pitchvis_viewer/src/ml_system.rs:24-69 runs it: one row on the host, many rows on the device (note_model.hpp)
+pvq_status pvq_note_model_create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights, pvq_note_model** out) {
+    try {
+        if (!out) return null_handle();
+        *out = nullptr;
+        std::unique_ptr<pvq::NoteModel> impl;
+        const pvq_status st = pvq::NoteModel::create(device_id, params, weights, impl);
+        if (st != PVQ_OK) return st;
+        *out = new pvq_note_model{std::move(impl)};
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+void pvq_note_model_destroy(pvq_note_model* m) {
+    try {
+        delete m;
+    } catch (...) { (void)translate_exception(); }
+}
+pvq_status pvq_note_model_sizes(const pvq_note_model* m, uint32_t out4[4]) {
+    try {
+        if (!m || !out4) return null_handle();
+        const pvq::NoteModelDims& d = m->impl->dims();
+        out4[0] = d.L; out4[1] = d.o_conv; out4[2] = d.o_pool; out4[3] = d.n_features;
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_note_model_infer(const pvq_note_model* m, const float* window_host, float out_prob[128]) {
+    try {
+        if (!m) return null_handle();
+        if (!window_host || !out_prob) {
+            pvq::set_last_error("note model: null window or output");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        m->impl->infer(window_host, out_prob);   // ml_system.rs:24-69
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_note_model_rows_device(pvq_note_model* m, const float* d_db, const size_t* n_frames, uint32_t n_streams, size_t stride_frames,
+                                      const pvq_note_model_outputs* outs, void* stream) {
+    try {
+        if (!m) return null_handle();
+        const pvq_note_model_outputs none{};
+        return m->impl->rows_device(d_db, n_frames, n_streams, stride_frames, outs ? *outs : none, static_cast<hipStream_t>(stream));
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_note_model_set_workspace_limit(pvq_note_model* m, uint64_t bytes) {
+    try {
+        if (!m) return null_handle();
+        m->impl->set_workspace_limit(bytes);
+        return PVQ_OK;
     } catch (...) { return translate_exception(); }
 }
 

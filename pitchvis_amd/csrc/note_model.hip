@@ -1,0 +1,456 @@
+// note_model.hip — see note_model.hpp.
+//
+// Both kernels are one GEMM shape.  A workgroup of 4 waves owns a tile of NM_BM = 128 rows x NM_BN = 64 columns; wave w owns rows
+// 32 w .. 32 w + 31 (two 16-row MFMA tiles) and ALL 64 columns (four 16-column strips): 8 accumulator tiles, 32 registers.  K is
+// walked in stages of NM_PC = 4 chunks of 16: the stage's B operand (16 KiB, host-packed so that lane l's float4 of strip s holds the
+// operands of the chunk's four v_mfma_f32_16x16x4_f32) is copied global -> registers -> LDS one stage ahead, double buffered, one
+// barrier per stage; 32 KiB of LDS, two workgroups per CU.  The A operand never touches LDS: lane l (row l & 15, k group g = l >> 4)
+// holds k = 4 g .. 4 g + 3 of the chunk as one float4,
+//   nm_conv_fc1: computed — the chunk is pooled position p, k = channel, so the lane evaluates channels 4 g .. 4 g + 3 of
+//                max(conv[2 p], conv[2 p + 1], 0) from x[4 p .. 4 p + 6] of its row's window, which it keeps in registers (19 per
+//                stage per row tile, 16 new ones fetched a stage ahead);
+//   nm_dense:    one 16-byte load from the [rows][K] activation, fetched a stage ahead.
+// A row's result depends on its window alone: the k order, the accumulator it meets and the instruction sequence are the same
+// wherever the row sits (tile, wave, lane, chunk of the call), so equal windows give equal bits.
+#include "note_model.hpp"
+
+#include <algorithm>
+#include <string>
+
+#include "vqt_engine.hpp"
+
+namespace pvq {
+
+#define PVQ_HIP(call)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (call);                                                                    \
+        if (e_ != hipSuccess) {                                                                    \
+            set_last_error(std::string(#call) + " failed: " + hipGetErrorString(e_));              \
+            return PVQ_ERR_DEVICE;                                                                 \
+        }                                                                                          \
+    } while (0)
+
+namespace {
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+constexpr int NM_THREADS = 256;
+constexpr int CHUNK_F4 = NM_BN * NM_KC / 4;    // float4 of one chunk of the packed B operand (4 strips x 64 lanes)
+constexpr int STAGE_F4 = NM_PC * CHUNK_F4;     // ... of one stage
+constexpr int STAGE_LD = STAGE_F4 / NM_THREADS;   // float4 per thread per stage
+constexpr int X_STAGE = 4 * NM_PC;             // new window values per stage and row
+constexpr int X_REGS = X_STAGE + 3;            // positions 4 p0 .. 4 p0 + 4 NM_PC + 2
+static_assert(STAGE_F4 % NM_THREADS == 0, "the stage copy is whole float4 per thread");
+static_assert(sizeof(NmTile) == 16, "NmTile is read as laid out in note_model_plan.hpp");
+
+struct NmArgs {
+    const NmTile* tiles;     // this launch's tiles
+    const float* db;         // nm_conv_fc1: [n_streams][stride_frames][n_bins]
+    const float* conv;       // nm_conv_fc1: conv weights [16][5], bias [16]
+    const float* a_in;       // nm_dense: [tiles * 128][k]
+    const float4* b_packed;  // [column tiles][stages * NM_PC chunks][CHUNK_F4]
+    const float* bias;       // [n]
+    float* h_out;            // ACT 0: [tiles * 128][n]
+    float* prob;             // ACT 1: [n_streams][stride_frames][128], may be null
+    float* logits;           //        the same
+    uint32_t* mask;          //        [n_streams][stride_frames][4], may be null
+    size_t stride_frames;
+    uint32_t n_bins, t_frames, L;
+    uint32_t chunks;         // K / 16: pooled positions (nm_conv_fc1), k / 16 (nm_dense)
+    uint32_t k, n;           // nm_dense: row length of a_in; columns of the product
+    uint32_t n_ct;           // column tiles
+};
+
+__device__ __forceinline__ void stage_fetch(const float4* __restrict__ src4, f32x4 (&r)[STAGE_LD]) {
+    const f32x4* src = reinterpret_cast<const f32x4*>(src4);
+#pragma unroll
+    for (int j = 0; j < STAGE_LD; ++j) r[j] = src[threadIdx.x + NM_THREADS * j];
+}
+__device__ __forceinline__ void stage_put(float4* dst4, const f32x4 (&r)[STAGE_LD]) {
+    f32x4* dst = reinterpret_cast<f32x4*>(dst4);
+#pragma unroll
+    for (int j = 0; j < STAGE_LD; ++j) dst[threadIdx.x + NM_THREADS * j] = r[j];
+}
+
+// acc[t][s] += a[t] (16 rows x 16 k) * chunk (16 k x 16 columns of strip s); consecutive instructions meet different accumulators
+__device__ __forceinline__ void chunk_mfma(const float4* chunk, int lane, const float4 (&a)[2], f32x4 (&acc)[2][4]) {
+    float4 b[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) b[s] = chunk[s * 64 + lane];
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) acc[t][s] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].x, b[s].x, acc[t][s], 0, 0, 0);
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) acc[t][s] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].y, b[s].y, acc[t][s], 0, 0, 0);
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) acc[t][s] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].z, b[s].z, acc[t][s], 0, 0, 0);
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) acc[t][s] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].w, b[s].w, acc[t][s], 0, 0, 0);
+}
+
+// ACT 0: ReLU(acc + bias) -> h_out.  ACT 1: logits, sigmoid and mask of the valid rows.  Accumulator layout of the 16x16 tile: lane l
+// holds column l & 15, rows 4 (l >> 4) + reg.
+template <int ACT>
+__device__ __forceinline__ void epilogue(const NmArgs& a, const NmTile tile, uint32_t tile_local, uint32_t ct, int wave, int lane,
+                                         const f32x4 (&acc)[2][4]) {
+    const int g = lane >> 4, c = lane & 15;
+    float bias[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const uint32_t col = NM_BN * ct + 16 * s + c;
+        bias[s] = col < a.n ? a.bias[col] : 0.0f;
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const uint32_t r = 32 * wave + 16 * t + 4 * g + reg;   // row of the tile
+            if constexpr (ACT == 0) {
+                float* dst = a.h_out + (static_cast<size_t>(tile_local) * NM_BM + r) * a.n;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const uint32_t col = NM_BN * ct + 16 * s + c;
+                    if (col < a.n) dst[col] = fmaxf(acc[t][s][reg] + bias[s], 0.0f);
+                }
+            } else {
+                float logit[4];
+                unsigned long long bal[4];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    logit[s] = acc[t][s][reg] + bias[s];
+                    bal[s] = __ballot(logit[s] > 0.0f);   // bits 16 g' .. 16 g' + 15: row 4 g' + reg, the strip's 16 columns
+                }
+                if (r < tile.n_valid) {
+                    const size_t row = static_cast<size_t>(tile.stream) * a.stride_frames + tile.f0 + r;
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        const size_t at = row * NM_OUT + NM_BN * ct + 16 * s + c;
+                        if (a.logits) a.logits[at] = logit[s];
+                        if (a.prob) a.prob[at] = 1.0f / (1.0f + expf(-logit[s]));
+                    }
+                    if (a.mask && c < 2) {   // lane c of the row's group writes word c of this column tile's two
+                        const unsigned long long lo = c == 0 ? bal[0] : bal[2], hi = c == 0 ? bal[1] : bal[3];
+                        a.mask[row * 4 + 2 * ct + c] = (static_cast<uint32_t>(lo >> (16 * g)) & 0xffffu) | ((static_cast<uint32_t>(hi >> (16 * g)) & 0xffffu) << 16);
+                    }
+                }
+            }
+        }
+}
+
+// conv + ReLU + pool as the A operand of fc1 (train.py:89-92): out = ReLU(features * fc1.weight^T + fc1.bias) -> h_out
+__global__ __launch_bounds__(NM_THREADS, 2) void nm_conv_fc1(const NmArgs a) {
+    __shared__ float4 s_b[2][STAGE_F4];
+    const uint32_t ct = blockIdx.x % a.n_ct, tile_local = blockIdx.x / a.n_ct;
+    const NmTile tile = a.tiles[tile_local];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+    const bool active = static_cast<uint32_t>(32 * wave) < tile.n_valid;   // wave-uniform: a wave with no valid row only copies B
+    const uint32_t stages = (a.chunks + NM_PC - 1) / NM_PC;
+    const float4* bsrc = a.b_packed + static_cast<size_t>(ct) * stages * STAGE_F4;
+
+    // this lane's four channels
+    float w[4][NM_KW], cb[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+#pragma unroll
+        for (int j = 0; j < NM_KW; ++j) w[c][j] = a.conv[(4 * g + c) * NM_KW + j];
+        cb[c] = a.conv[NM_CH * NM_KW + 4 * g + c];
+    }
+    // the windows of this lane's two rows; a row past the tile's last valid one reads the tile's first row (its result is not stored)
+    const float* xrow[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        uint32_t r = 32 * wave + 16 * t + (lane & 15);
+        if (r >= tile.n_valid) r = 0;
+        xrow[t] = a.db + (static_cast<size_t>(tile.stream) * a.stride_frames + tile.f0 + r - (a.t_frames - 1)) * a.n_bins;
+    }
+    const uint32_t last = a.L - 1;   // every position a real chunk reads is <= last; the clamp serves the padded chunks of the last stage
+    float x[2][X_REGS], xn[2][X_STAGE];
+    f32x4 breg[STAGE_LD];
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc[t][s] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    stage_fetch(bsrc, breg);
+    if (active) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int j = 0; j < X_REGS; ++j) x[t][j] = xrow[t][min(static_cast<uint32_t>(j), last)];
+    }
+    stage_put(s_b[0], breg);
+    __syncthreads();
+
+    for (uint32_t st = 0; st < stages; ++st) {
+        const bool more = st + 1 < stages;
+        if (more) {
+            stage_fetch(bsrc + static_cast<size_t>(st + 1) * STAGE_F4, breg);
+            if (active) {
+                const uint32_t at = X_STAGE * (st + 1) + 3;
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int j = 0; j < X_STAGE; ++j) xn[t][j] = xrow[t][min(at + j, last)];
+            }
+        }
+        if (active) {
+            const float4* sb = s_b[st & 1];
+#pragma unroll
+            for (int i = 0; i < NM_PC; ++i) {
+                if (NM_PC * st + i < a.chunks) {   // (uniform) the padded chunks of the last stage are skipped
+                    float4 av[2];
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) {
+                        float v[4];
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) {
+                            float e = cb[c], o = cb[c];   // conv positions 2 p and 2 p + 1
+#pragma unroll
+                            for (int j = 0; j < NM_KW; ++j) {
+                                e = fmaf(w[c][j], x[t][4 * i + j], e);
+                                o = fmaf(w[c][j], x[t][4 * i + 2 + j], o);
+                            }
+                            v[c] = fmaxf(fmaxf(e, o), 0.0f);
+                        }
+                        av[t] = make_float4(v[0], v[1], v[2], v[3]);
+                    }
+                    chunk_mfma(sb + i * CHUNK_F4, lane, av, acc);
+                }
+            }
+            if (more) {
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) x[t][j] = x[t][X_STAGE + j];
+#pragma unroll
+                    for (int j = 0; j < X_STAGE; ++j) x[t][3 + j] = xn[t][j];
+                }
+            }
+        }
+        if (more) stage_put(s_b[(st + 1) & 1], breg);
+        __syncthreads();
+    }
+    if (active) epilogue<0>(a, tile, tile_local, ct, wave, lane, acc);
+}
+
+// out = a_in * W^T + bias: ACT 0 -> ReLU -> h_out (train.py:93-95); ACT 1 -> logits, sigmoid, mask (train.py:96-98, ml_system.rs:56-65)
+template <int ACT>
+__global__ __launch_bounds__(NM_THREADS, 2) void nm_dense(const NmArgs a) {
+    __shared__ float4 s_b[2][STAGE_F4];
+    const uint32_t ct = blockIdx.x % a.n_ct, tile_local = blockIdx.x / a.n_ct;
+    const NmTile tile = a.tiles[tile_local];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+    const bool active = static_cast<uint32_t>(32 * wave) < tile.n_valid;
+    const uint32_t stages = (a.chunks + NM_PC - 1) / NM_PC;
+    const float4* bsrc = a.b_packed + static_cast<size_t>(ct) * stages * STAGE_F4;
+    // rows of the activation buffer: every row of an active wave was written by the previous layer
+    const float4* arow[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+        arow[t] = reinterpret_cast<const float4*>(a.a_in + (static_cast<size_t>(tile_local) * NM_BM + 32 * wave + 16 * t + (lane & 15)) * a.k) + g;
+    float4 av[NM_PC][2], an[NM_PC][2];
+    f32x4 breg[STAGE_LD];
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc[t][s] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    stage_fetch(bsrc, breg);
+    if (active) {
+#pragma unroll
+        for (int i = 0; i < NM_PC; ++i)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) av[i][t] = static_cast<uint32_t>(i) < a.chunks ? arow[t][4 * i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    stage_put(s_b[0], breg);
+    __syncthreads();
+
+    for (uint32_t st = 0; st < stages; ++st) {
+        const bool more = st + 1 < stages;
+        if (more) {
+            stage_fetch(bsrc + static_cast<size_t>(st + 1) * STAGE_F4, breg);
+            if (active) {
+#pragma unroll
+                for (int i = 0; i < NM_PC; ++i) {
+                    const uint32_t kc = NM_PC * (st + 1) + i;   // (a chunk past the row's end is not read)
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) an[i][t] = kc < a.chunks ? arow[t][4 * kc] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                }
+            }
+        }
+        if (active) {
+            const float4* sb = s_b[st & 1];
+#pragma unroll
+            for (int i = 0; i < NM_PC; ++i)
+                if (NM_PC * st + i < a.chunks) chunk_mfma(sb + i * CHUNK_F4, lane, av[i], acc);
+            if (more) {
+#pragma unroll
+                for (int i = 0; i < NM_PC; ++i)
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) av[i][t] = an[i][t];
+            }
+        }
+        if (more) stage_put(s_b[(st + 1) & 1], breg);
+        __syncthreads();
+    }
+    if (active) epilogue<ACT>(a, tile, tile_local, ct, wave, lane, acc);
+}
+
+pvq_status upload(const std::vector<float>& packed, const float* bias, uint32_t n_bias, float*& d, size_t& bias_at) {
+    bias_at = packed.size();
+    PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&d), (packed.size() + n_bias) * sizeof(float)));
+    PVQ_HIP(hipMemcpy(d, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
+    PVQ_HIP(hipMemcpy(d + bias_at, bias, n_bias * sizeof(float), hipMemcpyHostToDevice));
+    return PVQ_OK;
+}
+}  // namespace
+
+NoteModel::~NoteModel() {
+    if (device_id_ < 0) return;
+    (void)hipSetDevice(device_id_);
+    if (d_conv_) (void)hipFree(d_conv_);
+    if (d_fc1_) (void)hipFree(d_fc1_);
+    for (float* p : d_layer_)
+        if (p) (void)hipFree(p);
+    if (d_out_) (void)hipFree(d_out_);
+    if (d_ws_) (void)hipFree(d_ws_);
+}
+
+pvq_status NoteModel::create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
+                             std::unique_ptr<NoteModel>& out) {
+    out.reset();
+    NoteModelDims d;
+    std::string err;
+    const pvq_status st = note_model_check(params, weights, d, err);
+    if (st != PVQ_OK) {
+        set_last_error(err);
+        return st;
+    }
+    std::unique_ptr<NoteModel> m(new NoteModel());
+    m->device_id_ = device_id < 0 ? -1 : device_id;
+    m->host_.assign(d, *weights);
+    if (device_id >= 0) {
+        PVQ_HIP(hipSetDevice(device_id));
+        const NoteModelHost& h = m->host_;
+        std::vector<float> conv(h.conv_w);
+        size_t at = 0;
+        pvq_status s = upload(conv, h.conv_b.data(), NM_CH, m->d_conv_, at);
+        if (s == PVQ_OK) s = upload(note_model_pack_b(h.fc1_w.data(), d.mlp, d.n_features, true, d.o_pool), h.fc1_b.data(), d.mlp, m->d_fc1_, m->fc1_bias_at_);
+        m->d_layer_.assign(d.layers, nullptr);
+        for (uint32_t i = 0; s == PVQ_OK && i < d.layers; ++i)
+            s = upload(note_model_pack_b(h.layer_w[i].data(), d.mlp, d.mlp, false, 0), h.layer_b[i].data(), d.mlp, m->d_layer_[i], m->layer_bias_at_);
+        if (s == PVQ_OK) s = upload(note_model_pack_b(h.out_w.data(), NM_OUT, d.mlp, false, 0), h.out_b.data(), NM_OUT, m->d_out_, m->out_bias_at_);
+        if (s != PVQ_OK) return s;
+    }
+    out = std::move(m);
+    return PVQ_OK;
+}
+
+pvq_status NoteModel::rows_device(const float* d_db, const size_t* n_frames, uint32_t n_streams, size_t stride_frames,
+                                  const pvq_note_model_outputs& outs, hipStream_t stream) {
+    const NoteModelDims& d = host_.d;
+    if (!d_db) {
+        set_last_error("note model: d_db is null");
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(outs.d_mask) & 3) {
+        set_last_error("note model: d_mask must be 4-byte aligned");
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (stride_frames > 0x7fffffffull || (n_streams && stride_frames > (~0ull >> 12) / n_streams)) {
+        set_last_error("note model: too many frames in one call");
+        return PVQ_ERR_INVALID_ARG;
+    }
+    for (uint32_t s = 0; n_frames && s < n_streams; ++s)
+        if (n_frames[s] > stride_frames) {
+            set_last_error("note model: n_frames of stream " + std::to_string(s) + " exceeds stride_frames");
+            return PVQ_ERR_INVALID_ARG;
+        }
+    if (device_id_ < 0) {
+        set_last_error("the batched note model runs on a GPU; this handle has none (pvq_note_model_infer is the host face)");
+        return PVQ_ERR_NO_DEVICE;
+    }
+    const size_t rows_all = static_cast<size_t>(n_streams) * stride_frames;
+    if (rows_all == 0 || !(outs.d_prob || outs.d_logits || outs.d_mask)) return PVQ_OK;
+    PVQ_HIP(hipSetDevice(device_id_));
+    // every row that is no model row is zero; the model rows are overwritten below
+    if (outs.d_prob) PVQ_HIP(hipMemsetAsync(outs.d_prob, 0, rows_all * NM_OUT * sizeof(float), stream));
+    if (outs.d_logits) PVQ_HIP(hipMemsetAsync(outs.d_logits, 0, rows_all * NM_OUT * sizeof(float), stream));
+    if (outs.d_mask) PVQ_HIP(hipMemsetAsync(outs.d_mask, 0, rows_all * 4 * sizeof(uint32_t), stream));
+    const std::vector<NmTile> tiles = note_model_tiles(d, n_frames, n_streams, stride_frames);
+    if (tiles.empty()) return PVQ_OK;
+
+    // workspace: the tile table, then two activation buffers of chunk_tiles * 128 rows
+    const size_t tab_bytes = (tiles.size() * sizeof(NmTile) + 255) & ~static_cast<size_t>(255);
+    const size_t tile_bytes = 2 * static_cast<size_t>(NM_BM) * d.mlp * sizeof(float);
+    const uint32_t n_ct_mlp = (d.mlp + NM_BN - 1) / NM_BN;
+    size_t chunk_tiles = ws_limit_ > tab_bytes ? (ws_limit_ - tab_bytes) / tile_bytes : 0;
+    chunk_tiles = std::max<size_t>(1, std::min<size_t>({chunk_tiles, tiles.size(), 0x7fffffffull / std::max<uint32_t>(n_ct_mlp, NM_OUT / NM_BN)}));
+    const size_t need = tab_bytes + chunk_tiles * tile_bytes;
+    if (ws_bytes_ < need) {
+        if (d_ws_) PVQ_HIP(hipFree(d_ws_));   // (synchronises the device: nothing still reads the old buffer)
+        d_ws_ = nullptr;
+        ws_bytes_ = 0;
+        PVQ_HIP(hipMalloc(&d_ws_, need));
+        ws_bytes_ = need;
+    }
+    NmTile* d_tiles = static_cast<NmTile*>(d_ws_);
+    float* buf[2];
+    buf[0] = reinterpret_cast<float*>(static_cast<char*>(d_ws_) + tab_bytes);
+    buf[1] = buf[0] + chunk_tiles * NM_BM * d.mlp;
+    PVQ_HIP(hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(NmTile), hipMemcpyHostToDevice, stream));   // (pageable source: staged before the call returns)
+
+    for (size_t t0 = 0; t0 < tiles.size(); t0 += chunk_tiles) {
+        const uint32_t nt = static_cast<uint32_t>(std::min(chunk_tiles, tiles.size() - t0));
+        NmArgs a{};
+        a.tiles = d_tiles + t0;
+        a.stride_frames = stride_frames;
+        a.n_bins = d.n_bins;
+        a.t_frames = d.t_frames;
+        a.L = d.L;
+        // fc1 over the fused conv
+        a.db = d_db;
+        a.conv = d_conv_;
+        a.b_packed = reinterpret_cast<const float4*>(d_fc1_);
+        a.bias = d_fc1_ + fc1_bias_at_;
+        a.h_out = buf[0];
+        a.chunks = d.o_pool;
+        a.k = d.n_features;
+        a.n = d.mlp;
+        a.n_ct = n_ct_mlp;
+        hipLaunchKernelGGL(nm_conv_fc1, dim3(nt * a.n_ct), dim3(NM_THREADS), 0, stream, a);
+        int cur = 0;
+        a.chunks = d.mlp / NM_KC;
+        a.k = d.mlp;
+        for (uint32_t i = 0; i < d.layers; ++i) {
+            a.a_in = buf[cur];
+            a.h_out = buf[cur ^ 1];
+            a.b_packed = reinterpret_cast<const float4*>(d_layer_[i]);
+            a.bias = d_layer_[i] + layer_bias_at_;
+            hipLaunchKernelGGL(nm_dense<0>, dim3(nt * a.n_ct), dim3(NM_THREADS), 0, stream, a);
+            cur ^= 1;
+        }
+        a.a_in = buf[cur];
+        a.h_out = nullptr;
+        a.b_packed = reinterpret_cast<const float4*>(d_out_);
+        a.bias = d_out_ + out_bias_at_;
+        a.n = NM_OUT;
+        a.n_ct = NM_OUT / NM_BN;
+        a.prob = outs.d_prob;
+        a.logits = outs.d_logits;
+        a.mask = outs.d_mask;
+        hipLaunchKernelGGL(nm_dense<1>, dim3(nt * a.n_ct), dim3(NM_THREADS), 0, stream, a);
+    }
+    PVQ_HIP(hipGetLastError());
+    return PVQ_OK;
+}
+
+}  // namespace pvq

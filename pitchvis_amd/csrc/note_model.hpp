@@ -1,0 +1,54 @@
+// note_model.hpp — the trainer's note model (pitchvis_train/train.py:67-99; run per frame by pitchvis_viewer/src/ml_system.rs:24-69)
+// for MANY rows on the GPU: a row is one frame of one stream, its input the window of t_frames dB frames ending there, read in
+// place from the [n_streams][stride_frames][n_bins] buffer the batched transform writes.
+//
+// Two kernels, exact f32 on v_mfma_f32_16x16x4_f32 (note_model.hip):
+//   nm_conv_fc1   conv + ReLU + pool computed in registers as the A operand of the first Linear; the [rows][n_features]
+//                 activation never exists in memory
+//   nm_dense<ACT> one launch per further Linear; the output layer writes logits, sigmoid and the 128-bit mask in its epilogue
+// Hidden activations go through a grow-only workspace of the handle; rows are processed in chunks of whole tiles that fit its limit.
+// NoteModelHost (note_model_plan.hpp) is the one-row host face.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <memory>
+#include <vector>
+
+#include "../../include/pvq.h"
+#include "note_model_plan.hpp"
+
+namespace pvq {
+
+class NoteModel {
+   public:
+    // sizes and pointers are checked before any device is touched.  device_id < 0: a host-only object (infer works, rows_device
+    // returns PVQ_ERR_NO_DEVICE after its argument checks).
+    static pvq_status create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
+                             std::unique_ptr<NoteModel>& out);
+    ~NoteModel();
+    const NoteModelDims& dims() const { return host_.d; }
+    int device() const { return device_id_; }
+    void infer(const float* window, float* out_prob) const { host_.infer(window, out_prob); }
+    // n_frames: HOST array or null.  Asynchronous on `stream`; uses the handle's workspace, so one stream at a time.
+    pvq_status rows_device(const float* d_db, const size_t* n_frames, uint32_t n_streams, size_t stride_frames,
+                           const pvq_note_model_outputs& outs, hipStream_t stream);
+    void set_workspace_limit(uint64_t bytes) { ws_limit_ = bytes; }
+
+   private:
+    NoteModel() = default;
+    int device_id_ = -1;
+    NoteModelHost host_;
+    uint64_t ws_limit_ = 256ull << 20;
+    float* d_conv_ = nullptr;              // conv weights [16][5], then bias [16]
+    float* d_fc1_ = nullptr;               // packed B operand, then bias [mlp]
+    std::vector<float*> d_layer_;          // packed B operand, then bias [mlp], per hidden layer
+    float* d_out_ = nullptr;               // packed B operand, then bias [128]
+    size_t fc1_bias_at_ = 0, layer_bias_at_ = 0, out_bias_at_ = 0;   // float offsets of the biases
+    void* d_ws_ = nullptr;                 // tile table, then two [chunk rows][mlp] activation buffers
+    size_t ws_bytes_ = 0;
+};
+
+}  // namespace pvq

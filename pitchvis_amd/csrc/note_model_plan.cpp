@@ -1,0 +1,138 @@
+// note_model_plan.cpp — see note_model_plan.hpp
+#include "note_model_plan.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+namespace pvq {
+
+pvq_status note_model_check(const pvq_note_model_params* p, const pvq_note_model_weights* w, NoteModelDims& d, std::string& err) {
+    if (!p || !w) {
+        err = "note model: null params or weights";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (p->n_bins == 0 || p->t_frames == 0 || p->mlp_size == 0) {
+        err = "note model: n_bins, t_frames and mlp_size must be positive";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (p->mlp_size % 16 != 0) {
+        err = "note model: mlp_size must be a multiple of 16";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (p->n_bins < 3 || p->n_bins > 1024) {
+        err = "unsupported: the note model takes 3 .. 1024 bins";
+        return PVQ_ERR_UNSUPPORTED;
+    }
+    if (p->t_frames > 8 || p->t_frames * p->n_bins < 8) {
+        err = "unsupported: the note model takes windows of 1 .. 8 frames and at least 8 values";
+        return PVQ_ERR_UNSUPPORTED;
+    }
+    if (p->mlp_size > 4096) {
+        err = "unsupported: the note model takes an mlp_size of 16 .. 4096";
+        return PVQ_ERR_UNSUPPORTED;
+    }
+    if (p->mlp_layers > 8) {
+        err = "unsupported: the note model takes 0 .. 8 hidden layers";
+        return PVQ_ERR_UNSUPPORTED;
+    }
+    bool null_w = !w->conv_weight || !w->conv_bias || !w->fc1_weight || !w->fc1_bias || !w->output_weight || !w->output_bias;
+    if (p->mlp_layers && (!w->layer_weight || !w->layer_bias)) null_w = true;
+    for (uint32_t i = 0; !null_w && i < p->mlp_layers; ++i) null_w = !w->layer_weight[i] || !w->layer_bias[i];
+    if (null_w) {
+        err = "note model: a weight pointer is null";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    d.n_bins = p->n_bins;
+    d.t_frames = p->t_frames;
+    d.mlp = p->mlp_size;
+    d.layers = p->mlp_layers;
+    d.L = p->t_frames * p->n_bins;
+    d.o_conv = (d.L - NM_KW) / 2 + 1;
+    d.o_pool = d.o_conv / 2;
+    d.n_features = NM_CH * d.o_pool;
+    return PVQ_OK;
+}
+
+std::vector<float> note_model_pack_b(const float* W, uint32_t n, uint32_t k, bool conv_order, uint32_t o_pool) {
+    const uint32_t n_ct = (n + NM_BN - 1) / NM_BN;
+    const uint32_t chunks = k / NM_KC;   // k is a multiple of 16 in both orders
+    const uint32_t chunks_padded = note_model_stages(chunks) * NM_PC;
+    std::vector<float> out(static_cast<size_t>(n_ct) * chunks_padded * NM_BN * NM_KC, 0.0f);
+    for (uint32_t ct = 0; ct < n_ct; ++ct)
+        for (uint32_t kc = 0; kc < chunks; ++kc) {
+            float* dst = out.data() + (static_cast<size_t>(ct) * chunks_padded + kc) * NM_BN * NM_KC;
+            for (uint32_t s = 0; s < 4; ++s)
+                for (uint32_t l = 0; l < 64; ++l) {
+                    const uint32_t col = NM_BN * ct + 16 * s + (l & 15);
+                    if (col >= n) continue;
+                    for (uint32_t i = 0; i < 4; ++i) {
+                        const uint32_t kk = 4 * (l >> 4) + i;   // position in the chunk; in conv order the channel
+                        const size_t src = conv_order ? static_cast<size_t>(kk) * o_pool + kc : static_cast<size_t>(NM_KC) * kc + kk;
+                        dst[(s * 64 + l) * 4 + i] = W[static_cast<size_t>(col) * k + src];
+                    }
+                }
+        }
+    return out;
+}
+
+std::vector<NmTile> note_model_tiles(const NoteModelDims& d, const size_t* n_frames, uint32_t n_streams, size_t stride_frames) {
+    std::vector<NmTile> tiles;
+    for (uint32_t s = 0; s < n_streams; ++s) {
+        const size_t nf = n_frames ? n_frames[s] : stride_frames;
+        for (size_t f0 = d.t_frames - 1; f0 < nf; f0 += NM_BM)
+            tiles.push_back(NmTile{s, static_cast<uint32_t>(f0), static_cast<uint32_t>(std::min<size_t>(NM_BM, nf - f0)), 0u});
+    }
+    return tiles;
+}
+
+void NoteModelHost::assign(const NoteModelDims& dims, const pvq_note_model_weights& w) {
+    d = dims;
+    conv_w.assign(w.conv_weight, w.conv_weight + NM_CH * NM_KW);
+    conv_b.assign(w.conv_bias, w.conv_bias + NM_CH);
+    fc1_w.assign(w.fc1_weight, w.fc1_weight + static_cast<size_t>(d.mlp) * d.n_features);
+    fc1_b.assign(w.fc1_bias, w.fc1_bias + d.mlp);
+    layer_w.resize(d.layers);
+    layer_b.resize(d.layers);
+    for (uint32_t i = 0; i < d.layers; ++i) {
+        layer_w[i].assign(w.layer_weight[i], w.layer_weight[i] + static_cast<size_t>(d.mlp) * d.mlp);
+        layer_b[i].assign(w.layer_bias[i], w.layer_bias[i] + d.mlp);
+    }
+    out_w.assign(w.output_weight, w.output_weight + static_cast<size_t>(NM_OUT) * d.mlp);
+    out_b.assign(w.output_bias, w.output_bias + NM_OUT);
+}
+
+namespace {
+void linear(const float* W, const float* b, const float* x, uint32_t n, uint32_t k, bool relu, float* y) {
+    for (uint32_t j = 0; j < n; ++j) {
+        const float* row = W + static_cast<size_t>(j) * k;
+        float acc = 0.0f;
+        for (uint32_t i = 0; i < k; ++i) acc += row[i] * x[i];
+        acc += b[j];
+        y[j] = relu ? std::max(acc, 0.0f) : acc;
+    }
+}
+}  // namespace
+
+void NoteModelHost::infer(const float* window, float* out_prob) const {
+    std::vector<float> feat(d.n_features), h(d.mlp), h2(d.mlp);
+    for (int c = 0; c < NM_CH; ++c)
+        for (uint32_t p = 0; p < d.o_pool; ++p) {
+            float best = 0.0f;   // ReLU, then the pool's maximum over conv positions 2p and 2p + 1 (train.py:89-90)
+            for (uint32_t j = 2 * p; j < 2 * p + 2; ++j) {
+                float acc = 0.0f;
+                for (int i = 0; i < NM_KW; ++i) acc += conv_w[c * NM_KW + i] * window[2 * j + i];
+                best = std::max(best, acc + conv_b[c]);
+            }
+            feat[static_cast<size_t>(c) * d.o_pool + p] = best;
+        }
+    linear(fc1_w.data(), fc1_b.data(), feat.data(), d.mlp, d.n_features, true, h.data());
+    for (uint32_t i = 0; i < d.layers; ++i) {
+        linear(layer_w[i].data(), layer_b[i].data(), h.data(), d.mlp, d.mlp, true, h2.data());
+        h.swap(h2);
+    }
+    float logit[NM_OUT];
+    linear(out_w.data(), out_b.data(), h.data(), NM_OUT, d.mlp, false, logit);
+    for (int j = 0; j < NM_OUT; ++j) out_prob[j] = 1.0f / (1.0f + std::exp(-logit[j]));
+}
+
+}  // namespace pvq
