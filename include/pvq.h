@@ -592,6 +592,88 @@ pvq_status pvq_note_model_rows_device(pvq_note_model *m, const float *d_db, cons
  * results do not depend on the chunking.  One tile (1 KiB * mlp_size + its table entry) is the least a call works with. */
 pvq_status pvq_note_model_set_workspace_limit(pvq_note_model *m, uint64_t bytes);
 
+/* The trainer's optimisation step for that model (pitchvis_train/train.py:108-162): forward in training mode, BCELoss, backward,
+ * optim.Adam with weight decay, on a batch of rows gathered by index from a dataset that already sits in device memory (what
+ * train_dataset_streams leaves there).  The handle owns, on the device, the parameters in PyTorch layout, their gradients, Adam's two
+ * moments and the step counter, plus a workspace sized once from max_batch: 4 x the parameter count in floats, and per row of
+ * max_batch (2 n_features + (mlp_layers + 3) mlp_size + 355) floats, and 16 MiB of partial sums.  Nothing is allocated by a step.
+ *
+ * Dataset (train.py:17-21,34,46).  d_db is [n_rows][n_bins] f32, d_targets is [n_rows][128] f32, contiguous DEVICE buffers that are
+ *   never written.  Sample i (t_frames - 1 <= i < n_rows) has as input the t_frames * n_bins contiguous values of rows
+ *   i - t_frames + 1 .. i (window_data followed by the flat reshape) and as target row i of d_targets; a target is any value in [0, 1].
+ * Batch.  idx is a HOST array of `batch` sample indices.  It is validated before anything is launched: an index outside
+ *   [t_frames - 1, n_rows) or a batch outside 1 .. max_batch gives PVQ_ERR_INVALID_ARG.  It is copied to a pinned buffer of the
+ *   handle before the call returns and goes to the device on `stream`.  Duplicates are legal; their contributions add.
+ * Forward (train.py:87-99, training mode).  conv(1 -> 16, k 5, s 2) -> ReLU -> max_pool1d(2) -> flatten channel-major -> fc1 -> ReLU
+ *   -> mlp_layers x (Linear -> ReLU -> dropout) -> output.  Dropout follows the hidden `layers` only, not fc1 (train.py:93-95); it is
+ *   inverted dropout: a kept value is multiplied by 1 / (1 - p), rounded to f32.
+ * Dropout mask.  No stateful generator: a counter-based hash of (seed, step counter, layer, row in the batch, column).  With 64-bit
+ *   unsigned arithmetic modulo 2^64 and
+ *       mix(z):  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31   (splitmix64's finaliser)
+ *       key   = mix(mix(seed + 0x9E3779B97F4A7C15 * (step + 1)) ^ layer)
+ *       u     = mix(key ^ (row * 2^32 + col)) >> 40                                 (24 bits)
+ *   element (row, col) of the output of hidden layer `layer` (0-based) is KEPT when u >= floor(dropout * 2^24), the product taken in
+ *   double.  `step` is pvq_note_trainer_steps at the time of the call (the same for PVQ_TRAIN_GRAD and the PVQ_TRAIN_STEP that
+ *   follows it), `row` the position in idx.  pvq_note_trainer_dropout_keep evaluates it on the host.
+ * Loss (train.py:136,154).  The mean over batch * 128 of the binary cross-entropy, computed from the logits z in the stable form
+ *   max(z, 0) - z y + log1p(exp(-|z|)), terms in f32, their sum in double.  One difference from nn.BCELoss on sigmoid(z) in f32:
+ *   BCELoss clamps each logarithm at -100, so a saturated sigmoid (|z| beyond about 17 in f32, where 1 - sigmoid(z) rounds to 0)
+ *   costs at most 100 there; this form keeps the exact value |z| and its gradient.
+ * Backward (train.py:155).  dZ_out = (sigmoid(z) - y) / (batch * 128).  Per Linear layer dW = dZ^T H, db = sum over rows of dZ,
+ *   dH = (dZ W) * mask * 1 / (1 - p) * [H > 0].  Through the pool to the larger of each pair, the first on a tie (max_pool1d);
+ *   through the ReLU with gradient 0 at 0; to conv1.weight [16][5] and conv1.bias [16].
+ * Adam (train.py:141-144: torch.optim.Adam, L2 weight decay added to the gradient, not AdamW).  With t = steps + 1, per element
+ *   g += wd w;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  w -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps).
+ *   The element's arithmetic is carried out in double and each stored value (w, m, v) rounded once to f32; the stored gradient is
+ *   left as the backward pass wrote it (without the decay term).
+ * Determinism.  Equal weights, hyper-parameters, seed, counter, dataset and idx give equal bits in every gradient and every updated
+ *   weight, run after run: no floating-point atomics, every reduction in an order fixed by the shapes. */
+typedef struct pvq_note_trainer pvq_note_trainer;
+/* replaces the optimiser's and the module's constructor arguments, train.py:111,131-144 */
+typedef struct pvq_note_trainer_hyper {
+    double lr;            /* train.py:111 (1e-5); > 0 */
+    double beta1, beta2;  /* torch.optim.Adam's defaults 0.9 / 0.999; 0 <= beta < 1 */
+    double eps;           /* train.py:143 torch.finfo(torch.float32).eps = 1.1920929e-7; > 0 */
+    double weight_decay;  /* train.py:144 (5e-4); >= 0 */
+    double dropout;       /* train.py:131-138 (0.1); 0 <= dropout < 1 */
+    uint64_t seed;        /* of the dropout mask */
+} pvq_note_trainer_hyper;
+typedef enum pvq_train_mode {
+    PVQ_TRAIN_STEP = 0, /* train.py:153-158: dropout on, backward, Adam, counter + 1 */
+    PVQ_TRAIN_GRAD = 1, /* the same without Adam and without advancing the counter: the gradients stay readable */
+    PVQ_TRAIN_EVAL = 2  /* train.py:164-176 model.eval(): dropout off, forward and loss only (the validation loss) */
+} pvq_train_mode;
+typedef enum pvq_train_array { PVQ_TRAIN_WEIGHTS = 0, PVQ_TRAIN_GRADS = 1, PVQ_TRAIN_ADAM_M = 2, PVQ_TRAIN_ADAM_V = 3 } pvq_train_array;
+/* lr 1e-5, betas 0.9 / 0.999, eps 1.1920929e-7 (2^-23), weight decay 5e-4, dropout 0.1 (train.py:111,131-144), seed 0 */
+void pvq_note_trainer_hyper_default(pvq_note_trainer_hyper *h);
+/* replaces NoteModel(...) + optim.Adam(...) (train.py:131-144).  params and weights as for pvq_note_model_create, with its size
+ * checks; then lr > 0, 0 <= beta < 1, eps > 0, weight_decay >= 0, 0 <= dropout < 1, 1 <= max_batch <= 4096 (PVQ_ERR_INVALID_ARG).
+ * All checks run before any device is touched.  The weights are copied; gradients, moments and the counter start at zero.
+ * device_id < 0: a host-only handle (argument checks work, pvq_note_trainer_step returns PVQ_ERR_NO_DEVICE after them; no CPU
+ * fallback). */
+pvq_status pvq_note_trainer_create(int device_id, const pvq_note_model_params *params, const pvq_note_model_weights *weights,
+                                   const pvq_note_trainer_hyper *hyper, uint32_t max_batch, pvq_note_trainer **out);
+void pvq_note_trainer_destroy(pvq_note_trainer *t);
+/* One step of `mode` (a pvq_train_mode) on the batch idx[0 .. batch) of the dataset (d_db, d_targets, n_rows), as laid out above.
+ * d_loss (DEVICE, one float, may be NULL) receives the mean loss, d_logits (DEVICE, [batch][128], may be NULL) the logits; nothing
+ * else outside the handle is written, and the call never synchronises.  A refused call launches nothing and leaves the counter.
+ * Asynchronous on `stream`; the workspace belongs to the handle, so one handle serves one stream at a time. */
+pvq_status pvq_note_trainer_step(pvq_note_trainer *t, int mode, const float *d_db, const float *d_targets, size_t n_rows, const uint32_t *idx,
+                                 uint32_t batch, float *d_loss, float *d_logits, void *stream);
+/* completed PVQ_TRAIN_STEP calls: Adam's t - 1 and the `step` of the dropout mask */
+uint64_t pvq_note_trainer_steps(const pvq_note_trainer *t);
+/* number of parameters: 96 + mlp_size (n_features + 1) + mlp_layers mlp_size (mlp_size + 1) + 128 (mlp_size + 1) */
+uint64_t pvq_note_trainer_param_count(const pvq_note_trainer *t);
+/* Copies array `what` (a pvq_train_array) to out_host, param_count floats (capacity: floats out_host holds, PVQ_ERR_INVALID_ARG if
+ * fewer), in state_dict order and layout: conv1.weight [16][1][5], conv1.bias [16], fc1.weight [mlp_size][n_features], fc1.bias,
+ * layers.i.weight [mlp_size][mlp_size], layers.i.bias for i = 0 .., output.weight [128][mlp_size], output.bias [128].
+ * Synchronises the device. */
+pvq_status pvq_note_trainer_read(pvq_note_trainer *t, int what, float *out_host, size_t capacity);
+/* The dropout mask above as a pure host function: out_keep[j] = 1 when element (row, col0 + j) of hidden layer `layer` is kept at
+ * `step`, else 0, for j in 0 .. n.  Needs no handle; PVQ_ERR_INVALID_ARG for a null array or a dropout outside [0, 1). */
+pvq_status pvq_note_trainer_dropout_keep(uint64_t seed, uint64_t step, uint32_t layer, uint32_t row, uint32_t col0, uint32_t n, double dropout,
+                                         uint8_t *out_keep);
+
 /* Page-locked host memory for the host-buffer entry points (pvq_vqt_calculate_batch_db, pvq_analyze_batch,
  * pvq_train_frames_db): with pageable buffers those calls are bound by staged PCIe copies (~16 GB/s); buffers from
  * here are DMA-able directly.  NULL on failure (pvq_last_error). */

@@ -38,6 +38,8 @@ EXPORTS = [
     "pvq_spectrogram_row", "pvq_chroma_row", "pvq_render_batch_create", "pvq_render_batch_destroy", "pvq_render_batch_rows_device",
     "pvq_note_model_create", "pvq_note_model_destroy", "pvq_note_model_sizes", "pvq_note_model_infer", "pvq_note_model_rows_device",
     "pvq_note_model_set_workspace_limit",
+    "pvq_note_trainer_hyper_default", "pvq_note_trainer_create", "pvq_note_trainer_destroy", "pvq_note_trainer_step", "pvq_note_trainer_steps",
+    "pvq_note_trainer_param_count", "pvq_note_trainer_read", "pvq_note_trainer_dropout_keep",
     "pvq_vqt_input_status", "pvq_vqt_last_gemm_flop", "pvq_vqt_last_sclk_mhz",
     "pvq_vqt_bandwidths_3db", "pvq_vqt_warning_count", "pvq_vqt_warning",
 ]
@@ -56,6 +58,8 @@ PVQ_ERR_NONFINITE_INPUT = 9
 ALGO_AUTO, ALGO_FFT, ALGO_BLOCKDFT = 0, 1, 2
 GEMM_F32, GEMM_BF16X3 = 0, 1
 SPECTROGRAM_VQT, SPECTROGRAM_PEAKS = 0, 1
+TRAIN_STEP, TRAIN_GRAD, TRAIN_EVAL = 0, 1, 2                      # pvq_train_mode
+TRAIN_WEIGHTS, TRAIN_GRADS, TRAIN_ADAM_M, TRAIN_ADAM_V = 0, 1, 2, 3   # pvq_train_array
 
 
 class CParams(C.Structure):
@@ -105,6 +109,10 @@ class CNoteModelWeights(C.Structure):   # pvq_note_model_weights (host pointers)
 
 class CNoteModelOutputs(C.Structure):   # pvq_note_model_outputs (device pointers)
     _fields_ = [(n, C.c_void_p) for n in ("d_prob", "d_logits", "d_mask")]
+
+
+class CNoteTrainerHyper(C.Structure):   # pvq_note_trainer_hyper
+    _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "dropout")] + [("seed", C.c_uint64)]
 
 
 class CShard(C.Structure):   # pvq_shard
@@ -273,6 +281,17 @@ def load():
     L.pvq_note_model_rows_device.argtypes = [vp, vp, szp, C.c_uint32, C.c_size_t, C.POINTER(CNoteModelOutputs), vp]
     L.pvq_note_model_rows_device.restype = C.c_int
     L.pvq_note_model_set_workspace_limit.argtypes = [vp, C.c_uint64]; L.pvq_note_model_set_workspace_limit.restype = C.c_int
+    L.pvq_note_trainer_hyper_default.argtypes = [C.POINTER(CNoteTrainerHyper)]; L.pvq_note_trainer_hyper_default.restype = None
+    L.pvq_note_trainer_create.argtypes = [C.c_int, C.POINTER(CNoteModelParams), C.POINTER(CNoteModelWeights), C.POINTER(CNoteTrainerHyper), C.c_uint32,
+                                          C.POINTER(vp)]
+    L.pvq_note_trainer_create.restype = C.c_int
+    L.pvq_note_trainer_destroy.argtypes = [vp]; L.pvq_note_trainer_destroy.restype = None
+    L.pvq_note_trainer_step.argtypes = [vp, C.c_int, vp, vp, C.c_size_t, up, C.c_uint32, vp, vp, vp]; L.pvq_note_trainer_step.restype = C.c_int
+    L.pvq_note_trainer_steps.argtypes = [vp]; L.pvq_note_trainer_steps.restype = C.c_uint64
+    L.pvq_note_trainer_param_count.argtypes = [vp]; L.pvq_note_trainer_param_count.restype = C.c_uint64
+    L.pvq_note_trainer_read.argtypes = [vp, C.c_int, fp, C.c_size_t]; L.pvq_note_trainer_read.restype = C.c_int
+    L.pvq_note_trainer_dropout_keep.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, bp]
+    L.pvq_note_trainer_dropout_keep.restype = C.c_int
     L.pvq_host_alloc.argtypes = [C.c_size_t]; L.pvq_host_alloc.restype = C.c_void_p
     L.pvq_host_free.argtypes = [C.c_void_p]
     L.pvq_vqt_input_status.argtypes = [vp, vp]; L.pvq_vqt_input_status.restype = C.c_int

@@ -16,6 +16,7 @@
 #include "consumers_host.hpp"
 #include "multi_host.hpp"
 #include "note_model.hpp"
+#include "note_trainer.hpp"
 #include "render_batch.hpp"
 #include "vqt_engine.hpp"
 
@@ -39,6 +40,9 @@ struct pvq_render_batch {
 };
 struct pvq_note_model {
     std::unique_ptr<pvq::NoteModel> impl;
+};
+struct pvq_note_trainer {
+    std::unique_ptr<pvq::NoteTrainer> impl;
 };
 // device-resident ring: the newest buf_size samples are d_ring[w - buf_size, w); compacted when the linear
 // buffer (4 x buf_size) runs out
@@ -1143,6 +1147,63 @@ pvq_status pvq_note_model_set_workspace_limit(pvq_note_model* m, uint64_t bytes)
     try {
         if (!m) return null_handle();
         m->impl->set_workspace_limit(bytes);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+
+// pitchvis_train/train.py:108-162, the optimisation step, on the device (note_trainer.hpp)
+void pvq_note_trainer_hyper_default(pvq_note_trainer_hyper* h) {
+    if (!h) return;
+    h->lr = 1e-5;                  // train.py:111
+    h->beta1 = 0.9;                // torch.optim.Adam's defaults
+    h->beta2 = 0.999;
+    h->eps = 1.1920928955078125e-7;   // train.py:143 torch.finfo(torch.float32).eps
+    h->weight_decay = 5e-4;        // train.py:144
+    h->dropout = 0.1;              // train.py:131-138
+    h->seed = 0;
+}
+pvq_status pvq_note_trainer_create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
+                                   const pvq_note_trainer_hyper* hyper, uint32_t max_batch, pvq_note_trainer** out) {
+    try {
+        if (!out) return null_handle();
+        *out = nullptr;
+        std::unique_ptr<pvq::NoteTrainer> impl;
+        const pvq_status st = pvq::NoteTrainer::create(device_id, params, weights, hyper, max_batch, impl);
+        if (st != PVQ_OK) return st;
+        *out = new pvq_note_trainer{std::move(impl)};
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+void pvq_note_trainer_destroy(pvq_note_trainer* t) {
+    try {
+        delete t;
+    } catch (...) { (void)translate_exception(); }
+}
+pvq_status pvq_note_trainer_step(pvq_note_trainer* t, int mode, const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx,
+                                 uint32_t batch, float* d_loss, float* d_logits, void* stream) {
+    try {
+        if (!t) return null_handle();
+        return t->impl->step(mode, d_db, d_targets, n_rows, idx, batch, d_loss, d_logits, static_cast<hipStream_t>(stream));
+    } catch (...) { return translate_exception(); }
+}
+uint64_t pvq_note_trainer_steps(const pvq_note_trainer* t) { return t ? t->impl->steps() : 0; }
+uint64_t pvq_note_trainer_param_count(const pvq_note_trainer* t) { return t ? t->impl->n_params() : 0; }
+pvq_status pvq_note_trainer_read(pvq_note_trainer* t, int what, float* out_host, size_t capacity) {
+    try {
+        if (!t) return null_handle();
+        return t->impl->read(what, out_host, capacity);
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_note_trainer_dropout_keep(uint64_t seed, uint64_t step, uint32_t layer, uint32_t row, uint32_t col0, uint32_t n, double dropout,
+                                         uint8_t* out_keep) {
+    try {
+        if (!out_keep || !(dropout >= 0.0 && dropout < 1.0)) {
+            pvq::set_last_error("note trainer: out_keep is null or dropout lies outside [0, 1)");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        const uint64_t key = pvq::nt_layer_key(seed, step, layer);
+        const uint32_t threshold = pvq::nt_keep_threshold(dropout);
+        for (uint32_t j = 0; j < n; ++j) out_keep[j] = pvq::nt_keep(key, row, col0 + j, threshold) ? 1 : 0;
         return PVQ_OK;
     } catch (...) { return translate_exception(); }
 }

@@ -1,0 +1,559 @@
+// note_trainer.hip — see note_trainer.hpp.
+//
+// nt_gemm: a workgroup of 4 waves owns a tile of NT_BM = 64 rows x NT_BN = 64 columns; wave w owns rows 16 w .. 16 w + 15 and all 64
+// columns (four 16-column strips): 4 accumulator tiles, 16 registers.  K is walked in stages of NT_BK = 32.  Both operands of a
+// stage go global -> registers -> LDS one stage ahead, double buffered, one barrier per stage, and both lie in LDS as [row or
+// column][k] with a row of 36 floats, so lane l (row or column l & 15, k group g = l >> 4) reads k = 4 g .. 4 g + 3 of a 16-k chunk
+// as one 16-byte read: element i of it is the operand of the chunk's i-th v_mfma_f32_16x16x4_f32, for A and B alike.  An operand
+// whose k runs along its rows in memory (H and W in the NT product, dZ in NN) is copied as it is; one whose k runs down its columns
+// (W in NN, dZ and H in TN) is read in 16-byte pieces along its rows and written to LDS transposed.  Rows, columns and k beyond the
+// matrix are read as zeros and never stored: the K tail of the weight gradient (K = batch) adds exact zeros.
+//
+// Order of every sum is fixed by the shapes alone (tile, stage and split follow from M, N, K; reductions over rows walk them in
+// index order; nothing is accumulated atomically), so equal inputs give equal bits.
+#include "note_trainer.hpp"
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "vqt_engine.hpp"
+
+namespace pvq {
+
+#define PVQ_HIP(call)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (call);                                                                    \
+        if (e_ != hipSuccess) {                                                                    \
+            set_last_error(std::string(#call) + " failed: " + hipGetErrorString(e_));              \
+            return PVQ_ERR_DEVICE;                                                                 \
+        }                                                                                          \
+    } while (0)
+
+namespace {
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+constexpr int NT_THREADS = 256;
+constexpr int NT_LD = NT_BK + 4;   // LDS row: 36 floats, 16-byte aligned rows, 16-byte reads of neighbouring rows on different banks
+constexpr int NT_CONV_OUT = NM_CH * NM_KW + NM_CH;   // 96 conv gradients: weights [16][5], then bias [16]
+
+enum { G_NT = 0, G_NN = 1, G_TN = 2 };
+enum { E_RAW = 0, E_BIAS = 1, E_HIDDEN = 2, E_GATE = 3 };
+
+// what happens to an element of a product before it is stored
+struct Epi {
+    int kind;            // E_RAW: nothing.  E_BIAS: + bias[col].  E_HIDDEN: ReLU(+ bias[col]), then dropout.  E_GATE: * (gate > 0 ? scale : 0)
+    const float* bias;   // [N]
+    const float* gate;   // E_GATE: [M][N], the activation this gradient flows back through (as stored: after ReLU and dropout)
+    float scale;         // 1 / (1 - p) where dropout applies, else 1
+    int drop;            // E_HIDDEN: apply the mask
+    uint32_t threshold;  // keep when the 24-bit draw >= threshold
+    uint64_t key;        // nt_layer_key(seed, step, layer)
+};
+
+struct GemmArgs {
+    const float* A;
+    const float* B;
+    float* C;        // [M][N]; with splits > 1 the partial sums [splits][M][N]
+    uint32_t M, N, K;
+    uint32_t lda, ldb;   // row length of A and B as they lie in memory
+    uint32_t n_ct;       // column tiles
+    uint32_t stages, stages_per_split, splits;
+    Epi e;
+};
+
+__device__ __forceinline__ float epi_apply(const Epi& e, float v, uint32_t row, uint32_t col, uint32_t N) {
+    if (e.kind == E_BIAS) return v + e.bias[col];
+    if (e.kind == E_HIDDEN) {
+        v = fmaxf(v + e.bias[col], 0.0f);
+        if (e.drop) v = nt_keep(e.key, row, col, e.threshold) ? v * e.scale : 0.0f;
+        return v;
+    }
+    if (e.kind == E_GATE) return e.gate[static_cast<size_t>(row) * N + col] > 0.0f ? v * e.scale : 0.0f;
+    return v;
+}
+
+// k along the rows of src: tile rows r0 .. r0 + 63 (bound R), k0 .. k0 + 31 (bound K, a multiple of 4) -> two 16-byte pieces per thread
+__device__ __forceinline__ void fetch_rows(const float* __restrict__ src, uint32_t ld, uint32_t R, uint32_t r0, uint32_t K, uint32_t k0, f32x4 (&r)[2]) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const uint32_t f = threadIdx.x + NT_THREADS * j;
+        const uint32_t row = r0 + (f >> 3), k = k0 + 4 * (f & 7);
+        r[j] = (row < R && k < K) ? *reinterpret_cast<const f32x4*>(src + static_cast<size_t>(row) * ld + k) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+}
+__device__ __forceinline__ void put_rows(float (*dst)[NT_LD], const f32x4 (&r)[2]) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const uint32_t f = threadIdx.x + NT_THREADS * j;
+        *reinterpret_cast<f32x4*>(&dst[f >> 3][4 * (f & 7)]) = r[j];
+    }
+}
+// k down the columns of src ([K][X], X a multiple of 4): tile k0 .. k0 + 31 (bound K), x0 .. x0 + 63 (bound X).  A wave reads 64
+// contiguous bytes of each of 16 rows; thread: k = 16 j + ((tid >> 2) & 15), x = x0 + 4 ((tid & 3) + 4 wave)
+__device__ __forceinline__ void fetch_cols(const float* __restrict__ src, uint32_t ld, uint32_t X, uint32_t x0, uint32_t K, uint32_t k0, f32x4 (&r)[2]) {
+    const uint32_t x = x0 + 4 * ((threadIdx.x & 3) + 4 * (threadIdx.x >> 6));
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const uint32_t k = k0 + 16 * j + ((threadIdx.x >> 2) & 15);
+        r[j] = (k < K && x < X) ? *reinterpret_cast<const f32x4*>(src + static_cast<size_t>(k) * ld + x) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+}
+__device__ __forceinline__ void put_cols(float (*dst)[NT_LD], const f32x4 (&r)[2]) {
+    const uint32_t x = 4 * ((threadIdx.x & 3) + 4 * (threadIdx.x >> 6));
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const uint32_t k = 16 * j + ((threadIdx.x >> 2) & 15);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dst[x + i][k] = r[j][i];
+    }
+}
+
+template <int MODE>
+__device__ __forceinline__ void fetch_ab(const GemmArgs& a, uint32_t m0, uint32_t n0, uint32_t k0, f32x4 (&ra)[2], f32x4 (&rb)[2]) {
+    if constexpr (MODE == G_TN) fetch_cols(a.A, a.lda, a.M, m0, a.K, k0, ra);
+    else fetch_rows(a.A, a.lda, a.M, m0, a.K, k0, ra);
+    if constexpr (MODE == G_NT) fetch_rows(a.B, a.ldb, a.N, n0, a.K, k0, rb);
+    else fetch_cols(a.B, a.ldb, a.N, n0, a.K, k0, rb);
+}
+template <int MODE>
+__device__ __forceinline__ void put_ab(float (*sa)[NT_LD], float (*sb)[NT_LD], const f32x4 (&ra)[2], const f32x4 (&rb)[2]) {
+    if constexpr (MODE == G_TN) put_cols(sa, ra);
+    else put_rows(sa, ra);
+    if constexpr (MODE == G_NT) put_rows(sb, rb);
+    else put_cols(sb, rb);
+}
+
+// G_NT: C = A[M][K] * B[N][K]^T.  G_NN: C = A[M][K] * B[K][N].  G_TN: C = A[K][M]^T * B[K][N].
+template <int MODE>
+__global__ __launch_bounds__(NT_THREADS) void nt_gemm(const GemmArgs a) {
+    __shared__ __attribute__((aligned(16))) float s_a[2][NT_BM][NT_LD];
+    __shared__ __attribute__((aligned(16))) float s_b[2][NT_BN][NT_LD];
+    const uint32_t ct = blockIdx.x % a.n_ct, rt = blockIdx.x / a.n_ct, z = blockIdx.y;
+    const uint32_t m0 = NT_BM * rt, n0 = NT_BN * ct;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
+    const uint32_t st0 = z * a.stages_per_split, st1 = min(st0 + a.stages_per_split, a.stages);
+
+    f32x4 ra[2], rb[2];
+    f32x4 acc[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) acc[s] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    if (st0 < st1) {
+        fetch_ab<MODE>(a, m0, n0, NT_BK * st0, ra, rb);
+        put_ab<MODE>(s_a[0], s_b[0], ra, rb);
+    }
+    __syncthreads();
+    for (uint32_t st = st0; st < st1; ++st) {
+        const int cur = (st - st0) & 1;
+        const bool more = st + 1 < st1;
+        if (more) fetch_ab<MODE>(a, m0, n0, NT_BK * (st + 1), ra, rb);
+#pragma unroll
+        for (int ch = 0; ch < NT_BK / 16; ++ch) {
+            const f32x4 av = *reinterpret_cast<const f32x4*>(&s_a[cur][16 * wave + c][16 * ch + 4 * g]);
+            f32x4 bv[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) bv[s] = *reinterpret_cast<const f32x4*>(&s_b[cur][16 * s + c][16 * ch + 4 * g]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[s][i], acc[s], 0, 0, 0);
+        }
+        if (more) put_ab<MODE>(s_a[cur ^ 1], s_b[cur ^ 1], ra, rb);
+        __syncthreads();
+    }
+
+    // accumulator layout of a 16 x 16 tile: lane l holds column l & 15, rows 4 (l >> 4) + reg
+    float* dst = a.C + (a.splits > 1 ? static_cast<size_t>(z) * a.M * a.N : 0);
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+        const uint32_t row = m0 + 16 * wave + 4 * g + reg;
+        if (row >= a.M) continue;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const uint32_t col = n0 + 16 * s + c;
+            if (col >= a.N) continue;
+            const float v = acc[s][reg];
+            dst[static_cast<size_t>(row) * a.N + col] = a.splits > 1 ? v : epi_apply(a.e, v, row, col, a.N);
+        }
+    }
+}
+
+// C[i] = epilogue(part[0][i] + part[1][i] + ...), the splits added in their order
+__global__ __launch_bounds__(NT_THREADS) void nt_gemm_finish(const float* __restrict__ part, float* __restrict__ C, uint32_t M, uint32_t N, uint32_t splits, const Epi e) {
+    const size_t mn = static_cast<size_t>(M) * N;
+    const size_t i = static_cast<size_t>(blockIdx.x) * NT_THREADS + threadIdx.x;
+    if (i >= mn) return;
+    float v = part[i];
+    for (uint32_t z = 1; z < splits; ++z) v += part[z * mn + i];
+    C[i] = epi_apply(e, v, static_cast<uint32_t>(i / N), static_cast<uint32_t>(i % N), N);
+}
+
+// the two conv positions a pooled position covers (train.py:89-90), as nm_conv_fc1 evaluates them: bias first, taps in order, fused
+__device__ __forceinline__ void conv_pair(const float* w5, float cb, const float* x, float& e, float& o) {
+    e = cb;
+    o = cb;
+#pragma unroll
+    for (int j = 0; j < NM_KW; ++j) {
+        e = fmaf(w5[j], x[j], e);
+        o = fmaf(w5[j], x[2 + j], o);
+    }
+}
+
+// feat[b][c * o_pool + p] = max(conv[c][2 p], conv[c][2 p + 1], 0) of the window that ends at row idx[b] (train.py:17-21,46,89-91)
+__global__ __launch_bounds__(NT_THREADS) void nt_features(const float* __restrict__ db, const uint32_t* __restrict__ idx, const float* __restrict__ conv,
+                                                          float* __restrict__ feat, uint32_t n_bins, uint32_t t_frames, uint32_t L, uint32_t o_pool) {
+    extern __shared__ float s_x[];   // the window, L floats
+    __shared__ float s_w[NT_CONV_OUT];
+    const uint32_t b = blockIdx.x;
+    const float* x = db + (static_cast<size_t>(idx[b]) - (t_frames - 1)) * n_bins;
+    for (uint32_t i = threadIdx.x; i < L; i += NT_THREADS) s_x[i] = x[i];
+    if (threadIdx.x < NT_CONV_OUT) s_w[threadIdx.x] = conv[threadIdx.x];
+    __syncthreads();
+    const uint32_t F = NM_CH * o_pool;
+    float* dst = feat + static_cast<size_t>(b) * F;
+    for (uint32_t i = threadIdx.x; i < F; i += NT_THREADS) {
+        const uint32_t ch = i / o_pool, p = i - ch * o_pool;
+        float e, o;
+        conv_pair(s_w + ch * NM_KW, s_w[NM_CH * NM_KW + ch], s_x + 4 * p, e, o);   // reads x[4 p .. 4 p + 6] <= x[2 (O_conv - 1) + 4] <= x[L - 1]
+        dst[i] = fmaxf(fmaxf(e, o), 0.0f);
+    }
+}
+
+// Row b's share of the conv gradients: dFeat goes to the larger of each pair (the first on a tie, as max_pool1d), through the ReLU
+// (gradient 0 at 0), to the five taps and the bias.  Thread (channel ch = tid >> 4, q = tid & 15) walks pooled positions q, q + 16, ..
+// in order; the 16 partial sums of a channel are then added in q order.  part[b][0 .. 79] weights [16][5], [80 .. 95] bias.
+__global__ __launch_bounds__(NT_THREADS) void nt_conv_grad(const float* __restrict__ db, const uint32_t* __restrict__ idx, const float* __restrict__ conv,
+                                                           const float* __restrict__ dfeat, float* __restrict__ part, uint32_t n_bins, uint32_t t_frames,
+                                                           uint32_t L, uint32_t o_pool) {
+    extern __shared__ float s_x[];
+    __shared__ float s_w[NT_CONV_OUT];
+    __shared__ float s_red[NT_THREADS][NM_KW + 1];
+    const uint32_t b = blockIdx.x;
+    const float* x = db + (static_cast<size_t>(idx[b]) - (t_frames - 1)) * n_bins;
+    for (uint32_t i = threadIdx.x; i < L; i += NT_THREADS) s_x[i] = x[i];
+    if (threadIdx.x < NT_CONV_OUT) s_w[threadIdx.x] = conv[threadIdx.x];
+    __syncthreads();
+    const uint32_t ch = threadIdx.x >> 4, q = threadIdx.x & 15;
+    const float* g_row = dfeat + static_cast<size_t>(b) * NM_CH * o_pool + static_cast<size_t>(ch) * o_pool;
+    float acc[NM_KW + 1];
+#pragma unroll
+    for (int j = 0; j <= NM_KW; ++j) acc[j] = 0.0f;
+    for (uint32_t p = q; p < o_pool; p += 16) {
+        float e, o;
+        conv_pair(s_w + ch * NM_KW, s_w[NM_CH * NM_KW + ch], s_x + 4 * p, e, o);
+        const bool second = o > e;
+        if ((second ? o : e) > 0.0f) {
+            const float gv = g_row[p];
+            const float* xs = s_x + 4 * p + (second ? 2 : 0);
+#pragma unroll
+            for (int j = 0; j < NM_KW; ++j) acc[j] = fmaf(gv, xs[j], acc[j]);
+            acc[NM_KW] += gv;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j <= NM_KW; ++j) s_red[threadIdx.x][j] = acc[j];
+    __syncthreads();
+    if (threadIdx.x < NT_CONV_OUT) {
+        const uint32_t c2 = threadIdx.x / (NM_KW + 1), j = threadIdx.x % (NM_KW + 1);
+        float s = 0.0f;
+        for (int k = 0; k < 16; ++k) s += s_red[16 * c2 + k][j];
+        part[static_cast<size_t>(b) * NT_CONV_OUT + (j < NM_KW ? c2 * NM_KW + j : NM_CH * NM_KW + c2)] = s;
+    }
+}
+// grad[i] = part[0][i] + part[1][i] + ... in row order
+__global__ __launch_bounds__(128) void nt_conv_reduce(const float* __restrict__ part, float* __restrict__ grad, uint32_t batch) {
+    if (threadIdx.x >= NT_CONV_OUT) return;
+    float s = 0.0f;
+    for (uint32_t b = 0; b < batch; ++b) s += part[static_cast<size_t>(b) * NT_CONV_OUT + threadIdx.x];
+    grad[threadIdx.x] = s;
+}
+
+// out[col] = sum over rows of d[row][col]: thread (phase = tid >> 6, column) adds rows phase, phase + 4, .. in order, the four phases
+// are added in order
+__global__ __launch_bounds__(NT_THREADS) void nt_bias_grad(const float* __restrict__ d, float* __restrict__ out, uint32_t M, uint32_t N) {
+    __shared__ float s_red[4][64];
+    const uint32_t col = 64 * blockIdx.x + (threadIdx.x & 63), ph = threadIdx.x >> 6;
+    float s = 0.0f;
+    if (col < N)
+        for (uint32_t r = ph; r < M; r += 4) s += d[static_cast<size_t>(r) * N + col];
+    s_red[ph][threadIdx.x & 63] = s;
+    __syncthreads();
+    if (ph == 0 && col < N) out[col] = ((s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + s_red[2][threadIdx.x]) + s_red[3][threadIdx.x];
+}
+
+// One workgroup per row of the batch, one thread per output.  loss = max(z, 0) - z y + log1p(exp(-|z|)); dz = (sigmoid(z) - y) * inv_n
+// with inv_n = 1 / (batch * 128) (train.py:153-156: BCELoss's mean reduction, backward).  The row's 128 losses are added as a tree in double.
+__global__ __launch_bounds__(NM_OUT) void nt_loss(const float* __restrict__ z, const float* __restrict__ targets, const uint32_t* __restrict__ idx,
+                                                  float inv_n, float* __restrict__ dz, float* __restrict__ logits_out, double* __restrict__ row_loss) {
+    __shared__ double s_red[NM_OUT];
+    const uint32_t b = blockIdx.x, j = threadIdx.x;
+    const float zv = z[static_cast<size_t>(b) * NM_OUT + j];
+    const float y = targets[static_cast<size_t>(idx[b]) * NM_OUT + j];
+    const float l = fmaxf(zv, 0.0f) - zv * y + log1pf(expf(-fabsf(zv)));
+    dz[static_cast<size_t>(b) * NM_OUT + j] = (1.0f / (1.0f + expf(-zv)) - y) * inv_n;
+    if (logits_out) logits_out[static_cast<size_t>(b) * NM_OUT + j] = zv;
+    s_red[j] = static_cast<double>(l);
+    __syncthreads();
+    for (int s = NM_OUT / 2; s > 0; s >>= 1) {
+        if (j < static_cast<uint32_t>(s)) s_red[j] += s_red[j + s];
+        __syncthreads();
+    }
+    if (j == 0) row_loss[b] = s_red[0];
+}
+__global__ __launch_bounds__(NT_THREADS) void nt_loss_final(const double* __restrict__ row_loss, uint32_t batch, double inv_n, float* __restrict__ loss) {
+    __shared__ double s_red[NT_THREADS];
+    double s = 0.0;
+    for (uint32_t b = threadIdx.x; b < batch; b += NT_THREADS) s += row_loss[b];
+    s_red[threadIdx.x] = s;
+    __syncthreads();
+    for (int k = NT_THREADS / 2; k > 0; k >>= 1) {
+        if (threadIdx.x < static_cast<uint32_t>(k)) s_red[threadIdx.x] += s_red[threadIdx.x + k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *loss = static_cast<float>(s_red[0] * inv_n);
+}
+
+// torch.optim.Adam with L2 weight decay (train.py:141-144), four elements per thread.  The element's arithmetic is done in double
+// and rounded once per stored value: the kernel moves 28 bytes per element and has the time.
+__global__ __launch_bounds__(NT_THREADS) void nt_adam(f32x4* __restrict__ w, const f32x4* __restrict__ g, f32x4* __restrict__ m, f32x4* __restrict__ v,
+                                                      size_t n4, const NtAdamStep s) {
+    const size_t i = static_cast<size_t>(blockIdx.x) * NT_THREADS + threadIdx.x;
+    if (i >= n4) return;
+    f32x4 wv = w[i], mv = m[i], vv = v[i];
+    const f32x4 gv = g[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double wd = static_cast<double>(wv[k]);
+        const double gd = static_cast<double>(gv[k]) + s.weight_decay * wd;
+        const double md = s.beta1 * static_cast<double>(mv[k]) + (1.0 - s.beta1) * gd;
+        const double vd = s.beta2 * static_cast<double>(vv[k]) + (1.0 - s.beta2) * gd * gd;
+        mv[k] = static_cast<float>(md);
+        vv[k] = static_cast<float>(vd);
+        wv[k] = static_cast<float>(wd - s.step_size * md / (sqrt(vd) * s.inv_bc2_sqrt + s.eps));
+    }
+    w[i] = wv;
+    m[i] = mv;
+    v[i] = vv;
+}
+
+size_t round64(size_t n) { return (n + 63) & ~static_cast<size_t>(63); }
+
+// one product; a split one goes through `part` and nt_gemm_finish
+void gemm(int mode, const float* A, const float* B, float* C, uint32_t M, uint32_t N, uint32_t K, uint32_t lda, uint32_t ldb, const Epi& e, float* part,
+          hipStream_t stream) {
+    GemmArgs a{};
+    a.A = A;
+    a.B = B;
+    a.M = M;
+    a.N = N;
+    a.K = K;
+    a.lda = lda;
+    a.ldb = ldb;
+    a.n_ct = (N + NT_BN - 1) / NT_BN;
+    a.stages = (K + NT_BK - 1) / NT_BK;
+    const uint32_t want = nt_splits(M, N, K);
+    a.stages_per_split = (a.stages + want - 1) / want;
+    a.splits = (a.stages + a.stages_per_split - 1) / a.stages_per_split;   // no empty split
+    a.C = a.splits > 1 ? part : C;
+    a.e = e;
+    const dim3 grid(((M + NT_BM - 1) / NT_BM) * a.n_ct, a.splits);
+    if (mode == G_NT) hipLaunchKernelGGL(nt_gemm<G_NT>, grid, dim3(NT_THREADS), 0, stream, a);
+    else if (mode == G_NN) hipLaunchKernelGGL(nt_gemm<G_NN>, grid, dim3(NT_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL(nt_gemm<G_TN>, grid, dim3(NT_THREADS), 0, stream, a);
+    if (a.splits > 1) {
+        const size_t mn = static_cast<size_t>(M) * N;
+        hipLaunchKernelGGL(nt_gemm_finish, dim3(static_cast<uint32_t>((mn + NT_THREADS - 1) / NT_THREADS)), dim3(NT_THREADS), 0, stream, part, C, M, N,
+                           a.splits, e);
+    }
+}
+}  // namespace
+
+NoteTrainer::~NoteTrainer() {
+    if (device_id_ < 0) return;
+    (void)hipSetDevice(device_id_);
+    (void)hipDeviceSynchronize();
+    for (int s = 0; s < 2; ++s) {
+        if (idx_copied_[s]) (void)hipEventDestroy(idx_copied_[s]);
+        if (h_idx_[s]) (void)hipHostFree(h_idx_[s]);
+    }
+    if (d_arena_) (void)hipFree(d_arena_);
+    if (d_ws_) (void)hipFree(d_ws_);
+}
+
+pvq_status NoteTrainer::create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
+                               const pvq_note_trainer_hyper* hyper, uint32_t max_batch, std::unique_ptr<NoteTrainer>& out) {
+    out.reset();
+    NoteModelDims d;
+    std::string err;
+    pvq_status st = note_model_check(params, weights, d, err);
+    if (st == PVQ_OK) st = note_trainer_check_hyper(hyper, max_batch, err);
+    if (st != PVQ_OK) {
+        set_last_error(err);
+        return st;
+    }
+    std::unique_ptr<NoteTrainer> t(new NoteTrainer());
+    t->device_id_ = device_id < 0 ? -1 : device_id;
+    t->lay_ = note_trainer_layout(d);
+    t->hyper_ = *hyper;
+    t->max_batch_ = max_batch;
+    if (device_id >= 0) {
+        PVQ_HIP(hipSetDevice(device_id));
+        const size_t n = t->lay_.n_params;
+        const std::vector<float> arena = note_trainer_arena(t->lay_, *weights);
+        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_arena_), 4 * n * sizeof(float)));
+        PVQ_HIP(hipMemcpy(t->d_arena_, arena.data(), n * sizeof(float), hipMemcpyHostToDevice));
+        PVQ_HIP(hipMemset(t->d_arena_ + n, 0, 3 * n * sizeof(float)));
+        // the workspace, sized once from max_batch
+        const size_t B = max_batch;
+        size_t at = 0;
+        auto take = [&at](size_t floats) {
+            const size_t here = at;
+            at += round64(floats);
+            return here;
+        };
+        t->ws_feat_ = take(B * d.n_features);
+        t->ws_dfeat_ = take(B * d.n_features);
+        t->ws_h_ = take((d.layers + 1) * round64(B * d.mlp));
+        t->ws_da_ = take(2 * round64(B * d.mlp));
+        t->ws_z_ = take(B * NM_OUT);
+        t->ws_dz_ = take(B * NM_OUT);
+        t->ws_convpart_ = take(B * NT_CONV_OUT);
+        t->ws_rowloss_ = take(2 * B);   // doubles
+        t->ws_part_ = take(NT_PART_FLOATS);
+        t->ws_idx_ = take(B);           // uint32
+        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_ws_), at * sizeof(float)));
+        for (int s = 0; s < 2; ++s) {
+            PVQ_HIP(hipHostMalloc(reinterpret_cast<void**>(&t->h_idx_[s]), B * sizeof(uint32_t), hipHostMallocDefault));
+            PVQ_HIP(hipEventCreateWithFlags(&t->idx_copied_[s], hipEventDisableTiming));
+        }
+    }
+    out = std::move(t);
+    return PVQ_OK;
+}
+
+pvq_status NoteTrainer::step(int mode, const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx, uint32_t batch, float* d_loss,
+                             float* d_logits, hipStream_t stream) {
+    const NoteModelDims& d = lay_.d;
+    std::string err;
+    const pvq_status st = note_trainer_check_step(d, max_batch_, mode, d_db, d_targets, n_rows, idx, batch, err);
+    if (st != PVQ_OK) {
+        set_last_error(err);
+        return st;
+    }
+    if (device_id_ < 0) {
+        set_last_error("the note trainer runs on a GPU; this handle has none");
+        return PVQ_ERR_NO_DEVICE;
+    }
+    PVQ_HIP(hipSetDevice(device_id_));
+    // idx -> pinned slot -> device.  The slot is free once the copy queued from it two calls ago has run.
+    const int slot = static_cast<int>(calls_++ & 1);
+    if (idx_pending_[slot]) PVQ_HIP(hipEventSynchronize(idx_copied_[slot]));
+    std::memcpy(h_idx_[slot], idx, batch * sizeof(uint32_t));
+    uint32_t* d_idx = reinterpret_cast<uint32_t*>(d_ws_ + ws_idx_);
+    PVQ_HIP(hipMemcpyAsync(d_idx, h_idx_[slot], batch * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    PVQ_HIP(hipEventRecord(idx_copied_[slot], stream));
+    idx_pending_[slot] = true;
+
+    const size_t n = lay_.n_params;
+    const float* w = d_arena_;
+    float* grad = d_arena_ + n;
+    float* feat = d_ws_ + ws_feat_;
+    float* dfeat = d_ws_ + ws_dfeat_;
+    const size_t h_stride = round64(static_cast<size_t>(max_batch_) * d.mlp);
+    auto H = [&](uint32_t i) { return d_ws_ + ws_h_ + i * h_stride; };
+    float* dA[2] = {d_ws_ + ws_da_, d_ws_ + ws_da_ + h_stride};
+    float* Z = d_ws_ + ws_z_;
+    float* dZ = d_ws_ + ws_dz_;
+    float* part = d_ws_ + ws_part_;
+    double* row_loss = reinterpret_cast<double*>(d_ws_ + ws_rowloss_);
+    const uint32_t F = d.n_features, mlp = d.mlp;
+    const bool train = mode != PVQ_TRAIN_EVAL;
+    const uint32_t threshold = nt_keep_threshold(hyper_.dropout);
+    const bool drop = train && threshold > 0;
+    const float scale = drop ? static_cast<float>(1.0 / (1.0 - hyper_.dropout)) : 1.0f;
+    const size_t x_bytes = static_cast<size_t>(d.L) * sizeof(float);
+
+    // forward (train.py:87-99)
+    hipLaunchKernelGGL(nt_features, dim3(batch), dim3(NT_THREADS), x_bytes, stream, d_db, d_idx, w + lay_.conv_w.at, feat, d.n_bins, d.t_frames, d.L, d.o_pool);
+    Epi e{};
+    e.kind = E_HIDDEN;
+    e.bias = w + lay_.fc1_b.at;
+    e.scale = 1.0f;
+    gemm(G_NT, feat, w + lay_.fc1_w.at, H(0), batch, mlp, F, F, F, e, part, stream);
+    for (uint32_t i = 0; i < d.layers; ++i) {
+        e.bias = w + lay_.layer_b[i].at;
+        e.drop = drop ? 1 : 0;
+        e.scale = scale;
+        e.threshold = threshold;
+        e.key = nt_layer_key(hyper_.seed, steps_, i);
+        gemm(G_NT, H(i), w + lay_.layer_w[i].at, H(i + 1), batch, mlp, mlp, mlp, mlp, e, part, stream);
+    }
+    e = Epi{};
+    e.kind = E_BIAS;
+    e.bias = w + lay_.out_b.at;
+    gemm(G_NT, H(d.layers), w + lay_.out_w.at, Z, batch, NM_OUT, mlp, mlp, mlp, e, part, stream);
+    const double inv_n = 1.0 / (static_cast<double>(batch) * NM_OUT);
+    hipLaunchKernelGGL(nt_loss, dim3(batch), dim3(NM_OUT), 0, stream, Z, d_targets, d_idx, static_cast<float>(inv_n), dZ, d_logits, row_loss);
+    if (d_loss) hipLaunchKernelGGL(nt_loss_final, dim3(1), dim3(NT_THREADS), 0, stream, row_loss, batch, inv_n, d_loss);
+
+    if (train) {
+        // backward: the output layer, the hidden layers from the last to the first, fc1, the conv
+        Epi raw{};
+        raw.kind = E_RAW;
+        Epi gate{};
+        gate.kind = E_GATE;
+        gemm(G_TN, dZ, H(d.layers), grad + lay_.out_w.at, NM_OUT, mlp, batch, NM_OUT, mlp, raw, part, stream);
+        hipLaunchKernelGGL(nt_bias_grad, dim3((NM_OUT + 63) / 64), dim3(NT_THREADS), 0, stream, dZ, grad + lay_.out_b.at, batch, static_cast<uint32_t>(NM_OUT));
+        int cur = 0;
+        gate.gate = H(d.layers);
+        gate.scale = d.layers > 0 ? scale : 1.0f;   // (fc1 has no dropout behind it, train.py:93)
+        gemm(G_NN, dZ, w + lay_.out_w.at, dA[cur], batch, mlp, NM_OUT, NM_OUT, mlp, gate, part, stream);
+        for (uint32_t i = d.layers; i >= 1; --i) {
+            gemm(G_TN, dA[cur], H(i - 1), grad + lay_.layer_w[i - 1].at, mlp, mlp, batch, mlp, mlp, raw, part, stream);
+            hipLaunchKernelGGL(nt_bias_grad, dim3((mlp + 63) / 64), dim3(NT_THREADS), 0, stream, dA[cur], grad + lay_.layer_b[i - 1].at, batch, mlp);
+            gate.gate = H(i - 1);
+            gate.scale = i - 1 > 0 ? scale : 1.0f;
+            gemm(G_NN, dA[cur], w + lay_.layer_w[i - 1].at, dA[cur ^ 1], batch, mlp, mlp, mlp, mlp, gate, part, stream);
+            cur ^= 1;
+        }
+        gemm(G_TN, dA[cur], feat, grad + lay_.fc1_w.at, mlp, F, batch, mlp, F, raw, part, stream);
+        hipLaunchKernelGGL(nt_bias_grad, dim3((mlp + 63) / 64), dim3(NT_THREADS), 0, stream, dA[cur], grad + lay_.fc1_b.at, batch, mlp);
+        gemm(G_NN, dA[cur], w + lay_.fc1_w.at, dfeat, batch, F, mlp, mlp, F, raw, part, stream);
+        float* conv_part = d_ws_ + ws_convpart_;
+        hipLaunchKernelGGL(nt_conv_grad, dim3(batch), dim3(NT_THREADS), x_bytes, stream, d_db, d_idx, w + lay_.conv_w.at, dfeat, conv_part, d.n_bins, d.t_frames,
+                           d.L, d.o_pool);
+        hipLaunchKernelGGL(nt_conv_reduce, dim3(1), dim3(128), 0, stream, conv_part, grad + lay_.conv_w.at, batch);
+        if (mode == PVQ_TRAIN_STEP) {
+            const size_t n4 = n / 4;
+            hipLaunchKernelGGL(nt_adam, dim3(static_cast<uint32_t>((n4 + NT_THREADS - 1) / NT_THREADS)), dim3(NT_THREADS), 0, stream,
+                               reinterpret_cast<f32x4*>(d_arena_), reinterpret_cast<const f32x4*>(grad), reinterpret_cast<f32x4*>(d_arena_ + 2 * n),
+                               reinterpret_cast<f32x4*>(d_arena_ + 3 * n), n4, note_trainer_adam_step(hyper_, steps_ + 1));
+            ++steps_;
+        }
+    }
+    PVQ_HIP(hipGetLastError());
+    return PVQ_OK;
+}
+
+pvq_status NoteTrainer::read(int what, float* out, size_t capacity) {
+    if (what < PVQ_TRAIN_WEIGHTS || what > PVQ_TRAIN_ADAM_V) {
+        set_last_error("note trainer: unknown array");
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (!out || capacity < lay_.n_params) {
+        set_last_error("note trainer: the read-back buffer is null or holds fewer than " + std::to_string(lay_.n_params) + " floats");
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (device_id_ < 0) {
+        set_last_error("the note trainer's state lives on a GPU; this handle has none");
+        return PVQ_ERR_NO_DEVICE;
+    }
+    PVQ_HIP(hipSetDevice(device_id_));
+    PVQ_HIP(hipDeviceSynchronize());
+    PVQ_HIP(hipMemcpy(out, d_arena_ + static_cast<size_t>(what) * lay_.n_params, lay_.n_params * sizeof(float), hipMemcpyDeviceToHost));
+    return PVQ_OK;
+}
+
+}  // namespace pvq

@@ -1,0 +1,63 @@
+// note_trainer.hpp — the trainer's optimisation step (pitchvis_train/train.py:108-162) for the note model of note_model.hpp, on the
+// GPU: forward in training mode over a batch of rows gathered by index from a dataset in device memory, BCE loss, backward, Adam.
+// The handle owns the parameters in PyTorch layout ([out][in]: they change every step, so the inference kernels' host-packed operand
+// is of no use), their gradients and Adam's moments as four equal arenas (note_trainer_plan.hpp), and a workspace sized once from
+// max_batch; a step allocates nothing.
+//
+// Kernels (note_trainer.hip), all matrix work exact f32 on v_mfma_f32_16x16x4_f32:
+//   nt_features     conv + ReLU + pool of every gathered row -> feat [batch][n_features]
+//   nt_gemm<MODE>   one 64 x 64 tile kernel in three operand orientations: NT  Z = H W^T (forward), NN  dH = dZ W (data gradient,
+//                   W transposed while it is staged into LDS), TN  dW = dZ^T H (weight gradient, K = batch, tail rows read as zeros);
+//                   bias / ReLU / dropout and the backward gate live in its epilogue.  A product with few tiles is split along K
+//                   into partial sums that nt_gemm_finish adds in split order (a fixed order: nothing is accumulated atomically)
+//   nt_loss, nt_loss_final   stable BCE from the logits, dZ of the output layer, the mean as a two-level sum in double
+//   nt_bias_grad    column sums in a fixed order
+//   nt_conv_grad, nt_conv_reduce   dFeat through pool and ReLU to the 96 conv gradients: per row, then over rows, fixed order
+//   nt_adam         one launch over the arena
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <memory>
+
+#include "../../include/pvq.h"
+#include "note_trainer_plan.hpp"
+
+namespace pvq {
+
+class NoteTrainer {
+   public:
+    // every check runs before any device is touched.  device_id < 0: a host-only object (step returns PVQ_ERR_NO_DEVICE after its
+    // argument checks, read returns it at once).
+    static pvq_status create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
+                             const pvq_note_trainer_hyper* hyper, uint32_t max_batch, std::unique_ptr<NoteTrainer>& out);
+    ~NoteTrainer();
+    const NoteModelDims& dims() const { return lay_.d; }
+    size_t n_params() const { return lay_.n_params; }
+    uint64_t steps() const { return steps_; }
+    // idx: HOST array.  Asynchronous on `stream`; uses the handle's workspace, so one stream at a time.
+    pvq_status step(int mode, const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx, uint32_t batch, float* d_loss,
+                    float* d_logits, hipStream_t stream);
+    // the arena `what` names, n_params floats in state_dict order -> host.  Synchronises the device.
+    pvq_status read(int what, float* out, size_t capacity);
+
+   private:
+    NoteTrainer() = default;
+    int device_id_ = -1;
+    NoteTrainerLayout lay_;
+    pvq_note_trainer_hyper hyper_{};
+    uint32_t max_batch_ = 0;
+    uint64_t steps_ = 0;     // completed PVQ_TRAIN_STEP calls: Adam's t - 1, and the step the dropout mask is keyed by
+    uint64_t calls_ = 0;     // picks the pinned slot
+    float* d_arena_ = nullptr;   // weights, gradients, m, v: 4 x n_params
+    float* d_ws_ = nullptr;
+    uint32_t* h_idx_[2] = {nullptr, nullptr};   // pinned staging of idx, two slots so that a call may be queued behind a running one
+    hipEvent_t idx_copied_[2] = {nullptr, nullptr};
+    bool idx_pending_[2] = {false, false};
+    // float offsets into the workspace
+    size_t ws_feat_ = 0, ws_dfeat_ = 0, ws_h_ = 0, ws_da_ = 0, ws_z_ = 0, ws_dz_ = 0, ws_convpart_ = 0, ws_rowloss_ = 0, ws_part_ = 0, ws_idx_ = 0;
+};
+
+}  // namespace pvq

@@ -1,0 +1,82 @@
+// note_trainer_plan.hpp — host side of the note trainer (note_trainer.hip): the layout of the parameter arena, the argument checks,
+// the per-step Adam constants, the split-K rule of the GEMMs and the dropout mask function.  Plain data in, plain data out: no HIP,
+// no device pointer, no environment (the note_model_plan.cpp pattern).
+//
+// The step is pitchvis_train/train.py:108-162: forward in training mode (train.py:87-99), BCELoss, backward, optim.Adam with weight
+// decay (train.py:141-144).
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/pvq.h"
+#include "note_model_plan.hpp"
+
+#ifdef __HIPCC__
+#define PVQ_NT_HD __host__ __device__
+#else
+#define PVQ_NT_HD
+#endif
+
+namespace pvq {
+
+constexpr uint32_t NT_MAX_BATCH = 4096;
+constexpr int NT_BM = 64;   // rows of a GEMM workgroup tile: 4 waves x one MFMA row tile of 16
+constexpr int NT_BN = 64;   // columns: 4 MFMA column strips of 16, all held by every wave
+constexpr int NT_BK = 32;   // K of a stage: two chunks of four 16x16x4 steps
+constexpr size_t NT_PART_FLOATS = size_t(4) << 20;   // split-K partial sums: splits * M * N never exceeds this (nt_splits)
+
+// One tensor of the flat parameter arena.  The arena is the state_dict in its own order: conv1.weight [16][5], conv1.bias [16],
+// fc1.weight [mlp][n_features], fc1.bias [mlp], layers.i.weight [mlp][mlp], layers.i.bias [mlp] for i = 0 .., output.weight
+// [128][mlp], output.bias [128].  Every offset is a multiple of 4 floats (every size is), so float4 access is aligned.
+struct NtTensor {
+    size_t at = 0, n = 0;
+};
+struct NoteTrainerLayout {
+    NoteModelDims d;
+    NtTensor conv_w, conv_b, fc1_w, fc1_b, out_w, out_b;
+    std::vector<NtTensor> layer_w, layer_b;
+    size_t n_params = 0;
+};
+NoteTrainerLayout note_trainer_layout(const NoteModelDims& d);
+// the arena filled from host weights
+std::vector<float> note_trainer_arena(const NoteTrainerLayout& lay, const pvq_note_model_weights& w);
+
+// the hyper-parameter and max_batch ranges of include/pvq.h; err receives the text
+pvq_status note_trainer_check_hyper(const pvq_note_trainer_hyper* h, uint32_t max_batch, std::string& err);
+// the checks of a step that need no device: mode, pointers, n_rows, batch, every index.  err receives the text
+pvq_status note_trainer_check_step(const NoteModelDims& d, uint32_t max_batch, int mode, const void* d_db, const void* d_targets, size_t n_rows,
+                                   const uint32_t* idx, uint32_t batch, std::string& err);
+
+// The dropout mask (include/pvq.h states it in full).  nt_mix is the splitmix64 finaliser; the layer key folds seed, step and layer
+// on the host, the kernel does one nt_mix per element.
+PVQ_NT_HD inline uint64_t nt_mix(uint64_t z) {
+    z ^= z >> 30;
+    z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27;
+    z *= 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return z;
+}
+inline uint64_t nt_layer_key(uint64_t seed, uint64_t step, uint32_t layer) {
+    return nt_mix(nt_mix(seed + 0x9E3779B97F4A7C15ull * (step + 1)) ^ static_cast<uint64_t>(layer));
+}
+inline uint32_t nt_keep_threshold(double dropout) { return static_cast<uint32_t>(dropout * 16777216.0); }   // floor(p 2^24)
+PVQ_NT_HD inline bool nt_keep(uint64_t layer_key, uint32_t row, uint32_t col, uint32_t threshold) {
+    return static_cast<uint32_t>(nt_mix(layer_key ^ ((static_cast<uint64_t>(row) << 32) | col)) >> 40) >= threshold;
+}
+
+// Adam's per-step scalars (torch.optim.Adam, train.py:141-144), in double: step_size = lr / (1 - beta1^t), inv_bc2_sqrt = 1 / sqrt(1 - beta2^t)
+struct NtAdamStep {
+    double beta1, beta2, eps, weight_decay, step_size, inv_bc2_sqrt;
+};
+NtAdamStep note_trainer_adam_step(const pvq_note_trainer_hyper& h, uint64_t t);
+
+// K splits of a GEMM of m x n over k: enough workgroups to fill the chip (a fixed 512, not the device's count: the split decides
+// the summation order, and equal calls must give equal bits on every device), at least 8 K stages per split, at most 8 splits, and
+// splits * m * n within NT_PART_FLOATS.  1: no split, the GEMM writes its result itself.
+uint32_t nt_splits(uint32_t m, uint32_t n, uint32_t k);
+
+}  // namespace pvq

@@ -41,6 +41,35 @@ def _weights_dict(sd) -> dict:
     return out
 
 
+def _c_weights(params: "NoteModelParams", weights):
+    """(CNoteModelWeights over the arrays of a state_dict-named dict, what must stay alive while it is used)"""
+    w = _weights_dict(weights)
+    L, _, _, n_feat = params.sizes()
+    want = {"conv1.weight": 16 * 5, "conv1.bias": 16, "fc1.weight": params.mlp_size * n_feat, "fc1.bias": params.mlp_size,
+            "output.weight": N_OUT * params.mlp_size, "output.bias": N_OUT}
+    for i in range(params.mlp_layers):
+        want[f"layers.{i}.weight"] = params.mlp_size * params.mlp_size
+        want[f"layers.{i}.bias"] = params.mlp_size
+    cw = _lib.CNoteModelWeights()
+    in_range = (3 <= params.n_bins <= 1024 and 1 <= params.t_frames <= 8 and L >= 8 and 16 <= params.mlp_size <= 4096
+                and params.mlp_size % 16 == 0 and 0 <= params.mlp_layers <= 8)
+    if in_range:   # (sizes the library refuses are left to it: it reads no weight before its checks)
+        for name, n in want.items():
+            if name not in w or w[name].size != n:
+                raise ValueError(f"weights: {name} must have {n} elements")
+    nl = max(params.mlp_layers, 1)
+    lw, lb = (_fp * nl)(), (_fp * nl)()
+    for i in range(params.mlp_layers):
+        lw[i] = w[f"layers.{i}.weight"].ctypes.data_as(_fp) if f"layers.{i}.weight" in w else None
+        lb[i] = w[f"layers.{i}.bias"].ctypes.data_as(_fp) if f"layers.{i}.bias" in w else None
+    for field, name in (("conv_weight", "conv1.weight"), ("conv_bias", "conv1.bias"), ("fc1_weight", "fc1.weight"),
+                        ("fc1_bias", "fc1.bias"), ("output_weight", "output.weight"), ("output_bias", "output.bias")):
+        if name in w:
+            setattr(cw, field, w[name].ctypes.data_as(_fp))
+    cw.layer_weight, cw.layer_bias = lw, lb
+    return cw, (w, lw, lb)
+
+
 class NoteModel:
     """``weights``: PyTorch ``state_dict`` names -> arrays (conv1.weight [16][1][5], conv1.bias, fc1.weight [mlp][n_features],
     fc1.bias, layers.i.weight / .bias, output.weight [128][mlp], output.bias).  ``device=None``: a host-only handle (``infer`` works;
@@ -54,32 +83,10 @@ class NoteModel:
         self.params = params
         self.device = device
         self._h = C.c_void_p()
-        w = _weights_dict(weights)
-        L, _, _, n_feat = params.sizes()
-        want = {"conv1.weight": 16 * 5, "conv1.bias": 16, "fc1.weight": params.mlp_size * n_feat, "fc1.bias": params.mlp_size,
-                "output.weight": N_OUT * params.mlp_size, "output.bias": N_OUT}
-        for i in range(params.mlp_layers):
-            want[f"layers.{i}.weight"] = params.mlp_size * params.mlp_size
-            want[f"layers.{i}.bias"] = params.mlp_size
-        cw = _lib.CNoteModelWeights()
-        in_range = (3 <= params.n_bins <= 1024 and 1 <= params.t_frames <= 8 and L >= 8 and 16 <= params.mlp_size <= 4096
-                    and params.mlp_size % 16 == 0 and 0 <= params.mlp_layers <= 8)
-        if in_range:   # (sizes the library refuses are left to it: it reads no weight before its checks)
-            for name, n in want.items():
-                if name not in w or w[name].size != n:
-                    raise ValueError(f"weights: {name} must have {n} elements")
-        nl = max(params.mlp_layers, 1)
-        lw, lb = (_fp * nl)(), (_fp * nl)()
-        for i in range(params.mlp_layers):
-            lw[i] = w[f"layers.{i}.weight"].ctypes.data_as(_fp) if f"layers.{i}.weight" in w else None
-            lb[i] = w[f"layers.{i}.bias"].ctypes.data_as(_fp) if f"layers.{i}.bias" in w else None
-        for field, name in (("conv_weight", "conv1.weight"), ("conv_bias", "conv1.bias"), ("fc1_weight", "fc1.weight"),
-                            ("fc1_bias", "fc1.bias"), ("output_weight", "output.weight"), ("output_bias", "output.bias")):
-            if name in w:
-                setattr(cw, field, w[name].ctypes.data_as(_fp))
-        cw.layer_weight, cw.layer_bias = lw, lb
+        cw, keep = _c_weights(params, weights)   # (keep: alive until the library has copied them)
         cp = _lib.CNoteModelParams(params.n_bins, params.t_frames, params.mlp_size, params.mlp_layers)
         st = self._L.pvq_note_model_create(-1 if device is None else int(device), C.byref(cp), C.byref(cw), C.byref(self._h))
+        del keep
         if st == _lib.PVQ_ERR_INVALID_ARG:
             raise ValueError((self._L.pvq_last_error() or b"").decode())
         _check(st)

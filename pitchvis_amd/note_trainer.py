@@ -1,0 +1,153 @@
+"""The trainer's optimisation step (pitchvis_train/train.py:108-162) on the GPU: pvq_note_trainer_* of include/pvq.h.  ``NoteTrainer``
+owns the parameters, their gradients and Adam's moments on the device and runs forward (training mode), BCE loss, backward and Adam on
+a batch of rows gathered by index from a dataset in device memory: the ``[n_rows][n_bins]`` dB rows and ``[n_rows][128]`` targets
+``train_dataset_streams`` leaves there.  ``state_dict()`` is what ``NoteModel.from_state_dict`` takes."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import _lib
+from .note_model import N_OUT, NoteModelParams, _c_weights
+
+_fp = C.POINTER(C.c_float)
+STEP, GRAD, EVAL = _lib.TRAIN_STEP, _lib.TRAIN_GRAD, _lib.TRAIN_EVAL
+_MODES = {"step": STEP, "grad": GRAD, "eval": EVAL}
+_ARRAYS = {"weights": _lib.TRAIN_WEIGHTS, "grads": _lib.TRAIN_GRADS, "adam_m": _lib.TRAIN_ADAM_M, "adam_v": _lib.TRAIN_ADAM_V}
+
+
+@dataclass
+class NoteTrainerHyper:
+    """train.py:111,131-144: lr, torch.optim.Adam's betas, eps = finfo(float32).eps, L2 weight decay, dropout; the mask's seed"""
+    lr: float = 1e-5
+    beta1: float = 0.9
+    beta2: float = 0.999
+    eps: float = 1.1920928955078125e-7
+    weight_decay: float = 5e-4
+    dropout: float = 0.1
+    seed: int = 0
+
+    @staticmethod
+    def default() -> "NoteTrainerHyper":
+        h = _lib.CNoteTrainerHyper()
+        _lib.load().pvq_note_trainer_hyper_default(C.byref(h))
+        return NoteTrainerHyper(h.lr, h.beta1, h.beta2, h.eps, h.weight_decay, h.dropout, int(h.seed))
+
+    def _c(self) -> _lib.CNoteTrainerHyper:
+        return _lib.CNoteTrainerHyper(self.lr, self.beta1, self.beta2, self.eps, self.weight_decay, self.dropout, int(self.seed) & (2 ** 64 - 1))
+
+
+def dropout_keep(seed: int, step: int, layer: int, row: int, col0: int, n: int, dropout: float) -> np.ndarray:
+    """the dropout mask of include/pvq.h on the host: bool [n], True where element (row, col0 + j) of hidden layer ``layer`` is kept"""
+    from . import _check
+    out = np.empty(max(int(n), 1), np.uint8)
+    _check(_lib.load().pvq_note_trainer_dropout_keep(int(seed), int(step), int(layer), int(row), int(col0), int(n), float(dropout),
+                                                     out.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return out[:int(n)].astype(bool)
+
+
+def epoch(indices, batch: int):
+    """the batches of one epoch: consecutive slices of ``indices``, a permutation the caller seeded (the last one may be short)"""
+    idx = np.ascontiguousarray(indices, np.uint32)
+    for at in range(0, idx.size, int(batch)):
+        yield idx[at:at + int(batch)]
+
+
+class NoteTrainer:
+    """``weights``: the initial ``state_dict`` (names as for ``NoteModel``).  ``device=None``: a host-only handle (argument checks
+    work; ``step`` raises: no CPU fallback).  ``max_batch`` sizes the workspace once."""
+
+    def __init__(self, params: NoteModelParams, weights, hyper: Optional[NoteTrainerHyper] = None, max_batch: int = 300, device: Optional[int] = 0):
+        from . import _check
+        self._L = _lib.load()
+        self.params = params
+        self.hyper = hyper or NoteTrainerHyper()
+        self.max_batch = int(max_batch)
+        self.device = device
+        self._h = C.c_void_p()
+        cw, keep = _c_weights(params, weights)   # (keep: alive until the library has copied them)
+        cp = _lib.CNoteModelParams(params.n_bins, params.t_frames, params.mlp_size, params.mlp_layers)
+        ch = self.hyper._c()
+        st = self._L.pvq_note_trainer_create(-1 if device is None else int(device), C.byref(cp), C.byref(cw), C.byref(ch), self.max_batch,
+                                             C.byref(self._h))
+        del keep
+        if st == _lib.PVQ_ERR_INVALID_ARG:
+            raise ValueError((self._L.pvq_last_error() or b"").decode())
+        _check(st)
+        self.n_params = int(self._L.pvq_note_trainer_param_count(self._h))
+        self.window_len, _, _, self.n_features = params.sizes()
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._L.pvq_note_trainer_destroy(h)
+            self._h = None
+
+    @property
+    def steps(self) -> int:
+        """completed ``step`` calls in mode "step": Adam's t - 1 and the step the dropout mask is keyed by"""
+        return int(self._L.pvq_note_trainer_steps(self._h))
+
+    def step(self, d_db, d_targets, idx, mode="step", d_loss=None, d_logits=None, *, n_rows: Optional[int] = None, stream=None) -> None:
+        """One step on the batch ``idx`` (host sequence of sample indices, T - 1 <= i < n_rows).  ``d_db`` ``[n_rows][n_bins]`` and
+        ``d_targets`` ``[n_rows][128]``: contiguous f32 device tensors (or raw pointers, with ``n_rows``).  ``mode``: "step" (dropout,
+        backward, Adam), "grad" (the same without Adam and without advancing the counter) or "eval" (no dropout, forward and loss only).
+        ``d_loss`` (one float) and ``d_logits`` (``[len(idx)][128]``): optional device tensors to fill.  Asynchronous on ``stream``."""
+        from . import _check, _ptr, _stream_handle
+        if hasattr(d_db, "shape"):
+            if d_db.dim() != 2 or d_db.shape[1] != self.params.n_bins or not d_db.is_contiguous() or d_db.element_size() != 4:
+                raise ValueError("d_db must be a contiguous f32 tensor [n_rows][n_bins]")
+            if n_rows is None:
+                n_rows = int(d_db.shape[0])
+            if n_rows > d_db.shape[0]:
+                raise ValueError("d_db holds fewer than n_rows rows")
+        if n_rows is None:
+            raise ValueError("n_rows is needed with a raw pointer")
+        if hasattr(d_targets, "shape"):
+            if d_targets.dim() != 2 or d_targets.shape[1] != N_OUT or not d_targets.is_contiguous() or d_targets.element_size() != 4:
+                raise ValueError("d_targets must be a contiguous f32 tensor [n_rows][128]")
+            if n_rows > d_targets.shape[0]:
+                raise ValueError("d_targets holds fewer than n_rows rows")
+        ix = np.ascontiguousarray(idx, np.uint32).reshape(-1)
+        if hasattr(d_logits, "numel") and (d_logits.numel() < ix.size * N_OUT or not d_logits.is_contiguous() or d_logits.element_size() != 4):
+            raise ValueError("d_logits must be a contiguous f32 tensor [len(idx)][128]")
+        if hasattr(d_loss, "numel") and (d_loss.numel() < 1 or d_loss.element_size() != 4):
+            raise ValueError("d_loss must be an f32 tensor of one element")
+        st = self._L.pvq_note_trainer_step(self._h, _MODES[mode] if isinstance(mode, str) else int(mode), _ptr(d_db), _ptr(d_targets), int(n_rows),
+                                           ix.ctypes.data_as(C.POINTER(C.c_uint32)), ix.size, _ptr(d_loss), _ptr(d_logits), _stream_handle(stream))
+        if st == _lib.PVQ_ERR_INVALID_ARG:
+            raise ValueError((self._L.pvq_last_error() or b"").decode())
+        _check(st)
+
+    def read_flat(self, what: str = "weights", out: Optional[np.ndarray] = None) -> np.ndarray:
+        """"weights", "grads", "adam_m" or "adam_v" as one f32 array in state_dict order.  Synchronises."""
+        from . import _check
+        if out is None:
+            out = np.empty(self.n_params, np.float32)
+        _check(self._L.pvq_note_trainer_read(self._h, _ARRAYS[what], out.ctypes.data_as(_fp), out.size))
+        return out
+
+    def split(self, flat: np.ndarray) -> dict:
+        """a flat array in state_dict order -> state_dict names -> arrays in PyTorch's shapes (views)"""
+        p = self.params
+        shapes = [("conv1.weight", (16, 1, 5)), ("conv1.bias", (16,)), ("fc1.weight", (p.mlp_size, self.n_features)), ("fc1.bias", (p.mlp_size,))]
+        for i in range(p.mlp_layers):
+            shapes += [(f"layers.{i}.weight", (p.mlp_size, p.mlp_size)), (f"layers.{i}.bias", (p.mlp_size,))]
+        shapes += [("output.weight", (N_OUT, p.mlp_size)), ("output.bias", (N_OUT,))]
+        out, at = {}, 0
+        for name, shape in shapes:
+            n = int(np.prod(shape))
+            out[name] = flat[at:at + n].reshape(shape)
+            at += n
+        assert at == flat.size
+        return out
+
+    def read(self, what: str = "weights") -> dict:
+        return self.split(self.read_flat(what))
+
+    def state_dict(self) -> dict:
+        """the parameters, exactly what ``NoteModel.from_state_dict`` takes"""
+        return self.read("weights")
