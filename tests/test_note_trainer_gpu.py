@@ -14,7 +14,37 @@ Bars:
   * Adam: |w_dev - w_64| <= 1/2 ulp(w) + 1e-6 |dw_64| (the final rounding; the dozen roundings of the formula); m and v within
     4 * 2^-24 relative.  w_64, m_64, v_64 come from the device's own f32 gradients (PVQ_TRAIN_GRAD on the same batch: the counter
     does not move, so the mask is the same) and the previous device state.
-Every test prints the figures it observes before it asserts; DESIGN.md section 6b records them."""
+Every test prints the figures it observes before it asserts; DESIGN.md section 6b records them.
+
+Batches above 300 (trainers with max_batch = 4096, the most the API admits; the dataset keeps its 400 rows, so indices repeat).  A
+product M x N over K is split along K by nt_splits: want = min(512 / tiles, stages / 8, 8) with stages = ceil(K / 32) and 64 x 64 tiles,
+then stages_per_split = ceil(stages / want) and splits = ceil(stages / stages_per_split); a split product leaves partial sums that
+nt_gemm_finish adds and passes through the epilogue.  In the weight gradients (TN) K is the batch: 10 stages at 300, so none of the
+cases above splits one; the first that does is 481 (16 stages).  The smallest case of each path, splits as "n x stages (last)":
+  * D/481:  output.weight (128 x 48) and fc1.weight (48 x 2144, 34 tiles) 2 x 8 (8); stage 15 holds row 480 alone.
+  * D/2049: 65 stages; both weight gradients 8 x 9 (2), stage 64 holds row 2048 alone; 33 row tiles forward.
+  * C/2049: three hidden layers.  output.weight and layers.*.weight (2 x 2 tiles) 8 x 9 (2); fc1.weight (80 x 2496, 78 tiles: 512 / 78 = 6)
+    6 x 11 (10); the forward fc1 (2049 x 80 over 2496: 66 tiles, 78 stages) 7 x 12 (6).
+  * C/4096: 128 stages, exactly 64 row tiles, every reduction over the batch 4096 terms long.  output.weight and layers.*.weight
+    8 x 16 (16); fc1.weight 6 x 22 (18); the forward fc1 (128 tiles) 4 x 20 (18).
+  * F/2049: T = 1, mlp 64: one column tile in every hidden product.  All three weight gradients 8 x 9 (2); layers.0.weight is one tile.
+  * E/513:  mlp 256, 17 stages.  output.weight and layers.0.weight (256 x 256, 16 tiles) 2 x 9 (8); fc1.weight (256 x 7040, 440 tiles)
+    unsplit over its 17 stages.
+  * A/1025: mlp 1024, 33 stages, one past 16 row tiles.  layers.*.weight (256 tiles) 2 x 17 (16); output.weight (32 tiles) 4 x 9 (6);
+    fc1.weight (1264 tiles) unsplit.
+  * A/300 with p = 0.5: the hidden products (300 x 1024 over 1024: 80 tiles, 32 stages) are 4 x 8 (8) forward (NT, E_HIDDEN) and
+    backward (NN, E_GATE), so the mask and the gate are applied by nt_gemm_finish; no weight gradient splits.
+  * C/2049 with p = 0.5: the splits of C/2049; the mask's row numbers run to 2048 (applied inside nt_gemm: K = 80 does not split).
+The bars are the ones above.  torch's f32 CPU autograd against float64 on these inputs, worst share of max|g64| as conv1.weight /
+conv1.bias / dense weights / dense biases, measured before the bar was trusted:
+    D/481  5.6e-7 / 3.8e-7 / 5.2e-7 / 1.1e-7        D/2049 1.8e-6 / 1.1e-6 / 4.7e-7 / 1.2e-7
+    C/2049 2.4e-6 / 2.2e-6 / 5.1e-7 / 1.1e-7        C/4096 3.5e-6 / 3.7e-6 / 4.4e-7 / 1.2e-7
+    F/2049 1.8e-6 / 1.0e-6 / 4.0e-7 / 1.3e-7        E/513  1.6e-6 / 8.4e-7 / 5.5e-7 / 1.3e-7
+    A/1025 3.6e-6 / 2.0e-6 / 5.4e-7 / 1.3e-7
+    A/300, p = 0.5 (step 0)  8.8e-7 / 6.3e-7 / 8.3e-7 / 1.9e-7        C/2049, p = 0.5 (step 0)  1.5e-6 / 1.5e-6 / 3.0e-7 / 1.0e-7
+The f32 losses differ from float64 by at most 1.9e-7, the f32 logits by at most 7.6e-7 of max|logit|.  The worst, conv1.bias of C/4096
+at 3.7e-6, leaves 2.7 x room under 1e-5; no case exceeds 5e-6 (2 x room), so none was replaced by a smaller batch and GRAD_REL
+stands at 1e-5 for every tensor."""
 import functools
 
 import numpy as np
@@ -31,6 +61,8 @@ GRAD_REL, LOGIT_REL = 1e-5, 1e-5
 GUARD = 1024
 SEED = 11
 CASES = [(n, b) for n in "CDF" for b in (1, 37, 130)] + [("A", 300)]
+SPLIT_CASES = [("D", 481), ("D", 2049), ("C", 2049), ("C", 4096), ("F", 2049), ("E", 513), ("A", 1025)]      # (the module docstring)
+MAX_BATCH = 4096
 
 
 def _trainer(name, max_batch=300, **hyper):
@@ -45,6 +77,21 @@ def _device_data(name):
     return torch.from_numpy(db.copy()).cuda(), torch.from_numpy(tg.copy()).cuda()
 
 
+def _max_batch(batch):
+    """the trainers of the cases up to 300 keep their max_batch of 300; above, the most the API admits"""
+    return 300 if batch <= 300 else MAX_BATCH
+
+
+@functools.lru_cache(maxsize=None)
+def _ref64(name, batch):
+    """TR.step on the initial weights without dropout, once per case: (loss, logits, gradients), read-only"""
+    db, tg = TR.dataset(name)
+    loss, z, g = TR.step(R.weights(name), db, tg, TR.batch_idx(name, batch), R.SHAPES[name][1])
+    for a in (z, *g.values()):
+        a.setflags(write=False)
+    return loss, z, g
+
+
 def _compare_grads(tag, got, want):
     worst = 0.0
     for k, g64 in want.items():
@@ -57,33 +104,35 @@ def _compare_grads(tag, got, want):
     return worst
 
 
-@pytest.mark.parametrize("name,batch", CASES)
+@pytest.mark.parametrize("name,batch", CASES + SPLIT_CASES)
 def test_gradients_match_f64_autograd(name, batch):
     T = R.SHAPES[name][1]
-    db, tg = TR.dataset(name)
     d_db, d_tg = _device_data(name)
     idx = TR.batch_idx(name, batch)
     assert idx[0] == T - 1 and (batch == 1 or (idx[1] == TR.N_ROWS - 1 and len(set(idx.tolist())) < batch))
-    t = _trainer(name, dropout=0.0)
+    t = _trainer(name, _max_batch(batch), dropout=0.0)
     d_loss = torch.zeros(1, device="cuda")
     t.step(d_db, d_tg, idx, "grad", d_loss=d_loss)
     got = t.read("grads")
-    loss64, _, want = TR.step(R.weights(name), db, tg, idx, T)
+    loss64, _, want = _ref64(name, batch)
     print(f"shape {name} batch {batch}: loss {float(d_loss):.7f}, f64 {loss64:.7f}")
     _compare_grads(f"{name}/{batch}", got, want)
     assert t.steps == 0
 
 
-@pytest.mark.parametrize("batch", [37, 130])
-def test_gradients_with_dropout(batch):
-    """shape C (three hidden layers), p = 0.5, at step counter 0 and, after one optimisation step, at 1: the f64 model gets the mask of
-    the restatement.  A wrong mask, scale, layer index or step shows as an O(1) error."""
-    name, p = "C", 0.5
+# (the first two keep the ids they had when shape C was the only one)
+@pytest.mark.parametrize("name,batch,max_batch", [pytest.param("C", 37, 300, id="37"), pytest.param("C", 130, 300, id="130"),
+                                                  pytest.param("A", 300, MAX_BATCH, id="A-300"), pytest.param("C", 2049, MAX_BATCH, id="C-2049")])
+def test_gradients_with_dropout(name, batch, max_batch):
+    """p = 0.5, at step counter 0 and, after one optimisation step, at 1: the f64 model gets the mask of the restatement.  A wrong
+    mask, scale, layer index, row number or step shows as an O(1) error.  Shape C (three hidden layers) applies the mask inside nt_gemm,
+    at 2049 with row numbers up to 2048; shape A at 300 splits its hidden products, so nt_gemm_finish applies mask and gate."""
+    p = 0.5
     n_bins, T, mlp, layers, _ = R.SHAPES[name]
     db, tg = TR.dataset(name)
     d_db, d_tg = _device_data(name)
     idx = TR.batch_idx(name, batch)
-    t = _trainer(name, dropout=p, lr=1e-3)
+    t = _trainer(name, max_batch, dropout=p, lr=1e-3)
     for step in (0, 1):
         w = t.state_dict()
         t.step(d_db, d_tg, idx, "grad")
@@ -91,7 +140,7 @@ def test_gradients_with_dropout(batch):
         keep = TR.masks(SEED, step, layers, batch, mlp, p)
         print(f"step {step}: kept shares {[round(float(k.mean()), 3) for k in keep]}")
         _, _, want = TR.step(w, db, tg, idx, T, keep, p)
-        _compare_grads(f"C/{batch}/step {step}", got, want)
+        _compare_grads(f"{name}/{batch}/step {step}", got, want)
         _, _, plain = TR.step(w, db, tg, idx, T)
         far = max(float(np.abs(plain[k] - want[k]).max() / np.abs(want[k]).max()) for k in want)
         print(f"  (the gradients without the mask differ by {far:.2f} of the maximum)")
@@ -101,17 +150,16 @@ def test_gradients_with_dropout(batch):
             assert t.steps == 1
 
 
-@pytest.mark.parametrize("name,batch", [("C", 130), ("D", 37), ("F", 1), ("A", 300)])
+@pytest.mark.parametrize("name,batch", [("C", 130), ("D", 37), ("F", 1), ("A", 300), ("C", 4096), ("D", 2049)])
 def test_eval_loss_and_logits(name, batch):
     n_bins, T, mlp, layers, _ = R.SHAPES[name]
-    db, tg = TR.dataset(name)
     d_db, d_tg = _device_data(name)
     idx = TR.batch_idx(name, batch)
-    t = _trainer(name, dropout=0.5)          # (EVAL must not apply it)
+    t = _trainer(name, _max_batch(batch), dropout=0.5)          # (EVAL must not apply it)
     d_loss = torch.zeros(1, device="cuda")
     d_logits = torch.zeros((batch, 128), device="cuda")
     t.step(d_db, d_tg, idx, "eval", d_loss=d_loss, d_logits=d_logits)
-    loss64, z64, _ = TR.step(R.weights(name), db, tg, idx, T)
+    loss64, z64, _ = _ref64(name, batch)
     top = float(np.abs(z64).max())
     got, z = float(d_loss), d_logits.cpu().numpy()
     bar = 1e-5 * top + 1e-6 * loss64
@@ -187,6 +235,24 @@ def test_determinism_and_seed():
     assert (w_a != w_c).mean() > 0.1
 
 
+def test_gradients_depend_on_neither_the_handle_nor_the_workspace():
+    """shape C at 2049 (every weight gradient and the forward fc1 split, p = 0.1): two fresh handles give equal bits, and so does a
+    handle whose workspace was sized for 2049 rows and not 4096 (another h_stride, other offsets of everything behind it)."""
+    name, batch = "C", 2049
+    d_db, d_tg = _device_data(name)
+    idx = TR.batch_idx(name, batch)
+
+    def run(max_batch):
+        t = _trainer(name, max_batch)
+        t.step(d_db, d_tg, idx, "grad")
+        return t.read_flat("grads").view(np.uint32)
+    a, b, c = run(MAX_BATCH), run(MAX_BATCH), run(batch)
+    print(f"C/2049 grad: {int((a != b).sum())} of {a.size} gradient words differ between two handles of max_batch {MAX_BATCH}, "
+          f"{int((a != c).sum())} against a handle of max_batch {batch}; {int((a.view(np.float32) != 0).sum())} are not zero")
+    assert (a.view(np.float32) != 0).mean() > 0.5
+    assert np.array_equal(a, b) and np.array_equal(a, c)
+
+
 def _toy():
     """shape F (T = 1): output k is 1 when bin 30 (k % 8) of the row is above 4 dB (the median of 60 u^4 is 3.75)"""
     n_bins = R.SHAPES["F"][0]
@@ -240,3 +306,42 @@ def test_nothing_else_is_written_and_a_refused_call_launches_nothing():
             t.step(d_db, d_tg, bad, "step", d_loss=loss_all[:1])
     torch.cuda.synchronize()
     assert t.steps == 1 and np.array_equal(t.read_flat("weights").view(np.uint32), w.view(np.uint32)) and (loss_all == 7.0).all()
+
+
+
+def test_nothing_else_is_written_at_the_largest_batch():
+    """shape C at 4096 rows of a handle of max_batch 4096, the top of the range: the outputs are written in full and nothing
+    behind them; one row more is refused with nothing launched."""
+    name, batch = "C", MAX_BATCH
+    d_db0, d_tg0 = _device_data(name)
+    d_db, d_tg = d_db0.clone(), d_tg0.clone()
+    idx = TR.batch_idx(name, batch)
+    t = _trainer(name, MAX_BATCH)
+    loss_all = torch.full((1 + GUARD,), 7.0, device="cuda")
+    logits_all = torch.full((batch * 128 + GUARD,), 7.0, device="cuda")
+    for mode in ("eval", "grad", "step"):
+        loss_all.fill_(7.0)
+        logits_all.fill_(7.0)
+        t.step(d_db, d_tg, idx, mode, d_loss=loss_all[:1], d_logits=logits_all[:batch * 128])
+        torch.cuda.synchronize()
+        unwritten = int((logits_all[:batch * 128] == 7.0).sum())
+        print(f"C/{batch} {mode}: loss {float(loss_all[0]):.6f}, {unwritten} of {batch * 128} logits unwritten, guards "
+              f"{int((loss_all[1:] != 7.0).sum())} + {int((logits_all[batch * 128:] != 7.0).sum())} words changed")
+        assert (loss_all[1:] == 7.0).all() and (logits_all[batch * 128:] == 7.0).all()
+        assert loss_all[0] != 7.0 and torch.isfinite(loss_all[0]) and unwritten == 0 and torch.isfinite(logits_all).all()
+    assert t.steps == 1
+    assert torch.equal(d_db, d_db0) and torch.equal(d_tg, d_tg0)
+    for what in ("weights", "grads", "adam_m", "adam_v"):
+        buf = np.full(t.n_params + GUARD, 7.0, np.float32)
+        t.read_flat(what, buf[:t.n_params])
+        assert (buf[t.n_params:] == 7.0).all() and np.isfinite(buf).all(), what
+    # one row more than max_batch: the counter, the weights and the outputs stay
+    w = t.read_flat("weights")
+    loss_all.fill_(7.0)
+    logits_all.fill_(7.0)
+    T = R.SHAPES[name][1]
+    with pytest.raises(ValueError):
+        t.step(d_db, d_tg, np.full(batch + 1, T - 1, np.uint32), "step", d_loss=loss_all[:1], d_logits=logits_all)
+    torch.cuda.synchronize()
+    assert t.steps == 1 and np.array_equal(t.read_flat("weights").view(np.uint32), w.view(np.uint32))
+    assert (loss_all == 7.0).all() and (logits_all == 7.0).all()
