@@ -478,7 +478,7 @@ double fused_tile_count(const std::vector<BlockGroup>& groups, const std::vector
 
 // Whether every sample a tile's K loop reads lies inside its stream's readable bytes: then the kernel takes 16-byte loads without
 // range checks, and only such tiles may pair up into wide entries.  This MIRRORS the device-side test — `inside` in
-// blockdft_gemm_tree / _tree3 / _tree_bf16x3 (tile_lo >= 0 && tile_hi * 4 <= pcm_bytes over bm rows of hop samples) and in
+// blockdft_gemm_tree / _tree_bf16x3 (tile_lo >= 0 && tile_hi * 4 <= pcm_bytes over bm rows of hop samples) and in
 // blockdft_gemm_gen (bm - 1 whole hops + the tile kind's depth) — and must change with it: an entry marked wide here whose tile the
 // kernel would range-check reads past the stream's end.
 bool tile_inside_stream(const BlockGroup& G, const SegKey& seg, int f0, size_t hop, int bm, int kind) {

@@ -3,7 +3,7 @@
 // environment.  Compiled by g++ with the other host units and replayed under ASan / UBSan by tests/sanitize/host_main.cpp.
 //
 // The structs below are read by the kernels as they are laid out here (BlockGroup travels by value in the kernel arguments);
-// vqt_blockdft.hip asserts that Float2 / Float4 / Int4 have the size and alignment of HIP's float2 / float4 / int4.
+// blockdft_device.hpp asserts that Float2 / Float4 / Int4 have the size and alignment of HIP's float2 / float4 / int4.
 #pragma once
 
 #include <cstddef>

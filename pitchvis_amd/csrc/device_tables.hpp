@@ -25,7 +25,7 @@ struct GroupDev {
     int tpr;          // lanes that share one kernel row in the FFT path's row dots: the largest power of two <= 512 / n_rows, at most 16
 };
 
-// block-DFT path tables (vqt_blockdft.hip), built lazily per hop
+// block-DFT path tables (blockdft_device.hpp), built lazily per hop
 struct BlockDftTables;
 
 struct DeviceTables {

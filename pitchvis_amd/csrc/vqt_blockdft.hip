@@ -14,38 +14,20 @@
 // log2(Nb)-level tree  A_{l+1}[j] = A_l[j] + phi^(2^l) A_l[j+2^l]  evaluated in LDS, then the
 // banded complex row dots (vqt.rs:889-910) and power_to_db (vqt.rs:922-954) as in the FFT path.
 //
-// Kernels:  blockdft_gemm_tree[_bf16x3] (MFMA GEMM + combine tree fused; the first 64 hop blocks of a window)
-//           blockdft_tree_finish (the last one or two tree levels of windows of more than 64 hop blocks)
-//           blockdft_gemm_gen (hops that do not divide the windows: whole hop blocks + the window's remainder)
-//           blockdft_gemm_rows + blockdft_combine (the same two stages unfused: more than 8 window groups)
-//           blockdft_banddots4c_db / blockdft_banddots_db[_bf16x3] (kernel product as a banded MFMA GEMM + power_to_db)
-// Host planning (tables, run packing, tile lists) is blockdft_plan.cpp; this file uploads what it builds and launches.
+// Three units and one private header (blockdft_device.hpp: BlockDftTables, BlockLaunch, the workspace helper, the shared constants):
+//   vqt_blockdft.hip    this file, the path's host side: tables to the device, workspaces, a call's walk over its launches
+//   blockdft_gemm.hip   blockdft_gemm_tree[_bf16x3], blockdft_gemm_gen, blockdft_tree_finish, blockdft_gemm_rows + blockdft_combine,
+//                       their launchers and the tile-list cache
+//   blockdft_dots.hip   blockdft_banddots4c_db / blockdft_banddots_db[_bf16x3] (kernel product as a banded MFMA GEMM + power_to_db)
+//                       and their launcher
+// Host planning (tables, run packing, tile lists) is blockdft_plan.cpp; this file uploads what it builds and walks the launches.
 #include <algorithm>
 #include <cmath>
-#include <cstring>
-#include <type_traits>
 
-#include "blockdft_plan.hpp"
-#include "device_tables.hpp"
-#include "peaks_device.hpp"
-#include "vqt_engine.hpp"
+#include "blockdft_device.hpp"
 
 namespace pvq {
 
-#define PVQ_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_last_error(std::string(#call) + " failed: " + hipGetErrorString(e_));              \
-            return PVQ_ERR_DEVICE;                                                                 \
-        }                                                                                          \
-    } while (0)
-
-static_assert(sizeof(Float2) == sizeof(float2) && alignof(Float2) == alignof(float2), "blockdft_plan.hpp: Float2 must match float2");
-static_assert(sizeof(Float4) == sizeof(float4) && alignof(Float4) == alignof(float4), "blockdft_plan.hpp: Float4 must match float4");
-static_assert(sizeof(Int4) == sizeof(int4) && alignof(Int4) == alignof(int4), "blockdft_plan.hpp: Int4 must match int4");
-
-constexpr int CB_T = 128;    // frames per combine workgroup
 // Frames per sub-batch: the X (+ Y) workspace is sized for one.  As many as the handle's workspace limit holds (default 1 GiB:
 // 131 072 frames at 48 kHz / 252 bins = 0.74 GB; wide geometries — 840 bins: 15 KB per frame — take fewer), a multiple of 64,
 // at most 147 456 (BASELINE configs[2]'s 131 072 per rank is one sub-batch; against two of 65 536 the step is 4 % shorter: one ramp and
@@ -56,55 +38,6 @@ static size_t chunk_frames(size_t limit_bytes, size_t bytes_per_frame) {
     size_t f = limit_bytes / std::max<size_t>(bytes_per_frame, 1) / 64 * 64;
     return std::min<size_t>(std::max<size_t>(f, 64), 147456);   // (131 072 + an eighth: 64 staged streams of 2 048 frames with their gaps are 135 168 frames — one launch, not one and a 4 000-frame tail)
 }
-
-struct BlockDftTables {
-    size_t hop = 0;
-    int n_groups = 0;
-    int n_tiles = 0;   // total column tiles; Ntot = n_tiles*64 floats, XC = n_tiles*32 complex
-    int nb_max = 0;
-    int n_bins_pad = 0;
-    std::vector<BlockGroup> groups;
-    std::vector<float> h_E;        // host copy of E
-    float* d_E = nullptr;          // [hop][Ntot]
-    __bf16* d_Et = nullptr;        // [3][Ntot][hop] hi/mid/lo bf16 planes of E^T (split-bf16 GEMM), built on first use
-    int* d_tile_group = nullptr;   // [n_tiles]
-    long long* d_tile_s = nullptr; // [n_tiles] window begin of the tile's group relative to the buffer end
-    BlockGroup* d_groups = nullptr;
-    float2* d_comb_tw = nullptr;
-    // banded kernel product: blocks of 16 output bins x their union of spectrum columns, as MFMA B operands
-    struct BandBlock* d_band = nullptr;
-    float* d_band_B = nullptr;     // per block and column: 64 floats in v_mfma_f32_32x32x2_f32 B-operand lane order
-    __bf16* d_band_B3 = nullptr;   // per block and 8 columns: 3 planes x 64 lanes x 8 bf16 in v_mfma_f32_32x32x16_bf16 order
-    // 8-bin blocks for the 16x16x4 MFMA form of the kernel product (fp32, 64-frame tiles)
-    struct BandBlock* d_band8 = nullptr;
-    float* d_band_B4 = nullptr;    // per block and 4 columns: 64 x (Re coefficient, Im coefficient): the no-swap form
-    int* d_band_list8 = nullptr;   // [8][band_per_wave8]
-    int band_per_wave8 = 0;
-    int* d_band_list = nullptr;    // [band_waves][band_per_wave]: per wave of a workgroup, the count and then the blocks it walks
-    int band_per_wave = 0;
-    int band_waves = 4;            // waves per kernel-product workgroup (8 when the 64-frame form is used)
-    float* d_P = nullptr;  size_t p_cap = 0;   // workspace
-    float2* d_X = nullptr; size_t x_cap = 0;
-    float2* d_Y = nullptr; size_t y_cap = 0;   // 64-block partial sums (windows of more than 64 blocks)
-    // frame-stripe tile order of the fused kernels, built per launch shape and kept for the next launch
-    struct TileList {
-        int4* d = nullptr; size_t cap = 0;            // device: the list, then the launch's segment table and X-tile map
-        const struct SegDev* d_segs = nullptr;
-        const struct XTile* d_xmap = nullptr;
-        std::vector<SegKey> key;                      // the runs the list was built for (stream geometry included: which tiles may pair up / take 16-byte loads)
-        int bm = 0, wide = 0, blocks = 0, kind = 0;   // kind: 0 power-of-two hop (GEMM + tree); 1 / 2: R / Q tiles of a general hop
-        bool multi = false;
-        double eff_tiles = 0.0;                       // MFMA work of the list in whole 32-column tiles
-        double eff_flop = 0.0;                        // ... in flop (general hops: the depth differs by tile kind and group)
-        std::vector<size_t> slot_data;                // the staged streams' slots the X-tile map was built from (compared by content: the key's slot_hash alone is a hash)
-    } tile_lists[8];   // eight slots: a batch's first, middle and last sub-batch alternate without rebuilding; a general hop takes two lists per launch shape
-    int tile_list_next = 0;
-    unsigned long long* d_clk = nullptr; size_t clk_cap = 0; int clk_n = 0;   // K-loop clock samples of the last profiled launch: 4 slots per sampled tile
-    float4* d_E16 = nullptr;       // E in the B-operand order of the 16x16x4 GEMM: [column tile][k < hop / 2][n < 16]
-    bool general = false;          // the hop does not divide the windows: blockdft_gemm_gen (whole hop blocks + the window's remainder)
-    float4* d_E16R = nullptr;      // general hops: per group and column tile [k < rem / 2][n < 16]
-    float2* d_gen_tw = nullptr;    // general hops: per group phi, tau (n_tiles * 32 columns each)
-};
 
 void free_blockdft_tables(BlockDftTables* t) {
     if (!t) return;
@@ -117,2064 +50,6 @@ void free_blockdft_tables(BlockDftTables* t) {
     delete t;
 }
 
-// ------------------------------------------------------------------------------------------------
-// GEMM: P[j][n] = sum_m pcm[s(n) + j*K + m] * E[m][n]        (exact fp32 MFMA)
-// ------------------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-// 16-byte raw buffer load.  Bound to the LLVM intrinsic by name: this compiler lowers
-// __builtin_amdgcn_raw_buffer_load_b64 / _b128 to a single-dword load.
-__device__ f32x4 pvq_raw_buffer_load_f32x4(i32x4 srsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
-
-// LDS-DMA (global_load_lds_*): 64 lanes x 16 (4) bytes from per-lane global addresses to wave-uniform LDS base + 16 (4) * lane, no register
-// destination; counted in vmcnt like any load.
-typedef __attribute__((address_space(1))) const void pvq_gvoid;
-typedef __attribute__((address_space(3))) void pvq_lvoid;
-__device__ __forceinline__ void lds_dma16(const void* g_lane, void* lds_wave) {
-    __builtin_amdgcn_global_load_lds((pvq_gvoid*)g_lane, (pvq_lvoid*)lds_wave, 16, 0, 0);
-}
-__device__ __forceinline__ void lds_dma4(const void* g_lane, void* lds_wave) {
-    __builtin_amdgcn_global_load_lds((pvq_gvoid*)g_lane, (pvq_lvoid*)lds_wave, 4, 0, 0);
-}
-
-struct GemmArgs {
-    const float* pcm_base;    // rebased per launch so that byte offsets fit 32 bits
-    unsigned pcm_bytes;       // bytes readable from pcm_base (hardware bounds check: beyond -> 0)
-    const float* E;
-    int ld;                   // Ntot
-    float* P;
-    int n_rows;               // rows of P to produce
-    int K;                    // hop
-    const long long* tile_s;  // per 64-float column tile: window begin relative to the n_fft buffer end (w0 - n_fft)
-    long long base;           // index, relative to pcm_base, of the end of frame 0 of this launch
-    int n_col_tiles;          // column tiles of this kernel's BN
-    int p_rows;               // row capacity of the tile-major P: P[(tile64 * p_rows + row) * 64 + (col & 63)]
-};
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// ------------------------------------------------------------------------------------------------
-// Fused form (windows of <= 64 hop blocks): the 128 x 32-complex-column tile of P never leaves the
-// workgroup.  After the K loop the accumulators go to LDS (aliasing the staging buffers), the doubling
-// tree runs there, and only X_f for the tile's 128 - Nb + 1 complete frames is written.  Row tiles of a
-// group therefore advance by S_g = 129 - Nb_g blocks (1.02x ... 1.97x recomputation of the GEMM rows,
-// +20 % MFMA work at 48 kHz / hop 256) in exchange for dropping the P round trip through memory
-// (172 MB written + ~200 MB read per 32 768 frames) and the separate combine launch.
-// ------------------------------------------------------------------------------------------------
-// Many streams in one launch: SegDev / XTile (blockdft_plan.hpp).  segs == nullptr: one segment described by the kernel arguments
-// themselves (the single-stream entry points).
-
-struct GemmTreeArgs {
-    const float* pcm_base;
-    unsigned pcm_bytes;
-    const float* E;           // [K][Ntot], (cos, sin) of e^{-i th_c u_m} interleaved per column; the fp32 form reads rows m < K/2
-    int ld;                   // Ntot
-    float2* X;                // frame-tile blocked: X[((frame / 64) * xcp + col) * 64 + frame % 64]
-    float2* Y;                // same layout, 64-block partial sums of the groups whose windows span more than 64 blocks
-    int xcp;                  // columns per frame tile (incl. the zeroed pad columns)
-    int n_frames;             // frames of this launch
-    int K;                    // hop
-    long long base;           // index, relative to pcm_base, of the end of frame 0 of this launch
-    int n_groups;
-    const int4* tile_list;    // (group, column tile in the group, first frame, position) per tile — frame-stripe order in eight queues, see launch
-    const BlockGroup* groups;
-    BlockGroup gv[8];         // the same descriptors by value (the fused path takes at most 8 window groups): read from the kernel argument segment, not through a second dependent memory round trip
-    const float2* comb_tw;
-    const __bf16* Et;         // [3][Ntot][K] hi/mid/lo planes of E^T (split-bf16 form only)
-    const float4* E16;        // [column tile][k < K / 2][n < 16]: (cos c_n, cos c_{n+16}, -sin c_n, -sin c_{n+16}): B operands of the 16x16x4 fp32 form
-    unsigned long long* stamps;   // developer knob PVQ_STAMPS: [workgroup][8] 100 MHz clock: 0 start, 1 after K loop, 2 after tree, 3 end, 4 all waves past the K loop, 5 P tile in LDS, 6 register levels done
-    unsigned long long* clk;      // profiling only (pvq_vqt_set_profiling): every 64th workgroup stores (shader clock, 100 MHz clock) before and after its K loop
-    const SegDev* segs;           // many-streams launches: the segment table (nullptr: one segment = the arguments above)
-    // general hops (blockdft_gemm_gen)
-    const float4* E16R;           // per group and column tile: [k < rem / 2][n < 16], as E16
-    const float2* gen_tw;         // per group: phi_c = e^{-2 pi i c hop / W} and tau_c (see the kernel), n_tiles * 32 columns each
-    int gen_kind;                 // 1: remainder tiles (R' -> Y, or -> X for windows shorter than the hop); 2: whole-block tiles (Q', combined, + tau R' -> X)
-};
-#define PVQ_STAMP(i) \
-    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)stamp_slot * 8 + (i)] = wall_clock64();   // stamp_slot: the tile's (workgroup's) row of the dump
-
-constexpr int FT_BM = 128, FT_BN = 64;
-
-// which (group, row tile, column tile) a workgroup of the fused kernels owns
-struct FusedTile {
-    BlockGroup G;
-    int S;        // complete frames per row tile
-    int ntl, nt;  // column tile within the group / global
-    int f0;       // first frame == first block row
-    int nfr;      // rows this group produces: n_frames complete frames, or n_frames + nb - 64 partial sums when nb > 64
-    int xt0, yt0; // first 64-frame tile of the tile's segment in X / Y (0 in a single-stream launch)
-};
-// the stream a tile reads and where its frames go: the kernel arguments, or the tile's entry of the segment table
-struct TileStream {
-    const float* pcm_base;
-    unsigned pcm_bytes;
-    long long base;
-    int n_frames, xt0, yt0;
-};
-__device__ __forceinline__ TileStream tile_stream(const GemmTreeArgs& a, int entry_x) {
-    TileStream ts{a.pcm_base, a.pcm_bytes, a.base, a.n_frames, 0, 0};
-    if (a.segs) {
-        // The entry is the same for every lane, but the compiler cannot know that of loaded data: without the readfirstlanes the
-        // buffer resource built from it counts as lane-dependent and EVERY operand load of the K loop is wrapped in a waterfall loop.
-        const int4* sp = reinterpret_cast<const int4*>(a.segs + ((unsigned)entry_x >> 16));
-        const int4 lo = sp[0], hi = sp[1];   // (pcm_off, base), (pcm_bytes, n_frames, x_tile0, y_tile0)
-        auto rfl = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
-        const long long pcm_off = (long long)(((unsigned long long)(unsigned)rfl(lo.y) << 32) | (unsigned)rfl(lo.x));
-        ts.pcm_base = a.pcm_base + pcm_off;
-        ts.base = (long long)(((unsigned long long)(unsigned)rfl(lo.w) << 32) | (unsigned)rfl(lo.z));
-        ts.pcm_bytes = (unsigned)rfl(hi.x);
-        ts.n_frames = rfl(hi.y);
-        ts.xt0 = rfl(hi.z);
-        ts.yt0 = rfl(hi.w);
-    }
-    return ts;
-}
-template <int BM = FT_BM>
-__device__ __forceinline__ FusedTile fused_tile_of(const GemmTreeArgs& a, const int4& e, const TileStream& ts) {   // tile list entry: (group, column tile, first frame, slot)
-    FusedTile t;
-    t.G = a.gv[e.x];
-    t.S = BM - t.G.nb_f + 1;
-    t.nfr = ts.n_frames + t.G.nb - t.G.nb_f;
-    t.xt0 = ts.xt0;
-    t.yt0 = ts.yt0;
-    t.ntl = e.y;
-    t.f0 = e.z;
-    t.nt = t.G.tile0 + t.ntl;
-    return t;
-}
-template <int BM = FT_BM>
-__device__ __forceinline__ FusedTile fused_tile(const GemmTreeArgs& a, TileStream& ts) {   // (the kernels of 32-column tiles: their lists carry no wide entries)
-    int4 e = a.tile_list[blockIdx.x];
-    ts = tile_stream(a, e.x);
-    e.x &= 7;
-    return fused_tile_of<BM>(a, e, ts);
-}
-
-// doubling tree over the [128][32 complex] P tile in LDS (rows padded to 33 so that the transposed store
-// below is bank-conflict free), then the store of the S complete frames, column-major
-constexpr int FT_LDP = CB_C + 1;                      // P tile row stride in complex elements
-// the tile's combine twiddles (levels x 32 columns) into LDS, issued before the K loop so the tree never waits on memory
-constexpr int FT_MAXL = 6;
-__device__ __forceinline__ void fused_stage_twiddles(float2 (*tw)[CB_C], const FusedTile& t, const GemmTreeArgs& a, int tid) {
-    const int l = tid >> 5, c = tid & (CB_C - 1);
-    if (l < t.G.levels_f) tw[l][c] = a.comb_tw[t.G.tw_off + l * (t.G.n_tiles * CB_C) + t.ntl * CB_C + c];
-}
-
-// lo + w * hi with a fixed operation order — (re, im) = fma((-w.y, w.y), (hi.y, hi.x), fma((w.x, w.x), (hi.x, hi.y), lo)),
-// two packed fp32 fmas (v_pk_fma_f32): every tree level, whichever code path evaluates it, rounds identically, so a
-// frame's result does not depend on where it sits in a tile
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float2 tree_cmadd(float2 lo, float2 w, float2 hi) {
-    const f32x2 t = __builtin_elementwise_fma((f32x2){w.x, w.x}, (f32x2){hi.x, hi.y}, (f32x2){lo.x, lo.y});
-    const f32x2 r = __builtin_elementwise_fma((f32x2){-w.y, w.y}, (f32x2){hi.y, hi.x}, t);
-    return make_float2(r.x, r.y);
-}
-
-// the first R <= 4 tree levels (strides 1 .. 8) in registers: a thread owns 16 consecutive rows of one column and
-// reads them plus the 2^R - 1 rows above once; every A_{l+1}[j] = A_l[j] + w_l A_l[j + 2^l] is evaluated exactly as
-// the level-by-level form would, without a pass through LDS per level.  Rows past the tile read as zero: they only
-// feed outputs that are themselves incomplete.
-template <int R, int BM>
-__device__ __forceinline__ void fused_tree_register_levels(float2 (*A)[CB_C + 1], const float2 (*tw)[CB_C], int tid) {
-    constexpr int H = (1 << R) - 1;
-    const int c = tid & (CB_C - 1), j0 = (tid >> 5) * 16;
-    float2 v[16 + H];
-#pragma unroll
-    for (int i = 0; i < 16 + H; ++i) v[i] = A[j0 + i][c];   // rows BM .. BM + 14 are spare rows of the tile (zeroed by the caller)
-    int len = 16 + H;
-#pragma unroll
-    for (int l = 0; l < R; ++l) {
-        const int st = 1 << l;
-        const float2 w = tw[l][c];
-        len -= st;
-#pragma unroll
-        for (int i = 0; i < 16 + H; ++i)
-            if (i < len) v[i] = tree_cmadd(v[i], w, v[i + st]);
-    }
-    __syncthreads();   // every thread has read its halo
-#pragma unroll
-    for (int i = 0; i < 16; ++i) A[j0 + i][c] = v[i];
-    __syncthreads();
-}
-
-template <int BM = FT_BM>   // BM rows, 2 * BM threads
-__device__ __forceinline__ void fused_tree_levels(float* smem, const float2 (*tw)[CB_C], const FusedTile& t, const GemmTreeArgs& a, int tid, int stamp_slot) {
-    float2 (*A)[FT_LDP] = reinterpret_cast<float2 (*)[FT_LDP]>(smem);  // [BM][33]
-    const int c = tid & (CB_C - 1);
-    constexpr int THREADS = 2 * BM;
-    constexpr int PER = BM * CB_C / THREADS;  // 16
-    auto cmadd = [](float2 lo, float2 w, float2 hi) { return tree_cmadd(lo, w, hi); };
-    const int levels = t.G.levels_f;
-    int l = levels < 4 ? levels : 4;
-    switch (l) {   // wave-uniform
-        case 1: fused_tree_register_levels<1, BM>(A, tw, tid); break;
-        case 2: fused_tree_register_levels<2, BM>(A, tw, tid); break;
-        case 3: fused_tree_register_levels<3, BM>(A, tw, tid); break;
-        case 4: fused_tree_register_levels<4, BM>(A, tw, tid); break;
-        default: break;
-    }
-    PVQ_STAMP(6);
-    int valid = BM - ((1 << l) - 1);
-    // remaining levels (strides >= 16) through LDS, two per pass where possible: evaluated exactly as two radix-2
-    // levels (same operations in the same order), outputs in groups of four to bound the registers
-    for (; l + 1 < levels; l += 2) {
-        const int st = 1 << l;
-        const float2 w1 = tw[l][c], w2 = tw[l + 1][c];
-        valid -= 3 * st;
-        float2 v[PER];
-#pragma unroll
-        for (int g = 0; g < PER; g += 4) {
-#pragma unroll
-            for (int q = g; q < g + 4; ++q) {
-                const int j = (tid + q * THREADS) / CB_C;
-                if (j < valid) {
-                    const float2 t0 = cmadd(A[j][c], w1, A[j + st][c]);
-                    const float2 t1 = cmadd(A[j + 2 * st][c], w1, A[j + 3 * st][c]);
-                    v[q] = cmadd(t0, w2, t1);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int j = (tid + q * THREADS) / CB_C;
-            if (j < valid) A[j][c] = v[q];
-        }
-        __syncthreads();
-    }
-    for (; l < levels; ++l) {
-        const int st = 1 << l;
-        valid -= st;
-        const float2 w = tw[l][c];
-        float2 v[PER];
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int j = (tid + q * THREADS) / CB_C;
-            if (j < valid) v[q] = cmadd(A[j][c], w, A[j + st][c]);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int j = (tid + q * THREADS) / CB_C;
-            if (j < valid) A[j][c] = v[q];
-        }
-        __syncthreads();
-    }
-    PVQ_STAMP(2);
-}
-// the tile's S complete frames to X (or Y): lanes walk the frames of one column: 512-byte runs in memory, conflict-free LDS reads
-template <int BM = FT_BM>
-__device__ __forceinline__ void fused_store_x(float* smem, const FusedTile& t, const GemmTreeArgs& a, int tid) {
-    float2 (*A)[FT_LDP] = reinterpret_cast<float2 (*)[FT_LDP]>(smem);  // [BM][33]
-    const int j = tid % BM;
-    const int f = t.f0 + j;
-    if (j < t.S && f < t.nfr) {
-        // windows of more than 64 blocks: 64-block partial sums go to Y, blockdft_tree_finish adds the last levels
-        const bool to_y = t.G.nb > t.G.nb_f;
-        float2* dst = (to_y ? a.Y : a.X) + ((size_t)((f >> 6) + (to_y ? t.yt0 : t.xt0)) * a.xcp + t.nt * CB_C) * 64 + (f & 63);
-        const int ncv = t.G.n_cols - t.ntl * CB_C < CB_C ? t.G.n_cols - t.ntl * CB_C : CB_C;   // the tile's real columns: the padding of a group's last tile is never read with a non-zero coefficient and never written (X starts out zeroed)
-#pragma unroll 4
-        for (int cc = tid / BM; cc < ncv; cc += 2) {   // streamed out (non-temporal): the kernel-product stage that reads X back runs 5 % faster for it
-            const float2 val = A[j][cc];
-            __builtin_nontemporal_store((f32x2){val.x, val.y}, reinterpret_cast<f32x2*>(&dst[cc * 64]));   // one 8-byte store
-        }
-    }
-}
-template <int BM = FT_BM>
-__device__ __forceinline__ void fused_tree_store(float* smem, const float2 (*tw)[CB_C], const FusedTile& t, const GemmTreeArgs& a, int tid, int stamp_slot) {
-    fused_tree_levels<BM>(smem, tw, t, a, tid, stamp_slot);
-    fused_store_x<BM>(smem, t, a, tid);
-    if (a.stamps) {
-        __builtin_amdgcn_s_waitcnt(0);   // stores issued and acknowledged
-        __syncthreads();
-        PVQ_STAMP(3);
-    }
-}
-
-// fp32 MFMA form.  The hop DFT is evaluated about the centre of the hop block: with u_m = m - (K-1)/2,
-//     P'[j][c] = sum_{m < K/2} (x[m] + x[K-1-m]) cos(th_c u_m)  +  i sum_{m < K/2} (x[m] - x[K-1-m]) (-sin(th_c u_m))
-// (cos is even, sin odd about the centre), i.e. two real GEMMs of depth K/2 — the real parts from the mirrored sums,
-// the imaginary parts from the mirrored differences — instead of one of depth K: half the MFMA work, exactly.
-// P = rho_c P' with rho_c = e^{-i th_c (K-1)/2}; the tree is linear per column, so X = rho_c X' and the constant
-// phase is folded into the kernel-product coefficients on the host (prepare_blockdft).
-//
-// The PCM matrix goes from memory straight into MFMA operand registers, no LDS staging and no barrier in the K loop:
-// a wave owns 32 block rows x all 32 complex columns of the tile; lane (row = lane & 31, half = lane >> 5) fetches
-// the 16 consecutive samples k0 + 16 half .. + 15 of its row and the 16 mirrored ones (64-byte runs: every cache line
-// it touches is consumed by four back-to-back loads), forms the 16 sums and 16 differences in registers, and these
-// ARE the A operands of 16 v_mfma_f32_32x32x2_f32 pairs (k order within a stage: k0 + 16 half + t; any order works
-// as long as the B rows follow it).  acc0 += sums x cosines, acc1 += differences x (-sines).  The tile's slice of E
-// (rows m < K/2, (cos, -sin) interleaved) is staged into LDS once per 128 rows of K/2 and read as one b64 per pair.
-constexpr int FR_KC = 128;   // rows of E staged per pass (32 KB)
-// idx_f / idx_b: sample index (relative to pcm_base) of the lane's front run and of its mirrored run
-template <bool VEC>
-__device__ __forceinline__ void fused_f32_stage_load(const i32x4& rsrc4, __amdgpu_buffer_rsrc_t rsrc, long long idx_f, long long idx_b,
-                                                     float (&fr)[16], float (&bk)[16]) {
-    if (VEC) {   // the whole tile lies inside the stream: offsets are plain non-negative byte offsets
-        const unsigned off_f = (unsigned)(idx_f * 4ll), off_b = (unsigned)(idx_b * 4ll);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 v = pvq_raw_buffer_load_f32x4(rsrc4, (int)(off_f + 16u * q), 0, 0);
-            const f32x4 w = pvq_raw_buffer_load_f32x4(rsrc4, (int)(off_b + 16u * q), 0, 0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                fr[4 * q + i] = v[i];
-                bk[4 * q + i] = w[i];
-            }
-        }
-    } else {
-        // tiles that touch the stream start / end: samples before the stream get an explicit out-of-range offset
-        // (a wrapped negative offset plus the instruction's immediate offset would not wrap in the hardware's range
-        // check), samples past the end are zeroed by the range check itself
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const long long jf = idx_f + q, jb = idx_b + q;
-            const unsigned of = jf >= 0 ? (unsigned)(jf * 4ll) : 0xFFFFFFFCu;
-            const unsigned ob = jb >= 0 ? (unsigned)(jb * 4ll) : 0xFFFFFFFCu;
-            fr[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, of, 0, 0));
-            bk[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, ob, 0, 0));
-        }
-    }
-}
-
-template <bool VEC, int BM, typename Args>
-__device__ __forceinline__ void fused_f32_kloop(const Args& a, float* smem, long long idx_f0, long long idx_b0, const float* e_tile,
-                                                int tid, f32x16& acc0, f32x16& acc1) {
-    constexpr int THREADS = 2 * BM;
-    const int lane = tid & 63;
-    const unsigned long long pcm_addr = reinterpret_cast<unsigned long long>(a.pcm_base);
-    const i32x4 rsrc4 = {(int)(unsigned)pcm_addr, (int)(unsigned)(pcm_addr >> 32), (int)a.pcm_bytes, 0x00020000};
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pcm_base), 0, a.pcm_bytes, 0x00020000);
-    const int K2 = a.K / 2;
-    const float2* bsl = reinterpret_cast<const float2*>(smem) + (lane >> 5) * 16 * CB_C + (lane & 31);   // row 16 half, column lane & 31
-    float fr[16], bk[16];
-    for (int kc = 0; kc < K2; kc += FR_KC) {
-        const int rows = K2 - kc < FR_KC ? K2 - kc : FR_KC;
-        fused_f32_stage_load<VEC>(rsrc4, rsrc, idx_f0 + kc, idx_b0 - kc, fr, bk);
-        if (kc > 0) __syncthreads();   // every wave is done with the previous slice
-        for (int i = tid; i < rows * (FT_BN / 4); i += THREADS) {
-            const int r = i / (FT_BN / 4), c4 = i % (FT_BN / 4);
-            *reinterpret_cast<float4*>(smem + r * FT_BN + c4 * 4) = *reinterpret_cast<const float4*>(e_tile + (size_t)(kc + r) * a.ld + c4 * 4);
-        }
-        __syncthreads();
-        for (int k0 = 0; k0 < rows; k0 += 32) {
-            float sm[16], df[16];
-#pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                sm[t] = fr[t] + bk[15 - t];
-                df[t] = fr[t] - bk[15 - t];
-            }
-            if (k0 + 32 < rows)
-                fused_f32_stage_load<VEC>(rsrc4, rsrc, idx_f0 + (kc + k0 + 32), idx_b0 - (kc + k0 + 32), fr, bk);
-#pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                const float2 b = bsl[(k0 + t) * CB_C];
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(sm[t], b.x, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(df[t], b.y, acc1, 0, 0, 0);
-            }
-        }
-    }
-}
-
-// The same mirrored GEMM on v_mfma_f32_16x16x4_f32 (the form blockdft_gemm_tree runs).  A wave still owns 32 block rows x 32
-// complex columns (two 16-row tiles x (re, im) x two 16-column halves = 8 accumulators of 4 registers), but lane
-// (row = lane & 15, kq = lane >> 4) now fetches 4 consecutive samples of its row and the 4 mirrored ones with ONE 16-byte load
-// each: the four lanes of a row read one contiguous 64-byte run, 16 cache lines per load instruction where the 32x32x2 form's
-// lanes touch 64 — its address processing took as long as its MFMAs (16 vs 15.6 us per workgroup pair), which is what held a
-// workgroup running its K loop alone (its CU partner in its tree / store phase) at 63 % of the matrix pipe.  MFMA t of a k
-// group (16 mirrored sample pairs) takes sample 4 kq + t of every lane; B operand of lane (n, kq): row 16 g + 4 kq + t of the
-// E slice, (cos c_n, cos c_{n+16}, -sin c_n, -sin c_{n+16}) as one 16-byte LDS read.  Operands double-buffered, one k group ahead.
-typedef float f32x4a __attribute__((ext_vector_type(4)));
-template <int BM, bool HALF>   // tiles that lie wholly inside the stream (all but a handful per launch); HALF: at most 16 columns (a group's last tile): the second 16-column half is not computed
-// depth: samples of a row the DFT runs over (the hop; the general-hop kernel's second GEMM runs over the first `rem` samples of rows that
-// still lie a.K = hop samples apart)
-__device__ __forceinline__ void fused_f32_kloop16(const GemmTreeArgs& a, const float* pcm_base, unsigned pcm_bytes, float* smem, long long tile_lo, const float4* e_tile, int tid,
-                                                  f32x4a (&accR)[2][2], f32x4a (&accI)[2][2], const float* tw_src, float* tw_dst, int tw_levels, int tw_stride, int stamp_slot, int depth) {
-    constexpr int THREADS = 2 * BM;
-    const int lane = tid & 63, wave = tid >> 6, m16 = lane & 15, kq = lane >> 4;
-    const unsigned long long pcm_addr = reinterpret_cast<unsigned long long>(pcm_base);
-    const i32x4 rsrc4 = {(int)(unsigned)pcm_addr, (int)(unsigned)(pcm_addr >> 32), (int)pcm_bytes, 0x00020000};
-    const int K2 = depth / 2;
-    const int nG = K2 / 32;   // (K2 is a multiple of 32: the fused path takes hops that are multiples of 64)
-    // A load step fetches a DOUBLE k group (32 mirrored sample pairs): lane (row, kq) takes the 8 consecutive samples 32 G + 8 kq ...
-    // of its row and the 8 mirrored ones, two 16-byte loads each, issued back to back — the four lanes of a row read one whole
-    // 128-byte line at a time.  Fetched 16 pairs at a time (one 64-byte half line per step, the other half a step later) every line
-    // crossed the L2 -> L1 path twice: by then the CU's other waves had pushed it out of the L1 again, and the K loop ran at the
-    // L2's 64-66 GB/s per CU, not at the matrix pipe's rate.  MFMA t of half h of double group G takes sample
-    // 32 G + 8 kq + 4 h + t of every lane; the B rows follow that order.
-    // Addresses: one loop-invariant byte offset per lane, row tile and direction; the double group moves in the instruction's
-    // SCALAR offset (front runs + 128 G bytes; the mirrored runs are anchored at the LAST double group and take + 128 (nG - 1 - G)).
-    unsigned vf[2], vb[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        const long long row_lo = tile_lo + (long long)(wave * 32 + mt * 16 + m16) * a.K;
-        vf[mt] = (unsigned)((row_lo + 8 * kq) * 4ll);
-        vb[mt] = (unsigned)((row_lo + depth - 8 - 8 * kq) * 4ll) - 128u * (unsigned)(nG - 1);
-    }
-    float fr[2][2][8], bk[2][2][8];
-    // The prefetch is UNCONDITIONAL (the group index is clamped: past the last group the last one is fetched again into the idle
-    // buffer).  Inside a uniform `if` the compiler must place the s_waitcnt for the path on which the loads were NOT issued: it waited
-    // for vmcnt(4), then vmcnt(0) right after issuing the eight loads of the next group, i.e. for the loads it had just issued — the
-    // K loop ran with no prefetch distance at all, hidden only while a CU's other workgroup had its own K loop to run.
-    auto load_dgroup = [&](int buf, int G) {   // G: double k group of the whole depth
-        const int Gc = G < nG - 1 ? G : nG - 1;
-        const int sf = 128 * Gc, sb = 128 * (nG - 1 - Gc);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const f32x4 v = pvq_raw_buffer_load_f32x4(rsrc4, (int)vf[mt], sf + 16 * h, 0);   // (the half's 16 bytes ride in the scalar offset too: one address register per run)
-                const f32x4 w = pvq_raw_buffer_load_f32x4(rsrc4, (int)vb[mt], sb + 16 * h, 0);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    fr[buf][mt][4 * h + t] = v[t];
-                    bk[buf][mt][4 * h + t] = w[t];
-                }
-            }
-        }
-    };
-    float4* El = reinterpret_cast<float4*>(smem);   // [rows][16]
-    // one k row = 8 MFMAs; its B operand (one 16-byte LDS read per lane) is fetched one row ahead, so that no MFMA waits on the LDS
-    const float4* erow = El + (8 * kq) * 16 + m16;   // row 32 Gl + 8 kq + 4 h + t of the staged slice
-    auto b_at = [&](int Gl, int h, int t) { return erow[(32 * Gl + 4 * h + t) * 16]; };
-    auto mfma_row = [&](int buf, int h, int t, const float4& b) {
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            const float sm = fr[buf][mt][4 * h + t] + bk[buf][mt][7 - 4 * h - t];
-            const float df = fr[buf][mt][4 * h + t] - bk[buf][mt][7 - 4 * h - t];
-            accR[mt][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(sm, b.x, accR[mt][0], 0, 0, 0);
-            if (!HALF) accR[mt][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(sm, b.y, accR[mt][1], 0, 0, 0);
-            accI[mt][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(df, b.z, accI[mt][0], 0, 0, 0);
-            if (!HALF) accI[mt][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(df, b.w, accI[mt][1], 0, 0, 0);
-        }
-    };
-    // the 8 k rows of double group Gl from operand buffer `buf`; bc: the first row's B operand (already fetched), returns the next group's
-    auto mfma_dgroup = [&](int buf, int Gl, float4 bc) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int h = r >> 2, t = r & 3;
-            // (past the slice's last row this reads on into the workgroup's LDS region: in bounds, never used)
-            const float4 bn = r < 7 ? b_at(Gl, (r + 1) >> 2, (r + 1) & 3) : b_at(Gl + 1, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);   // the next row's read is in flight before this row's MFMAs
-            mfma_row(buf, h, t, bc);
-            __builtin_amdgcn_sched_barrier(0);
-            bc = bn;
-        }
-        return bc;
-    };
-    // The slice of E goes straight to LDS (LDS-DMA, 1 KB per wave instruction, no registers), issued ahead of the first operand
-    // loads: ONE memory round trip before the first MFMA.  (As a load -> wait -> ds_write loop it was four dependent round
-    // trips, each also waiting for the operand loads issued before it, behind two more for the tile's twiddles and descriptor.)
-    auto stage_e = [&](int kc, int rows) {   // 1 KB pieces of the slice (rows x 256 bytes), dealt to the waves; a full slice unrolled: all pieces in flight together
-        constexpr int NWV = THREADS / 64, FULL = FR_KC / 4 / NWV;
-        const float4* src = e_tile + (size_t)kc * 16 + wave * 64 + lane;
-        float4* dst = El + wave * 64;
-        if (rows == FR_KC && FR_KC / 4 % NWV == 0) {
-#pragma unroll
-            for (int q = 0; q < FULL; ++q) lds_dma16(src + q * (NWV * 64), dst + q * (NWV * 64));
-        } else {
-            for (int j = wave; j < rows / 4; j += NWV) lds_dma16(e_tile + (size_t)kc * 16 + j * 64 + lane, El + j * 64);
-        }
-    };
-    stage_e(0, K2 < FR_KC ? K2 : FR_KC);
-    for (int l = wave; l < tw_levels; l += THREADS / 64)   // the tile's combine twiddles: one level (32 complex = 64 floats) per wave instruction
-        lds_dma4(tw_src + (size_t)l * tw_stride, tw_dst + l * (2 * CB_C));
-    load_dgroup(0, 0);
-    // (one wait for everything the prologue fetched.  Waiting only for the DMA pieces — s_waitcnt vmcnt(8) + a raw s_barrier — lets a
-    // wave start on its own first operands, but hipcc does not credit a hand-written wait: with an LDS-DMA "possibly in flight" it
-    // waits vmcnt(0) at the first use of every later load, which takes the K loop's prefetch distance away again.)
-    __syncthreads();
-    PVQ_STAMP(7);
-    for (int kc = 0; kc < K2; kc += FR_KC) {
-        const int rows = K2 - kc < FR_KC ? K2 - kc : FR_KC;
-        if (kc > 0) {   // (hops of 512 and more: the next slice of E replaces the one every wave is done with)
-            __syncthreads();
-            stage_e(kc, rows);
-            __syncthreads();
-        }
-        const int ng = rows / 32, G0 = kc / 32;
-        float4 bc = b_at(0, 0, 0);
-        for (int Gl = 0; Gl < ng; Gl += 2) {   // two double groups per pass: buffer indices stay compile-time
-            load_dgroup(1, G0 + Gl + 1);
-            bc = mfma_dgroup(0, Gl, bc);
-            if (Gl + 1 >= ng) break;           // (a 32-row slice: hop 64)
-            load_dgroup(0, G0 + Gl + 2);
-            bc = mfma_dgroup(1, Gl + 1, bc);
-        }
-    }
-}
-
-// The same loop for the tiles that touch the stream's start or end (dword loads, each range-checked by the buffer hardware;
-// samples before the stream get an explicit out-of-range offset, see fused_f32_stage_load): same MFMAs on the same samples in
-// the same order — k group g = 2 G + h — but one 16-pair half of a double group per load step, which keeps its 32 dword loads
-// per step inside the register budget.
-template <int BM>
-__device__ __forceinline__ void fused_f32_kloop16_edge(const GemmTreeArgs& a, const float* pcm_base, unsigned pcm_bytes, float* smem, long long tile_lo, const float4* e_tile, int tid,
-                                                       f32x4a (&accR)[2][2], f32x4a (&accI)[2][2], const float* tw_src, float* tw_dst, int tw_levels, int tw_stride, int stamp_slot, int depth) {
-    constexpr int THREADS = 2 * BM;
-    const int lane = tid & 63, wave = tid >> 6, m16 = lane & 15, kq = lane >> 4;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pcm_base), 0, pcm_bytes, 0x00020000);
-    const int K2 = depth / 2;
-    int jf0[2], jb0[2];   // sample indices relative to pcm_base (|.| < 2^30: the launch's stream is at most 4 GB)
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        const int row_lo = (int)tile_lo + (wave * 32 + mt * 16 + m16) * a.K;
-        jf0[mt] = row_lo + 8 * kq;
-        jb0[mt] = row_lo + depth - 4 - 8 * kq;
-    }
-    float fr[2][2][4], bk[2][2][4];
-    auto load_group = [&](int buf, int g) {
-        const int so = 32 * (g >> 1) + 4 * (g & 1);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int xf = jf0[mt] + so + t, xb = jb0[mt] - so + t;
-                fr[buf][mt][t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, xf >= 0 ? (unsigned)xf * 4u : 0xFFFFFFFCu, 0, 0));
-                bk[buf][mt][t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, xb >= 0 ? (unsigned)xb * 4u : 0xFFFFFFFCu, 0, 0));
-            }
-    };
-    float4* El = reinterpret_cast<float4*>(smem);   // [rows][16]
-    auto mfma_group = [&](int buf, int gl) {        // gl: k group inside the staged slice
-        const float4* e = El + (32 * (gl >> 1) + 8 * kq + 4 * (gl & 1)) * 16 + m16;
-        float4 b[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) b[t] = e[t * 16];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                const float sm = fr[buf][mt][t] + bk[buf][mt][3 - t];
-                const float df = fr[buf][mt][t] - bk[buf][mt][3 - t];
-                accR[mt][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(sm, b[t].x, accR[mt][0], 0, 0, 0);
-                accR[mt][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(sm, b[t].y, accR[mt][1], 0, 0, 0);
-                accI[mt][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(df, b[t].z, accI[mt][0], 0, 0, 0);
-                accI[mt][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(df, b[t].w, accI[mt][1], 0, 0, 0);
-            }
-        }
-    };
-    load_group(0, 0);
-    for (int l = wave; l < tw_levels; l += THREADS / 64) tw_dst[l * (2 * CB_C) + lane] = tw_src[(size_t)l * tw_stride];
-    for (int kc = 0; kc < K2; kc += FR_KC) {
-        const int rows = K2 - kc < FR_KC ? K2 - kc : FR_KC;
-        if (kc > 0) __syncthreads();   // every wave is done with the previous slice
-        for (int i = tid; i < rows * 16; i += THREADS) El[i] = e_tile[(size_t)kc * 16 + i];
-        __syncthreads();
-        const int ng = rows / 16, g0 = kc / 16;
-        for (int gl = 0; gl < ng; gl += 2) {   // two k groups per pass: buffer indices stay compile-time (rows is a multiple of 32)
-            load_group(1, g0 + gl + 1);
-            mfma_group(0, gl);
-            if (g0 + gl + 2 < K2 / 16) load_group(0, g0 + gl + 2);
-            mfma_group(1, gl + 1);
-        }
-    }
-}
-
-// WIDE tiles: the same rows against TWO neighbouring column tiles (64 complex columns) in one K loop.  What bounds a workgroup is
-// not a resource but the chain of latencies a tile pays once — launch gap, descriptor, the first operand burst, the waves' skew at
-// the loop's end — so a wide tile pays them once for twice the MFMAs.  A wave holds 16 accumulators (64 registers);
-// the A operands are single-buffered per 16-row tile and fetched one STAGE ahead — stage = (row tile, double k group) = 64 MFMAs,
-// the same prefetch distance in MFMAs as the narrow loop's double buffer: while row tile 1 of double group G runs, row tile 0's
-// loads of group G + 1 are in flight, and so on in turn.  Every accumulator adds the same products in the same order as in the
-// narrow loop: results are bit-identical whichever form a tile takes.  The two tiles' slices of E lie 32 KB apart in LDS.
-template <int BM>
-__device__ __forceinline__ void fused_f32_kloop64(const GemmTreeArgs& a, const float* pcm_base, unsigned pcm_bytes, float* smem, long long tile_lo, const float4* e_tile, int tid,
-                                                  f32x4a (&accR)[2][4], f32x4a (&accI)[2][4], const float* tw_src, float* tw_dst, int tw_levels, int tw_stride, int stamp_slot) {
-    constexpr int THREADS = 2 * BM, NWV = THREADS / 64;
-    const int lane = tid & 63, wave = tid >> 6, m16 = lane & 15, kq = lane >> 4;
-    const unsigned long long pcm_addr = reinterpret_cast<unsigned long long>(pcm_base);
-    const i32x4 rsrc4 = {(int)(unsigned)pcm_addr, (int)(unsigned)(pcm_addr >> 32), (int)pcm_bytes, 0x00020000};
-    const int K2 = a.K / 2;
-    const int nG = K2 / 32;
-    unsigned vf[2], vb[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        const long long row_lo = tile_lo + (long long)(wave * 32 + mt * 16 + m16) * a.K;
-        vf[mt] = (unsigned)((row_lo + 8 * kq) * 4ll);
-        vb[mt] = (unsigned)((row_lo + a.K - 8 - 8 * kq) * 4ll) - 128u * (unsigned)(nG - 1);
-    }
-    float fr[2][8], bk[2][8];
-    auto load_stage = [&](int mt, int G) {   // unconditional, clamped (see fused_f32_kloop16)
-        const int Gc = G < nG - 1 ? G : nG - 1;
-        const int sf = 128 * Gc, sb = 128 * (nG - 1 - Gc);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const f32x4 v = pvq_raw_buffer_load_f32x4(rsrc4, (int)vf[mt], sf + 16 * h, 0);
-            const f32x4 w = pvq_raw_buffer_load_f32x4(rsrc4, (int)vb[mt], sb + 16 * h, 0);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                fr[mt][4 * h + t] = v[t];
-                bk[mt][4 * h + t] = w[t];
-            }
-        }
-    };
-    float4* El = reinterpret_cast<float4*>(smem);   // [column tile][FR_KC rows][16]
-    const float4* erow = El + (8 * kq) * 16 + m16;
-    auto b_at = [&](int Gl, int r, int ct) { return erow[(32 * Gl + r) * 16 + ct * (FR_KC * 16)]; };
-    // one stage: 8 k rows x 2 column tiles = 16 steps of 4 MFMAs, the B operand fetched one step ahead
-    auto mfma_stage = [&](int mt, int Gl, int Gl_next, float4 bc) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int r = i >> 1, ct = i & 1;
-            const float4 bn = i < 15 ? b_at(Gl, (i + 1) >> 1, (i + 1) & 1) : b_at(Gl_next, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            const float sm = fr[mt][r] + bk[mt][7 - r];
-            const float df = fr[mt][r] - bk[mt][7 - r];
-            accR[mt][2 * ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(sm, bc.x, accR[mt][2 * ct], 0, 0, 0);
-            accR[mt][2 * ct + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(sm, bc.y, accR[mt][2 * ct + 1], 0, 0, 0);
-            accI[mt][2 * ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(df, bc.z, accI[mt][2 * ct], 0, 0, 0);
-            accI[mt][2 * ct + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(df, bc.w, accI[mt][2 * ct + 1], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            bc = bn;
-        }
-        return bc;
-    };
-    auto stage_e = [&](int kc, int rows) {   // both tiles' slices, 1 KB pieces dealt to the waves
-        constexpr int FULL = FR_KC / 4 / NWV;
-        if (rows == FR_KC && FR_KC / 4 % NWV == 0) {
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-                for (int q = 0; q < FULL; ++q)
-                    lds_dma16(e_tile + (size_t)ct * K2 * 16 + (size_t)kc * 16 + (q * NWV + wave) * 64 + lane, El + ct * (FR_KC * 16) + (q * NWV + wave) * 64);
-        } else {
-            for (int j = wave; j < 2 * (rows / 4); j += NWV) {
-                const int ct = j >= rows / 4, jj = ct ? j - rows / 4 : j;
-                lds_dma16(e_tile + (size_t)ct * K2 * 16 + (size_t)kc * 16 + jj * 64 + lane, El + ct * (FR_KC * 16) + jj * 64);
-            }
-        }
-    };
-    stage_e(0, K2 < FR_KC ? K2 : FR_KC);
-    // twiddles: levels x 64 complex columns = two 64-float pieces per level, [column tile][level][32]
-    for (int j = wave; j < 2 * tw_levels; j += NWV) {
-        const int l = j >> 1, ct = j & 1;
-        lds_dma4(tw_src + (size_t)l * tw_stride + ct * (2 * CB_C), tw_dst + (ct * FT_MAXL + l) * (2 * CB_C));
-    }
-    load_stage(0, 0);
-    load_stage(1, 0);
-    __syncthreads();
-    PVQ_STAMP(7);
-    for (int kc = 0; kc < K2; kc += FR_KC) {
-        const int rows = K2 - kc < FR_KC ? K2 - kc : FR_KC;
-        if (kc > 0) {
-            __syncthreads();
-            stage_e(kc, rows);
-            __syncthreads();
-        }
-        const int ng = rows / 32, G0 = kc / 32;
-        float4 bc = b_at(0, 0, 0);
-        for (int Gl = 0; Gl < ng; ++Gl) {
-            bc = mfma_stage(0, Gl, Gl, bc);
-            load_stage(0, G0 + Gl + 1);
-            bc = mfma_stage(1, Gl, Gl + 1, bc);
-            load_stage(1, G0 + Gl + 1);
-        }
-    }
-}
-
-// P' accumulators of one 32-column tile -> LDS as [row][32 complex + pad]  (C/D layout of the 16x16 MFMA: column = lane & 15,
-// rows 4 (lane >> 4) + r), and the 15 spare rows zeroed
-template <int BM, int NP, int NP0>
-__device__ __forceinline__ void fused_dump_p(float* smem, const f32x4a (&accR)[2][NP], const f32x4a (&accI)[2][NP], int tid) {
-    float2 (*Pt)[FT_LDP] = reinterpret_cast<float2 (*)[FT_LDP]>(smem);
-    const int lane = tid & 63, wave = tid >> 6, m16 = lane & 15, kq = lane >> 4;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int np = 0; np < 2; ++np)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                Pt[wave * 32 + mt * 16 + 4 * kq + r][np * 16 + m16] = make_float2(accR[mt][NP0 + np][r], accI[mt][NP0 + np][r]);
-    for (int i = tid; i < 15 * FT_LDP; i += 2 * BM) Pt[BM][i] = make_float2(0.0f, 0.0f);   // the spare rows (Pt[BM][..] runs on through them)
-}
-
-// one 32-column tile from the K loop to the store
-template <int BM>
-__device__ __forceinline__ void fused_f32_narrow_tile(const GemmTreeArgs& a, const float* pcm_base, unsigned pcm_bytes, float* smem, float2 (*tw_lds)[CB_C], const FusedTile& T, bool inside,
-                                                      long long tile_lo, int tid, int stamp_slot) {
-    const int lane = tid & 63;
-    // the tile's combine twiddles (levels x 32 complex columns = 64 floats per level): a wave copies a level, a dword per lane
-    const float* tw_src = reinterpret_cast<const float*>(a.comb_tw + T.G.tw_off + T.ntl * CB_C) + lane;   // level l: + l * tw_stride floats
-    float* tw_dst = reinterpret_cast<float*>(&tw_lds[0][0]);
-    const int tw_levels = T.G.levels_f, tw_stride = 2 * T.G.n_tiles * CB_C;
-    const float4* e_tile = a.E16 + (size_t)T.nt * (a.K / 2) * 16;
-    f32x4a accR[2][2], accI[2][2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int np = 0; np < 2; ++np)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                accR[mt][np][r] = 0.0f;
-                accI[mt][np][r] = 0.0f;
-            }
-    // the clock the chip holds under this kernel's MFMA load: shader-clock ticks over 100 MHz ticks across the K loop.  The
-    // start stamps go straight to memory so that nothing stays live in registers across the loop
-    if (a.clk != nullptr && (blockIdx.x & 63) == 0 && tid == 0) {
-        a.clk[(blockIdx.x >> 6) * 4 + 0] = __builtin_amdgcn_s_memtime();
-        a.clk[(blockIdx.x >> 6) * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-    }
-    // a group's last column tile may hold 16 columns or fewer (3 of the 21 tiles at 48 kHz / 252 bins): half the MFMAs
-    const bool half = T.ntl == T.G.n_tiles - 1 && T.G.n_cols - T.ntl * CB_C <= 16;
-    if (!inside)
-        fused_f32_kloop16_edge<BM>(a, pcm_base, pcm_bytes, smem, tile_lo, e_tile, tid, accR, accI, tw_src, tw_dst, tw_levels, tw_stride, stamp_slot, a.K);
-    else if (half)
-        fused_f32_kloop16<BM, true>(a, pcm_base, pcm_bytes, smem, tile_lo, e_tile, tid, accR, accI, tw_src, tw_dst, tw_levels, tw_stride, stamp_slot, a.K);
-    else
-        fused_f32_kloop16<BM, false>(a, pcm_base, pcm_bytes, smem, tile_lo, e_tile, tid, accR, accI, tw_src, tw_dst, tw_levels, tw_stride, stamp_slot, a.K);
-    if (a.clk != nullptr && (blockIdx.x & 63) == 0 && tid == 0) {
-        a.clk[(blockIdx.x >> 6) * 4 + 2] = __builtin_amdgcn_s_memtime();
-        a.clk[(blockIdx.x >> 6) * 4 + 3] = __builtin_amdgcn_s_memrealtime();
-    }
-    PVQ_STAMP(1);
-    __syncthreads();   // the E slice is dead: the P' tile takes its place
-    PVQ_STAMP(4);
-    fused_dump_p<BM, 2, 0>(smem, accR, accI, tid);
-    __syncthreads();
-    PVQ_STAMP(5);
-    fused_tree_store<BM>(smem, tw_lds, T, a, tid, stamp_slot);
-}
-
-
-// three more stamps per workgroup, behind the gridDim.x rows of eight: its first instruction, its last wave's last store issued, and that
-// store acknowledged — what lies between one workgroup's last and the next one's first is the dispatcher's (scripts/dev_conc.py)
-#define PVQ_END_STAMPS \
-    if (a.stamps) { \
-        unsigned long long* ends = a.stamps + (size_t)gridDim.x * 8 + (size_t)stamp_slot * 4; \
-        if (lane == 0) atomicMax(ends + 1, wall_clock64()); \
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
-        if (lane == 0) atomicMax(ends + 2, wall_clock64()); \
-        if (tid == 0) ends[0] = t_entry; \
-    }
-template <int BM, int KFIX = 0>   // rows of hop blocks per tile; 2 * BM threads = BM / 32 waves of 32 rows x 32 (wide tiles: 64) complex columns; KFIX: the hop, where the instantiation knows it (0: any)
-__global__ __launch_bounds__(2 * BM, 4) void blockdft_gemm_tree(GemmTreeArgs a) {
-    if constexpr (KFIX != 0) __builtin_assume(a.K == KFIX);   // 4 waves per SIMD = two 512-thread (four 256-thread) workgroups per CU: at most 128 registers
-    constexpr bool WIDE = BM == 256;                   // (the 128-row form, a test shape, takes narrow tiles only)
-    constexpr int B_FLOATS = (WIDE ? 2 : 1) * FR_KC * FT_BN;   // a wide tile's two slices of E
-    constexpr int P_FLOATS = (BM + 15) * FT_LDP * 2;   // 15 spare rows: the register tree levels read their halo without a range check
-    __shared__ __attribute__((aligned(16))) float smem[B_FLOATS > P_FLOATS ? B_FLOATS : P_FLOATS];  // the E slice(s), then the P tile
-    __shared__ float2 tw_lds[2][FT_MAXL][CB_C];
-    const unsigned long long t_entry = wall_clock64();
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int4 entry = a.tile_list[blockIdx.x];   // .x: group | wide << 8 | segment << 16
-    const TileStream ts = tile_stream(a, entry.x);
-    FusedTile T = fused_tile_of<BM>(a, make_int4(entry.x & 7, entry.y, entry.z, entry.w), ts);   // (gv[8])
-    const bool wide = ((entry.x >> 8) & 1) != 0;
-    if (T.f0 >= T.nfr) return;
-    const int stamp_slot = blockIdx.x;
-    PVQ_STAMP(0);
-    const long long s = ts.base + T.G.s_rel;
-    const long long tile_lo = s + (long long)T.f0 * a.K, tile_hi = tile_lo + (long long)BM * a.K;  // sample range of the tile
-    const bool inside = tile_lo >= 0 && tile_hi * 4ll <= (long long)ts.pcm_bytes;
-    if (WIDE && wide && inside) {
-        const float* tw_src = reinterpret_cast<const float*>(a.comb_tw + T.G.tw_off + T.ntl * CB_C) + lane;
-        float* tw_dst = reinterpret_cast<float*>(&tw_lds[0][0][0]);
-        const float4* e_tile = a.E16 + (size_t)T.nt * (a.K / 2) * 16;
-        f32x4a accR[2][4], accI[2][4];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int np = 0; np < 4; ++np)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    accR[mt][np][r] = 0.0f;
-                    accI[mt][np][r] = 0.0f;
-                }
-        if (a.clk != nullptr && (blockIdx.x & 63) == 0 && tid == 0) {
-            a.clk[(blockIdx.x >> 6) * 4 + 0] = __builtin_amdgcn_s_memtime();
-            a.clk[(blockIdx.x >> 6) * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-        }
-        fused_f32_kloop64<BM>(a, ts.pcm_base, ts.pcm_bytes, smem, tile_lo, e_tile, tid, accR, accI, tw_src, tw_dst, T.G.levels_f, 2 * T.G.n_tiles * CB_C, stamp_slot);
-        if (a.clk != nullptr && (blockIdx.x & 63) == 0 && tid == 0) {
-            a.clk[(blockIdx.x >> 6) * 4 + 2] = __builtin_amdgcn_s_memtime();
-            a.clk[(blockIdx.x >> 6) * 4 + 3] = __builtin_amdgcn_s_memrealtime();
-        }
-        PVQ_STAMP(1);
-        // the two tiles' P' one after the other through the same buffer (the second waits in its accumulators)
-        __syncthreads();   // the E slices are dead
-        PVQ_STAMP(4);
-        fused_dump_p<BM, 4, 0>(smem, accR, accI, tid);
-        __syncthreads();
-        PVQ_STAMP(5);
-        fused_tree_store<BM>(smem, tw_lds[0], T, a, tid, stamp_slot);
-        __syncthreads();
-        fused_dump_p<BM, 4, 2>(smem, accR, accI, tid);
-        __syncthreads();
-        T.ntl += 1;
-        T.nt += 1;
-        fused_tree_store<BM>(smem, tw_lds[1], T, a, tid, stamp_slot);
-        PVQ_END_STAMPS
-        return;
-    }
-    // (the host pairs only tiles that lie inside the stream — same test, same numbers, launch(): the range-checked loop takes one tile)
-    fused_f32_narrow_tile<BM>(a, ts.pcm_base, ts.pcm_bytes, smem, tw_lds[0], T, inside, tile_lo, tid, stamp_slot);
-    PVQ_END_STAMPS
-}
-
-#ifdef PVQ_DEV_KNOBS   // developer library only: measured, not adopted (PVQ_TREE3=1)
-// ------------------------------------------------------------------------------------------------
-// THREE workgroups per CU (round 5; DESIGN.md 5.2 "(i)").  The 256 x 32 tile's life is a serial chain of latencies of which the K loop
-// is about a third; two such lives per CU leave the matrix pipe idle whenever both are outside their K loops.  This form buys a third
-// life with registers and LDS instead of a longer K share per life: at most 80 registers (6 waves per SIMD) and 38 KB of LDS, so
-//   * the K loop keeps ONE operand buffer per 16-row tile, fetched one stage (row tile x double k group = 32 MFMAs) ahead — the wide
-//     loop's scheme on one column tile: 32 accumulator + 32 operand registers;
-//   * the P' tile goes through LDS in two 16-column QUARTERS ([256 + 15][17] complex = 36.9 KB), one after the other through the same
-//     buffer (the second waits in its 16 accumulator registers), each with the doubling tree and the store of its own.
-// Every accumulator adds the same products in the same order as in the other K loops, every tree level is the same tree_cmadd: a
-// frame's bits do not depend on which form computed it (tests/test_configs_gpu.py::test_tile_shapes_bit_identical_in_subprocesses).
-// ------------------------------------------------------------------------------------------------
-constexpr int Q_C = 16;            // complex columns of a P quarter
-constexpr int Q_LDP = Q_C + 1;     // its row stride in LDS
-template <int BM, bool HALF>
-__device__ __forceinline__ void fused_f32_kloop16s(const GemmTreeArgs& a, const float* pcm_base, unsigned pcm_bytes, float* smem, long long tile_lo, const float4* e_tile, int tid,
-                                                   f32x4a (&accR)[2][2], f32x4a (&accI)[2][2], const float* tw_src, float* tw_dst, int tw_levels, int tw_stride, int stamp_slot) {
-    constexpr int THREADS = 2 * BM, NWV = THREADS / 64;
-    const int lane = tid & 63, wave = tid >> 6, m16 = lane & 15, kq = lane >> 4;
-    const unsigned long long pcm_addr = reinterpret_cast<unsigned long long>(pcm_base);
-    const i32x4 rsrc4 = {(int)(unsigned)pcm_addr, (int)(unsigned)(pcm_addr >> 32), (int)pcm_bytes, 0x00020000};
-    const int K2 = a.K / 2;
-    const int nG = K2 / 32;
-    // one byte offset per lane and direction (row tile 0); row tile 1 lies 16 rows = 16 K samples further on: that, the double group and
-    // the half ride in the instruction's SCALAR offset
-    const long long row_lo = tile_lo + (long long)(wave * 32 + m16) * a.K;
-    const unsigned vf = (unsigned)((row_lo + 8 * kq) * 4ll);
-    const unsigned vb = (unsigned)((row_lo + a.K - 8 - 8 * kq) * 4ll) - 128u * (unsigned)(nG - 1);
-    const int mt_step = 64 * a.K;   // bytes between the two row tiles of a wave
-    float fr[2][8], bk[2][8];
-    auto load_stage = [&](int mt, int G) {   // unconditional, clamped (see fused_f32_kloop16)
-        const int Gc = G < nG - 1 ? G : nG - 1;
-        const int sf = 128 * Gc + mt * mt_step, sb = 128 * (nG - 1 - Gc) + mt * mt_step;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const f32x4 v = pvq_raw_buffer_load_f32x4(rsrc4, (int)vf, sf + 16 * h, 0);
-            const f32x4 w = pvq_raw_buffer_load_f32x4(rsrc4, (int)vb, sb + 16 * h, 0);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                fr[mt][4 * h + t] = v[t];
-                bk[mt][4 * h + t] = w[t];
-            }
-        }
-    };
-    float4* El = reinterpret_cast<float4*>(smem);   // [rows][16]
-    const float4* erow = El + (8 * kq) * 16 + m16;
-    auto b_at = [&](int Gl, int r) { return erow[(32 * Gl + r) * 16]; };
-    // one stage: the 8 k rows of a double group for one 16-row tile, 4 MFMAs each, the B operand fetched one row ahead
-    auto mfma_stage = [&](int mt, int Gl, int Gl_next, float4 bc) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const float4 bn = r < 7 ? b_at(Gl, r + 1) : b_at(Gl_next, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            const float sm = fr[mt][r] + bk[mt][7 - r];
-            const float df = fr[mt][r] - bk[mt][7 - r];
-            accR[mt][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(sm, bc.x, accR[mt][0], 0, 0, 0);
-            if (!HALF) accR[mt][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(sm, bc.y, accR[mt][1], 0, 0, 0);
-            accI[mt][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(df, bc.z, accI[mt][0], 0, 0, 0);
-            if (!HALF) accI[mt][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(df, bc.w, accI[mt][1], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            bc = bn;
-        }
-        return bc;
-    };
-    auto stage_e = [&](int kc, int rows) {
-        constexpr int FULL = FR_KC / 4 / NWV;
-        const float4* src = e_tile + (size_t)kc * 16 + wave * 64 + lane;
-        float4* dst = El + wave * 64;
-        if (rows == FR_KC && FR_KC / 4 % NWV == 0) {
-#pragma unroll
-            for (int q = 0; q < FULL; ++q) lds_dma16(src + q * (NWV * 64), dst + q * (NWV * 64));
-        } else {
-            for (int j = wave; j < rows / 4; j += NWV) lds_dma16(e_tile + (size_t)kc * 16 + j * 64 + lane, El + j * 64);
-        }
-    };
-    stage_e(0, K2 < FR_KC ? K2 : FR_KC);
-    for (int l = wave; l < tw_levels; l += NWV) lds_dma4(tw_src + (size_t)l * tw_stride, tw_dst + l * (2 * CB_C));
-    load_stage(0, 0);
-    load_stage(1, 0);
-    __syncthreads();
-    PVQ_STAMP(7);
-    for (int kc = 0; kc < K2; kc += FR_KC) {
-        const int rows = K2 - kc < FR_KC ? K2 - kc : FR_KC;
-        if (kc > 0) {
-            __syncthreads();
-            stage_e(kc, rows);
-            __syncthreads();
-        }
-        const int ng = rows / 32, G0 = kc / 32;
-        float4 bc = b_at(0, 0);
-        for (int Gl = 0; Gl < ng; ++Gl) {
-            bc = mfma_stage(0, Gl, Gl, bc);
-            load_stage(0, G0 + Gl + 1);
-            bc = mfma_stage(1, Gl, Gl + 1, bc);
-            load_stage(1, G0 + Gl + 1);
-        }
-    }
-}
-
-// the 16 columns NP of the accumulators -> LDS as [row][16 complex + pad], the 15 spare rows zeroed
-template <int BM>
-__device__ __forceinline__ void q_dump_p(float* smem, const f32x4a (&accR)[2][2], const f32x4a (&accI)[2][2], int np, int tid) {
-    float2 (*Pt)[Q_LDP] = reinterpret_cast<float2 (*)[Q_LDP]>(smem);
-    const int lane = tid & 63, wave = tid >> 6, m16 = lane & 15, kq = lane >> 4;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            Pt[wave * 32 + mt * 16 + 4 * kq + r][m16] = np == 0 ? make_float2(accR[mt][0][r], accI[mt][0][r]) : make_float2(accR[mt][1][r], accI[mt][1][r]);
-    for (int i = tid; i < 15 * Q_LDP; i += 2 * BM) Pt[BM][i] = make_float2(0.0f, 0.0f);
-}
-// the first R <= 4 tree levels in registers: a thread owns 8 consecutive rows of one of the quarter's 16 columns (+ the 2^R - 1 rows above)
-template <int R, int BM>
-__device__ __forceinline__ void q_tree_register_levels(float2 (*A)[Q_LDP], const float2 (*tw)[CB_C], int cq, int tid) {
-    constexpr int H = (1 << R) - 1;
-    constexpr int RPT = BM * Q_C / (2 * BM);   // 8 rows per thread
-    const int c = tid & (Q_C - 1), j0 = (tid >> 4) * RPT;
-    float2 v[RPT + H];
-#pragma unroll
-    for (int i = 0; i < RPT + H; ++i) v[i] = A[j0 + i][c];
-    int len = RPT + H;
-#pragma unroll
-    for (int l = 0; l < R; ++l) {
-        const int st = 1 << l;
-        const float2 w = tw[l][cq + c];
-        len -= st;
-#pragma unroll
-        for (int i = 0; i < RPT + H; ++i)
-            if (i < len) v[i] = tree_cmadd(v[i], w, v[i + st]);
-    }
-    __syncthreads();   // every thread has read its halo
-#pragma unroll
-    for (int i = 0; i < RPT; ++i) A[j0 + i][c] = v[i];
-    __syncthreads();
-}
-// one quarter from the P' tile in LDS to X: the tree (same operations, level by level, as fused_tree_levels), then the store
-template <int BM>
-__device__ __forceinline__ void q_tree_store(float* smem, const float2 (*tw)[CB_C], const FusedTile& t, const GemmTreeArgs& a, int cq, int tid, int stamp_slot) {
-    float2 (*A)[Q_LDP] = reinterpret_cast<float2 (*)[Q_LDP]>(smem);
-    constexpr int THREADS = 2 * BM;
-    constexpr int PER = BM * Q_C / THREADS;  // 8
-    const int c = tid & (Q_C - 1);
-    const int levels = t.G.levels_f;
-    int l = levels < 4 ? levels : 4;
-    switch (l) {   // wave-uniform
-        case 1: q_tree_register_levels<1, BM>(A, tw, cq, tid); break;
-        case 2: q_tree_register_levels<2, BM>(A, tw, cq, tid); break;
-        case 3: q_tree_register_levels<3, BM>(A, tw, cq, tid); break;
-        case 4: q_tree_register_levels<4, BM>(A, tw, cq, tid); break;
-        default: break;
-    }
-    PVQ_STAMP(6);
-    int valid = BM - ((1 << l) - 1);
-    for (; l + 1 < levels; l += 2) {
-        const int st = 1 << l;
-        const float2 w1 = tw[l][cq + c], w2 = tw[l + 1][cq + c];
-        valid -= 3 * st;
-        float2 v[PER];
-#pragma unroll
-        for (int g = 0; g < PER; g += 4) {
-#pragma unroll
-            for (int q = g; q < g + 4; ++q) {
-                const int j = (tid + q * THREADS) / Q_C;
-                if (j < valid) {
-                    const float2 t0 = tree_cmadd(A[j][c], w1, A[j + st][c]);
-                    const float2 t1 = tree_cmadd(A[j + 2 * st][c], w1, A[j + 3 * st][c]);
-                    v[q] = tree_cmadd(t0, w2, t1);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int j = (tid + q * THREADS) / Q_C;
-            if (j < valid) A[j][c] = v[q];
-        }
-        __syncthreads();
-    }
-    for (; l < levels; ++l) {
-        const int st = 1 << l;
-        valid -= st;
-        const float2 w = tw[l][cq + c];
-        float2 v[PER];
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int j = (tid + q * THREADS) / Q_C;
-            if (j < valid) v[q] = tree_cmadd(A[j][c], w, A[j + st][c]);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int j = (tid + q * THREADS) / Q_C;
-            if (j < valid) A[j][c] = v[q];
-        }
-        __syncthreads();
-    }
-    PVQ_STAMP(2);
-    // store: lanes walk the frames of one column (512-byte runs)
-    const int j = tid % BM;
-    const int f = t.f0 + j;
-    if (j < t.S && f < t.nfr) {
-        const bool to_y = t.G.nb > t.G.nb_f;
-        float2* dst = (to_y ? a.Y : a.X) + ((size_t)((f >> 6) + (to_y ? t.yt0 : t.xt0)) * a.xcp + t.nt * CB_C + cq) * 64 + (f & 63);
-        int ncv = t.G.n_cols - t.ntl * CB_C - cq;   // the quarter's real columns
-        ncv = ncv < Q_C ? ncv : Q_C;
-#pragma unroll 4
-        for (int cc = tid / BM; cc < ncv; cc += 2) {
-            const float2 val = A[j][cc];
-            __builtin_nontemporal_store((f32x2){val.x, val.y}, reinterpret_cast<f32x2*>(&dst[cc * 64]));
-        }
-    }
-}
-
-template <int BM>
-__global__ __launch_bounds__(2 * BM, 6) void blockdft_gemm_tree3(GemmTreeArgs a) {   // 6 waves per SIMD = three 512-thread workgroups per CU: at most 80 registers
-    constexpr int B_FLOATS = FR_KC * FT_BN;
-    constexpr int P_FLOATS = (BM + 15) * Q_LDP * 2;
-    __shared__ __attribute__((aligned(16))) float smem[B_FLOATS > P_FLOATS ? B_FLOATS : P_FLOATS];  // the E slice, then a P quarter
-    __shared__ float2 tw_lds[FT_MAXL][CB_C];
-    const unsigned long long t_entry = wall_clock64();
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int4 entry = a.tile_list[blockIdx.x];   // .x: group | segment << 16 (no wide entries in this kernel's lists)
-    const TileStream ts = tile_stream(a, entry.x);
-    const FusedTile T = fused_tile_of<BM>(a, make_int4(entry.x & 7, entry.y, entry.z, entry.w), ts);
-    if (T.f0 >= T.nfr) return;
-    const int stamp_slot = blockIdx.x;
-    PVQ_STAMP(0);
-    const long long s = ts.base + T.G.s_rel;
-    const long long tile_lo = s + (long long)T.f0 * a.K, tile_hi = tile_lo + (long long)BM * a.K;
-    const bool inside = tile_lo >= 0 && tile_hi * 4ll <= (long long)ts.pcm_bytes;
-    const float* tw_src = reinterpret_cast<const float*>(a.comb_tw + T.G.tw_off + T.ntl * CB_C) + lane;
-    float* tw_dst = reinterpret_cast<float*>(&tw_lds[0][0]);
-    const int tw_levels = T.G.levels_f, tw_stride = 2 * T.G.n_tiles * CB_C;
-    const float4* e_tile = a.E16 + (size_t)T.nt * (a.K / 2) * 16;
-    f32x4a accR[2][2], accI[2][2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int np = 0; np < 2; ++np)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                accR[mt][np][r] = 0.0f;
-                accI[mt][np][r] = 0.0f;
-            }
-    if (a.clk != nullptr && (blockIdx.x & 63) == 0 && tid == 0) {
-        a.clk[(blockIdx.x >> 6) * 4 + 0] = __builtin_amdgcn_s_memtime();
-        a.clk[(blockIdx.x >> 6) * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-    }
-    const bool half = T.ntl == T.G.n_tiles - 1 && T.G.n_cols - T.ntl * CB_C <= 16;
-    if (!inside)
-        fused_f32_kloop16_edge<BM>(a, ts.pcm_base, ts.pcm_bytes, smem, tile_lo, e_tile, tid, accR, accI, tw_src, tw_dst, tw_levels, tw_stride, stamp_slot, a.K);
-    else if (half)
-        fused_f32_kloop16s<BM, true>(a, ts.pcm_base, ts.pcm_bytes, smem, tile_lo, e_tile, tid, accR, accI, tw_src, tw_dst, tw_levels, tw_stride, stamp_slot);
-    else
-        fused_f32_kloop16s<BM, false>(a, ts.pcm_base, ts.pcm_bytes, smem, tile_lo, e_tile, tid, accR, accI, tw_src, tw_dst, tw_levels, tw_stride, stamp_slot);
-    if (a.clk != nullptr && (blockIdx.x & 63) == 0 && tid == 0) {
-        a.clk[(blockIdx.x >> 6) * 4 + 2] = __builtin_amdgcn_s_memtime();
-        a.clk[(blockIdx.x >> 6) * 4 + 3] = __builtin_amdgcn_s_memrealtime();
-    }
-    PVQ_STAMP(1);
-    __syncthreads();   // the E slice is dead: the first P' quarter takes its place
-    PVQ_STAMP(4);
-    q_dump_p<BM>(smem, accR, accI, 0, tid);
-    __syncthreads();
-    PVQ_STAMP(5);
-    q_tree_store<BM>(smem, tw_lds, T, a, 0, tid, stamp_slot);
-    if (T.G.n_cols - T.ntl * CB_C > Q_C) {   // (a last tile of at most 16 columns has no second quarter)
-        __syncthreads();
-        q_dump_p<BM>(smem, accR, accI, 1, tid);
-        __syncthreads();
-        q_tree_store<BM>(smem, tw_lds, T, a, Q_C, tid, stamp_slot);
-    }
-    if (a.stamps) {
-        __builtin_amdgcn_s_waitcnt(0);
-        __syncthreads();
-        PVQ_STAMP(3);
-    }
-    PVQ_END_STAMPS
-}
-#endif   // PVQ_DEV_KNOBS
-
-// ------------------------------------------------------------------------------------------------
-// General hops: a multiple of 64 samples that does NOT divide the windows (1 600 samples = 30 analyses per second at 48 kHz, the
-// cadence of pitchvis_serial/src/main.rs:41; the trainer's 3 x chunk, pitchvis_train/src/train.rs:43).  With W = nq hop + rem,
-//
-//     X_f[c] = sum_{q < nq} phi_c^q Q[f + q][c]  +  phi_c^nq R[f + nq][c],     phi_c = e^{-2 pi i c hop / W},
-//     Q[j][c] = sum_{m < hop} x[s + j hop + m] e^{-2 pi i c m / W}   (the whole hop block, as in the power-of-two case),
-//     R[j][c] = sum_{m < rem} x[s + j hop + m] e^{-2 pi i c m / W}   (the block's first rem samples),
-//
-// so every hop block is still transformed once (twice: whole and head) for all the frames that share it — the cost is per SAMPLE,
-// not per frame — and only the combine changes: nq <= 16 terms by Horner's rule instead of a power-of-two tree.  Both GEMMs are the
-// mirrored half-depth form about their block's centre (Q' = Q / rho_Q, R' = R / rho_R); rho_Q goes into the kernel-product
-// coefficients as before and tau_c = phi_c^nq rho_R / rho_Q multiplies R'.  Two launches of this kernel: the R tiles first (256 rows
-// = 256 frames, rows taken nq blocks further on, results to Y — or straight to X for a window shorter than the hop, nq = 0), then
-// the Q tiles (257 - nq frames per tile), which add tau Y on their way out.  Same K loop, same P tile, same X layout as
-// blockdft_gemm_tree: the kernel-product and peak stages do not know the difference.
-// ------------------------------------------------------------------------------------------------
-template <int BM>
-__device__ __forceinline__ void gen_horner(float* smem, const float2* phi, int nq, int tid) {
-    float2 (*A)[FT_LDP] = reinterpret_cast<float2 (*)[FT_LDP]>(smem);  // [BM + 15][33]
-    const int c = tid & (CB_C - 1), j0 = (tid >> 5) * 16;
-    const float2 w = phi[c];
-    float2 acc[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = make_float2(0.0f, 0.0f);
-    // out[i] = v[i] + w (v[i + 1] + w (... + w v[i + nq - 1])): rows taken from the far end; row r feeds output i as term q = r - i
-    for (int r = 15 + nq - 1; r >= 0; --r) {
-        const float2 x = A[j0 + r][c];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int q = r - i;
-            if (q >= 0 && q < nq) acc[i] = tree_cmadd(x, w, acc[i]);   // (uniform; the first term: x + w * 0 = x exactly)
-        }
-    }
-    __syncthreads();   // every thread has read its halo
-#pragma unroll
-    for (int i = 0; i < 16; ++i) A[j0 + i][c] = acc[i];
-    __syncthreads();
-}
-
-template <int BM>
-__global__ __launch_bounds__(2 * BM, 4) void blockdft_gemm_gen(GemmTreeArgs a) {
-    constexpr int B_FLOATS = FR_KC * FT_BN;
-    constexpr int P_FLOATS = (BM + 15) * FT_LDP * 2;
-    __shared__ __attribute__((aligned(16))) float smem[B_FLOATS > P_FLOATS ? B_FLOATS : P_FLOATS];  // the E slice, then the P tile
-    __shared__ float2 gtw[2][CB_C];   // phi, tau of the tile's columns
-    const int tid = threadIdx.x;
-    const int4 entry = a.tile_list[blockIdx.x];   // .x: group | segment << 16
-    const TileStream ts = tile_stream(a, entry.x);
-    const BlockGroup G = a.gv[entry.x & 7];
-    const int ntl = entry.y, f0 = entry.z, nt = G.tile0 + ntl;
-    if (f0 >= ts.n_frames) return;
-    const int stamp_slot = blockIdx.x;
-    const bool is_r = a.gen_kind == 1;
-    const int depth = is_r ? G.rem : a.K;
-    // rows of the tile: hop blocks f0 .. f0 + BM - 1 of the group's block grid (R tiles: nq blocks further on)
-    const long long tile_lo = ts.base + G.s_rel + (long long)(f0 + (is_r ? G.nq : 0)) * a.K;
-    const long long tile_hi = tile_lo + (long long)(BM - 1) * a.K + depth;
-    const bool inside = tile_lo >= 0 && tile_hi * 4ll <= (long long)ts.pcm_bytes;
-    const float4* e_tile = is_r ? a.E16R + G.e16r_off + (size_t)ntl * (G.rem / 2) * 16 : a.E16 + (size_t)nt * (a.K / 2) * 16;
-    if (tid < 2 * CB_C) gtw[tid >> 5][tid & (CB_C - 1)] = a.gen_tw[G.gtw_off + (tid >> 5) * (G.n_tiles * CB_C) + ntl * CB_C + (tid & (CB_C - 1))];
-    f32x4a accR[2][2], accI[2][2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int np = 0; np < 2; ++np)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                accR[mt][np][r] = 0.0f;
-                accI[mt][np][r] = 0.0f;
-            }
-    const bool half = ntl == G.n_tiles - 1 && G.n_cols - ntl * CB_C <= 16;
-    float* no_tw = reinterpret_cast<float*>(&gtw[0][0]);   // (no tree twiddles to stage: tw_levels = 0)
-    if (!inside)
-        fused_f32_kloop16_edge<BM>(a, ts.pcm_base, ts.pcm_bytes, smem, tile_lo, e_tile, tid, accR, accI, no_tw, no_tw, 0, 0, stamp_slot, depth);
-    else if (half)
-        fused_f32_kloop16<BM, true>(a, ts.pcm_base, ts.pcm_bytes, smem, tile_lo, e_tile, tid, accR, accI, no_tw, no_tw, 0, 0, stamp_slot, depth);
-    else
-        fused_f32_kloop16<BM, false>(a, ts.pcm_base, ts.pcm_bytes, smem, tile_lo, e_tile, tid, accR, accI, no_tw, no_tw, 0, 0, stamp_slot, depth);
-    __syncthreads();   // the E slice is dead: the P' tile takes its place
-    fused_dump_p<BM, 2, 0>(smem, accR, accI, tid);
-    __syncthreads();
-    if (!is_r && G.nq > 1) gen_horner<BM>(smem, gtw[0], G.nq, tid);
-    // store: lanes walk the frames of one column (512-byte runs); Q tiles add tau * R'[f + nq] (the R launch left it in Y)
-    float2 (*A)[FT_LDP] = reinterpret_cast<float2 (*)[FT_LDP]>(smem);
-    const int j = tid % BM;
-    const int f = f0 + j;
-    const int S = is_r ? BM : BM - (G.nq > 1 ? G.nq - 1 : 0);
-    if (j < S && f < ts.n_frames) {
-        const size_t at = ((size_t)((f >> 6) + ts.xt0) * a.xcp + nt * CB_C) * 64 + (f & 63);
-        float2* dst = (is_r && G.nq > 0 ? a.Y : a.X) + at;
-        const float2* ysrc = a.Y + at;
-        const bool add_y = !is_r && G.rem > 0;
-        const int ncv = G.n_cols - ntl * CB_C < CB_C ? G.n_cols - ntl * CB_C : CB_C;
-#pragma unroll 4
-        for (int cc = tid / BM; cc < ncv; cc += 2) {
-            float2 val = A[j][cc];
-            if (add_y) val = tree_cmadd(val, gtw[1][cc], ysrc[cc * 64]);
-            if (is_r && G.nq > 0)
-                dst[cc * 64] = val;   // read back by the Q launch: through the L2
-            else
-                __builtin_nontemporal_store((f32x2){val.x, val.y}, reinterpret_cast<f32x2*>(&dst[cc * 64]));
-        }
-    }
-}
-
-// Unfused form of the same GEMM (windows of more than 64 hop blocks: the tree runs as its own kernel over P' in memory):
-// BM rows x 32 complex columns per workgroup, the K loop of the fused kernel, P' written tile-major as (re, im) pairs.
-template <int BM>
-__global__ __launch_bounds__(2 * BM, 2) void blockdft_gemm_rows(GemmArgs a) {
-    __shared__ __attribute__((aligned(16))) float smem[FR_KC * FT_BN];   // the E slice
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // XCD-aware tile order: workgroups are dealt round robin over the 8 XCDs (b and b + 8 share an L2), so an XCD owns
-    // whole row panels: all column tiles that re-read one panel of the stream hit one L2
-    const int b = blockIdx.x;
-    const int xcd = b & 7, bi = b >> 3;
-    const int nt = bi % a.n_col_tiles;
-    const int mt = (bi / a.n_col_tiles) * 8 + xcd;
-    if (mt * BM >= a.n_rows) return;
-    const int j0 = mt * BM;
-    const long long s = a.base + a.tile_s[nt];
-    const long long tile_lo = s + (long long)j0 * a.K, tile_hi = tile_lo + (long long)BM * a.K;
-    const long long row0 = tile_lo + (long long)(wave * 32 + (lane & 31)) * a.K;
-    const int half = lane >> 5;
-    const long long off_f0 = row0 + 16 * half;
-    const long long off_b0 = row0 + a.K - 16 - 16 * half;
-    const float* e_tile = a.E + (size_t)nt * FT_BN;
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        acc0[q] = 0.0f;
-        acc1[q] = 0.0f;
-    }
-    if (tile_lo >= 0 && tile_hi * 4ll <= (long long)a.pcm_bytes)
-        fused_f32_kloop<true, BM>(a, smem, off_f0, off_b0, e_tile, tid, acc0, acc1);
-    else
-        fused_f32_kloop<false, BM>(a, smem, off_f0, off_b0, e_tile, tid, acc0, acc1);
-    // C/D layout of the 32x32 MFMA: col = lane & 31, row = (q & 3) + 8 (q >> 2) + 4 (lane >> 5); a row of the tile is 256 contiguous bytes
-    float2* Pt = reinterpret_cast<float2*>(a.P) + (size_t)nt * a.p_rows * CB_C;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const int row = j0 + wave * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-        if (row < a.n_rows) Pt[(size_t)row * CB_C + (lane & 31)] = make_float2(acc0[q], acc1[q]);
-    }
-}
-
-// Split-bf16 form of the fused kernel ("bf16x3", the default; pvq_vqt_set_gemm_precision): same tile, same
-// epilogue.  Each fp32 operand is written exactly as hi + mid + lo with three bf16 values (8+8+8 mantissa bits)
-// and the product is accumulated in fp32 from the six partial products whose weight is >= 2^-16 (hh, hm, mh, hl,
-// lh, mm); the dropped terms are below 2^-24 of the product, i.e. at fp32 rounding level, and every partial
-// product of two bf16 numbers is exact in fp32.  v_mfma_f32_32x32x16_bf16 runs at 16x the rate of the fp32 MFMA,
-// so six of them replace eight fp32 MFMAs at 6/16 of the matrix-pipe time.  E is split once on the host (planes
-// stored [plane][n][k], k contiguous = the B-operand fragment order); the PCM tile is split while it is staged
-// (16 consecutive samples per thread: 16-byte loads, 16-byte LDS writes).  LDS: 3 planes x (128 + 64) rows x 32
-// bf16 = 36 KB of staging, swizzled instead of padded (4 workgroups per CU), aliased by the P tile.  Measured
-// accuracy equals the fp32 MFMA form (6e-7 of the frame peak); the K loop runs at ~35 % of the bf16 matrix peak,
-// bounded by the LDS staging and barrier structure of a 128 x 64 tile, not by the matrix pipe.
-template <int BM> struct FbGeom {
-    static constexpr int PLANE = (BM + FT_BN) * FB_BK;            // bf16 elements of one plane: BM PCM rows, then 64 E^T rows
-    static constexpr int STAGE_BYTES = 3 * PLANE * 2;             // 36 864 B at BM = 128
-    static constexpr int P_BYTES = (BM + 15) * FT_LDP * 8;        // the P tile that aliases the staging area (+ 15 spare rows: the tree's halo reads need no range check)
-    static constexpr int LDS_BYTES = STAGE_BYTES > P_BYTES ? STAGE_BYTES : P_BYTES;
-};
-// element offset of the 8-sample chunk `ch` (0..3) of row `row` inside a plane.  Rows are 64 bytes, unpadded; the
-// chunk index is XORed with (row / 4) % 4, which makes the b128 fragment reads (16 consecutive rows, one chunk),
-// the PCM staging writes (8 rows x 2 chunks) and the E^T staging writes (4 rows x 4 chunks) bank-conflict free.
-__device__ __forceinline__ int fb_off(int row, int ch) { return row * FB_BK + ((ch ^ ((row >> 2) & 3)) << 3); }
-
-// K loop of the split-bf16 fused kernel.  VEC: the tile's samples all lie inside the stream, so each
-// thread's 16 consecutive samples come as four 16-byte loads; otherwise (tiles that touch the stream start
-// or end) as 16 dword loads, each range-checked by the buffer hardware.
-template <bool VEC, int BM>
-__device__ __forceinline__ void fused_bf16x3_kloop(const GemmTreeArgs& a, const float* pcm_base, unsigned pcm_bytes, unsigned char* smem_raw, long long a_idx0, const __bf16* e_ptr,
-                                                   int tid, f32x16& acc0, f32x16& acc1) {
-    constexpr int FB_PLANE = FbGeom<BM>::PLANE;
-    __bf16* lds = reinterpret_cast<__bf16*>(smem_raw);
-    const int lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
-    const unsigned long long pcm_addr = reinterpret_cast<unsigned long long>(pcm_base);
-    const i32x4 rsrc4 = {(int)(unsigned)pcm_addr, (int)(unsigned)(pcm_addr >> 32), (int)pcm_bytes, 0x00020000};
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pcm_base), 0, pcm_bytes, 0x00020000);
-    // A staging: thread -> (row = tid / 2, 16 consecutive k); B staging: thread -> (n = tid / 4, 8 consecutive k) x 3 planes
-    const int a_row = tid >> 1, b_n = tid >> 2;
-    const size_t plane = (size_t)a.ld * a.K;
-    float ra[16];
-    bf16x8 rb[3];
-    auto load = [&](int k0) {
-        if (VEC) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f32x4 v = pvq_raw_buffer_load_f32x4(rsrc4, (int)((unsigned)(a_idx0 * 4ll) + (unsigned)k0 * 4u + 16u * q), 0, 0);
-                ra[4 * q + 0] = v[0];
-                ra[4 * q + 1] = v[1];
-                ra[4 * q + 2] = v[2];
-                ra[4 * q + 3] = v[3];
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {   // samples before the stream: an explicit out-of-range offset (see fused_f32_stage_load)
-                const long long j = a_idx0 + k0 + q;
-                ra[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, j >= 0 ? (unsigned)(j * 4ll) : 0xFFFFFFFCu, 0, 0));
-            }
-        }
-        if (BM == 128 || tid < 256) {
-#pragma unroll
-            for (int p = 0; p < 3; ++p) rb[p] = *reinterpret_cast<const bf16x8*>(e_ptr + p * plane + k0);
-        }
-    };
-    auto store = [&]() {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            bf16x8 vh, vm, vl;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const float x = ra[8 * h + q];
-                const __bf16 hi = (__bf16)x;
-                const float r1 = x - (float)hi;
-                const __bf16 mid = (__bf16)r1;
-                vh[q] = hi;
-                vm[q] = mid;
-                vl[q] = (__bf16)(r1 - (float)mid);
-            }
-            const int o = fb_off(a_row, (tid & 1) * 2 + h);
-            *reinterpret_cast<bf16x8*>(lds + o) = vh;
-            *reinterpret_cast<bf16x8*>(lds + FB_PLANE + o) = vm;
-            *reinterpret_cast<bf16x8*>(lds + 2 * FB_PLANE + o) = vl;
-        }
-        if (BM == 128 || tid < 256) {   // 64 E^T rows x 4 chunks: 256 threads
-            const int ob = fb_off(BM + b_n, tid & 3);
-#pragma unroll
-            for (int p = 0; p < 3; ++p) *reinterpret_cast<bf16x8*>(lds + p * FB_PLANE + ob) = rb[p];
-        }
-    };
-    const int n_iter = a.K / FB_BK;
-    const int ar = wm * 64 + (lane & 31), kh = lane >> 5, bc = BM + wn * 32 + (lane & 31);
-    load(0);
-    for (int it = 0; it < n_iter; ++it) {
-        store();
-        __syncthreads();
-        if (it + 1 < n_iter) load((it + 1) * FB_BK);
-#pragma unroll
-        for (int kk = 0; kk < FB_BK / 16; ++kk) {
-            bf16x8 a0[3], a1[3], bv[3];
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                a0[p] = *reinterpret_cast<const bf16x8*>(lds + p * FB_PLANE + fb_off(ar, kk * 2 + kh));
-                a1[p] = *reinterpret_cast<const bf16x8*>(lds + p * FB_PLANE + fb_off(ar + 32, kk * 2 + kh));
-                bv[p] = *reinterpret_cast<const bf16x8*>(lds + p * FB_PLANE + fb_off(bc, kk * 2 + kh));
-            }
-            // smallest terms first
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[1], bv[1], acc0, 0, 0, 0);  // mid*mid
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[1], bv[1], acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[0], bv[2], acc0, 0, 0, 0);  // hi*lo
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], bv[2], acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[2], bv[0], acc0, 0, 0, 0);  // lo*hi
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[2], bv[0], acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[0], bv[1], acc0, 0, 0, 0);  // hi*mid
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], bv[1], acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[1], bv[0], acc0, 0, 0, 0);  // mid*hi
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[1], bv[0], acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[0], bv[0], acc0, 0, 0, 0);  // hi*hi
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], bv[0], acc1, 0, 0, 0);
-        }
-        __syncthreads();
-    }
-}
-
-template <int BM>   // rows of hop blocks per tile; 2 * BM threads (wave tile 64 x 32)
-__global__ __launch_bounds__(2 * BM, BM == 128 ? 4 : 2) void blockdft_gemm_tree_bf16x3(GemmTreeArgs a) {
-    __shared__ __attribute__((aligned(16))) unsigned char smem_raw[FbGeom<BM>::LDS_BYTES];
-    __shared__ float2 tw_lds[FT_MAXL][CB_C];
-    float* smem = reinterpret_cast<float*>(smem_raw);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    TileStream ts;
-    const FusedTile T = fused_tile<BM>(a, ts);
-    const int f0 = T.f0, nt = T.nt;
-    if (f0 >= T.nfr) return;
-    if (tid < 256) fused_stage_twiddles(tw_lds, T, a, tid);
-    const int wm = wave >> 1, wn = wave & 1;
-    const long long s = ts.base + T.G.s_rel;
-    const long long tile_lo = s + (long long)f0 * a.K, tile_hi = tile_lo + (long long)BM * a.K;  // sample range of the tile
-    const long long a_off0 = tile_lo + (long long)(tid >> 1) * a.K + (tid & 1) * 16;   // sample index of the thread's 16-sample run
-    const __bf16* e_ptr = a.Et + (size_t)(nt * FT_BN + ((tid & 255) >> 2)) * a.K + (tid & 3) * 8;
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        acc0[q] = 0.0f;
-        acc1[q] = 0.0f;
-    }
-    if (tile_lo >= 0 && tile_hi * 4ll <= (long long)ts.pcm_bytes)
-        fused_bf16x3_kloop<true, BM>(a, ts.pcm_base, ts.pcm_bytes, smem_raw, a_off0, e_ptr, tid, acc0, acc1);
-    else
-        fused_bf16x3_kloop<false, BM>(a, ts.pcm_base, ts.pcm_bytes, smem_raw, a_off0, e_ptr, tid, acc0, acc1);
-    const int bc = wn * 32 + (lane & 31);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const int row = wm * 64 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-        smem[row * (2 * FT_LDP) + bc] = acc0[q];
-        smem[(row + 32) * (2 * FT_LDP) + bc] = acc1[q];
-    }
-    if (tid < 15 * FT_LDP) reinterpret_cast<float2*>(smem)[BM * FT_LDP + tid] = make_float2(0.0f, 0.0f);   // the spare rows
-    __syncthreads();
-    fused_tree_store<BM>(smem, tw_lds, T, a, tid, blockIdx.x);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Last tree levels for windows of more than 64 hop blocks: the fused kernel leaves Y_f = sum_{b<64} phi^b P'[f+b];
-// X'_f = sum_q phi^{64 q} Y_{f+64q} (2 or 4 terms) with the same level-by-level multiply-adds as the rest of the tree.
-// Y_{f+64q} is the same lane of the same column q frame tiles further on: 512-byte runs in, 512-byte runs out.
-// ------------------------------------------------------------------------------------------------
-struct FinishArgs {
-    const float2* Y;
-    float2* X;
-    int xcp;
-    int n_frames;
-    int col0;          // first X column of the group
-    int n_cols;        // columns of the group (padded to its tiles): the twiddle table's row stride
-    int n_real;        // columns of the group that exist (the padding is neither written by the fused kernel nor combined here)
-    int levels_f, levels;
-    const float2* tw;  // the group's combine twiddles: [levels][n_cols]
-    const XTile* xmap; // many-streams launches: per X tile, the Y tile of the same frames and the number of frames that exist
-};
-__global__ __launch_bounds__(256) void blockdft_tree_finish(FinishArgs a) {
-    const int fr = threadIdx.x & 63, cc = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int tile = blockIdx.x;
-    int ytile = tile, n_live = a.n_frames - tile * 64;
-    if (a.xmap) {
-        ytile = a.xmap[tile].y_tile;
-        n_live = a.xmap[tile].live_step & 255;
-    }
-    if (cc >= a.n_real || fr >= n_live) return;
-    const int col = a.col0 + cc;
-    const int nq = 1 << (a.levels - a.levels_f);   // 2 or 4
-    float2 v[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        if (q < nq) v[q] = a.Y[((size_t)(ytile + q) * a.xcp + col) * 64 + fr];
-    const float2 w0 = a.tw[(size_t)a.levels_f * a.n_cols + cc];
-    if (nq == 2) {
-        v[0] = tree_cmadd(v[0], w0, v[1]);
-    } else {
-        const float2 w1 = a.tw[(size_t)(a.levels_f + 1) * a.n_cols + cc];
-        v[0] = tree_cmadd(tree_cmadd(v[0], w0, v[1]), w1, tree_cmadd(v[2], w0, v[3]));
-    }
-    a.X[((size_t)tile * a.xcp + col) * 64 + fr] = v[0];
-}
-
-// ------------------------------------------------------------------------------------------------
-// combine: X_f[c] = sum_b phi_c^b P[f+b][c] by a doubling tree in LDS
-// ------------------------------------------------------------------------------------------------
-struct CombineArgs {
-    const float* P;
-    int p_rows;        // row capacity of the tile-major P
-    float2* X;         // frame-tile blocked: X[((frame / 64) * xcp + col) * 64 + frame % 64]
-    int xcp;
-    int n_frames;      // frames in this chunk
-    int n_rows;        // rows of P present
-    const int* tile_group;
-    const BlockGroup* groups;
-    const float2* comb_tw;
-};
-
-// CT frames x CW complex columns per workgroup; windows of up to MAXNB hop blocks.
-template <int CT, int CW, int MAXNB>
-__global__ __launch_bounds__(256) void blockdft_combine(CombineArgs a) {
-    constexpr int MAXR = CT + MAXNB - 1;
-    __shared__ float2 A[MAXR][CW + 1];   // +1: the transposed store below reads a column per wave
-    const int tid = threadIdx.x;
-    const int col0 = blockIdx.x * CW;          // first complex column of this tile (global X column)
-    const int f0 = blockIdx.y * CT;
-    const BlockGroup G = a.groups[a.tile_group[col0 / CB_C]];
-    const int R = CT + G.nb - 1;
-    const int c = tid & (CW - 1);
-    // stage rows f0 .. f0+R-1 of this column tile
-    for (int idx = tid; idx < R * CW; idx += 256) {
-        const int j = idx / CW;
-        const int row = f0 + j;
-        float2 v = make_float2(0.0f, 0.0f);
-        if (row < a.n_rows)
-            v = *reinterpret_cast<const float2*>(a.P + ((size_t)(col0 / CB_C) * a.p_rows + row) * 64 + 2 * ((col0 % CB_C) + c));
-        A[j][c] = v;
-    }
-    __syncthreads();
-    constexpr int PER = (MAXR * CW + 255) / 256;
-    int valid = R;
-    for (int l = 0; l < G.levels; ++l) {
-        const int s = 1 << l;
-        valid -= s;  // rows with a complete span after this level
-        const float2 w = a.comb_tw[G.tw_off + l * (G.n_tiles * CB_C) + (col0 - G.tile0 * CB_C) + c];
-        float2 v[PER];
-#pragma unroll
-        for (int t = 0; t < PER; ++t) {
-            const int idx = tid + t * 256;
-            const int j = idx / CW;
-            if (j < valid) {
-                const float2 lo = A[j][c], hi = A[j + s][c];
-                v[t] = make_float2(lo.x + (w.x * hi.x - w.y * hi.y), lo.y + (w.x * hi.y + w.y * hi.x));
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < PER; ++t) {
-            const int idx = tid + t * 256;
-            const int j = idx / CW;
-            if (j < valid) A[j][c] = v[t];
-        }
-        __syncthreads();
-    }
-    {
-        const int j = tid & (CT - 1);
-        const int f = f0 + j;
-        if (f < a.n_frames)
-            for (int cc = tid / CT; cc < CW; cc += 256 / CT) a.X[((size_t)(f >> 6) * a.xcp + col0 + cc) * 64 + (f & 63)] = A[j][cc];
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// kernel product + dB:  x_vqt[k] = sum_c K[k][c] X[c] (+ conjugate part), then power_to_db (vqt.rs:889-954)
-//
-// The rows of a window group's spectral kernel are band-limited wavelets: consecutive bins read
-// overlapping, nearly contiguous column ranges (27 % of a 16-bin x 70-column block is non-zero).  A block
-// of 16 bins is therefore a small dense real GEMM per frame tile,
-//     [32 frames x 2 kb] . [2 kb x 32]   (columns: Xr, Xi of kb spectrum columns; outputs: 16 x re, 16 x im),
-// one v_mfma_f32_32x32x2_f32 per spectrum column, with both operands read straight from memory in lane
-// order (X is column-major, so the 32 frames of a column are 256 contiguous bytes; the coefficient table
-// is stored as B operands and stays in L2).  The conjugate part (negative_filter_bank) lands in the same
-// B matrix with the signs of the Xi row flipped.  A workgroup owns FT frames and all bins: its four waves
-// walk disjoint lists of blocks, drop the dB values into LDS, and the frame-wide max / floor / shift of
-// power_to_db is applied from there.
-// ------------------------------------------------------------------------------------------------
-struct BandArgs {
-    const float* X;            // complex spectrum columns, as floats: [frame / 64][column][frame % 64][re, im]
-    int xcp;                   // columns per 64-frame tile of X (incl. pad)
-    int n_frames;
-    int n_bins;
-    int ldb;                   // LDS row stride of the dB tile
-    const BandBlock* blocks;
-    const float* B;
-    const __bf16* B3;          // split-bf16 coefficient planes
-    const int* list;           // [waves][per_wave]: count, then the blocks of that wave
-    int per_wave;
-    float* out_db;             // [n_frames][n_bins]
-    float2* out_cplx;          // optional
-    unsigned* status;          // the handle's sticky flag word: bit 0 <- a live frame holds a non-finite power value
-    const XTile* xmap;         // many-streams launches: per X tile, its output rows and how many of its frames exist (nullptr: tile t holds rows 64 t ...)
-    unsigned long long* stamps;   // developer knob PVQ_STAMPS_DOTS: [workgroup][8] 100 MHz clock: 0 start, 1 wave 0 done with its blocks, 2 all waves done, 3 end
-};
-
-#define PVQ_REF_POWER (0.3f * 0.3f)
-#define PVQ_A_MIN (1e-6f * 1e-6f)
-#define PVQ_TOP_DB 60.0f
-
-// gfx950 lane-row swaps.  Inline asm: this compiler's two-result builtins (__builtin_amdgcn_permlane16_swap /
-// permlane32_swap) were seen to hand the same register to both results once inlined into a larger kernel.
-// x' = [x.rows 0, y.rows 0, x.rows 2, y.rows 2],  y' = [x.rows 1, y.rows 1, x.rows 3, y.rows 3]   (rows of 16 lanes)
-__device__ __forceinline__ void permlane16_swap(float& x, float& y) {
-    asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x), "+v"(y));
-}
-// x' = [x.lo, y.lo],  y' = [x.hi, y.hi]   (halves of 32 lanes)
-__device__ __forceinline__ void permlane32_swap(float& x, float& y) {
-    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x), "+v"(y));
-}
-
-// wave-wide max / min by DPP (within rows of 16 lanes) and the gfx950 row / half swaps (across rows)
-#define PVQ_DPP(v, ctrl) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (v)), (ctrl), 0xf, 0xf, true))
-__device__ __forceinline__ float wave_max(float v) {
-    v = fmaxf(v, PVQ_DPP(v, 0xB1));    // quad_perm(1,0,3,2)
-    v = fmaxf(v, PVQ_DPP(v, 0x4E));    // quad_perm(2,3,0,1)
-    v = fmaxf(v, PVQ_DPP(v, 0x141));   // row_half_mirror
-    v = fmaxf(v, PVQ_DPP(v, 0x140));   // row_mirror
-    float x = v, y = v;
-    permlane16_swap(x, y);
-    v = fmaxf(x, y);
-    x = v;
-    y = v;
-    permlane32_swap(x, y);
-    return fmaxf(x, y);
-}
-__device__ __forceinline__ float wave_min(float v) { return -wave_max(-v); }
-
-// results of one block (C layout: column n = lane & 31: bin row = n & 15, re / im = n >> 4; frame =
-// (q&3) + 8(q>>2) + 4(lane>>5)) -> |x_vqt|^2 into the LDS tile (+ the optional complex output).
-// v_permlane16_swap brings the im column's value into the re column's lane.
-// LDB: compile-time row stride of the tile (0: a.ldb) — with it every LDS address below is one base plus an immediate
-// offset; the optional complex output recomputes its addresses per block (the row stride is laundered through an
-// asm so that 32 loop-invariant 64-bit addresses are not kept live across the whole block loop).
-constexpr int BAND_LDB2 = 260;   // the 64-frame form: up to 256 bins + 4 (rows 4 apart land 16 banks apart)
-constexpr int BAND_LDB3 = 308;   // the 64-frame 8-bin form up to 304 bins (78.8 KB: still two workgroups per CU)
-template <int MT, int LDB>
-__device__ __forceinline__ void band_writeout(const f32x16 (&acc)[MT], float* dbs, const BandArgs& a, long long row0, int n_live, int rstep, int bin0, int nrows,
-                                              int lane) {
-    const int ldb = LDB ? LDB : a.ldb;
-    const int n = lane & 31, kx = lane >> 5;
-    const int row = n & 15, part = n >> 4;
-    const bool mine = part == 0 && row < nrows;
-    const int bin = bin0 + row;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        float im[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            float re = acc[mt][q], o = 0.0f;
-            permlane16_swap(re, o);   // o: rows 0 / 2 now hold the im columns' values
-            im[q] = o;
-        }
-        if (mine) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int fr = mt * 32 + (q & 3) + 8 * (q >> 2) + 4 * kx;
-                dbs[fr * ldb + bin] = acc[mt][q] * acc[mt][q] + im[q] * im[q];
-            }
-            if (a.out_cplx) {
-                int row_stride = a.n_bins;
-                asm volatile("" : "+s"(row_stride));
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const int fr = mt * 32 + (q & 3) + 8 * (q >> 2) + 4 * kx;
-                    if (fr < n_live) a.out_cplx[(size_t)(row0 + (long long)fr * rstep) * row_stride + bin] = make_float2(acc[mt][q], im[q]);
-                }
-            }
-        }
-    }
-}
-
-// power_to_db per frame (vqt.rs:922-954): a wave per frame, lanes over bins.  Up to 512 bins: four (two) frames at a
-// time with their dB values in registers, so the read -> log -> reduce -> rescale chains of the frames overlap
-// (the phase is latency-bound at two waves per SIMD); more bins: one frame at a time through LDS.
-template <int MT, int NW, int LDB = (MT == 2 ? BAND_LDB2 : 0)>
-__device__ __forceinline__ void band_finish(float* dbs, const BandArgs& a, long long row0, int n_live, int rstep, int wave, int lane) {
-    const int ldb = LDB ? LDB : a.ldb;
-    const float ref_db = 10.0f * log10f(PVQ_REF_POWER);
-    // 10 log10(p) = 10 log10(2) * log2(p) on the hardware log2 (1 ulp): within 2e-5 dB of the libm route
-    auto to_db = [&](float p) { return 3.01029995663981f * __log2f(fmaxf(p, PVQ_A_MIN)) - ref_db; };
-    // non-finite input (a NaN / Inf sample inside one of the frame's windows) reaches every bin of the frame as a NaN or Inf
-    // power; fmaxf would silently turn it into the A_MIN floor, so it is flagged instead (Vqt::input_status)
-    bool bad = false;
-    auto flag = [&]() {
-        if (a.status && __builtin_amdgcn_ballot_w64(bad) != 0 && lane == 0) atomicOr(a.status, 1u);
-    };
-    auto in_registers = [&](auto fu_c, auto nkb_c) {
-        constexpr int FU = decltype(fu_c)::value, NKB = decltype(nkb_c)::value;
-        for (int fr0 = wave; fr0 < MT * 32; fr0 += NW * FU) {
-            float d[FU][NKB], mx[FU], mn[FU];
-#pragma unroll
-            for (int u = 0; u < FU; ++u) {
-                mx[u] = -3.40282347e+38f;
-                mn[u] = 3.40282347e+38f;
-                const bool live = fr0 + NW * u < n_live;
-#pragma unroll
-                for (int kk = 0; kk < NKB; ++kk) {
-                    const int k = lane + 64 * kk;
-                    const bool in = k < a.n_bins;
-                    const float p = in ? dbs[(fr0 + NW * u) * ldb + k] : 1.0f;
-                    bad |= live && !(p <= 3.40282347e+38f);
-                    d[u][kk] = to_db(p);
-                    mx[u] = fmaxf(mx[u], in ? d[u][kk] : -3.40282347e+38f);
-                    mn[u] = fminf(mn[u], in ? d[u][kk] : 3.40282347e+38f);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < FU; ++u) {
-                mx[u] = wave_max(mx[u]);
-                mn[u] = wave_min(mn[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < FU; ++u) {
-                const int fr = fr0 + NW * u;
-                if (fr >= n_live) continue;
-                const float floor_db = mx[u] - PVQ_TOP_DB;
-                const float m2 = fmaxf(mn[u], floor_db);
-                float* dst = a.out_db + (size_t)(row0 + (long long)fr * rstep) * a.n_bins;
-#pragma unroll
-                for (int kk = 0; kk < NKB; ++kk) {
-                    const int k = lane + 64 * kk;
-                    const float c = fmaxf(d[u][kk], floor_db);
-                    if (k < a.n_bins) dst[k] = (m2 > 0.0f) ? (c - m2) : fmaxf(c, 0.0f);
-                }
-            }
-        }
-    };
-    if (a.n_bins <= 256) {
-        in_registers(std::integral_constant<int, 4>{}, std::integral_constant<int, 4>{});
-        flag();
-        return;
-    }
-    if (a.n_bins <= 512) {
-        in_registers(std::integral_constant<int, 2>{}, std::integral_constant<int, 8>{});
-        flag();
-        return;
-    }
-    for (int fr = wave; fr < MT * 32; fr += NW) {
-        if (fr >= n_live) break;
-        float* rowp = dbs + fr * ldb;
-        float mx = -3.40282347e+38f, mn = 3.40282347e+38f;
-        for (int k = lane; k < a.n_bins; k += 64) {
-            bad |= !(rowp[k] <= 3.40282347e+38f);
-            const float d = to_db(rowp[k]);
-            rowp[k] = d;
-            mx = fmaxf(mx, d);
-            mn = fminf(mn, d);
-        }
-        mx = wave_max(mx);
-        mn = wave_min(mn);
-        const float floor_db = mx - PVQ_TOP_DB;
-        const float m2 = fmaxf(mn, floor_db);
-        float* dst = a.out_db + (size_t)(row0 + (long long)fr * rstep) * a.n_bins;
-        for (int k = lane; k < a.n_bins; k += 64) {
-            const float c = fmaxf(rowp[k], floor_db);
-            dst[k] = (m2 > 0.0f) ? (c - m2) : fmaxf(c, 0.0f);
-        }
-    }
-    flag();
-}
-
-template <int MT, int NW>   // 32-frame MFMA row tiles per workgroup, waves per workgroup
-__global__ __launch_bounds__(64 * NW, NW / 2) void blockdft_banddots_db(BandArgs a) {
-    const int stamp_slot = blockIdx.x;
-    extern __shared__ __attribute__((aligned(16))) float dbs[];   // [MT * 32][ldb]: |x_vqt|^2, then dB
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int f0 = blockIdx.x * (MT * 32);
-    const int n = lane & 31, kx = lane >> 5;
-    constexpr int col_stride = 128;   // floats between consecutive X columns of a 64-frame tile
-    const float* xtile = a.X + ((size_t)(f0 >> 6) * a.xcp) * col_stride + (f0 & 63) * 2;   // this workgroup's frames
-    // the output rows of this workgroup's frames: rows f0 ... of a single stream, or what the X tile's entry of the map says
-    long long row0 = f0;
-    int n_live = a.n_frames - f0, rstep = 1;
-    if (a.xmap) {   // (uniform)
-        const XTile xt = a.xmap[f0 >> 6];
-        rstep = xt.live_step >> 8;
-        row0 = xt.out_row0 + (long long)(f0 & 63) * rstep;
-        n_live = (xt.live_step & 255) - (f0 & 63);
-        if (n_live <= 0) return;   // (uniform) a staged buffer's gap frames: nothing of this tile is wanted (Vqt::batch_streams_device)
-    }
-    PVQ_STAMP(0);
-    const int* my_list = a.list + wave * a.per_wave;
-    const int n_blocks = __builtin_amdgcn_readfirstlane(my_list[0]);
-    // MT == 2: a lane loads (Re, Im) of one of 64 frames; a half swap then leaves Re of frames 0..31 / Im of frames
-    // 0..31 in the two lane halves of one register (the A operand of row tile 0) and frames 32..63 in the other.
-    // MT == 1: a lane loads the one float it feeds to the MFMA.
-    const float* xa = nullptr;
-    const float2* bp = nullptr;   // column pairs
-    float2 av[BD_NS][BD_KU], bv[BD_NS][BD_KU / 2];
-    auto fetch = [&](int s, int c) {
-#pragma unroll
-        for (int u = 0; u < BD_KU / 2; ++u) bv[s][u] = bp[(size_t)(c / 2 + u) * 64];
-#pragma unroll
-        for (int u = 0; u < BD_KU; ++u) {
-            if (MT == 2)
-                av[s][u] = *reinterpret_cast<const float2*>(xa + (size_t)(c + u) * col_stride);
-            else
-                av[s][u].x = xa[(size_t)(c + u) * col_stride];
-        }
-    };
-    // point the operand streams at a block and put its first BD_NS - 1 stages in flight
-    auto open_block = [&](const BandBlock& blk) {
-        xa = MT == 2 ? xtile + (size_t)blk.x0 * col_stride + lane * 2 : xtile + (size_t)blk.x0 * col_stride + n * 2 + kx;
-        bp = reinterpret_cast<const float2*>(a.B) + (size_t)blk.boff * 32 + lane;
-#pragma unroll
-        for (int s = 0; s < BD_NS - 1; ++s) fetch(s, s * BD_KU);
-    };
-    BandBlock blk{};
-    if (n_blocks > 0) {
-        blk = a.blocks[__builtin_amdgcn_readfirstlane(my_list[1])];
-        open_block(blk);
-    }
-    for (int bi = 0; bi < n_blocks; ++bi) {
-        f32x16 acc[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[mt][q] = 0.0f;
-        auto mul = [&](int s) {
-#pragma unroll
-            for (int u = 0; u < BD_KU; ++u) {
-                const float b = (u & 1) ? bv[s][u / 2].y : bv[s][u / 2].x;
-                if (MT == 2) {
-                    float t0 = av[s][u].x, t1 = av[s][u].y;
-                    permlane32_swap(t0, t1);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(t0, b, acc[0], 0, 0, 0);
-                    acc[MT - 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(t1, b, acc[MT - 1], 0, 0, 0);
-                } else {
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s][u].x, b, acc[0], 0, 0, 0);
-                }
-            }
-        };
-        // ring of BD_NS stages of BD_KU columns: BD_NS - 1 stages of operands in flight while one is multiplied.
-        // kb is a multiple of BD_KU; the fetches run up to (BD_NS - 1) * BD_KU columns past the block (in bounds
-        // by construction, never multiplied).
-        const int kb = __builtin_amdgcn_readfirstlane(blk.kb);
-        const int kb_full = kb - kb % (BD_NS * BD_KU);
-        int c = 0;
-        for (; c < kb_full; c += BD_NS * BD_KU) {   // steady state: no branches, exact load counting
-#pragma unroll
-            for (int s = 0; s < BD_NS; ++s) {
-                fetch((s + BD_NS - 1) % BD_NS, c + (s + BD_NS - 1) * BD_KU);
-                mul(s);
-                // keep a stage's lane swaps (and the waits on its operands) inside the stage: the scheduler would
-                // otherwise hoist the swaps of later stages to the top and wait for the whole ring
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < BD_NS - 1; ++s)         // remainder: the operands are already in flight
-            if (c + s * BD_KU < kb) mul(s);
-        // the next block's first operands fly while this block's results are written out
-        const int bin0 = blk.bin0, nrows = blk.nrows;
-        if (bi + 1 < n_blocks) {
-            blk = a.blocks[__builtin_amdgcn_readfirstlane(my_list[bi + 2])];
-            open_block(blk);
-        }
-        band_writeout<MT, MT == 2 ? BAND_LDB2 : 0>(acc, dbs, a, row0, n_live, rstep, bin0, nrows, lane);
-    }
-    PVQ_STAMP(1);
-    __syncthreads();
-    PVQ_STAMP(2);
-    band_finish<MT, NW>(dbs, a, row0, n_live, rstep, wave, lane);
-    if (a.stamps) {
-        __builtin_amdgcn_s_waitcnt(0);
-        __syncthreads();
-        PVQ_STAMP(3);
-    }
-}
-
-// 16x16x4 form of the fp32 kernel product (64-frame tiles, up to 304 bins: the default): blocks of 8 bins, so a block walks the union
-// of only 8 rows' columns (about 35 instead of 57) — the same products in 39 % fewer matrix-pipe cycles than the 32x32x2 form above.
-// Its first version (round 2) fetched 8 bytes per lane — one complex value of one column — and turned four such registers into the
-// MFMA operands of the four 16-frame tiles with two v_permlane32_swap + two v_permlane16_swap per column pair: 133-150 us per
-// 65 536 frames, bound by its vector-memory instructions.  This form needs NO lane swaps and issues half the loads (16 bytes each):
-// 113-125 us on the same boxes.
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-// Lane (i = lane & 15, kq = lane >> 4) loads 16 bytes of column c + kq: (Re, Im) of the frame PAIR 16 u + i of the tile (frames 32 u + 2 i and + 1), and each
-// of its four registers IS an A operand of v_mfma_f32_16x16x4_f32 as it stands: the k slots of an MFMA are the four columns
-// c .. c + 3 (Re parts for register 0 / 2, Im parts for 1 / 3), its rows the 16 even (registers 0, 1) or odd (2, 3) frames of the
-// half tile u; the B operand of lane (n, kq) is the coefficient of column c + kq for output n (n < 8: re of bin row n, else im),
-// one register for the Re parts and one for the Im parts.  Per four columns: two 16-byte X loads and one 8-byte B load per lane
-// instead of four 8-byte loads + one, eight MFMAs as before, no swaps.  C layout: output n = lane & 15, frame 32 u + 2 (4 (lane >> 4) + r) + p.
-template <int NW, int NS, int LDB, int NU>   // LDB: row stride of the LDS tile (4 mod 16, >= bins); NU: half tiles of 32 frames per workgroup (2: a whole X tile; 1 — half a tile, 4 waves, four workgroups per CU — was measured slower: 141-150 against 121 us)
-__global__ __launch_bounds__(64 * NW, NU == 2 || NW == 8 ? NW / 2 : NW) void blockdft_banddots4c_db(BandArgs a) {   // (four waves per SIMD)
-    // the bin counts an LDS row stride serves (the host's choice of the instantiation): the finish's other size classes fold away
-    if constexpr (LDB == 260) __builtin_assume(a.n_bins <= 256);
-    else if constexpr (LDB == 308) __builtin_assume(a.n_bins > 256 && a.n_bins <= 304);
-    else if constexpr (LDB == 372) __builtin_assume(a.n_bins > 256 && a.n_bins <= 368);   // (257 ... 304 bins come here with the developer knob PVQ_DOTS_F32 behind the split-bf16 GEMM)
-    else if constexpr (LDB == 596) __builtin_assume(a.n_bins > 368 && a.n_bins <= 592);
-    else if constexpr (LDB == 852) __builtin_assume(a.n_bins > 592 && a.n_bins <= 848);
-    else if constexpr (LDB == 1028) __builtin_assume(a.n_bins > 848 && a.n_bins <= 1024);
-    const int stamp_slot = blockIdx.x;
-    extern __shared__ __attribute__((aligned(16))) float dbs[];   // [64][LDB]: |x_vqt|^2, then dB
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int f0 = blockIdx.x * (32 * NU);
-    constexpr int col_stride = 128;   // floats between consecutive X columns of a 64-frame tile
-    const float* xtile = a.X + ((size_t)(f0 >> 6) * a.xcp) * col_stride + (f0 & 63) * 2;   // (a half-tile workgroup starts at frame pair 16 of its tile)
-    // the output rows of this workgroup's frames: rows f0 ... of a single stream, or what the X tile's entry of the map says
-    long long row0 = f0;
-    int n_live = a.n_frames - f0, rstep = 1;
-    if (a.xmap) {   // (uniform)
-        const XTile xt = a.xmap[f0 >> 6];
-        rstep = xt.live_step >> 8;
-        row0 = xt.out_row0 + (long long)(f0 & 63) * rstep;
-        n_live = (xt.live_step & 255) - (f0 & 63);
-        if (n_live <= 0) return;   // (uniform) a staged buffer's gap frames: nothing of this tile is wanted (Vqt::batch_streams_device)
-    }
-    PVQ_STAMP(0);
-    const int* my_list = a.list + wave * a.per_wave;
-    const int n_blocks = __builtin_amdgcn_readfirstlane(my_list[0]);
-    const int n = lane & 15, kq = lane >> 4;
-    const float* xa = nullptr;
-    const float2* bp = nullptr;
-    f32x4 av[NS][NU];
-    float2 bv[NS];
-    auto fetch = [&](int s, int c) {   // stage: columns c .. c + 3 of the block
-        bv[s] = bp[(size_t)(c / 4) * 64];
-#pragma unroll
-        for (int u = 0; u < NU; ++u) av[s][u] = *reinterpret_cast<const f32x4*>(xa + (size_t)c * col_stride + u * 64);
-    };
-    auto open_block = [&](const BandBlock& blk) {
-        xa = xtile + (size_t)(blk.x0 + kq) * col_stride + n * 4;
-        bp = reinterpret_cast<const float2*>(a.B) + (size_t)blk.boff3 * 64 + lane;
-#pragma unroll
-        for (int s = 0; s < NS - 1; ++s) fetch(s, s * 4);
-    };
-    BandBlock blk{};
-    if (n_blocks > 0) {
-        blk = a.blocks[__builtin_amdgcn_readfirstlane(my_list[1])];
-        open_block(blk);
-    }
-    for (int bi = 0; bi < n_blocks; ++bi) {
-        f32x4v acc[NU][2];   // [half tile u][p: even / odd frames]
-#pragma unroll
-        for (int u = 0; u < NU; ++u)
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[u][p][q] = 0.0f;
-        auto mul = [&](int s) {   // independent accumulators between two uses of one
-#pragma unroll
-            for (int part = 0; part < 2; ++part) {   // Re parts of the four columns, then Im parts
-                const float b = part ? bv[s].y : bv[s].x;
-#pragma unroll
-                for (int u = 0; u < NU; ++u) {
-                    acc[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s][u][part], b, acc[u][0], 0, 0, 0);
-                    acc[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s][u][2 + part], b, acc[u][1], 0, 0, 0);
-                }
-            }
-        };
-        const int kb = __builtin_amdgcn_readfirstlane(blk.kb);
-        const int kb_full = kb - kb % (NS * 4);
-        int c = 0;
-        for (; c < kb_full; c += NS * 4) {   // steady state: no branches, exact load counting
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                fetch((s + NS - 1) % NS, c + (s + NS - 1) * 4);
-                mul(s);
-                __builtin_amdgcn_sched_barrier(0);   // keep the waits on a stage's operands inside the stage
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < NS - 1; ++s)          // remainder: the operands are already in flight
-            if (c + s * 4 < kb) mul(s);
-        const int bin0 = blk.bin0, nrows = blk.nrows;
-        if (bi + 1 < n_blocks) {                      // the next block's first operands fly during the write-out
-            blk = a.blocks[__builtin_amdgcn_readfirstlane(my_list[bi + 2])];
-            open_block(blk);
-        }
-        const bool mine = n < nrows;                  // re columns of live rows
-        const int bin = bin0 + n;
-#pragma unroll
-        for (int u = 0; u < NU; ++u)
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                float im[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {   // row_ror:8: lane n <- lane n ^ 8 (through a scalar copy: the DPP of a vector element was seen merged across q)
-                    const float re_q = acc[u][p][q];
-                    im[q] = PVQ_DPP(re_q, 0x128);
-                }
-                if (mine) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) dbs[(32 * u + 8 * kq + 2 * q + p) * LDB + bin] = acc[u][p][q] * acc[u][p][q] + im[q] * im[q];
-                    if (a.out_cplx) {
-                        int row_stride = a.n_bins;
-                        asm volatile("" : "+s"(row_stride));
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const int fr = 32 * u + 8 * kq + 2 * q + p;
-                            if (fr < n_live) a.out_cplx[(size_t)(row0 + (long long)fr * rstep) * row_stride + bin] = make_float2(acc[u][p][q], im[q]);
-                        }
-                    }
-                }
-            }
-    }
-    PVQ_STAMP(1);
-    __syncthreads();
-    PVQ_STAMP(2);
-    band_finish<NU, NW, LDB>(dbs, a, row0, n_live, rstep, wave, lane);
-    if (a.stamps) {
-        __builtin_amdgcn_s_waitcnt(0);
-        __syncthreads();
-        PVQ_STAMP(3);
-    }
-}
-
-// Split-bf16 form of the kernel product (the default, with the split-bf16 GEMM): the fp32 MFMA above runs at 1/16
-// of the bf16 matrix rate, and a 16-bin block is 73 % zeros, so the stage is matrix-bound.  Here X and the
-// coefficients are written as hi + mid + lo bf16 (exact 3-way split, see blockdft_gemm_tree_bf16x3) and eight
-// spectrum columns (16 real k) go through six v_mfma_f32_32x32x16_bf16: 6 x 32 cycles instead of 8 x 64.  A lane
-// (frame m, half kh) loads (Re, Im) of columns 4 kh .. 4 kh + 3 of its frame — the same bytes per lane as the fp32
-// form — and splits them in registers; the coefficient planes come pre-split in B-operand order.
-
-template <int MT, int NW>
-__global__ __launch_bounds__(64 * NW, NW / 2) void blockdft_banddots_db_bf16x3(BandArgs a) {
-    const int stamp_slot = blockIdx.x;
-    extern __shared__ __attribute__((aligned(16))) float dbs[];   // [MT * 32][ldb]: |x_vqt|^2, then dB
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int f0 = blockIdx.x * (MT * 32);
-    const int n = lane & 31, kx = lane >> 5;
-    constexpr int col_stride = 128;   // floats between consecutive X columns of a 64-frame tile
-    const float* xtile = a.X + ((size_t)(f0 >> 6) * a.xcp) * col_stride + (f0 & 63) * 2;   // this workgroup's frames
-    // the output rows of this workgroup's frames: rows f0 ... of a single stream, or what the X tile's entry of the map says
-    long long row0 = f0;
-    int n_live = a.n_frames - f0, rstep = 1;
-    if (a.xmap) {   // (uniform)
-        const XTile xt = a.xmap[f0 >> 6];
-        rstep = xt.live_step >> 8;
-        row0 = xt.out_row0 + (long long)(f0 & 63) * rstep;
-        n_live = (xt.live_step & 255) - (f0 & 63);
-        if (n_live <= 0) return;   // (uniform) a staged buffer's gap frames: nothing of this tile is wanted (Vqt::batch_streams_device)
-    }
-    PVQ_STAMP(0);
-    const int* my_list = a.list + wave * a.per_wave;
-    const int n_blocks = __builtin_amdgcn_readfirstlane(my_list[0]);
-    const float* xa = nullptr;
-    const bf16x8* bp = nullptr;
-    float2 av[B3_NS][MT][4];
-    bf16x8 bv[B3_NS][3];
-    auto fetch = [&](int s, int g) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p) bv[s][p] = bp[((size_t)g * 3 + p) * 64];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) av[s][mt][q] = *reinterpret_cast<const float2*>(xa + (size_t)(8 * g + q) * col_stride + mt * 64);
-    };
-    auto open_block = [&](const BandBlock& blk) {
-        xa = xtile + (size_t)(blk.x0 + 4 * kx) * col_stride + n * 2;
-        bp = reinterpret_cast<const bf16x8*>(a.B3) + (size_t)blk.boff3 * 3 * 64 + lane;
-#pragma unroll
-        for (int s = 0; s < B3_NS - 1; ++s) fetch(s, s);
-    };
-    BandBlock blk{};
-    if (n_blocks > 0) {
-        blk = a.blocks[__builtin_amdgcn_readfirstlane(my_list[1])];
-        open_block(blk);
-    }
-    for (int bi = 0; bi < n_blocks; ++bi) {
-        f32x16 acc[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[mt][q] = 0.0f;
-        auto mul = [&](int s) {
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                bf16x8 vh, vm, vl;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-#pragma unroll
-                    for (int part = 0; part < 2; ++part) {
-                        const float x = part ? av[s][mt][q].y : av[s][mt][q].x;
-                        const __bf16 hi = (__bf16)x;
-                        const float r1 = x - (float)hi;
-                        const __bf16 mid = (__bf16)r1;
-                        vh[2 * q + part] = hi;
-                        vm[2 * q + part] = mid;
-                        vl[2 * q + part] = (__bf16)(r1 - (float)mid);
-                    }
-                }
-                // smallest terms first
-                acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vm, bv[s][1], acc[mt], 0, 0, 0);  // mid*mid
-                acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, bv[s][2], acc[mt], 0, 0, 0);  // hi*lo
-                acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, bv[s][0], acc[mt], 0, 0, 0);  // lo*hi
-                acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, bv[s][1], acc[mt], 0, 0, 0);  // hi*mid
-                acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vm, bv[s][0], acc[mt], 0, 0, 0);  // mid*hi
-                acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, bv[s][0], acc[mt], 0, 0, 0);  // hi*hi
-            }
-        };
-        const int kg = __builtin_amdgcn_readfirstlane(blk.kg);
-        const int kg_full = kg - kg % B3_NS;
-        int g = 0;
-        for (; g < kg_full; g += B3_NS) {   // steady state: no branches, exact load counting
-#pragma unroll
-            for (int s = 0; s < B3_NS; ++s) {
-                fetch((s + B3_NS - 1) % B3_NS, g + s + B3_NS - 1);
-                mul(s);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < B3_NS - 1; ++s)         // remainder: the operands are already in flight
-            if (g + s < kg) mul(s);
-        // the next block's first operands fly while this block's results are written out
-        const int bin0 = blk.bin0, nrows = blk.nrows;
-        if (bi + 1 < n_blocks) {
-            blk = a.blocks[__builtin_amdgcn_readfirstlane(my_list[bi + 2])];
-            open_block(blk);
-        }
-        band_writeout<MT, MT == 2 ? BAND_LDB2 : 0>(acc, dbs, a, row0, n_live, rstep, bin0, nrows, lane);
-    }
-    PVQ_STAMP(1);
-    __syncthreads();
-    PVQ_STAMP(2);
-    band_finish<MT, NW>(dbs, a, row0, n_live, rstep, wave, lane);
-    if (a.stamps) {
-        __builtin_amdgcn_s_waitcnt(0);
-        __syncthreads();
-        PVQ_STAMP(3);
-    }
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// host side
-// ------------------------------------------------------------------------------------------------
 // median over the sampled workgroups of the last profiled fused-GEMM launch: shader clock (MHz) held inside the K loop
 float Vqt::last_sclk_mhz() {
     if (!dev_ || !dev_->block || !dev_->block->d_clk || dev_->block->clk_n <= 0) return 0.0f;
@@ -2267,35 +142,6 @@ pvq_status Vqt::launch_blockdft_path(const float* d_pcm, size_t n_lead, size_t h
     return launch_blockdft_streams(&one, 1, hop, d_out_db, d_out_cplx, n_frames, pk, stream);
 }
 
-// grow-only device buffer: freed and allocated anew when `bytes` exceed its capacity
-template <typename T>
-static pvq_status grow(T** ptr, size_t* cap, size_t bytes, bool* grown = nullptr) {
-    if (grown) *grown = false;
-    if (*cap >= bytes) return PVQ_OK;
-    if (*ptr) PVQ_HIP(hipFree(*ptr));
-    *ptr = nullptr;
-    *cap = 0;
-    PVQ_HIP(hipMalloc(reinterpret_cast<void**>(ptr), bytes));
-    *cap = bytes;
-    if (grown) *grown = true;
-    return PVQ_OK;
-}
-
-// What the stages of one launch share.  X is blocked by 64-frame tiles: [tile][column][64 frames], so the kernel-product workgroup
-// of a tile streams one contiguous region (and a column step is a constant 512 bytes); X_PAD_COLS zeroed columns close every tile.
-struct BlockLaunch {
-    const LaunchShape* shape;
-    const std::vector<BdRun>* runs;
-    const BdStream* streams;
-    bool use_bf;               // the split-bf16 GEMM
-    bool multi;                // several runs, or one whose rows go through the X-tile map: the launch reads the segment table
-    const float* pcm_base;     // the launch's base pointer (a launch of one run: that run's rebased stream pointer, as the single-stream entry point always did)
-    size_t nf;                 // frames the per-frame stages of the launch cover
-    size_t rows_cap;           // row capacity of the unfused stages' P
-    int ntot, xcp;             // floats per row of E; columns per frame tile of X (incl. the zeroed pad columns)
-    const XTile* d_xmap;       // set by the fused GEMM stage: the X-tile map of a multi launch (else nullptr)
-};
-
 // the X (+ Y, P) workspaces for the largest of the call's launches, and the split-bf16 GEMM's E^T planes on first use
 pvq_status Vqt::grow_blockdft_workspaces(const std::vector<LaunchShape>& shapes, size_t rows_cap, bool fused, bool use_bf, hipStream_t stream) {
     BlockDftTables* t = dev_->block;
@@ -2318,355 +164,6 @@ pvq_status Vqt::grow_blockdft_workspaces(const std::vector<LaunchShape>& shapes,
         const std::vector<uint16_t> Et = build_Et_bf16x3(t->h_E, ntot, t->hop);
         PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_Et), Et.size() * 2));
         PVQ_HIP(hipMemcpy(t->d_Et, Et.data(), Et.size() * 2, hipMemcpyHostToDevice));
-    }
-    return PVQ_OK;
-}
-
-// The launch's tile list of one kind, from the cache or built and uploaded with its segment table and X-tile map (one allocation:
-// list | segments | map).  The list is cached per (tile rows, kernel family, the runs' stream geometry): which tiles lie wholly
-// inside their stream — 16-byte loads, wide entries — is decided by the planner with the kernel's own test (tile_inside_stream), so a
-// list built for one geometry must never be used for another (round 3: a list keyed on the frame count alone let a launch read past
-// a shorter stream's end).  A launch of one run hands its stream pointer and output rows over in the kernel arguments: they are not
-// part of its key, so the middle sub-batches of a long stream share one list, and so do different buffers of one geometry.
-static pvq_status get_tile_list(BlockDftTables* t, const BlockLaunch& L, int kind, int bm, int wide_mode, const TileListOptions& opt,
-                                hipStream_t stream, BlockDftTables::TileList** out) {
-    const LaunchShape& sh = *L.shape;
-    std::vector<SegKey> key = sh.segs;
-    if (!L.multi) key[0].pcm_off = key[0].out_row0 = key[0].fbeg = 0;
-    for (auto& c : t->tile_lists)
-        if (c.bm == bm && c.wide == wide_mode && c.multi == L.multi && c.kind == kind && c.key == key && c.slot_data == sh.slot_data) {
-            *out = &c;
-            return PVQ_OK;
-        }
-    BlockDftTables::TileList* tl = &t->tile_lists[t->tile_list_next];
-    t->tile_list_next = (t->tile_list_next + 1) & 7;
-    const HostTileList h = build_tile_list(t->groups, sh.segs, t->hop, bm, wide_mode, kind, opt);
-    std::vector<SegDev> hsegs;
-    std::vector<XTile> hmap;
-    build_segment_map(L.streams, *L.runs, sh, hsegs, hmap);
-    const size_t b_list = h.list.size() * sizeof(int4), b_segs = (hsegs.size() * sizeof(SegDev) + 15) / 16 * 16, b_map = hmap.size() * sizeof(XTile);
-    pvq_status s = grow(&tl->d, &tl->cap, b_list + b_segs + b_map);
-    if (s != PVQ_OK) return s;
-    PVQ_HIP(hipStreamSynchronize(stream));   // an earlier launch may still read this slot
-    char* dbase = reinterpret_cast<char*>(tl->d);
-    PVQ_HIP(hipMemcpy(dbase, h.list.data(), b_list, hipMemcpyHostToDevice));
-    PVQ_HIP(hipMemcpy(dbase + b_list, hsegs.data(), hsegs.size() * sizeof(SegDev), hipMemcpyHostToDevice));
-    PVQ_HIP(hipMemcpy(dbase + b_list + b_segs, hmap.data(), b_map, hipMemcpyHostToDevice));
-    tl->d_segs = reinterpret_cast<const SegDev*>(dbase + b_list);
-    tl->d_xmap = reinterpret_cast<const XTile*>(dbase + b_list + b_segs);
-    tl->key = key;
-    tl->slot_data = sh.slot_data;
-    tl->bm = bm;
-    tl->wide = wide_mode;
-    tl->multi = L.multi;
-    tl->kind = kind;
-    tl->blocks = (int)h.list.size();
-    tl->eff_tiles = h.eff_tiles;
-    tl->eff_flop = h.eff_flop;
-    *out = tl;
-    return PVQ_OK;
-}
-
-// developer knobs PVQ_STAMPS / PVQ_STAMPS_DOTS: the phase stamps of one launch to a file, once the launch has finished
-static pvq_status dump_stamps(const char* path, unsigned long long* d_stamps, size_t n_words, hipStream_t stream) {
-    std::vector<unsigned long long> h(n_words);
-    PVQ_HIP(hipStreamSynchronize(stream));
-    PVQ_HIP(hipMemcpy(h.data(), d_stamps, h.size() * 8, hipMemcpyDeviceToHost));
-    PVQ_HIP(hipFree(d_stamps));
-    if (FILE* fp = fopen(path, "wb")) {
-        fwrite(h.data(), 8, h.size(), fp);
-        fclose(fp);
-    }
-    return PVQ_OK;
-}
-
-// GEMM + tree fused: picks the tile shape, fetches the launch's tile list(s) and runs the kernel family of the hop and arithmetic
-pvq_status Vqt::launch_blockdft_gemm_fused(BlockLaunch& L, hipStream_t stream) {
-    BlockDftTables* t = dev_->block;
-    const std::vector<SegKey>& segs = L.shape->segs;
-    const size_t hop = t->hop;
-    const bool use_bf = L.use_bf;
-    if (segs.size() > 0xFFFFu) {
-        set_last_error("too many streams in one launch");
-        return PVQ_ERR_INTERNAL;
-    }
-    // 256-row tiles: 257 - Nb complete frames per tile (1.08x row recomputation instead of 1.2x with 128 rows) — for a launch that
-    // fills the chip's 512 workgroup slots a few times over.  A smaller one (fewer than FUSED_SMALL 256-row tiles: up to ~12 000
-    // frames at 48 kHz / 252 bins) takes 128-row tiles: twice the workgroups, each half as long — what such a launch lacks is
-    // parallelism, not efficiency (hop 1 600: 4 096 frames 294 -> 216 us, 8 192: 324 -> 292; hop 256: 2 048 frames 61 -> 54;
-    // profiles/r04_small_tiles.txt).  Same bits either way (a frame's values do not depend on its tile: tests/test_tile_shapes).
-    constexpr double FUSED_SMALL = 1400.0;
-    static const int bm_env = dev_knob("PVQ_FUSED_BM", 0);          // 128: 128-row tiles (the tile-shape bit-identity test)
-    int fused_bm = 256;
-    if (!use_bf && (bm_env == 128 || (bm_env == 0 && fused_tile_count(t->groups, segs, 256, use_bf) < FUSED_SMALL))) fused_bm = 128;
-    // the tile order's knobs (blockdft_plan.hpp: build_tile_list)
-    static const TileListOptions opt = [] {
-        TileListOptions o;
-        o.fs = dev_knob("PVQ_TILE_FS", 2048);
-        o.balance = dev_knob("PVQ_BALANCE", 1);
-        o.tail = dev_knob("PVQ_TAIL", 128);
-        return o;
-    }();
-    static const int wide_env = dev_knob("PVQ_WIDE", 1);         // 0: narrow tiles only; 2: wide tiles to the very end of every queue
-#ifdef PVQ_DEV_KNOBS
-    static const int tree3_env = dev_knob("PVQ_TREE3", 0);       // 1: blockdft_gemm_tree3 (three workgroups per CU, 32-column tiles, P' in 16-column quarters)
-    const bool tree3 = tree3_env && !use_bf && fused_bm == 256 && !t->general;
-#else
-    const bool tree3 = false;
-#endif
-    const int wide_mode = !use_bf && fused_bm == 256 && !t->general && !tree3 ? wide_env : 0;   // (the split-bf16 kernel, the 128-row form and the general-hop kernel take 32-column tiles only)
-    BlockDftTables::TileList* tl = nullptr;
-    BlockDftTables::TileList* tl_r = nullptr;   // general hops: the remainder tiles
-    pvq_status ls;
-    if (t->general) {
-        if ((ls = get_tile_list(t, L, 1, fused_bm, wide_mode, opt, stream, &tl_r)) != PVQ_OK) return ls;
-        if ((ls = get_tile_list(t, L, 2, fused_bm, wide_mode, opt, stream, &tl)) != PVQ_OK) return ls;
-        // (the second lookup may have evicted the first — the slots are handed out round robin — look it up again)
-        if ((ls = get_tile_list(t, L, 1, fused_bm, wide_mode, opt, stream, &tl_r)) != PVQ_OK) return ls;
-    } else if ((ls = get_tile_list(t, L, 0, fused_bm, wide_mode, opt, stream, &tl)) != PVQ_OK)
-        return ls;
-    L.d_xmap = L.multi ? tl->d_xmap : nullptr;
-    const int n_wg = tl->blocks;   // list entries = workgroups of the non-persistent forms = rows of the stamp dump
-    GemmTreeArgs fa;
-    fa.pcm_base = L.pcm_base;
-    fa.pcm_bytes = segs[0].pcm_bytes;
-    fa.E = t->d_E;
-    fa.ld = L.ntot;
-    fa.X = t->d_X;
-    fa.Y = t->d_Y;
-    fa.xcp = L.xcp;
-    fa.n_frames = (int)segs[0].nf;
-    fa.K = (int)hop;
-    fa.base = segs[0].base;
-    fa.n_groups = t->n_groups;
-    fa.tile_list = tl->d;
-    fa.segs = L.multi ? tl->d_segs : nullptr;
-    fa.groups = t->d_groups;
-    for (int g = 0; g < 8; ++g) fa.gv[g] = t->groups[std::min(g, t->n_groups - 1)];
-    fa.comb_tw = t->d_comb_tw;
-    fa.Et = t->d_Et;
-    fa.E16 = t->d_E16;
-    fa.E16R = t->d_E16R;
-    fa.gen_tw = t->d_gen_tw;
-    fa.gen_kind = 0;
-    static const char* stamps_env = dev_knob_str("PVQ_STAMPS");   // dump per-tile phase stamps of the first launch
-    static bool stamps_done = false;
-    static int stamps_skip = dev_knob("PVQ_STAMPS_SKIP", 0);         // ... of launch n + 1 (a warm one)
-    const bool do_stamps = stamps_env && !stamps_done && stamps_skip-- <= 0;
-    fa.stamps = nullptr;
-    if (do_stamps) PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&fa.stamps), (size_t)n_wg * 12 * 8 + 8));   // rows of 8, then rows of 4 (PVQ_END_STAMPS)
-    if (do_stamps) PVQ_HIP(hipMemset(fa.stamps, 0, (size_t)n_wg * 12 * 8 + 8));
-    // flop the GEMM's matrix instructions issue in this launch: tiles x rows x 64 real columns x depth x 2
-    // (depth hop / 2 in the mirrored fp32 form, hop in the split-bf16 form, where it counts fp32-equivalent products; fp32: what the
-    // list's entries issue: a wide entry two whole tiles, a lone half tile half a tile)
-    const double eff_tiles = use_bf ? fused_tile_count(t->groups, segs, fused_bm, use_bf) : tl->eff_tiles;
-    last_gemm_flop_ = eff_tiles * fused_bm * (2 * CB_C) * (use_bf ? (double)hop : (double)hop / 2) * 2.0;
-    fa.clk = nullptr;
-    if (profiling_ && !use_bf) {
-        const size_t need = ((size_t)n_wg / 64 + 1) * 4 * sizeof(unsigned long long);
-        bool grown = false;
-        if ((ls = grow(&t->d_clk, &t->clk_cap, need, &grown)) != PVQ_OK) return ls;
-        if (grown) PVQ_HIP(hipMemset(t->d_clk, 0, need));   // once: every sampled workgroup rewrites its slot at every launch (a fill per launch cost the stream 3 us)
-        t->clk_n = n_wg / 64 + 1;
-        fa.clk = t->d_clk;
-    }
-    slot_begin(SLOT_BLOCKDFT_GEMM, stream);
-    if (t->general) {
-        // the remainder tiles first (their results wait in Y), then the whole-block tiles; flop: both launches' K loops
-        double flop = 0.0;
-        for (int kind = 1; kind <= 2; ++kind) {
-            const BlockDftTables::TileList* list = kind == 1 ? tl_r : tl;
-            if (list->blocks == 0 || list->eff_tiles == 0.0) continue;
-            GemmTreeArgs ga = fa;
-            ga.tile_list = list->d;
-            ga.segs = L.multi ? list->d_segs : nullptr;
-            ga.gen_kind = kind;
-            ga.stamps = nullptr;
-            ga.clk = nullptr;
-            if (fused_bm == 256)
-                hipLaunchKernelGGL(blockdft_gemm_gen<256>, dim3(list->blocks), dim3(512), 0, stream, ga);
-            else
-                hipLaunchKernelGGL(blockdft_gemm_gen<128>, dim3(list->blocks), dim3(256), 0, stream, ga);
-            flop += list->eff_flop;
-        }
-        last_gemm_flop_ = flop;
-    } else if (use_bf)
-        hipLaunchKernelGGL(blockdft_gemm_tree_bf16x3<256>, dim3(n_wg), dim3(512), 0, stream, fa);
-#ifdef PVQ_DEV_KNOBS
-    else if (tree3)
-        hipLaunchKernelGGL(blockdft_gemm_tree3<256>, dim3(n_wg), dim3(512), 0, stream, fa);
-#endif
-    else if (fused_bm == 256 && fa.K == 256 && dev_knob("PVQ_KFIX", 1))   // the instantiations that know the hop: 2 % fewer cycles (its strides and trip counts fold)
-        hipLaunchKernelGGL((blockdft_gemm_tree<256, 256>), dim3(n_wg), dim3(512), 0, stream, fa);
-    else if (fused_bm == 256)
-        hipLaunchKernelGGL(blockdft_gemm_tree<256>, dim3(n_wg), dim3(512), 0, stream, fa);
-    else
-        hipLaunchKernelGGL(blockdft_gemm_tree<128>, dim3(n_wg), dim3(256), 0, stream, fa);
-    slot_end(SLOT_BLOCKDFT_GEMM, stream);
-    if (do_stamps) {
-        stamps_done = true;
-        return dump_stamps(stamps_env, fa.stamps, (size_t)n_wg * 12, stream);
-    }
-    return PVQ_OK;
-}
-
-// the last one or two tree levels of the windows of more than 64 hop blocks: Y (64-block partial sums) -> X
-void Vqt::launch_blockdft_tree_finish(const BlockLaunch& L, hipStream_t stream) {
-    BlockDftTables* t = dev_->block;
-    slot_begin(SLOT_BLOCKDFT_COMBINE, stream);
-    for (int g = 0; g < t->n_groups; ++g) {
-        const BlockGroup& G = t->groups[g];
-        if (G.nb <= G.nb_f) continue;
-        FinishArgs fin;
-        fin.Y = t->d_Y;
-        fin.X = t->d_X;
-        fin.xcp = L.xcp;
-        fin.n_frames = (int)L.nf;
-        fin.col0 = G.tile0 * CB_C;
-        fin.n_cols = G.n_tiles * CB_C;
-        fin.n_real = G.n_cols;
-        fin.levels_f = G.levels_f;
-        fin.levels = G.levels;
-        fin.tw = t->d_comb_tw + G.tw_off;
-        fin.xmap = L.d_xmap;
-        hipLaunchKernelGGL(blockdft_tree_finish, dim3((unsigned)((L.nf + 63) / 64), (unsigned)((fin.n_real + 3) / 4)), dim3(256), 0,
-                           stream, fin);
-    }
-    slot_end(SLOT_BLOCKDFT_COMBINE, stream);
-}
-
-// GEMM and tree as two kernels with P in memory (more than 8 window groups, or PVQ_NO_FUSE in the developer library): one stream
-void Vqt::launch_blockdft_gemm_unfused(const BlockLaunch& L, hipStream_t stream) {
-    BlockDftTables* t = dev_->block;
-    const size_t hop = t->hop, nf = L.nf;
-    const int n_rows = (int)(nf + t->nb_max - 1);
-    GemmArgs ga;
-    ga.pcm_base = L.pcm_base;
-    ga.pcm_bytes = L.shape->segs[0].pcm_bytes;
-    ga.E = t->d_E;
-    ga.ld = L.ntot;
-    ga.P = t->d_P;
-    ga.n_rows = n_rows;
-    ga.K = (int)hop;
-    ga.tile_s = t->d_tile_s;
-    ga.base = L.shape->segs[0].base;
-    ga.n_col_tiles = t->n_tiles;
-    ga.p_rows = (int)L.rows_cap;
-    const int m_tiles8 = (((n_rows + 255) / 256) + 7) / 8 * 8;
-    last_gemm_flop_ = (double)ga.n_col_tiles * ((n_rows + 255) / 256) * 256.0 * FT_BN * ((double)hop / 2) * 2.0;
-    slot_begin(SLOT_BLOCKDFT_GEMM, stream);
-    hipLaunchKernelGGL(blockdft_gemm_rows<256>, dim3(ga.n_col_tiles * m_tiles8), dim3(512), 0, stream, ga);
-    slot_end(SLOT_BLOCKDFT_GEMM, stream);
-    CombineArgs ca;
-    ca.P = t->d_P;
-    ca.p_rows = (int)L.rows_cap;
-    ca.X = t->d_X;
-    ca.xcp = L.xcp;
-    ca.n_frames = (int)nf;
-    ca.n_rows = n_rows;
-    ca.tile_group = t->d_tile_group;
-    ca.groups = t->d_groups;
-    ca.comb_tw = t->d_comb_tw;
-    slot_begin(SLOT_BLOCKDFT_COMBINE, stream);
-    if (t->nb_max <= 64)
-        hipLaunchKernelGGL((blockdft_combine<128, 16, 64>), dim3(t->n_tiles * 2, (unsigned)((nf + 127) / 128)), dim3(256), 0,
-                           stream, ca);
-    else
-        hipLaunchKernelGGL((blockdft_combine<CB_T, 16, 256>), dim3(t->n_tiles * 2, (unsigned)((nf + CB_T - 1) / CB_T)), dim3(256),
-                           0, stream, ca);
-    slot_end(SLOT_BLOCKDFT_COMBINE, stream);
-}
-
-// kernel product + power_to_db over the launch's X tiles: the form follows the bin count and the GEMM arithmetic
-pvq_status Vqt::launch_blockdft_dots(const BlockLaunch& L, float* d_out_db, float* d_out_cplx, hipStream_t stream) {
-    BlockDftTables* t = dev_->block;
-    const int nb = (int)n_bins();
-    const size_t nf = L.nf;
-    BandArgs da;
-    da.X = reinterpret_cast<const float*>(t->d_X);
-    da.xcp = L.xcp;
-    da.n_frames = (int)nf;
-    da.n_bins = nb;
-    // 4 rows apart (the two lane halves of a C tile) land 16 banks apart; the 64-frame form has the stride compiled in
-    // more than 256 bins (32-frame tiles): the smallest stride >= n_bins that is 4 mod 16, so that up to 596 bins still fit two workgroups per CU
-    // 64-frame tiles while two 64-row tiles fit a CU: up to 256 bins (stride 260) or up to 304 (stride 308; fp32 8-bin form only)
-    const bool wide308 = !gemm_split_bf16_ && t->n_bins_pad > 256 && nb <= BAND_LDB3 - 4;
-    const bool wide = t->n_bins_pad <= 256 || wide308;
-    da.ldb = wide308 ? BAND_LDB3 : wide ? BAND_LDB2 : ((nb + 11) / 16 * 16 + 4);
-    da.blocks = t->d_band;
-    da.B = t->d_band_B;
-    da.B3 = t->d_band_B3;
-    da.list = t->d_band_list;
-    da.per_wave = t->band_per_wave;
-    // one run: its rows follow each other from its first output row; several: the X-tile map names every tile's rows
-    da.xmap = L.d_xmap;
-    const size_t row_first = L.multi ? 0 : (size_t)L.shape->segs[0].out_row0;
-    da.out_db = d_out_db + row_first * nb;
-    da.out_cplx = d_out_cplx ? reinterpret_cast<float2*>(d_out_cplx) + row_first * nb : nullptr;
-    da.status = dev_->d_status;
-    static const char* dstamps_env = dev_knob_str("PVQ_STAMPS_DOTS");   // dump per-workgroup phase stamps of the first launch
-    static bool dstamps_done = false;
-    const bool do_dstamps = dstamps_env && !dstamps_done;
-    da.stamps = nullptr;
-    const size_t n_wg = (nf + 63) / 32;   // upper bound of the grid
-    if (do_dstamps) PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&da.stamps), n_wg * 8 * 8));
-    if (do_dstamps) PVQ_HIP(hipMemset(da.stamps, 0, n_wg * 8 * 8));
-    slot_begin(SLOT_BLOCKDFT_DOTS, stream);
-    const int mt = wide ? 2 : 1;
-    static const int dots_f32_env = dev_knob("PVQ_DOTS_F32", 0);
-    const bool dots_split = gemm_split_bf16_ && !dots_f32_env;   // the kernel product follows the GEMM arithmetic
-#ifdef PVQ_DEV_KNOBS
-    static const int dots16_env = dev_knob("PVQ_DOTS_16BIN", 0);   // the 16-bin 32x32x2 form wherever it fits
-#else
-    constexpr int dots16_env = 0;
-#endif
-    const size_t lds = sizeof(float) * 32 * mt * da.ldb;
-    const dim3 grid((unsigned)((nf + 32 * mt - 1) / (32 * mt)));
-    auto use_8bin_blocks = [&] {   // 8-bin blocks, 16x16x4 MFMAs, the no-swap coefficient order
-        da.blocks = t->d_band8;
-        da.list = t->d_band_list8;
-        da.per_wave = t->band_per_wave8;
-        da.B = t->d_band_B4;
-    };
-    if (dots_split) {
-        da.list = t->d_band_list + (size_t)t->band_waves * t->band_per_wave;   // the 4-wave lists
-        if (mt == 2)
-            hipLaunchKernelGGL((blockdft_banddots_db_bf16x3<2, 4>), grid, dim3(256), lds, stream, da);
-        else
-            hipLaunchKernelGGL((blockdft_banddots_db_bf16x3<1, 4>), grid, dim3(256), lds, stream, da);
-#ifdef PVQ_DEV_KNOBS
-    } else if (mt == 2 && dots16_env && !wide308) {
-        hipLaunchKernelGGL((blockdft_banddots_db<2, 8>), grid, dim3(512), lds, stream, da);
-#endif
-    } else if (mt == 2) {
-        use_8bin_blocks();
-        if (wide308)
-            hipLaunchKernelGGL((blockdft_banddots4c_db<8, BD8_NS, BAND_LDB3, 2>), grid, dim3(512), lds, stream, da);
-        else
-            hipLaunchKernelGGL((blockdft_banddots4c_db<8, BD8_NS, BAND_LDB2, 2>), grid, dim3(512), lds, stream, da);
-    } else if (dots16_env || nb > 1024 - 4) {
-        hipLaunchKernelGGL((blockdft_banddots_db<1, 8>), grid, dim3(512), lds, stream, da);
-    } else {
-        // more than 304 bins (the reference's default 588, 360, 840): the 8-bin / 16x16x4 / no-swap form on HALF tiles (32 frames x all bins
-        // per workgroup, 8 waves), its LDS row stride compiled in per class of bin counts — round 5; before, these geometries ran the
-        // 16-bin 32x32x2 form (PVQ_DOTS_16BIN=1 in the developer library)
-        use_8bin_blocks();
-        const int ldb_c = nb <= 368 ? 372 : nb <= 592 ? 596 : nb <= 848 ? 852 : 1028;
-        da.ldb = ldb_c;
-        const size_t lds_c = sizeof(float) * 32 * ldb_c;
-        auto launch_c = [&](auto kern) -> pvq_status {
-            if (lds_c > 64 * 1024) PVQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
-            hipLaunchKernelGGL(kern, grid, dim3(512), lds_c, stream, da);
-            return PVQ_OK;
-        };
-        pvq_status lcs = ldb_c == 372 ? launch_c(blockdft_banddots4c_db<8, BD8_NS, 372, 1>) : ldb_c == 596 ? launch_c(blockdft_banddots4c_db<8, BD8_NS, 596, 1>)
-                         : ldb_c == 852 ? launch_c(blockdft_banddots4c_db<8, BD8_NS, 852, 1>) : launch_c(blockdft_banddots4c_db<8, BD8_NS, 1028, 1>);
-        if (lcs != PVQ_OK) return lcs;
-    }
-    slot_end(SLOT_BLOCKDFT_DOTS, stream);
-    if (do_dstamps) {
-        dstamps_done = true;
-        return dump_stamps(dstamps_env, da.stamps, n_wg * 8, stream);
     }
     return PVQ_OK;
 }

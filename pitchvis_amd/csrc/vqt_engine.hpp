@@ -46,7 +46,7 @@ struct AnalysisParameters {
 
 struct DeviceTables;   // opaque (device_tables.hpp)
 struct PeakParamsDev;  // peaks_device.hpp
-struct BlockLaunch;    // vqt_blockdft.hip
+struct BlockLaunch;    // blockdft_device.hpp
 struct FftArgs;        // vqt_engine.hip
 
 class Vqt {
@@ -141,7 +141,7 @@ class Vqt {
                                        const PeakParamsDev* pk, hipStream_t stream);
     pvq_status stage_buffer(const StagedBuffer& b, size_t hop, hipStream_t stream);   // the staged buffer into ws_stage_: piece table up, copy kernel
     pvq_status prepare_blockdft(size_t hop);
-    // the stages of one launch of the block-DFT path (vqt_blockdft.hip)
+    // the stages of one launch of the block-DFT path (vqt_blockdft.hip walks them; blockdft_gemm.hip, blockdft_dots.hip)
     pvq_status grow_blockdft_workspaces(const std::vector<LaunchShape>& shapes, size_t rows_cap, bool fused, bool use_bf, hipStream_t stream);
     pvq_status launch_blockdft_gemm_fused(BlockLaunch& L, hipStream_t stream);
     void launch_blockdft_gemm_unfused(const BlockLaunch& L, hipStream_t stream);

@@ -2,7 +2,7 @@
 lies between one workgroup's end and the next one's start on a slot (the dispatcher's gap), and how even the eight XCD queues run."""
 import sys, numpy as np
 raw = np.fromfile(sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/stamps.bin", dtype=np.uint64).astype(np.int64)
-SLOTS = int(sys.argv[2]) if len(sys.argv) > 2 else 512   # workgroup slots of the chip: 2 per CU (3 for blockdft_gemm_tree3)
+SLOTS = int(sys.argv[2]) if len(sys.argv) > 2 else 512   # workgroup slots of the chip: 2 per CU
 n = len(raw) // 12
 s8, s4 = raw[:n * 8].reshape(n, 8), raw[n * 8:n * 12].reshape(n, 4)
 idx = np.nonzero(s4[:, 0] > 0)[0]          # (padding entries of the tile list leave no stamps)

@@ -147,7 +147,8 @@ def _ints(m):
 
 
 def test_kernel_product_thresholds_match_the_restatement():
-    s = _src("vqt_blockdft.hip") + _src("blockdft_plan.cpp") + _src("blockdft_plan.hpp")   # (the launches; the path's host planning)
+    # (the block-DFT path's three units and their shared header: the launches; the path's host planning)
+    s = "".join(_src(f) for f in ("vqt_blockdft.hip", "blockdft_gemm.hip", "blockdft_dots.hip", "blockdft_device.hpp", "blockdft_plan.cpp", "blockdft_plan.hpp"))
     ldb2 = int(re.search(r"constexpr int BAND_LDB2 = (\d+);", s).group(1))
     ldb3 = int(re.search(r"constexpr int BAND_LDB3 = (\d+);", s).group(1))
     assert (ldb2, ldb3) == (260, 308)

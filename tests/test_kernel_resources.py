@@ -16,20 +16,24 @@ HIPCC = "/opt/rocm/bin/hipcc"
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_register_budgets_of_the_block_dft_kernels(tmp_path):
-    src = os.path.join(ROOT, "pitchvis_amd", "csrc", "vqt_blockdft.hip")
-    r = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Rpass-analysis=kernel-resource-usage",
-                        "-c", src, "-o", str(tmp_path / "x.o")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
+    # the block-DFT path's three units (vqt_blockdft.hip: host side; blockdft_gemm.hip; blockdft_dots.hip), usage and bodies merged over them
+    units = ("vqt_blockdft.hip", "blockdft_gemm.hip", "blockdft_dots.hip")
     usage = {}
-    name = None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name:
-            usage[name][m.group(1).split(" ")[0]] = int(m.group(2))
+    for unit in units:
+        src = os.path.join(ROOT, "pitchvis_amd", "csrc", unit)
+        r = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Rpass-analysis=kernel-resource-usage",
+                            "-c", src, "-o", str(tmp_path / "x.o")], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        name = None
+        for line in r.stderr.splitlines():
+            m = re.search(r"Function Name: (\S+)", line)
+            if m:
+                name = m.group(1)
+                assert name not in usage, name
+                usage[name] = {}
+            m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
+            if m and name:
+                usage[name][m.group(1).split(" ")[0]] = int(m.group(2))
 
     def find(sub):
         hits = [v for k, v in usage.items() if sub in k]
@@ -40,22 +44,28 @@ def test_register_budgets_of_the_block_dft_kernels(tmp_path):
         # two 512-thread workgroups per CU; a few dwords of the tile set-up (stream-edge variant) may spill, the K loop bodies may not
         assert u["VGPRs"] + u.get("AGPRs", 0) <= 128 and u["ScratchSize"] <= 64, u
     asm = tmp_path / "x.s"
-    r = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", src, "-o", str(asm)],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    body, inside = {}, None
-    for line in asm.read_text().splitlines():
-        m = re.match(r"(_ZN3pvq\w+):", line)
-        if m:
-            inside = m.group(1)
-            body[inside] = []
-        elif line.startswith(".Lfunc_end"):
-            inside = None
-        elif inside:
-            body[inside].append(line)
-    # The product build holds exactly the kernels its dispatch can reach (vqt_blockdft.hip: launch_blockdft_gemm_fused / _gemm_unfused /
-    # _tree_finish / _dots): the forms that only a developer knob selects — blockdft_gemm_tree3, the 16-bin kernel product on 64-frame
-    # tiles (blockdft_banddots_db<MT = 2, NW = 8>) — compile under -DPVQ_DEV_KNOBS alone.
+    body, in_unit = {}, {}
+    for unit in units:
+        r = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only",
+                            os.path.join(ROOT, "pitchvis_amd", "csrc", unit), "-o", str(asm)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        inside = None
+        in_unit[unit] = set()
+        for line in asm.read_text().splitlines():
+            m = re.match(r"(_ZN3pvq\w+):", line)
+            if m:
+                inside = m.group(1)
+                assert inside not in body, inside
+                body[inside] = []
+                in_unit[unit].add(inside)
+            elif line.startswith(".Lfunc_end"):
+                inside = None
+            elif inside:
+                body[inside].append(line)
+    # The product build holds exactly the kernels its dispatch can reach (launch_blockdft_gemm_fused / _gemm_unfused / _tree_finish in
+    # blockdft_gemm.hip, launch_blockdft_dots in blockdft_dots.hip): the form that only a developer knob selects — the 16-bin kernel
+    # product on 64-frame tiles (blockdft_banddots_db<MT = 2, NW = 8>) — compiles under -DPVQ_DEV_KNOBS alone.  (blockdft_gemm_tree3,
+    # which was such a form too, has been removed.)
     reachable = {
         "_ZN3pvq18blockdft_gemm_treeILi256ELi256EEEvNS_12GemmTreeArgsE", "_ZN3pvq18blockdft_gemm_treeILi256ELi0EEEvNS_12GemmTreeArgsE",
         "_ZN3pvq18blockdft_gemm_treeILi128ELi0EEEvNS_12GemmTreeArgsE", "_ZN3pvq25blockdft_gemm_tree_bf16x3ILi256EEEvNS_12GemmTreeArgsE",
@@ -71,6 +81,10 @@ def test_register_budgets_of_the_block_dft_kernels(tmp_path):
     }
     assert set(body) == reachable, (sorted(set(body) - reachable), sorted(reachable - set(body)))
     assert not any("tree3" in k or "blockdft_banddots_dbILi2ELi8E" in k for k in body)
+    # each stage's kernels in its own unit, none in the host unit
+    assert in_unit["blockdft_gemm.hip"] == {k for k in reachable if "banddots" not in k} and len(in_unit["blockdft_gemm.hip"]) == 10
+    assert in_unit["blockdft_dots.hip"] == {k for k in reachable if "banddots" in k} and len(in_unit["blockdft_dots.hip"]) == 9
+    assert in_unit["vqt_blockdft.hip"] == set()
     checked = 0
     for name, lines in body.items():
         if "blockdft_gemm_treeILi" not in name and "blockdft_gemm_tree_bf16x3" not in name:   # the shipped kernels (not the opt-in experiments)
