@@ -17,6 +17,20 @@ SHAPES = {
     "E": (588, 3, 256, 1, (880, 440, 7040)),    # wide window (1764 values per row)
     "F": (252, 1, 64, 1, (124, 62, 992)),       # no history rows
 }
+# the edges of the sizes note_model_check admits (3 .. 1024 bins, T 1 .. 8 with L >= 8, mlp 16 .. 4096, 0 .. 8 hidden layers); a table
+# of its own, so that every parametrisation over SHAPES keeps its cases
+EDGE_SHAPES = {
+    "G": (3, 3, 16, 0, (3, 1, 16)),             # the smallest of everything: L = 9, one pooled position, K = 16 in fc1, N = 16
+    "H": (183, 1, 32, 8, (90, 45, 720)),        # O_pool mod 4 = 1; eight hidden layers (dropout layer keys 0 .. 7)
+    "I": (191, 1, 112, 1, (94, 47, 752)),       # O_pool mod 4 = 3; mlp = 64 + 48: a column tile of three strips, 7 K chunks
+    "J": (1024, 8, 16, 1, (4094, 2047, 32752)),  # the widest window, L = 8192: 512 K stages, 3 chunks in the last
+    "K": (12, 1, 4096, 1, (4, 2, 32)),          # the widest mlp: 64 column tiles, 256 K chunks; O_pool = 2 < 4, L = 12 < 19
+}
+
+
+def shape(name):
+    """the tuple of a name of SHAPES or EDGE_SHAPES"""
+    return SHAPES[name] if name in SHAPES else EDGE_SHAPES[name]
 
 
 def sizes(n_bins, t_frames):
@@ -28,7 +42,7 @@ def sizes(n_bins, t_frames):
 @functools.lru_cache(maxsize=None)
 def weights(name, seed=1234):
     """state_dict-named f32 arrays, uniform +-1/sqrt(fan_in)"""
-    n_bins, T, mlp, layers, _ = SHAPES[name]
+    n_bins, T, mlp, layers, _ = shape(name)
     n_feat = sizes(n_bins, T)[3]
     rng = np.random.default_rng(seed + sum(map(ord, name)))
 

@@ -94,8 +94,8 @@ def adam(w, g, m, v, t, lr, beta1, beta2, eps, wd):
 
 @functools.lru_cache(maxsize=None)
 def dataset(name):
-    """400 dB-like rows and soft targets in [0, 1] for a shape of note_model_ref.SHAPES (read-only)"""
-    n_bins = R.SHAPES[name][0]
+    """400 dB-like rows and soft targets in [0, 1] for a shape of note_model_ref.SHAPES or EDGE_SHAPES (read-only)"""
+    n_bins = R.shape(name)[0]
     db = R.db_like((N_ROWS, n_bins), seed=700 + ord(name))
     tg = np.random.default_rng(800 + ord(name)).random((N_ROWS, 128)).astype(np.float32)
     db.setflags(write=False)
@@ -105,7 +105,7 @@ def dataset(name):
 
 def batch_idx(name, batch, seed=0):
     """a batch that holds index T - 1, index n_rows - 1 and one duplicate (batch 1: index T - 1 alone)"""
-    T = R.SHAPES[name][1]
+    T = R.shape(name)[1]
     if batch == 1:
         return np.array([T - 1], np.uint32)
     rng = np.random.default_rng(900 + seed + batch)

@@ -3,11 +3,13 @@ host-only handle, and the dropout mask against tests/note_trainer_ref.py, the re
 import ctypes as C
 import os
 import re
+import shutil
 
 import numpy as np
 import pytest
 
 import note_model_ref as R
+import note_plan_tool
 import note_trainer_ref as TR
 import pitchvis_amd as P
 from pitchvis_amd import _lib
@@ -18,8 +20,18 @@ SYMBOLS = ("pvq_note_trainer_hyper_default", "pvq_note_trainer_create", "pvq_not
            "pvq_note_trainer_steps", "pvq_note_trainer_param_count", "pvq_note_trainer_read", "pvq_note_trainer_dropout_keep")
 
 
+ALL_SHAPES = sorted(R.SHAPES) + sorted(R.EDGE_SHAPES)
+
+
+@pytest.fixture(scope="module")
+def plan_tool(tmp_path_factory):
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not installed")
+    return note_plan_tool.build(tmp_path_factory.mktemp("note_plan"))
+
+
 def _params(name="D"):
-    n_bins, T, mlp, layers, _ = R.SHAPES[name]
+    n_bins, T, mlp, layers, _ = R.shape(name)
     return P.NoteModelParams(n_bins, T, mlp, layers)
 
 
@@ -76,6 +88,58 @@ def test_create_takes_the_edges():
     n_bins, T, mlp, layers, (_, _, n_feat) = R.SHAPES["C"]
     t = _host("C")
     assert t.n_params == 96 + mlp * (n_feat + 1) + layers * mlp * (mlp + 1) + 128 * (mlp + 1)
+
+
+@pytest.mark.parametrize("name", ALL_SHAPES)
+def test_layout_and_arena_are_the_state_dict_in_its_order(name, plan_tool, tmp_path):
+    """note_trainer_layout: the tensors in state_dict order, back to back, every offset a multiple of 4 floats (nt_adam and the GEMMs
+    read 16 bytes at a time); note_trainer_arena: every tensor's elements at its offset.  Shape H has 22 tensors, K 16.9 M parameters."""
+    n_bins, T, mlp, layers, (_, _, n_feat) = R.shape(name)
+    path = str(tmp_path / "arena.f32")
+    lines = [line.split() for line in note_plan_tool.run(plan_tool, "layout", n_bins, T, mlp, layers, path).splitlines()]
+    want = [("conv1.weight", 80), ("conv1.bias", 16), ("fc1.weight", mlp * n_feat), ("fc1.bias", mlp)]
+    for i in range(layers):
+        want += [(f"layers.{i}.weight", mlp * mlp), (f"layers.{i}.bias", mlp)]
+    want += [("output.weight", 128 * mlp), ("output.bias", 128)]
+    assert [k for k, _ in want] == list(R.weights(name)) and [n for _, n in want] == [v.size for v in R.weights(name).values()]
+    arena = np.fromfile(path, np.float32)
+    os.remove(path)
+    at = 0
+    for j, ((k, n), line) in enumerate(zip(want, lines)):
+        assert (line[0], int(line[1]), int(line[2])) == (k, at, n) and at % 4 == 0, (k, line, at)
+        assert np.array_equal(arena[at:at + n], note_plan_tool.fill(1000003 * j + np.arange(n, dtype=np.int64))), k
+        at += n
+    assert lines[len(want)] == ["n_params", str(at)] and arena.size == at and len(lines) == len(want) + 1
+    assert _host(name).n_params == at
+    print(f"shape {name}: {len(want)} tensors, {at} parameters")
+
+
+def _splits(m, n, k):
+    """nt_splits restated from note_trainer_plan.hpp: enough workgroups for a fixed 512, at least 8 K stages of 32 per split, at most 8
+    splits, splits * m * n within 4 Mi floats"""
+    tiles, stages = -(-m // 64) * -(-n // 64), -(-k // 32)
+    s = min(512 // tiles, stages // 8, 8)
+    while s > 1 and s * m * n > 4 << 20:
+        s -= 1
+    return max(s, 1)
+
+
+@pytest.mark.parametrize("name", ALL_SHAPES)
+def test_splits_of_every_product_of_a_step(name, plan_tool):
+    """the nine kinds of product of NoteTrainer::step at batches 1, 37, 130, 300 and 4096"""
+    n_bins, T, mlp, layers, (_, _, F) = R.shape(name)
+    products = []
+    for b in (1, 37, 130, 300, 4096):
+        products += [(b, mlp, F), (b, mlp, mlp), (b, 128, mlp),            # forward: fc1, a hidden layer, the output layer
+                     (128, mlp, b), (b, mlp, 128), (mlp, mlp, b), (b, mlp, mlp), (mlp, F, b), (b, F, mlp)]     # backward
+    got = [int(x) for x in note_plan_tool.run(plan_tool, "splits", *[v for p in products for v in p]).split()]
+    assert got == [_splits(*p) for p in products]
+    for (m, n, k), s in zip(products, got):
+        assert 1 <= s <= 8 and (s == 1 or (s * m * n <= 4 << 20 and -(-k // 32) >= 8 * s))
+    print(f"shape {name}: splits at batch 37: {got[9:18]}")
+    pinned = {"G": [1] * 9, "J": [8, 1, 1, 1, 1, 1, 1, 1, 1], "K": [1, 8, 8, 1, 1, 1, 8, 1, 8], "H": [2, 1, 1, 1, 1, 1, 1, 1, 1]}
+    if name in pinned:      # worked out by hand from the rule: J's fc1 has 1024 stages in one tile, K's products over mlp 128 stages in at most 64 tiles
+        assert got[9:18] == pinned[name]
 
 
 def test_create_keeps_the_note_model_size_checks():
