@@ -19,6 +19,7 @@ import pytest
 
 import oracle as O
 import pitchvis_amd as P
+import render_cases as RC
 import render_model as M
 from helpers import get_geom, white_noise
 from pitchvis_amd import _lib
@@ -282,3 +283,104 @@ def test_host_matches_model_on_analysis_state_rows(geom, seed):
     rel = float(np.max(np.abs(g - w) / w))
     print(f"{geom} chroma: host vs model: max relative difference {rel:.2e}")
     assert rel <= CHROMA_REL and np.all(w.max(axis=1) == 1.0)
+
+
+# ---- crafted rows (tests/render_cases.py): the builder's own conditions, then host against model ---------------------------------
+CRAFTED = [(61.74, 2, 24), (55.0, 7, 36), (32.70, 16, 64)]   # 48, 252 and 1024 bins: one 64-chunk of bins, the benchmark's, sixteen
+
+
+def test_class_table_reaches_every_class_and_four_pitch_classes():
+    ns = [o * b for _, o, b in RC.CLASS_TABLE]
+    assert sorted({(n + 63) // 64 for n in ns}) == list(range(1, 17))
+    assert {3, 64, 65, 128, 961, 1024} <= set(ns)                                # both ends of NK = 1 (3: the admitted end), 2 and 16
+    bpos = [b for _, _, b in RC.CLASS_TABLE]
+    assert min(bpos) < 12 and max(bpos) > 100 and any(b > 12 and b % 12 for b in bpos)
+    classes = {M.bin_0_pitch_class(f) for f, _, _ in RC.CLASS_TABLE}
+    assert {0, 11} <= classes and len(classes) >= 4, classes
+    for f, o, b in RC.CLASS_TABLE:                                               # the host's class: a row whose only energy is bin 0
+        x = np.full(o * b, -1000.0, np.float32)
+        x[0] = 10.0
+        assert int(np.argmax(PC.chroma_row(f, o * b, b, x))) == M.bin_0_pitch_class(f), f
+        n = o * b
+        _, lists = RC.class_rows(n, n)
+        assert (len(lists[3]) > 64) == (n >= 100) and all(0.0 <= c < n for pk in lists for c, _ in pk)
+
+
+@pytest.mark.parametrize("min_freq,octaves,bpo", CRAFTED)
+def test_crafted_lists_depend_on_their_order(min_freq, octaves, bpo):
+    """Conditions on the INPUTS, from the model alone: reversing any crafted list repaints at least 5 % of the bytes either picture
+    lights (observed: spectrogram 64 - 95 %, LED 6 - 34 %), and the two orders of the chunk-straddling pair differ in the contested
+    bin.  A kernel that ignored list order could not pass on such lists."""
+    n = octaves * bpo
+    cases = RC.list_cases(n, n)
+    assert ("straddle_pq" in cases) == (n >= 97) and len(cases) >= 12
+    assert n < 140 or {len(pk) for pk in cases.values()} >= set(RC.LONG_COUNTS)
+    for name, pk in cases.items():
+        assert all(0.0 <= c < n for c, _ in pk) and len({s for _, s in pk}) == len(pk), name
+        gaps = np.diff(sorted(c for c, _ in pk))
+        assert gaps.min() >= 1.0 and (name.startswith("straddle") or 1.249 <= gaps.min() and gaps.max() <= 3.001), (name, gaps.min(), gaps.max())
+        spec, led = RC.order_dependence(n, bpo, pk)
+        print(f"{n} bins, {name} ({len(pk)} peaks): reversal repaints {spec:.3f} of the spectrogram bytes, {led:.3f} of the LED bytes")
+        assert spec >= RC.MIN_ORDER_SHARE and led >= RC.MIN_ORDER_SHARE, (name, spec, led)
+    if "straddle_pq" in cases:
+        a, b, B = RC.straddle_pair(n, n)
+        assert a == cases["straddle_pq"] and a[:63] == b[:63] and a[65:] == b[65:] and (a[63], a[64]) == (b[64], b[63])
+        (sa, la), (sb, lb) = RC.model_of_peaks(n, bpo, a), RC.model_of_peaks(n, bpo, b)
+        assert np.any(sa[B, :3] != sb[B, :3]) and np.any(la[3 + 3 * B:6 + 3 * B] != lb[3 + 3 * B:6 + 3 * B])
+        only_q = RC.model_of_peaks(n, bpo, a[:63] + [a[64]] + a[65:])[0]           # P then Q: Q's pixel stands; Q then P: not Q's
+        assert np.array_equal(sa[B], only_q[B]) and not np.array_equal(sb[B], only_q[B])
+
+
+def _host_rows(min_freq, n, bpo, xs, peak_lists):
+    led = lambda pk: np.frombuffer(PC.led_frame(n, bpo, pk, PC.COLORS, PC.GRAY_LEVEL, PC.EASING_POW), np.uint8)
+    return {"spectrogram_vqt": np.asarray([PC.spectrogram_row(PC.SPECTROGRAM_VQT, n, bpo, x) for x in xs]),
+            "chroma": np.asarray([PC.chroma_row(min_freq, n, bpo, x) for x in xs]),
+            "spectrogram_peaks": np.asarray([PC.spectrogram_row(PC.SPECTROGRAM_PEAKS, n, bpo, None, pk) for pk in peak_lists]),
+            "led": np.asarray([led(pk) for pk in peak_lists])}
+
+
+def hold_to_the_bars(tag, got, want, who="host"):
+    """the file's bars on the four outputs of a set of rows; chroma: NaN / inf where the model has them, the rest within CHROMA_REL"""
+    for k in ("spectrogram_vqt", "spectrogram_peaks", "led"):
+        assert got[k].shape == want[k].shape and got[k].dtype == np.uint8
+        levels, share = M.compare_u8(got[k], want[k])
+        print(f"{tag} {k}: {who} vs model: max {levels} level(s), {share:.2e} of the bytes differ")
+        assert levels <= U8_LEVELS and share <= U8_SHARE, (tag, k, levels, share)
+    same = int(sum(np.array_equal(g, w) for g, w in zip(got["led"], want["led"])))
+    print(f"{tag} led: {same}/{len(want['led'])} rows byte-identical")   # (a figure: crafted rows hold hundreds of peaks)
+    rel = RC.chroma_agrees(got["chroma"], want["chroma"], CHROMA_REL)
+    print(f"{tag} chroma: {who} vs model: max relative difference {rel:.2e}")
+
+
+@pytest.mark.parametrize("min_freq,octaves,bpo", CRAFTED)
+def test_host_matches_model_on_crafted_rows(min_freq, octaves, bpo):
+    """the sequential loops of the host face — the device's second reference — on long lists in every order and on the edge rows"""
+    n = octaves * bpo
+    cases = RC.list_cases(n, n)
+    xs = list(RC.db_rows(n, n).values())
+    lists = list(cases.values())
+    hold_to_the_bars(f"{n} bins, lists", _host_rows(min_freq, n, bpo, xs, lists), RC.model_rows(min_freq, n, bpo, xs, lists))
+    edge = RC.edge_rows(n, n)
+    xs, lists = [x for x, _ in edge.values()], [pk for _, pk in edge.values()]
+    got, want = _host_rows(min_freq, n, bpo, xs, lists), RC.model_rows(min_freq, n, bpo, xs, lists)
+    hold_to_the_bars(f"{n} bins, edges", got, want)
+    check_edge_rows(n, edge, got)
+
+
+def check_edge_rows(n, edge, got):
+    """known answers of the edge rows (RC.edge_rows): a NaN brightness is a 0 byte; sizes all zero paint nothing"""
+    names = list(edge)
+    at = (2 * n) // 3
+    for name in ("db_nan", "db_plus_inf"):                                        # NaN; inf / (inf + 0.001) -> NaN
+        assert got["spectrogram_vqt"][names.index(name), at, 3] == 0 and got["spectrogram_vqt"][names.index(name), at, :3].any()
+        assert np.isnan(got["chroma"][names.index(name)]).any()
+    assert not got["spectrogram_vqt"][names.index("db_negative"), :, 3].any()     # max_val stays 0
+    assert np.isfinite(got["chroma"][names.index("db_negative")]).all() and got["chroma"][names.index("db_negative")].max() == 1.0
+    assert np.isnan(got["chroma"][names.index("db_overflow")]).sum() == 1         # inf / inf in one class, 0 in the others
+    for name in ("edges_all_zero", "short_all_zero"):
+        r = names.index(name)
+        assert not got["spectrogram_peaks"][r].any() and not got["led"][r, 3:].any()   # max_size > 0 fails; 0 / 0 -> NaN -> 0
+    for name in ("edges_equal", "short_one_zero", "edges_reversed"):
+        r = names.index(name)
+        assert got["spectrogram_peaks"][r].any() and got["led"][r, 3:].any()
+    assert np.all(got["led"][:, 0] == 0xFF) and np.all(got["led"][:, 1].astype(int) * 256 + got["led"][:, 2] == n)

@@ -12,10 +12,11 @@ import numpy as np
 import pytest
 
 import pitchvis_amd as P
+import render_cases as RC
 import render_model as M
 from helpers import get_geom
 from pitchvis_amd import consumers as PC
-from test_render import CHROMA_REL, U8_LEVELS, U8_SHARE
+from test_render import CHROMA_REL, U8_LEVELS, U8_SHARE, check_edge_rows, hold_to_the_bars
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -226,3 +227,193 @@ def test_every_subset_of_outputs_and_row_counts(chain):
         again = r.rows_device(f)
     s.synchronize()
     assert all(torch.equal(again[name], out[name]) for name in names)
+
+
+# ---- crafted rows (tests/render_cases.py): long lists in any order, every class, the row stride, value edges, placement ------------
+# The bars are the file's (test_render.hold_to_the_bars).  The share of byte-identical LED rows is printed, not asserted: its 97 % was
+# set on rows of about a dozen peaks; a crafted row holds hundreds.
+def _range(min_freq, octaves, bpo):
+    return P.VqtRange(min_freq, octaves, bpo)
+
+
+def _inputs(xs, peak_lists, max_peaks):
+    center, size, count = RC.pack(peak_lists, max_peaks)
+    return _upload(np.asarray(xs, np.float32), center, size, count)
+
+
+def _render(r, xs, peak_lists, max_peaks):
+    d_x, d_c, d_s, d_n = _inputs(xs, peak_lists, max_peaks)
+    out = r.rows_device(x_vqt_smoothed=d_x, center=d_c, size=d_s, peak_count=d_n)
+    torch.cuda.synchronize()
+    return {k: t.cpu().numpy() for k, t in out.items()}
+
+
+@pytest.mark.parametrize("min_freq,octaves,bpo", RC.CLASS_TABLE)
+def test_every_bin_count_class(min_freq, octaves, bpo):
+    """render_rows<1> .. <16>, 3 and 1024 bins included (tests/test_render.py holds the table to its coverage): an ordinary row, a
+    peakless all-zero row, the centre edges, and a shuffled list of as many peaks as fit"""
+    n = octaves * bpo
+    xs, lists = RC.class_rows(n, n)
+    got = _render(P.RenderBatch(_range(min_freq, octaves, bpo)), xs, lists, max(len(pk) for pk in lists))
+    hold_to_the_bars(f"class {(n + 63) // 64}, {n} bins", got, RC.model_rows(min_freq, n, bpo, xs, lists), "device")
+    assert not got["spectrogram_peaks"][1].any() and not got["led"][1, 3:].any() and not got["spectrogram_vqt"][1, :, 3].any()
+    assert got["spectrogram_peaks"][[0, 2, 3]].any(axis=(1, 2)).all() and got["led"][[0, 2, 3], 3:].any(axis=1).all()
+    assert np.all(got["led"][:, 0] == 0xFF) and np.all(got["led"][:, 1].astype(int) * 256 + got["led"][:, 2] == n)
+
+
+def _list_call(n, max_peaks):
+    """(dB rows, peak lists): every crafted list of at most max_peaks peaks in every order, among rows of 0, 1, 64, 65 and max_peaks
+    peaks; three dB rows in turn"""
+    cases = RC.list_cases(n, n)
+    lists = [pk for pk in cases.values() if len(pk) <= max_peaks]
+    mix = [[], [(n / 2 + 0.25, 5.0)]] + [RC.spaced_list(n, c, n + 7 * c) for c in (64, 65, max_peaks) if c <= max_peaks]
+    mix = [pk if i % 2 else pk[::-1] for i, pk in enumerate(mix)]
+    assert all(pk is not None for pk in mix) and sorted({len(pk) for pk in mix}) == sorted({0, 1, max_peaks} | ({64, 65} if max_peaks > 64 else {64}))
+    lists = [pk for pair in itertools.zip_longest(lists, mix) for pk in pair if pk is not None]   # short after long, peakless after crowded
+    db = RC.db_rows(n, n)
+    xs = [(db["ordinary"], np.zeros(n, np.float32), db["negative"])[i % 3] for i in range(len(lists))]
+    return xs, lists, cases
+
+
+LIST_GEOMETRIES = [(55.0, 7, 36), (32.70, 16, 64)]   # 252 and 1024 bins
+FULLEST = {252: len(RC.spaced_list(252, None, 252 + 999)), 1024: len(RC.spaced_list(1024, None, 1024 + 999))}
+
+
+@pytest.mark.parametrize("max_peaks", [64, 65, 129, 200, "fullest"])
+@pytest.mark.parametrize("min_freq,octaves,bpo", LIST_GEOMETRIES)
+def test_long_lists_in_every_order(min_freq, octaves, bpo, max_peaks):
+    """Rows of 64, 65, 127, 128, 129 peaks and of as many as fit, ascending, descending and shuffled, and the pair of lists whose
+    deciding two peaks sit either side of the chunk edge: the chunk loop, its barriers, the `p < cnt` tail of a later chunk, a later
+    chunk repainting an earlier one's bins.  (tests/test_render.py: reversing any of these lists repaints 64 - 95 % of the spectrogram
+    bytes and 6 - 34 % of the LED bytes, so no rule but "the last in list order" passes.)  The width of the arrays does not matter:
+    what a row gives at max_peaks 64 it gives at 487, entries beyond its count being NaN."""
+    n = octaves * bpo
+    if max_peaks == "fullest":
+        max_peaks = max(FULLEST[n], 130)
+    xs, lists, cases = _list_call(n, max_peaks)
+    if max_peaks >= 129:
+        assert all(pk in lists for pk in cases.values()) or max_peaks < FULLEST[n]
+    assert any(len(pk) == max_peaks for pk in lists) and [] in lists
+    got = _render(P.RenderBatch(_range(min_freq, octaves, bpo)), xs, lists, max_peaks)
+    hold_to_the_bars(f"{n} bins, max_peaks {max_peaks}, {len(lists)} rows", got, RC.model_rows(min_freq, n, bpo, xs, lists), "device")
+    for r, pk in enumerate(lists):                                                # a row at a time: no row hides in the aggregate
+        want = RC.model_of_peaks(n, bpo, pk)
+        for g, w, k in ((got["spectrogram_peaks"][r], want[0], "spectrogram_peaks"), (got["led"][r], want[1], "led")):
+            levels, share = M.compare_u8(g, w)
+            assert levels <= U8_LEVELS and share <= U8_SHARE, (r, len(pk), k, levels, share)
+
+
+def test_straddle_pair_on_the_device():
+    """entries 63 and 64 swapped: the contested bin takes the later one's pixel both ways round, the rest of the row is the same"""
+    n, bpo = 252, 36
+    a, b, B = RC.straddle_pair(n, n)
+    got = _render(P.RenderBatch(_range(55.0, 7, bpo)), [np.zeros(n, np.float32)] * 2, [a, b], 67)
+    for k, sl in (("spectrogram_peaks", slice(B, B + 1)), ("led", slice(3 + 3 * B, 6 + 3 * B))):
+        wa, wb = (RC.model_of_peaks(n, bpo, pk)[k == "led"] for pk in (a, b))
+        assert np.any(wa[sl] != wb[sl])
+        assert np.abs(got[k][0][sl].astype(int) - wa[sl]).max() <= U8_LEVELS and np.abs(got[k][1][sl].astype(int) - wb[sl]).max() <= U8_LEVELS
+        assert np.abs(got[k][0][sl].astype(int) - got[k][1][sl]).max() > 2 * U8_LEVELS       # (so the two could not both match one answer)
+    far = got["spectrogram_peaks"][:, :B - 3]
+    assert np.array_equal(far[0], far[1]) and far.any()
+
+
+def test_peak_count_above_max_peaks_is_max_peaks():
+    """include/pvq.h: "a count above max_peaks is taken as max_peaks" — max_peaks + 1 and 0xFFFFFFFF on rows whose lists are full"""
+    n, max_peaks = 252, 65
+    xs, lists, _ = _list_call(n, max_peaks)
+    d_x, d_c, d_s, d_n = _inputs(xs, lists, max_peaks)
+    r = P.RenderBatch(_range(55.0, 7, 36))
+    base = r.rows_device(x_vqt_smoothed=d_x, center=d_c, size=d_s, peak_count=d_n)
+    count = d_n.cpu().numpy().astype(np.int64)
+    full = np.nonzero(count == max_peaks)[0]
+    assert len(full) >= 4
+    count[full[0::2]] = max_peaks + 1
+    count[full[1::2]] = 0xFFFFFFFF
+    raised = torch.from_numpy(count.astype(np.uint32).view(np.int32)).cuda()
+    out = r.rows_device(x_vqt_smoothed=d_x, center=d_c, size=d_s, peak_count=raised)
+    torch.cuda.synchronize()
+    for k in P.RenderBatch.OUTPUTS:
+        assert torch.equal(out[k].view(torch.uint8), base[k].view(torch.uint8)), k
+    assert base["spectrogram_peaks"].cpu().numpy()[full].any(axis=(1, 2)).all()
+
+
+def test_row_stride_with_a_different_row_each_time():
+    """8192 workgroups stride over 2 x 8192 + 61 rows of 61 distinct ones: as 8192 = 134 x 61 + 18, a workgroup's next row is
+    another row (peakless after crowded, a short list after a long one, a NaN row after an ordinary one), so whatever a row leaves
+    in LDS or registers meets a row it does not fit.  Every row must be, bit for bit, what the 61-row call gives, which the model pins."""
+    n, bpo, m, max_peaks = 252, 36, 61, 129
+    cases, db = RC.list_cases(n, n), RC.db_rows(n, n)
+    crowded = [pk for name, pk in cases.items() if len(pk) >= 64]
+    short = [pk for name, pk in cases.items() if len(pk) <= 12] + [RC.centre_edges(n, n)]
+    xs, lists = [], []
+    for i in range(m):
+        kind = i % 4
+        xs.append((np.zeros(n, np.float32), db["ordinary"], db["nan"], db["negative"])[kind] if i % 8 < 4 else
+                  (db["ordinary"], db["plus_inf"], db["ordinary"], db["overflow"])[kind])
+        lists.append(([], crowded[(i // 4) % len(crowded)], short[(i // 4) % len(short)], crowded[(i // 4 + 7) % len(crowded)][:64 + i])[kind])
+    assert sum(not pk for pk in lists) >= 15 and max(len(pk) for pk in lists) == max_peaks
+    total = 2 * 8192 + m
+    idx = _upload(np.arange(total, dtype=np.int64) % m)[0]
+    assert 8192 % m == 18 and all(lists[i] != lists[(i + 8192) % m] or xs[i] is not xs[(i + 8192) % m] for i in range(m))
+    d_x, d_c, d_s, d_n = _inputs(xs, lists, max_peaks)
+    r = P.RenderBatch(_range(55.0, 7, bpo))
+    small = r.rows_device(x_vqt_smoothed=d_x, center=d_c, size=d_s, peak_count=d_n)
+    big = r.rows_device(x_vqt_smoothed=d_x[idx].contiguous(), center=d_c[idx].contiguous(), size=d_s[idx].contiguous(), peak_count=d_n[idx].contiguous())
+    torch.cuda.synchronize()
+    for k in P.RenderBatch.OUTPUTS:
+        want = small[k].view(torch.uint8 if k != "chroma" else torch.int32)[idx]                # chroma by its bits: NaN rows
+        assert torch.equal(big[k].view(want.dtype), want), k
+    hold_to_the_bars(f"{m} distinct rows", {k: t.cpu().numpy() for k, t in small.items()}, RC.model_rows(55.0, n, bpo, xs, lists), "device")
+
+
+def test_value_edges_on_the_device():
+    """all-negative, NaN, +inf, -inf and overflowing dB rows; integer centres, centres in the last bucket and at n - 1; equal sizes,
+    all-zero sizes, one zero size"""
+    n, bpo = 252, 36
+    edge = RC.edge_rows(n, n)
+    xs, lists = [x for x, _ in edge.values()], [pk for _, pk in edge.values()]
+    got = _render(P.RenderBatch(_range(55.0, 7, bpo)), xs, lists, 12)
+    hold_to_the_bars(f"{n} bins, value edges", got, RC.model_rows(55.0, n, bpo, xs, lists), "device")
+    check_edge_rows(n, edge, got)
+
+
+SENTINEL, GUARD = 0xA5, 64
+
+
+def _carved(shape, dtype, offset):
+    """a contiguous tensor of `shape` starting `GUARD + offset` bytes into a sentinel-filled byte buffer; (view, buffer, first, last)"""
+    nbytes = int(np.prod(shape)) * (1 if dtype == torch.uint8 else 4)
+    buf = torch.full((GUARD + offset + nbytes + GUARD + 4,), SENTINEL, dtype=torch.uint8).cuda()
+    assert buf.data_ptr() % 4 == 0
+    first = GUARD + offset
+    view = buf[first:first + nbytes]
+    view = (view if dtype == torch.uint8 else view.view(torch.float32)).view(shape)
+    assert view.data_ptr() == buf.data_ptr() + first and view.is_contiguous()
+    return view, buf, first, first + nbytes
+
+
+@pytest.mark.parametrize("min_freq,octaves,bpo", [(32.70, 1, 3), (49.0, 7, 25), (32.70, 16, 64)])   # 3, 175 and 1024 bins
+def test_outputs_land_where_they_are_told_and_nowhere_else(min_freq, octaves, bpo):
+    """the LED output at byte offsets 0 .. 3 of a dword (its rows, 3 + 3 n bytes long, then start at every offset the head and tail
+    logic knows), the RGBA outputs and chroma at their natural alignment: the same bytes as a plain call, and the 64 bytes either
+    side untouched"""
+    n = octaves * bpo
+    xs, lists = RC.class_rows(n, n)
+    xs, lists = xs + xs[:3], lists + [lists[3], lists[0], lists[2][::-1]]          # 7 rows
+    max_peaks = max(len(pk) for pk in lists)
+    d_x, d_c, d_s, d_n = _inputs(xs, lists, max_peaks)
+    r = P.RenderBatch(_range(min_freq, octaves, bpo))
+    plain = r.rows_device(x_vqt_smoothed=d_x, center=d_c, size=d_s, peak_count=d_n)
+    torch.cuda.synchronize()
+    assert plain["led"][:, 3:].any() and plain["spectrogram_peaks"].any()
+    for offset in range(4):
+        carved = {}
+        for name in P.RenderBatch.OUTPUTS:
+            shape, dt = r.output_shape(name, len(lists))
+            carved[name] = _carved(shape, torch.uint8 if dt == np.uint8 else torch.float32, offset if name == "led" else 0)
+        assert carved["led"][0].data_ptr() % 4 == offset
+        r.rows_device(x_vqt_smoothed=d_x, center=d_c, size=d_s, peak_count=d_n, outputs={k: v[0] for k, v in carved.items()})
+        torch.cuda.synchronize()
+        for name, (view, buf, first, last) in carved.items():
+            assert torch.equal(view.view(torch.uint8), plain[name].view(torch.uint8)), (name, offset)
+            assert bool((buf[:first] == SENTINEL).all()) and bool((buf[last:] == SENTINEL).all()), (name, offset)
