@@ -674,6 +674,49 @@ pvq_status pvq_note_trainer_read(pvq_note_trainer *t, int what, float *out_host,
 pvq_status pvq_note_trainer_dropout_keep(uint64_t seed, uint64_t step, uint32_t layer, uint32_t row, uint32_t col0, uint32_t n, double dropout,
                                          uint8_t *out_keep);
 
+/* The test pass of the trainer (pitchvis_train/train.py:164-198): model.eval(), the test set in batches, per batch
+ * f1_score(labels > 0.5, outputs > 0.5, average='micro'), then the mean of those scores and the element-wise accuracy.
+ *
+ * Rows.  idx is a HOST array of n_idx sample indices (t_frames - 1 <= i < n_rows, as for a step; duplicates are legal and count once
+ *   each), 1 <= n_idx <= 2^25.  Batch k is idx[k * batch .. min((k + 1) * batch, n_idx)): the last batch may be short and still
+ *   counts as one batch in the mean, because the DataLoader keeps it (train.py:65).  The caller's permutation is the shuffle.
+ *   batch >= 1 and is NOT bounded by max_batch: it shapes only the metric.  Dropout is off (model.eval()), so a row's forward
+ *   depends on no other row: the forward runs in chunks of at most max_batch consecutive entries of idx, whatever `batch` is.
+ * Decisions.  The prediction is z > 0 on the f32 logit z: sigmoid(z) > 0.5 (train.py:177) in exact arithmetic, and the rule of
+ *   pvq_note_model_outputs.d_mask.  The two differ only for 0 < z <~ 6e-8, where the f32 sigmoid rounds to 0.5.  The label is
+ *   y > 0.5 (train.py:178).  tp, fp, fn count the elements of a batch that are (predicted and labelled), (predicted, not
+ *   labelled), (labelled, not predicted); `correct` those where prediction and label agree (train.py:190).
+ * Loss.  Per element the stable form of the step (above), terms in f32; a row's 128 terms are added as a tree in double, a batch's
+ *   rows in double in an order that depends only on its number of rows; `loss` is that sum / (rows * 128), the batch's mean BCE.
+ * Scalars (pvq_note_test_metrics).  The F1 of a batch is 2 tp / (2 tp + fp + fn), and 0 when that denominator is 0 (sklearn's
+ *   zero-division value); mean_f1 is the plain mean over the batches (train.py:193); accuracy is sum(correct) / (128 * sum(rows))
+ *   (train.py:198); mean_loss is the plain mean of the batch losses, as running_loss / len(loader) is for training (train.py:162).
+ * Determinism.  Equal handles and equal inputs give equal bits.  The logits may differ in their last bits between handles of
+ *   different max_batch, and from pvq_note_trainer_step(PVQ_TRAIN_EVAL) on the same rows: the split of a product along K follows
+ *   its number of rows, and a chunk has other rows than a batch. */
+typedef struct pvq_note_test_batch {   /* one record per test batch, 32 bytes */
+    uint32_t rows, tp, fp, fn, correct, _pad;
+    double   loss;                      /* mean BCE of the batch: sum / (rows * 128) */
+} pvq_note_test_batch;
+/* One test pass over idx[0 .. n_idx) of the dataset (d_db, d_targets, n_rows: DEVICE, as for a step, never written).  out_batches
+ * (HOST, ceil(n_idx / batch) records) receives one record per batch; out_pitch (HOST, [128][3] tp, fp, fn per output over the whole
+ * pass, may be NULL) the counts behind a per-note F1; d_logits (DEVICE, [n_idx][128], may be NULL) the logits, row r those of
+ * idx[r].  Bad arguments (a null d_db, d_targets, idx or out_batches, batch 0, n_idx outside 1 .. 2^25, an index outside
+ * [t_frames - 1, n_rows)) give PVQ_ERR_INVALID_ARG with a message and launch nothing; a host-only handle returns PVQ_ERR_NO_DEVICE
+ * after these checks, as pvq_note_trainer_step does.  The call runs on `stream`, is synchronous with respect to its host outputs and
+ * waits on the stream once, at the end.  It neither advances pvq_note_trainer_steps nor touches the weights, the gradients or
+ * Adam's moments.  Per-row records and masks (56 bytes per row of idx) live in a grow-only buffer of the handle, allocated by the
+ * first pass that needs it. */
+pvq_status pvq_note_trainer_test(pvq_note_trainer *t, const float *d_db, const float *d_targets, size_t n_rows,
+                                 const uint32_t *idx, size_t n_idx, uint32_t batch,
+                                 pvq_note_test_batch *out_batches /* host, ceil(n_idx / batch) */,
+                                 uint32_t *out_pitch /* host [128][3] tp, fp, fn over the whole pass, or NULL */,
+                                 float *d_logits /* device [n_idx][128] or NULL */, void *stream);
+/* pure host: what train.py:193-198 prints, from the records (formulas above).  Each output may be NULL.  PVQ_ERR_INVALID_ARG for
+ * null records, n_batches 0 or records without rows. */
+pvq_status pvq_note_test_metrics(const pvq_note_test_batch *b, size_t n_batches,
+                                 double *mean_f1, double *accuracy, double *mean_loss);
+
 /* Page-locked host memory for the host-buffer entry points (pvq_vqt_calculate_batch_db, pvq_analyze_batch,
  * pvq_train_frames_db): with pageable buffers those calls are bound by staged PCIe copies (~16 GB/s); buffers from
  * here are DMA-able directly.  NULL on failure (pvq_last_error). */

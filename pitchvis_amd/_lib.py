@@ -39,7 +39,7 @@ EXPORTS = [
     "pvq_note_model_create", "pvq_note_model_destroy", "pvq_note_model_sizes", "pvq_note_model_infer", "pvq_note_model_rows_device",
     "pvq_note_model_set_workspace_limit",
     "pvq_note_trainer_hyper_default", "pvq_note_trainer_create", "pvq_note_trainer_destroy", "pvq_note_trainer_step", "pvq_note_trainer_steps",
-    "pvq_note_trainer_param_count", "pvq_note_trainer_read", "pvq_note_trainer_dropout_keep",
+    "pvq_note_trainer_param_count", "pvq_note_trainer_read", "pvq_note_trainer_dropout_keep", "pvq_note_trainer_test", "pvq_note_test_metrics",
     "pvq_vqt_input_status", "pvq_vqt_last_gemm_flop", "pvq_vqt_last_sclk_mhz",
     "pvq_vqt_bandwidths_3db", "pvq_vqt_warning_count", "pvq_vqt_warning",
 ]
@@ -113,6 +113,10 @@ class CNoteModelOutputs(C.Structure):   # pvq_note_model_outputs (device pointer
 
 class CNoteTrainerHyper(C.Structure):   # pvq_note_trainer_hyper
     _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "dropout")] + [("seed", C.c_uint64)]
+
+
+class CNoteTestBatch(C.Structure):   # pvq_note_test_batch
+    _fields_ = [(n, C.c_uint32) for n in ("rows", "tp", "fp", "fn", "correct", "_pad")] + [("loss", C.c_double)]
 
 
 class CShard(C.Structure):   # pvq_shard
@@ -292,6 +296,10 @@ def load():
     L.pvq_note_trainer_read.argtypes = [vp, C.c_int, fp, C.c_size_t]; L.pvq_note_trainer_read.restype = C.c_int
     L.pvq_note_trainer_dropout_keep.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, bp]
     L.pvq_note_trainer_dropout_keep.restype = C.c_int
+    L.pvq_note_trainer_test.argtypes = [vp, vp, vp, C.c_size_t, up, C.c_size_t, C.c_uint32, C.POINTER(CNoteTestBatch), up, vp, vp]
+    L.pvq_note_trainer_test.restype = C.c_int
+    dp = C.POINTER(C.c_double)
+    L.pvq_note_test_metrics.argtypes = [C.POINTER(CNoteTestBatch), C.c_size_t, dp, dp, dp]; L.pvq_note_test_metrics.restype = C.c_int
     L.pvq_host_alloc.argtypes = [C.c_size_t]; L.pvq_host_alloc.restype = C.c_void_p
     L.pvq_host_free.argtypes = [C.c_void_p]
     L.pvq_vqt_input_status.argtypes = [vp, vp]; L.pvq_vqt_input_status.restype = C.c_int

@@ -1194,6 +1194,22 @@ pvq_status pvq_note_trainer_read(pvq_note_trainer* t, int what, float* out_host,
         return t->impl->read(what, out_host, capacity);
     } catch (...) { return translate_exception(); }
 }
+// train.py:164-198, the test pass
+pvq_status pvq_note_trainer_test(pvq_note_trainer* t, const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx, size_t n_idx,
+                                 uint32_t batch, pvq_note_test_batch* out_batches, uint32_t* out_pitch, float* d_logits, void* stream) {
+    try {
+        if (!t) return null_handle();
+        return t->impl->test(d_db, d_targets, n_rows, idx, n_idx, batch, out_batches, out_pitch, d_logits, static_cast<hipStream_t>(stream));
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_note_test_metrics(const pvq_note_test_batch* b, size_t n_batches, double* mean_f1, double* accuracy, double* mean_loss) {
+    try {
+        std::string err;
+        const pvq_status st = pvq::note_test_metrics(b, n_batches, mean_f1, accuracy, mean_loss, err);
+        if (st != PVQ_OK) pvq::set_last_error(err);
+        return st;
+    } catch (...) { return translate_exception(); }
+}
 pvq_status pvq_note_trainer_dropout_keep(uint64_t seed, uint64_t step, uint32_t layer, uint32_t row, uint32_t col0, uint32_t n, double dropout,
                                          uint8_t* out_keep) {
     try {

@@ -315,6 +315,99 @@ __global__ __launch_bounds__(NT_THREADS) void nt_loss_final(const double* __rest
     if (threadIdx.x == 0) *loss = static_cast<float>(s_red[0] * inv_n);
 }
 
+// The test pass (train.py:164-198).  One workgroup per row of a chunk, one thread per output, shaped like nt_loss without its dz.  Row b of
+// the chunk is entry pos0 + b of the pass; everything it leaves is indexed by that position, so a test batch that straddles two chunks
+// needs no special case.  Prediction z > 0, label y > 0.5 (train.py:177-178): a wave's ballot is 64 bits of the row's 128-bit mask (bit k =
+// word k / 32, bit k % 32, as pvq_note_model_outputs.d_mask); masks[pos][0 .. 3] prediction, [4 .. 7] label.  counts[pos] = tp, fp, fn,
+// correct by popcount; row_loss[pos] the row's 128 losses added as nt_loss's tree in double.
+__global__ __launch_bounds__(NM_OUT) void nt_test_rows(const float* __restrict__ z, const float* __restrict__ targets, const uint32_t* __restrict__ idx,
+                                                       size_t pos0, uint32_t* __restrict__ masks, uint4* __restrict__ counts, double* __restrict__ row_loss,
+                                                       float* __restrict__ logits_out) {
+    __shared__ double s_red[NM_OUT];
+    __shared__ uint32_t s_cnt[NM_OUT / 64][4];
+    const uint32_t b = blockIdx.x, j = threadIdx.x, wave = j >> 6;
+    const size_t pos = pos0 + b;
+    const float zv = z[static_cast<size_t>(b) * NM_OUT + j];
+    const float y = targets[static_cast<size_t>(idx[b]) * NM_OUT + j];
+    const float l = fmaxf(zv, 0.0f) - zv * y + log1pf(expf(-fabsf(zv)));
+    if (logits_out) logits_out[pos * NM_OUT + j] = zv;
+    const unsigned long long p = __ballot(zv > 0.0f), q = __ballot(y > 0.5f);
+    if ((j & 63) == 0) {
+        uint32_t* m = masks + pos * 8;
+        m[2 * wave] = static_cast<uint32_t>(p);
+        m[2 * wave + 1] = static_cast<uint32_t>(p >> 32);
+        m[4 + 2 * wave] = static_cast<uint32_t>(q);
+        m[4 + 2 * wave + 1] = static_cast<uint32_t>(q >> 32);
+        s_cnt[wave][0] = __popcll(p & q);
+        s_cnt[wave][1] = __popcll(p & ~q);
+        s_cnt[wave][2] = __popcll(~p & q);
+        s_cnt[wave][3] = 64 - __popcll(p ^ q);
+    }
+    s_red[j] = static_cast<double>(l);
+    __syncthreads();
+    for (int s = NM_OUT / 2; s > 0; s >>= 1) {
+        if (j < static_cast<uint32_t>(s)) s_red[j] += s_red[j + s];
+        __syncthreads();
+    }
+    if (j == 0) {
+        counts[pos] = make_uint4(s_cnt[0][0] + s_cnt[1][0], s_cnt[0][1] + s_cnt[1][1], s_cnt[0][2] + s_cnt[1][2], s_cnt[0][3] + s_cnt[1][3]);
+        row_loss[pos] = s_red[0];
+    }
+}
+// One wave per test batch k = rows k * batch .. of the pass (the last may be short).  Lane l adds rows l, l + 64, .. of the batch in that
+// order, then the 64 lanes are added as a tree: the order of the loss sum in double depends on the batch's row count alone.
+__global__ __launch_bounds__(NT_THREADS) void nt_test_batches(const uint4* __restrict__ counts, const double* __restrict__ row_loss, size_t n_idx,
+                                                              uint32_t batch, size_t n_batches, pvq_note_test_batch* __restrict__ out) {
+    const size_t k = static_cast<size_t>(blockIdx.x) * (NT_THREADS / 64) + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63;
+    if (k >= n_batches) return;   // (a whole wave)
+    const size_t r0 = k * batch;
+    const uint32_t rows = static_cast<uint32_t>(min(static_cast<size_t>(batch), n_idx - r0));
+    uint32_t tp = 0, fp = 0, fn = 0, ok = 0;
+    double s = 0.0;
+    for (uint32_t r = lane; r < rows; r += 64) {
+        const uint4 c = counts[r0 + r];
+        tp += c.x;
+        fp += c.y;
+        fn += c.z;
+        ok += c.w;
+        s += row_loss[r0 + r];
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        tp += __shfl_down(tp, off);
+        fp += __shfl_down(fp, off);
+        fn += __shfl_down(fn, off);
+        ok += __shfl_down(ok, off);
+        s += __shfl_down(s, off);
+    }
+    if (lane == 0) {
+        pvq_note_test_batch o;
+        o.rows = rows;
+        o.tp = tp;
+        o.fp = fp;
+        o.fn = fn;
+        o.correct = ok;
+        o._pad = 0;
+        o.loss = s / (static_cast<double>(rows) * NM_OUT);
+        out[k] = o;
+    }
+}
+// out[pitch][tp, fp, fn] over all rows of the pass, from the masks: thread = pitch, a workgroup walks rows blockIdx.x, + gridDim.x, ..
+// and adds its counts to `out` (zeroed before the launch) atomically: integer sums, the same in any order.
+__global__ __launch_bounds__(NM_OUT) void nt_test_pitches(const uint32_t* __restrict__ masks, size_t n_idx, uint32_t* __restrict__ out) {
+    const uint32_t w = threadIdx.x >> 5, bit = threadIdx.x & 31;
+    uint32_t tp = 0, fp = 0, fn = 0;
+    for (size_t r = blockIdx.x; r < n_idx; r += gridDim.x) {
+        const uint32_t p = (masks[r * 8 + w] >> bit) & 1u, q = (masks[r * 8 + 4 + w] >> bit) & 1u;
+        tp += p & q;
+        fp += p & (q ^ 1u);
+        fn += (p ^ 1u) & q;
+    }
+    atomicAdd(out + 3 * threadIdx.x, tp);
+    atomicAdd(out + 3 * threadIdx.x + 1, fp);
+    atomicAdd(out + 3 * threadIdx.x + 2, fn);
+}
+
 // torch.optim.Adam with L2 weight decay (train.py:141-144), four elements per thread.  The element's arithmetic is done in double
 // and rounded once per stored value: the kernel moves 28 bytes per element and has the time.
 __global__ __launch_bounds__(NT_THREADS) void nt_adam(f32x4* __restrict__ w, const f32x4* __restrict__ g, f32x4* __restrict__ m, f32x4* __restrict__ v,
@@ -380,6 +473,9 @@ NoteTrainer::~NoteTrainer() {
     }
     if (d_arena_) (void)hipFree(d_arena_);
     if (d_ws_) (void)hipFree(d_ws_);
+    if (d_test_rows_) (void)hipFree(d_test_rows_);
+    if (d_test_out_) (void)hipFree(d_test_out_);
+    if (h_test_out_) (void)hipHostFree(h_test_out_);
 }
 
 pvq_status NoteTrainer::create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
@@ -433,49 +529,34 @@ pvq_status NoteTrainer::create(int device_id, const pvq_note_model_params* param
     return PVQ_OK;
 }
 
-pvq_status NoteTrainer::step(int mode, const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx, uint32_t batch, float* d_loss,
-                             float* d_logits, hipStream_t stream) {
-    const NoteModelDims& d = lay_.d;
-    std::string err;
-    const pvq_status st = note_trainer_check_step(d, max_batch_, mode, d_db, d_targets, n_rows, idx, batch, err);
-    if (st != PVQ_OK) {
-        set_last_error(err);
-        return st;
-    }
-    if (device_id_ < 0) {
-        set_last_error("the note trainer runs on a GPU; this handle has none");
-        return PVQ_ERR_NO_DEVICE;
-    }
-    PVQ_HIP(hipSetDevice(device_id_));
-    // idx -> pinned slot -> device.  The slot is free once the copy queued from it two calls ago has run.
+// idx -> pinned slot -> device.  The slot is free once the copy queued from it two calls ago has run.
+pvq_status NoteTrainer::upload_idx(const uint32_t* idx, uint32_t rows, hipStream_t stream) {
     const int slot = static_cast<int>(calls_++ & 1);
     if (idx_pending_[slot]) PVQ_HIP(hipEventSynchronize(idx_copied_[slot]));
-    std::memcpy(h_idx_[slot], idx, batch * sizeof(uint32_t));
+    std::memcpy(h_idx_[slot], idx, rows * sizeof(uint32_t));
     uint32_t* d_idx = reinterpret_cast<uint32_t*>(d_ws_ + ws_idx_);
-    PVQ_HIP(hipMemcpyAsync(d_idx, h_idx_[slot], batch * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    PVQ_HIP(hipMemcpyAsync(d_idx, h_idx_[slot], rows * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     PVQ_HIP(hipEventRecord(idx_copied_[slot], stream));
     idx_pending_[slot] = true;
+    return PVQ_OK;
+}
 
-    const size_t n = lay_.n_params;
+// forward (train.py:87-99)
+void NoteTrainer::forward(const float* d_db, uint32_t batch, bool train, hipStream_t stream) {
+    const NoteModelDims& d = lay_.d;
     const float* w = d_arena_;
-    float* grad = d_arena_ + n;
+    const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d_ws_ + ws_idx_);
     float* feat = d_ws_ + ws_feat_;
-    float* dfeat = d_ws_ + ws_dfeat_;
     const size_t h_stride = round64(static_cast<size_t>(max_batch_) * d.mlp);
     auto H = [&](uint32_t i) { return d_ws_ + ws_h_ + i * h_stride; };
-    float* dA[2] = {d_ws_ + ws_da_, d_ws_ + ws_da_ + h_stride};
     float* Z = d_ws_ + ws_z_;
-    float* dZ = d_ws_ + ws_dz_;
     float* part = d_ws_ + ws_part_;
-    double* row_loss = reinterpret_cast<double*>(d_ws_ + ws_rowloss_);
     const uint32_t F = d.n_features, mlp = d.mlp;
-    const bool train = mode != PVQ_TRAIN_EVAL;
     const uint32_t threshold = nt_keep_threshold(hyper_.dropout);
     const bool drop = train && threshold > 0;
     const float scale = drop ? static_cast<float>(1.0 / (1.0 - hyper_.dropout)) : 1.0f;
     const size_t x_bytes = static_cast<size_t>(d.L) * sizeof(float);
 
-    // forward (train.py:87-99)
     hipLaunchKernelGGL(nt_features, dim3(batch), dim3(NT_THREADS), x_bytes, stream, d_db, d_idx, w + lay_.conv_w.at, feat, d.n_bins, d.t_frames, d.L, d.o_pool);
     Epi e{};
     e.kind = E_HIDDEN;
@@ -494,6 +575,45 @@ pvq_status NoteTrainer::step(int mode, const float* d_db, const float* d_targets
     e.kind = E_BIAS;
     e.bias = w + lay_.out_b.at;
     gemm(G_NT, H(d.layers), w + lay_.out_w.at, Z, batch, NM_OUT, mlp, mlp, mlp, e, part, stream);
+}
+
+pvq_status NoteTrainer::step(int mode, const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx, uint32_t batch, float* d_loss,
+                             float* d_logits, hipStream_t stream) {
+    const NoteModelDims& d = lay_.d;
+    std::string err;
+    const pvq_status st = note_trainer_check_step(d, max_batch_, mode, d_db, d_targets, n_rows, idx, batch, err);
+    if (st != PVQ_OK) {
+        set_last_error(err);
+        return st;
+    }
+    if (device_id_ < 0) {
+        set_last_error("the note trainer runs on a GPU; this handle has none");
+        return PVQ_ERR_NO_DEVICE;
+    }
+    PVQ_HIP(hipSetDevice(device_id_));
+    const pvq_status up = upload_idx(idx, batch, stream);
+    if (up != PVQ_OK) return up;
+    const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d_ws_ + ws_idx_);
+
+    const size_t n = lay_.n_params;
+    const float* w = d_arena_;
+    float* grad = d_arena_ + n;
+    float* feat = d_ws_ + ws_feat_;
+    float* dfeat = d_ws_ + ws_dfeat_;
+    const size_t h_stride = round64(static_cast<size_t>(max_batch_) * d.mlp);
+    auto H = [&](uint32_t i) { return d_ws_ + ws_h_ + i * h_stride; };
+    float* dA[2] = {d_ws_ + ws_da_, d_ws_ + ws_da_ + h_stride};
+    float* Z = d_ws_ + ws_z_;
+    float* dZ = d_ws_ + ws_dz_;
+    float* part = d_ws_ + ws_part_;
+    double* row_loss = reinterpret_cast<double*>(d_ws_ + ws_rowloss_);
+    const uint32_t F = d.n_features, mlp = d.mlp;
+    const bool train = mode != PVQ_TRAIN_EVAL;
+    const bool drop = train && nt_keep_threshold(hyper_.dropout) > 0;
+    const float scale = drop ? static_cast<float>(1.0 / (1.0 - hyper_.dropout)) : 1.0f;
+    const size_t x_bytes = static_cast<size_t>(d.L) * sizeof(float);
+
+    forward(d_db, batch, train, stream);
     const double inv_n = 1.0 / (static_cast<double>(batch) * NM_OUT);
     hipLaunchKernelGGL(nt_loss, dim3(batch), dim3(NM_OUT), 0, stream, Z, d_targets, d_idx, static_cast<float>(inv_n), dZ, d_logits, row_loss);
     if (d_loss) hipLaunchKernelGGL(nt_loss_final, dim3(1), dim3(NT_THREADS), 0, stream, row_loss, batch, inv_n, d_loss);
@@ -534,6 +654,70 @@ pvq_status NoteTrainer::step(int mode, const float* d_db, const float* d_targets
         }
     }
     PVQ_HIP(hipGetLastError());
+    return PVQ_OK;
+}
+
+pvq_status NoteTrainer::test(const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx, size_t n_idx, uint32_t batch,
+                             pvq_note_test_batch* out_batches, uint32_t* out_pitch, float* d_logits, hipStream_t stream) {
+    std::string err;
+    const pvq_status st = note_trainer_check_test(lay_.d, d_db, d_targets, n_rows, idx, n_idx, batch, out_batches, err);
+    if (st != PVQ_OK) {
+        set_last_error(err);
+        return st;
+    }
+    if (device_id_ < 0) {
+        set_last_error("the note trainer runs on a GPU; this handle has none");
+        return PVQ_ERR_NO_DEVICE;
+    }
+    PVQ_HIP(hipSetDevice(device_id_));
+    const NoteTrainerTestPlan plan = note_trainer_test_plan(n_idx, max_batch_, batch);
+    // grow-only buffers: the rows' masks [cap][8] words, counts [cap] uint4 and losses [cap] doubles; the records and pitch counts
+    if (n_idx > test_rows_cap_) {
+        if (d_test_rows_) PVQ_HIP(hipFree(d_test_rows_));
+        d_test_rows_ = nullptr;
+        test_rows_cap_ = 0;
+        PVQ_HIP(hipMalloc(&d_test_rows_, plan.rows_bytes));
+        test_rows_cap_ = n_idx;
+    }
+    if (plan.out_bytes > test_out_cap_) {
+        if (d_test_out_) PVQ_HIP(hipFree(d_test_out_));
+        d_test_out_ = nullptr;
+        if (h_test_out_) PVQ_HIP(hipHostFree(h_test_out_));
+        h_test_out_ = nullptr;
+        test_out_cap_ = 0;
+        PVQ_HIP(hipMalloc(&d_test_out_, plan.out_bytes));
+        PVQ_HIP(hipHostMalloc(&h_test_out_, plan.out_bytes, hipHostMallocDefault));
+        test_out_cap_ = plan.out_bytes;
+    }
+    char* rows_base = static_cast<char*>(d_test_rows_);
+    uint32_t* masks = reinterpret_cast<uint32_t*>(rows_base);
+    uint4* counts = reinterpret_cast<uint4*>(rows_base + 32 * test_rows_cap_);
+    double* row_loss = reinterpret_cast<double*>(rows_base + 48 * test_rows_cap_);
+    pvq_note_test_batch* d_batches = static_cast<pvq_note_test_batch*>(d_test_out_);
+    const size_t batch_bytes = plan.n_batches * sizeof(pvq_note_test_batch);
+    uint32_t* d_pitch = reinterpret_cast<uint32_t*>(static_cast<char*>(d_test_out_) + batch_bytes);
+    const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d_ws_ + ws_idx_);
+
+    for (const NtTestChunk& c : plan.chunks) {
+        const pvq_status up = upload_idx(idx + c.begin, c.rows, stream);
+        if (up != PVQ_OK) return up;
+        forward(d_db, c.rows, false, stream);
+        hipLaunchKernelGGL(nt_test_rows, dim3(c.rows), dim3(NM_OUT), 0, stream, d_ws_ + ws_z_, d_targets, d_idx, c.begin, masks, counts, row_loss, d_logits);
+    }
+    constexpr uint32_t per_block = NT_THREADS / 64;
+    hipLaunchKernelGGL(nt_test_batches, dim3(static_cast<uint32_t>((plan.n_batches + per_block - 1) / per_block)), dim3(NT_THREADS), 0, stream, counts, row_loss,
+                       n_idx, batch, plan.n_batches, d_batches);
+    if (out_pitch) {
+        PVQ_HIP(hipMemsetAsync(d_pitch, 0, NT_TEST_PITCH_BYTES, stream));
+        hipLaunchKernelGGL(nt_test_pitches, dim3(static_cast<uint32_t>(std::min<size_t>(n_idx, 1024))), dim3(NM_OUT), 0, stream, masks, n_idx, d_pitch);
+    }
+    PVQ_HIP(hipGetLastError());
+    // the one read-back, the one wait
+    const size_t back = batch_bytes + (out_pitch ? NT_TEST_PITCH_BYTES : 0);
+    PVQ_HIP(hipMemcpyAsync(h_test_out_, d_test_out_, back, hipMemcpyDeviceToHost, stream));
+    PVQ_HIP(hipStreamSynchronize(stream));
+    std::memcpy(out_batches, h_test_out_, batch_bytes);
+    if (out_pitch) std::memcpy(out_pitch, static_cast<const char*>(h_test_out_) + batch_bytes, NT_TEST_PITCH_BYTES);
     return PVQ_OK;
 }
 

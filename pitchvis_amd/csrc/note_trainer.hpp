@@ -14,6 +14,11 @@
 //   nt_bias_grad    column sums in a fixed order
 //   nt_conv_grad, nt_conv_reduce   dFeat through pool and ReLU to the 96 conv gradients: per row, then over rows, fixed order
 //   nt_adam         one launch over the arena
+// The test pass (train.py:164-198) runs the same forward without dropout over chunks of at most max_batch rows, then
+//   nt_test_rows    per row: the 128-bit masks of prediction (z > 0) and label (y > 0.5) by wave ballots, tp / fp / fn / correct by
+//                   popcount, the row's loss as nt_loss's tree in double, the logits when asked; indexed by the position in idx
+//   nt_test_batches one wave per test batch: its rows' records added, the loss in double in an order fixed by the row count
+//   nt_test_pitches tp / fp / fn per output over all rows, from the masks
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -40,11 +45,19 @@ class NoteTrainer {
     // idx: HOST array.  Asynchronous on `stream`; uses the handle's workspace, so one stream at a time.
     pvq_status step(int mode, const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx, uint32_t batch, float* d_loss,
                     float* d_logits, hipStream_t stream);
+    // train.py:164-198 over idx[0 .. n_idx) (HOST) in test batches of `batch`; fills the HOST outputs, so it waits on `stream` at its end.
+    // Leaves the counter, the weights, the gradients and the moments as they are.
+    pvq_status test(const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx, size_t n_idx, uint32_t batch,
+                    pvq_note_test_batch* out_batches, uint32_t* out_pitch, float* d_logits, hipStream_t stream);
     // the arena `what` names, n_params floats in state_dict order -> host.  Synchronises the device.
     pvq_status read(int what, float* out, size_t capacity);
 
    private:
     NoteTrainer() = default;
+    // rows -> pinned slot -> the workspace's index array, on `stream`
+    pvq_status upload_idx(const uint32_t* idx, uint32_t rows, hipStream_t stream);
+    // train.py:87-99 on the rows the workspace's index array names: features, fc1, the hidden layers, the logits Z.  Queues only.
+    void forward(const float* d_db, uint32_t batch, bool train, hipStream_t stream);
     int device_id_ = -1;
     NoteTrainerLayout lay_;
     pvq_note_trainer_hyper hyper_{};
@@ -56,6 +69,12 @@ class NoteTrainer {
     uint32_t* h_idx_[2] = {nullptr, nullptr};   // pinned staging of idx, two slots so that a call may be queued behind a running one
     hipEvent_t idx_copied_[2] = {nullptr, nullptr};
     bool idx_pending_[2] = {false, false};
+    // the test pass: per-row masks, counts and losses (grow-only), the batch records and pitch counts and their pinned copy
+    void* d_test_rows_ = nullptr;
+    size_t test_rows_cap_ = 0;    // rows
+    void* d_test_out_ = nullptr;
+    void* h_test_out_ = nullptr;
+    size_t test_out_cap_ = 0;     // bytes
     // float offsets into the workspace
     size_t ws_feat_ = 0, ws_dfeat_ = 0, ws_h_ = 0, ws_da_ = 0, ws_z_ = 0, ws_dz_ = 0, ws_convpart_ = 0, ws_rowloss_ = 0, ws_part_ = 0, ws_idx_ = 0;
 };

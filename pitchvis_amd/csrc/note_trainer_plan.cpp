@@ -127,4 +127,73 @@ uint32_t nt_splits(uint32_t m, uint32_t n, uint32_t k) {
     return static_cast<uint32_t>(std::max<uint64_t>(s, 1));
 }
 
+NoteTrainerTestPlan note_trainer_test_plan(size_t n_idx, uint32_t max_batch, uint32_t batch) {
+    NoteTrainerTestPlan p;
+    if (n_idx == 0 || max_batch == 0 || batch == 0) return p;
+    for (size_t at = 0; at < n_idx; at += max_batch) {
+        NtTestChunk c;
+        c.begin = at;
+        c.rows = static_cast<uint32_t>(std::min<size_t>(max_batch, n_idx - at));
+        p.chunks.push_back(c);
+    }
+    p.n_batches = (n_idx + batch - 1) / batch;
+    p.rows_bytes = n_idx * NT_TEST_ROW_BYTES;
+    p.out_bytes = p.n_batches * sizeof(pvq_note_test_batch) + NT_TEST_PITCH_BYTES;
+    return p;
+}
+
+pvq_status note_trainer_check_test(const NoteModelDims& d, const void* d_db, const void* d_targets, size_t n_rows, const uint32_t* idx, size_t n_idx,
+                                   uint32_t batch, const void* out_batches, std::string& err) {
+    if (!d_db || !d_targets || !idx) {
+        err = "note trainer: d_db, d_targets or idx is null";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (!out_batches) {
+        err = "note trainer: out_batches is null";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (batch < 1) {
+        err = "note trainer: the test batch must be at least 1";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (n_idx < 1 || n_idx > NT_TEST_MAX_IDX) {
+        err = "note trainer: n_idx must lie in 1 .. 2^25";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (n_rows > 0xffffffffull) {
+        err = "note trainer: a dataset holds at most 2^32 - 1 rows";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    for (size_t i = 0; i < n_idx; ++i)
+        if (idx[i] < d.t_frames - 1 || idx[i] >= n_rows) {
+            err = "note trainer: idx[" + std::to_string(i) + "] = " + std::to_string(idx[i]) + " is outside [t_frames - 1, n_rows)";
+            return PVQ_ERR_INVALID_ARG;
+        }
+    return PVQ_OK;
+}
+
+pvq_status note_test_metrics(const pvq_note_test_batch* b, size_t n_batches, double* mean_f1, double* accuracy, double* mean_loss, std::string& err) {
+    if (!b || n_batches < 1) {
+        err = "note test metrics: the records are null or there is none";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    double f1 = 0.0, loss = 0.0;
+    uint64_t correct = 0, rows = 0;
+    for (size_t k = 0; k < n_batches; ++k) {
+        const uint64_t den = 2 * static_cast<uint64_t>(b[k].tp) + b[k].fp + b[k].fn;
+        if (den > 0) f1 += 2.0 * static_cast<double>(b[k].tp) / static_cast<double>(den);   // (else 0: sklearn's zero-division value)
+        loss += b[k].loss;
+        correct += b[k].correct;
+        rows += b[k].rows;
+    }
+    if (rows == 0) {
+        err = "note test metrics: the records hold no rows";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (mean_f1) *mean_f1 = f1 / static_cast<double>(n_batches);
+    if (accuracy) *accuracy = static_cast<double>(correct) / (static_cast<double>(NM_OUT) * static_cast<double>(rows));
+    if (mean_loss) *mean_loss = loss / static_cast<double>(n_batches);
+    return PVQ_OK;
+}
+
 }  // namespace pvq

@@ -1,9 +1,9 @@
 // note_trainer_plan.hpp — host side of the note trainer (note_trainer.hip): the layout of the parameter arena, the argument checks,
-// the per-step Adam constants, the split-K rule of the GEMMs and the dropout mask function.  Plain data in, plain data out: no HIP,
-// no device pointer, no environment (the note_model_plan.cpp pattern).
+// the per-step Adam constants, the split-K rule of the GEMMs, the dropout mask function, and the plan and the metrics of the test
+// pass.  Plain data in, plain data out: no HIP, no device pointer, no environment (the note_model_plan.cpp pattern).
 //
 // The step is pitchvis_train/train.py:108-162: forward in training mode (train.py:87-99), BCELoss, backward, optim.Adam with weight
-// decay (train.py:141-144).
+// decay (train.py:141-144).  The test pass is train.py:164-198.
 #pragma once
 
 #include <cstddef>
@@ -78,5 +78,28 @@ NtAdamStep note_trainer_adam_step(const pvq_note_trainer_hyper& h, uint64_t t);
 // the summation order, and equal calls must give equal bits on every device), at least 8 K stages per split, at most 8 splits, and
 // splits * m * n within NT_PART_FLOATS.  1: no split, the GEMM writes its result itself.
 uint32_t nt_splits(uint32_t m, uint32_t n, uint32_t k);
+
+// The test pass (train.py:164-198).  Dropout is off, so a row's forward depends on no other row: the forward runs in chunks of at
+// most max_batch consecutive entries of idx, a function of n_idx and max_batch alone; `batch` shapes only the counting.
+constexpr size_t NT_TEST_MAX_IDX = size_t(1) << 25;   // rows of a pass: 128 * rows, the most a count can reach, stays below 2^32
+constexpr size_t NT_TEST_ROW_BYTES = 24 + 32;         // per row: tp, fp, fn, correct and the loss in double; two 128-bit masks
+constexpr size_t NT_TEST_PITCH_BYTES = NM_OUT * 3 * sizeof(uint32_t);
+struct NtTestChunk {
+    size_t begin = 0;     // position in idx
+    uint32_t rows = 0;    // 1 .. max_batch
+};
+struct NoteTrainerTestPlan {
+    std::vector<NtTestChunk> chunks;   // in order, back to back, covering 0 .. n_idx
+    size_t n_batches = 0;              // ceil(n_idx / batch): the last batch may be short
+    size_t rows_bytes = 0;             // device: the per-row records and masks, n_idx * NT_TEST_ROW_BYTES
+    size_t out_bytes = 0;              // the one read-back: n_batches records of 32 bytes, then the [128][3] pitch counts
+};
+NoteTrainerTestPlan note_trainer_test_plan(size_t n_idx, uint32_t max_batch, uint32_t batch);
+// the checks of a test pass that need no device; err receives the text
+pvq_status note_trainer_check_test(const NoteModelDims& d, const void* d_db, const void* d_targets, size_t n_rows, const uint32_t* idx, size_t n_idx,
+                                   uint32_t batch, const void* out_batches, std::string& err);
+// what train.py:185-198 prints, from the records: the plain mean of the batch F1 scores (2 tp / (2 tp + fp + fn), 0 when that
+// denominator is 0), sum of correct / (128 * sum of rows), the plain mean of the batch losses.  An output may be null.
+pvq_status note_test_metrics(const pvq_note_test_batch* b, size_t n_batches, double* mean_f1, double* accuracy, double* mean_loss, std::string& err);
 
 }  // namespace pvq

@@ -1,7 +1,8 @@
 """The trainer's optimisation step (pitchvis_train/train.py:108-162) on the GPU: pvq_note_trainer_* of include/pvq.h.  ``NoteTrainer``
 owns the parameters, their gradients and Adam's moments on the device and runs forward (training mode), BCE loss, backward and Adam on
 a batch of rows gathered by index from a dataset in device memory: the ``[n_rows][n_bins]`` dB rows and ``[n_rows][128]`` targets
-``train_dataset_streams`` leaves there.  ``state_dict()`` is what ``NoteModel.from_state_dict`` takes."""
+``train_dataset_streams`` leaves there.  ``state_dict()`` is what ``NoteModel.from_state_dict`` takes.  ``NoteTrainer.test`` is the test
+pass that follows the last epoch (train.py:164-198): micro-F1 per batch, accuracy and loss, counted on the device."""
 from __future__ import annotations
 
 import ctypes as C
@@ -56,6 +57,74 @@ def epoch(indices, batch: int):
         yield idx[at:at + int(batch)]
 
 
+def random_split(n_rows: int, t_frames: int, train_fraction: float = 0.8, seed: int = 0):
+    """``(train_idx, test_idx)``: a seeded permutation of the admissible sample indices ``t_frames - 1 .. n_rows - 1``, cut at
+    ``int(total * train_fraction)`` (train.py:56-61).  Stands for ``random_split`` and the loaders' shuffle, as ``epoch`` stands for the
+    ``DataLoader``.  Host only."""
+    first = int(t_frames) - 1
+    total = int(n_rows) - first
+    if first < 0 or total < 1:
+        raise ValueError("random_split: n_rows must exceed t_frames - 1 >= 0")
+    if not 0.0 <= train_fraction <= 1.0:
+        raise ValueError("random_split: train_fraction must lie in [0, 1]")
+    perm = (np.random.default_rng(seed).permutation(total) + first).astype(np.uint32)
+    cut = int(total * train_fraction)
+    return perm[:cut], perm[cut:]
+
+
+_RECORD = np.dtype([(n, np.uint32) for n in ("rows", "tp", "fp", "fn", "correct", "_pad")] + [("loss", np.float64)])   # pvq_note_test_batch
+assert _RECORD.itemsize == C.sizeof(_lib.CNoteTestBatch) == 32
+
+
+def _f1(tp, fp, fn) -> np.ndarray:
+    """2 tp / (2 tp + fp + fn) per entry, 0 where that denominator is 0"""
+    num = 2.0 * np.asarray(tp, np.float64)
+    den = num + np.asarray(fp, np.float64) + np.asarray(fn, np.float64)
+    return np.divide(num, den, out=np.zeros_like(den), where=den > 0)
+
+
+def note_test_metrics(records: np.ndarray):
+    """``(mean_f1, accuracy, mean_loss)`` of an array of batch records (``NoteTestResult.records``): what train.py:193-198 prints, by
+    ``pvq_note_test_metrics``"""
+    from . import _check
+    rec = np.ascontiguousarray(records, _RECORD).reshape(-1)
+    f1, acc, loss = C.c_double(), C.c_double(), C.c_double()
+    st = _lib.load().pvq_note_test_metrics(rec.ctypes.data_as(C.POINTER(_lib.CNoteTestBatch)), rec.size, C.byref(f1), C.byref(acc), C.byref(loss))
+    if st == _lib.PVQ_ERR_INVALID_ARG:
+        raise ValueError((_lib.load().pvq_last_error() or b"").decode())
+    _check(st)
+    return f1.value, acc.value, loss.value
+
+
+@dataclass
+class NoteTestResult:
+    """One test pass (train.py:164-198).  Per batch: ``rows``, ``tp``, ``fp``, ``fn``, ``correct`` (uint32), ``loss`` (the batch's mean
+    BCE) and ``f1``, views of ``records`` (the ``pvq_note_test_batch`` array) but for ``f1``; ``mean_f1``, ``accuracy`` and
+    ``mean_loss`` as train.py prints them; ``pitch_counts`` ``[128][3]`` tp / fp / fn per output over the whole pass and ``pitch_f1``
+    ``[128]`` (both None when the pass was run without them)."""
+    records: np.ndarray
+    rows: np.ndarray
+    tp: np.ndarray
+    fp: np.ndarray
+    fn: np.ndarray
+    correct: np.ndarray
+    loss: np.ndarray
+    f1: np.ndarray
+    mean_f1: float
+    accuracy: float
+    mean_loss: float
+    pitch_counts: Optional[np.ndarray]
+    pitch_f1: Optional[np.ndarray]
+
+    @staticmethod
+    def from_records(records: np.ndarray, pitch_counts: Optional[np.ndarray] = None) -> "NoteTestResult":
+        r = records
+        mean_f1, accuracy, mean_loss = note_test_metrics(r)
+        c = pitch_counts
+        return NoteTestResult(r, r["rows"], r["tp"], r["fp"], r["fn"], r["correct"], r["loss"], _f1(r["tp"], r["fp"], r["fn"]), mean_f1, accuracy,
+                              mean_loss, c, None if c is None else _f1(c[:, 0], c[:, 1], c[:, 2]))
+
+
 class NoteTrainer:
     """``weights``: the initial ``state_dict`` (names as for ``NoteModel``).  ``device=None``: a host-only handle (argument checks
     work; ``step`` raises: no CPU fallback).  ``max_batch`` sizes the workspace once."""
@@ -91,12 +160,8 @@ class NoteTrainer:
         """completed ``step`` calls in mode "step": Adam's t - 1 and the step the dropout mask is keyed by"""
         return int(self._L.pvq_note_trainer_steps(self._h))
 
-    def step(self, d_db, d_targets, idx, mode="step", d_loss=None, d_logits=None, *, n_rows: Optional[int] = None, stream=None) -> None:
-        """One step on the batch ``idx`` (host sequence of sample indices, T - 1 <= i < n_rows).  ``d_db`` ``[n_rows][n_bins]`` and
-        ``d_targets`` ``[n_rows][128]``: contiguous f32 device tensors (or raw pointers, with ``n_rows``).  ``mode``: "step" (dropout,
-        backward, Adam), "grad" (the same without Adam and without advancing the counter) or "eval" (no dropout, forward and loss only).
-        ``d_loss`` (one float) and ``d_logits`` (``[len(idx)][128]``): optional device tensors to fill.  Asynchronous on ``stream``."""
-        from . import _check, _ptr, _stream_handle
+    def _dataset_rows(self, d_db, d_targets, n_rows: Optional[int]) -> int:
+        """the layout checks of a dataset given as tensors -> n_rows"""
         if hasattr(d_db, "shape"):
             if d_db.dim() != 2 or d_db.shape[1] != self.params.n_bins or not d_db.is_contiguous() or d_db.element_size() != 4:
                 raise ValueError("d_db must be a contiguous f32 tensor [n_rows][n_bins]")
@@ -111,6 +176,15 @@ class NoteTrainer:
                 raise ValueError("d_targets must be a contiguous f32 tensor [n_rows][128]")
             if n_rows > d_targets.shape[0]:
                 raise ValueError("d_targets holds fewer than n_rows rows")
+        return int(n_rows)
+
+    def step(self, d_db, d_targets, idx, mode="step", d_loss=None, d_logits=None, *, n_rows: Optional[int] = None, stream=None) -> None:
+        """One step on the batch ``idx`` (host sequence of sample indices, T - 1 <= i < n_rows).  ``d_db`` ``[n_rows][n_bins]`` and
+        ``d_targets`` ``[n_rows][128]``: contiguous f32 device tensors (or raw pointers, with ``n_rows``).  ``mode``: "step" (dropout,
+        backward, Adam), "grad" (the same without Adam and without advancing the counter) or "eval" (no dropout, forward and loss only).
+        ``d_loss`` (one float) and ``d_logits`` (``[len(idx)][128]``): optional device tensors to fill.  Asynchronous on ``stream``."""
+        from . import _check, _ptr, _stream_handle
+        n_rows = self._dataset_rows(d_db, d_targets, n_rows)
         ix = np.ascontiguousarray(idx, np.uint32).reshape(-1)
         if hasattr(d_logits, "numel") and (d_logits.numel() < ix.size * N_OUT or not d_logits.is_contiguous() or d_logits.element_size() != 4):
             raise ValueError("d_logits must be a contiguous f32 tensor [len(idx)][128]")
@@ -121,6 +195,30 @@ class NoteTrainer:
         if st == _lib.PVQ_ERR_INVALID_ARG:
             raise ValueError((self._L.pvq_last_error() or b"").decode())
         _check(st)
+
+    def test(self, d_db, d_targets, idx, batch: int = 100, d_logits=None, pitches: bool = True, *, n_rows: Optional[int] = None,
+             stream=None) -> NoteTestResult:
+        """The test pass (train.py:164-198) over ``idx`` (host sequence of sample indices; the caller's permutation is the shuffle) in
+        batches of ``batch`` (the last may be short; not bounded by ``max_batch``: it shapes only the metric).  Dropout is off; the
+        prediction is logit > 0, the label target > 0.5.  ``d_logits`` (``[len(idx)][128]``): optional device tensor to fill.
+        Synchronous: waits on ``stream`` once.  Leaves ``steps``, the weights, the gradients and the moments as they are."""
+        from . import _check, _ptr, _stream_handle
+        n_rows = self._dataset_rows(d_db, d_targets, n_rows)
+        ix = np.ascontiguousarray(idx, np.uint32).reshape(-1)
+        if hasattr(d_logits, "numel") and (d_logits.numel() < ix.size * N_OUT or not d_logits.is_contiguous() or d_logits.element_size() != 4):
+            raise ValueError("d_logits must be a contiguous f32 tensor [len(idx)][128]")
+        batch = int(batch)
+        if not 0 <= batch < 2 ** 32:
+            raise ValueError("note trainer: the test batch must lie in 1 .. 2^32 - 1")
+        rec = np.zeros(-(-ix.size // batch) if batch > 0 and ix.size else 1, _RECORD)
+        counts = np.zeros((N_OUT, 3), np.uint32) if pitches else None
+        st = self._L.pvq_note_trainer_test(self._h, _ptr(d_db), _ptr(d_targets), n_rows, ix.ctypes.data_as(C.POINTER(C.c_uint32)), ix.size, batch,
+                                           rec.ctypes.data_as(C.POINTER(_lib.CNoteTestBatch)),
+                                           counts.ctypes.data_as(C.POINTER(C.c_uint32)) if pitches else None, _ptr(d_logits), _stream_handle(stream))
+        if st == _lib.PVQ_ERR_INVALID_ARG:
+            raise ValueError((self._L.pvq_last_error() or b"").decode())
+        _check(st)
+        return NoteTestResult.from_records(rec, counts)
 
     def read_flat(self, what: str = "weights", out: Optional[np.ndarray] = None) -> np.ndarray:
         """"weights", "grads", "adam_m" or "adam_v" as one f32 array in state_dict order.  Synchronises."""
