@@ -529,6 +529,114 @@ pvq_status pvq_render_batch_rows_device(pvq_render_batch *r, size_t n_rows, cons
                                         const float *d_size, const uint32_t *d_peak_count, uint32_t max_peaks,
                                         const pvq_render_outputs *outs, void *stream);
 
+/* ---- the viewer's main picture: pitch balls, bass spiral, bloom --------------------------------------
+ * pitchvis_viewer/src/display_system/update.rs:38-426 (update_display) turns an AnalysisState, frame after frame, into
+ *   - a ball per bin (setup.rs:89-125) that lights on a peak, fades between frames and hides beside a stronger neighbour,
+ *   - the bass spiral (setup.rs:127-172) lit up to the lowest note,
+ *   - the bloom intensity, driven by the scene's calmness.
+ * Unlike the render stage above the scene is STATEFUL: a ball's scale, alpha and depth carry from frame to frame
+ * (fade_pitch_balls, update.rs:136-178), and a frame without peaks leaves balls, bass spiral and bloom as the previous frame left
+ * them (the early return at update.rs:85-87).
+ *
+ * Construction (setup.rs:89-125, :127-172, util.rs:3-20): ball idx sits at bin_to_spiral(bpo, idx) with z = -0.01; its scale is 3.0
+ * and it is visible if idx % 17 == 0, otherwise scale 0 and hidden; its colour is LinearRgba::from(Color::srgb(1.0, 0.7, 0.6)), its
+ * params {calmness 0, pitch_accuracy 0, pitch_deviation 0}.  The bass spiral has min(octaves * 72, 168) - 1 segments, all hidden,
+ * colour srgb(0.8, 0.7, 0.6).  Bloom intensity starts at 0 (the reference leaves Bevy's default there until the first frame with
+ * peaks).
+ *
+ * One frame with (peaks_continuous, calmness[], pitch_accuracy[], pitch_deviation[], scene_calmness, dt), in this order:
+ *  1. fade (update.rs:147-178), every ball: size = scale / F; if size * F >= 0.019 { visible; size *= dropoff; scale = size * F;
+ *     alpha = max(alpha * dropoff, 0.7); z -= 0.001 * 30.0 * dt }; if size * F < 0.019 { hidden }, with F = 1.0f / 305.0f and
+ *     dropoff = (0.85 - 0.15 * (idx as f32 / n as f32)).powf(30 * dt).
+ *  2. no peaks: return, nothing else changes (update.rs:85-87).
+ *  3. update_pitch_balls (update.rs:199-334): max_size by util::arg_max (first wins); balls keyed by trunc(center) as usize, the
+ *     LATER list entry of a key wins (HashMap::insert); translation (bin_to_spiral(bpo, center).xy, (size / max_size - 1.01) * 12.5);
+ *     colour LinearRgba::from(Color::srgba(r, g, b, 1 - (1 - size / max_size).powf(2.0))) with (r, g, b) = calculate_color at
+ *     (center + (bpo - 3 (bpo / 12))) % bpo, clamped to 0..1 (r, g, b only, update.rs:276-284); params calmness =
+ *     clamp(calmness[idx] - 0.27, 0, 1), pitch_accuracy[idx], pitch_deviation[idx] (both DisplayMode variants take this branch);
+ *     scale = size * (Performance ? 0.7 : 1.0) * F * (1 + 0.2 * calmness), visible if scale >= 0.002.  Hide pass (update.rs:307-330):
+ *     radius = (bpo / 12) as f32 * 0.23; the bins round(center - radius).max(0) ..= round(center + radius).min(n - 1) of every entry
+ *     the map kept are marked, the keyed bins unmarked; visible marked balls become hidden and keep their scale.
+ *     A peak with trunc(center) >= n_bins is ignored (the reference would index out of range); it still counts for max_size.
+ *  4. update_bloom (update.rs:336-351): 0 when bloom is disabled or the mode is Performance, else clamp(scene_calmness * 1.3, 0, 1).
+ *  5. update_bass_spiral (update.rs:369-425): all segments hidden; nothing more in Galaxy mode; otherwise, from the FIRST peak,
+ *     c = center / bpo * 12; nothing is lit if round(c) * 6 >= n_segments; otherwise segments [0, (round(c) * 6) as usize) are lit, all
+ *     in one colour: calculate_color at (round(c) * bpo / 12 + (bpo - 3 (bpo / 12))) % bpo with alpha 1 - (1 - size / max_size)^2 — a
+ *     Color, not converted to linear.  The visible state is (lit count, rgba); rgba keeps its last value while nothing is lit.
+ * Left out: the `ml` branch (update.rs:247-255; it reads an AnalysisState field that no longer exists), params.time (the caller's
+ * clock), the debug meshes (update_spectrum, the calmness histogram and graph).
+ * Every libm call of steps 3 and 5 is the double-precision function rounded once to f32, on the host and on the device (DESIGN.md
+ * 6c); the fade's powf is the host's, also for the device stage. */
+typedef enum pvq_visuals_mode { PVQ_VISUALS_FULL = 0, PVQ_VISUALS_ZEN = 1, PVQ_VISUALS_PERFORMANCE = 2, PVQ_VISUALS_GALAXY = 3 } pvq_visuals_mode;
+/* fixed at create; a change needs a new handle (as a palette does for pvq_render_batch_create) */
+typedef struct pvq_scene_settings {
+    int visuals_mode;          /* pvq_visuals_mode (SettingsState::visuals_mode) */
+    int enable_bloom;          /* SettingsState::enable_bloom */
+    const float *colors;       /* 12 RGB triples in [0, 1]; NULL: pitchvis_colors::COLORS */
+    float gray_level, easing_pow;   /* GRAY_LEVEL 60.0, EASING_POW 1.3 (lib.rs:56-57) */
+} pvq_scene_settings;
+void pvq_scene_default_settings(pvq_scene_settings *s);   /* Full, bloom on, COLORS, 60.0, 1.3 */
+
+/* One stream on the host: the one-stream face of the stage, in the manner of pvq_analysis_state_*.  settings NULL: the defaults.
+ * PVQ_ERR_INVALID_ARG for octaves or buckets_per_octave 0 or an unknown mode. */
+typedef struct pvq_scene_state pvq_scene_state;
+pvq_status pvq_scene_state_create(uint32_t octaves, uint32_t buckets_per_octave, const pvq_scene_settings *settings,
+                                  pvq_scene_state **out);
+void pvq_scene_state_destroy(pvq_scene_state *s);
+uint32_t pvq_scene_state_n_bins(const pvq_scene_state *s);
+uint32_t pvq_scene_state_n_segments(const pvq_scene_state *s);   /* min(octaves * 72, 168) - 1 */
+/* replaces update_display (update.rs:38-134) for one frame: center / size [n_peaks] (peaks_continuous, in list order), calmness /
+ * pitch_accuracy / pitch_deviation [n_bins], smoothed_scene_calmness, and the frame's Time::delta in nanoseconds */
+pvq_status pvq_scene_state_update(pvq_scene_state *s, const float *center, const float *size, uint32_t n_peaks,
+                                  const float *calmness, const float *pitch_accuracy, const float *pitch_deviation,
+                                  float scene_calmness, uint64_t frame_time_ns);
+/* the scene as it stands; any pointer may be NULL.  ball_xyzs [n_bins][4]: x, y, z, scale; ball_rgba [n_bins][4] (linear r, g, b and
+ * alpha); ball_params [n_bins][3]: calmness, pitch_accuracy, pitch_deviation; ball_visible [ceil(n_bins / 32)]: bit bin % 32 of word
+ * bin / 32 (the bit order of peak_mask); bass_lit: the number of lit segments; bass_rgba [4]; bloom: Bloom::intensity */
+pvq_status pvq_scene_state_get(const pvq_scene_state *s, float *ball_xyzs, float *ball_rgba, float *ball_params,
+                               uint32_t *ball_visible, uint32_t *bass_lit, float *bass_rgba, float *bloom);
+
+/* The same for MANY streams on the GPU: n_streams scenes in one handle, their state kept on the device between calls, so PCM ->
+ * VQT -> AnalysisState::preprocess -> scene never leaves the device.  A frame-parallel kernel turns every peak into a finished
+ * record (all the libm of a frame), a wavefront per stream then fades and applies records frame after frame.  scale, z, the visible
+ * mask, the params, bass_lit and bloom carry the bits of pvq_scene_state_update; x, y and the colours too but for a libm rounding. */
+typedef struct pvq_scene_batch pvq_scene_batch;
+/* per-frame inputs, DEVICE pointers laid out as pvq_analysis_batch_outputs describes: center / size [n_streams][n_frames][max_peaks]
+ * with peak_count [n_streams][n_frames] (a count above max_peaks is taken as max_peaks); calmness / pitch_accuracy / pitch_deviation
+ * [n_streams][n_frames][n_bins]; scene_calmness [n_streams][n_frames].  All are needed. */
+typedef struct pvq_scene_inputs {
+    const float *center, *size;
+    const uint32_t *peak_count;
+    uint32_t max_peaks;
+    const float *calmness, *pitch_accuracy, *pitch_deviation, *scene_calmness;
+} pvq_scene_inputs;
+/* per-frame results, DEVICE pointers, any may be NULL: the scene after each frame, as pvq_scene_state_get gives it */
+typedef struct pvq_scene_outputs {
+    float *ball_xyzs;        /* [n_streams][n_frames][n_bins][4]; 16-byte aligned */
+    float *ball_rgba;        /* [n_streams][n_frames][n_bins][4]; 16-byte aligned */
+    float *ball_params;      /* [n_streams][n_frames][n_bins][3] */
+    uint32_t *ball_visible;  /* [n_streams][n_frames][ceil(n_bins / 32)] */
+    uint32_t *bass_lit;      /* [n_streams][n_frames] */
+    float *bass_rgba;        /* [n_streams][n_frames][4]; 16-byte aligned */
+    float *bloom;            /* [n_streams][n_frames] */
+} pvq_scene_outputs;
+/* n_streams scenes as constructed above on device_id.  The arguments are checked before any device is touched; takes the bin counts
+ * pvq_analysis_batch_create takes, 3 .. 1024 (PVQ_ERR_UNSUPPORTED beyond); device_id < 0: a host-only handle whose frames call
+ * returns PVQ_ERR_NO_DEVICE after its argument checks. */
+pvq_status pvq_scene_batch_create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, const pvq_scene_settings *settings,
+                                  uint32_t n_streams, pvq_scene_batch **out);
+void pvq_scene_batch_destroy(pvq_scene_batch *b);
+uint32_t pvq_scene_batch_n_segments(const pvq_scene_batch *b);
+/* Every stream advances by n_frames frames, in order.  frame_time_ns applies to every frame unless frame_times_ns (HOST array of
+ * n_frames) is given.  PVQ_ERR_INVALID_ARG for a missing input, max_peaks == 0 or a misaligned output, before anything is launched.
+ * Asynchronous on `stream`, one handle's calls are stream-ordered — except that a call whose frame time differs from the previous
+ * call's, or that brings per-frame times, first waits for `stream` (the fade table, built with the host's libm, is replaced). */
+pvq_status pvq_scene_batch_frames_device(pvq_scene_batch *b, size_t n_frames, const pvq_scene_inputs *in, uint64_t frame_time_ns,
+                                         const uint64_t *frame_times_ns, const pvq_scene_outputs *outs, void *stream);
+/* the state of one stream after the last call (synchronises), laid out as pvq_scene_state_get */
+pvq_status pvq_scene_batch_get_state(pvq_scene_batch *b, uint32_t stream_index, float *ball_xyzs, float *ball_rgba,
+                                     float *ball_params, uint32_t *ball_visible, uint32_t *bass_lit, float *bass_rgba, float *bloom);
+
 /* The note model the dataset of pitchvis_train exists for (pitchvis_train/train.py:67-99), which the viewer runs per rendered frame
  * through TorchScript on a CUDA device (pitchvis_viewer/src/ml_system.rs:24-69): a window of t_frames consecutive dB frames,
  * flattened to L = t_frames * n_bins values -> Conv1d(1, 16, kernel 5, stride 2, no padding) -> ReLU -> max_pool1d(2) -> flatten

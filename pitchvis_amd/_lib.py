@@ -36,6 +36,9 @@ EXPORTS = [
     "pvq_stream_push", "pvq_stream_gain", "pvq_stream_chunk_size_ms", "pvq_stream_frame_db", "pvq_stream_read",
     "pvq_calculate_color", "pvq_led_frame", "pvq_host_alloc", "pvq_host_free",
     "pvq_spectrogram_row", "pvq_chroma_row", "pvq_render_batch_create", "pvq_render_batch_destroy", "pvq_render_batch_rows_device",
+    "pvq_scene_default_settings", "pvq_scene_state_create", "pvq_scene_state_destroy", "pvq_scene_state_n_bins", "pvq_scene_state_n_segments",
+    "pvq_scene_state_update", "pvq_scene_state_get", "pvq_scene_batch_create", "pvq_scene_batch_destroy", "pvq_scene_batch_n_segments",
+    "pvq_scene_batch_frames_device", "pvq_scene_batch_get_state",
     "pvq_note_model_create", "pvq_note_model_destroy", "pvq_note_model_sizes", "pvq_note_model_infer", "pvq_note_model_rows_device",
     "pvq_note_model_set_workspace_limit",
     "pvq_note_trainer_hyper_default", "pvq_note_trainer_create", "pvq_note_trainer_destroy", "pvq_note_trainer_step", "pvq_note_trainer_steps",
@@ -58,6 +61,7 @@ PVQ_ERR_NONFINITE_INPUT = 9
 ALGO_AUTO, ALGO_FFT, ALGO_BLOCKDFT = 0, 1, 2
 GEMM_F32, GEMM_BF16X3 = 0, 1
 SPECTROGRAM_VQT, SPECTROGRAM_PEAKS = 0, 1
+VISUALS_FULL, VISUALS_ZEN, VISUALS_PERFORMANCE, VISUALS_GALAXY = 0, 1, 2, 3   # pvq_visuals_mode
 TRAIN_STEP, TRAIN_GRAD, TRAIN_EVAL = 0, 1, 2                      # pvq_train_mode
 TRAIN_WEIGHTS, TRAIN_GRADS, TRAIN_ADAM_M, TRAIN_ADAM_V = 0, 1, 2, 3   # pvq_train_array
 
@@ -94,6 +98,20 @@ class CAnalysisBatchOutputs(C.Structure):   # pvq_analysis_batch_outputs (device
 
 class CRenderOutputs(C.Structure):   # pvq_render_outputs (device pointers)
     _fields_ = [(n, C.c_void_p) for n in ("spectrogram_vqt", "spectrogram_peaks", "chroma", "led")]
+
+
+class CSceneSettings(C.Structure):   # pvq_scene_settings
+    _fields_ = [("visuals_mode", C.c_int), ("enable_bloom", C.c_int), ("colors", C.POINTER(C.c_float)), ("gray_level", C.c_float),
+                ("easing_pow", C.c_float)]
+
+
+class CSceneInputs(C.Structure):   # pvq_scene_inputs (device pointers)
+    _fields_ = [("center", C.c_void_p), ("size", C.c_void_p), ("peak_count", C.c_void_p), ("max_peaks", C.c_uint32),
+                ("calmness", C.c_void_p), ("pitch_accuracy", C.c_void_p), ("pitch_deviation", C.c_void_p), ("scene_calmness", C.c_void_p)]
+
+
+class CSceneOutputs(C.Structure):   # pvq_scene_outputs (device pointers)
+    _fields_ = [(n, C.c_void_p) for n in ("ball_xyzs", "ball_rgba", "ball_params", "ball_visible", "bass_lit", "bass_rgba", "bloom")]
 
 
 class CNoteModelParams(C.Structure):   # pvq_note_model_params
@@ -277,6 +295,20 @@ def load():
     L.pvq_render_batch_destroy.argtypes = [vp]
     L.pvq_render_batch_rows_device.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, C.c_uint32, C.POINTER(CRenderOutputs), vp]
     L.pvq_render_batch_rows_device.restype = C.c_int
+    ssp = C.POINTER(CSceneSettings)
+    L.pvq_scene_default_settings.argtypes = [ssp]; L.pvq_scene_default_settings.restype = None
+    L.pvq_scene_state_create.argtypes = [C.c_uint32, C.c_uint32, ssp, C.POINTER(vp)]; L.pvq_scene_state_create.restype = C.c_int
+    L.pvq_scene_state_destroy.argtypes = [vp]; L.pvq_scene_state_destroy.restype = None
+    L.pvq_scene_state_n_bins.argtypes = [vp]; L.pvq_scene_state_n_bins.restype = C.c_uint32
+    L.pvq_scene_state_n_segments.argtypes = [vp]; L.pvq_scene_state_n_segments.restype = C.c_uint32
+    L.pvq_scene_state_update.argtypes = [vp, fp, fp, C.c_uint32, fp, fp, fp, C.c_float, C.c_uint64]; L.pvq_scene_state_update.restype = C.c_int
+    L.pvq_scene_state_get.argtypes = [vp, fp, fp, fp, up, up, fp, fp]; L.pvq_scene_state_get.restype = C.c_int
+    L.pvq_scene_batch_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, ssp, C.c_uint32, C.POINTER(vp)]; L.pvq_scene_batch_create.restype = C.c_int
+    L.pvq_scene_batch_destroy.argtypes = [vp]; L.pvq_scene_batch_destroy.restype = None
+    L.pvq_scene_batch_n_segments.argtypes = [vp]; L.pvq_scene_batch_n_segments.restype = C.c_uint32
+    L.pvq_scene_batch_frames_device.argtypes = [vp, C.c_size_t, C.POINTER(CSceneInputs), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(CSceneOutputs), vp]
+    L.pvq_scene_batch_frames_device.restype = C.c_int
+    L.pvq_scene_batch_get_state.argtypes = [vp, C.c_uint32, fp, fp, fp, up, up, fp, fp]; L.pvq_scene_batch_get_state.restype = C.c_int
     L.pvq_note_model_create.argtypes = [C.c_int, C.POINTER(CNoteModelParams), C.POINTER(CNoteModelWeights), C.POINTER(vp)]
     L.pvq_note_model_create.restype = C.c_int
     L.pvq_note_model_destroy.argtypes = [vp]

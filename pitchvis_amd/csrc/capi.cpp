@@ -18,6 +18,8 @@
 #include "note_model.hpp"
 #include "note_trainer.hpp"
 #include "render_batch.hpp"
+#include "scene_batch.hpp"
+#include "scene_host.hpp"
 #include "vqt_engine.hpp"
 
 struct pvq_vqt {
@@ -37,6 +39,12 @@ struct pvq_agc_batch {
 };
 struct pvq_render_batch {
     std::unique_ptr<pvq::RenderBatch> impl;
+};
+struct pvq_scene_state {
+    std::unique_ptr<pvq::SceneState> impl;
+};
+struct pvq_scene_batch {
+    std::unique_ptr<pvq::SceneBatch> impl;
 };
 struct pvq_note_model {
     std::unique_ptr<pvq::NoteModel> impl;
@@ -1096,6 +1104,112 @@ pvq_status pvq_render_batch_rows_device(pvq_render_batch* r, size_t n_rows, cons
         const pvq_render_outputs none{};
         return r->impl->rows_device(n_rows, d_x_vqt_smoothed, d_center, d_size, d_peak_count, max_peaks, outs ? *outs : none,
                                     static_cast<hipStream_t>(stream));   // update.rs:961-1065, 1102-1131; main.rs:122-175
+    } catch (...) { return translate_exception(); }
+}
+
+// pitchvis_viewer/src/display_system/update.rs:38-426: the pitch-ball scene, one stream on the host (scene_host.hpp) and many on the
+// device (scene_batch.hpp)
+void pvq_scene_default_settings(pvq_scene_settings* s) {
+    if (!s) return;
+    s->visuals_mode = PVQ_VISUALS_FULL;
+    s->enable_bloom = 1;
+    s->colors = nullptr;
+    s->gray_level = 60.0f;   // pitchvis_colors/src/lib.rs:56-57
+    s->easing_pow = 1.3f;
+}
+pvq_status pvq_scene_state_create(uint32_t octaves, uint32_t buckets_per_octave, const pvq_scene_settings* settings, pvq_scene_state** out) {
+    try {
+        if (!out) return null_handle();
+        *out = nullptr;
+        if (octaves == 0 || buckets_per_octave == 0 || static_cast<uint64_t>(octaves) * buckets_per_octave > 0x7FFFFFFFull) {
+            pvq::set_last_error("scene: octaves and buckets_per_octave must be positive");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        pvq_scene_settings cfg;
+        pvq_scene_default_settings(&cfg);
+        if (settings) cfg = *settings;
+        pvq::scene::Settings s;
+        if (!pvq::scene_settings(octaves, buckets_per_octave, cfg.visuals_mode, cfg.enable_bloom, cfg.colors, cfg.gray_level, cfg.easing_pow, s)) {
+            pvq::set_last_error("scene: unknown visuals mode");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        *out = new pvq_scene_state{std::unique_ptr<pvq::SceneState>(new pvq::SceneState(s))};
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+void pvq_scene_state_destroy(pvq_scene_state* s) {
+    try {
+        delete s;
+    } catch (...) { (void)translate_exception(); }
+}
+uint32_t pvq_scene_state_n_bins(const pvq_scene_state* s) { return s ? s->impl->settings().n_bins : 0; }
+uint32_t pvq_scene_state_n_segments(const pvq_scene_state* s) { return s ? s->impl->settings().n_segments : 0; }
+pvq_status pvq_scene_state_update(pvq_scene_state* s, const float* center, const float* size, uint32_t n_peaks, const float* calmness,
+                                  const float* pitch_accuracy, const float* pitch_deviation, float scene_calmness, uint64_t frame_time_ns) {
+    try {
+        if (!s) return null_handle();
+        if (n_peaks && (!center || !size || !calmness || !pitch_accuracy || !pitch_deviation)) {
+            pvq::set_last_error("scene: a frame with peaks needs center, size, calmness, pitch_accuracy and pitch_deviation");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        s->impl->update(center, size, n_peaks, calmness, pitch_accuracy, pitch_deviation, scene_calmness, frame_time_ns);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_scene_state_get(const pvq_scene_state* s, float* ball_xyzs, float* ball_rgba, float* ball_params, uint32_t* ball_visible,
+                               uint32_t* bass_lit, float* bass_rgba, float* bloom) {
+    try {
+        if (!s) return null_handle();
+        const pvq::SceneBalls& b = s->impl->balls();
+        const uint32_t n = s->impl->settings().n_bins;
+        if (ball_visible)
+            for (uint32_t w = 0; w < (n + 31) / 32; ++w) ball_visible[w] = 0u;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (ball_xyzs) { ball_xyzs[4 * i] = b.x[i]; ball_xyzs[4 * i + 1] = b.y[i]; ball_xyzs[4 * i + 2] = b.z[i]; ball_xyzs[4 * i + 3] = b.scale[i]; }
+            if (ball_rgba) { ball_rgba[4 * i] = b.r[i]; ball_rgba[4 * i + 1] = b.g[i]; ball_rgba[4 * i + 2] = b.b[i]; ball_rgba[4 * i + 3] = b.a[i]; }
+            if (ball_params) { ball_params[3 * i] = b.calmness[i]; ball_params[3 * i + 1] = b.accuracy[i]; ball_params[3 * i + 2] = b.deviation[i]; }
+            if (ball_visible && b.visible[i]) ball_visible[i / 32] |= 1u << (i % 32);
+        }
+        if (bass_lit) *bass_lit = s->impl->bass_lit();
+        if (bass_rgba)
+            for (int i = 0; i < 4; ++i) bass_rgba[i] = s->impl->bass_rgba()[i];
+        if (bloom) *bloom = s->impl->bloom();
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_scene_batch_create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, const pvq_scene_settings* settings,
+                                  uint32_t n_streams, pvq_scene_batch** out) {
+    try {
+        if (!out) return null_handle();
+        *out = nullptr;
+        std::unique_ptr<pvq::SceneBatch> impl;
+        const pvq_status st = pvq::SceneBatch::create(device_id, octaves, buckets_per_octave, settings, n_streams, impl);
+        if (st != PVQ_OK) return st;
+        *out = new pvq_scene_batch{std::move(impl)};
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+void pvq_scene_batch_destroy(pvq_scene_batch* b) {
+    try {
+        delete b;
+    } catch (...) { (void)translate_exception(); }
+}
+uint32_t pvq_scene_batch_n_segments(const pvq_scene_batch* b) { return b ? b->impl->n_segments() : 0; }
+pvq_status pvq_scene_batch_frames_device(pvq_scene_batch* b, size_t n_frames, const pvq_scene_inputs* in, uint64_t frame_time_ns,
+                                         const uint64_t* frame_times_ns, const pvq_scene_outputs* outs, void* stream) {
+    try {
+        if (!b) return null_handle();
+        const pvq_scene_inputs no_in{};
+        const pvq_scene_outputs none{};
+        return b->impl->frames_device(n_frames, in ? *in : no_in, frame_time_ns, frame_times_ns, outs ? *outs : none,
+                                      static_cast<hipStream_t>(stream));
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_scene_batch_get_state(pvq_scene_batch* b, uint32_t stream_index, float* ball_xyzs, float* ball_rgba, float* ball_params,
+                                     uint32_t* ball_visible, uint32_t* bass_lit, float* bass_rgba, float* bloom) {
+    try {
+        if (!b) return null_handle();
+        return b->impl->get_state(stream_index, ball_xyzs, ball_rgba, ball_params, ball_visible, bass_lit, bass_rgba, bloom);
     } catch (...) { return translate_exception(); }
 }
 

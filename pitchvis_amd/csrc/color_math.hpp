@@ -34,14 +34,23 @@ constexpr float E_0_255 = 3294.6f * S_0;
 constexpr float WHITE_X = 0.9504492182750991f;
 constexpr float WHITE_Z = 1.0889166484304715f;
 
+// Which powf / cosf / sinf the conversions below call: the build's libm by default.  A caller that needs host and device to agree
+// beyond libm (scene_math.hpp) passes its own.
+struct LibmF32 {
+    static PVQ_HD float pow(float x, float y) { return powf(x, y); }
+    static PVQ_HD float cos(float x) { return cosf(x); }
+    static PVQ_HD float sin(float x) { return sinf(x); }
+};
+
 PVQ_HD float srgb_expand(float c) {   // c in 0..255
     PVQ_FP_STRICT
     if (c > E_0_255) return powf((c + 0.055f * 255.0f) / (1.055f * 255.0f), 2.4f);
     return c / (12.92f * 255.0f);
 }
+template <class M = LibmF32>
 PVQ_HD float srgb_compress(float c) {
     PVQ_FP_STRICT
-    const float v = (c > S_0) ? 1.055f * powf(c, 1.0f / 2.4f) - 0.055f : 12.92f * c;
+    const float v = (c > S_0) ? 1.055f * M::pow(c, 1.0f / 2.4f) - 0.055f : 12.92f * c;
     return fmaxf(fminf(v, 1.0f), 0.0f);
 }
 PVQ_HD float lab_map(float c) {
@@ -62,9 +71,10 @@ PVQ_HD void rgb_to_lch(const uint8_t rgb[3], float& l, float& c, float& h) {
     c = hypotf(a, bb);
     h = atan2f(bb, a);
 }
+template <class M = LibmF32>
 PVQ_HD void lch_to_rgb(float l, float c, float h, uint8_t rgb[3]) {
     PVQ_FP_STRICT
-    const float a = c * cosf(h), bb = c * sinf(h);
+    const float a = c * M::cos(h), bb = c * M::sin(h);
     const float fy = (l + 16.0f) / 116.0f;
     const float fx = (a / 500.0f) + fy;
     const float fz = fy - (bb / 200.0f);
@@ -75,9 +85,9 @@ PVQ_HD void lch_to_rgb(float l, float c, float h, uint8_t rgb[3]) {
     const float r = x * 3.240812398895283f - y * 1.5373084456298136f - z * 0.4985865229069666f;
     const float g = x * -0.9692430170086407f + y * 1.8759663029085742f + z * 0.04155503085668564f;
     const float b = x * 0.055638398436112804f - y * 0.20400746093241362f + z * 1.0571295702861434f;
-    rgb[0] = static_cast<uint8_t>(roundf(srgb_compress(r) * 255.0f));
-    rgb[1] = static_cast<uint8_t>(roundf(srgb_compress(g) * 255.0f));
-    rgb[2] = static_cast<uint8_t>(roundf(srgb_compress(b) * 255.0f));
+    rgb[0] = static_cast<uint8_t>(roundf(srgb_compress<M>(r) * 255.0f));
+    rgb[1] = static_cast<uint8_t>(roundf(srgb_compress<M>(g) * 255.0f));
+    rgb[2] = static_cast<uint8_t>(roundf(srgb_compress<M>(b) * 255.0f));
 }
 PVQ_HD uint8_t sat_u8(float v) {   // Rust `as u8`: saturating, NaN -> 0, truncation toward zero
     if (!(v > 0.0f)) return 0;
@@ -98,12 +108,13 @@ PVQ_HD void tone_of_bucket(uint32_t buckets_per_octave, float bucket, uint32_t& 
     inaccuracy_cents = fabsf(pitch_continuous - rounded);                                      // lib.rs:96
 }
 // lib.rs:98-108 from the tone's (L, C, h) (lib.rs:98: rgb_to_lch of the palette entry as u8)
+template <class M = LibmF32>
 PVQ_HD void lch_color_u8(float l, float c, float h, float inaccuracy_cents, float gray_level, float easing_pow, uint8_t rgb[3]) {
     PVQ_FP_STRICT
-    const float saturation = 1.0f - powf(2.0f * inaccuracy_cents, easing_pow);   // lib.rs:104
+    const float saturation = 1.0f - M::pow(2.0f * inaccuracy_cents, easing_pow);   // lib.rs:104
     c *= saturation;                                                              // lib.rs:105
     l = saturation * l + (1.0f - saturation) * gray_level;                        // lib.rs:106
-    lch_to_rgb(l, c, h, rgb);                                                     // lib.rs:108
+    lch_to_rgb<M>(l, c, h, rgb);                                                  // lib.rs:108
 }
 
 // update.rs:998-1001 / :1053-1059: `(x * 255.0 * 1.2).clamp(0.0, 255.0) as u8`
