@@ -93,14 +93,24 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void scene_peaks(Scene
         if (cnt == 0u) continue;   // update.rs:85-87: scene_frames never reads this row's records or header
         const float* c_row = a.center + g * a.max_peaks;
         const float* z_row = a.size + g * a.max_peaks;
-        float best = scene::F32_MIN;   // util::arg_max (util.rs:48-57); only the value is used
+        // util::arg_max (util.rs:48-57): the FIRST maximum.  Its value is all that is used, but with both signs of zero in the list
+        // the first one's sign is the value: every lane carries (value, list index) and ends with the same pair
+        float best = scene::F32_MIN;
+        uint32_t best_at = 0xFFFFFFFFu;
         for (uint32_t p = lane; p < cnt; p += 64) {
             const float v = z_row[p];
-            if (v > best) best = v;
+            if (v > best) {
+                best = v;
+                best_at = p;
+            }
         }
         for (int o = 32; o; o >>= 1) {
             const float other = __shfl_xor(best, o);
-            best = other > best ? other : best;
+            const uint32_t other_at = __shfl_xor(best_at, o);
+            if (other > best || (!(other < best) && other_at < best_at)) {   // (a NaN never gets into `best`)
+                best = other;
+                best_at = other_at;
+            }
         }
         const float max_size = best > scene::F32_MIN ? best : z_row[0];
         const size_t bins = g * static_cast<size_t>(a.n_bins);

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import pitchvis_amd as P
+import scene_cases as SC
 import scene_model as M
 from pitchvis_amd import _lib
 from pitchvis_amd import scene as PS
@@ -221,7 +222,7 @@ def test_hide_range_at_bpo_84(who):
 
 
 # ---- host against model -------------------------------------------------------------------------------------------------------
-def run_both(octaves, bpo, frames, dts=None, **kw):
+def run_both(octaves, bpo, frames, dts=None, also=None, **kw):
     host = P.SceneState(P.VqtRange(55.0, octaves, bpo), **kw)
     model = M.SceneModel(octaves, bpo, kw.get("visuals_mode", 0), kw.get("enable_bloom", True))
     worst = 0.0
@@ -230,6 +231,8 @@ def run_both(octaves, bpo, frames, dts=None, **kw):
         host.update(pk, calm, acc, dev, scene, dt)
         model.update(pk, calm, acc, dev, scene, dt)
         worst = max(worst, M.compare(host.get(), model.get(), CHROMA_REL))
+        if also is not None:
+            also(host.get(), model.get())
     return worst, host, model
 
 
@@ -273,3 +276,100 @@ def test_host_matches_model_on_crafted_frames(geom, seed):
         after = e.get()
         assert after["bass_lit"] == before["bass_lit"] and after["bloom"] == before["bloom"]
         assert np.array_equal(after["ball_params"], before["ball_params"]) and after["ball_xyzs"][m + 2, 3] < before["ball_xyzs"][m + 2, 3]
+
+
+# ---- the cases of tests/scene_cases.py: edge geometries, long lists, hide ranges, odd entries, frame times ---------------------------
+def model_accepts(frame, octaves, bpo):
+    try:
+        M.SceneModel(octaves, bpo).update(*frame[1:], DT)
+        return True
+    except ValueError:
+        return False
+
+
+@pytest.mark.parametrize("geom", SC.GEOMS_EDGE)
+def test_host_matches_model_on_edge_cases(geom):
+    """the crafted frames, the long lists, the hide cases, the odd entries and the odd fields in one walk; a list the model refuses
+    (a NaN centre) is left out of the walk and held on the host alone by test_nan_centre_on_the_host"""
+    octaves, bpo = geom
+    n = octaves * bpo
+    cases = M.crafted_frames(n, bpo, 50 + n) + SC.long_lists(n, bpo, 60 + n)
+    for hc in SC.hide_cases(octaves, bpo):
+        cases += hc[1]
+    cases += SC.edge_entries(n) + SC.edge_fields(n)
+    refused = [c[0] for c in cases if "nan_centre" in c[0] and not model_accepts(c, octaves, bpo)]
+    frames = [c[1:] for c in cases if c[0] not in refused]
+    assert len(frames) >= len(cases) - 2 and max(len(f[0]) for f in frames) == 200
+    worst, _, _ = run_both(octaves, bpo, frames, dts=[DT if i % 3 else 16_666_667 for i in range(len(frames))],
+                           also=lambda g, w: SC.close_with_specials(g, w, CHROMA_REL))
+    print(f"{octaves} x {bpo}: host vs model over {len(frames)} edge frames ({len(refused)} refused): max |d| / max(1, |want|) = {worst:.2e}")
+
+
+@pytest.mark.parametrize("geom", [(1, 1024), (7, 9), (1, 12), (1, 11), (5, 13), (11, 93)])
+@pytest.mark.parametrize("who", ["host", "model"])
+def test_hide_known_answers(who, geom):
+    octaves, bpo = geom
+    cases = SC.hide_cases(octaves, bpo)
+    assert len(cases) == len(SC.HIDE_TABLE.get(geom, [0]))
+    for case in cases:
+        s = P.SceneState(P.VqtRange(55.0, octaves, bpo)) if who == "host" else M.SceneModel(octaves, bpo)
+        for fr in case[1]:
+            s.update(*fr[1:], DT)
+        SC.hide_holds(s.get(), case)
+
+
+@pytest.mark.parametrize("who", ["host", "model"])
+def test_long_lists_honour_list_order(who):
+    """the builder's own check, on both faces: a long list and its reversal leave different balls, and key A of the list — entered
+    in chunk 0 only — carries its LAST entry (index 40), not an earlier one"""
+    octaves, bpo, n = 7, 36, 252
+    for fr in SC.long_lists(n, bpo, 5):
+        pk = fr[1]
+        a = int(pk[40][0])
+        first = next(i for i, (c, _) in enumerate(pk) if int(c) == a)
+        assert first <= 3 and int(pk[3][0]) == a and all(int(c) != a for c, _ in pk[41:])
+        got = []
+        for lst in (pk, pk[::-1]):
+            s = P.SceneState(P.VqtRange(55.0, octaves, bpo)) if who == "host" else M.SceneModel(octaves, bpo)
+            s.update(lst, *fr[2:], DT)
+            got.append(s.get())
+        assert not np.array_equal(SC.balls(got[0]), SC.balls(got[1]), equal_nan=True), fr[0]
+        big = max(z for _, z in pk)
+        want = lambda z: f32(f32(f32(f32(z) / f32(big)) - f32(1.01)) * f32(12.5))           # update.rs:233
+        assert got[0]["ball_xyzs"][a, 2] == want(pk[40][1]) and got[1]["ball_xyzs"][a, 2] == want(pk[first][1]), fr[0]
+
+
+def test_nan_centre_on_the_host():
+    """what the reference text gives for a NaN centre: trunc(NaN) as usize is 0 (update.rs:211), so the entry lands on ball 0, whose
+    x and y become NaN (util.rs:9-20); every other ball is as without the entry"""
+    n = 252
+    named = {c[0]: c for c in SC.edge_entries(n)}
+    for name in ("nan_centre", "nan_centre_first"):
+        fr = named[name]
+        with_nan, without = P.SceneState(P.VqtRange(55.0, 7, 36)), P.SceneState(P.VqtRange(55.0, 7, 36))
+        with_nan.update(*fr[1:], DT)
+        without.update([p for p in fr[1] if p[0] == p[0]], *fr[2:], DT)
+        g, w = with_nan.get(), without.get()
+        size = next(z for c, z in fr[1] if c != c)
+        assert np.isnan(g["ball_xyzs"][0, 0]) and np.isnan(g["ball_xyzs"][0, 1])
+        assert g["ball_xyzs"][0, 3] == f32(f32(f32(size) * M.F) * f32(f32(1.0) + f32(f32(0.2) * g["ball_params"][0, 0])))
+        assert np.array_equal(g["ball_xyzs"][1:, :2], w["ball_xyzs"][1:, :2]) and np.array_equal(g["ball_rgba"][1:, :3], w["ball_rgba"][1:, :3])
+        assert g["bass_lit"] == (0 if name == "nan_centre_first" else w["bass_lit"])     # round(NaN) as usize is 0 segments
+
+
+@pytest.mark.parametrize("geom", [(7, 36), (1, 3)])
+def test_frame_times_at_the_edges(geom):
+    """Duration::as_secs_f32 at 0 ns, 1 ns, 1 s, 5 s + 7 ns and 2^40 ns: host against model, and the split itself"""
+    octaves, bpo = geom
+    n = octaves * bpo
+    assert M.secs_f32(5_000_000_007) == f32(f32(5.0) + f32(f32(7.0) / f32(1e9))) and M.secs_f32(2 ** 40) == f32(f32(1099.0) + f32(f32(511627776.0) / f32(1e9)))
+    frames = [c[1:] for c in SC.plain_frames(n, 3 * len(SC.FRAME_TIMES_NS), 17)]
+    dts = [SC.FRAME_TIMES_NS[i // 3] if i % 3 == 1 else DT for i in range(len(frames))]
+    worst, host, _ = run_both(octaves, bpo, frames, dts=dts)
+    print(f"{n} bins: host vs model over frame times {SC.FRAME_TIMES_NS}: max |d| / max(1, |want|) = {worst:.2e}")
+    s = P.SceneState(P.VqtRange(55.0, octaves, bpo))
+    before = s.get()
+    s.update([], *zeros(n), 0.0, 0)                                                       # 0 ns: dropoff x^0 = 1, z step 0
+    after = s.get()
+    for k in ("ball_xyzs", "ball_rgba"):
+        assert np.array_equal(before[k], after[k]), k
