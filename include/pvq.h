@@ -564,7 +564,7 @@ pvq_status pvq_render_batch_rows_device(pvq_render_batch *r, size_t n_rows, cons
  *     in one colour: calculate_color at (round(c) * bpo / 12 + (bpo - 3 (bpo / 12))) % bpo with alpha 1 - (1 - size / max_size)^2 — a
  *     Color, not converted to linear.  The visible state is (lit count, rgba); rgba keeps its last value while nothing is lit.
  * Left out: the `ml` branch (update.rs:247-255; it reads an AnalysisState field that no longer exists), params.time (the caller's
- * clock), the debug meshes (update_spectrum, the calmness histogram and graph).
+ * clock).  The debug meshes (update_spectrum, the calmness histogram and graph) are the panels stage below.
  * Every libm call of steps 3 and 5 is the double-precision function rounded once to f32, on the host and on the device (DESIGN.md
  * 6c); the fade's powf is the host's, also for the device stage. */
 typedef enum pvq_visuals_mode { PVQ_VISUALS_FULL = 0, PVQ_VISUALS_ZEN = 1, PVQ_VISUALS_PERFORMANCE = 2, PVQ_VISUALS_GALAXY = 3 } pvq_visuals_mode;
@@ -636,6 +636,87 @@ pvq_status pvq_scene_batch_frames_device(pvq_scene_batch *b, size_t n_frames, co
 /* the state of one stream after the last call (synchronises), laid out as pvq_scene_state_get */
 pvq_status pvq_scene_batch_get_state(pvq_scene_batch *b, uint32_t stream_index, float *ball_xyzs, float *ball_rgba,
                                      float *ball_params, uint32_t *ball_visible, uint32_t *bass_lit, float *bass_rgba, float *bloom);
+
+/* ---- the viewer's debug panels: spectrum line with peak discs, calmness histogram, scene calmness graph ------
+ * The three meshes of DisplayMode::Debugging (pitchvis_viewer/src/display_system/update.rs:474-869), the last part of update_display
+ * the stages above leave out.  A mesh is positions [vertices][3] (z = 0) and colours [vertices][4]; indices, UVs and the normal
+ * (0, 0, 1) of every vertex depend on the counts alone: pvq_panel_topology.  The reference's transforms (the histogram's y flip, the
+ * placement relative to the camera), the visibility toggles and the concatenation of line and discs into one mesh stay with the caller.
+ *
+ * Thick-line quad of a segment (p, q) with thickness t (update.rs:531-541, :691-700, :815-827): dx = p.x - q.x, dy = p.y - q.y,
+ * l = dx.hypot(dy), u = dx * t * 0.5 / l, v = dy * t * 0.5 / l; v0 = (p.x + v, p.y - u), v1 = (p.x - v, p.y + u), v2 = (q.x - v,
+ * q.y + u), v3 = (q.x + v, q.y - u).  hypot is the double-precision function rounded once to f32.
+ *  - Spectrum line (update.rs:506-579), t = 0.02: point i = (i * 0.011, x[i] / 10), n - 1 segments; the four vertices of segment i
+ *    carry [r, g, b, 1 - (0.5 - x[i] / max / 2).powf(0.5)] with max = x[util::arg_max(x)] (the first maximum) and (r, g, b) =
+ *    calculate_color(bpo, (i + 0.5 + (bpo - 3 (bpo / 12))) % bpo, colors, gray_level, 10.0); powf(0.5) is the correctly rounded sqrt.
+ *  - Peak discs (update.rs:582-615, :435-471), one per entry of peaks_continuous in list order: 13 vertices, the centre (center *
+ *    0.011, size / 10), then (cx + 0.08 cos a_i, cy + 0.08 sin a_i) with a_i = (i / 12) * TAU; all carry [r, g, b, 0.9], the colour
+ *    above at bucket (center.round() as usize) % bpo.
+ *  - Calmness histogram (update.rs:787-845), t = 0.01: p = (i * 0.011, c[i] * 0.5), q = ((i + 1) * 0.011, c[i + 1] * 0.5); colour by
+ *    (c[i] + c[i + 1]) / 2: > 0.7 (0.5, 0.8, 1.0, 1.0), > 0.3 (1.0, 1.0, 0.5, 1.0), else (1.0, 0.5, 0.5, 1.0).  Always n - 1 quads:
+ *    the reference's `l < 0.0001` skip cannot fire at a point spacing of 0.011.
+ *  - Scene calmness graph (update.rs:652-718), t = 0.01, capacity C (300 in the viewer): after pushing the frame's value, point i =
+ *    (i / C - 0.5, h[i]) with h the last C pushed values, oldest first, zeros where nothing was pushed; C - 1 segments, segment i
+ *    coloured by the class of h[i]. */
+
+/* One stream on the host.  colors: 12 RGB triples in [0, 1].  Any output may be NULL.  line_pos [4 (n - 1)][3], line_rgba
+ * [4 (n - 1)][4], disc_pos [n_peaks][13][3], disc_rgba [n_peaks][13][4].  PVQ_ERR_INVALID_ARG for n_buckets < 2,
+ * buckets_per_octave == 0, colors NULL or a requested output whose input is missing. */
+pvq_status pvq_spectrum_mesh(uint32_t n_buckets, uint16_t buckets_per_octave, const float *x_vqt_smoothed, const float *center,
+                             const float *size, uint32_t n_peaks, const float *colors, float gray_level, float *line_pos,
+                             float *line_rgba, float *disc_pos, float *disc_rgba);
+/* pos [4 (n - 1)][3], rgba [4 (n - 1)][4]; either may be NULL */
+pvq_status pvq_calmness_histogram_mesh(uint32_t n_buckets, const float *calmness, float *pos, float *rgba);
+/* the graph and its history ring (SceneCalmnessHistory, mod.rs:114-133).  capacity 2 .. 1024, 0: 300 */
+typedef struct pvq_calmness_graph pvq_calmness_graph;
+pvq_status pvq_calmness_graph_create(uint32_t capacity, pvq_calmness_graph **out);
+void pvq_calmness_graph_destroy(pvq_calmness_graph *g);
+uint32_t pvq_calmness_graph_capacity(const pvq_calmness_graph *g);
+pvq_status pvq_calmness_graph_push(pvq_calmness_graph *g, float value);
+/* pos [4 (C - 1)][3], rgba [4 (C - 1)][4], history [C] (oldest first); any may be NULL */
+pvq_status pvq_calmness_graph_mesh(const pvq_calmness_graph *g, float *pos, float *rgba, float *history);
+/* n_quads quads followed by n_circles discs: indices [6 n_quads + 36 n_circles] (a quad with base b: b+2, b+1, b, b+2, b, b+3; a
+ * disc with base b: triangles (b, b+1+i, b+1+(i+1)%12)), uvs [4 n_quads + 13 n_circles][2] ((0,1), (0,0), (1,0), (1,1) per quad;
+ * (0.5, 0.5), then (0.5 + 0.5 cos a_i, 0.5 + 0.5 sin a_i) per disc).  Either may be NULL. */
+pvq_status pvq_panel_topology(uint32_t n_quads, uint32_t n_circles, uint32_t *indices, float *uvs);
+
+/* The same for MANY streams on the GPU, from the arrays pvq_analysis_batch_outputs describes.  The device evaluates only IEEE + - * /
+ * and sqrt on the host's inputs and tables: every output carries the bits of the host functions above. */
+typedef struct pvq_panels_batch pvq_panels_batch;
+/* per-row results, DEVICE pointers, any may be NULL.  Line and disc parts are separate arrays (the caller draws both, the disc
+ * indices offset), so a row's line part stays a multiple of 16 bytes. */
+typedef struct pvq_panels_outputs {
+    float *line_pos;    /* [n_rows][4 (n_bins - 1)][3]; 16-byte aligned */
+    float *line_rgba;   /* [n_rows][4 (n_bins - 1)][4]; 16-byte aligned */
+    float *disc_pos;    /* [n_rows][max_peaks][13][3]; slots beyond a row's count are zeros (degenerate triangles) */
+    float *disc_rgba;   /* [n_rows][max_peaks][13][4]; likewise */
+    float *hist_pos;    /* [n_rows][4 (n_bins - 1)][3]; 16-byte aligned */
+    float *hist_rgba;   /* [n_rows][4 (n_bins - 1)][4]; 16-byte aligned */
+} pvq_panels_outputs;
+/* One geometry, one palette (colors NULL: pitchvis_colors::COLORS), n_streams graph histories of graph_capacity values (2 .. 1024,
+ * 0: 300), all zeros.  The arguments are checked before any device is touched; takes the bin counts pvq_analysis_batch_create takes,
+ * 3 .. 1024 (PVQ_ERR_UNSUPPORTED beyond); device_id < 0: a host-only handle whose device calls return PVQ_ERR_NO_DEVICE after their
+ * argument checks. */
+pvq_status pvq_panels_batch_create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, const float *colors, float gray_level,
+                                   uint32_t n_streams, uint32_t graph_capacity, pvq_panels_batch **out);
+void pvq_panels_batch_destroy(pvq_panels_batch *b);
+uint32_t pvq_panels_batch_graph_capacity(const pvq_panels_batch *b);
+/* Spectrum and histogram meshes of n_rows rows (n_streams * n_frames, flattened as for pvq_render_batch_rows_device); stateless.
+ * d_x_vqt_smoothed / d_calmness [n_rows][n_bins]; d_center / d_size [n_rows][max_peaks] with d_peak_count [n_rows] (a count above
+ * max_peaks is taken as max_peaks; list entries beyond a row's count are never read).  Inputs an output does not read may be NULL;
+ * PVQ_ERR_INVALID_ARG for a requested output whose inputs are missing or that is misaligned, before anything is launched.
+ * Asynchronous on `stream`; calls on several streams may overlap. */
+pvq_status pvq_panels_batch_rows_device(pvq_panels_batch *b, size_t n_rows, const float *d_x_vqt_smoothed, const float *d_center,
+                                        const float *d_size, const uint32_t *d_peak_count, uint32_t max_peaks,
+                                        const float *d_calmness, const pvq_panels_outputs *outs, void *stream);
+/* The graph: stateful, the handle keeps every stream's last C values between calls.  d_scene_calmness [n_streams][n_frames]; every
+ * stream's history advances by all n_frames values; meshes are written for frames first_emitted .. n_frames - 1 only (a viewer
+ * draws the newest): graph_pos [n_streams][n_frames - first_emitted][4 (C - 1)][3], graph_rgba [..][..][4 (C - 1)][4], 16-byte
+ * aligned, either may be NULL.  Asynchronous on `stream`; one handle's calls are stream-ordered. */
+pvq_status pvq_panels_batch_graph_device(pvq_panels_batch *b, size_t n_frames, const float *d_scene_calmness, size_t first_emitted,
+                                         float *graph_pos, float *graph_rgba, void *stream);
+/* one stream's history after the last call, oldest first, out [C] (synchronises) */
+pvq_status pvq_panels_batch_get_history(pvq_panels_batch *b, uint32_t stream_index, float *out);
 
 /* The note model the dataset of pitchvis_train exists for (pitchvis_train/train.py:67-99), which the viewer runs per rendered frame
  * through TorchScript on a CUDA device (pitchvis_viewer/src/ml_system.rs:24-69): a window of t_frames consecutive dB frames,

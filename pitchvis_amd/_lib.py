@@ -39,6 +39,9 @@ EXPORTS = [
     "pvq_scene_default_settings", "pvq_scene_state_create", "pvq_scene_state_destroy", "pvq_scene_state_n_bins", "pvq_scene_state_n_segments",
     "pvq_scene_state_update", "pvq_scene_state_get", "pvq_scene_batch_create", "pvq_scene_batch_destroy", "pvq_scene_batch_n_segments",
     "pvq_scene_batch_frames_device", "pvq_scene_batch_get_state",
+    "pvq_spectrum_mesh", "pvq_calmness_histogram_mesh", "pvq_calmness_graph_create", "pvq_calmness_graph_destroy", "pvq_calmness_graph_capacity",
+    "pvq_calmness_graph_push", "pvq_calmness_graph_mesh", "pvq_panel_topology", "pvq_panels_batch_create", "pvq_panels_batch_destroy",
+    "pvq_panels_batch_graph_capacity", "pvq_panels_batch_rows_device", "pvq_panels_batch_graph_device", "pvq_panels_batch_get_history",
     "pvq_note_model_create", "pvq_note_model_destroy", "pvq_note_model_sizes", "pvq_note_model_infer", "pvq_note_model_rows_device",
     "pvq_note_model_set_workspace_limit",
     "pvq_note_trainer_hyper_default", "pvq_note_trainer_create", "pvq_note_trainer_destroy", "pvq_note_trainer_step", "pvq_note_trainer_steps",
@@ -112,6 +115,10 @@ class CSceneInputs(C.Structure):   # pvq_scene_inputs (device pointers)
 
 class CSceneOutputs(C.Structure):   # pvq_scene_outputs (device pointers)
     _fields_ = [(n, C.c_void_p) for n in ("ball_xyzs", "ball_rgba", "ball_params", "ball_visible", "bass_lit", "bass_rgba", "bloom")]
+
+
+class CPanelsOutputs(C.Structure):   # pvq_panels_outputs (device pointers)
+    _fields_ = [(n, C.c_void_p) for n in ("line_pos", "line_rgba", "disc_pos", "disc_rgba", "hist_pos", "hist_rgba")]
 
 
 class CNoteModelParams(C.Structure):   # pvq_note_model_params
@@ -309,6 +316,22 @@ def load():
     L.pvq_scene_batch_frames_device.argtypes = [vp, C.c_size_t, C.POINTER(CSceneInputs), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(CSceneOutputs), vp]
     L.pvq_scene_batch_frames_device.restype = C.c_int
     L.pvq_scene_batch_get_state.argtypes = [vp, C.c_uint32, fp, fp, fp, up, up, fp, fp]; L.pvq_scene_batch_get_state.restype = C.c_int
+    L.pvq_spectrum_mesh.argtypes = [C.c_uint32, C.c_uint16, fp, fp, fp, C.c_uint32, fp, C.c_float, fp, fp, fp, fp]; L.pvq_spectrum_mesh.restype = C.c_int
+    L.pvq_calmness_histogram_mesh.argtypes = [C.c_uint32, fp, fp, fp]; L.pvq_calmness_histogram_mesh.restype = C.c_int
+    L.pvq_calmness_graph_create.argtypes = [C.c_uint32, C.POINTER(vp)]; L.pvq_calmness_graph_create.restype = C.c_int
+    L.pvq_calmness_graph_destroy.argtypes = [vp]; L.pvq_calmness_graph_destroy.restype = None
+    L.pvq_calmness_graph_capacity.argtypes = [vp]; L.pvq_calmness_graph_capacity.restype = C.c_uint32
+    L.pvq_calmness_graph_push.argtypes = [vp, C.c_float]; L.pvq_calmness_graph_push.restype = C.c_int
+    L.pvq_calmness_graph_mesh.argtypes = [vp, fp, fp, fp]; L.pvq_calmness_graph_mesh.restype = C.c_int
+    L.pvq_panel_topology.argtypes = [C.c_uint32, C.c_uint32, up, fp]; L.pvq_panel_topology.restype = C.c_int
+    L.pvq_panels_batch_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, fp, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.pvq_panels_batch_create.restype = C.c_int
+    L.pvq_panels_batch_destroy.argtypes = [vp]; L.pvq_panels_batch_destroy.restype = None
+    L.pvq_panels_batch_graph_capacity.argtypes = [vp]; L.pvq_panels_batch_graph_capacity.restype = C.c_uint32
+    L.pvq_panels_batch_rows_device.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, C.c_uint32, vp, C.POINTER(CPanelsOutputs), vp]
+    L.pvq_panels_batch_rows_device.restype = C.c_int
+    L.pvq_panels_batch_graph_device.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp]; L.pvq_panels_batch_graph_device.restype = C.c_int
+    L.pvq_panels_batch_get_history.argtypes = [vp, C.c_uint32, fp]; L.pvq_panels_batch_get_history.restype = C.c_int
     L.pvq_note_model_create.argtypes = [C.c_int, C.POINTER(CNoteModelParams), C.POINTER(CNoteModelWeights), C.POINTER(vp)]
     L.pvq_note_model_create.restype = C.c_int
     L.pvq_note_model_destroy.argtypes = [vp]

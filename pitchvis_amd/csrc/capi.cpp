@@ -17,6 +17,8 @@
 #include "multi_host.hpp"
 #include "note_model.hpp"
 #include "note_trainer.hpp"
+#include "panels_batch.hpp"
+#include "panels_host.hpp"
 #include "render_batch.hpp"
 #include "scene_batch.hpp"
 #include "scene_host.hpp"
@@ -45,6 +47,12 @@ struct pvq_scene_state {
 };
 struct pvq_scene_batch {
     std::unique_ptr<pvq::SceneBatch> impl;
+};
+struct pvq_calmness_graph {
+    pvq::CalmnessGraph impl;
+};
+struct pvq_panels_batch {
+    std::unique_ptr<pvq::PanelsBatch> impl;
 };
 struct pvq_note_model {
     std::unique_ptr<pvq::NoteModel> impl;
@@ -1210,6 +1218,125 @@ pvq_status pvq_scene_batch_get_state(pvq_scene_batch* b, uint32_t stream_index, 
     try {
         if (!b) return null_handle();
         return b->impl->get_state(stream_index, ball_xyzs, ball_rgba, ball_params, ball_visible, bass_lit, bass_rgba, bloom);
+    } catch (...) { return translate_exception(); }
+}
+
+// pitchvis_viewer/src/display_system/update.rs:474-869: the debug panels, one stream on the host (panels_host.hpp) and many on the
+// device (panels_batch.hpp)
+pvq_status pvq_spectrum_mesh(uint32_t n_buckets, uint16_t buckets_per_octave, const float* x_vqt_smoothed, const float* center, const float* size,
+                             uint32_t n_peaks, const float* colors, float gray_level, float* line_pos, float* line_rgba, float* disc_pos,
+                             float* disc_rgba) {
+    try {
+        if (n_buckets < 2 || buckets_per_octave == 0 || !colors) {
+            pvq::set_last_error("spectrum mesh: n_buckets < 2, buckets_per_octave == 0 or no colors");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        if (((line_pos || line_rgba) && !x_vqt_smoothed) || ((disc_pos || disc_rgba) && n_peaks && (!center || !size))) {
+            pvq::set_last_error("spectrum mesh: the line reads x_vqt_smoothed, the discs read center and size");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        std::vector<float> rgb(3 * static_cast<size_t>(buckets_per_octave));
+        float cs[24];
+        pvq::panel_color_table(buckets_per_octave, colors, gray_level, rgb.data());
+        pvq::panel_disc_table(cs);
+        pvq::spectrum_mesh(n_buckets, buckets_per_octave, x_vqt_smoothed, center, size, n_peaks, rgb.data(), cs, line_pos, line_rgba, disc_pos,
+                           disc_rgba);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_calmness_histogram_mesh(uint32_t n_buckets, const float* calmness, float* pos, float* rgba) {
+    try {
+        if (n_buckets < 2 || !calmness) {
+            pvq::set_last_error("calmness histogram: n_buckets < 2 or no calmness");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        pvq::calmness_histogram_mesh(n_buckets, calmness, pos, rgba);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_calmness_graph_create(uint32_t capacity, pvq_calmness_graph** out) {
+    try {
+        if (!out) return null_handle();
+        *out = nullptr;
+        const uint32_t cap = capacity ? capacity : pvq::panels::DEFAULT_GRAPH_CAPACITY;
+        if (cap < 2 || cap > 1024) {
+            pvq::set_last_error("calmness graph: capacity must be 2 .. 1024 (0: 300)");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        *out = new pvq_calmness_graph{pvq::CalmnessGraph(cap)};
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+void pvq_calmness_graph_destroy(pvq_calmness_graph* g) {
+    try {
+        delete g;
+    } catch (...) { (void)translate_exception(); }
+}
+uint32_t pvq_calmness_graph_capacity(const pvq_calmness_graph* g) { return g ? g->impl.capacity() : 0; }
+pvq_status pvq_calmness_graph_push(pvq_calmness_graph* g, float value) {
+    try {
+        if (!g) return null_handle();
+        g->impl.push(value);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_calmness_graph_mesh(const pvq_calmness_graph* g, float* pos, float* rgba, float* history) {
+    try {
+        if (!g) return null_handle();
+        g->impl.mesh(pos, rgba);
+        if (history) g->impl.history(history);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_panel_topology(uint32_t n_quads, uint32_t n_circles, uint32_t* indices, float* uvs) {
+    try {
+        if (4ull * n_quads + 13ull * n_circles > 0xFFFFFFFFull) {
+            pvq::set_last_error("panel topology: the vertex count does not fit a u32 index");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        pvq::panel_topology(n_quads, n_circles, indices, uvs);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_panels_batch_create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, const float* colors, float gray_level,
+                                   uint32_t n_streams, uint32_t graph_capacity, pvq_panels_batch** out) {
+    try {
+        if (!out) return null_handle();
+        *out = nullptr;
+        std::unique_ptr<pvq::PanelsBatch> impl;
+        const pvq_status st = pvq::PanelsBatch::create(device_id, octaves, buckets_per_octave, colors, gray_level, n_streams, graph_capacity, impl);
+        if (st != PVQ_OK) return st;
+        *out = new pvq_panels_batch{std::move(impl)};
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+void pvq_panels_batch_destroy(pvq_panels_batch* b) {
+    try {
+        delete b;
+    } catch (...) { (void)translate_exception(); }
+}
+uint32_t pvq_panels_batch_graph_capacity(const pvq_panels_batch* b) { return b ? b->impl->graph_capacity() : 0; }
+pvq_status pvq_panels_batch_rows_device(pvq_panels_batch* b, size_t n_rows, const float* d_x_vqt_smoothed, const float* d_center,
+                                        const float* d_size, const uint32_t* d_peak_count, uint32_t max_peaks, const float* d_calmness,
+                                        const pvq_panels_outputs* outs, void* stream) {
+    try {
+        if (!b) return null_handle();
+        const pvq_panels_outputs none{};
+        return b->impl->rows_device(n_rows, d_x_vqt_smoothed, d_center, d_size, d_peak_count, max_peaks, d_calmness, outs ? *outs : none,
+                                    static_cast<hipStream_t>(stream));
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_panels_batch_graph_device(pvq_panels_batch* b, size_t n_frames, const float* d_scene_calmness, size_t first_emitted,
+                                         float* graph_pos, float* graph_rgba, void* stream) {
+    try {
+        if (!b) return null_handle();
+        return b->impl->graph_device(n_frames, d_scene_calmness, first_emitted, graph_pos, graph_rgba, static_cast<hipStream_t>(stream));
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_panels_batch_get_history(pvq_panels_batch* b, uint32_t stream_index, float* out) {
+    try {
+        if (!b) return null_handle();
+        return b->impl->get_history(stream_index, out);
     } catch (...) { return translate_exception(); }
 }
 

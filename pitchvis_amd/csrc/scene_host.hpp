@@ -13,7 +13,7 @@
 // Bloom intensity starts at 0 here; the reference leaves Bevy's default on the camera until the first frame with peaks.
 // A peak whose trunc(center) is >= n_bins is ignored (the reference would index out of range); it still counts for max_size.
 // Left out: the `ml` branch (update.rs:247-255: it reads an AnalysisState field that no longer exists), params.time (the caller's
-// clock) and the debug meshes (update_spectrum, the calmness histogram and graph).
+// clock).  The debug meshes (update_spectrum, the calmness histogram and graph) are panels_host.hpp's.
 #pragma once
 
 #include <cstdint>
