@@ -637,6 +637,78 @@ pvq_status pvq_scene_batch_frames_device(pvq_scene_batch *b, size_t n_frames, co
 pvq_status pvq_scene_batch_get_state(pvq_scene_batch *b, uint32_t stream_index, float *ball_xyzs, float *ball_rgba,
                                      float *ball_params, uint32_t *ball_visible, uint32_t *bass_lit, float *bass_rgba, float *bloom);
 
+/* ---- the pitch balls as pixels: the ball material's fragment, z-order, alpha blend -------------------------------
+ * What the viewer's renderer makes of the ball records the scene stage above produces — the last data-parallel piece of its
+ * per-frame work.  Restated from behaviour, all of it f32 without FMA contraction, components left to right; sin, cos and atan2
+ * are the double-precision functions rounded once to f32, sqrt and `/` IEEE f32, so the host face and the device carry the same
+ * bits (DESIGN.md 6e has the table of the WGSL built-ins and the Bevy semantics assumed).
+ *
+ *  - The material (pitchvis_viewer/src/display_system/material.rs:33-35 names assets/shaders/noisy_color_rings_2d.wgsl; its
+ *    fragment is :395-428): from the ball's linear rgba and (calmness, time, pitch_accuracy, pitch_deviation), at mesh uv (u, v)
+ *    with p = 2 uv - 1 and r = |p|: noise = clamp(simplex3(4.3 u, 4.3 v, 0.8 time) - 0.15, 0, 1) (:408-409; the 3-D simplex noise
+ *    of McEwan and Gustavson, :6-75); ring = sin(r sqrt(r) PI)^2 (:116-120); ring colour (mix(rgb, 1, noise calmness ring), a ring)
+ *    (:413); the centre dot for pitch_accuracy >= 0.85 (:126-141) and the six-armed tuning star for 0.01 <= r <= 0.25 (:231-260)
+ *    added with strength 0.4 (:422-423); the result mixed with the plain colour by clamp(1 - 1.65 calmness, 0, 1)^3 (:426-427); the
+ *    rim smoothstep(0.96, 1, r) towards alpha 0 (:100-102).  Alpha is exactly 0 where r >= 1: such pixels are left untouched.
+ *  - A ball is a 20 x 20 rectangle (setup.rs:110-112) scaled by `scale` at (x, y); mesh v runs downwards.
+ *  - The camera (setup.rs:359-365) is orthographic, FixedVertical: 38 * 0.41421357 world units over the image height, centred on
+ *    the origin; pixel (i, j) is column i, row j with row 0 at the top, sampled at its centre.
+ *  - Composition: the clear colour LinearRgba::from(srgb(0.23, 0.23, 0.25)), in Galaxy mode srgb(0.05, 0, 0.05) (mod.rs:19-21,
+ *    update.rs:914-915), alpha 1 — or the caller's background; then the balls back to front, ascending z, ties by ascending bin
+ *    (assumed for Bevy's Transparent2d sort), each blended as AlphaMode2d::Blend: rgb = src.rgb src.a + dst.rgb (1 - src.a),
+ *    a = src.a + dst.a (1 - src.a).  Not drawn: a ball whose visible bit is clear, whose scale is <= 0, or one of whose values
+ *    (x, y, z, scale, rgba, the three params, time) is not finite.
+ *  - params.time is per-ball state: update_pitch_balls sets it to Time::elapsed_secs() only for the balls a peak keys in the frame
+ *    (update.rs:239), so a fading ball's noise and pulses freeze.  It starts at 0 (Params::default()).
+ * The output is the linear HDR target before bloom and tone mapping, f32 [H][W][4].
+ * Left out: bloom and the display transform — Bevy's own passes, not in the reference tree; the spider net, the bass spiral and the
+ * text (the background argument is their hook); noisy_color_2d.wgsl, which nothing references. */
+/* one fragment: rgba linear, params = (calmness, time, pitch_accuracy, pitch_deviation) */
+pvq_status pvq_raster_shade(const float *rgba, const float *params, float u, float v, float *out4);
+/* the time update of one frame: every entry of the list sets time[trunc(center)] = elapsed (keys >= n_bins are ignored, as the
+ * scene ignores them).  time_inout [n_bins]. */
+pvq_status pvq_raster_touch(uint32_t n_bins, const float *center, uint32_t n_peaks, float elapsed, float *time_inout);
+/* One frame on the host.  ball_xyzs / ball_rgba [n_bins][4], ball_params [n_bins][3], ball_visible [ceil(n_bins / 32)] as
+ * pvq_scene_state_get gives them, ball_time [n_bins]; viewport_height 0: the viewer's; background [height][width][4] or NULL: the
+ * clear colour of visuals_mode.  image_out [height][width][4].  width, height 1 .. 4096. */
+pvq_status pvq_raster_frame(uint32_t n_bins, uint32_t width, uint32_t height, float viewport_height, int visuals_mode,
+                            const float *ball_xyzs, const float *ball_rgba, const float *ball_params, const uint32_t *ball_visible,
+                            const float *ball_time, const float *background, float *image_out);
+
+/* The same for MANY streams on the GPU, fed with what pvq_scene_batch_frames_device leaves in device memory.  The handle keeps
+ * every ball's time between calls. */
+typedef struct pvq_raster_batch pvq_raster_batch;
+/* DEVICE pointers laid out as pvq_scene_outputs and pvq_scene_inputs lay them out.  center, peak_count and max_peaks are always
+ * needed (a count above max_peaks is taken as max_peaks); the four ball arrays when an image is asked for. */
+typedef struct pvq_raster_inputs {
+    const float *ball_xyzs;        /* [n_streams][n_frames][n_bins][4]; 16-byte aligned */
+    const float *ball_rgba;        /* [n_streams][n_frames][n_bins][4]; 16-byte aligned */
+    const float *ball_params;      /* [n_streams][n_frames][n_bins][3] */
+    const uint32_t *ball_visible;  /* [n_streams][n_frames][ceil(n_bins / 32)] */
+    const float *center;           /* [n_streams][n_frames][max_peaks] */
+    const uint32_t *peak_count;    /* [n_streams][n_frames] */
+    uint32_t max_peaks;
+    const float *background;       /* optional: [height][width][4], shared by all rows; 16-byte aligned */
+} pvq_raster_inputs;
+/* The arguments are checked before any device is touched: bin counts 3 .. 1024 (PVQ_ERR_UNSUPPORTED beyond), width and height
+ * 1 .. 4096, viewport_height 0 (the viewer's) or positive and finite — at seven octaves the spiral reaches radius 9.2 and the
+ * viewer's view only +-7.87, so callers may widen it.  device_id < 0: a host-only handle whose frames call returns
+ * PVQ_ERR_NO_DEVICE after its argument checks. */
+pvq_status pvq_raster_batch_create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, int visuals_mode, float viewport_height,
+                                   uint32_t n_streams, uint32_t width, uint32_t height, pvq_raster_batch **out);
+void pvq_raster_batch_destroy(pvq_raster_batch *b);
+/* n_frames frames of every stream, in order: first frame f's peak list sets the times of its key bins to elapsed_s[f] (HOST array
+ * of n_frames, shared by all streams; balls the scene's hide pass hides take it too), then frame f is drawn with those times.
+ * d_image (optional) [n_streams][n_frames][height][width][4], 16-byte aligned; d_ball_time (optional) [n_streams][n_frames][n_bins]:
+ * the times each frame was drawn with.  PVQ_ERR_INVALID_ARG for a missing input, max_peaks == 0 or a misaligned pointer, before
+ * anything is launched.  One handle's calls are stream-ordered; the kernels run asynchronously on `stream`, but every call first
+ * waits for `stream` (the frame clocks go through a buffer of the handle), and a call that needs a larger workspace than any
+ * before it waits for the device. */
+pvq_status pvq_raster_batch_frames_device(pvq_raster_batch *b, size_t n_frames, const pvq_raster_inputs *in, const float *elapsed_s,
+                                          float *d_image, float *d_ball_time, void *stream);
+/* one stream's ball times after the last call (synchronises); out [n_bins] */
+pvq_status pvq_raster_batch_get_times(pvq_raster_batch *b, uint32_t stream_index, float *out);
+
 /* ---- the viewer's debug panels: spectrum line with peak discs, calmness histogram, scene calmness graph ------
  * The three meshes of DisplayMode::Debugging (pitchvis_viewer/src/display_system/update.rs:474-869), the last part of update_display
  * the stages above leave out.  A mesh is positions [vertices][3] (z = 0) and colours [vertices][4]; indices, UVs and the normal

@@ -42,6 +42,8 @@ EXPORTS = [
     "pvq_spectrum_mesh", "pvq_calmness_histogram_mesh", "pvq_calmness_graph_create", "pvq_calmness_graph_destroy", "pvq_calmness_graph_capacity",
     "pvq_calmness_graph_push", "pvq_calmness_graph_mesh", "pvq_panel_topology", "pvq_panels_batch_create", "pvq_panels_batch_destroy",
     "pvq_panels_batch_graph_capacity", "pvq_panels_batch_rows_device", "pvq_panels_batch_graph_device", "pvq_panels_batch_get_history",
+    "pvq_raster_shade", "pvq_raster_touch", "pvq_raster_frame", "pvq_raster_batch_create", "pvq_raster_batch_destroy",
+    "pvq_raster_batch_frames_device", "pvq_raster_batch_get_times",
     "pvq_note_model_create", "pvq_note_model_destroy", "pvq_note_model_sizes", "pvq_note_model_infer", "pvq_note_model_rows_device",
     "pvq_note_model_set_workspace_limit",
     "pvq_note_trainer_hyper_default", "pvq_note_trainer_create", "pvq_note_trainer_destroy", "pvq_note_trainer_step", "pvq_note_trainer_steps",
@@ -119,6 +121,11 @@ class CSceneOutputs(C.Structure):   # pvq_scene_outputs (device pointers)
 
 class CPanelsOutputs(C.Structure):   # pvq_panels_outputs (device pointers)
     _fields_ = [(n, C.c_void_p) for n in ("line_pos", "line_rgba", "disc_pos", "disc_rgba", "hist_pos", "hist_rgba")]
+
+
+class CRasterInputs(C.Structure):   # pvq_raster_inputs (device pointers)
+    _fields_ = [("ball_xyzs", C.c_void_p), ("ball_rgba", C.c_void_p), ("ball_params", C.c_void_p), ("ball_visible", C.c_void_p),
+                ("center", C.c_void_p), ("peak_count", C.c_void_p), ("max_peaks", C.c_uint32), ("background", C.c_void_p)]
 
 
 class CNoteModelParams(C.Structure):   # pvq_note_model_params
@@ -332,6 +339,14 @@ def load():
     L.pvq_panels_batch_rows_device.restype = C.c_int
     L.pvq_panels_batch_graph_device.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp]; L.pvq_panels_batch_graph_device.restype = C.c_int
     L.pvq_panels_batch_get_history.argtypes = [vp, C.c_uint32, fp]; L.pvq_panels_batch_get_history.restype = C.c_int
+    L.pvq_raster_shade.argtypes = [fp, fp, C.c_float, C.c_float, fp]; L.pvq_raster_shade.restype = C.c_int
+    L.pvq_raster_touch.argtypes = [C.c_uint32, fp, C.c_uint32, C.c_float, fp]; L.pvq_raster_touch.restype = C.c_int
+    L.pvq_raster_frame.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int, fp, fp, fp, up, fp, fp, fp]; L.pvq_raster_frame.restype = C.c_int
+    L.pvq_raster_batch_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.pvq_raster_batch_create.restype = C.c_int
+    L.pvq_raster_batch_destroy.argtypes = [vp]; L.pvq_raster_batch_destroy.restype = None
+    L.pvq_raster_batch_frames_device.argtypes = [vp, C.c_size_t, C.POINTER(CRasterInputs), fp, vp, vp, vp]; L.pvq_raster_batch_frames_device.restype = C.c_int
+    L.pvq_raster_batch_get_times.argtypes = [vp, C.c_uint32, fp]; L.pvq_raster_batch_get_times.restype = C.c_int
     L.pvq_note_model_create.argtypes = [C.c_int, C.POINTER(CNoteModelParams), C.POINTER(CNoteModelWeights), C.POINTER(vp)]
     L.pvq_note_model_create.restype = C.c_int
     L.pvq_note_model_destroy.argtypes = [vp]

@@ -19,6 +19,8 @@
 #include "note_trainer.hpp"
 #include "panels_batch.hpp"
 #include "panels_host.hpp"
+#include "raster_batch.hpp"
+#include "raster_host.hpp"
 #include "render_batch.hpp"
 #include "scene_batch.hpp"
 #include "scene_host.hpp"
@@ -47,6 +49,9 @@ struct pvq_scene_state {
 };
 struct pvq_scene_batch {
     std::unique_ptr<pvq::SceneBatch> impl;
+};
+struct pvq_raster_batch {
+    std::unique_ptr<pvq::RasterBatch> impl;
 };
 struct pvq_calmness_graph {
     pvq::CalmnessGraph impl;
@@ -1218,6 +1223,86 @@ pvq_status pvq_scene_batch_get_state(pvq_scene_batch* b, uint32_t stream_index, 
     try {
         if (!b) return null_handle();
         return b->impl->get_state(stream_index, ball_xyzs, ball_rgba, ball_params, ball_visible, bass_lit, bass_rgba, bloom);
+    } catch (...) { return translate_exception(); }
+}
+
+// noisy_color_rings_2d.wgsl:395-428 with setup.rs:110-112, :359-365: the pitch balls as pixels, one frame on the host
+// (raster_host.hpp) and many streams on the device (raster_batch.hpp)
+pvq_status pvq_raster_shade(const float* rgba, const float* params, float u, float v, float* out4) {
+    try {
+        if (!rgba || !params || !out4) {
+            pvq::set_last_error("raster shade: rgba, params and out4 are needed");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        pvq::raster_shade(rgba, params, u, v, out4);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_raster_touch(uint32_t n_bins, const float* center, uint32_t n_peaks, float elapsed, float* time_inout) {
+    try {
+        if (!time_inout || (n_peaks && !center)) {
+            pvq::set_last_error("raster touch: time_inout is needed, and center with n_peaks > 0");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        pvq::raster_touch(n_bins, center, n_peaks, elapsed, time_inout);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_raster_frame(uint32_t n_bins, uint32_t width, uint32_t height, float viewport_height, int visuals_mode, const float* ball_xyzs,
+                            const float* ball_rgba, const float* ball_params, const uint32_t* ball_visible, const float* ball_time,
+                            const float* background, float* image_out) {
+    try {
+        if (!ball_xyzs || !ball_rgba || !ball_params || !ball_visible || !ball_time || !image_out) {
+            pvq::set_last_error("raster frame: the five ball arrays and image_out are needed");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        if (width == 0 || height == 0 || width > pvq::raster::MAX_IMAGE || height > pvq::raster::MAX_IMAGE) {
+            pvq::set_last_error("raster frame: width and height are 1 .. 4096");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        if (!(viewport_height >= 0.0f) || !pvq::raster::finite_f(viewport_height)) {
+            pvq::set_last_error("raster frame: viewport_height is 0 (the viewer's) or positive and finite");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        if (visuals_mode < pvq::scene::FULL || visuals_mode > pvq::scene::GALAXY) {
+            pvq::set_last_error("raster frame: unknown visuals mode");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        pvq::raster_frame(n_bins, width, height, viewport_height == 0.0f ? pvq::raster::VIEWPORT_HEIGHT : viewport_height, visuals_mode,
+                          ball_xyzs, ball_rgba, ball_params, ball_visible, ball_time, background, image_out);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_raster_batch_create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, int visuals_mode, float viewport_height,
+                                   uint32_t n_streams, uint32_t width, uint32_t height, pvq_raster_batch** out) {
+    try {
+        if (!out) return null_handle();
+        *out = nullptr;
+        std::unique_ptr<pvq::RasterBatch> impl;
+        const pvq_status st = pvq::RasterBatch::create(device_id, octaves, buckets_per_octave, visuals_mode, viewport_height, n_streams,
+                                                       width, height, impl);
+        if (st != PVQ_OK) return st;
+        *out = new pvq_raster_batch{std::move(impl)};
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+void pvq_raster_batch_destroy(pvq_raster_batch* b) {
+    try {
+        delete b;
+    } catch (...) { (void)translate_exception(); }
+}
+pvq_status pvq_raster_batch_frames_device(pvq_raster_batch* b, size_t n_frames, const pvq_raster_inputs* in, const float* elapsed_s,
+                                          float* d_image, float* d_ball_time, void* stream) {
+    try {
+        if (!b) return null_handle();
+        const pvq_raster_inputs no_in{};
+        return b->impl->frames_device(n_frames, in ? *in : no_in, elapsed_s, d_image, d_ball_time, static_cast<hipStream_t>(stream));
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_raster_batch_get_times(pvq_raster_batch* b, uint32_t stream_index, float* out) {
+    try {
+        if (!b) return null_handle();
+        return b->impl->get_times(stream_index, out);
     } catch (...) { return translate_exception(); }
 }
 
