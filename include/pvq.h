@@ -661,8 +661,9 @@ pvq_status pvq_scene_batch_get_state(pvq_scene_batch *b, uint32_t stream_index, 
  *  - params.time is per-ball state: update_pitch_balls sets it to Time::elapsed_secs() only for the balls a peak keys in the frame
  *    (update.rs:239), so a fading ball's noise and pulses freeze.  It starts at 0 (Params::default()).
  * The output is the linear HDR target before bloom and tone mapping, f32 [H][W][4].
- * Left out: bloom and the display transform — Bevy's own passes, not in the reference tree; the spider net, the bass spiral and the
- * text (the background argument is their hook); noisy_color_2d.wgsl, which nothing references. */
+ * Left out: bloom and the display transform — Bevy's own passes, not in the reference tree; noisy_color_2d.wgsl, which nothing
+ * references.  The spider net, the bass spiral and the debug panels are the backdrop stage further down, which draws the picture the
+ * balls go over; the pitch-name text and the other parts that section lists stay left out. */
 /* one fragment: rgba linear, params = (calmness, time, pitch_accuracy, pitch_deviation) */
 pvq_status pvq_raster_shade(const float *rgba, const float *params, float u, float v, float *out4);
 /* the time update of one frame: every entry of the list sets time[trunc(center)] = elapsed (keys >= n_bins are ignored, as the
@@ -789,6 +790,112 @@ pvq_status pvq_panels_batch_graph_device(pvq_panels_batch *b, size_t n_frames, c
                                          float *graph_pos, float *graph_rgba, void *stream);
 /* one stream's history after the last call, oldest first, out [C] (synchronises) */
 pvq_status pvq_panels_batch_get_history(pvq_panels_batch *b, uint32_t stream_index, float *out);
+
+/* ---- the backdrop: spider net, debug panels and lit bass spiral as pixels, the picture the balls go over -------
+ * The rest of the 2-D layer of setup_display (pitchvis_viewer/src/display_system/setup.rs, update.rs).  Every layer is a list of
+ * flat-coloured triangles in world units, seen by the raster section's camera (orthographic, viewport_height over the image height,
+ * pixel centres, row 0 at the top) and blended with its blend into linear f32, back to front:
+ *  0. the clear colour of the mode, or the caller's shared background;
+ *  1. the net spiral (setup.rs:208-222): thick-line quads (mod.rs:277-306, thickness 0.05) between consecutive points of
+ *     calculate_spiral_points(octaves, 72), 72 octaves - 1 quads, LinearRgba::from(srgb(0.3, 0.3, 0.3)), alpha 1 — an opaque
+ *     material, so it is drawn first;
+ *  2. the net rays (setup.rs:181-206): 12 thick-line quads from the origin to radius octaves as f32 * 2.2 at angle i / 12 * 2 PI,
+ *     thickness 0.05, the same grey;
+ *  3. the spectrum line, n_bins - 1 quads, then a 12-triangle fan for each of the row's peak discs;
+ *  4. the scene-calmness graph, C - 1 quads;
+ *  5. the calmness histogram, n_bins - 1 quads;
+ *  6. the lit bass segments (setup.rs:127-172, update.rs:369-425): segments [0, bass_lit) of min(72 octaves, 168) - 1 rectangles,
+ *     each 0.05 wide and h + 0.01 long, centred on the midpoint of consecutive spiral points p, q with h = |p - q| and the long
+ *     axis along p - q, coloured LinearRgba::from(srgba(bass_rgba)) with the alpha as it is.  A bass_lit above the segment count is
+ *     taken as the segment count.
+ *  7. the balls: the raster stage, unchanged, through pvq_backdrop_balls_over_device or the background argument of its host face.
+ * Layers 1, 2 and 6 are absent in Galaxy mode (update.rs:888-895, :374-376).  Layers 3 - 5 are meshes as the panels section lays
+ * them out, drawn where their pointers are given; vertex colours are linear and not converted, a triangle takes the colour of its
+ * quad's first vertex or of its disc's centre.  Each of them carries its own transform (tx, ty, sx, sy), applied as x * sx + tx,
+ * y * sy + ty; pvq_backdrop_panel_transforms gives the reference's.  Within a mesh the triangles are blended in index order, the
+ * topology being pvq_panel_topology's: quad triangles (2, 1, 0), (2, 0, 3), disc fans.  Neighbouring line quads overlap at their
+ * joints and are blended twice there, as the reference's GPU would.  The static geometry goes through bin_to_spiral with every
+ * libm call the double-precision function rounded once to f32; it is built once on the host, for the device stage too.
+ *
+ * The coverage rule — one rule, carried bit for bit by the test model, the host face and the device; f32 without FMA contraction.
+ * One sample per pixel at its centre p (Msaa::Off).  Both windings are drawn (the 2-D mesh pipeline does not cull, and the
+ * histogram's sy = -1 flips its winding).  An edge is evaluated from its canonically ordered endpoints, lo being the endpoint with
+ * the smaller x, then the smaller y:
+ *     e = (hi.x - lo.x) * (p.y - lo.y) - (hi.y - lo.y) * (p.x - lo.x)
+ * so two triangles that share an edge compute the same number for it.  A triangle's sign for an edge is the sign of e at its third
+ * vertex.  A pixel is inside when, for all three edges, e has the triangle's sign, or e == 0 and the triangle's sign is positive:
+ * an edge through a pixel centre goes to exactly one of the two triangles beside it.  A triangle with a zero or non-finite sign, a
+ * non-finite vertex (after its transform) or a non-finite colour draws nothing.  Pixel boxes are an acceleration only and err
+ * outwards.
+ *
+ * Left out: the pitch-name text (it needs a font); the spectrogram quad at z = 5 and the chroma boxes (UI nodes in pixels, in front
+ * of the balls); bloom and tone mapping; MSAA; a ball whose z has fallen below -12.7, which in the reference would go under the bass
+ * spiral — here the balls are always on top (at keying z >= -12.625, and the fade lowers it by 0.03 per second while the ball
+ * lives). */
+enum { PVQ_BACKDROP_NET_SPIRAL = 0, PVQ_BACKDROP_NET_RAYS = 1, PVQ_BACKDROP_BASS = 2 };
+/* the static quads of one layer: quads_out [n][4][2] (v0 .. v3 as x, y; triangles (2, 1, 0), (2, 0, 3)), n_out: their number —
+ * 72 octaves - 1, 12, min(72 octaves, 168) - 1.  Either may be NULL.  octaves 1 .. 1024. */
+pvq_status pvq_backdrop_geometry(uint32_t octaves, int what, float *quads_out, uint32_t *n_out);
+/* the reference's transforms, out [3][4]: spectrum (max.x - n_bins * 0.011 - 0.2, max.y - 4.2, 1, 1) with max = (vh / 2 * W / H,
+ * vh / 2) (update.rs:496-500), histogram the same with sy = -1 (:776-781), graph (-5, -6.5, 3, 1) (setup.rs:284-288).
+ * viewport_height 0: the viewer's. */
+pvq_status pvq_backdrop_panel_transforms(uint32_t n_bins, uint32_t width, uint32_t height, float viewport_height, float *out);
+/* The rule's one-mesh face: n_triangles triangles, pos [n][3][2], rgba [n][4] (linear), blended in index order into image_inout
+ * [height][width][4]; transform [4] or NULL.  width, height 1 .. 4096; viewport_height 0: the viewer's. */
+pvq_status pvq_backdrop_draw_mesh(uint32_t width, uint32_t height, float viewport_height, size_t n_triangles, const float *pos,
+                                  const float *rgba, const float *transform, float *image_inout);
+/* the panels of one frame, HOST pointers as pvq_spectrum_mesh, pvq_calmness_histogram_mesh and pvq_calmness_graph_mesh fill them;
+ * a mesh is drawn where its pos and rgba are given (PVQ_ERR_INVALID_ARG for one without the other, or a graph with a capacity
+ * below 2) */
+typedef struct pvq_backdrop_panels {
+    const float *line_pos, *line_rgba;   /* [4 (n_bins - 1)][3], [..][4] */
+    const float *disc_pos, *disc_rgba;   /* [n_peaks][13][3], [..][13][4] */
+    uint32_t n_peaks;
+    const float *hist_pos, *hist_rgba;
+    const float *graph_pos, *graph_rgba; /* [4 (C - 1)][3], [..][4] */
+    uint32_t graph_capacity;
+    float spectrum_transform[4], histogram_transform[4], graph_transform[4];   /* tx, ty, sx, sy */
+} pvq_backdrop_panels;
+/* One frame on the host: layers 0 - 6.  bass_rgba [4] (needed with bass_lit > 0), panels NULL: none; background [height][width][4]
+ * or NULL: the clear colour of visuals_mode.  image_out [height][width][4]. */
+pvq_status pvq_backdrop_frame(uint32_t octaves, uint32_t buckets_per_octave, uint32_t width, uint32_t height, float viewport_height,
+                              int visuals_mode, uint32_t bass_lit, const float *bass_rgba, const pvq_backdrop_panels *panels,
+                              const float *background, float *image_out);
+
+/* The same for MANY streams on the GPU, fed with what the scene and panels stages leave in device memory.  Stateless. */
+typedef struct pvq_backdrop_batch pvq_backdrop_batch;
+/* DEVICE pointers laid out as pvq_scene_outputs and pvq_panels_outputs lay them out, a row being (stream, frame); the graph as
+ * pvq_panels_batch_graph_device writes it with first_emitted == 0.  Every group is optional: bass_lit with bass_rgba; line_pos with
+ * line_rgba; disc_pos with disc_rgba, peak_count and max_peaks > 0 (a count above max_peaks is taken as max_peaks; slots beyond a
+ * row's count are not drawn); hist_pos with hist_rgba; graph_pos with graph_rgba and graph_capacity >= 2.  The rgba arrays, bass_rgba
+ * and background are 16-byte aligned. */
+typedef struct pvq_backdrop_inputs {
+    const uint32_t *bass_lit;     /* [n_streams][n_frames] */
+    const float *bass_rgba;       /* [n_streams][n_frames][4] */
+    const float *line_pos, *line_rgba;
+    const float *disc_pos, *disc_rgba;
+    const uint32_t *peak_count;   /* [n_streams][n_frames] */
+    uint32_t max_peaks;
+    const float *hist_pos, *hist_rgba;
+    const float *graph_pos, *graph_rgba;
+    uint32_t graph_capacity;
+    float spectrum_transform[4], histogram_transform[4], graph_transform[4];   /* tx, ty, sx, sy */
+    const float *background;      /* optional: [height][width][4], shared by all rows */
+} pvq_backdrop_inputs;
+/* Takes the argument ranges of pvq_raster_batch_create and checks them before any device is touched; device_id < 0: a host-only
+ * handle whose frames call returns PVQ_ERR_NO_DEVICE after its argument checks. */
+pvq_status pvq_backdrop_batch_create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, int visuals_mode, float viewport_height,
+                                     uint32_t n_streams, uint32_t width, uint32_t height, pvq_backdrop_batch **out);
+void pvq_backdrop_batch_destroy(pvq_backdrop_batch *b);
+/* Layers 0 - 6 of n_frames frames of every stream into d_image [n_streams][n_frames][height][width][4], 16-byte aligned.
+ * PVQ_ERR_INVALID_ARG before anything is launched for a half-given group or a misaligned pointer.  Asynchronous on `stream`; a call
+ * that needs a larger workspace than any before it waits for the device. */
+pvq_status pvq_backdrop_batch_frames_device(pvq_backdrop_batch *b, size_t n_frames, const pvq_backdrop_inputs *in, float *d_image,
+                                            void *stream);
+/* Layer 7: pvq_raster_batch_frames_device, except that each row's balls are blended over what d_image_inout already holds for that
+ * row (in place: a pixel is read and written by the same lane).  in->background must be NULL and d_image_inout is needed. */
+pvq_status pvq_backdrop_balls_over_device(pvq_raster_batch *b, size_t n_frames, const pvq_raster_inputs *in, const float *elapsed_s,
+                                          float *d_image_inout, float *d_ball_time, void *stream);
 
 /* The note model the dataset of pitchvis_train exists for (pitchvis_train/train.py:67-99), which the viewer runs per rendered frame
  * through TorchScript on a CUDA device (pitchvis_viewer/src/ml_system.rs:24-69): a window of t_frames consecutive dB frames,

@@ -44,6 +44,8 @@ EXPORTS = [
     "pvq_panels_batch_graph_capacity", "pvq_panels_batch_rows_device", "pvq_panels_batch_graph_device", "pvq_panels_batch_get_history",
     "pvq_raster_shade", "pvq_raster_touch", "pvq_raster_frame", "pvq_raster_batch_create", "pvq_raster_batch_destroy",
     "pvq_raster_batch_frames_device", "pvq_raster_batch_get_times",
+    "pvq_backdrop_geometry", "pvq_backdrop_panel_transforms", "pvq_backdrop_draw_mesh", "pvq_backdrop_frame", "pvq_backdrop_batch_create",
+    "pvq_backdrop_batch_destroy", "pvq_backdrop_batch_frames_device", "pvq_backdrop_balls_over_device",
     "pvq_note_model_create", "pvq_note_model_destroy", "pvq_note_model_sizes", "pvq_note_model_infer", "pvq_note_model_rows_device",
     "pvq_note_model_set_workspace_limit",
     "pvq_note_trainer_hyper_default", "pvq_note_trainer_create", "pvq_note_trainer_destroy", "pvq_note_trainer_step", "pvq_note_trainer_steps",
@@ -126,6 +128,21 @@ class CPanelsOutputs(C.Structure):   # pvq_panels_outputs (device pointers)
 class CRasterInputs(C.Structure):   # pvq_raster_inputs (device pointers)
     _fields_ = [("ball_xyzs", C.c_void_p), ("ball_rgba", C.c_void_p), ("ball_params", C.c_void_p), ("ball_visible", C.c_void_p),
                 ("center", C.c_void_p), ("peak_count", C.c_void_p), ("max_peaks", C.c_uint32), ("background", C.c_void_p)]
+
+
+class CBackdropPanels(C.Structure):   # pvq_backdrop_panels (host pointers, one row)
+    _fields_ = [("line_pos", C.c_void_p), ("line_rgba", C.c_void_p), ("disc_pos", C.c_void_p), ("disc_rgba", C.c_void_p), ("n_peaks", C.c_uint32),
+                ("hist_pos", C.c_void_p), ("hist_rgba", C.c_void_p), ("graph_pos", C.c_void_p), ("graph_rgba", C.c_void_p),
+                ("graph_capacity", C.c_uint32), ("spectrum_transform", C.c_float * 4), ("histogram_transform", C.c_float * 4),
+                ("graph_transform", C.c_float * 4)]
+
+
+class CBackdropInputs(C.Structure):   # pvq_backdrop_inputs (device pointers)
+    _fields_ = [("bass_lit", C.c_void_p), ("bass_rgba", C.c_void_p), ("line_pos", C.c_void_p), ("line_rgba", C.c_void_p),
+                ("disc_pos", C.c_void_p), ("disc_rgba", C.c_void_p), ("peak_count", C.c_void_p), ("max_peaks", C.c_uint32),
+                ("hist_pos", C.c_void_p), ("hist_rgba", C.c_void_p), ("graph_pos", C.c_void_p), ("graph_rgba", C.c_void_p),
+                ("graph_capacity", C.c_uint32), ("spectrum_transform", C.c_float * 4), ("histogram_transform", C.c_float * 4),
+                ("graph_transform", C.c_float * 4), ("background", C.c_void_p)]
 
 
 class CNoteModelParams(C.Structure):   # pvq_note_model_params
@@ -347,6 +364,17 @@ def load():
     L.pvq_raster_batch_destroy.argtypes = [vp]; L.pvq_raster_batch_destroy.restype = None
     L.pvq_raster_batch_frames_device.argtypes = [vp, C.c_size_t, C.POINTER(CRasterInputs), fp, vp, vp, vp]; L.pvq_raster_batch_frames_device.restype = C.c_int
     L.pvq_raster_batch_get_times.argtypes = [vp, C.c_uint32, fp]; L.pvq_raster_batch_get_times.restype = C.c_int
+    L.pvq_backdrop_geometry.argtypes = [C.c_uint32, C.c_int, fp, up]; L.pvq_backdrop_geometry.restype = C.c_int
+    L.pvq_backdrop_panel_transforms.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, fp]; L.pvq_backdrop_panel_transforms.restype = C.c_int
+    L.pvq_backdrop_draw_mesh.argtypes = [C.c_uint32, C.c_uint32, C.c_float, C.c_size_t, fp, fp, fp, fp]; L.pvq_backdrop_draw_mesh.restype = C.c_int
+    L.pvq_backdrop_frame.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_uint32, fp, C.POINTER(CBackdropPanels),
+                                     fp, fp]
+    L.pvq_backdrop_frame.restype = C.c_int
+    L.pvq_backdrop_batch_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.pvq_backdrop_batch_create.restype = C.c_int
+    L.pvq_backdrop_batch_destroy.argtypes = [vp]; L.pvq_backdrop_batch_destroy.restype = None
+    L.pvq_backdrop_batch_frames_device.argtypes = [vp, C.c_size_t, C.POINTER(CBackdropInputs), vp, vp]; L.pvq_backdrop_batch_frames_device.restype = C.c_int
+    L.pvq_backdrop_balls_over_device.argtypes = [vp, C.c_size_t, C.POINTER(CRasterInputs), fp, vp, vp, vp]; L.pvq_backdrop_balls_over_device.restype = C.c_int
     L.pvq_note_model_create.argtypes = [C.c_int, C.POINTER(CNoteModelParams), C.POINTER(CNoteModelWeights), C.POINTER(vp)]
     L.pvq_note_model_create.restype = C.c_int
     L.pvq_note_model_destroy.argtypes = [vp]

@@ -12,6 +12,8 @@
 
 #include "analysis_batch.hpp"
 #include "analysis_host.hpp"
+#include "backdrop_batch.hpp"
+#include "backdrop_host.hpp"
 #include "condition_batch.hpp"
 #include "consumers_host.hpp"
 #include "multi_host.hpp"
@@ -52,6 +54,9 @@ struct pvq_scene_batch {
 };
 struct pvq_raster_batch {
     std::unique_ptr<pvq::RasterBatch> impl;
+};
+struct pvq_backdrop_batch {
+    std::unique_ptr<pvq::BackdropBatch> impl;
 };
 struct pvq_calmness_graph {
     pvq::CalmnessGraph impl;
@@ -1422,6 +1427,120 @@ pvq_status pvq_panels_batch_get_history(pvq_panels_batch* b, uint32_t stream_ind
     try {
         if (!b) return null_handle();
         return b->impl->get_history(stream_index, out);
+    } catch (...) { return translate_exception(); }
+}
+
+// The picture behind the balls — spider net, debug panels, lit bass spiral (setup.rs:127-222, update.rs:369-425, :474-869 as pixels):
+// one frame on the host (backdrop_host.hpp) and many streams on the device (backdrop_batch.hpp)
+static bool backdrop_image_args(const char* who, uint32_t width, uint32_t height, float viewport_height) {
+    if (width == 0 || height == 0 || width > pvq::raster::MAX_IMAGE || height > pvq::raster::MAX_IMAGE) {
+        pvq::set_last_error(std::string(who) + ": width and height are 1 .. 4096");
+        return false;
+    }
+    if (!(viewport_height >= 0.0f) || !pvq::raster::finite_f(viewport_height)) {
+        pvq::set_last_error(std::string(who) + ": viewport_height is 0 (the viewer's) or positive and finite");
+        return false;
+    }
+    return true;
+}
+pvq_status pvq_backdrop_geometry(uint32_t octaves, int what, float* quads_out, uint32_t* n_out) {
+    try {
+        if (octaves == 0 || octaves > 1024 || what < pvq::backdrop::NET_SPIRAL || what > pvq::backdrop::BASS) {
+            pvq::set_last_error("backdrop geometry: octaves 1 .. 1024, what one of net spiral, rays, bass");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        if (n_out) *n_out = pvq::backdrop::geometry_count(octaves, what);
+        if (quads_out) {
+            const std::vector<float> q = pvq::backdrop_geometry(octaves, what);
+            std::copy(q.begin(), q.end(), quads_out);
+        }
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_backdrop_panel_transforms(uint32_t n_bins, uint32_t width, uint32_t height, float viewport_height, float* out) {
+    try {
+        if (!out) {
+            pvq::set_last_error("backdrop panel transforms: out is needed");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        if (!backdrop_image_args("backdrop panel transforms", width, height, viewport_height)) return PVQ_ERR_INVALID_ARG;
+        pvq::backdrop::panel_transforms(n_bins, width, height, viewport_height == 0.0f ? pvq::raster::VIEWPORT_HEIGHT : viewport_height, out);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_backdrop_draw_mesh(uint32_t width, uint32_t height, float viewport_height, size_t n_triangles, const float* pos, const float* rgba,
+                                  const float* transform, float* image_inout) {
+    try {
+        if (!image_inout || (n_triangles && (!pos || !rgba))) {
+            pvq::set_last_error("backdrop draw mesh: image_inout is needed, and pos and rgba with n_triangles > 0");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        if (!backdrop_image_args("backdrop draw mesh", width, height, viewport_height)) return PVQ_ERR_INVALID_ARG;
+        pvq::backdrop_draw_mesh(width, height, viewport_height == 0.0f ? pvq::raster::VIEWPORT_HEIGHT : viewport_height, n_triangles, pos, rgba,
+                                transform, image_inout);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_backdrop_frame(uint32_t octaves, uint32_t buckets_per_octave, uint32_t width, uint32_t height, float viewport_height,
+                              int visuals_mode, uint32_t bass_lit, const float* bass_rgba, const pvq_backdrop_panels* panels,
+                              const float* background, float* image_out) {
+    try {
+        if (!image_out || (bass_lit && !bass_rgba)) {
+            pvq::set_last_error("backdrop frame: image_out is needed, and bass_rgba with bass_lit > 0");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        const uint64_t n = static_cast<uint64_t>(octaves) * buckets_per_octave;
+        if (octaves == 0 || buckets_per_octave == 0 || octaves > 1024 || n < 2 || n > 0x7FFFFFFFull) {
+            pvq::set_last_error("backdrop frame: octaves 1 .. 1024, buckets_per_octave positive, at least two bins");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        if (!backdrop_image_args("backdrop frame", width, height, viewport_height)) return PVQ_ERR_INVALID_ARG;
+        if (visuals_mode < pvq::scene::FULL || visuals_mode > pvq::scene::GALAXY) {
+            pvq::set_last_error("backdrop frame: unknown visuals mode");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        if (panels && (!panels->line_pos != !panels->line_rgba || !panels->disc_pos != !panels->disc_rgba ||
+                       !panels->hist_pos != !panels->hist_rgba || !panels->graph_pos != !panels->graph_rgba ||
+                       (panels->graph_pos && panels->graph_capacity < 2))) {
+            pvq::set_last_error("backdrop frame: a mesh needs its positions and its colours, the graph its graph_capacity >= 2");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        pvq::backdrop_frame(octaves, buckets_per_octave, width, height, viewport_height == 0.0f ? pvq::raster::VIEWPORT_HEIGHT : viewport_height,
+                            visuals_mode, bass_lit, bass_rgba, panels, background, image_out);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_backdrop_batch_create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, int visuals_mode, float viewport_height,
+                                     uint32_t n_streams, uint32_t width, uint32_t height, pvq_backdrop_batch** out) {
+    try {
+        if (!out) return null_handle();
+        *out = nullptr;
+        std::unique_ptr<pvq::BackdropBatch> impl;
+        const pvq_status st = pvq::BackdropBatch::create(device_id, octaves, buckets_per_octave, visuals_mode, viewport_height, n_streams,
+                                                         width, height, impl);
+        if (st != PVQ_OK) return st;
+        *out = new pvq_backdrop_batch{std::move(impl)};
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+void pvq_backdrop_batch_destroy(pvq_backdrop_batch* b) {
+    try {
+        delete b;
+    } catch (...) { (void)translate_exception(); }
+}
+pvq_status pvq_backdrop_batch_frames_device(pvq_backdrop_batch* b, size_t n_frames, const pvq_backdrop_inputs* in, float* d_image, void* stream) {
+    try {
+        if (!b) return null_handle();
+        const pvq_backdrop_inputs no_in{};
+        return b->impl->frames_device(n_frames, in ? *in : no_in, d_image, static_cast<hipStream_t>(stream));
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_backdrop_balls_over_device(pvq_raster_batch* b, size_t n_frames, const pvq_raster_inputs* in, const float* elapsed_s,
+                                          float* d_image_inout, float* d_ball_time, void* stream) {
+    try {
+        if (!b) return null_handle();
+        const pvq_raster_inputs no_in{};
+        return b->impl->frames_device(n_frames, in ? *in : no_in, elapsed_s, d_image_inout, d_ball_time, static_cast<hipStream_t>(stream), true);
     } catch (...) { return translate_exception(); }
 }
 

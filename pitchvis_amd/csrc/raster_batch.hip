@@ -9,7 +9,8 @@
 // pulses, the cube, the star's brightness: all the per-ball libm) lands at its rank in the workspace.
 // raster_tiles (frame-parallel, a workgroup per (row, 16 x 16 pixels), a wave per 8 x 8 block, a lane per pixel): the row's list
 // goes through LDS in chunks of 64 balls (one 16-byte load a lane); the box-against-block test reads LDS at a wave-uniform address
-// and branches the whole wave; the pixel's colour stays in registers across all balls and leaves in one 16-byte store.
+// and branches the whole wave; the pixel's colour stays in registers across all balls and leaves in one 16-byte store.  The
+// colour starts as the clear colour, the shared background, or — drawing over a backdrop — what the image holds for that row.
 //
 // FMA contraction is off and `/` and sqrt are the correctly rounded ones, as in scene_batch.hip.
 #include "raster_batch.hpp"
@@ -47,6 +48,7 @@ struct RasterArgs {
     const float* center;        // [..][max_peaks]
     const uint32_t* peak_count;
     const float* background;    // [H][W][4] or null
+    size_t bg_row;              // pixels from a row's background to the next row's: 0, one picture shared by all rows
     const float* elapsed;       // [n_frames]
     uint32_t max_peaks, n_streams, n_bins, words;
     uint32_t n_frames, f0, pf;  // the call's frames; this piece is frames f0 .. f0 + pf
@@ -168,7 +170,7 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void raster_tiles(Ras
         const size_t g = static_cast<size_t>(r / a.pf) * a.n_frames + a.f0 + r % a.pf;
         float dst[4] = {a.clear[0], a.clear[1], a.clear[2], a.clear[3]};
         if (a.background && inside) {
-            const float4 bg = reinterpret_cast<const float4*>(a.background)[pixel];
+            const float4 bg = reinterpret_cast<const float4*>(a.background)[g * a.bg_row + pixel];
             dst[0] = bg.x; dst[1] = bg.y; dst[2] = bg.z; dst[3] = bg.w;
         }
         const uint32_t m = a.counts[r];
@@ -250,7 +252,11 @@ pvq_status RasterBatch::create(int device_id, uint32_t octaves, uint32_t buckets
 }
 
 pvq_status RasterBatch::frames_device(size_t n_frames, const pvq_raster_inputs& in, const float* elapsed_s, float* d_image,
-                                      float* d_ball_time, hipStream_t stream) {
+                                      float* d_ball_time, hipStream_t stream, bool over) {
+    if (over && (in.background || !d_image)) {
+        set_last_error("raster batch: drawing over the image takes no background and needs d_image");
+        return PVQ_ERR_INVALID_ARG;
+    }
     if (!in.center || !in.peak_count || in.max_peaks == 0) {
         set_last_error("raster batch: center and peak_count are needed, with max_peaks > 0");
         return PVQ_ERR_INVALID_ARG;
@@ -311,7 +317,8 @@ pvq_status RasterBatch::frames_device(size_t n_frames, const pvq_raster_inputs& 
     a.visible = in.ball_visible;
     a.center = in.center;
     a.peak_count = in.peak_count;
-    a.background = in.background;
+    a.background = over ? d_image : in.background;   // in place: a lane reads its pixel before it writes it
+    a.bg_row = over ? static_cast<size_t>(width_) * height_ : 0;
     a.elapsed = d_elapsed_;
     a.max_peaks = in.max_peaks;
     a.n_streams = n_streams_;

@@ -27,9 +27,10 @@ class RasterBatch {
     ~RasterBatch();
     uint32_t n_bins() const { return n_bins_; }
     float viewport_height() const { return vh_; }
-    // n_frames frames of every stream.  Asynchronous on `stream`; one handle's calls are stream-ordered.
+    // n_frames frames of every stream.  Asynchronous on `stream`; one handle's calls are stream-ordered.  over: every row's balls
+    // are blended over what d_image holds for that row (the backdrop stage's picture) instead of the clear colour.
     pvq_status frames_device(size_t n_frames, const pvq_raster_inputs& in, const float* elapsed_s, float* d_image, float* d_ball_time,
-                             hipStream_t stream);
+                             hipStream_t stream, bool over = false);
     // one stream's ball times after the last call (synchronises)
     pvq_status get_times(uint32_t stream_index, float* out);
 

@@ -6,7 +6,8 @@ mapping, float32 [height][width][4].
 * ``raster_shade`` — one fragment, ``raster_touch`` — a frame's update of the balls' times, ``raster_frame`` — one frame on the
   host (pvq_raster_shade / _touch / _frame), the one-frame face
 * ``RasterBatch`` — many streams on the GPU (pvq_raster_batch_*), fed with what ``SceneBatch.frames_device`` leaves in device
-  memory; the handle keeps every ball's time between calls
+  memory; the handle keeps every ball's time between calls.  ``RasterBatch.frames_over`` draws the balls over the picture
+  ``backdrop.BackdropBatch`` leaves (pvq_backdrop_balls_over_device)
 """
 from __future__ import annotations
 
@@ -104,6 +105,10 @@ class RasterBatch:
         shared by all streams).  ``image`` / ``ball_time``: True to allocate, a device tensor to fill, False / None to leave out.
         ``background``: a device tensor [height][width][4].  Returns {"image": ..., "ball_time": ...} of what was asked for.
         The kernels run asynchronously on ``stream``."""
+        return self._frames(False, balls, peaks, elapsed, image, ball_time, background, n_frames, max_peaks, stream, inputs)
+
+    def _frames(self, over, balls, peaks, elapsed, image, ball_time, background, n_frames, max_peaks, stream, inputs) -> dict:
+        """frames_device (over False) and frames_over (over True): the same checks, one of the two C calls"""
         from . import _ptr, _stream_handle
         unknown = set(inputs) - set(INPUTS)
         if unknown:
@@ -140,9 +145,19 @@ class RasterBatch:
             out[name] = want
         i = _lib.CRasterInputs(_ptr(t["ball_xyzs"]), _ptr(t["ball_rgba"]), _ptr(t["ball_params"]), _ptr(t["ball_visible"]), _ptr(t["center"]),
                                _ptr(t["peak_count"]), int(max_peaks), _ptr(background))
-        _checked(self._L, self._L.pvq_raster_batch_frames_device(self._h, int(n_frames), C.byref(i), _f(el) if el.size else None,
-                                                                 _ptr(out.get("image")), _ptr(out.get("ball_time")), _stream_handle(stream)))
+        call = self._L.pvq_backdrop_balls_over_device if over else self._L.pvq_raster_batch_frames_device
+        _checked(self._L, call(self._h, int(n_frames), C.byref(i), _f(el) if el.size else None, _ptr(out.get("image")),
+                               _ptr(out.get("ball_time")), _stream_handle(stream)))
         return out
+
+    def frames_over(self, image, balls=None, peaks=None, *, elapsed, ball_time=False, n_frames: Optional[int] = None,
+                    max_peaks: Optional[int] = None, stream=None, **inputs) -> dict:
+        """``frames_device``, except that every row's balls are blended over what ``image`` (a device tensor
+        [n_streams][n_frames][height][width][4], as ``BackdropBatch.frames`` fills it) already holds for that row, in place.
+        Returns {"image": image, "ball_time": ...}."""
+        if image is None or image is True or image is False:
+            raise ValueError("frames_over draws into an image that is given")
+        return self._frames(True, balls, peaks, elapsed, image, ball_time, None, n_frames, max_peaks, stream, inputs)
 
     def times(self, stream_index: int) -> np.ndarray:
         """One stream's ball times after the last call (synchronises)"""
