@@ -22,15 +22,6 @@
 
 namespace pvq {
 
-#define PVQ_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_last_error(std::string(#call) + " failed: " + hipGetErrorString(e_));              \
-            return PVQ_ERR_DEVICE;                                                                 \
-        }                                                                                          \
-    } while (0)
-
 struct AbArgs {
     const float* db;   // [n_streams][n_frames][n_bins]
     int n_streams, n_frames, n_bins, bpo, octaves;
@@ -636,25 +627,13 @@ __global__ __launch_bounds__(256) void ab_tuning(AbArgs a) {
 // host side
 // ------------------------------------------------------------------------------------------------
 AnalysisBatch::~AnalysisBatch() {
-    if (device_id_ >= 0) (void)hipSetDevice(device_id_);
-    for (float* p : {d_smoothed_, d_calm_, d_released_, d_afterglow_, d_peakfiltered_, d_pitch_acc_, d_pitch_dev_, d_scene_, d_tuning_, d_lnf_})
-        if (p) (void)hipFree(p);
-    if (d_times_) (void)hipFree(d_times_);
-    if (d_tab_) (void)hipFree(d_tab_);
-    if (d_frames_) (void)hipFree(d_frames_);
-    if (d_raw_) (void)hipFree(d_raw_);
+    if (device_id_ >= 0) (void)hipSetDevice(device_id_);   // the buffers go after this body, with their device set
 }
 
 pvq_status AnalysisBatch::frames_buffer(size_t bytes, float** out) {
     PVQ_HIP(hipSetDevice(device_id_));
-    if (frames_cap_ < bytes) {
-        if (d_frames_) PVQ_HIP(hipFree(d_frames_));   // (synchronises the device: nothing still reads the old buffer)
-        d_frames_ = nullptr;
-        frames_cap_ = 0;
-        PVQ_HIP(hipMalloc(&d_frames_, bytes));
-        frames_cap_ = bytes;
-    }
-    *out = static_cast<float*>(d_frames_);
+    if (pvq_status s = frames_.reserve(bytes)) return s;
+    *out = frames_.as<float>();
     return PVQ_OK;
 }
 
@@ -681,20 +660,19 @@ pvq_status AnalysisBatch::create(int device_id, const VqtRange& range, const Ful
     b->params_ = params;
     b->n_streams_ = n_streams;
     const size_t per = (size_t)n_streams * n * sizeof(float);
-    for (float** p : {&b->d_smoothed_, &b->d_calm_, &b->d_released_, &b->d_afterglow_, &b->d_peakfiltered_, &b->d_pitch_acc_, &b->d_pitch_dev_}) {
-        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(p), per));
-        PVQ_HIP(hipMemset(*p, 0, per));   // analysis.rs:192-241: every EMA starts at 0
+    for (DeviceBuffer* p : {&b->smoothed_, &b->calm_, &b->released_, &b->afterglow_, &b->peakfiltered_, &b->pitch_acc_, &b->pitch_dev_}) {
+        if (pvq_status s = p->reserve(per)) return s;
+        PVQ_HIP(hipMemset(p->as<float>(), 0, per));   // analysis.rs:192-241: every EMA starts at 0
     }
-    for (float** p : {&b->d_scene_, &b->d_tuning_}) {
-        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(p), n_streams * sizeof(float)));
-        PVQ_HIP(hipMemset(*p, 0, n_streams * sizeof(float)));
+    for (DeviceBuffer* p : {&b->scene_, &b->tuning_}) {
+        if (pvq_status s = p->reserve(n_streams * sizeof(float))) return s;
+        PVQ_HIP(hipMemset(p->as<float>(), 0, n_streams * sizeof(float)));
     }
     VqtParameters vp;
     vp.range = range;
     std::vector<float> lnf;
     bin_log_frequencies(vp, lnf);
-    PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&b->d_lnf_), lnf.size() * sizeof(float)));
-    PVQ_HIP(hipMemcpy(b->d_lnf_, lnf.data(), lnf.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (pvq_status s = b->lnf_.upload(lnf.data(), lnf.size() * sizeof(float))) return s;
     out = std::move(b);
     return PVQ_OK;
 }
@@ -744,15 +722,9 @@ pvq_status AnalysisBatch::preprocess_device(const float* d_db, size_t n_frames, 
     a.frame_ns = frame_time.ns;
     a.frame_times = nullptr;
     if (frame_times_ns) {
-        if (times_cap_ < n_frames) {
-            if (d_times_) PVQ_HIP(hipFree(d_times_));
-            d_times_ = nullptr;
-            times_cap_ = 0;
-            PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&d_times_), n_frames * sizeof(unsigned long long)));
-            times_cap_ = n_frames;
-        }
-        PVQ_HIP(hipMemcpyAsync(d_times_, frame_times_ns, n_frames * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-        a.frame_times = d_times_;
+        if (pvq_status s = times_.reserve(n_frames * sizeof(unsigned long long))) return s;
+        PVQ_HIP(hipMemcpyAsync(times_.as<void>(), frame_times_ns, n_frames * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+        a.frame_times = times_.as<unsigned long long>();
     }
     // EMA weights from the host's libm (util.rs:106-110: alpha = 1 - exp(-2 timestep / time_horizon), all f32).  The per-bin
     // horizons of analysis.rs:301-323 are whole milliseconds between 0 and base * 1.5 * max(calmness multiplier): one table row per
@@ -798,34 +770,27 @@ pvq_status AnalysisBatch::preprocess_device(const float* d_db, size_t n_frames, 
             // the table of the last call is reused as it stands when nothing it depends on changed (the usual case: one frame time for
             // every call) — no upload, no wait; otherwise the stream is drained first: an earlier call may still read the buffer
             const size_t need = tab.size() * sizeof(float) + rows.size() * sizeof(uint32_t);
-            const bool same = rows.empty() && d_tab_ && tab == tab_host_;
+            const bool same = rows.empty() && tab == tab_host_;   // (tab is never empty: tab_host_ is what the device holds, or empty)
             if (!same) {
                 PVQ_HIP(hipStreamSynchronize(stream));
-                if (tab_cap_ < need) {
-                    PVQ_HIP(hipDeviceSynchronize());   // (a call on another stream may read it too)
-                    if (d_tab_) PVQ_HIP(hipFree(d_tab_));
-                    d_tab_ = nullptr;
-                    tab_cap_ = 0;
-                    tab_host_.clear();
-                    PVQ_HIP(hipMalloc(&d_tab_, need));
-                    tab_cap_ = need;
-                }
+                tab_host_.clear();
+                if (pvq_status s = tab_.reserve(need)) return s;   // (growing waits for the device: a call on another stream may read it too)
                 // (synchronous copies from pageable host memory)
-                PVQ_HIP(hipMemcpy(d_tab_, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+                PVQ_HIP(hipMemcpy(tab_.as<float>(), tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
                 tab_host_ = rows.empty() ? tab : std::vector<float>();
             }
-            a.alpha_tab = static_cast<const float*>(d_tab_);
+            a.alpha_tab = tab_.as<float>();
             a.tab_n = (int)tab_n;
             a.tab_stride = (int)stride;
             a.tab_lds = rows.empty() && stride <= 4096 ? (int)stride : 0;   // (16 KB of LDS at most)
             if (!rows.empty()) {
-                uint32_t* d_rows = reinterpret_cast<uint32_t*>(static_cast<char*>(d_tab_) + tab.size() * sizeof(float));
+                uint32_t* d_rows = reinterpret_cast<uint32_t*>(tab_.as<char>() + tab.size() * sizeof(float));
                 PVQ_HIP(hipMemcpy(d_rows, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
                 a.frame_row = d_rows;
             }
         }
     }
-    a.lnf = d_lnf_;
+    a.lnf = lnf_.as<float>();
     a.log2_min_freq = std::log2(range_.min_freq);
     {   // peak_detection.rs:37, :45 and calmness.rs:37, as the batched peak kernels derive them
         const float dist_f = std::round((float)a.bpo * 0.4f / 12.0f);
@@ -833,9 +798,9 @@ pvq_status AnalysisBatch::preprocess_device(const float* d_db, size_t n_frames, 
         a.min_bin = ((a.bpo / 12) + 1) / 2;
         a.radius = a.bpo / 12 / 3;
     }
-    a.smoothed = d_smoothed_; a.calm = d_calm_; a.released = d_released_; a.afterglow = d_afterglow_;
-    a.peakfiltered = d_peakfiltered_; a.pitch_acc = d_pitch_acc_; a.pitch_dev = d_pitch_dev_;
-    a.scene = d_scene_; a.tuning = d_tuning_;
+    a.smoothed = smoothed_.as<float>(); a.calm = calm_.as<float>(); a.released = released_.as<float>(); a.afterglow = afterglow_.as<float>();
+    a.peakfiltered = peakfiltered_.as<float>(); a.pitch_acc = pitch_acc_.as<float>(); a.pitch_dev = pitch_dev_.as<float>();
+    a.scene = scene_.as<float>(); a.tuning = tuning_.as<float>();
     a.o = outs;
     const int npad = (a.n_bins + 63) / 64 * 64;
     a.scratch_bytes = (unsigned)((std::max(peaks_scratch_bytes(a.n_bins, a.dist), peaks_lean_scratch_bytes(a.n_bins, a.dist)) + 15) / 16 * 16);
@@ -847,14 +812,8 @@ pvq_status AnalysisBatch::preprocess_device(const float* d_db, size_t n_frames, 
         const size_t rows = (size_t)n_streams_ * n_frames, words = (size_t)(a.n_bins + 31) / 32;
         const size_t b_mask = rows * words * sizeof(uint32_t), b_tun = rows * sizeof(float), b_sm = outs.x_vqt_smoothed ? 0 : rows * (size_t)a.n_bins * sizeof(float);
         const size_t need = b_mask + b_tun + b_sm + rows;
-        if (raw_cap_ < need) {
-            if (d_raw_) PVQ_HIP(hipFree(d_raw_));   // (synchronises the device: nothing still reads the old buffer)
-            d_raw_ = nullptr;
-            raw_cap_ = 0;
-            PVQ_HIP(hipMalloc(&d_raw_, need));
-            raw_cap_ = need;
-        }
-        char* wsb = static_cast<char*>(d_raw_);
+        if (pvq_status s = raw_.reserve(need)) return s;
+        char* wsb = raw_.as<char>();
         a.raw_mask = reinterpret_cast<const uint32_t*>(wsb);
         a.tuning_in = reinterpret_cast<float*>(wsb + b_mask);
         a.sm_rows = outs.x_vqt_smoothed ? outs.x_vqt_smoothed : reinterpret_cast<float*>(wsb + b_mask + b_tun);
@@ -919,20 +878,20 @@ pvq_status AnalysisBatch::get_field(uint32_t stream_index, int field, float* out
         set_last_error("stream index out of range or null output");
         return PVQ_ERR_INVALID_ARG;
     }
-    const float* src = nullptr;
+    const DeviceBuffer* src = nullptr;
     switch (field) {
-        case PVQ_FIELD_X_VQT_SMOOTHED: src = d_smoothed_; break;
-        case PVQ_FIELD_X_VQT_PEAKFILTERED: src = d_peakfiltered_; break;
-        case PVQ_FIELD_X_VQT_AFTERGLOW: src = d_afterglow_; break;
-        case PVQ_FIELD_CALMNESS: src = d_calm_; break;
-        case PVQ_FIELD_PITCH_ACCURACY: src = d_pitch_acc_; break;
-        case PVQ_FIELD_PITCH_DEVIATION: src = d_pitch_dev_; break;
+        case PVQ_FIELD_X_VQT_SMOOTHED: src = &smoothed_; break;
+        case PVQ_FIELD_X_VQT_PEAKFILTERED: src = &peakfiltered_; break;
+        case PVQ_FIELD_X_VQT_AFTERGLOW: src = &afterglow_; break;
+        case PVQ_FIELD_CALMNESS: src = &calm_; break;
+        case PVQ_FIELD_PITCH_ACCURACY: src = &pitch_acc_; break;
+        case PVQ_FIELD_PITCH_DEVIATION: src = &pitch_dev_; break;
         default: set_last_error("unknown field"); return PVQ_ERR_INVALID_ARG;
     }
     PVQ_HIP(hipSetDevice(device_id_));
     PVQ_HIP(hipDeviceSynchronize());
     const size_t n = range_.n_buckets();
-    PVQ_HIP(hipMemcpy(out, src + (size_t)stream_index * n, n * sizeof(float), hipMemcpyDeviceToHost));
+    PVQ_HIP(hipMemcpy(out, src->as<float>() + (size_t)stream_index * n, n * sizeof(float), hipMemcpyDeviceToHost));
     return PVQ_OK;
 }
 
@@ -943,8 +902,8 @@ pvq_status AnalysisBatch::get_scalars(uint32_t stream_index, float* scene_calmne
     }
     PVQ_HIP(hipSetDevice(device_id_));
     PVQ_HIP(hipDeviceSynchronize());
-    if (scene_calmness) PVQ_HIP(hipMemcpy(scene_calmness, d_scene_ + stream_index, sizeof(float), hipMemcpyDeviceToHost));
-    if (tuning_grid_inaccuracy) PVQ_HIP(hipMemcpy(tuning_grid_inaccuracy, d_tuning_ + stream_index, sizeof(float), hipMemcpyDeviceToHost));
+    if (scene_calmness) PVQ_HIP(hipMemcpy(scene_calmness, scene_.as<float>() + stream_index, sizeof(float), hipMemcpyDeviceToHost));
+    if (tuning_grid_inaccuracy) PVQ_HIP(hipMemcpy(tuning_grid_inaccuracy, tuning_.as<float>() + stream_index, sizeof(float), hipMemcpyDeviceToHost));
     return PVQ_OK;
 }
 

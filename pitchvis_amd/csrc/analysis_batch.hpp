@@ -17,6 +17,7 @@
 
 #include "../../include/pvq.h"
 #include "analysis_host.hpp"
+#include "device_support.hpp"
 
 namespace pvq {
 
@@ -67,19 +68,14 @@ class AnalysisBatch {
     bool smooth_has_ = true;   // x_vqt_smoothed[..] has a time horizon (update_vqt_smoothing_duration(None) clears it)
     uint32_t n_streams_ = 0;
     // device state: [n_streams][n_bins] each, then [n_streams]
-    float *d_smoothed_ = nullptr, *d_calm_ = nullptr, *d_released_ = nullptr, *d_afterglow_ = nullptr, *d_peakfiltered_ = nullptr;
-    float *d_pitch_acc_ = nullptr, *d_pitch_dev_ = nullptr;
-    float *d_scene_ = nullptr, *d_tuning_ = nullptr;
-    float* d_lnf_ = nullptr;           // ln(f_k), host libm (peak_detection.rs:81-86)
-    unsigned long long* d_times_ = nullptr;   // per-frame times of the running call
-    size_t times_cap_ = 0;
-    void* d_tab_ = nullptr;            // EMA weights of the running call (host libm), then the frames' row indices
-    size_t tab_cap_ = 0;
-    void* d_frames_ = nullptr;         // dB frames of pvq_analysis_batch_preprocess_pcm
-    size_t frames_cap_ = 0;
-    void* d_raw_ = nullptr;            // peak masks of the raw frames of the running call (frame-parallel pre-pass), then its scratch flags
-    size_t raw_cap_ = 0;
-    std::vector<float> tab_host_;      // what d_tab_ holds (constant frame time: reused by the next call without an upload)
+    DeviceBuffer smoothed_, calm_, released_, afterglow_, peakfiltered_, pitch_acc_, pitch_dev_;
+    DeviceBuffer scene_, tuning_;
+    DeviceBuffer lnf_;                 // ln(f_k), host libm (peak_detection.rs:81-86)
+    DeviceBuffer times_;               // grow-only: per-frame times (u64) of the running call
+    DeviceBuffer tab_;                 // grow-only: EMA weights of the running call (host libm), then the frames' row indices
+    DeviceBuffer frames_;              // grow-only: dB frames of pvq_analysis_batch_preprocess_pcm
+    DeviceBuffer raw_;                 // grow-only: peak masks of the raw frames of the running call (frame-parallel pre-pass), then its scratch flags
+    std::vector<float> tab_host_;      // what tab_ holds (constant frame time: reused by the next call without an upload)
 };
 
 }  // namespace pvq

@@ -18,24 +18,17 @@
 #include <string>
 #include <vector>
 
+#include "stage_device.hpp"
+#include "stage_plan.hpp"
 #include "vqt_engine.hpp"
 
 namespace pvq {
-
-#define PVQ_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_last_error(std::string(#call) + " failed: " + hipGetErrorString(e_));              \
-            return PVQ_ERR_DEVICE;                                                                 \
-        }                                                                                          \
-    } while (0)
 
 namespace {
 constexpr uint32_t MAX_BINS = 1024;
 constexpr size_t WORKSPACE_LIMIT = 256ull << 20;   // the lists of one piece of a call
 constexpr int LIST_THREADS = 256;
-constexpr int TILE = 16;                            // pixels a side of a workgroup's tile: 2 x 2 waves of 8 x 8
+constexpr int TILE = stage::TILE;
 constexpr uint32_t WORDS = sizeof(backdrop::Tri) / 16;   // 16-byte words a record
 
 struct BackdropArgs {
@@ -66,7 +59,7 @@ __global__ __launch_bounds__(LIST_THREADS) __attribute__((flatten)) void backdro
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const uint32_t rows = a.n_streams * a.pf;
     for (uint32_t r = blockIdx.x; r < rows; r += gridDim.x) {
-        const size_t g = static_cast<size_t>(r / a.pf) * a.n_frames + a.f0 + r % a.pf;
+        const size_t g = stage::piece_row(r, a.pf, a.n_frames, a.f0);
         if (tid == 0) s_base = 0u;
         __syncthreads();
         // the row's layers, in draw order: [0, e_line) line, [.., e_disc) discs, [.., e_graph) graph, [.., e_hist) histogram, bass
@@ -185,33 +178,21 @@ __device__ __forceinline__ void walk(const uint4* list, uint32_t m, uint32_t lan
 __global__ __launch_bounds__(256) __attribute__((flatten)) void backdrop_tiles(BackdropArgs a) {
 #pragma clang fp contract(off)
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    const uint32_t tiles_x = (a.W + TILE - 1) / TILE;
-    const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-    const uint32_t bx0 = tx * TILE + (wave & 1u) * 8u, by0 = ty * TILE + (wave >> 1) * 8u;   // the wave's 8 x 8 block
-    const uint32_t i = bx0 + (lane & 7u), j = by0 + (lane >> 3);
-    const bool inside = i < a.W && j < a.H;
-    float wx, wy;
-    raster::pixel_world(i, j, a.W, a.H, a.vh, wx, wy);
-    const size_t pixel = static_cast<size_t>(j) * a.W + i;
+    const stage::TilePixel px = stage::tile_pixel(wave, lane, a.W, a.H, a.vh);
     const uint32_t rows = a.n_streams * a.pf;
     for (uint32_t r = blockIdx.y; r < rows; r += gridDim.y) {
-        const size_t g = static_cast<size_t>(r / a.pf) * a.n_frames + a.f0 + r % a.pf;
+        const size_t g = stage::piece_row(r, a.pf, a.n_frames, a.f0);
         float dst[4] = {a.clear[0], a.clear[1], a.clear[2], a.clear[3]};
-        if (a.background && inside) {
-            const float4 bg = reinterpret_cast<const float4*>(a.background)[pixel];
+        if (a.background && px.inside) {
+            const float4 bg = reinterpret_cast<const float4*>(a.background)[px.pixel];
             dst[0] = bg.x; dst[1] = bg.y; dst[2] = bg.z; dst[3] = bg.w;
         }
-        walk(a.net, a.n_net, lane, bx0, by0, wx, wy, dst);
-        walk(a.list + static_cast<size_t>(r) * a.cap * WORDS, a.counts[r], lane, bx0, by0, wx, wy, dst);
-        if (inside) reinterpret_cast<float4*>(a.image)[g * a.W * a.H + pixel] = make_float4(dst[0], dst[1], dst[2], dst[3]);
+        walk(a.net, a.n_net, lane, px.bx0, px.by0, px.wx, px.wy, dst);
+        walk(a.list + static_cast<size_t>(r) * a.cap * WORDS, a.counts[r], lane, px.bx0, px.by0, px.wx, px.wy, dst);
+        if (px.inside) reinterpret_cast<float4*>(a.image)[g * a.W * a.H + px.pixel] = make_float4(dst[0], dst[1], dst[2], dst[3]);
     }
 }
 }  // namespace
-
-BackdropBatch::~BackdropBatch() {
-    for (void* p : {d_net_, static_cast<void*>(d_bass_), d_ws_})
-        if (p) (void)hipFree(p);
-}
 
 pvq_status BackdropBatch::create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, int visuals_mode, float viewport_height,
                                  uint32_t n_streams, uint32_t width, uint32_t height, std::unique_ptr<BackdropBatch>& out) {
@@ -220,16 +201,9 @@ pvq_status BackdropBatch::create(int device_id, uint32_t octaves, uint32_t bucke
         set_last_error("backdrop batch: octaves, buckets_per_octave and n_streams must be positive");
         return PVQ_ERR_INVALID_ARG;
     }
-    if (visuals_mode < scene::FULL || visuals_mode > scene::GALAXY) {
-        set_last_error("backdrop batch: unknown visuals mode");
-        return PVQ_ERR_INVALID_ARG;
-    }
-    if (width == 0 || height == 0 || width > raster::MAX_IMAGE || height > raster::MAX_IMAGE) {
-        set_last_error("backdrop batch: width and height are 1 .. 4096");
-        return PVQ_ERR_INVALID_ARG;
-    }
-    if (!(viewport_height >= 0.0f) || !raster::finite_f(viewport_height)) {
-        set_last_error("backdrop batch: viewport_height is 0 (the viewer's) or positive and finite");
+    std::string err;
+    if (!stage_mode_ok("backdrop batch", visuals_mode, err) || !stage_image_ok("backdrop batch", width, height, viewport_height, err)) {
+        set_last_error(err);
         return PVQ_ERR_INVALID_ARG;
     }
     const uint64_t n = static_cast<uint64_t>(octaves) * buckets_per_octave;
@@ -267,14 +241,11 @@ pvq_status BackdropBatch::create(int device_id, uint32_t octaves, uint32_t bucke
                 }
             }
             b->n_net_ = static_cast<uint32_t>(net.size());
-            if (b->n_net_) {
-                PVQ_HIP(hipMalloc(&b->d_net_, net.size() * sizeof(backdrop::Tri)));
-                PVQ_HIP(hipMemcpy(b->d_net_, net.data(), net.size() * sizeof(backdrop::Tri), hipMemcpyHostToDevice));
-            }
+            if (b->n_net_)
+                if (pvq_status s = b->net_.upload(net.data(), net.size() * sizeof(backdrop::Tri))) return s;
             const std::vector<float> bass = backdrop_geometry(octaves, backdrop::BASS);
             b->n_bass_ = backdrop::geometry_count(octaves, backdrop::BASS);
-            PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&b->d_bass_), bass.size() * sizeof(float)));
-            PVQ_HIP(hipMemcpy(b->d_bass_, bass.data(), bass.size() * sizeof(float), hipMemcpyHostToDevice));
+            if (pvq_status s = b->bass_.upload(bass.data(), bass.size() * sizeof(float))) return s;
         }
     }
     out = std::move(b);
@@ -314,8 +285,9 @@ pvq_status BackdropBatch::frames_device(size_t n_frames, const pvq_backdrop_inpu
         set_last_error("backdrop batch: max_peaks is too large");
         return PVQ_ERR_INVALID_ARG;
     }
-    if (n_frames > 0x7FFFFFFFull || n_frames * n_streams_ > 0x7FFFFFFFull) {
-        set_last_error("backdrop batch: too many frames in one call");
+    std::string err;
+    if (!stage_frames_ok("backdrop batch", n_frames, n_streams_, err)) {
+        set_last_error(err);
         return PVQ_ERR_INVALID_ARG;
     }
     if (device_id_ < 0) {
@@ -343,8 +315,8 @@ pvq_status BackdropBatch::frames_device(size_t n_frames, const pvq_backdrop_inpu
         a.clear[i] = clear_[i];
     }
     a.background = in.background;
-    a.bass_quads = d_bass_;
-    a.net = static_cast<const uint4*>(d_net_);
+    a.bass_quads = bass_.as<float>();
+    a.net = net_.as<uint4>();
     a.n_bass = n_bass_;
     a.n_net = n_net_;
     a.n_streams = n_streams_;
@@ -361,17 +333,10 @@ pvq_status BackdropBatch::frames_device(size_t n_frames, const pvq_backdrop_inpu
     // the lists of a piece of the call's frames fit the workspace
     const size_t per_row = static_cast<size_t>(cap) * sizeof(backdrop::Tri) + sizeof(uint32_t);
     const size_t limit = static_cast<size_t>(std::max(1, dev_knob("PVQ_BACKDROP_WS_KB", static_cast<int>(WORKSPACE_LIMIT >> 10)))) << 10;
-    const size_t pf = std::min<size_t>(n_frames, std::max<size_t>(1, limit / (per_row * n_streams_)));
+    const size_t pf = stage_piece_frames(n_frames, n_streams_, per_row, limit);
     const size_t rows_max = static_cast<size_t>(n_streams_) * pf;
-    const size_t need = per_row * rows_max;
-    if (need > ws_bytes_) {
-        if (d_ws_) PVQ_HIP(hipFree(d_ws_));   // (waits for the device)
-        d_ws_ = nullptr;
-        ws_bytes_ = 0;
-        PVQ_HIP(hipMalloc(&d_ws_, need));
-        ws_bytes_ = need;
-    }
-    a.list = static_cast<uint4*>(d_ws_);   // the 80-byte records first: the workspace is 256-byte aligned
+    if (pvq_status s = ws_.reserve(per_row * rows_max)) return s;
+    a.list = ws_.as<uint4>();   // the 80-byte records first: the workspace is 256-byte aligned
     a.counts = reinterpret_cast<uint32_t*>(a.list + rows_max * cap * WORDS);
     const uint32_t tiles = ((width_ + TILE - 1) / TILE) * ((height_ + TILE - 1) / TILE);
     for (size_t f0 = 0; f0 < n_frames; f0 += pf) {

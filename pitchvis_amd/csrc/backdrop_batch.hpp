@@ -12,6 +12,7 @@
 
 #include "../../include/pvq.h"
 #include "backdrop_host.hpp"
+#include "device_support.hpp"
 
 namespace pvq {
 
@@ -21,7 +22,6 @@ class BackdropBatch {
     // frames_device returns PVQ_ERR_NO_DEVICE after the argument checks.
     static pvq_status create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, int visuals_mode, float viewport_height,
                              uint32_t n_streams, uint32_t width, uint32_t height, std::unique_ptr<BackdropBatch>& out);
-    ~BackdropBatch();
     // n_frames frames of every stream.  Asynchronous on `stream`.
     pvq_status frames_device(size_t n_frames, const pvq_backdrop_inputs& in, float* d_image, hipStream_t stream);
 
@@ -33,10 +33,9 @@ class BackdropBatch {
     bool galaxy_ = false;
     float clear_[4] = {0.0f, 0.0f, 0.0f, 1.0f};
     uint32_t n_net_ = 0, n_bass_ = 0;   // the net's finished triangles that meet the image; the bass quads
-    void* d_net_ = nullptr;             // [n_net] backdrop::Tri, shared by all rows
-    float* d_bass_ = nullptr;           // [n_bass][4][2]
-    void* d_ws_ = nullptr;              // grow-only: the lists and counts of one piece of a call
-    size_t ws_bytes_ = 0;
+    DeviceBuffer net_;                  // [n_net] backdrop::Tri, shared by all rows
+    DeviceBuffer bass_;                 // [n_bass][4][2] floats
+    DeviceBuffer ws_;                   // grow-only: the lists and counts of one piece of a call
 };
 
 }  // namespace pvq

@@ -13,15 +13,6 @@
 
 namespace pvq {
 
-#define PVQ_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_last_error(std::string(#call) + " failed: " + hipGetErrorString(e_));              \
-            return PVQ_ERR_DEVICE;                                                                 \
-        }                                                                                          \
-    } while (0)
-
 static_assert(sizeof(Float2) == sizeof(float2) && alignof(Float2) == alignof(float2), "blockdft_plan.hpp: Float2 must match float2");
 static_assert(sizeof(Float4) == sizeof(float4) && alignof(Float4) == alignof(float4), "blockdft_plan.hpp: Float4 must match float4");
 static_assert(sizeof(Int4) == sizeof(int4) && alignof(Int4) == alignof(int4), "blockdft_plan.hpp: Int4 must match int4");

@@ -26,6 +26,7 @@
 #include "render_batch.hpp"
 #include "scene_batch.hpp"
 #include "scene_host.hpp"
+#include "stage_plan.hpp"
 #include "vqt_engine.hpp"
 
 struct pvq_vqt {
@@ -917,15 +918,6 @@ pvq_status pvq_npy_write_f32(const char* path, const float* data, uint64_t n) {
     } catch (...) { return translate_exception(); }
 }
 
-#define PVQ_CAPI_HIP(call)                                                                  \
-    do {                                                                                    \
-        hipError_t e_ = (call);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            pvq::set_last_error(std::string(#call) + " failed: " + hipGetErrorString(e_));  \
-            return PVQ_ERR_DEVICE;                                                          \
-        }                                                                                   \
-    } while (0)
-
 pvq_status pvq_stream_create(pvq_vqt* v, size_t buf_size, int with_agc, pvq_stream** out) {
     try {
         if (!v || !out) return null_handle();
@@ -944,14 +936,14 @@ pvq_status pvq_stream_create(pvq_vqt* v, size_t buf_size, int with_agc, pvq_stre
         s->buf_size = buf_size;
         s->cap = 4 * buf_size;
         s->with_agc = with_agc != 0;
-        PVQ_CAPI_HIP(hipSetDevice(v->impl->device()));
-        PVQ_CAPI_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_ring), s->cap * sizeof(float)));
-        PVQ_CAPI_HIP(hipMemset(s->d_ring, 0, s->cap * sizeof(float)));
-        PVQ_CAPI_HIP(hipStreamSynchronize(nullptr));   // (the object's own stream does not wait for the null stream)
-        PVQ_CAPI_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_db), v->impl->n_bins() * sizeof(float)));
-        PVQ_CAPI_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-        PVQ_CAPI_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_in), buf_size * sizeof(float), hipHostMallocDefault));
-        PVQ_CAPI_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_out), v->impl->n_bins() * sizeof(float), hipHostMallocDefault));
+        PVQ_HIP(hipSetDevice(v->impl->device()));
+        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_ring), s->cap * sizeof(float)));
+        PVQ_HIP(hipMemset(s->d_ring, 0, s->cap * sizeof(float)));
+        PVQ_HIP(hipStreamSynchronize(nullptr));   // (the object's own stream does not wait for the null stream)
+        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_db), v->impl->n_bins() * sizeof(float)));
+        PVQ_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+        PVQ_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_in), buf_size * sizeof(float), hipHostMallocDefault));
+        PVQ_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_out), v->impl->n_bins() * sizeof(float), hipHostMallocDefault));
         s->w = buf_size;
         *out = s.release();
         return PVQ_OK;
@@ -972,9 +964,9 @@ pvq_status pvq_stream_push(pvq_stream* s, const float* data, size_t n) {
             pvq::set_last_error("chunk longer than the ring buffer");
             return PVQ_ERR_BAD_LENGTH;
         }
-        PVQ_CAPI_HIP(hipSetDevice(s->vqt->impl->device()));
+        PVQ_HIP(hipSetDevice(s->vqt->impl->device()));
         if (s->in_flight) {   // a second push before the previous one's copy was waited for (no frame in between)
-            PVQ_CAPI_HIP(hipStreamSynchronize(s->stream));
+            PVQ_HIP(hipStreamSynchronize(s->stream));
             s->in_flight = false;
         }
         std::copy(data, data + n, s->h_in);
@@ -986,10 +978,10 @@ pvq_status pvq_stream_push(pvq_stream* s, const float* data, size_t n) {
             s->gain = s->agc.gain();                                    // :112
         }
         if (s->w + n > s->cap) {   // compact: newest buf_size samples to the front (ranges do not overlap: cap = 4 buf_size)
-            PVQ_CAPI_HIP(hipMemcpyAsync(s->d_ring, s->d_ring + s->w - s->buf_size, s->buf_size * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+            PVQ_HIP(hipMemcpyAsync(s->d_ring, s->d_ring + s->w - s->buf_size, s->buf_size * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
             s->w = s->buf_size;
         }
-        PVQ_CAPI_HIP(hipMemcpyAsync(s->d_ring + s->w, s->h_in, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+        PVQ_HIP(hipMemcpyAsync(s->d_ring + s->w, s->h_in, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
         s->in_flight = true;
         s->w += n;
         s->chunk_size_ms = static_cast<float>(n) / s->vqt->impl->params().sr * 1000.0f;   // :118
@@ -1014,8 +1006,8 @@ pvq_status pvq_stream_frame_db(pvq_stream* s, float* out_db) {
         pvq_status st = s->vqt->impl->calculate_batch_db_device(s->d_ring + s->w - n_fft, n_fft - 1, 1, 1, s->d_db, nullptr, s->stream);
         if (st != PVQ_OK) return st;
         const size_t nb = s->vqt->impl->n_bins();
-        PVQ_CAPI_HIP(hipMemcpyAsync(s->h_out, s->d_db, nb * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-        PVQ_CAPI_HIP(hipStreamSynchronize(s->stream));
+        PVQ_HIP(hipMemcpyAsync(s->h_out, s->d_db, nb * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        PVQ_HIP(hipStreamSynchronize(s->stream));
         s->in_flight = false;
         std::copy(s->h_out, s->h_out + nb, out_db);
         return PVQ_OK;
@@ -1028,10 +1020,10 @@ pvq_status pvq_stream_read(pvq_stream* s, float* out, size_t n_last) {
             pvq::set_last_error("n_last exceeds the ring buffer");
             return PVQ_ERR_BAD_LENGTH;
         }
-        PVQ_CAPI_HIP(hipSetDevice(s->vqt->impl->device()));
-        PVQ_CAPI_HIP(hipStreamSynchronize(s->stream));   // the appends queued on the object's stream
+        PVQ_HIP(hipSetDevice(s->vqt->impl->device()));
+        PVQ_HIP(hipStreamSynchronize(s->stream));   // the appends queued on the object's stream
         s->in_flight = false;
-        PVQ_CAPI_HIP(hipMemcpy(out, s->d_ring + s->w - n_last, n_last * sizeof(float), hipMemcpyDeviceToHost));
+        PVQ_HIP(hipMemcpy(out, s->d_ring + s->w - n_last, n_last * sizeof(float), hipMemcpyDeviceToHost));
         return PVQ_OK;
     } catch (...) { return translate_exception(); }
 }
@@ -1261,16 +1253,9 @@ pvq_status pvq_raster_frame(uint32_t n_bins, uint32_t width, uint32_t height, fl
             pvq::set_last_error("raster frame: the five ball arrays and image_out are needed");
             return PVQ_ERR_INVALID_ARG;
         }
-        if (width == 0 || height == 0 || width > pvq::raster::MAX_IMAGE || height > pvq::raster::MAX_IMAGE) {
-            pvq::set_last_error("raster frame: width and height are 1 .. 4096");
-            return PVQ_ERR_INVALID_ARG;
-        }
-        if (!(viewport_height >= 0.0f) || !pvq::raster::finite_f(viewport_height)) {
-            pvq::set_last_error("raster frame: viewport_height is 0 (the viewer's) or positive and finite");
-            return PVQ_ERR_INVALID_ARG;
-        }
-        if (visuals_mode < pvq::scene::FULL || visuals_mode > pvq::scene::GALAXY) {
-            pvq::set_last_error("raster frame: unknown visuals mode");
+        std::string err;
+        if (!pvq::stage_image_ok("raster frame", width, height, viewport_height, err) || !pvq::stage_mode_ok("raster frame", visuals_mode, err)) {
+            pvq::set_last_error(err);
             return PVQ_ERR_INVALID_ARG;
         }
         pvq::raster_frame(n_bins, width, height, viewport_height == 0.0f ? pvq::raster::VIEWPORT_HEIGHT : viewport_height, visuals_mode,
@@ -1432,17 +1417,6 @@ pvq_status pvq_panels_batch_get_history(pvq_panels_batch* b, uint32_t stream_ind
 
 // The picture behind the balls — spider net, debug panels, lit bass spiral (setup.rs:127-222, update.rs:369-425, :474-869 as pixels):
 // one frame on the host (backdrop_host.hpp) and many streams on the device (backdrop_batch.hpp)
-static bool backdrop_image_args(const char* who, uint32_t width, uint32_t height, float viewport_height) {
-    if (width == 0 || height == 0 || width > pvq::raster::MAX_IMAGE || height > pvq::raster::MAX_IMAGE) {
-        pvq::set_last_error(std::string(who) + ": width and height are 1 .. 4096");
-        return false;
-    }
-    if (!(viewport_height >= 0.0f) || !pvq::raster::finite_f(viewport_height)) {
-        pvq::set_last_error(std::string(who) + ": viewport_height is 0 (the viewer's) or positive and finite");
-        return false;
-    }
-    return true;
-}
 pvq_status pvq_backdrop_geometry(uint32_t octaves, int what, float* quads_out, uint32_t* n_out) {
     try {
         if (octaves == 0 || octaves > 1024 || what < pvq::backdrop::NET_SPIRAL || what > pvq::backdrop::BASS) {
@@ -1463,7 +1437,11 @@ pvq_status pvq_backdrop_panel_transforms(uint32_t n_bins, uint32_t width, uint32
             pvq::set_last_error("backdrop panel transforms: out is needed");
             return PVQ_ERR_INVALID_ARG;
         }
-        if (!backdrop_image_args("backdrop panel transforms", width, height, viewport_height)) return PVQ_ERR_INVALID_ARG;
+        std::string err;
+        if (!pvq::stage_image_ok("backdrop panel transforms", width, height, viewport_height, err)) {
+            pvq::set_last_error(err);
+            return PVQ_ERR_INVALID_ARG;
+        }
         pvq::backdrop::panel_transforms(n_bins, width, height, viewport_height == 0.0f ? pvq::raster::VIEWPORT_HEIGHT : viewport_height, out);
         return PVQ_OK;
     } catch (...) { return translate_exception(); }
@@ -1475,7 +1453,11 @@ pvq_status pvq_backdrop_draw_mesh(uint32_t width, uint32_t height, float viewpor
             pvq::set_last_error("backdrop draw mesh: image_inout is needed, and pos and rgba with n_triangles > 0");
             return PVQ_ERR_INVALID_ARG;
         }
-        if (!backdrop_image_args("backdrop draw mesh", width, height, viewport_height)) return PVQ_ERR_INVALID_ARG;
+        std::string err;
+        if (!pvq::stage_image_ok("backdrop draw mesh", width, height, viewport_height, err)) {
+            pvq::set_last_error(err);
+            return PVQ_ERR_INVALID_ARG;
+        }
         pvq::backdrop_draw_mesh(width, height, viewport_height == 0.0f ? pvq::raster::VIEWPORT_HEIGHT : viewport_height, n_triangles, pos, rgba,
                                 transform, image_inout);
         return PVQ_OK;
@@ -1494,9 +1476,9 @@ pvq_status pvq_backdrop_frame(uint32_t octaves, uint32_t buckets_per_octave, uin
             pvq::set_last_error("backdrop frame: octaves 1 .. 1024, buckets_per_octave positive, at least two bins");
             return PVQ_ERR_INVALID_ARG;
         }
-        if (!backdrop_image_args("backdrop frame", width, height, viewport_height)) return PVQ_ERR_INVALID_ARG;
-        if (visuals_mode < pvq::scene::FULL || visuals_mode > pvq::scene::GALAXY) {
-            pvq::set_last_error("backdrop frame: unknown visuals mode");
+        std::string err;
+        if (!pvq::stage_image_ok("backdrop frame", width, height, viewport_height, err) || !pvq::stage_mode_ok("backdrop frame", visuals_mode, err)) {
+            pvq::set_last_error(err);
             return PVQ_ERR_INVALID_ARG;
         }
         if (panels && (!panels->line_pos != !panels->line_rgba || !panels->disc_pos != !panels->disc_rgba ||

@@ -23,15 +23,6 @@
 
 namespace pvq {
 
-#define PVQ_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_last_error(std::string(#call) + " failed: " + hipGetErrorString(e_));              \
-            return PVQ_ERR_DEVICE;                                                                 \
-        }                                                                                          \
-    } while (0)
-
 struct CondStream {
     const float* left;
     const float* right;   // null: mono
@@ -282,12 +273,6 @@ __global__ __launch_bounds__(64) void cond_recurrence(CondArgs a) {
 }
 }  // namespace
 
-AgcBatch::~AgcBatch() {
-    if (d_gain_) (void)hipFree(d_gain_);
-    if (d_tab_) (void)hipFree(d_tab_);
-    if (d_frozen_) (void)hipFree(d_frozen_);
-}
-
 pvq_status AgcBatch::create(int device_id, uint32_t n_streams, float desired_output_rms, float distortion_factor, std::unique_ptr<AgcBatch>& out) {
     out.reset();
     std::string why;
@@ -306,10 +291,9 @@ pvq_status AgcBatch::create(int device_id, uint32_t n_streams, float desired_out
     b->distortion_factor_ = distortion_factor;
     if (device_id >= 0) {
         PVQ_HIP(hipSetDevice(device_id));
-        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&b->d_gain_), n_streams * sizeof(float)));
-        PVQ_HIP(hipMalloc(&b->d_tab_, n_streams * sizeof(CondStream)));
         const std::vector<float> ones(n_streams, 1.0f);   // lib.rs:50: gain = 1
-        PVQ_HIP(hipMemcpy(b->d_gain_, ones.data(), n_streams * sizeof(float), hipMemcpyHostToDevice));
+        if (pvq_status s = b->gain_.upload(ones.data(), n_streams * sizeof(float))) return s;
+        if (pvq_status s = b->tab_.reserve(n_streams * sizeof(CondStream))) return s;
     }
     out = std::move(b);
     return PVQ_OK;
@@ -350,22 +334,15 @@ pvq_status AgcBatch::condition_device(const float* const* d_left, const float* c
     }
     if (max_chunks == 0) return PVQ_OK;
     PVQ_HIP(hipSetDevice(device_id_));
-    const size_t need = (size_t)n_streams_ * max_chunks;
-    if (frozen_cap_ < need) {
-        if (d_frozen_) PVQ_HIP(hipFree(d_frozen_));   // (synchronises the device: nothing still reads the old buffer)
-        d_frozen_ = nullptr;
-        frozen_cap_ = 0;
-        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&d_frozen_), need));
-        frozen_cap_ = need;
-    }
-    PVQ_HIP(hipMemcpyAsync(d_tab_, tab.data(), tab.size() * sizeof(CondStream), hipMemcpyHostToDevice, stream));   // (pageable source: staged before the call returns)
+    if (pvq_status s = frozen_.reserve((size_t)n_streams_ * max_chunks)) return s;
+    PVQ_HIP(hipMemcpyAsync(tab_.as<void>(), tab.data(), tab.size() * sizeof(CondStream), hipMemcpyHostToDevice, stream));   // (pageable source: staged before the call returns)
     CondArgs a{};
-    a.tab = static_cast<const CondStream*>(d_tab_);
+    a.tab = tab_.as<CondStream>();
     a.n_streams = n_streams_;
     a.max_chunks = (uint32_t)max_chunks;
     a.chunk = chunk;
-    a.frozen = d_frozen_;
-    a.gain = d_gain_;
+    a.frozen = frozen_.as<uint8_t>();
+    a.gain = gain_.as<float>();
     a.gain_out = d_gain_out;
     a.gain_stride = gain_stride;
     a.rms = desired_output_rms_;
@@ -391,7 +368,7 @@ pvq_status AgcBatch::get_gains(float* gains) {
     }
     PVQ_HIP(hipSetDevice(device_id_));
     PVQ_HIP(hipDeviceSynchronize());
-    PVQ_HIP(hipMemcpy(gains, d_gain_, n_streams_ * sizeof(float), hipMemcpyDeviceToHost));
+    PVQ_HIP(hipMemcpy(gains, gain_.as<float>(), n_streams_ * sizeof(float), hipMemcpyDeviceToHost));
     return PVQ_OK;
 }
 

@@ -14,6 +14,7 @@
 #include <memory>
 
 #include "../../include/pvq.h"
+#include "device_support.hpp"
 
 namespace pvq {
 
@@ -22,7 +23,6 @@ class AgcBatch {
     // n_streams MonoAgc::new(desired_output_rms, distortion_factor) (lib.rs:35-53).  The arguments are checked before any device is
     // touched (MonoAgc::valid, the reference's texts); device_id < 0: a host-only object whose condition_device returns PVQ_ERR_NO_DEVICE.
     static pvq_status create(int device_id, uint32_t n_streams, float desired_output_rms, float distortion_factor, std::unique_ptr<AgcBatch>& out);
-    ~AgcBatch();
     uint32_t n_streams() const { return n_streams_; }
     int device() const { return device_id_; }
     // train.rs:286-301 for every stream.  d_left / d_right / d_mono_out: HOST arrays of n_streams device pointers (d_right null, or an
@@ -39,10 +39,9 @@ class AgcBatch {
     int device_id_ = -1;
     uint32_t n_streams_ = 0;
     float desired_output_rms_ = 0.0f, distortion_factor_ = 0.0f;
-    float* d_gain_ = nullptr;    // [n_streams]: MonoAgc::gain
-    void* d_tab_ = nullptr;      // [n_streams] stream descriptors of the running call
-    uint8_t* d_frozen_ = nullptr;   // [max_chunks][n_streams]: the gate of every chunk of the running call
-    size_t frozen_cap_ = 0;
+    DeviceBuffer gain_;      // [n_streams] floats: MonoAgc::gain
+    DeviceBuffer tab_;       // [n_streams] stream descriptors of the running call
+    DeviceBuffer frozen_;    // grow-only: [max_chunks][n_streams] bytes: the gate of every chunk of the running call
 };
 
 }  // namespace pvq

@@ -21,15 +21,6 @@
 
 namespace pvq {
 
-#define PVQ_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_last_error(std::string(#call) + " failed: " + hipGetErrorString(e_));              \
-            return PVQ_ERR_DEVICE;                                                                 \
-        }                                                                                          \
-    } while (0)
-
 namespace {
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
@@ -304,24 +295,17 @@ __global__ __launch_bounds__(NM_THREADS, 2) void nm_dense(const NmArgs a) {
     if (active) epilogue<ACT>(a, tile, tile_local, ct, wave, lane, acc);
 }
 
-pvq_status upload(const std::vector<float>& packed, const float* bias, uint32_t n_bias, float*& d, size_t& bias_at) {
+pvq_status upload(const std::vector<float>& packed, const float* bias, uint32_t n_bias, DeviceBuffer& d, size_t& bias_at) {
     bias_at = packed.size();
-    PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&d), (packed.size() + n_bias) * sizeof(float)));
-    PVQ_HIP(hipMemcpy(d, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-    PVQ_HIP(hipMemcpy(d + bias_at, bias, n_bias * sizeof(float), hipMemcpyHostToDevice));
+    if (pvq_status s = d.reserve((packed.size() + n_bias) * sizeof(float))) return s;
+    PVQ_HIP(hipMemcpy(d.as<float>(), packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
+    PVQ_HIP(hipMemcpy(d.as<float>() + bias_at, bias, n_bias * sizeof(float), hipMemcpyHostToDevice));
     return PVQ_OK;
 }
 }  // namespace
 
 NoteModel::~NoteModel() {
-    if (device_id_ < 0) return;
-    (void)hipSetDevice(device_id_);
-    if (d_conv_) (void)hipFree(d_conv_);
-    if (d_fc1_) (void)hipFree(d_fc1_);
-    for (float* p : d_layer_)
-        if (p) (void)hipFree(p);
-    if (d_out_) (void)hipFree(d_out_);
-    if (d_ws_) (void)hipFree(d_ws_);
+    if (device_id_ >= 0) (void)hipSetDevice(device_id_);   // the buffers go after this body, with their device set
 }
 
 pvq_status NoteModel::create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
@@ -342,12 +326,12 @@ pvq_status NoteModel::create(int device_id, const pvq_note_model_params* params,
         const NoteModelHost& h = m->host_;
         std::vector<float> conv(h.conv_w);
         size_t at = 0;
-        pvq_status s = upload(conv, h.conv_b.data(), NM_CH, m->d_conv_, at);
-        if (s == PVQ_OK) s = upload(note_model_pack_b(h.fc1_w.data(), d.mlp, d.n_features, true, d.o_pool), h.fc1_b.data(), d.mlp, m->d_fc1_, m->fc1_bias_at_);
-        m->d_layer_.assign(d.layers, nullptr);
+        pvq_status s = upload(conv, h.conv_b.data(), NM_CH, m->conv_, at);
+        if (s == PVQ_OK) s = upload(note_model_pack_b(h.fc1_w.data(), d.mlp, d.n_features, true, d.o_pool), h.fc1_b.data(), d.mlp, m->fc1_, m->fc1_bias_at_);
+        m->layer_ = std::vector<DeviceBuffer>(d.layers);
         for (uint32_t i = 0; s == PVQ_OK && i < d.layers; ++i)
-            s = upload(note_model_pack_b(h.layer_w[i].data(), d.mlp, d.mlp, false, 0), h.layer_b[i].data(), d.mlp, m->d_layer_[i], m->layer_bias_at_);
-        if (s == PVQ_OK) s = upload(note_model_pack_b(h.out_w.data(), NM_OUT, d.mlp, false, 0), h.out_b.data(), NM_OUT, m->d_out_, m->out_bias_at_);
+            s = upload(note_model_pack_b(h.layer_w[i].data(), d.mlp, d.mlp, false, 0), h.layer_b[i].data(), d.mlp, m->layer_[i], m->layer_bias_at_);
+        if (s == PVQ_OK) s = upload(note_model_pack_b(h.out_w.data(), NM_OUT, d.mlp, false, 0), h.out_b.data(), NM_OUT, m->out_, m->out_bias_at_);
         if (s != PVQ_OK) return s;
     }
     out = std::move(m);
@@ -394,17 +378,10 @@ pvq_status NoteModel::rows_device(const float* d_db, const size_t* n_frames, uin
     const uint32_t n_ct_mlp = (d.mlp + NM_BN - 1) / NM_BN;
     size_t chunk_tiles = ws_limit_ > tab_bytes ? (ws_limit_ - tab_bytes) / tile_bytes : 0;
     chunk_tiles = std::max<size_t>(1, std::min<size_t>({chunk_tiles, tiles.size(), 0x7fffffffull / std::max<uint32_t>(n_ct_mlp, NM_OUT / NM_BN)}));
-    const size_t need = tab_bytes + chunk_tiles * tile_bytes;
-    if (ws_bytes_ < need) {
-        if (d_ws_) PVQ_HIP(hipFree(d_ws_));   // (synchronises the device: nothing still reads the old buffer)
-        d_ws_ = nullptr;
-        ws_bytes_ = 0;
-        PVQ_HIP(hipMalloc(&d_ws_, need));
-        ws_bytes_ = need;
-    }
-    NmTile* d_tiles = static_cast<NmTile*>(d_ws_);
+    if (pvq_status s = ws_.reserve(tab_bytes + chunk_tiles * tile_bytes)) return s;
+    NmTile* d_tiles = ws_.as<NmTile>();
     float* buf[2];
-    buf[0] = reinterpret_cast<float*>(static_cast<char*>(d_ws_) + tab_bytes);
+    buf[0] = reinterpret_cast<float*>(ws_.as<char>() + tab_bytes);
     buf[1] = buf[0] + chunk_tiles * NM_BM * d.mlp;
     PVQ_HIP(hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(NmTile), hipMemcpyHostToDevice, stream));   // (pageable source: staged before the call returns)
 
@@ -418,9 +395,9 @@ pvq_status NoteModel::rows_device(const float* d_db, const size_t* n_frames, uin
         a.L = d.L;
         // fc1 over the fused conv
         a.db = d_db;
-        a.conv = d_conv_;
-        a.b_packed = reinterpret_cast<const float4*>(d_fc1_);
-        a.bias = d_fc1_ + fc1_bias_at_;
+        a.conv = conv_.as<float>();
+        a.b_packed = fc1_.as<float4>();
+        a.bias = fc1_.as<float>() + fc1_bias_at_;
         a.h_out = buf[0];
         a.chunks = d.o_pool;
         a.k = d.n_features;
@@ -433,15 +410,15 @@ pvq_status NoteModel::rows_device(const float* d_db, const size_t* n_frames, uin
         for (uint32_t i = 0; i < d.layers; ++i) {
             a.a_in = buf[cur];
             a.h_out = buf[cur ^ 1];
-            a.b_packed = reinterpret_cast<const float4*>(d_layer_[i]);
-            a.bias = d_layer_[i] + layer_bias_at_;
+            a.b_packed = layer_[i].as<float4>();
+            a.bias = layer_[i].as<float>() + layer_bias_at_;
             hipLaunchKernelGGL(nm_dense<0>, dim3(nt * a.n_ct), dim3(NM_THREADS), 0, stream, a);
             cur ^= 1;
         }
         a.a_in = buf[cur];
         a.h_out = nullptr;
-        a.b_packed = reinterpret_cast<const float4*>(d_out_);
-        a.bias = d_out_ + out_bias_at_;
+        a.b_packed = out_.as<float4>();
+        a.bias = out_.as<float>() + out_bias_at_;
         a.n = NM_OUT;
         a.n_ct = NM_OUT / NM_BN;
         a.prob = outs.d_prob;

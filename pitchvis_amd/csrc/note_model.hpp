@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/pvq.h"
+#include "device_support.hpp"
 #include "note_model_plan.hpp"
 
 namespace pvq {
@@ -42,13 +43,12 @@ class NoteModel {
     int device_id_ = -1;
     NoteModelHost host_;
     uint64_t ws_limit_ = 256ull << 20;
-    float* d_conv_ = nullptr;              // conv weights [16][5], then bias [16]
-    float* d_fc1_ = nullptr;               // packed B operand, then bias [mlp]
-    std::vector<float*> d_layer_;          // packed B operand, then bias [mlp], per hidden layer
-    float* d_out_ = nullptr;               // packed B operand, then bias [128]
+    DeviceBuffer conv_;                    // floats: conv weights [16][5], then bias [16]
+    DeviceBuffer fc1_;                     // floats: packed B operand, then bias [mlp]
+    std::vector<DeviceBuffer> layer_;      // floats: packed B operand, then bias [mlp], per hidden layer
+    DeviceBuffer out_;                     // floats: packed B operand, then bias [128]
     size_t fc1_bias_at_ = 0, layer_bias_at_ = 0, out_bias_at_ = 0;   // float offsets of the biases
-    void* d_ws_ = nullptr;                 // tile table, then two [chunk rows][mlp] activation buffers
-    size_t ws_bytes_ = 0;
+    DeviceBuffer ws_;                      // grow-only: tile table, then two [chunk rows][mlp] activation buffers
 };
 
 }  // namespace pvq

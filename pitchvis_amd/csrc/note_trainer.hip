@@ -22,15 +22,6 @@
 
 namespace pvq {
 
-#define PVQ_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_last_error(std::string(#call) + " failed: " + hipGetErrorString(e_));              \
-            return PVQ_ERR_DEVICE;                                                                 \
-        }                                                                                          \
-    } while (0)
-
 namespace {
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
@@ -471,10 +462,6 @@ NoteTrainer::~NoteTrainer() {
         if (idx_copied_[s]) (void)hipEventDestroy(idx_copied_[s]);
         if (h_idx_[s]) (void)hipHostFree(h_idx_[s]);
     }
-    if (d_arena_) (void)hipFree(d_arena_);
-    if (d_ws_) (void)hipFree(d_ws_);
-    if (d_test_rows_) (void)hipFree(d_test_rows_);
-    if (d_test_out_) (void)hipFree(d_test_out_);
     if (h_test_out_) (void)hipHostFree(h_test_out_);
 }
 
@@ -498,9 +485,9 @@ pvq_status NoteTrainer::create(int device_id, const pvq_note_model_params* param
         PVQ_HIP(hipSetDevice(device_id));
         const size_t n = t->lay_.n_params;
         const std::vector<float> arena = note_trainer_arena(t->lay_, *weights);
-        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_arena_), 4 * n * sizeof(float)));
-        PVQ_HIP(hipMemcpy(t->d_arena_, arena.data(), n * sizeof(float), hipMemcpyHostToDevice));
-        PVQ_HIP(hipMemset(t->d_arena_ + n, 0, 3 * n * sizeof(float)));
+        if (pvq_status s = t->arena_.reserve(4 * n * sizeof(float))) return s;
+        PVQ_HIP(hipMemcpy(t->arena_.as<float>(), arena.data(), n * sizeof(float), hipMemcpyHostToDevice));
+        PVQ_HIP(hipMemset(t->arena_.as<float>() + n, 0, 3 * n * sizeof(float)));
         // the workspace, sized once from max_batch
         const size_t B = max_batch;
         size_t at = 0;
@@ -519,7 +506,7 @@ pvq_status NoteTrainer::create(int device_id, const pvq_note_model_params* param
         t->ws_rowloss_ = take(2 * B);   // doubles
         t->ws_part_ = take(NT_PART_FLOATS);
         t->ws_idx_ = take(B);           // uint32
-        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_ws_), at * sizeof(float)));
+        if (pvq_status s = t->ws_.reserve(at * sizeof(float))) return s;
         for (int s = 0; s < 2; ++s) {
             PVQ_HIP(hipHostMalloc(reinterpret_cast<void**>(&t->h_idx_[s]), B * sizeof(uint32_t), hipHostMallocDefault));
             PVQ_HIP(hipEventCreateWithFlags(&t->idx_copied_[s], hipEventDisableTiming));
@@ -534,7 +521,7 @@ pvq_status NoteTrainer::upload_idx(const uint32_t* idx, uint32_t rows, hipStream
     const int slot = static_cast<int>(calls_++ & 1);
     if (idx_pending_[slot]) PVQ_HIP(hipEventSynchronize(idx_copied_[slot]));
     std::memcpy(h_idx_[slot], idx, rows * sizeof(uint32_t));
-    uint32_t* d_idx = reinterpret_cast<uint32_t*>(d_ws_ + ws_idx_);
+    uint32_t* d_idx = reinterpret_cast<uint32_t*>(ws(ws_idx_));
     PVQ_HIP(hipMemcpyAsync(d_idx, h_idx_[slot], rows * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     PVQ_HIP(hipEventRecord(idx_copied_[slot], stream));
     idx_pending_[slot] = true;
@@ -544,13 +531,13 @@ pvq_status NoteTrainer::upload_idx(const uint32_t* idx, uint32_t rows, hipStream
 // forward (train.py:87-99)
 void NoteTrainer::forward(const float* d_db, uint32_t batch, bool train, hipStream_t stream) {
     const NoteModelDims& d = lay_.d;
-    const float* w = d_arena_;
-    const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d_ws_ + ws_idx_);
-    float* feat = d_ws_ + ws_feat_;
+    const float* w = arena_.as<float>();
+    const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(ws(ws_idx_));
+    float* feat = ws(ws_feat_);
     const size_t h_stride = round64(static_cast<size_t>(max_batch_) * d.mlp);
-    auto H = [&](uint32_t i) { return d_ws_ + ws_h_ + i * h_stride; };
-    float* Z = d_ws_ + ws_z_;
-    float* part = d_ws_ + ws_part_;
+    auto H = [&](uint32_t i) { return ws(ws_h_) + i * h_stride; };
+    float* Z = ws(ws_z_);
+    float* part = ws(ws_part_);
     const uint32_t F = d.n_features, mlp = d.mlp;
     const uint32_t threshold = nt_keep_threshold(hyper_.dropout);
     const bool drop = train && threshold > 0;
@@ -593,20 +580,20 @@ pvq_status NoteTrainer::step(int mode, const float* d_db, const float* d_targets
     PVQ_HIP(hipSetDevice(device_id_));
     const pvq_status up = upload_idx(idx, batch, stream);
     if (up != PVQ_OK) return up;
-    const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d_ws_ + ws_idx_);
+    const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(ws(ws_idx_));
 
     const size_t n = lay_.n_params;
-    const float* w = d_arena_;
-    float* grad = d_arena_ + n;
-    float* feat = d_ws_ + ws_feat_;
-    float* dfeat = d_ws_ + ws_dfeat_;
+    const float* w = arena_.as<float>();
+    float* grad = arena_.as<float>() + n;
+    float* feat = ws(ws_feat_);
+    float* dfeat = ws(ws_dfeat_);
     const size_t h_stride = round64(static_cast<size_t>(max_batch_) * d.mlp);
-    auto H = [&](uint32_t i) { return d_ws_ + ws_h_ + i * h_stride; };
-    float* dA[2] = {d_ws_ + ws_da_, d_ws_ + ws_da_ + h_stride};
-    float* Z = d_ws_ + ws_z_;
-    float* dZ = d_ws_ + ws_dz_;
-    float* part = d_ws_ + ws_part_;
-    double* row_loss = reinterpret_cast<double*>(d_ws_ + ws_rowloss_);
+    auto H = [&](uint32_t i) { return ws(ws_h_) + i * h_stride; };
+    float* dA[2] = {ws(ws_da_), ws(ws_da_) + h_stride};
+    float* Z = ws(ws_z_);
+    float* dZ = ws(ws_dz_);
+    float* part = ws(ws_part_);
+    double* row_loss = reinterpret_cast<double*>(ws(ws_rowloss_));
     const uint32_t F = d.n_features, mlp = d.mlp;
     const bool train = mode != PVQ_TRAIN_EVAL;
     const bool drop = train && nt_keep_threshold(hyper_.dropout) > 0;
@@ -641,15 +628,15 @@ pvq_status NoteTrainer::step(int mode, const float* d_db, const float* d_targets
         gemm(G_TN, dA[cur], feat, grad + lay_.fc1_w.at, mlp, F, batch, mlp, F, raw, part, stream);
         hipLaunchKernelGGL(nt_bias_grad, dim3((mlp + 63) / 64), dim3(NT_THREADS), 0, stream, dA[cur], grad + lay_.fc1_b.at, batch, mlp);
         gemm(G_NN, dA[cur], w + lay_.fc1_w.at, dfeat, batch, F, mlp, mlp, F, raw, part, stream);
-        float* conv_part = d_ws_ + ws_convpart_;
+        float* conv_part = ws(ws_convpart_);
         hipLaunchKernelGGL(nt_conv_grad, dim3(batch), dim3(NT_THREADS), x_bytes, stream, d_db, d_idx, w + lay_.conv_w.at, dfeat, conv_part, d.n_bins, d.t_frames,
                            d.L, d.o_pool);
         hipLaunchKernelGGL(nt_conv_reduce, dim3(1), dim3(128), 0, stream, conv_part, grad + lay_.conv_w.at, batch);
         if (mode == PVQ_TRAIN_STEP) {
             const size_t n4 = n / 4;
             hipLaunchKernelGGL(nt_adam, dim3(static_cast<uint32_t>((n4 + NT_THREADS - 1) / NT_THREADS)), dim3(NT_THREADS), 0, stream,
-                               reinterpret_cast<f32x4*>(d_arena_), reinterpret_cast<const f32x4*>(grad), reinterpret_cast<f32x4*>(d_arena_ + 2 * n),
-                               reinterpret_cast<f32x4*>(d_arena_ + 3 * n), n4, note_trainer_adam_step(hyper_, steps_ + 1));
+                               reinterpret_cast<f32x4*>(arena_.as<float>()), reinterpret_cast<const f32x4*>(grad), reinterpret_cast<f32x4*>(arena_.as<float>() + 2 * n),
+                               reinterpret_cast<f32x4*>(arena_.as<float>() + 3 * n), n4, note_trainer_adam_step(hyper_, steps_ + 1));
             ++steps_;
         }
     }
@@ -671,38 +658,30 @@ pvq_status NoteTrainer::test(const float* d_db, const float* d_targets, size_t n
     }
     PVQ_HIP(hipSetDevice(device_id_));
     const NoteTrainerTestPlan plan = note_trainer_test_plan(n_idx, max_batch_, batch);
-    // grow-only buffers: the rows' masks [cap][8] words, counts [cap] uint4 and losses [cap] doubles; the records and pitch counts
-    if (n_idx > test_rows_cap_) {
-        if (d_test_rows_) PVQ_HIP(hipFree(d_test_rows_));
-        d_test_rows_ = nullptr;
-        test_rows_cap_ = 0;
-        PVQ_HIP(hipMalloc(&d_test_rows_, plan.rows_bytes));
-        test_rows_cap_ = n_idx;
-    }
-    if (plan.out_bytes > test_out_cap_) {
-        if (d_test_out_) PVQ_HIP(hipFree(d_test_out_));
-        d_test_out_ = nullptr;
+    // grow-only buffers: the rows' masks [n_idx][8] words, counts [n_idx] uint4 and losses [n_idx] doubles; the records and pitch counts
+    if (pvq_status s = test_rows_.reserve(plan.rows_bytes)) return s;
+    if (pvq_status s = test_out_.reserve(plan.out_bytes)) return s;
+    if (plan.out_bytes > h_test_out_bytes_) {
         if (h_test_out_) PVQ_HIP(hipHostFree(h_test_out_));
         h_test_out_ = nullptr;
-        test_out_cap_ = 0;
-        PVQ_HIP(hipMalloc(&d_test_out_, plan.out_bytes));
+        h_test_out_bytes_ = 0;
         PVQ_HIP(hipHostMalloc(&h_test_out_, plan.out_bytes, hipHostMallocDefault));
-        test_out_cap_ = plan.out_bytes;
+        h_test_out_bytes_ = plan.out_bytes;
     }
-    char* rows_base = static_cast<char*>(d_test_rows_);
+    char* rows_base = test_rows_.as<char>();
     uint32_t* masks = reinterpret_cast<uint32_t*>(rows_base);
-    uint4* counts = reinterpret_cast<uint4*>(rows_base + 32 * test_rows_cap_);
-    double* row_loss = reinterpret_cast<double*>(rows_base + 48 * test_rows_cap_);
-    pvq_note_test_batch* d_batches = static_cast<pvq_note_test_batch*>(d_test_out_);
+    uint4* counts = reinterpret_cast<uint4*>(rows_base + 32 * n_idx);
+    double* row_loss = reinterpret_cast<double*>(rows_base + 48 * n_idx);
+    pvq_note_test_batch* d_batches = test_out_.as<pvq_note_test_batch>();
     const size_t batch_bytes = plan.n_batches * sizeof(pvq_note_test_batch);
-    uint32_t* d_pitch = reinterpret_cast<uint32_t*>(static_cast<char*>(d_test_out_) + batch_bytes);
-    const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d_ws_ + ws_idx_);
+    uint32_t* d_pitch = reinterpret_cast<uint32_t*>(test_out_.as<char>() + batch_bytes);
+    const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(ws(ws_idx_));
 
     for (const NtTestChunk& c : plan.chunks) {
         const pvq_status up = upload_idx(idx + c.begin, c.rows, stream);
         if (up != PVQ_OK) return up;
         forward(d_db, c.rows, false, stream);
-        hipLaunchKernelGGL(nt_test_rows, dim3(c.rows), dim3(NM_OUT), 0, stream, d_ws_ + ws_z_, d_targets, d_idx, c.begin, masks, counts, row_loss, d_logits);
+        hipLaunchKernelGGL(nt_test_rows, dim3(c.rows), dim3(NM_OUT), 0, stream, ws(ws_z_), d_targets, d_idx, c.begin, masks, counts, row_loss, d_logits);
     }
     constexpr uint32_t per_block = NT_THREADS / 64;
     hipLaunchKernelGGL(nt_test_batches, dim3(static_cast<uint32_t>((plan.n_batches + per_block - 1) / per_block)), dim3(NT_THREADS), 0, stream, counts, row_loss,
@@ -714,7 +693,7 @@ pvq_status NoteTrainer::test(const float* d_db, const float* d_targets, size_t n
     PVQ_HIP(hipGetLastError());
     // the one read-back, the one wait
     const size_t back = batch_bytes + (out_pitch ? NT_TEST_PITCH_BYTES : 0);
-    PVQ_HIP(hipMemcpyAsync(h_test_out_, d_test_out_, back, hipMemcpyDeviceToHost, stream));
+    PVQ_HIP(hipMemcpyAsync(h_test_out_, test_out_.as<void>(), back, hipMemcpyDeviceToHost, stream));
     PVQ_HIP(hipStreamSynchronize(stream));
     std::memcpy(out_batches, h_test_out_, batch_bytes);
     if (out_pitch) std::memcpy(out_pitch, static_cast<const char*>(h_test_out_) + batch_bytes, NT_TEST_PITCH_BYTES);
@@ -736,7 +715,7 @@ pvq_status NoteTrainer::read(int what, float* out, size_t capacity) {
     }
     PVQ_HIP(hipSetDevice(device_id_));
     PVQ_HIP(hipDeviceSynchronize());
-    PVQ_HIP(hipMemcpy(out, d_arena_ + static_cast<size_t>(what) * lay_.n_params, lay_.n_params * sizeof(float), hipMemcpyDeviceToHost));
+    PVQ_HIP(hipMemcpy(out, arena_.as<float>() + static_cast<size_t>(what) * lay_.n_params, lay_.n_params * sizeof(float), hipMemcpyDeviceToHost));
     return PVQ_OK;
 }
 

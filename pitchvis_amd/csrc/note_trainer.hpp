@@ -28,6 +28,7 @@
 #include <memory>
 
 #include "../../include/pvq.h"
+#include "device_support.hpp"
 #include "note_trainer_plan.hpp"
 
 namespace pvq {
@@ -64,17 +65,16 @@ class NoteTrainer {
     uint32_t max_batch_ = 0;
     uint64_t steps_ = 0;     // completed PVQ_TRAIN_STEP calls: Adam's t - 1, and the step the dropout mask is keyed by
     uint64_t calls_ = 0;     // picks the pinned slot
-    float* d_arena_ = nullptr;   // weights, gradients, m, v: 4 x n_params
-    float* d_ws_ = nullptr;
+    DeviceBuffer arena_;     // floats: weights, gradients, m, v: 4 x n_params
+    DeviceBuffer ws_;        // floats, sized once from max_batch
+    float* ws(size_t at) const { return ws_.as<float>() + at; }   // at: one of the float offsets below
     uint32_t* h_idx_[2] = {nullptr, nullptr};   // pinned staging of idx, two slots so that a call may be queued behind a running one
     hipEvent_t idx_copied_[2] = {nullptr, nullptr};
     bool idx_pending_[2] = {false, false};
     // the test pass: per-row masks, counts and losses (grow-only), the batch records and pitch counts and their pinned copy
-    void* d_test_rows_ = nullptr;
-    size_t test_rows_cap_ = 0;    // rows
-    void* d_test_out_ = nullptr;
+    DeviceBuffer test_rows_, test_out_;
     void* h_test_out_ = nullptr;
-    size_t test_out_cap_ = 0;     // bytes
+    size_t h_test_out_bytes_ = 0;
     // float offsets into the workspace
     size_t ws_feat_ = 0, ws_dfeat_ = 0, ws_h_ = 0, ws_da_ = 0, ws_z_ = 0, ws_dz_ = 0, ws_convpart_ = 0, ws_rowloss_ = 0, ws_part_ = 0, ws_idx_ = 0;
 };

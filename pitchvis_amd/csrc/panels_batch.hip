@@ -22,18 +22,10 @@
 
 #include "panels_host.hpp"
 #include "panels_math.hpp"
+#include "stage_plan.hpp"
 #include "vqt_engine.hpp"
 
 namespace pvq {
-
-#define PVQ_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_last_error(std::string(#call) + " failed: " + hipGetErrorString(e_));              \
-            return PVQ_ERR_DEVICE;                                                                 \
-        }                                                                                          \
-    } while (0)
 
 namespace {
 constexpr uint32_t MAX_BINS = 1024;
@@ -282,11 +274,6 @@ void launch_nk(int nk, const RowsArgs& a, dim3 grid, hipStream_t stream) {
 bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 }  // namespace
 
-PanelsBatch::~PanelsBatch() {
-    if (d_tab_) (void)hipFree(d_tab_);
-    if (d_hist_) (void)hipFree(d_hist_);
-}
-
 pvq_status PanelsBatch::create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, const float* colors, float gray_level,
                                uint32_t n_streams, uint32_t graph_capacity, std::unique_ptr<PanelsBatch>& out) {
     out.reset();
@@ -322,10 +309,9 @@ pvq_status PanelsBatch::create(int device_id, uint32_t octaves, uint32_t buckets
         panel_disc_table(t.cs);
         const size_t hist_bytes = 2 * static_cast<size_t>(n_streams) * cap * sizeof(float);
         PVQ_HIP(hipSetDevice(device_id));
-        PVQ_HIP(hipMalloc(&b->d_tab_, sizeof(PanelTables)));
-        PVQ_HIP(hipMemcpy(b->d_tab_, &t, sizeof(PanelTables), hipMemcpyHostToDevice));
-        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&b->d_hist_), hist_bytes));
-        PVQ_HIP(hipMemset(b->d_hist_, 0, hist_bytes));   // SceneCalmnessHistory::new (mod.rs:125-132)
+        if (pvq_status s = b->tab_.upload(&t, sizeof(PanelTables))) return s;
+        if (pvq_status s = b->hist_.reserve(hist_bytes)) return s;
+        PVQ_HIP(hipMemset(b->hist_.as<float>(), 0, hist_bytes));   // SceneCalmnessHistory::new (mod.rs:125-132)
         PVQ_HIP(hipDeviceSynchronize());
     }
     out = std::move(b);
@@ -375,7 +361,7 @@ pvq_status PanelsBatch::rows_device(size_t n_rows, const float* d_x_vqt_smoothed
     a.n_rows = static_cast<uint32_t>(n_rows);
     a.n_bins = static_cast<int>(n_bins_);
     a.bpo = bpo_;
-    a.tab = static_cast<const PanelTables*>(d_tab_);
+    a.tab = tab_.as<PanelTables>();
     a.line_pos = outs.line_pos;
     a.line_rgba = outs.line_rgba;
     a.disc_pos = outs.disc_pos;
@@ -403,8 +389,9 @@ pvq_status PanelsBatch::graph_device(size_t n_frames, const float* d_scene_calmn
         set_last_error("panels batch: a graph output must be 16-byte aligned");
         return PVQ_ERR_INVALID_ARG;
     }
-    if (n_frames * static_cast<uint64_t>(n_streams_) > 0x7FFFFFFFull) {
-        set_last_error("panels batch: too many frames in one call");
+    std::string err;
+    if (!stage_frames_ok("panels batch", n_frames, n_streams_, err)) {
+        set_last_error(err);
         return PVQ_ERR_INVALID_ARG;
     }
     if (device_id_ < 0) {
@@ -415,8 +402,8 @@ pvq_status PanelsBatch::graph_device(size_t n_frames, const float* d_scene_calmn
     PVQ_HIP(hipSetDevice(device_id_));
     const size_t half = static_cast<size_t>(n_streams_) * capacity_;
     GraphArgs a{};
-    a.hist = d_hist_ + cur_ * half;
-    a.hist_next = d_hist_ + (1 - cur_) * half;
+    a.hist = hist_.as<float>() + cur_ * half;
+    a.hist_next = hist_.as<float>() + (1 - cur_) * half;
     a.vals = d_scene_calmness;
     a.n_streams = n_streams_;
     a.n_frames = static_cast<uint32_t>(n_frames);
@@ -447,7 +434,7 @@ pvq_status PanelsBatch::get_history(uint32_t stream_index, float* out) {
     PVQ_HIP(hipSetDevice(device_id_));
     PVQ_HIP(hipDeviceSynchronize());
     const size_t half = static_cast<size_t>(n_streams_) * capacity_;
-    PVQ_HIP(hipMemcpy(out, d_hist_ + cur_ * half + static_cast<size_t>(stream_index) * capacity_, capacity_ * sizeof(float), hipMemcpyDeviceToHost));
+    PVQ_HIP(hipMemcpy(out, hist_.as<float>() + cur_ * half + static_cast<size_t>(stream_index) * capacity_, capacity_ * sizeof(float), hipMemcpyDeviceToHost));
     return PVQ_OK;
 }
 

@@ -16,6 +16,7 @@
 #include <memory>
 
 #include "../../include/pvq.h"
+#include "device_support.hpp"
 
 namespace pvq {
 
@@ -26,7 +27,6 @@ class PanelsBatch {
     // return PVQ_ERR_NO_DEVICE after the argument checks.
     static pvq_status create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, const float* colors, float gray_level,
                              uint32_t n_streams, uint32_t graph_capacity, std::unique_ptr<PanelsBatch>& out);
-    ~PanelsBatch();
     uint32_t n_bins() const { return n_bins_; }
     uint32_t n_streams() const { return n_streams_; }
     uint32_t graph_capacity() const { return capacity_; }
@@ -46,8 +46,8 @@ class PanelsBatch {
     PanelsBatch() = default;
     int device_id_ = -1;
     uint32_t n_bins_ = 0, bpo_ = 0, n_streams_ = 0, capacity_ = 0;
-    void* d_tab_ = nullptr;      // PanelTables (panels_batch.hip)
-    float* d_hist_ = nullptr;    // [2][n_streams][capacity]: the histories, and where the next call leaves them
+    DeviceBuffer tab_;           // PanelTables (panels_batch.hip)
+    DeviceBuffer hist_;          // [2][n_streams][capacity] floats: the histories, and where the next call leaves them
     int cur_ = 0;                // which half holds the histories
 };
 

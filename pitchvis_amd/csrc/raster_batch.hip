@@ -20,25 +20,18 @@
 #include <string>
 #include <vector>
 
+#include "stage_device.hpp"
+#include "stage_plan.hpp"
 #include "vqt_engine.hpp"
 
 namespace pvq {
-
-#define PVQ_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_last_error(std::string(#call) + " failed: " + hipGetErrorString(e_));              \
-            return PVQ_ERR_DEVICE;                                                                 \
-        }                                                                                          \
-    } while (0)
 
 namespace {
 constexpr uint32_t MAX_BINS = 1024;
 constexpr size_t WORKSPACE_LIMIT = 256ull << 20;   // the lists of one piece of a call
 constexpr int LIST_THREADS = 256;
 constexpr int CHUNK = 64;                           // balls staged through LDS at a time: 64 x 64 bytes, 16 bytes a lane of 256
-constexpr int TILE = 16;                            // pixels a side of a workgroup's tile: 2 x 2 waves of 8 x 8
+constexpr int TILE = stage::TILE;
 
 struct RasterArgs {
     const float* xyzs;          // [n_streams][n_frames][n_bins][4]
@@ -69,7 +62,7 @@ __global__ __launch_bounds__(64) void raster_marks(RasterArgs a) {
     const int lane = threadIdx.x;
     const uint32_t rows = a.n_streams * a.pf;
     for (uint32_t r = blockIdx.x; r < rows; r += gridDim.x) {
-        const size_t g = static_cast<size_t>(r / a.pf) * a.n_frames + a.f0 + r % a.pf;
+        const size_t g = stage::piece_row(r, a.pf, a.n_frames, a.f0);
         if (lane < static_cast<int>(MAX_BINS / 32)) s_mask[lane] = 0u;
         __syncthreads();
         const uint32_t cnt = min(a.peak_count[g], a.max_peaks);
@@ -119,7 +112,7 @@ __global__ __launch_bounds__(LIST_THREADS) __attribute__((flatten)) void raster_
     const uint32_t tid = threadIdx.x;
     const uint32_t rows = a.n_streams * a.pf;
     for (uint32_t r = blockIdx.x; r < rows; r += gridDim.x) {
-        const size_t g = static_cast<size_t>(r / a.pf) * a.n_frames + a.f0 + r % a.pf;
+        const size_t g = stage::piece_row(r, a.pf, a.n_frames, a.f0);
         if (tid == 0) s_n = 0u;
         __syncthreads();
         for (uint32_t bin = tid; bin < a.n_bins; bin += LIST_THREADS) {
@@ -157,20 +150,13 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void raster_tiles(Ras
 #pragma clang fp contract(off)
     __shared__ uint4 s_ball[CHUNK * 4];
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    const uint32_t tiles_x = (a.W + TILE - 1) / TILE;
-    const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-    const uint32_t bx0 = tx * TILE + (wave & 1u) * 8u, by0 = ty * TILE + (wave >> 1) * 8u;   // the wave's 8 x 8 block
-    const uint32_t i = bx0 + (lane & 7u), j = by0 + (lane >> 3);
-    const bool inside = i < a.W && j < a.H;
-    float wx, wy;
-    raster::pixel_world(i, j, a.W, a.H, a.vh, wx, wy);
-    const size_t pixel = static_cast<size_t>(j) * a.W + i;
+    const stage::TilePixel px = stage::tile_pixel(wave, lane, a.W, a.H, a.vh);
     const uint32_t rows = a.n_streams * a.pf;
     for (uint32_t r = blockIdx.y; r < rows; r += gridDim.y) {
-        const size_t g = static_cast<size_t>(r / a.pf) * a.n_frames + a.f0 + r % a.pf;
+        const size_t g = stage::piece_row(r, a.pf, a.n_frames, a.f0);
         float dst[4] = {a.clear[0], a.clear[1], a.clear[2], a.clear[3]};
-        if (a.background && inside) {
-            const float4 bg = reinterpret_cast<const float4*>(a.background)[g * a.bg_row + pixel];
+        if (a.background && px.inside) {
+            const float4 bg = reinterpret_cast<const float4*>(a.background)[g * a.bg_row + px.pixel];
             dst[0] = bg.x; dst[1] = bg.y; dst[2] = bg.z; dst[3] = bg.w;
         }
         const uint32_t m = a.counts[r];
@@ -183,7 +169,7 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void raster_tiles(Ras
             for (uint32_t k = 0; k < here; ++k) {
                 const uint4 q3 = s_ball[k * 4 + 3];   // wave-uniform address
                 const uint32_t bx = __builtin_amdgcn_readfirstlane(q3.z), by = __builtin_amdgcn_readfirstlane(q3.w);
-                if ((bx & 0xFFFFu) > bx0 + 7u || (bx >> 16) < bx0 || (by & 0xFFFFu) > by0 + 7u || (by >> 16) < by0) continue;
+                if ((bx & 0xFFFFu) > px.bx0 + 7u || (bx >> 16) < px.bx0 || (by & 0xFFFFu) > px.by0 + 7u || (by >> 16) < px.by0) continue;
                 const uint4 q0 = s_ball[k * 4], q1 = s_ball[k * 4 + 1], q2 = s_ball[k * 4 + 2];
                 raster::Ball q;
                 q.x = __uint_as_float(q0.x); q.y = __uint_as_float(q0.y); q.side = __uint_as_float(q0.z); q.noise_z = __uint_as_float(q0.w);
@@ -192,18 +178,13 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void raster_tiles(Ras
                 q.dot_factor = __uint_as_float(q2.z); q.dot_pulse = __uint_as_float(q2.w);
                 q.spiral = __uint_as_float(q3.x); q.star_brightness = __uint_as_float(q3.y);
                 q.box_x = bx; q.box_y = by;
-                raster::compose_ball(q, wx, wy, dst);
+                raster::compose_ball(q, px.wx, px.wy, dst);
             }
         }
-        if (inside) reinterpret_cast<float4*>(a.image)[g * a.W * a.H + pixel] = make_float4(dst[0], dst[1], dst[2], dst[3]);
+        if (px.inside) reinterpret_cast<float4*>(a.image)[g * a.W * a.H + px.pixel] = make_float4(dst[0], dst[1], dst[2], dst[3]);
     }
 }
 }  // namespace
-
-RasterBatch::~RasterBatch() {
-    for (void* p : {static_cast<void*>(d_time_), static_cast<void*>(d_elapsed_), d_ws_})
-        if (p) (void)hipFree(p);
-}
 
 pvq_status RasterBatch::create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, int visuals_mode, float viewport_height,
                                uint32_t n_streams, uint32_t width, uint32_t height, std::unique_ptr<RasterBatch>& out) {
@@ -212,16 +193,9 @@ pvq_status RasterBatch::create(int device_id, uint32_t octaves, uint32_t buckets
         set_last_error("raster batch: octaves, buckets_per_octave and n_streams must be positive");
         return PVQ_ERR_INVALID_ARG;
     }
-    if (visuals_mode < scene::FULL || visuals_mode > scene::GALAXY) {
-        set_last_error("raster batch: unknown visuals mode");
-        return PVQ_ERR_INVALID_ARG;
-    }
-    if (width == 0 || height == 0 || width > raster::MAX_IMAGE || height > raster::MAX_IMAGE) {
-        set_last_error("raster batch: width and height are 1 .. 4096");
-        return PVQ_ERR_INVALID_ARG;
-    }
-    if (!(viewport_height >= 0.0f) || !raster::finite_f(viewport_height)) {
-        set_last_error("raster batch: viewport_height is 0 (the viewer's) or positive and finite");
+    std::string err;
+    if (!stage_mode_ok("raster batch", visuals_mode, err) || !stage_image_ok("raster batch", width, height, viewport_height, err)) {
+        set_last_error(err);
         return PVQ_ERR_INVALID_ARG;
     }
     const uint64_t n = static_cast<uint64_t>(octaves) * buckets_per_octave;
@@ -244,8 +218,8 @@ pvq_status RasterBatch::create(int device_id, uint32_t octaves, uint32_t buckets
     if (device_id >= 0) {
         PVQ_HIP(hipSetDevice(device_id));
         const size_t bytes = static_cast<size_t>(n_streams) * n * sizeof(float);
-        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&b->d_time_), bytes));
-        PVQ_HIP(hipMemset(b->d_time_, 0, bytes));   // Params::default()
+        if (pvq_status s = b->time_.reserve(bytes)) return s;
+        PVQ_HIP(hipMemset(b->time_.as<float>(), 0, bytes));   // Params::default()
     }
     out = std::move(b);
     return PVQ_OK;
@@ -270,8 +244,9 @@ pvq_status RasterBatch::frames_device(size_t n_frames, const pvq_raster_inputs& 
         set_last_error("raster batch: ball_xyzs, ball_rgba, background and d_image must be 16-byte aligned");
         return PVQ_ERR_INVALID_ARG;
     }
-    if (n_frames > 0x7FFFFFFFull || n_frames * n_streams_ > 0x7FFFFFFFull) {
-        set_last_error("raster batch: too many frames in one call");
+    std::string err;
+    if (!stage_frames_ok("raster batch", n_frames, n_streams_, err)) {
+        set_last_error(err);
         return PVQ_ERR_INVALID_ARG;
     }
     if (n_frames && !elapsed_s) {
@@ -286,30 +261,17 @@ pvq_status RasterBatch::frames_device(size_t n_frames, const pvq_raster_inputs& 
     PVQ_HIP(hipSetDevice(device_id_));
     const uint32_t n = n_bins_, words = (n + 31u) / 32u;
 
-    if (n_frames > elapsed_cap_) {
-        if (d_elapsed_) PVQ_HIP(hipFree(d_elapsed_));   // (waits for the device)
-        d_elapsed_ = nullptr;
-        elapsed_cap_ = 0;
-        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&d_elapsed_), n_frames * sizeof(float)));
-        elapsed_cap_ = n_frames;
-    }
+    if (pvq_status s = elapsed_.reserve(n_frames * sizeof(float))) return s;
     // stream-ordered behind the call before, which may still read the buffer; the host array is the caller's again on return
-    PVQ_HIP(hipMemcpyAsync(d_elapsed_, elapsed_s, n_frames * sizeof(float), hipMemcpyHostToDevice, stream));
+    PVQ_HIP(hipMemcpyAsync(elapsed_.as<float>(), elapsed_s, n_frames * sizeof(float), hipMemcpyHostToDevice, stream));
     PVQ_HIP(hipStreamSynchronize(stream));
 
     // the lists of a piece of the call's frames fit the workspace
     const size_t per_row = static_cast<size_t>(n) * (sizeof(raster::Ball) + sizeof(float)) + (words + 1u) * sizeof(uint32_t);
     const size_t limit = static_cast<size_t>(std::max(1, dev_knob("PVQ_RASTER_WS_KB", static_cast<int>(WORKSPACE_LIMIT >> 10)))) << 10;
-    const size_t pf = std::min<size_t>(n_frames, std::max<size_t>(1, limit / (per_row * n_streams_)));
+    const size_t pf = stage_piece_frames(n_frames, n_streams_, per_row, limit);
     const size_t rows_max = static_cast<size_t>(n_streams_) * pf;
-    const size_t need = per_row * rows_max;
-    if (need > ws_bytes_) {
-        if (d_ws_) PVQ_HIP(hipFree(d_ws_));   // (waits for the device)
-        d_ws_ = nullptr;
-        ws_bytes_ = 0;
-        PVQ_HIP(hipMalloc(&d_ws_, need));
-        ws_bytes_ = need;
-    }
+    if (pvq_status s = ws_.reserve(per_row * rows_max)) return s;
     RasterArgs a{};
     a.xyzs = in.ball_xyzs;
     a.rgba = in.ball_rgba;
@@ -319,7 +281,7 @@ pvq_status RasterBatch::frames_device(size_t n_frames, const pvq_raster_inputs& 
     a.peak_count = in.peak_count;
     a.background = over ? d_image : in.background;   // in place: a lane reads its pixel before it writes it
     a.bg_row = over ? static_cast<size_t>(width_) * height_ : 0;
-    a.elapsed = d_elapsed_;
+    a.elapsed = elapsed_.as<float>();
     a.max_peaks = in.max_peaks;
     a.n_streams = n_streams_;
     a.n_bins = n;
@@ -329,8 +291,8 @@ pvq_status RasterBatch::frames_device(size_t n_frames, const pvq_raster_inputs& 
     a.H = height_;
     a.vh = vh_;
     for (int i = 0; i < 4; ++i) a.clear[i] = clear_[i];
-    a.state = d_time_;
-    a.list = static_cast<raster::Ball*>(d_ws_);   // the 64-byte records first: the workspace is 256-byte aligned
+    a.state = time_.as<float>();
+    a.list = ws_.as<raster::Ball>();   // the 64-byte records first: the workspace is 256-byte aligned
     a.times = reinterpret_cast<float*>(a.list + rows_max * n);
     a.marks = reinterpret_cast<uint32_t*>(a.times + rows_max * n);
     a.counts = a.marks + rows_max * words;
@@ -364,7 +326,7 @@ pvq_status RasterBatch::get_times(uint32_t stream_index, float* out) {
     }
     PVQ_HIP(hipSetDevice(device_id_));
     PVQ_HIP(hipDeviceSynchronize());
-    PVQ_HIP(hipMemcpy(out, d_time_ + static_cast<size_t>(stream_index) * n_bins_, n_bins_ * sizeof(float), hipMemcpyDeviceToHost));
+    PVQ_HIP(hipMemcpy(out, time_.as<float>() + static_cast<size_t>(stream_index) * n_bins_, n_bins_ * sizeof(float), hipMemcpyDeviceToHost));
     return PVQ_OK;
 }
 

@@ -13,6 +13,7 @@
 #include <memory>
 
 #include "../../include/pvq.h"
+#include "device_support.hpp"
 #include "raster_host.hpp"
 
 namespace pvq {
@@ -24,7 +25,6 @@ class RasterBatch {
     // returns PVQ_ERR_NO_DEVICE after the argument checks.
     static pvq_status create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, int visuals_mode, float viewport_height,
                              uint32_t n_streams, uint32_t width, uint32_t height, std::unique_ptr<RasterBatch>& out);
-    ~RasterBatch();
     uint32_t n_bins() const { return n_bins_; }
     float viewport_height() const { return vh_; }
     // n_frames frames of every stream.  Asynchronous on `stream`; one handle's calls are stream-ordered.  over: every row's balls
@@ -40,11 +40,9 @@ class RasterBatch {
     uint32_t n_streams_ = 0, n_bins_ = 0, width_ = 0, height_ = 0;
     float vh_ = 0.0f;
     float clear_[4] = {0.0f, 0.0f, 0.0f, 1.0f};
-    float* d_time_ = nullptr;      // [n_streams][n_bins]: the state
-    float* d_elapsed_ = nullptr;   // grow-only: [n_frames] of the call
-    size_t elapsed_cap_ = 0;
-    void* d_ws_ = nullptr;         // grow-only: the lists, times, marks and counts of one piece of a call
-    size_t ws_bytes_ = 0;
+    DeviceBuffer time_;      // [n_streams][n_bins] floats: the state
+    DeviceBuffer elapsed_;   // grow-only: [n_frames] floats of the call
+    DeviceBuffer ws_;        // grow-only: the lists, times, marks and counts of one piece of a call
 };
 
 }  // namespace pvq

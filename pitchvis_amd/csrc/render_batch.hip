@@ -31,15 +31,6 @@
 
 namespace pvq {
 
-#define PVQ_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_last_error(std::string(#call) + " failed: " + hipGetErrorString(e_));              \
-            return PVQ_ERR_DEVICE;                                                                 \
-        }                                                                                          \
-    } while (0)
-
 namespace {
 constexpr uint32_t MAX_BINS = 1024;
 
@@ -302,10 +293,6 @@ void launch_nk(int nk, const RenderArgs& a, dim3 grid, hipStream_t stream) {
 }
 }  // namespace
 
-RenderBatch::~RenderBatch() {
-    if (d_tab_) (void)hipFree(d_tab_);
-}
-
 pvq_status RenderBatch::create(int device_id, float min_freq, uint32_t octaves, uint32_t buckets_per_octave, const float* colors,
                                float gray_level, float easing_pow, std::unique_ptr<RenderBatch>& out) {
     out.reset();
@@ -351,8 +338,7 @@ pvq_status RenderBatch::create(int device_id, float min_freq, uint32_t octaves, 
         }
         for (uint32_t k = 12; k < 16; ++k) t.class_start[k] = static_cast<uint16_t>(at);
         PVQ_HIP(hipSetDevice(device_id));
-        PVQ_HIP(hipMalloc(&b->d_tab_, sizeof(RenderTables)));
-        PVQ_HIP(hipMemcpy(b->d_tab_, &t, sizeof(RenderTables), hipMemcpyHostToDevice));
+        if (pvq_status s = b->tab_.upload(&t, sizeof(RenderTables))) return s;
     }
     out = std::move(b);
     return PVQ_OK;
@@ -394,7 +380,7 @@ pvq_status RenderBatch::rows_device(size_t n_rows, const float* d_x_vqt_smoothed
     a.semitone_offset = semitone_offset_;
     a.gray_level = gray_level_;
     a.easing_pow = easing_pow_;
-    a.tab = static_cast<const RenderTables*>(d_tab_);
+    a.tab = tab_.as<RenderTables>();
     a.out_vqt = outs.spectrogram_vqt;
     a.out_peaks = outs.spectrogram_peaks;
     a.out_chroma = outs.chroma;

@@ -17,6 +17,7 @@
 #include <memory>
 
 #include "../../include/pvq.h"
+#include "device_support.hpp"
 
 namespace pvq {
 
@@ -27,7 +28,6 @@ class RenderBatch {
     // rows_device returns PVQ_ERR_NO_DEVICE after the argument checks.
     static pvq_status create(int device_id, float min_freq, uint32_t octaves, uint32_t buckets_per_octave, const float* colors,
                              float gray_level, float easing_pow, std::unique_ptr<RenderBatch>& out);
-    ~RenderBatch();
     uint32_t n_bins() const { return n_bins_; }
     int device() const { return device_id_; }
     // Every requested output (a non-null pointer of outs) for n_rows rows.  d_x_vqt_smoothed [n_rows][n_bins]; d_center / d_size
@@ -41,7 +41,7 @@ class RenderBatch {
     int device_id_ = -1;
     uint32_t n_bins_ = 0, bpo_ = 0;
     float gray_level_ = 0.0f, easing_pow_ = 0.0f, semitone_offset_ = 0.0f;
-    void* d_tab_ = nullptr;   // RenderTables (render_batch.hip)
+    DeviceBuffer tab_;   // RenderTables (render_batch.hip)
 };
 
 }  // namespace pvq

@@ -25,18 +25,11 @@
 #include <cstring>
 #include <string>
 
+#include "stage_device.hpp"
+#include "stage_plan.hpp"
 #include "vqt_engine.hpp"
 
 namespace pvq {
-
-#define PVQ_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_last_error(std::string(#call) + " failed: " + hipGetErrorString(e_));              \
-            return PVQ_ERR_DEVICE;                                                                 \
-        }                                                                                          \
-    } while (0)
 
 namespace {
 constexpr uint32_t MAX_BINS = 1024;
@@ -88,7 +81,7 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void scene_peaks(Scene
     __syncthreads();
     const uint32_t rows = a.n_streams * a.pf;
     for (uint32_t r = blockIdx.x; r < rows; r += gridDim.x) {
-        const size_t g = static_cast<size_t>(r / a.pf) * a.n_frames + a.f0 + r % a.pf;
+        const size_t g = stage::piece_row(r, a.pf, a.n_frames, a.f0);
         const uint32_t cnt = min(a.peak_count[g], a.max_peaks);
         if (cnt == 0u) continue;   // update.rs:85-87: scene_frames never reads this row's records or header
         const float* c_row = a.center + g * a.max_peaks;
@@ -297,12 +290,6 @@ void launch_nk(int nk, const SceneArgs& a, dim3 grid, hipStream_t stream) {
 }
 }  // namespace
 
-SceneBatch::~SceneBatch() {
-    for (void* p : {d_settings_, static_cast<void*>(d_state_), static_cast<void*>(d_scalars_), d_rec_, static_cast<void*>(d_fade_),
-                    static_cast<void*>(d_fade_row_)})
-        if (p) (void)hipFree(p);
-}
-
 pvq_status SceneBatch::create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, const pvq_scene_settings* settings,
                               uint32_t n_streams, std::unique_ptr<SceneBatch>& out) {
     out.reset();
@@ -343,12 +330,9 @@ pvq_status SceneBatch::create(int device_id, uint32_t octaves, uint32_t buckets_
             for (int i = 0; i < 4; ++i) scal[static_cast<size_t>(8) * s + 1 + i] = bass[i];
         }
         PVQ_HIP(hipSetDevice(device_id));
-        PVQ_HIP(hipMalloc(&b->d_settings_, sizeof(scene::Settings)));
-        PVQ_HIP(hipMemcpy(b->d_settings_, &b->s_, sizeof(scene::Settings), hipMemcpyHostToDevice));
-        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&b->d_state_), all.size() * sizeof(float)));
-        PVQ_HIP(hipMemcpy(b->d_state_, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
-        PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&b->d_scalars_), scal.size() * sizeof(float)));
-        PVQ_HIP(hipMemcpy(b->d_scalars_, scal.data(), scal.size() * sizeof(float), hipMemcpyHostToDevice));
+        if (pvq_status s = b->settings_.upload(&b->s_, sizeof(scene::Settings))) return s;
+        if (pvq_status s = b->state_.upload(all.data(), all.size() * sizeof(float))) return s;
+        if (pvq_status s = b->scalars_.upload(scal.data(), scal.size() * sizeof(float))) return s;
     }
     out = std::move(b);
     return PVQ_OK;
@@ -369,8 +353,9 @@ pvq_status SceneBatch::frames_device(size_t n_frames, const pvq_scene_inputs& in
         set_last_error("scene batch: ball_xyzs, ball_rgba and bass_rgba must be 16-byte aligned");
         return PVQ_ERR_INVALID_ARG;
     }
-    if (n_frames > 0x7FFFFFFFull || n_frames * n_streams_ > 0x7FFFFFFFull) {
-        set_last_error("scene batch: too many frames in one call");
+    std::string err;
+    if (!stage_frames_ok("scene batch", n_frames, n_streams_, err)) {
+        set_last_error(err);
         return PVQ_ERR_INVALID_ARG;
     }
     if (device_id_ < 0) {
@@ -396,41 +381,19 @@ pvq_status SceneBatch::frames_device(size_t n_frames, const pvq_scene_inputs& in
     }
     if (distinct != fade_times_ || frame_times_ns) PVQ_HIP(hipStreamSynchronize(stream));   // the buffers below may still be read
     if (distinct != fade_times_) {
-        if (distinct.size() > fade_rows_cap_) {
-            if (d_fade_) PVQ_HIP(hipFree(d_fade_));
-            d_fade_ = nullptr;
-            fade_rows_cap_ = 0;
-            fade_times_.clear();
-            PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&d_fade_), distinct.size() * (n + 1) * sizeof(float)));
-            fade_rows_cap_ = distinct.size();
-        }
         std::vector<float> tab(distinct.size() * (n + 1));
         for (size_t r = 0; r < distinct.size(); ++r) scene_fade_table(n, distinct[r], &tab[r * (n + 1)], tab[r * (n + 1) + n]);
-        PVQ_HIP(hipMemcpy(d_fade_, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+        fade_times_.clear();   // until the new table is whole on the device
+        if (pvq_status s = fade_.upload(tab.data(), tab.size() * sizeof(float))) return s;
         fade_times_ = distinct;
     }
-    if (frame_times_ns) {
-        if (n_frames > fade_idx_cap_) {
-            if (d_fade_row_) PVQ_HIP(hipFree(d_fade_row_));
-            d_fade_row_ = nullptr;
-            fade_idx_cap_ = 0;
-            PVQ_HIP(hipMalloc(reinterpret_cast<void**>(&d_fade_row_), n_frames * sizeof(uint32_t)));
-            fade_idx_cap_ = n_frames;
-        }
-        PVQ_HIP(hipMemcpy(d_fade_row_, rows.data(), n_frames * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
+    if (frame_times_ns)
+        if (pvq_status s = fade_row_.upload(rows.data(), n_frames * sizeof(uint32_t))) return s;
 
     // the records of a piece of the call's frames fit the workspace
     const size_t per_row = static_cast<size_t>(in.max_peaks) * sizeof(scene::PeakRecord) + sizeof(RowHeader);
-    const size_t pf = std::min<size_t>(n_frames, std::max<size_t>(1, WORKSPACE_LIMIT / (per_row * n_streams_)));
-    const size_t need = per_row * n_streams_ * pf;
-    if (need > rec_bytes_) {
-        if (d_rec_) PVQ_HIP(hipFree(d_rec_));   // (waits for the device)
-        d_rec_ = nullptr;
-        rec_bytes_ = 0;
-        PVQ_HIP(hipMalloc(&d_rec_, need));
-        rec_bytes_ = need;
-    }
+    const size_t pf = stage_piece_frames(n_frames, n_streams_, per_row, WORKSPACE_LIMIT);
+    if (pvq_status s = rec_.reserve(per_row * n_streams_ * pf)) return s;
     SceneArgs a{};
     a.center = in.center;
     a.size = in.size;
@@ -443,11 +406,11 @@ pvq_status SceneBatch::frames_device(size_t n_frames, const pvq_scene_inputs& in
     a.n_streams = n_streams_;
     a.n_frames = static_cast<uint32_t>(n_frames);
     a.n_bins = static_cast<int>(n);
-    a.settings = static_cast<const scene::Settings*>(d_settings_);
-    a.fade = d_fade_;
-    a.fade_row = frame_times_ns ? d_fade_row_ : nullptr;
-    a.state = d_state_;
-    a.scalars = d_scalars_;
+    a.settings = settings_.as<scene::Settings>();
+    a.fade = fade_.as<float>();
+    a.fade_row = frame_times_ns ? fade_row_.as<uint32_t>() : nullptr;
+    a.state = state_.as<float>();
+    a.scalars = scalars_.as<float>();
     a.out_xyzs = outs.ball_xyzs;
     a.out_rgba = outs.ball_rgba;
     a.out_params = outs.ball_params;
@@ -459,9 +422,9 @@ pvq_status SceneBatch::frames_device(size_t n_frames, const pvq_scene_inputs& in
         a.f0 = static_cast<uint32_t>(f0);
         a.pf = static_cast<uint32_t>(std::min(pf, n_frames - f0));
         const size_t rows_here = static_cast<size_t>(n_streams_) * a.pf;
-        a.rec = static_cast<scene::PeakRecord*>(d_rec_);
+        a.rec = rec_.as<scene::PeakRecord>();
         // the headers follow the records of the largest piece
-        a.hdr = reinterpret_cast<RowHeader*>(static_cast<char*>(d_rec_) + static_cast<size_t>(in.max_peaks) * sizeof(scene::PeakRecord) * n_streams_ * pf);
+        a.hdr = reinterpret_cast<RowHeader*>(rec_.as<char>() + static_cast<size_t>(in.max_peaks) * sizeof(scene::PeakRecord) * n_streams_ * pf);
         hipLaunchKernelGGL(scene_peaks, dim3(static_cast<unsigned>(std::min<size_t>(rows_here, 256 * 32))), dim3(64), 0, stream, a);
         launch_nk<1>(static_cast<int>((n + 63) / 64), a, dim3(n_streams_), stream);
     }
@@ -484,8 +447,8 @@ pvq_status SceneBatch::get_state(uint32_t stream_index, float* ball_xyzs, float*
     const uint32_t n = s_.n_bins;
     std::vector<float> st(static_cast<size_t>(STATE_FIELDS) * n);
     float sc[8];
-    PVQ_HIP(hipMemcpy(st.data(), d_state_ + static_cast<size_t>(stream_index) * st.size(), st.size() * sizeof(float), hipMemcpyDeviceToHost));
-    PVQ_HIP(hipMemcpy(sc, d_scalars_ + static_cast<size_t>(stream_index) * 8, sizeof(sc), hipMemcpyDeviceToHost));
+    PVQ_HIP(hipMemcpy(st.data(), state_.as<float>() + static_cast<size_t>(stream_index) * st.size(), st.size() * sizeof(float), hipMemcpyDeviceToHost));
+    PVQ_HIP(hipMemcpy(sc, scalars_.as<float>() + static_cast<size_t>(stream_index) * 8, sizeof(sc), hipMemcpyDeviceToHost));
     const uint32_t words = (n + 31) / 32;
     if (ball_visible) std::fill(ball_visible, ball_visible + words, 0u);
     for (uint32_t i = 0; i < n; ++i) {

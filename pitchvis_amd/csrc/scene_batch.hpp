@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/pvq.h"
+#include "device_support.hpp"
 #include "scene_host.hpp"
 
 namespace pvq {
@@ -24,7 +25,6 @@ class SceneBatch {
     // host-only object whose frames_device returns PVQ_ERR_NO_DEVICE after the argument checks.
     static pvq_status create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, const pvq_scene_settings* settings,
                              uint32_t n_streams, std::unique_ptr<SceneBatch>& out);
-    ~SceneBatch();
     uint32_t n_bins() const { return s_.n_bins; }
     uint32_t n_streams() const { return n_streams_; }
     uint32_t n_segments() const { return s_.n_segments; }
@@ -41,14 +41,12 @@ class SceneBatch {
     int device_id_ = -1;
     uint32_t n_streams_ = 0;
     scene::Settings s_{};
-    void* d_settings_ = nullptr;   // scene::Settings
-    float* d_state_ = nullptr;     // [n_streams][STATE_FIELDS][n_bins]
-    float* d_scalars_ = nullptr;   // [n_streams][8]: bass_lit (bits), bass rgba, bloom
-    void* d_rec_ = nullptr;        // grow-only: [rows][max_peaks] PeakRecord, then [rows] row headers
-    size_t rec_bytes_ = 0;
-    float* d_fade_ = nullptr;      // grow-only: [distinct frame times][n_bins + 1] dropoff, z_step
-    uint32_t* d_fade_row_ = nullptr;   // grow-only: [n_frames] row of the table
-    size_t fade_rows_cap_ = 0, fade_idx_cap_ = 0;
+    DeviceBuffer settings_;   // scene::Settings
+    DeviceBuffer state_;      // [n_streams][STATE_FIELDS][n_bins] floats
+    DeviceBuffer scalars_;    // [n_streams][8] floats: bass_lit (bits), bass rgba, bloom
+    DeviceBuffer rec_;        // grow-only: [rows][max_peaks] PeakRecord, then [rows] row headers
+    DeviceBuffer fade_;       // grow-only: [distinct frame times][n_bins + 1] floats: dropoff, z_step
+    DeviceBuffer fade_row_;   // grow-only: [n_frames] u32: row of the table
     std::vector<uint64_t> fade_times_;   // the frame times the table on the device holds, row by row
 };
 

@@ -50,15 +50,6 @@ void set_last_error_noexcept(const char* s) noexcept {
 }
 const char* get_last_error() { return g_last_error.c_str(); }
 
-#define PVQ_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_last_error(std::string(#call) + " failed: " + hipGetErrorString(e_));              \
-            return PVQ_ERR_DEVICE;                                                                 \
-        }                                                                                          \
-    } while (0)
-
 // ------------------------------------------------------------------------------------------------
 // device helpers
 // ------------------------------------------------------------------------------------------------
@@ -1094,15 +1085,6 @@ Vqt::~Vqt() {
             free_device_tables(dev_);
             dev_ = nullptr;
         }
-        if (ws_pcm_) (void)hipFree(ws_pcm_);
-        if (ws_out_) (void)hipFree(ws_out_);
-        if (ws_misc_) (void)hipFree(ws_misc_);
-        if (ws_flags_) (void)hipFree(ws_flags_);
-        if (ws_stage_) (void)hipFree(ws_stage_);
-        if (ws_stage_tab_) (void)hipFree(ws_stage_tab_);
-        if (ws_split_) (void)hipFree(ws_split_);
-        for (void* b : multi_buf_)
-            if (b) (void)hipFree(b);
         if (multi_stream_) (void)hipStreamDestroy(multi_stream_);
         if (host_streams_ready_)
             for (int i = 0; i < 3; ++i) (void)hipStreamDestroy(host_streams_[i]);
@@ -1114,6 +1096,7 @@ Vqt::~Vqt() {
             for (int k = 0; k < 2; ++k)
                 for (hipEvent_t e : ev_[s][k]) (void)hipEventDestroy(e);
     }
+    // (the workspaces and shard buffers go after this body, with their device set)
 }
 
 pvq_status Vqt::set_twiddle_fp16(bool on) {
@@ -1136,16 +1119,6 @@ pvq_status Vqt::upload_tables() {
         set_last_error(msg);
         return msg.rfind("unsupported", 0) == 0 ? PVQ_ERR_UNSUPPORTED : PVQ_ERR_DEVICE;
     }
-    return PVQ_OK;
-}
-
-pvq_status Vqt::ensure_workspace(void** ptr, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return PVQ_OK;
-    if (*ptr) PVQ_HIP(hipFree(*ptr));
-    *ptr = nullptr;
-    *cap = 0;
-    PVQ_HIP(hipMalloc(ptr, bytes));
-    *cap = bytes;
     return PVQ_OK;
 }
 
@@ -1238,10 +1211,10 @@ pvq_status Vqt::launch_fft_streams(const void* st_table, size_t n_st, const floa
     a.streams = nullptr;
     a.n_streams = 0;
     if (st_table) {
-        pvq_status es = ensure_workspace(&ws_stage_tab_, &ws_stage_tab_cap_, n_st * sizeof(FftStream));
+        pvq_status es = ws_stage_tab_.reserve(n_st * sizeof(FftStream));
         if (es != PVQ_OK) return es;
-        PVQ_HIP(hipMemcpyAsync(ws_stage_tab_, st_table, n_st * sizeof(FftStream), hipMemcpyHostToDevice, stream));   // (pageable source: staged before the call returns)
-        a.streams = static_cast<const FftStream*>(ws_stage_tab_);
+        PVQ_HIP(hipMemcpyAsync(ws_stage_tab_.as<void>(), st_table, n_st * sizeof(FftStream), hipMemcpyHostToDevice, stream));   // (pageable source: staged before the call returns)
+        a.streams = ws_stage_tab_.as<FftStream>();
         a.n_streams = (int)n_st;
     }
     a.pcm = d_pcm;
@@ -1310,9 +1283,9 @@ pvq_status Vqt::launch_fft_streams(const void* st_table, size_t n_st, const floa
 // the per-window kernels: a launch per window group and 16 384-frame part, the parts' dB rows behind them
 pvq_status Vqt::launch_fft_groups(FftArgs& a, size_t n_frames, hipStream_t stream) {
     constexpr size_t PART = 16384;
-    pvq_status es = ensure_workspace(&ws_split_, &ws_split_cap_, std::min(PART, n_frames) * (size_t)a.n_bins * sizeof(float2));
+    pvq_status es = ws_split_.reserve(std::min(PART, n_frames) * (size_t)a.n_bins * sizeof(float2));
     if (es != PVQ_OK) return es;
-    a.xv_split = static_cast<float2*>(ws_split_);
+    a.xv_split = ws_split_.as<float2>();
     slot_begin(SLOT_FFT_FRAMES, stream);
     auto launch_group = [&](auto n_c, auto block_c, int g, int f0, int nf) -> pvq_status {
         constexpr int N = decltype(n_c)::value, BLK = decltype(block_c)::value;
@@ -1341,10 +1314,10 @@ pvq_status Vqt::launch_fft_groups(FftArgs& a, size_t n_frames, hipStream_t strea
             if (ls != PVQ_OK) return ls;
         }
         if (fft_db_threads(256, a.n_bins) == 256)
-            hipLaunchKernelGGL(db_rows_batch<256>, dim3((unsigned)nf), dim3(256), 0, stream, static_cast<const float2*>(ws_split_), nf, (int)f0, a.n_bins, a.streams,
+            hipLaunchKernelGGL(db_rows_batch<256>, dim3((unsigned)nf), dim3(256), 0, stream, ws_split_.as<float2>(), nf, (int)f0, a.n_bins, a.streams,
                                a.n_streams, a.out_db, a.out_cplx, a.status);
         else   // more than 1 024 bins
-            hipLaunchKernelGGL(db_rows_batch<1024>, dim3((unsigned)nf), dim3(1024), 0, stream, static_cast<const float2*>(ws_split_), nf, (int)f0, a.n_bins, a.streams,
+            hipLaunchKernelGGL(db_rows_batch<1024>, dim3((unsigned)nf), dim3(1024), 0, stream, ws_split_.as<float2>(), nf, (int)f0, a.n_bins, a.streams,
                                a.n_streams, a.out_db, a.out_cplx, a.status);
     }
     slot_end(SLOT_FFT_FRAMES, stream);
@@ -1354,9 +1327,9 @@ pvq_status Vqt::launch_fft_groups(FftArgs& a, size_t n_frames, hipStream_t strea
 // the walk (every workgroup its frames' window groups in turn), or its group-split launch with db_rows behind it
 pvq_status Vqt::launch_fft_walk(FftArgs& a, int T, int grid, size_t lds, bool split, size_t n_frames, hipStream_t stream) {
     if (split) {
-        pvq_status es = ensure_workspace(&ws_split_, &ws_split_cap_, n_frames * (size_t)a.n_bins * sizeof(float2));
+        pvq_status es = ws_split_.reserve(n_frames * (size_t)a.n_bins * sizeof(float2));
         if (es != PVQ_OK) return es;
-        a.xv_split = static_cast<float2*>(ws_split_);
+        a.xv_split = ws_split_.as<float2>();
         grid *= a.n_groups;
     }
     slot_begin(SLOT_FFT_FRAMES, stream);
@@ -1370,7 +1343,7 @@ pvq_status Vqt::launch_fft_walk(FftArgs& a, int T, int grid, size_t lds, bool sp
                      : T == 512 ? launch(vqt_fft_frames<512, 16, 512>, grid, BLOCK, lds, a) : launch(vqt_fft_frames<1024, 16, 1024>, grid, BLOCK, lds, a);
     if (lst != PVQ_OK) return lst;
     if (split) {
-        const float2* rows = static_cast<const float2*>(ws_split_);
+        const float2* rows = ws_split_.as<float2>();
         const unsigned nr = (unsigned)n_frames;
         lst = T == 128 ? launch(db_rows<128>, nr, 128, 0, rows, (int)n_frames, a.n_bins, a.out_db, a.out_cplx, a.status)
               : T == 256 ? launch(db_rows<256>, nr, 256, 0, rows, (int)n_frames, a.n_bins, a.out_db, a.out_cplx, a.status)
@@ -1552,7 +1525,7 @@ pvq_status Vqt::batch_streams_device(const float* const* d_pcm, const size_t* n_
                 pvq_status ls = stage_buffer(b, hop, stream);
                 if (ls != PVQ_OK) return ls;
                 std::vector<StreamRun> runs;
-                append_staged_runs(runs, b, static_cast<const float*>(ws_stage_), hop, r);
+                append_staged_runs(runs, b, ws_stage_.as<float>(), hop, r);
                 ls = launch_blockdft_streams(runs.data(), runs.size(), hop * r, d_out_db, nullptr, rows_total, nullptr, stream);
                 if (ls != PVQ_OK) return ls;
             }
@@ -1573,16 +1546,16 @@ pvq_status Vqt::batch_streams_device(const float* const* d_pcm, const size_t* n_
 
 // One staged buffer into ws_stage_: the piece table up, then the copy kernel (every sample of the buffer is written).
 pvq_status Vqt::stage_buffer(const StagedBuffer& b, size_t hop, hipStream_t stream) {
-    pvq_status es = ensure_workspace(&ws_stage_, &ws_stage_cap_, b.frames * hop * sizeof(float));
+    pvq_status es = ws_stage_.reserve(b.frames * hop * sizeof(float));
     if (es != PVQ_OK) return es;
-    es = ensure_workspace(&ws_stage_tab_, &ws_stage_tab_cap_, b.pieces.size() * sizeof(StagePiece));
+    es = ws_stage_tab_.reserve(b.pieces.size() * sizeof(StagePiece));
     if (es != PVQ_OK) return es;
-    PVQ_HIP(hipMemcpyAsync(ws_stage_tab_, b.pieces.data(), b.pieces.size() * sizeof(StagePiece), hipMemcpyHostToDevice, stream));   // (pageable source: staged before the call returns)
+    PVQ_HIP(hipMemcpyAsync(ws_stage_tab_.as<void>(), b.pieces.data(), b.pieces.size() * sizeof(StagePiece), hipMemcpyHostToDevice, stream));   // (pageable source: staged before the call returns)
     // (the piece table holds at most 65 535 pieces per launch of the copy kernel: grid.y)
     for (size_t p0 = 0; p0 < b.pieces.size(); p0 += 65535) {
         const unsigned np = (unsigned)std::min<size_t>(65535, b.pieces.size() - p0);
         const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((b.longest + 1023) / 1024, 64));
-        hipLaunchKernelGGL(stage_streams, dim3(gx, np), dim3(256), 0, stream, static_cast<float*>(ws_stage_), static_cast<const StagePiece*>(ws_stage_tab_) + p0);
+        hipLaunchKernelGGL(stage_streams, dim3(gx, np), dim3(256), 0, stream, ws_stage_.as<float>(), ws_stage_tab_.as<StagePiece>() + p0);
     }
     return PVQ_OK;
 }
@@ -1600,18 +1573,18 @@ pvq_status Vqt::calculate_batch_db(const float* pcm, size_t n_lead, size_t hop, 
     PVQ_HIP(hipDeviceSynchronize());
     PVQ_HIP(hipMemset(dev_->d_status, 0, sizeof(uint32_t)));
     const size_t n_samples = n_lead + n_frames * hop;
-    pvq_status st = ensure_workspace(&ws_pcm_, &ws_pcm_cap_, n_samples * sizeof(float));
+    pvq_status st = ws_pcm_.reserve(n_samples * sizeof(float));
     if (st != PVQ_OK) return st;
-    st = ensure_workspace(&ws_out_, &ws_out_cap_, n_frames * n_bins() * sizeof(float));
+    st = ws_out_.reserve(n_frames * n_bins() * sizeof(float));
     if (st != PVQ_OK) return st;
     const size_t nb = n_bins();
     constexpr size_t PART = 16384;   // frames per pipeline part
     if (n_frames < 2 * PART) {
-        PVQ_HIP(hipMemcpy(ws_pcm_, pcm, n_samples * sizeof(float), hipMemcpyHostToDevice));
-        st = calculate_batch_db_device(static_cast<const float*>(ws_pcm_), n_lead, hop, n_frames,
-                                       static_cast<float*>(ws_out_), nullptr, nullptr);
+        PVQ_HIP(hipMemcpy(ws_pcm_.as<void>(), pcm, n_samples * sizeof(float), hipMemcpyHostToDevice));
+        st = calculate_batch_db_device(ws_pcm_.as<float>(), n_lead, hop, n_frames,
+                                       ws_out_.as<float>(), nullptr, nullptr);
         if (st != PVQ_OK) return st;
-        PVQ_HIP(hipMemcpy(out_db, ws_out_, n_frames * nb * sizeof(float), hipMemcpyDeviceToHost));
+        PVQ_HIP(hipMemcpy(out_db, ws_out_.as<void>(), n_frames * nb * sizeof(float), hipMemcpyDeviceToHost));
         return input_status(nullptr);
     }
     // Large batches: upload, transform and download in parts on three streams, so that with page-locked host buffers
@@ -1629,8 +1602,8 @@ pvq_status Vqt::calculate_batch_db(const float* pcm, size_t n_lead, size_t hop, 
         PVQ_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         host_events_.push_back(e);
     }
-    float* d_pcm = static_cast<float*>(ws_pcm_);
-    float* d_out = static_cast<float*>(ws_out_);
+    float* d_pcm = ws_pcm_.as<float>();
+    float* d_out = ws_out_.as<float>();
     size_t sample_done = 0;
     // the path is decided ONCE for the whole call and pinned for its parts (as analyze_batch_multi does for its shards): left to itself
     // PVQ_ALGO_AUTO would send a tail part below its threshold to the FFT path, whose values agree with the block-DFT path's to the
@@ -1697,9 +1670,9 @@ pvq_status Vqt::calculate_vqt_instant_in_db(const float* x, size_t len, float* o
         pvq_status os = order_on(inst_stream_);
         if (os != PVQ_OK) return os;
     }
-    pvq_status st = ensure_workspace(&ws_pcm_, &ws_pcm_cap_, wu * sizeof(float));
+    pvq_status st = ws_pcm_.reserve(wu * sizeof(float));
     if (st != PVQ_OK) return st;
-    st = ensure_workspace(&ws_out_, &ws_out_cap_, nb * sizeof(float));
+    st = ws_out_.reserve(nb * sizeof(float));
     if (st != PVQ_OK) return st;
     const float* src = x + (n_fft - wu);
     float bad = 0.0f;   // x - x is 0 for a finite x, NaN for NaN / Inf
@@ -1712,12 +1685,12 @@ pvq_status Vqt::calculate_vqt_instant_in_db(const float* x, size_t len, float* o
                        "callback drops such chunks, audio_desktop.rs:102-105; peak_detection.rs:145 would panic)");
         return PVQ_ERR_NONFINITE_INPUT;
     }
-    PVQ_HIP(hipMemcpyAsync(ws_pcm_, inst_pin_, wu * sizeof(float), hipMemcpyHostToDevice, inst_stream_));
+    PVQ_HIP(hipMemcpyAsync(ws_pcm_.as<void>(), inst_pin_, wu * sizeof(float), hipMemcpyHostToDevice, inst_stream_));
     // frame 0 of a stream of `wu` samples with wu - 1 of them as history and a hop of 1: its n_fft buffer ends at the last sample
-    st = launch_fft_path(static_cast<const float*>(ws_pcm_), wu - 1, 1, 1, static_cast<float*>(ws_out_), nullptr, nullptr, inst_stream_);
+    st = launch_fft_path(ws_pcm_.as<float>(), wu - 1, 1, 1, ws_out_.as<float>(), nullptr, nullptr, inst_stream_);
     if (st != PVQ_OK) return st;
     last_algo_ = PVQ_ALGO_FFT;
-    PVQ_HIP(hipMemcpyAsync(inst_pin_ + wu, ws_out_, nb * sizeof(float), hipMemcpyDeviceToHost, inst_stream_));
+    PVQ_HIP(hipMemcpyAsync(inst_pin_ + wu, ws_out_.as<void>(), nb * sizeof(float), hipMemcpyDeviceToHost, inst_stream_));
     PVQ_HIP(hipStreamSynchronize(inst_stream_));
     std::copy(inst_pin_ + wu, inst_pin_ + wu + nb, out_db);
     return PVQ_OK;
@@ -1726,8 +1699,8 @@ pvq_status Vqt::calculate_vqt_instant_in_db(const float* x, size_t len, float* o
 // the peak kernels as one timed stage (SLOT_PEAKS); callers check hipGetLastError where they always did
 pvq_status Vqt::peaks_stage(const float* d_db, size_t n_frames, const PeakParamsDev& a, hipStream_t stream) {
     slot_begin(SLOT_PEAKS, stream);
-    pvq_status st = ensure_workspace(&ws_flags_, &ws_flags_cap_, n_frames);
-    if (st == PVQ_OK) st = launch_peaks_frames(d_db, n_frames, a, static_cast<uint8_t*>(ws_flags_), stream);
+    pvq_status st = ws_flags_.reserve(n_frames);
+    if (st == PVQ_OK) st = launch_peaks_frames(d_db, n_frames, a, ws_flags_.as<uint8_t>(), stream);
     slot_end(SLOT_PEAKS, stream);
     return st;
 }
@@ -1824,18 +1797,18 @@ pvq_status Vqt::analyze_batch(const float* db, size_t n_frames, const AnalysisPa
     const size_t b_mask = n_frames * words * sizeof(uint32_t);
     const size_t b_cnt = n_frames * sizeof(uint32_t);
     const size_t b_pk = n_frames * (size_t)max_peaks * sizeof(float);
-    pvq_status st = ensure_workspace(&ws_out_, &ws_out_cap_, b_db);
+    pvq_status st = ws_out_.reserve(b_db);
     if (st != PVQ_OK) return st;
-    st = ensure_workspace(&ws_misc_, &ws_misc_cap_, b_mask + b_cnt + 2 * b_pk + 64);
+    st = ws_misc_.reserve(b_mask + b_cnt + 2 * b_pk + 64);
     if (st != PVQ_OK) return st;
-    char* base = static_cast<char*>(ws_misc_);
+    char* base = ws_misc_.as<char>();
     uint32_t* d_mask = reinterpret_cast<uint32_t*>(base);
     uint32_t* d_cnt = reinterpret_cast<uint32_t*>(base + b_mask);
     float* d_ctr = reinterpret_cast<float*>(base + b_mask + b_cnt);
     float* d_sz = reinterpret_cast<float*>(base + b_mask + b_cnt + b_pk);
-    PVQ_HIP(hipMemcpy(ws_out_, db, b_db, hipMemcpyHostToDevice));
+    PVQ_HIP(hipMemcpy(ws_out_.as<void>(), db, b_db, hipMemcpyHostToDevice));
     if (max_peaks) PVQ_HIP(hipMemset(d_ctr, 0, 2 * b_pk));
-    st = analyze_batch_device(static_cast<const float*>(ws_out_), n_frames, ap, d_mask, d_cnt,
+    st = analyze_batch_device(ws_out_.as<float>(), n_frames, ap, d_mask, d_cnt,
                               max_peaks ? d_ctr : nullptr, max_peaks ? d_sz : nullptr, max_peaks, nullptr);
     if (st != PVQ_OK) return st;
     PVQ_HIP(hipDeviceSynchronize());
@@ -1866,9 +1839,9 @@ pvq_status Vqt::multi_buffers(const size_t (&bytes)[6], void* (&out)[6], hipStre
             out[i] = nullptr;
             continue;
         }
-        pvq_status e = ensure_workspace(&multi_buf_[i], &multi_cap_[i], bytes[i]);
+        pvq_status e = multi_buf_[i].reserve(bytes[i]);
         if (e != PVQ_OK) return e;
-        out[i] = multi_buf_[i];
+        out[i] = multi_buf_[i].as<void>();
     }
     *st = multi_stream_;
     return PVQ_OK;

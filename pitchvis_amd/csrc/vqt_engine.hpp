@@ -15,6 +15,7 @@
 #include "../../include/pvq.h"
 #include "batch_plan.hpp"
 #include "blockdft_plan.hpp"
+#include "device_support.hpp"
 #include "multi_host.hpp"
 #include "vqt_host.hpp"
 
@@ -149,7 +150,6 @@ class Vqt {
     pvq_status launch_blockdft_dots(const BlockLaunch& L, float* d_out_db, float* d_out_cplx, hipStream_t stream);
     pvq_status launch_blockdft_path(const float* d_pcm, size_t n_lead, size_t hop, size_t n_frames,
                                     float* d_out_db, float* d_out_cplx, const PeakParamsDev* pk, hipStream_t stream);
-    pvq_status ensure_workspace(void** ptr, size_t* cap, size_t bytes);
     pvq_status peaks_stage(const float* d_db, size_t n_frames, const PeakParamsDev& p, hipStream_t s);   // the peak kernels as the timed SLOT_PEAKS stage
     void slot_begin(int slot, hipStream_t s);
     // One handle's calls are ORDERED: the workspaces (X, the group-split rows, staging buffers, tile-list slots, the peak kernels' redo
@@ -184,16 +184,13 @@ class Vqt {
     std::vector<hipEvent_t> ev_[N_SLOTS][2];  // event pool, grown on demand
     int ev_count_[N_SLOTS] = {};              // launches recorded since profiling was enabled
     // grow-only workspaces for the host-pointer wrappers
-    void* ws_pcm_ = nullptr;  size_t ws_pcm_cap_ = 0;
-    void* ws_out_ = nullptr;  size_t ws_out_cap_ = 0;
-    void* ws_misc_ = nullptr; size_t ws_misc_cap_ = 0;
-    void* ws_flags_ = nullptr; size_t ws_flags_cap_ = 0;  // per-frame redo flags of the peak kernels
-    void* ws_stage_ = nullptr; size_t ws_stage_cap_ = 0;  // many short streams staged one behind the other (batch_streams_device)
-    void* ws_stage_tab_ = nullptr; size_t ws_stage_tab_cap_ = 0;
-    void* ws_split_ = nullptr; size_t ws_split_cap_ = 0;   // x_vqt rows of a group-split launch of the FFT path (few frames)
+    DeviceBuffer ws_pcm_, ws_out_, ws_misc_;
+    DeviceBuffer ws_flags_;   // per-frame redo flags of the peak kernels
+    DeviceBuffer ws_stage_;   // many short streams staged one behind the other (batch_streams_device)
+    DeviceBuffer ws_stage_tab_;
+    DeviceBuffer ws_split_;   // x_vqt rows of a group-split launch of the FFT path (few frames)
     // the multi-device driver's per-handle shard buffers (PCM, dB, mask, count, center, size) and stream, grow-only
-    void* multi_buf_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t multi_cap_[6] = {0, 0, 0, 0, 0, 0};
+    DeviceBuffer multi_buf_[6];
     hipStream_t multi_stream_ = nullptr;
    public:
     pvq_status multi_buffers(const size_t (&bytes)[6], void* (&out)[6], hipStream_t* st);   // (used by analyze_batch_multi's workers)
@@ -210,9 +207,5 @@ pvq_status analyze_batch_multi(Vqt* const* handles, uint32_t n_handles, const fl
 
 // find_peaks over n_frames independent dB rows [n_frames][a.n_bins] (vqt_engine.hip; redo: n_frames bytes of device scratch)
 pvq_status launch_peaks_frames(const float* d_db, size_t n_frames, const PeakParamsDev& a, uint8_t* redo, hipStream_t stream);
-
-void set_last_error(const std::string& s);
-void set_last_error_noexcept(const char* s) noexcept;   // for exception handlers: never throws (drops the text if it cannot be stored)
-const char* get_last_error();
 
 }  // namespace pvq

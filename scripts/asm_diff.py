@@ -1,23 +1,24 @@
 #!/usr/bin/env python3
-"""Compare the compiled device code of the block-DFT kernels of two source trees, kernel by kernel (no GPU needed).
+"""Compare the compiled device code of two source trees, kernel by kernel (no GPU needed).
 
-    scripts/blockdft_asm_diff.py OLD_TREE NEW_TREE
+    scripts/asm_diff.py OLD_TREE NEW_TREE [UNIT.hip ...]
 
-Each tree's block-DFT units (whichever of vqt_blockdft.hip, blockdft_gemm.hip, blockdft_dots.hip it has) are compiled with the
-HIPFLAGS of its own Makefile plus -S --cuda-device-only, once without and once with -DPVQ_DEV_KNOBS.  The output is cut into
+The units are every *.hip under pitchvis_amd/csrc that either tree has, or the ones named (the block-DFT path alone:
+vqt_blockdft.hip blockdft_gemm.hip blockdft_dots.hip).  Each is compiled with the
+HIPFLAGS of its own tree's Makefile plus -S --cuda-device-only, once without and once with -DPVQ_DEV_KNOBS.  The output is cut into
 function bodies as tests/test_kernel_resources.py cuts it (label `_ZN3pvq...:` to `.Lfunc_end`); the per-function counters of local
 labels (.LBB<n>_, .Ltmp<n>, .Lfunc_begin<n>, and the BB<n>_ of the loop comments) are replaced by a fixed string — they move when a
 kernel before this one leaves the unit — together with the padding between a label and its comment, which follows the counter's
-width; nothing else is normalised.  Prints, per flavour, the names on either side and whether each body is equal; exits 1 if
-any body that both trees have differs."""
+width; nothing else is normalised.  Prints, per flavour, the (unit, name) pairs on either side and whether each body is equal;
+exits 1 if any body that both trees have differs, or if the two sides' names differ."""
 import hashlib
 import os
 import re
 import subprocess
 import sys
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
-UNITS = ("vqt_blockdft.hip", "blockdft_gemm.hip", "blockdft_dots.hip")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -27,21 +28,28 @@ def hipflags(csrc):
     return re.search(r"^HIPFLAGS\s*:=\s*(.*)$", mk, re.M).group(1).replace("$(ARCH)", arch).split()
 
 
-def bodies(tree, dev, tmp):
-    csrc = os.path.join(tree, "pitchvis_amd", "csrc")
+def csrc_of(tree):
+    return os.path.join(tree, "pitchvis_amd", "csrc")
+
+
+def bodies(tree, units, dev, tmp):
+    csrc = csrc_of(tree)
     out = {}
-    for unit in UNITS:
-        src = os.path.join(csrc, unit)
-        if not os.path.exists(src):
-            continue
+    units = [u for u in units if os.path.exists(os.path.join(csrc, u))]
+
+    def compile_unit(unit):
+        cmd = [HIPCC] + hipflags(csrc) + (["-DPVQ_DEV_KNOBS"] if dev else [])
+        subprocess.run(cmd + ["-S", "--cuda-device-only", os.path.join(csrc, unit), "-o", os.path.join(tmp, unit + ".s")], check=True, stderr=subprocess.DEVNULL)
+
+    with ThreadPoolExecutor(max_workers=8) as pool:
+        list(pool.map(compile_unit, units))
+    for unit in units:
         asm = os.path.join(tmp, unit + ".s")
-        cmd = [HIPCC] + hipflags(csrc) + (["-DPVQ_DEV_KNOBS"] if dev else []) + ["-S", "--cuda-device-only", src, "-o", asm]
-        subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
         inside = None
         for line in open(asm).read().splitlines():
             m = re.match(r"(_ZN3pvq\w+):", line)
             if m:
-                inside = m.group(1)
+                inside = (unit, m.group(1))
                 assert inside not in out, inside
                 out[inside] = []
             elif line.startswith(".Lfunc_end"):
@@ -54,17 +62,19 @@ def bodies(tree, dev, tmp):
 
 def main():
     old, new = sys.argv[1:3]
+    units = sys.argv[3:] or sorted({f for t in (old, new) for f in os.listdir(csrc_of(t)) if f.endswith(".hip")})
     differ = 0
     with tempfile.TemporaryDirectory() as tmp:
         for dev in (False, True):
-            a, b = bodies(old, dev, tmp), bodies(new, dev, tmp)
+            a, b = bodies(old, units, dev, tmp), bodies(new, units, dev, tmp)
+            differ += set(a) != set(b)
             print("== %s build: old %d kernels, new %d kernels" % ("dev (-DPVQ_DEV_KNOBS)" if dev else "prod", len(a), len(b)))
             print("only in old: %s" % sorted(set(a) - set(b)))
             print("only in new: %s" % sorted(set(b) - set(a)))
             for k in sorted(set(a) & set(b)):
                 same = a[k] == b[k]
                 differ += not same
-                print("  %s  lines %d  sha256 %s  %s" % (k, len(b[k]), hashlib.sha256("\n".join(b[k]).encode()).hexdigest()[:16], "equal" if same else "DIFFERS"))
+                print("  %s %s  lines %d  sha256 %s  %s" % (k[0], k[1], len(b[k]), hashlib.sha256("\n".join(b[k]).encode()).hexdigest()[:16], "equal" if same else "DIFFERS"))
             print("names compared: %d; bodies equal: %d" % (len(set(a) & set(b)), sum(a[k] == b[k] for k in set(a) & set(b))))
     return 1 if differ else 0
 

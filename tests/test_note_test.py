@@ -81,13 +81,7 @@ def test_metrics_refuses():
 def plan_tool(tmp_path_factory):
     if shutil.which("g++") is None:
         pytest.skip("g++ not installed")
-    csrc = os.path.join(ROOT, "pitchvis_amd", "csrc")
-    exe = os.path.join(str(tmp_path_factory.mktemp("note_test_plan")), "note_test_plan")
-    cmd = ["g++", "-std=c++17", "-Wall", *note_plan_tool.SAN, "-I", csrc, os.path.join(ROOT, "tests", "sanitize", "note_test_plan_main.cpp"),
-           os.path.join(csrc, "note_model_plan.cpp"), os.path.join(csrc, "note_trainer_plan.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+    return note_plan_tool.build(tmp_path_factory.mktemp("note_test_plan"), "note_test_plan_main.cpp")
 
 
 def _plan(exe, n_idx, max_batch, batch):
