@@ -54,6 +54,9 @@ struct BlockDftTables {
     float* d_band_B4 = nullptr;    // per block and 4 columns: 64 x (Re coefficient, Im coefficient): the no-swap form
     int* d_band_list8 = nullptr;   // [8][band_per_wave8]
     int band_per_wave8 = 0;
+    struct BandStage* d_band_stages8 = nullptr;   // [8][band_stage_stride8]: the 8-bin blocks as one stage stream per wave
+    int band_stage_stride8 = 0;
+    int band_stage_count8[8] = {};
     int* d_band_list = nullptr;    // [band_waves][band_per_wave]: per wave of a workgroup, the count and then the blocks it walks
     int band_per_wave = 0;
     int band_waves = 4;            // waves per kernel-product workgroup (8 when the 64-frame form is used)

@@ -1,6 +1,7 @@
 // blockdft_dots.hip — the kernel product + power_to_db stage of the block-DFT path (vqt_blockdft.hip has the map), with its launcher.
 //
-// Kernels:  blockdft_banddots4c_db / blockdft_banddots_db[_bf16x3] (kernel product as a banded MFMA GEMM + power_to_db)
+// Kernels:  blockdft_banddots4c_db / blockdft_banddots_db[_bf16x3] (kernel product as a banded MFMA GEMM + power_to_db);
+//           developer library only: blockdft_banddots4c_blocks_db, blockdft_banddots_db<2, 8>
 #include <type_traits>
 
 #include "blockdft_device.hpp"
@@ -32,6 +33,9 @@ struct BandArgs {
     const __bf16* B3;          // split-bf16 coefficient planes
     const int* list;           // [waves][per_wave]: count, then the blocks of that wave
     int per_wave;
+    const BandStage* stages;   // 8-bin stream form: [8][stage_stride], a wave's stages end to end (blockdft_plan.hpp)
+    int stage_stride;
+    int stage_count[8];        // stages wave w multiplies: a multiple of BD8_NS
     float* out_db;             // [n_frames][n_bins]
     float2* out_cplx;          // optional
     unsigned* status;          // the handle's sticky flag word: bit 0 <- a live frame holds a non-finite power value
@@ -325,8 +329,151 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 // half tile u; the B operand of lane (n, kq) is the coefficient of column c + kq for output n (n < 8: re of bin row n, else im),
 // one register for the Re parts and one for the Im parts.  Per four columns: two 16-byte X loads and one 8-byte B load per lane
 // instead of four 8-byte loads + one, eight MFMAs as before, no swaps.  C layout: output n = lane & 15, frame 32 u + 2 (4 (lane >> 4) + r) + p.
+typedef const __attribute__((address_space(4))) i32x4 stage_desc_c;   // a BandStage as the scalar unit loads it
+static_assert(sizeof(BandStage) == sizeof(i32x4) && alignof(BandStage) == alignof(i32x4), "blockdft_plan.hpp: BandStage must be one 16-byte load");
 template <int NW, int NS, int LDB, int NU>   // LDB: row stride of the LDS tile (4 mod 16, >= bins); NU: half tiles of 32 frames per workgroup (2: a whole X tile; 1 — half a tile, 4 waves, four workgroups per CU — was measured slower: 141-150 against 121 us)
 __global__ __launch_bounds__(64 * NW, NU == 2 || NW == 8 ? NW / 2 : NW) void blockdft_banddots4c_db(BandArgs a) {   // (four waves per SIMD)
+    // the bin counts an LDS row stride serves (the host's choice of the instantiation): the finish's other size classes fold away
+    if constexpr (LDB == 260) __builtin_assume(a.n_bins <= 256);
+    else if constexpr (LDB == 308) __builtin_assume(a.n_bins > 256 && a.n_bins <= 304);
+    else if constexpr (LDB == 372) __builtin_assume(a.n_bins > 256 && a.n_bins <= 368);   // (257 ... 304 bins come here with the developer knob PVQ_DOTS_F32 behind the split-bf16 GEMM)
+    else if constexpr (LDB == 596) __builtin_assume(a.n_bins > 368 && a.n_bins <= 592);
+    else if constexpr (LDB == 852) __builtin_assume(a.n_bins > 592 && a.n_bins <= 848);
+    else if constexpr (LDB == 1028) __builtin_assume(a.n_bins > 848 && a.n_bins <= 1024);
+    const int stamp_slot = blockIdx.x;
+    extern __shared__ __attribute__((aligned(16))) float dbs[];   // [64][LDB]: |x_vqt|^2, then dB
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int f0 = blockIdx.x * (32 * NU);
+    constexpr int col_stride = 128;   // floats between consecutive X columns of a 64-frame tile
+    const float* xtile = a.X + ((size_t)(f0 >> 6) * a.xcp) * col_stride + (f0 & 63) * 2;   // (a half-tile workgroup starts at frame pair 16 of its tile)
+    // the output rows of this workgroup's frames: rows f0 ... of a single stream, or what the X tile's entry of the map says
+    long long row0 = f0;
+    int n_live = a.n_frames - f0, rstep = 1;
+    if (a.xmap) {   // (uniform)
+        const XTile xt = a.xmap[f0 >> 6];
+        rstep = xt.live_step >> 8;
+        row0 = xt.out_row0 + (long long)(f0 & 63) * rstep;
+        n_live = (xt.live_step & 255) - (f0 & 63);
+        if (n_live <= 0) return;   // (uniform) a staged buffer's gap frames: nothing of this tile is wanted (Vqt::batch_streams_device)
+    }
+    PVQ_STAMP(0);
+    // The wave's stage stream (BandStage, blockdft_plan.hpp): its blocks' 4-column stages end to end, null stages after the last.  The
+    // descriptors are scalar loads through the constant cache, issued two rounds of NS stages before the stage they describe is
+    // fetched; the count travels in the kernel arguments.  One operand ring runs over the whole stream: a block boundary is a
+    // wave-uniform branch (write-out + accumulator reset) with no load in it, and nothing is fetched that is not multiplied except
+    // the null stages (zeroed pad columns of X, zero coefficients: they add +0 to an accumulator that is never written out).
+    const stage_desc_c* sl = reinterpret_cast<const stage_desc_c*>(reinterpret_cast<uintptr_t>(a.stages)) + (size_t)wave * a.stage_stride;
+    const int n_rounds = a.stage_count[wave] / NS;
+    const int n = lane & 15, kq = lane >> 4;
+    const unsigned xlane = (unsigned)(kq * col_stride + n * 4);   // a lane's 16 bytes within a stage's four columns
+    const float2* bcoef = reinterpret_cast<const float2*>(a.B);
+    f32x4 av[NS][NU];
+    float2 bv[NS];
+    auto fetch = [&](int s, const i32x4& d) {   // uniform base + lane offset: the stage's columns d.x .. d.x + 3, coefficient group d.y
+        bv[s] = (bcoef + (size_t)(unsigned)d.y * 64)[(unsigned)lane];
+        const float* xs = xtile + (size_t)(unsigned)d.x * col_stride;
+#pragma unroll
+        for (int u = 0; u < NU; ++u) av[s][u] = *reinterpret_cast<const f32x4*>(xs + u * 64 + xlane);
+    };
+    i32x4 cur[NS], nxt[NS], far[NS];   // descriptors of this round's stages, of the next round's, of the one after
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        cur[s] = sl[s];
+        nxt[s] = sl[NS + s];
+    }
+#pragma unroll
+    for (int s = 0; s < NS - 1; ++s) {
+        fetch(s, cur[s]);
+        __builtin_amdgcn_sched_barrier(0);   // in ring order: the first round's waits count the loads behind a stage's own
+    }
+    f32x4v acc[NU][2];   // [half tile u][p: even / odd frames]
+    auto reset = [&] {
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[u][p][q] = 0.0f;
+    };
+    auto mul = [&](int s) {   // independent accumulators between two uses of one
+#pragma unroll
+        for (int part = 0; part < 2; ++part) {   // Re parts of the four columns, then Im parts
+            const float b = part ? bv[s].y : bv[s].x;
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+                acc[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s][u][part], b, acc[u][0], 0, 0, 0);
+                acc[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s][u][2 + part], b, acc[u][1], 0, 0, 0);
+            }
+        }
+    };
+    auto writeout = [&](int bin0, int nrows) {
+        const bool mine = n < nrows;                  // re columns of live rows
+        const int bin = bin0 + n;
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                float im[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {   // row_ror:8: lane n <- lane n ^ 8 (through a scalar copy: the DPP of a vector element was seen merged across q)
+                    const float re_q = acc[u][p][q];
+                    im[q] = PVQ_DPP(re_q, 0x128);
+                }
+                if (mine) {
+#pragma unroll
+                    // re^2 rounded, then im^2 fused on top: spelled out, so that every instantiation rounds as the block loop's did
+                    for (int q = 0; q < 4; ++q) dbs[(32 * u + 8 * kq + 2 * q + p) * LDB + bin] = __builtin_fmaf(im[q], im[q], acc[u][p][q] * acc[u][p][q]);
+                    if (a.out_cplx) {
+                        int row_stride = a.n_bins;
+                        asm volatile("" : "+s"(row_stride));
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const int fr = 32 * u + 8 * kq + 2 * q + p;
+                            if (fr < n_live) a.out_cplx[(size_t)(row0 + (long long)fr * rstep) * row_stride + bin] = make_float2(acc[u][p][q], im[q]);
+                        }
+                    }
+                }
+            }
+    };
+    reset();
+    for (int r = 0; r < n_rounds; ++r) {   // a round: NS stages, ring slots fixed at compile time
+        sl += NS;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) far[s] = sl[NS + s];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            fetch((s + NS - 1) % NS, s == 0 ? cur[NS - 1] : nxt[s - 1]);   // the stage NS - 1 ahead
+            mul(s);
+            __builtin_amdgcn_sched_barrier(0);   // keep the waits on a stage's operands inside the stage
+            if (cur[s].w) {                      // (uniform) the block's last stage
+                writeout(cur[s].z, cur[s].w & (BAND_STAGE_LAST - 1));
+                reset();
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            cur[s] = nxt[s];
+            nxt[s] = far[s];
+        }
+    }
+    PVQ_STAMP(1);
+    __syncthreads();
+    PVQ_STAMP(2);
+    band_finish<NU, NW, LDB>(dbs, a, row0, n_live, rstep, wave, lane);
+    if (a.stamps) {
+        __builtin_amdgcn_s_waitcnt(0);
+        __syncthreads();
+        PVQ_STAMP(3);
+    }
+}
+
+
+#ifdef PVQ_DEV_KNOBS
+// The block loop this kernel had before the stage stream: per block, two dependent descriptor loads, a ring restart and NS - 1
+// stages fetched past the block's end.  Same MFMAs in the same order: what the stream form is compared against, bit for bit
+// (developer knob PVQ_DOTS_BLOCKS; tests/test_dots_stream_gpu.py, scripts/dev_ab_knob.py).
+template <int NW, int NS, int LDB, int NU>
+__global__ __launch_bounds__(64 * NW, NU == 2 || NW == 8 ? NW / 2 : NW) void blockdft_banddots4c_blocks_db(BandArgs a) {   // (four waves per SIMD)
     // the bin counts an LDS row stride serves (the host's choice of the instantiation): the finish's other size classes fold away
     if constexpr (LDB == 260) __builtin_assume(a.n_bins <= 256);
     else if constexpr (LDB == 308) __builtin_assume(a.n_bins > 256 && a.n_bins <= 304);
@@ -449,6 +596,7 @@ __global__ __launch_bounds__(64 * NW, NU == 2 || NW == 8 ? NW / 2 : NW) void blo
         PVQ_STAMP(3);
     }
 }
+#endif
 
 // Split-bf16 form of the kernel product (the default, with the split-bf16 GEMM): the fp32 MFMA above runs at 1/16
 // of the bf16 matrix rate, and a 16-bin block is 73 % zeros, so the stage is matrix-bound.  Here X and the
@@ -588,6 +736,9 @@ pvq_status Vqt::launch_blockdft_dots(const BlockLaunch& L, float* d_out_db, floa
     da.B3 = t->d_band_B3;
     da.list = t->d_band_list;
     da.per_wave = t->band_per_wave;
+    da.stages = nullptr;
+    da.stage_stride = 0;
+    std::fill(da.stage_count, da.stage_count + 8, 0);
     // one run: its rows follow each other from its first output row; several: the X-tile map names every tile's rows
     da.xmap = L.d_xmap;
     const size_t row_first = L.multi ? 0 : (size_t)L.shape->segs[0].out_row0;
@@ -607,6 +758,7 @@ pvq_status Vqt::launch_blockdft_dots(const BlockLaunch& L, float* d_out_db, floa
     const bool dots_split = gemm_split_bf16_ && !dots_f32_env;   // the kernel product follows the GEMM arithmetic
 #ifdef PVQ_DEV_KNOBS
     static const int dots16_env = dev_knob("PVQ_DOTS_16BIN", 0);   // the 16-bin 32x32x2 form wherever it fits
+    static const int dots_blocks_env = dev_knob("PVQ_DOTS_BLOCKS", 0);   // the 8-bin form's block loop instead of its stage stream (A/B, bit identity)
 #else
     constexpr int dots16_env = 0;
 #endif
@@ -617,6 +769,9 @@ pvq_status Vqt::launch_blockdft_dots(const BlockLaunch& L, float* d_out_db, floa
         da.list = t->d_band_list8;
         da.per_wave = t->band_per_wave8;
         da.B = t->d_band_B4;
+        da.stages = t->d_band_stages8;
+        da.stage_stride = t->band_stage_stride8;
+        std::copy(t->band_stage_count8, t->band_stage_count8 + 8, da.stage_count);
     };
     if (dots_split) {
         da.list = t->d_band_list + (size_t)t->band_waves * t->band_per_wave;   // the 4-wave lists
@@ -630,6 +785,14 @@ pvq_status Vqt::launch_blockdft_dots(const BlockLaunch& L, float* d_out_db, floa
 #endif
     } else if (mt == 2) {
         use_8bin_blocks();
+#ifdef PVQ_DEV_KNOBS
+        if (dots_blocks_env) {
+            if (wide308)
+                hipLaunchKernelGGL((blockdft_banddots4c_blocks_db<8, BD8_NS, BAND_LDB3, 2>), grid, dim3(512), lds, stream, da);
+            else
+                hipLaunchKernelGGL((blockdft_banddots4c_blocks_db<8, BD8_NS, BAND_LDB2, 2>), grid, dim3(512), lds, stream, da);
+        } else
+#endif
         if (wide308)
             hipLaunchKernelGGL((blockdft_banddots4c_db<8, BD8_NS, BAND_LDB3, 2>), grid, dim3(512), lds, stream, da);
         else
@@ -649,9 +812,18 @@ pvq_status Vqt::launch_blockdft_dots(const BlockLaunch& L, float* d_out_db, floa
             hipLaunchKernelGGL(kern, grid, dim3(512), lds_c, stream, da);
             return PVQ_OK;
         };
-        pvq_status lcs = ldb_c == 372 ? launch_c(blockdft_banddots4c_db<8, BD8_NS, 372, 1>) : ldb_c == 596 ? launch_c(blockdft_banddots4c_db<8, BD8_NS, 596, 1>)
-                         : ldb_c == 852 ? launch_c(blockdft_banddots4c_db<8, BD8_NS, 852, 1>) : launch_c(blockdft_banddots4c_db<8, BD8_NS, 1028, 1>);
-        if (lcs != PVQ_OK) return lcs;
+#ifdef PVQ_DEV_KNOBS
+        if (dots_blocks_env) {
+            pvq_status lbs = ldb_c == 372 ? launch_c(blockdft_banddots4c_blocks_db<8, BD8_NS, 372, 1>) : ldb_c == 596 ? launch_c(blockdft_banddots4c_blocks_db<8, BD8_NS, 596, 1>)
+                             : ldb_c == 852 ? launch_c(blockdft_banddots4c_blocks_db<8, BD8_NS, 852, 1>) : launch_c(blockdft_banddots4c_blocks_db<8, BD8_NS, 1028, 1>);
+            if (lbs != PVQ_OK) return lbs;
+        } else
+#endif
+        {
+            pvq_status lcs = ldb_c == 372 ? launch_c(blockdft_banddots4c_db<8, BD8_NS, 372, 1>) : ldb_c == 596 ? launch_c(blockdft_banddots4c_db<8, BD8_NS, 596, 1>)
+                             : ldb_c == 852 ? launch_c(blockdft_banddots4c_db<8, BD8_NS, 852, 1>) : launch_c(blockdft_banddots4c_db<8, BD8_NS, 1028, 1>);
+            if (lcs != PVQ_OK) return lcs;
+        }
     }
     slot_end(SLOT_BLOCKDFT_DOTS, stream);
     if (do_dstamps) {

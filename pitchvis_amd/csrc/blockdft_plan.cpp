@@ -292,6 +292,31 @@ bool build_blockdft_tables(const HostPlan& plan, size_t hop, bool twiddle_fp16, 
     t.band_per_wave8 = (int)t.band8.size() + 2;
     t.band_list8.assign((size_t)8 * t.band_per_wave8, 0);
     deal_blocks(t.band8.size(), 8, t.band_per_wave8, t.band_list8.data());
+    // ... and as one stage stream per wave (BandStage): a wave's blocks end to end, so the kernel's operand ring never restarts
+    {
+        const BandStage null_stage{t.n_tiles * CB_C, (int)(t.band_B4.size() / 128) - 8, 0, 0};   // zeroed X columns x zero coefficients
+        int longest = 0;
+        for (int w = 0; w < 8; ++w) {
+            const int* row = t.band_list8.data() + (size_t)w * t.band_per_wave8;
+            int n = 0;
+            for (int i = 0; i < row[0]; ++i) n += t.band8[row[1 + i]].kb / BD8_KU;
+            t.band_stage_count8[w] = (n + BD8_NS - 1) / BD8_NS * BD8_NS;
+            longest = std::max(longest, t.band_stage_count8[w]);
+        }
+        t.band_stage_stride8 = longest + 2 * BD8_NS;
+        t.band_stages8.assign((size_t)8 * t.band_stage_stride8, null_stage);
+        for (int w = 0; w < 8; ++w) {
+            const int* row = t.band_list8.data() + (size_t)w * t.band_per_wave8;
+            BandStage* st = t.band_stages8.data() + (size_t)w * t.band_stage_stride8;
+            for (int i = 0; i < row[0]; ++i) {
+                const BandBlock& bb = t.band8[row[1 + i]];
+                const int ns = bb.kb / BD8_KU;
+                for (int s = 0; s < ns; ++s) *st++ = BandStage{bb.x0 + BD8_KU * s, bb.boff3 + s, 0, 0};
+                st[-1].bin0 = bb.bin0;
+                st[-1].fin = bb.nrows | BAND_STAGE_LAST;
+            }
+        }
+    }
     // split-bf16 planes of the 16-bin coefficients, 8 columns (16 real k) per MFMA: lane (n = l & 31, kh = l >> 5)
     // holds k = 8 kh + t, t = 0..7  <->  column 4 kh + t / 2, Re / Im row t & 1
     for (BandBlock& bb : t.band) {

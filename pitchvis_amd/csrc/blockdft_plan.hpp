@@ -60,6 +60,16 @@ struct BandBlock {
     int boff3;   // 16-bin blocks: first group in band_B3 (units of 3 planes x 64 lanes x 8 bf16); 8-bin blocks: first 4-column group in band_B4
 };
 
+// One 4-column stage of an 8-bin block, as blockdft_banddots4c_db walks a wave's blocks: one stream of stages per wave, the
+// blocks' stages one after the other in the order the wave was dealt them.  The kernel reads the entries through the constant cache.
+constexpr int BAND_STAGE_LAST = 1 << 8;
+struct alignas(16) BandStage {
+    int x;      // first X column of the stage: x0 + 4 s
+    int b;      // its 4-column coefficient group in band_B4: boff3 + s
+    int bin0;   // a block's last stage: the block's first output bin (else 0)
+    int fin;    // a block's last stage: nrows | BAND_STAGE_LAST (else 0)
+};
+
 // MANY streams in one launch (pvq_vqt_*_streams: the trainer's shape, pitchvis_train/src/train.rs:146-163 — many files side by side).
 // A launch covers a list of SEGMENTS, each a contiguous run of frames of one stream; a tile list entry names its segment
 // (.x bits 16..31), the segment table gives the tile its stream (offset from the launch's base pointer, readable bytes, where
@@ -119,6 +129,12 @@ struct BlockDftHostTables {
     std::vector<float> band_B4;       // per block and 4 columns: 64 x (Re coefficient, Im coefficient): the no-swap form
     std::vector<int> band_list8;      // [8][band_per_wave8]
     int band_per_wave8 = 0;
+    // the same blocks as one stage stream per wave: row w holds the stages of wave w's blocks of band_list8, then null stages (the
+    // zeroed pad columns of X times the zero pad of band_B4) up to band_stage_count8[w], a multiple of BD8_NS, and on to the end of
+    // the row: the ring's last BD8_NS - 1 operand fetches and the descriptor reads two rounds ahead stay inside it
+    std::vector<BandStage> band_stages8;   // [8][band_stage_stride8]
+    int band_stage_stride8 = 0;            // max count + 2 BD8_NS
+    int band_stage_count8[8] = {};         // stages wave w multiplies
 };
 // false (with the text in *err): the geometry has too many spectrum columns for the path
 bool build_blockdft_tables(const HostPlan& plan, size_t hop, bool twiddle_fp16, BlockDftHostTables& out, std::string* err);

@@ -42,7 +42,7 @@ static size_t chunk_frames(size_t limit_bytes, size_t bytes_per_frame) {
 void free_blockdft_tables(BlockDftTables* t) {
     if (!t) return;
     for (void* p : {(void*)t->d_E, (void*)t->d_Et, (void*)t->d_tile_group, (void*)t->d_tile_s, (void*)t->d_groups, (void*)t->d_comb_tw, (void*)t->d_band, (void*)t->d_band_B,
-                    (void*)t->d_band8, (void*)t->d_band_B4, (void*)t->d_band_list8, (void*)t->d_band_B3, (void*)t->d_band_list, (void*)t->d_P, (void*)t->d_X, (void*)t->d_Y,
+                    (void*)t->d_band8, (void*)t->d_band_B4, (void*)t->d_band_list8, (void*)t->d_band_stages8, (void*)t->d_band_B3, (void*)t->d_band_list, (void*)t->d_P, (void*)t->d_X, (void*)t->d_Y,
                     (void*)t->d_clk, (void*)t->d_E16, (void*)t->d_E16R, (void*)t->d_gen_tw})
         if (p) (void)hipFree(p);
     for (auto& tl : t->tile_lists)
@@ -119,9 +119,11 @@ pvq_status Vqt::prepare_blockdft(size_t hop) {
     t->band_per_wave = h.band_per_wave;
     t->band_waves = h.band_waves;
     t->band_per_wave8 = h.band_per_wave8;
+    t->band_stage_stride8 = h.band_stage_stride8;
+    std::copy(h.band_stage_count8, h.band_stage_count8 + 8, t->band_stage_count8);
     const bool ok = up(&t->d_E16R, h.E16R) && up(&t->d_gen_tw, h.gen_tw) && up(&t->d_E, h.E) && up(&t->d_tile_group, h.tile_group) && up(&t->d_tile_s, h.tile_s) &&
                     up(&t->d_groups, h.groups) && up(&t->d_comb_tw, h.comb_tw) && up(&t->d_band, h.band) && up(&t->d_band_B, h.band_B) && up(&t->d_band_list, h.band_list) &&
-                    up(&t->d_band8, h.band8) && up(&t->d_band_B4, h.band_B4) && up(&t->d_band_list8, h.band_list8) && up(&t->d_band_B3, h.band_B3) && up(&t->d_E16, h.E16);
+                    up(&t->d_band8, h.band8) && up(&t->d_band_B4, h.band_B4) && up(&t->d_band_list8, h.band_list8) && up(&t->d_band_stages8, h.band_stages8) && up(&t->d_band_B3, h.band_B3) && up(&t->d_E16, h.E16);
     if (!ok) {
         free_blockdft_tables(t);
         set_last_error("hipMalloc/hipMemcpy failed while building block-DFT tables");

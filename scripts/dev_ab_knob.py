@@ -42,4 +42,5 @@ for r in range(rounds):
 for x in vals:
     a = res[x]
     print(f"{knob}={x}: step ms " + " ".join(f"{r[0]:.4f}" for r in a) + f" (median {statistics.median(r[0] for r in a):.4f})  gemm us " +
-          " ".join(f"{r[1]:.1f}" for r in a) + f" (median {statistics.median(r[1] for r in a):.1f})  dots us median {statistics.median(r[2] for r in a):.1f}", flush=True)
+          " ".join(f"{r[1]:.1f}" for r in a) + f" (median {statistics.median(r[1] for r in a):.1f})  dots us " +
+          " ".join(f"{r[2]:.1f}" for r in a) + f" (median {statistics.median(r[2] for r in a):.1f})", flush=True)
