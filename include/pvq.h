@@ -479,7 +479,7 @@ size_t pvq_led_frame(uint32_t n_buckets, uint16_t buckets_per_octave, const floa
  * pitchvis_viewer/src/display_system/update.rs turns an AnalysisState into a spectrogram texture row (update_spectrogram_system,
  * update.rs:929-1087, both SpectrogramModes) and twelve chroma strengths (update_chroma_system, update.rs:1090-1144);
  * pitchvis_serial turns it into an LED frame (pvq_led_frame above).  Stateless: texture management (the ring of rows, its vertical
- * flip, clearing the next line, the scroll offset) stays with the caller. */
+ * flip, clearing the next line, the scroll offset) stays with the caller, or with the overlay stage further down, which keeps it. */
 typedef enum pvq_spectrogram_mode {
     PVQ_SPECTROGRAM_VQT = 0,   /* SpectrogramMode::VQT (update.rs:962-1004): x_vqt_smoothed, brightness against the row's maximum */
     PVQ_SPECTROGRAM_PEAKS = 1  /* SpectrogramMode::Peaks (update.rs:1005-1065): peaks_continuous, a radius of 2 bins each */
@@ -663,7 +663,8 @@ pvq_status pvq_scene_batch_get_state(pvq_scene_batch *b, uint32_t stream_index, 
  * The output is the linear HDR target before bloom and tone mapping, f32 [H][W][4].
  * Left out: bloom and the display transform — Bevy's own passes, not in the reference tree; noisy_color_2d.wgsl, which nothing
  * references.  The spider net, the bass spiral and the debug panels are the backdrop stage further down, which draws the picture the
- * balls go over; the pitch-name text and the other parts that section lists stay left out. */
+ * balls go over, the spectrogram quad and the chroma boxes the overlay stage after it, which draws in front of the balls; the
+ * pitch-name text and the other parts the backdrop section lists stay left out. */
 /* one fragment: rgba linear, params = (calmness, time, pitch_accuracy, pitch_deviation) */
 pvq_status pvq_raster_shade(const float *rgba, const float *params, float u, float v, float *out4);
 /* the time update of one frame: every entry of the list sets time[trunc(center)] = elapsed (keys >= n_bins are ignored, as the
@@ -828,10 +829,9 @@ pvq_status pvq_panels_batch_get_history(pvq_panels_batch *b, uint32_t stream_ind
  * non-finite vertex (after its transform) or a non-finite colour draws nothing.  Pixel boxes are an acceleration only and err
  * outwards.
  *
- * Left out: the pitch-name text (it needs a font); the spectrogram quad at z = 5 and the chroma boxes (UI nodes in pixels, in front
- * of the balls); bloom and tone mapping; MSAA; a ball whose z has fallen below -12.7, which in the reference would go under the bass
- * spiral — here the balls are always on top (at keying z >= -12.625, and the fade lowers it by 0.03 per second while the ball
- * lives). */
+ * Left out: the pitch-name text (it needs a font); bloom and tone mapping; MSAA; a ball whose z has fallen below -12.7, which in the
+ * reference would go under the bass spiral — here the balls are always on top (at keying z >= -12.625, and the fade lowers it by
+ * 0.03 per second while the ball lives).  The spectrogram quad at z = 5 and the chroma boxes are the overlay stage below. */
 enum { PVQ_BACKDROP_NET_SPIRAL = 0, PVQ_BACKDROP_NET_RAYS = 1, PVQ_BACKDROP_BASS = 2 };
 /* the static quads of one layer: quads_out [n][4][2] (v0 .. v3 as x, y; triangles (2, 1, 0), (2, 0, 3)), n_out: their number —
  * 72 octaves - 1, 12, min(72 octaves, 168) - 1.  Either may be NULL.  octaves 1 .. 1024. */
@@ -896,6 +896,72 @@ pvq_status pvq_backdrop_batch_frames_device(pvq_backdrop_batch *b, size_t n_fram
  * row (in place: a pixel is read and written by the same lane).  in->background must be NULL and d_image_inout is needed. */
 pvq_status pvq_backdrop_balls_over_device(pvq_raster_batch *b, size_t n_frames, const pvq_raster_inputs *in, const float *elapsed_s,
                                           float *d_image_inout, float *d_ball_time, void *stream);
+
+/* ---- the overlay: scrolling spectrogram quad and chroma boxes, in front of the balls -------------------------------
+ * The last two parts of the DisplayMode::Debugging picture (pitchvis_viewer/src/display_system/setup.rs:418-541, update.rs:929-1172,
+ * material.rs:42-71, assets/shaders/spectrogram_scroll.wgsl), blended in place over a finished image of the raster section's camera:
+ * layer 8 the quad, layer 9 the boxes.  In the other display modes the caller does not call this stage, and the reference's ring
+ * does not advance either.  Restated from behaviour; f32 without FMA contraction, `/` and floor IEEE f32, so the test model, the
+ * host face and the device carry the same bits (DESIGN.md 6g has the table of assumed semantics).
+ *
+ * The texture.  Rgba8UnormSrgb, n_bins wide, history_rows (h, 200 in the viewer) high, all zeros at start, sampled nearest with
+ * clamp-to-edge.  A frame's row — what pvq_spectrogram_row returns, in either mode — is written to texture row h - 1 - write_index;
+ * then the row of next = (write_index + 1) % h is zeroed, write_index = next, and the material's scroll_offset = next as f32 / h as f32.
+ *
+ * The rule, per pixel (i, j) with (wx, wy) its centre's world position as the raster section places it:
+ *  8. the quad (cx, cy, ex, ey) — centre, extent along x (time) and along y (frequency); the reference's is (-7, 6, 12,
+ *     12 * (h as f32 / n_bins as f32)): Rectangle(12 * h / n_bins, 12) at (-7, 6, 5), turned by -PI / 2 (taken as the exact quarter
+ *     turn) and mirrored, so bins run bottom to top and time leftwards, the newest row at the right edge, the zeroed row at the
+ *     left.  u = (wy - cy) / ey + 0.5, v = 0.5 - (wx - cx) / ex; the pixel is covered when 0 <= u < 1 and 0 <= v < 1 (a NaN covers
+ *     nothing).  t = v + (1 - scroll), v2 = t - floor(t) (the fragment's fract); texture row ty = min(floor(v2 * h), h - 1), column
+ *     tx = min(floor(u * n_bins), n_bins - 1).  The texel's colour bytes decode through srgb_to_linear(byte / 255) (the curve of the
+ *     scene section), its alpha is byte / 255; a texel with alpha byte 0 leaves the pixel as it is, any other is blended with the
+ *     raster section's blend.
+ *  9. the chroma boxes, with s = ui_scale and the pixel's centre at (i + 0.5, j + 0.5) measured from the top left: box pc of twelve
+ *     spans x from (400 + 45 pc) s, 40 s wide, and y from height - 50 s to height - 10 s, each half-open; in the four 4 s corner
+ *     squares the centre must lie within 4 s of the corner circle's centre (<=).  The boxes do not overlap.  Colour
+ *     srgb_to_linear(colors[pc]), alpha the strength pvq_chroma_row gives; a strength that is not finite or is <= 0 draws nothing.
+ *     No edge anti-aliasing.  (Bevy draws UI after tone mapping; here the boxes are blended in the same linear target.)
+ * Left out of the 2-D picture after this stage: what the backdrop section lists. */
+/* the reference's quad for n_bins (3 .. 1024) and history_rows (0: 200, or 2 .. 4096): out4 = (cx, cy, ex, ey) */
+pvq_status pvq_overlay_quad(uint32_t n_bins, uint32_t history_rows, float *out4);
+/* One stream's texture on the host, kept literally as the reference keeps it.  n_bins 3 .. 1024; history_rows 0 (200) or 2 .. 4096. */
+typedef struct pvq_overlay_state pvq_overlay_state;
+pvq_status pvq_overlay_state_create(uint32_t n_bins, uint32_t history_rows, pvq_overlay_state **out);
+void pvq_overlay_state_destroy(pvq_overlay_state *s);
+/* one frame's row, row_rgba [n_bins][4], as update.rs:1066-1087 stores it */
+pvq_status pvq_overlay_state_push(pvq_overlay_state *s, const uint8_t *row_rgba);
+/* the texture as it stands, out [history_rows][n_bins][4], and the write index; either may be NULL */
+pvq_status pvq_overlay_state_texture(const pvq_overlay_state *s, uint8_t *out, uint32_t *write_index);
+/* Both layers over image_inout [height][width][4], in place: the frame whose row was pushed last is the one drawn (scroll =
+ * write_index / h).  state NULL: no quad; quad NULL: the reference's for the state; chroma12 NULL: no boxes (both NULL:
+ * PVQ_ERR_INVALID_ARG); colors 12 RGB triples in [0, 1], NULL: pitchvis_colors::COLORS.  width, height 1 .. 4096; viewport_height
+ * 0: the viewer's; ui_scale 0: 1, else positive and finite; quad finite with positive extents. */
+pvq_status pvq_overlay_frame(const pvq_overlay_state *state, uint32_t width, uint32_t height, float viewport_height, float ui_scale,
+                             const float *quad, const float *chroma12, const float *colors, float *image_inout);
+
+/* The same for MANY streams on the GPU, fed with what pvq_render_batch_rows_device leaves in device memory.  The handle keeps every
+ * stream's last history_rows rows — n_streams * history_rows * n_bins * 4 bytes of device memory (201,600 bytes a stream at 252
+ * bins and 200 rows) — and the number of frames seen. */
+typedef struct pvq_overlay_batch pvq_overlay_batch;
+/* The arguments are checked before any device is touched: bin counts 3 .. 1024 (PVQ_ERR_UNSUPPORTED beyond), the other ranges as
+ * for pvq_overlay_frame.  device_id < 0: a host-only handle whose device calls return PVQ_ERR_NO_DEVICE after their argument checks. */
+pvq_status pvq_overlay_batch_create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, uint32_t history_rows,
+                                    float viewport_height, float ui_scale, const float *quad, const float *colors, uint32_t n_streams,
+                                    uint32_t width, uint32_t height, pvq_overlay_batch **out);
+void pvq_overlay_batch_destroy(pvq_overlay_batch *b);
+/* n_frames frames of every stream, in order, each blended over its row of d_image_inout [n_streams][n_frames][height][width][4]
+ * (16-byte aligned) in place: a pixel is read and written by the same lane, and a pixel neither layer draws on is not touched.
+ * d_rows [n_streams][n_frames][n_bins][4] bytes, 4-byte aligned, as pvq_render_outputs.spectrogram_vqt or .spectrogram_peaks;
+ * d_chroma [n_streams][n_frames][12].  d_rows NULL: no quad, and the rings do not advance; d_chroma NULL: no boxes; both NULL:
+ * PVQ_ERR_INVALID_ARG.  Frame f of a call reads the rows of frames f - (h - 2) .. f: the call's own where they are in the call, the
+ * handle's ring otherwise; after the draw the call's last min(n_frames, h) rows go to the ring.  Asynchronous on `stream`; one
+ * handle's calls are stream-ordered. */
+pvq_status pvq_overlay_batch_frames_device(pvq_overlay_batch *b, size_t n_frames, const uint8_t *d_rows, const float *d_chroma,
+                                           float *d_image_inout, void *stream);
+/* one stream's ring as the reference's texture would stand after the frames seen (synchronises): out [history_rows][n_bins][4],
+ * write_index may be NULL */
+pvq_status pvq_overlay_batch_get_texture(pvq_overlay_batch *b, uint32_t stream_index, uint8_t *out, uint32_t *write_index);
 
 /* The note model the dataset of pitchvis_train exists for (pitchvis_train/train.py:67-99), which the viewer runs per rendered frame
  * through TorchScript on a CUDA device (pitchvis_viewer/src/ml_system.rs:24-69): a window of t_frames consecutive dB frames,

@@ -46,6 +46,9 @@ EXPORTS = [
     "pvq_raster_batch_frames_device", "pvq_raster_batch_get_times",
     "pvq_backdrop_geometry", "pvq_backdrop_panel_transforms", "pvq_backdrop_draw_mesh", "pvq_backdrop_frame", "pvq_backdrop_batch_create",
     "pvq_backdrop_batch_destroy", "pvq_backdrop_batch_frames_device", "pvq_backdrop_balls_over_device",
+    "pvq_overlay_quad", "pvq_overlay_state_create", "pvq_overlay_state_destroy", "pvq_overlay_state_push", "pvq_overlay_state_texture",
+    "pvq_overlay_frame", "pvq_overlay_batch_create", "pvq_overlay_batch_destroy", "pvq_overlay_batch_frames_device",
+    "pvq_overlay_batch_get_texture",
     "pvq_note_model_create", "pvq_note_model_destroy", "pvq_note_model_sizes", "pvq_note_model_infer", "pvq_note_model_rows_device",
     "pvq_note_model_set_workspace_limit",
     "pvq_note_trainer_hyper_default", "pvq_note_trainer_create", "pvq_note_trainer_destroy", "pvq_note_trainer_step", "pvq_note_trainer_steps",
@@ -375,6 +378,18 @@ def load():
     L.pvq_backdrop_batch_destroy.argtypes = [vp]; L.pvq_backdrop_batch_destroy.restype = None
     L.pvq_backdrop_batch_frames_device.argtypes = [vp, C.c_size_t, C.POINTER(CBackdropInputs), vp, vp]; L.pvq_backdrop_batch_frames_device.restype = C.c_int
     L.pvq_backdrop_balls_over_device.argtypes = [vp, C.c_size_t, C.POINTER(CRasterInputs), fp, vp, vp, vp]; L.pvq_backdrop_balls_over_device.restype = C.c_int
+    L.pvq_overlay_quad.argtypes = [C.c_uint32, C.c_uint32, fp]; L.pvq_overlay_quad.restype = C.c_int
+    L.pvq_overlay_state_create.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(vp)]; L.pvq_overlay_state_create.restype = C.c_int
+    L.pvq_overlay_state_destroy.argtypes = [vp]; L.pvq_overlay_state_destroy.restype = None
+    L.pvq_overlay_state_push.argtypes = [vp, bp]; L.pvq_overlay_state_push.restype = C.c_int
+    L.pvq_overlay_state_texture.argtypes = [vp, bp, up]; L.pvq_overlay_state_texture.restype = C.c_int
+    L.pvq_overlay_frame.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float, fp, fp, fp, fp]; L.pvq_overlay_frame.restype = C.c_int
+    L.pvq_overlay_batch_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, fp, fp, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, C.POINTER(vp)]
+    L.pvq_overlay_batch_create.restype = C.c_int
+    L.pvq_overlay_batch_destroy.argtypes = [vp]; L.pvq_overlay_batch_destroy.restype = None
+    L.pvq_overlay_batch_frames_device.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]; L.pvq_overlay_batch_frames_device.restype = C.c_int
+    L.pvq_overlay_batch_get_texture.argtypes = [vp, C.c_uint32, bp, up]; L.pvq_overlay_batch_get_texture.restype = C.c_int
     L.pvq_note_model_create.argtypes = [C.c_int, C.POINTER(CNoteModelParams), C.POINTER(CNoteModelWeights), C.POINTER(vp)]
     L.pvq_note_model_create.restype = C.c_int
     L.pvq_note_model_destroy.argtypes = [vp]

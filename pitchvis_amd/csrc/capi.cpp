@@ -19,6 +19,8 @@
 #include "multi_host.hpp"
 #include "note_model.hpp"
 #include "note_trainer.hpp"
+#include "overlay_batch.hpp"
+#include "overlay_host.hpp"
 #include "panels_batch.hpp"
 #include "panels_host.hpp"
 #include "raster_batch.hpp"
@@ -58,6 +60,12 @@ struct pvq_raster_batch {
 };
 struct pvq_backdrop_batch {
     std::unique_ptr<pvq::BackdropBatch> impl;
+};
+struct pvq_overlay_state {
+    pvq::OverlayState impl;
+};
+struct pvq_overlay_batch {
+    std::unique_ptr<pvq::OverlayBatch> impl;
 };
 struct pvq_calmness_graph {
     pvq::CalmnessGraph impl;
@@ -1523,6 +1531,122 @@ pvq_status pvq_backdrop_balls_over_device(pvq_raster_batch* b, size_t n_frames, 
         if (!b) return null_handle();
         const pvq_raster_inputs no_in{};
         return b->impl->frames_device(n_frames, in ? *in : no_in, elapsed_s, d_image_inout, d_ball_time, static_cast<hipStream_t>(stream), true);
+    } catch (...) { return translate_exception(); }
+}
+
+// The spectrogram quad and the chroma boxes in front of the balls (setup.rs:418-541, update.rs:929-1172, spectrogram_scroll.wgsl):
+// one stream on the host (overlay_host.hpp) and many streams on the device (overlay_batch.hpp)
+namespace {
+bool overlay_bins_ok(const char* who, uint32_t n_bins) {
+    if (n_bins >= pvq::overlay::MIN_BINS && n_bins <= pvq::overlay::MAX_BINS) return true;
+    pvq::set_last_error(std::string(who) + ": n_bins is 3 .. 1024");
+    return false;
+}
+}  // namespace
+pvq_status pvq_overlay_quad(uint32_t n_bins, uint32_t history_rows, float* out4) {
+    try {
+        std::string err;
+        if (!out4) {
+            pvq::set_last_error("overlay quad: out4 is needed");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        if (!overlay_bins_ok("overlay quad", n_bins)) return PVQ_ERR_INVALID_ARG;
+        if (!pvq::overlay_args_ok("overlay quad", history_rows, 0.0f, nullptr, err)) {
+            pvq::set_last_error(err);
+            return PVQ_ERR_INVALID_ARG;
+        }
+        pvq::overlay::reference_quad(n_bins, history_rows == 0 ? pvq::overlay::HISTORY_ROWS : history_rows, out4);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_overlay_state_create(uint32_t n_bins, uint32_t history_rows, pvq_overlay_state** out) {
+    try {
+        if (!out) return null_handle();
+        *out = nullptr;
+        std::string err;
+        if (!overlay_bins_ok("overlay state", n_bins)) return PVQ_ERR_INVALID_ARG;
+        if (!pvq::overlay_args_ok("overlay state", history_rows, 0.0f, nullptr, err)) {
+            pvq::set_last_error(err);
+            return PVQ_ERR_INVALID_ARG;
+        }
+        *out = new pvq_overlay_state{pvq::OverlayState(n_bins, history_rows == 0 ? pvq::overlay::HISTORY_ROWS : history_rows)};
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+void pvq_overlay_state_destroy(pvq_overlay_state* s) {
+    try {
+        delete s;
+    } catch (...) { (void)translate_exception(); }
+}
+pvq_status pvq_overlay_state_push(pvq_overlay_state* s, const uint8_t* row_rgba) {
+    try {
+        if (!s) return null_handle();
+        if (!row_rgba) {
+            pvq::set_last_error("overlay state: row_rgba is needed");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        s->impl.push(row_rgba);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_overlay_state_texture(const pvq_overlay_state* s, uint8_t* out, uint32_t* write_index) {
+    try {
+        if (!s) return null_handle();
+        if (out) std::memcpy(out, s->impl.texture(), static_cast<size_t>(s->impl.history_rows()) * s->impl.n_bins() * 4);
+        if (write_index) *write_index = s->impl.write_index();
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_overlay_frame(const pvq_overlay_state* state, uint32_t width, uint32_t height, float viewport_height, float ui_scale,
+                             const float* quad, const float* chroma12, const float* colors, float* image_inout) {
+    try {
+        if (!image_inout || (!state && !chroma12)) {
+            pvq::set_last_error("overlay frame: image_inout is needed, and a state or chroma12");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        std::string err;
+        if (!pvq::stage_image_ok("overlay frame", width, height, viewport_height, err) ||
+            !pvq::overlay_args_ok("overlay frame", 0, ui_scale, quad, err)) {
+            pvq::set_last_error(err);
+            return PVQ_ERR_INVALID_ARG;
+        }
+        pvq::overlay::Tables tables;
+        pvq::overlay_tables(colors, tables);
+        pvq::overlay_frame(state ? &state->impl : nullptr, width, height, viewport_height == 0.0f ? pvq::raster::VIEWPORT_HEIGHT : viewport_height,
+                           ui_scale == 0.0f ? 1.0f : ui_scale, quad, chroma12, tables, image_inout);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_overlay_batch_create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, uint32_t history_rows, float viewport_height,
+                                    float ui_scale, const float* quad, const float* colors, uint32_t n_streams, uint32_t width, uint32_t height,
+                                    pvq_overlay_batch** out) {
+    try {
+        if (!out) return null_handle();
+        *out = nullptr;
+        std::unique_ptr<pvq::OverlayBatch> impl;
+        const pvq_status st = pvq::OverlayBatch::create(device_id, octaves, buckets_per_octave, history_rows, viewport_height, ui_scale, quad, colors,
+                                                        n_streams, width, height, impl);
+        if (st != PVQ_OK) return st;
+        *out = new pvq_overlay_batch{std::move(impl)};
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+void pvq_overlay_batch_destroy(pvq_overlay_batch* b) {
+    try {
+        delete b;
+    } catch (...) { (void)translate_exception(); }
+}
+pvq_status pvq_overlay_batch_frames_device(pvq_overlay_batch* b, size_t n_frames, const uint8_t* d_rows, const float* d_chroma,
+                                           float* d_image_inout, void* stream) {
+    try {
+        if (!b) return null_handle();
+        return b->impl->frames_device(n_frames, d_rows, d_chroma, d_image_inout, static_cast<hipStream_t>(stream));
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_overlay_batch_get_texture(pvq_overlay_batch* b, uint32_t stream_index, uint8_t* out, uint32_t* write_index) {
+    try {
+        if (!b) return null_handle();
+        return b->impl->get_texture(stream_index, out, write_index);
     } catch (...) { return translate_exception(); }
 }
 

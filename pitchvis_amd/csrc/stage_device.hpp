@@ -1,5 +1,5 @@
-// stage_device.hpp — device side of what the batch stages' kernels share (raster_batch.hip, backdrop_batch.hip, scene_batch.hip): how
-// a row of a piece of a call maps to the call's rows, and a lane's pixel in the 16 x 16 tile kernels.
+// stage_device.hpp — device side of what the batch stages' kernels share (raster_batch.hip, backdrop_batch.hip, scene_batch.hip,
+// overlay_batch.hip): how a row of a piece of a call maps to the call's rows, and a lane's pixel in the 16 x 16 tile kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,6 +35,21 @@ __device__ __forceinline__ TilePixel tile_pixel(uint32_t wave, uint32_t lane, ui
     p.bx0 = tx * TILE + (wave & 1u) * 8u;
     p.by0 = ty * TILE + (wave >> 1) * 8u;
     const uint32_t i = p.bx0 + (lane & 7u), j = p.by0 + (lane >> 3);
+    p.inside = i < W && j < H;
+    raster::pixel_world(i, j, W, H, vh, p.wx, p.wy);
+    p.pixel = static_cast<size_t>(j) * W + i;
+    return p;
+}
+// The same for a kernel launched over a list of tiles (overlay_batch.hip): `tile` is the workgroup's row-major tile number.
+__device__ __forceinline__ TilePixel tile_pixel_of(uint32_t tile, uint32_t wave, uint32_t lane, uint32_t W, uint32_t H, float vh, uint32_t& i,
+                                                   uint32_t& j) {
+#pragma clang fp contract(off)
+    TilePixel p;
+    const uint32_t tiles_x = (W + TILE - 1) / TILE;
+    p.bx0 = (tile % tiles_x) * TILE + (wave & 1u) * 8u;
+    p.by0 = (tile / tiles_x) * TILE + (wave >> 1) * 8u;
+    i = p.bx0 + (lane & 7u);
+    j = p.by0 + (lane >> 3);
     p.inside = i < W && j < H;
     raster::pixel_world(i, j, W, H, vh, p.wx, p.wy);
     p.pixel = static_cast<size_t>(j) * W + i;
