@@ -126,3 +126,41 @@ def device_rows(n, bpo, ns, nf, seed, max_peaks, capacity, peak_counts=None, lit
             a["bass_rgba"][s, f] = rng.random(4, dtype=f32)
             rows[-1].append(m)
     return a, rows
+
+
+# ---- the row-stride test: 61 distinct rows of 3 bins (two line quads) and one disc slot -------------------------------------------
+STRIDE_ROWS = 61
+# (line triangles, discs) of row i, by i % 11: 11 shares no factor with the steps a workgroup takes through the 61 rows
+STRIDE_KINDS = ((4, 0), (1, 0), (4, 1), (0, 0), (2, 0), (4, 0), (0, 0), (1, 1), (2, 1), (0, 1), (4, 1))
+
+
+def stride_rows(W, H, vh, seed):
+    """(arrays [61][...] of line_pos, line_rgba, disc_pos, disc_rgba, peak_count; per row the host panels dict): translucent
+    triangles a pixel or two wide around pixel centres; a row's unused line triangles are degenerate (zeros; an odd count ends in a
+    quad whose vertex 3 repeats vertex 0), its unused disc slot is zeros"""
+    m, n = STRIDE_ROWS, 3
+    rng = np.random.default_rng(seed)
+    pitch = vh / H
+    a = {"line_pos": np.zeros((m, n - 1, 4, 3), f32), "line_rgba": np.zeros((m, n - 1, 4, 4), f32), "disc_pos": np.zeros((m, 1, 13, 3), f32),
+         "disc_rgba": np.zeros((m, 1, 13, 4), f32), "peak_count": np.zeros(m, np.int32)}
+    rows = []
+    for r in range(m):
+        tris, discs = STRIDE_KINDS[r % 11]
+        quads = (tris + 1) // 2
+        for q in range(quads):
+            c = pixel_centre(W, H, vh, int(rng.integers(0, W)), int(rng.integers(0, H)))
+            a["line_pos"][r, q, :, :2] = np.asarray(c) + np.asarray([[0.9, -0.8], [0.1, 1.1], [-1.0, -0.7], [0.2, -1.2]]) * pitch * rng.uniform(0.8, 1.6)
+            a["line_rgba"][r, q] = np.append(rng.uniform(0.1, 1.0, 3), 0.5)
+        if tris % 2:
+            a["line_pos"][r, quads - 1, 3] = a["line_pos"][r, quads - 1, 0]
+        if discs:
+            c = pixel_centre(W, H, vh, int(rng.integers(0, W)), int(rng.integers(0, H)))
+            ang = 2.0 * np.pi * np.arange(12) / 12.0
+            a["disc_pos"][r, 0, 0, :2] = c
+            a["disc_pos"][r, 0, 1:, :2] = np.asarray(c) + pitch * rng.uniform(0.7, 1.4) * np.stack([np.cos(ang), np.sin(ang)], 1)
+            a["disc_rgba"][r, 0] = np.append(rng.uniform(0.1, 1.0, 3), 0.9)
+        a["peak_count"][r] = discs
+        rows.append({"line_pos": a["line_pos"][r].reshape(-1, 3), "line_rgba": a["line_rgba"][r].reshape(-1, 4),
+                     "disc_pos": a["disc_pos"][r, :discs], "disc_rgba": a["disc_rgba"][r, :discs]})
+    a["line_pos"], a["line_rgba"] = a["line_pos"].reshape(m, 4 * (n - 1), 3), a["line_rgba"].reshape(m, 4 * (n - 1), 4)
+    return a, rows

@@ -74,3 +74,19 @@ def host_chain(n_bins, h, rows_s, chroma_s, images_s, before=(), quad_=None, **k
             st.push(rows_s[f])
         out.append(P.overlay_frame(img, st if rows_s is not None else None, None if chroma_s is None else chroma_s[f], quad=quad_, **kw))
     return np.asarray(out, f32), st
+
+
+# ---- the row-stride test: 61 distinct streams of a few frames --------------------------------------------------------------------
+STRIDE_STREAMS = 61
+STRIDE_EMPTY = (3, 6)       # stream pattern p draws nothing where p % 11 is one of these: rows all zero, no box lit
+
+
+def stride_streams(n_frames, n_bins, W, H, seed):
+    """(rows, chroma, images) of 61 distinct streams; the crafted empty ones hold zero rows and zero strengths"""
+    m = STRIDE_STREAMS
+    r, c, img = rows(m, n_frames, n_bins, seed), chroma(m, n_frames, seed + 1), images(m, n_frames, W, H, seed + 2)
+    r[:, :, :, 3] = np.maximum(r[:, :, :, 3], 1)               # few bins, few pixels: every texel of an ordinary row draws
+    for p in range(m):
+        if p % 11 in STRIDE_EMPTY:
+            r[p], c[p] = 0, 0.0
+    return r, c, img

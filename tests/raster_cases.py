@@ -114,3 +114,27 @@ def pack_peaks(lists, max_peaks, counts=None):
             center[s, f, :len(c)] = c
             count[s, f] = len(lists[s][f]) if counts is None else counts[s][f]
     return center, count
+
+
+# ---- the row-stride test: 61 distinct streams of a few frames, 3 bins ------------------------------------------------------------
+STRIDE_STREAMS = 61
+STRIDE_BALLS = (3, 1, 3, 0, 2)          # drawable balls of stream pattern p, by p % 5: none after three where the patterns wrap
+
+
+def stride_rows(nf, W, H, seed, vh=2.0 * HALF_VIEW, n=3):
+    """[61][nf] rows of n balls whose drawable ones sit within a fifth of a pixel of a pixel centre of the W x H image and are 0.6
+    to 2.5 pixels wide, so that on an image of a few pixels a drawable ball shows"""
+    pitch = vh / H
+    out = []
+    for p in range(STRIDE_STREAMS):
+        frames = []
+        for f in range(nf):
+            rng = np.random.default_rng(seed + 10 * p + f)
+            r = row(n, seed + 10 * p + f, drawable=STRIDE_BALLS[p % 5])
+            i, j = rng.integers(0, W, n), rng.integers(0, H, n)
+            r["ball_xyzs"][:, 0] = (i + 0.5 - 0.5 * W) * pitch + rng.uniform(-0.2, 0.2, n) * pitch
+            r["ball_xyzs"][:, 1] = (0.5 * H - (j + 0.5)) * pitch + rng.uniform(-0.2, 0.2, n) * pitch
+            r["ball_xyzs"][:, 3] = rng.uniform(0.6, 2.5, n) * pitch / 20.0     # the rectangle's side is 20 scale
+            frames.append(r)
+        out.append(frames)
+    return out

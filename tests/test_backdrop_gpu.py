@@ -266,3 +266,53 @@ def test_chain():
             same(img[s, f], host, ("chain", s, f))
     assert not np.array_equal(img, backdrop) and not np.array_equal(img, download(plain["image"]))
     assert g["bass_lit"].max() > 0 and len(np.unique(backdrop.reshape(-1, 4), axis=0)) > 20
+
+
+def test_row_stride_past_both_grid_caps():
+    """backdrop_lists (8192 workgroups) and backdrop_tiles (gridDim.y 65 535) over 2 streams x 32 799 frames = 65 598 rows of 3 bins on
+    a 3 x 2 image in Galaxy mode (no net: a row's own list alone), in one piece.  Row r is row r % 61 of 61 distinct ones, which the
+    host face pins.  A list workgroup's next row, r + 8192, is row + 18's of the 61 and a tile workgroup's, r + 65 535, row + 21's:
+    another list length (none after four triangles and a disc), so s_base and the wave counts of one row meet the next.  Rows
+    65 535 .. 65 597 exist only if the tile kernel strides by the very cap the host clamps to."""
+    import torch
+    geom, W, H, vh, m = (1, 3), 3, 2, 2.0, BC.STRIDE_ROWS
+    ns, nf = 2, 32799
+    total = ns * nf
+    assert total == 65535 + 63
+    cap = 2 * 2 + 12 * 1                                       # mirrors backdrop_batch.hip: two line quads and one disc slot
+    per_row = cap * 80 + 4
+    assert per_row * total <= 256 << 20                        # one piece: the strides are taken, not cut away
+    a, rows = BC.stride_rows(W, H, vh, 9000)
+    host = np.asarray([P.backdrop_frame(*geom, W, H, viewport_height=vh, visuals_mode=3, panels=r) for r in rows], f32)
+    clear = P.backdrop_frame(*geom, W, H, viewport_height=vh, visuals_mode=3)
+    # no stride test passes by drawing nothing: a row is empty only where it has no triangle, a quarter of the rows at most
+    empty = [i for i in range(m) if not (bits(host[i]) != bits(clear)).any()]
+    assert empty == [i for i in range(m) if BC.STRIDE_KINDS[i % 11] == (0, 0)] and 4 * len(empty) <= m
+    for grid in (8192, 65535):
+        assert grid % m != 0 and grid < total
+        for i in range(m):
+            j = (i + grid) % m
+            assert (bits(host[i]) != bits(host[j])).any() and BC.STRIDE_KINDS[i % 11] != BC.STRIDE_KINDS[j % 11], (grid, i, j)
+            assert (a["line_pos"][i] != a["line_pos"][j]).any() or (a["disc_pos"][i] != a["disc_pos"][j]).any(), (grid, i, j)
+    follows = {(BC.STRIDE_KINDS[i % 11], BC.STRIDE_KINDS[(i + 8192) % m % 11]) for i in range(m)}
+    assert ((4, 1), (0, 0)) in follows and any(x == (0, 0) and sum(y) for x, y in follows), follows
+    names = ("line_pos", "line_rgba", "disc_pos", "disc_rgba", "peak_count")
+    small_in = {k: to_device(a[k]) for k in names}
+    rng = P.VqtRange(55.0, *geom)
+    small = P.BackdropBatch(rng, 1, W, H, visuals_mode=3, viewport_height=vh).frames(m, **small_in)
+    got = download(small)[0]
+    print(f"{m} distinct rows: {got.size} channels, {int((bits(got) != bits(host)).sum())} differ from the host face")
+    same(got, host, "61 distinct rows")
+    assert not (bits(got) == GUARD).any()
+    idx = to_device(np.arange(total, dtype=np.int64) % m)
+    buf = torch.full((total * H * W * 4 + 8,), GUARD, dtype=torch.int32, device="cuda")
+    b = P.BackdropBatch(rng, ns, W, H, visuals_mode=3, viewport_height=vh)
+    b.frames(nf, **{k: v[idx].contiguous() for k, v in small_in.items()}, image=buf[4:-4].view(torch.float32))
+    torch.cuda.synchronize()
+    big = buf[4:-4].view(total, -1)
+    differing = int((big != small.view(torch.int32).view(m, -1)[idx]).sum())
+    unwritten = int((big[8192:] == GUARD).sum())                                    # of rows 8192 .. and 65 535 ..
+    print(f"{total} rows over 8192 list workgroups and 65535 tile rows: {differing} 32-bit words differ from the {m}-row call; "
+          f"{unwritten} words of rows 8192 .. are still the fill value")
+    assert differing == 0 and unwritten == 0
+    assert bool((buf[:4] == GUARD).all()) and bool((buf[-4:] == GUARD).all())

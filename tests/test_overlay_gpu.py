@@ -301,3 +301,81 @@ def test_chain():
             same(img[s], host, ("chain", mode, s))
         assert not np.array_equal(img, under)
     assert r["spectrogram_peaks"][..., 3].any() and r["spectrogram_vqt"][..., 3].any()
+
+
+def test_row_stride_past_the_draw_grid_cap():
+    """overlay_draw (gridDim.y 65 535) over 32 769 streams x 2 frames = 65 538 rows of 3 bins, a ring of 3 rows, quad and boxes on a
+    17 x 5 image (two tile columns; ui_scale 0.02 puts nine boxes on pixel centres).  Stream s is pattern s % 61 of 61 distinct
+    streams, which the host face and the model pin.  Rows 0, 1, 2 have a second trip, to rows 65 535 .. 65 537: the other frame of
+    pattern 10 or 11, so s, f, the ring slot and r - age all change inside the loop; those rows exist only if the kernel strides by
+    the very cap the host clamps to."""
+    import torch
+    n, h, nf, W, H, scale, cap, m = 3, 3, 2, 17, 5, 0.02, 65535, OC.STRIDE_STREAMS
+    ns = cap // nf + 2
+    total = ns * nf
+    assert total == 65538 and cap % m != 0 and cap % nf == 1
+    rows, chroma, imgs = OC.stride_streams(nf, n, W, H, 5000)
+    host, states, info = references(n, h, rows, chroma, imgs, ui_scale=scale)
+    drawn_enough("61 distinct streams", info, host, imgs, n, h)
+    assert sum(d["boxed"] for d in info) > m * nf                                   # chroma is present and shows
+    # no stride test passes by drawing nothing: a row is empty only where it was crafted so, a quarter of the rows at most
+    empty = [(p, f) for p in range(m) for f in range(nf) if not (bits(host[p, f]) != bits(imgs[p, f])).any()]
+    assert empty == [(p, f) for p in range(m) for f in range(nf) if p % 11 in OC.STRIDE_EMPTY] and 4 * len(empty) <= m * nf
+    of = lambda r: ((r // nf) % m, r % nf)
+    for r in range(total - cap):                                                    # a workgroup's second row fits nothing of its first
+        (p, f), (q, g) = of(r), of(r + cap)
+        assert p != q and f != g and (p, f) not in empty and (q, g) not in empty
+        assert (bits(host[p, f]) != bits(host[q, g])).any() and (rows[p, f] != rows[q, g]).any() and (bits(chroma[p, f]) != bits(chroma[q, g])).any()
+    small = draw(batch(n, m, W, H, h, ui_scale=scale), imgs, rows, chroma)
+    print(f"{m} distinct streams: {small.size} channels, {int((bits(small) != bits(host)).sum())} differ from the host face")
+    same(small, host, "61 distinct streams")
+    idx = to_device(np.arange(ns, dtype=np.int64) % m)
+    buf = torch.full((total * H * W * 4 + 8,), GUARD, dtype=torch.int32, device="cuda")
+    buf[4:-4] = to_device(bits(imgs).view(np.int32).reshape(m, -1))[idx].reshape(-1)
+    b = batch(n, ns, W, H, h, ui_scale=scale)
+    b.frames(nf, buf[4:-4].view(torch.float32), to_device(rows)[idx].contiguous(), to_device(chroma)[idx].contiguous())
+    torch.cuda.synchronize()
+    big = buf[4:-4].view(ns, -1)
+    differing = int((big != to_device(bits(small).view(np.int32).reshape(m, -1))[idx]).sum())
+    print(f"{total} rows over {cap} grid rows: {differing} 32-bit words differ from the {m}-stream call")
+    assert differing == 0
+    assert bool((buf[:4] == GUARD).all()) and bool((buf[-4:] == GUARD).all())
+    last = buf[4:-4].view(total, -1)[cap:].cpu().numpy().view(np.uint32)            # rows 65 535 .. 65 537 were drawn on
+    for k in range(total - cap):
+        p, f = of(cap + k)
+        assert (last[k] != bits(imgs[p, f]).ravel()).any(), k
+    for s in (0, ns - 1):
+        tex, w = b.texture(s)
+        want, ww = states[s % m].texture()
+        assert np.array_equal(tex, want) and w == ww == nf % h, s
+
+
+def test_keep_stride_past_two_million_texels():
+    """overlay_keep: 11 streams x the last 200 of 203 frames x 1024 bins = 2 252 800 texels over 8192 x 256 = 2 097 152 lanes, on a
+    1 x 1 image; the second trip's texels are ring rows 48 .. 199 of the last stream.  Every stream's texture is the host state's,
+    and a second call draws from that ring what the host draws"""
+    n, h, ns, nf, more = 1024, 200, 11, 203, 3
+    assert ns * min(nf, h) * n > 8192 * 256 > (ns - 1) * min(nf, h) * n
+    rows, imgs = OC.rows(ns, nf + more, n, 5200), OC.images(ns, nf + more, 1, 1, 5201)
+    rows[..., 3] = np.maximum(rows[..., 3], 1)
+    b = batch(n, ns, 1, 1, h)
+    first = draw(b, imgs[:, :nf], rows[:, :nf])
+    ends = (0, ns - 1)
+    host = {s: OC.host_chain(n, h, rows[s], None, imgs[s], quad_=OC.full_quad(1, 1, VH), viewport_height=VH) for s in ends}
+    kept = {}
+    for s in range(ns):
+        st = P.OverlayState(n, h)
+        for r in rows[s, :nf]:
+            st.push(r)
+        tex, w = b.texture(s)
+        want, ww = st.texture()
+        kept[s] = int((tex != want).sum())
+        assert w == ww == nf % h and want.any(axis=(1, 2)).sum() == h - 1, s
+    print(f"{ns * h * n} texels over {8192 * 256} lanes: differing texture bytes per stream: {kept}")
+    assert not any(kept.values()), kept
+    second = draw(b, imgs[:, nf:], rows[:, nf:])                                    # ages 3 .. 198 of these frames come from the ring
+    for s in ends:
+        got = np.concatenate([first[s], second[s]])
+        print(f"stream {s}: {got.size} channels, {int((bits(got) != bits(host[s][0])).sum())} differ from the host face")
+        same(got, host[s][0], ("images", s))
+        assert np.array_equal(b.texture(s)[0], host[s][1].texture()[0]), s

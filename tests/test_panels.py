@@ -254,7 +254,83 @@ def test_host_matches_model(min_freq, octaves, bpo):
     assert np.isnan(zero["line_rgba"][:, 3]).all() and np.isfinite(zero["line_pos"]).all() and zero["disc_pos"].shape == (0, 13, 3)
 
 
-@pytest.mark.parametrize("capacity", [2, 5, 64, 65])
+def _line_differs(n, bpo, x, y):
+    """differing 32-bit words of line_rgba between two spectra on the host face"""
+    return M.same_bits(P.spectrum_mesh(n, bpo, x)["line_rgba"], P.spectrum_mesh(n, bpo, y)["line_rgba"])
+
+
+@pytest.mark.parametrize("min_freq,octaves,bpo", PC.EDGE_GEOMETRIES)
+def test_arg_max_edges_host_matches_model(min_freq, octaves, bpo):
+    """util::arg_max on rows it was not written for (tests/panels_cases.edge_spectra): both signs of zero as the maximum, NaN, rows
+    that never exceed f32::MIN, +inf, the maximum on a 64-chunk edge and in the last bin.  max_size is x[arg_max]; its value and
+    its sign show in every alpha of the row."""
+    n = octaves * bpo
+    spectra = PC.edge_spectra(n, 700 + n)
+    assert len(spectra) == 16
+    worst = {}
+    for name, (x, at) in spectra.items():
+        assert M.arg_max(x) == (0 if at is None else at), name                       # the model's fold finds what the case was built for
+        if at is None:
+            assert not (x > M.F32_MIN).any()
+        elif name != "plus_inf":
+            assert x[at] == np.nanmax(x) and (name.startswith("zeros") or int(np.sum(x == x[at])) == 1), name
+        assert (x < 0).any() or name == "all_nan", name
+        got, want = P.spectrum_mesh(n, bpo, x), M.spectrum_mesh(n, bpo, x)
+        worst[name] = sum(M.same_bits(got[k], want[k]) for k in got)
+        alpha = got["line_rgba"].reshape(n - 1, 4, 4)[:, 0, 3]
+        ms = x[0 if at is None else at]
+        with np.errstate(all="ignore"):
+            expect = (f32(1.0) - np.sqrt(f32(0.5) - x[:-1] / ms / f32(2.0))).astype(f32)
+        assert M.same_bits(alpha, expect) == 0, name                                 # the alphas of THIS max_size, sign included
+    print(f"{n} bins: host vs model, differing 32-bit words per crafted spectrum: {worst}")
+    assert not any(worst.values()), worst
+    for name in ("zeros_first_and_last", "zeros_one_lane", "zeros_two_lanes"):       # -0 first and +0 first are told apart
+        a, b = spectra[name][0], spectra[name + "_swapped"][0]
+        assert np.array_equal(a, b) and np.signbit(a[spectra[name][1]]) and not np.signbit(b[spectra[name][1]])
+        d = _line_differs(n, bpo, a, b)
+        assert d >= 4 * (n - 3), (name, d)                                            # every negative bin: +inf against -inf under the root
+        al = P.spectrum_mesh(n, bpo, a)["line_rgba"][:, 3]
+        assert np.isnan(al).all(), name                                               # x / -0 = +inf: sqrt(0.5 - inf) is NaN
+        assert np.isneginf(P.spectrum_mesh(n, bpo, b)["line_rgba"][:, 3]).sum() >= 4 * (n - 3), name
+    nan_row = P.spectrum_mesh(n, bpo, spectra["all_nan"][0])
+    assert np.isnan(nan_row["line_rgba"][:, 3]).all()
+    flt = P.spectrum_mesh(n, bpo, spectra["all_minus_flt_max"][0])["line_rgba"][:, 3]
+    assert np.all(flt == 1.0)                                                         # max_size = x[0] = every entry
+    inf_row = P.spectrum_mesh(n, bpo, spectra["plus_inf"][0])["line_rgba"].reshape(n - 1, 4, 4)[:, 0, 3]
+    assert np.isnan(inf_row[n // 3]) and np.all(np.delete(inf_row, n // 3) == f32(1.0) - np.sqrt(f32(0.5)))
+
+
+@pytest.mark.parametrize("max_peaks", sorted(PC.DISC_COUNTS))
+def test_long_disc_lists_host_matches_model(max_peaks):
+    """lists of 63, 64, 65, 128 and 129 discs (tests/test_panels_gpu.py takes them through the device's 64-chunk loop)"""
+    counts = PC.DISC_COUNTS[max_peaks]
+    assert {63, 64}.issubset(counts) and max(counts) == max_peaks and 0 in counts and all(c <= max_peaks for c in counts)
+    case = PC.list_case(55.0, 5, 39, max_peaks, counts, 800 + max_peaks)
+    got, want = PC.host_rows(P, case), PC.model_rows(M, case)
+    diff = {k: M.same_bits(got[k], want[k]) for k in got}
+    print(f"max_peaks {max_peaks}, counts {counts}: host vs model, differing 32-bit words: {diff}")
+    assert not any(diff.values()), diff
+    assert np.isnan(case["center"][np.arange(max_peaks)[None, :] >= case["count"][:, None]]).all()
+
+
+def test_stride_rows_host_matches_model():
+    """the 61 rows of the device's row-stride test: the model's bits, and the orders the test is there for"""
+    case, kinds = PC.stride_case()
+    m = PC.STRIDE_ROWS
+    got, want = PC.host_rows(P, case), PC.model_rows(M, case)
+    diff = {k: M.same_bits(got[k], want[k]) for k in got}
+    print(f"{m} stride rows: host vs model, differing 32-bit words: {diff}")
+    assert not any(diff.values()), diff
+    empty = [r for r in range(m) if not got["disc_pos"][r].view(np.uint32).any() and not got["disc_rgba"][r].view(np.uint32).any()]
+    assert empty == [r for r in range(m) if kinds[r][0] == "empty"] and 4 * len(empty) <= m
+    differ = lambda i, j: all(M.same_bits(got[k][i], got[k][j]) for k in got) and all(
+        not np.array_equal(case[k][i], case[k][j], equal_nan=True) for k in ("x", "calmness", "center", "size"))     # (two counts may both be 65)
+    pairs = PC.stride_follows(m, 8192, differ)
+    orders = {(kinds[i][0], kinds[j][0]) for i, j in pairs} | {(kinds[i][1], kinds[j][1]) for i, j in pairs}
+    assert {("full", "empty"), ("crossing", "short"), ("ordinary", "nan")} <= orders, orders
+
+
+@pytest.mark.parametrize("capacity", [2, 5, 64, 65, 129, 1024])
 def test_graph_handle_matches_model(capacity):
     rng = np.random.default_rng(capacity)
     for k in (1, capacity - 1, capacity, capacity + 1, 2 * capacity + 3):

@@ -288,3 +288,65 @@ def test_from_a_scene_batch():
     lit = (img != M.clear_color()).any(-1).mean()
     print(f"scene -> raster: {lit:.2%} of the pixels are covered")
     assert lit > 0.05
+
+
+def _stride_pairs(total, cap, nf, m):
+    """the rows a workgroup that starts on row r < total - cap takes next, as (pattern, frame) pairs: ((p, f), (p', f'))"""
+    of = lambda r: ((r // nf) % m, r % nf)
+    return sorted({(of(r), of(r + cap)) for r in range(total - cap)})
+
+
+def test_row_stride_past_both_grid_caps():
+    """raster_marks and raster_lists (8192 workgroups) and raster_tiles (gridDim.y 65 535) over 32 769 streams x 2 frames = 65 538
+    rows of 3 bins on a 3 x 2 image, in one piece.  Stream s is pattern s % 61 of 61 distinct streams, which the host face and the
+    model pin.  A list workgroup's next row, r + 8192, is pattern + 9's (another count of drawable balls: s_key and s_n as a row of
+    three left them meet a row of none); a tile workgroup's, r + 65 535, is the other frame of pattern + 10 or + 11.  Rows
+    65 535 .. 65 537 exist only if the tile kernel strides by the very cap the host clamps to."""
+    import torch
+    n, nf, W, H, m = 3, 2, 3, 2, RC.STRIDE_STREAMS
+    ns = 65535 // nf + 2
+    total = ns * nf
+    assert total == 65538
+    per_row = n * (64 + 4) + (1 + 1) * 4                        # mirrors raster_batch.hip, as test_workspace_pieces does
+    assert per_row == 212 and per_row * total <= 256 << 20      # one piece: the strides are taken, not cut away
+    rows, lists, el = RC.stride_rows(nf, W, H, 7000), RC.peak_lists(n, m, nf, 7001), clocks(nf)
+    rng = P.VqtRange(55.0, 1, 3)
+    img, bt = hold(f"{m} distinct streams", P.RasterBatch(rng, m, W, H), rows, lists, el, W, H)
+    # no stride test passes by drawing nothing: a row is empty only where it has no drawable ball, a quarter of the rows at most
+    clear = np.broadcast_to(np.asarray(M.clear_color(), f32), (H, W, 4))
+    empty = [(p, f) for p in range(m) for f in range(nf) if not (bits(img[p, f]) != bits(clear)).any()]
+    assert empty == [(p, f) for p in range(m) for f in range(nf) if RC.STRIDE_BALLS[p % 5] == 0] and 4 * len(empty) <= m * nf
+    packed = RC.stack(rows)
+    center, count = RC.pack_peaks(lists, MAX_PEAKS)
+    for cap in (8192, 65535):
+        assert cap % m != 0 and cap < total
+        for (p, f), (q, g) in _stride_pairs(total, cap, nf, m):
+            assert (bits(img[p, f]) != bits(img[q, g])).any(), (cap, p, f, q, g)
+            assert all((packed[k][p, f] != packed[k][q, g]).any() for k in ("ball_xyzs", "ball_rgba", "ball_params")), (cap, p, f, q, g)
+    # (three bins have eight bin masks and three clock values: the times of two rows can agree; those of most pairs do not, and a
+    # frame without peaks follows one with peaks)
+    marks = _stride_pairs(total, 8192, nf, m)
+    assert 2 * sum(bool((bits(bt[p, f]) != bits(bt[q, g])).any()) for (p, f), (q, g) in marks) >= len(marks)
+    assert any(lists[p][f] and not lists[q][g] for (p, f), (q, g) in marks)
+    kinds = {(RC.STRIDE_BALLS[p % 5], RC.STRIDE_BALLS[q % 5]) for (p, _), (q, _) in _stride_pairs(total, 8192, nf, m)}
+    assert {(3, 0), (0, 3), (0, 1), (2, 3)} <= kinds and any(f != g for (_, f), (_, g) in _stride_pairs(total, 65535, nf, m)), kinds
+    idx = to_device(np.arange(ns, dtype=np.int64) % m)
+    balls = {k: to_device(v)[idx].contiguous() for k, v in packed.items()}
+    bufs = {"image": torch.full((total * H * W * 4 + 8,), GUARD, dtype=torch.int32, device="cuda"),
+            "ball_time": torch.full((total * n + 8,), GUARD, dtype=torch.int32, device="cuda")}
+    b = P.RasterBatch(rng, ns, W, H)
+    b.frames_device(balls, center=to_device(center)[idx].contiguous(), peak_count=to_device(count)[idx].contiguous(), elapsed=el,
+                    image=bufs["image"][4:-4].view(torch.float32), ball_time=bufs["ball_time"][4:-4].view(torch.float32))
+    torch.cuda.synchronize()
+    differing, unwritten = {}, {}
+    for k, small in (("image", img), ("ball_time", bt)):
+        assert not (bits(small) == GUARD).any(), k
+        got = bufs[k][4:-4].view(ns, nf, -1)
+        differing[k] = int((got != to_device(bits(small).view(np.int32).reshape(m, nf, -1))[idx]).sum())
+        unwritten[k] = int((got.view(total, -1)[8192:] == GUARD).sum())                         # of rows 8192 .. and 65 535 ..
+        assert bool((bufs[k][:4] == GUARD).all()) and bool((bufs[k][-4:] == GUARD).all()), k
+    print(f"{total} rows over 8192 list workgroups and 65535 tile rows: differing 32-bit words against the {m}-stream call: {differing}; "
+          f"words of rows 8192 .. still the fill value: {unwritten}")
+    assert not any(differing.values()) and not any(unwritten.values()), (differing, unwritten)
+    for s in (0, 1, ns - 2, ns - 1):
+        same(b.times(s), bt[s % m, -1], ("state", s))
