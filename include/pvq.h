@@ -660,9 +660,9 @@ pvq_status pvq_scene_batch_get_state(pvq_scene_batch *b, uint32_t stream_index, 
  *    (x, y, z, scale, rgba, the three params, time) is not finite.
  *  - params.time is per-ball state: update_pitch_balls sets it to Time::elapsed_secs() only for the balls a peak keys in the frame
  *    (update.rs:239), so a fading ball's noise and pulses freeze.  It starts at 0 (Params::default()).
- * The output is the linear HDR target before bloom and tone mapping, f32 [H][W][4].
- * Left out: bloom and the display transform — Bevy's own passes, not in the reference tree; noisy_color_2d.wgsl, which nothing
- * references.  The spider net, the bass spiral and the debug panels are the backdrop stage further down, which draws the picture the
+ * The output is the linear HDR target before bloom and tone mapping, f32 [H][W][4]; bloom, the display transform and the sRGB
+ * bytes are the present stage further down, which takes that target.
+ * Left out: noisy_color_2d.wgsl, which nothing references.  The spider net, the bass spiral and the debug panels are the backdrop stage further down, which draws the picture the
  * balls go over, the spectrogram quad and the chroma boxes the overlay stage after it, which draws in front of the balls; the
  * pitch-name text and the other parts the backdrop section lists stay left out. */
 /* one fragment: rgba linear, params = (calmness, time, pitch_accuracy, pitch_deviation) */
@@ -829,9 +829,11 @@ pvq_status pvq_panels_batch_get_history(pvq_panels_batch *b, uint32_t stream_ind
  * non-finite vertex (after its transform) or a non-finite colour draws nothing.  Pixel boxes are an acceleration only and err
  * outwards.
  *
- * Left out: the pitch-name text (it needs a font); bloom and tone mapping; MSAA; a ball whose z has fallen below -12.7, which in the
+ * Left out: the pitch-name text (it needs a font); MSAA; a ball whose z has fallen below -12.7, which in the
  * reference would go under the bass spiral — here the balls are always on top (at keying z >= -12.625, and the fade lowers it by
- * 0.03 per second while the ball lives).  The spectrogram quad at z = 5 and the chroma boxes are the overlay stage below. */
+ * 0.03 per second while the ball lives).  The spectrogram quad at z = 5 and the chroma boxes are the overlay stage below, bloom and
+ * tone mapping the present stage after it (which names what stays out of the displayed picture: the text, MSAA, the deband dither
+ * and a draw of the boxes in display space). */
 enum { PVQ_BACKDROP_NET_SPIRAL = 0, PVQ_BACKDROP_NET_RAYS = 1, PVQ_BACKDROP_BASS = 2 };
 /* the static quads of one layer: quads_out [n][4][2] (v0 .. v3 as x, y; triangles (2, 1, 0), (2, 0, 3)), n_out: their number —
  * 72 octaves - 1, 12, min(72 octaves, 168) - 1.  Either may be NULL.  octaves 1 .. 1024. */
@@ -962,6 +964,84 @@ pvq_status pvq_overlay_batch_frames_device(pvq_overlay_batch *b, size_t n_frames
 /* one stream's ring as the reference's texture would stand after the frames seen (synchronises): out [history_rows][n_bins][4],
  * write_index may be NULL */
 pvq_status pvq_overlay_batch_get_texture(pvq_overlay_batch *b, uint32_t stream_index, uint8_t *out, uint32_t *write_index);
+
+/* ---- the present stage: bloom, display transform and sRGB bytes ----------------------------------------------------
+ * What turns the linear HDR target [H][W][4] of the sections above into something a screen, a PNG or a video encoder takes: the
+ * camera's Bloom, its Tonemapping::SomewhatBoringDisplayTransform and the surface's sRGB encode.  The reference fixes the settings
+ * (pitchvis_viewer/src/display_system/setup.rs:347-383: Hdr, low_frequency_boost 1.0, low_frequency_boost_curvature 1.0,
+ * high_pass_frequency 0.52, prefilter threshold 0.17 and softness 0.82, Additive) and the intensity (update.rs:346-347, the scene
+ * section's `bloom`); the passes themselves are Bevy's and not in the reference tree, so the rule below is restated from Bevy's
+ * published behaviour (DESIGN.md 6h has the table of assumed semantics).  All arithmetic is f32 without FMA contraction, `/` IEEE,
+ * every sum in the order written.  The first pass's pow is taken in double arithmetic without libm and rounded once to f32 on host and device,
+ * so both carry the same bits in the bloomed linear picture; the bytes go through each side's own expf and powf and agree within a level.
+ *
+ * Mips.  d = max_mip_dimension, n_mips = max(floor(log2 d), 2) - 1; mip 0 is max(1, round(W r)) x max(1, round(H r)) with r = d as
+ * f32 / H as f32, mip k is max(1, w0 >> k) x max(1, h0 >> k).  A mip holds RGB in f32 (Bevy: Rg11b10Ufloat).
+ * Sampling.  A texture (w, h) at uv, bilinear with clamp-to-edge: p = uv * (w, h) - 0.5, i0 = floor(p), f = p - i0, indices clamped
+ * to 0 .. size - 1, x interpolated before y, lerp(a, b, t) = a + (b - a) * t.  Target texel (i, j) of (wt, ht) has uv = ((i + 0.5) /
+ * wt, (j + 0.5) / ht).
+ * Downsample.  13 taps at uv + (ox / ws, oy / hs): a (-2, 2) b (0, 2) c (2, 2) d (-2, 0) e (0, 0) f (2, 0) g (-2, -2) h (0, -2) i (2,
+ * -2) j (-1, 1) k (1, 1) l (-1, -1) m (1, -1).  Mip k -> k + 1: (a + c + g + i) * 0.03125 + (b + d + f + h) * 0.0625 + (e + j + k +
+ * l + m) * 0.125.  The picture -> mip 0 (its RGB; alpha ignored): g0 = (a + b + d + e) * 0.03125, g1 = (b + c + e + f) * 0.03125, g2 =
+ * (d + e + g + h) * 0.03125, g3 = (e + f + h + i) * 0.03125, g4 = (j + k + l + m) * 0.125, each times 1 / (1 + luma(pow(max(g, 0),
+ * 1 / 2.2)) / 4) with luma(v) = 0.2126 r + 0.7152 g + 0.0722 b, summed in order; then per channel fmin(fmax(x, 1e-4), 3.40282347e37)
+ * (a NaN becomes 1e-4); then, unless threshold == 0, with knee = threshold * softness and br = max(r, g, b): s = clamp(br -
+ * (threshold - knee), 0, 2 knee), s = s * s * (0.25 / (knee + 1e-5)), colour *= max(br - threshold, s) / max(br, 1e-5).
+ * Upsample.  k = n_mips - 1 .. 1 into mip k - 1, in place: tent = e * 0.25 + (b + d + f + h) * 0.125 + (a + c + g + i) * 0.0625 of
+ * mip k at uv offsets (+-x, +-y), x = 0.004 / (W / H), y = 0.004 (a .. i placed as above); additive dst += B_k * tent, energy-conserving
+ * dst = dst * (1 - B_k) + B_k * tent.  The last step takes the tent of mip 0 at the picture's pixel with B_0 into the picture's RGB;
+ * alpha passes through.
+ * Blend factor.  r = k / (n_mips - 1) (0 when n_mips is 1); lf = (1 - powf(1 - r, 1 / (1 - curvature))) * low_frequency_boost (at
+ * curvature 1 the exponent is +inf: powf(1, inf) = 1, powf(x < 1, inf) = 0); hp = 1 - clamp((r - high_pass_frequency) /
+ * high_pass_frequency, 0, 1); energy-conserving: lf *= 1 - intensity; B_k = (intensity + lf) * hp.
+ * A picture whose intensity is not finite or is <= 0 skips bloom (as Bevy's node does at 0) and still gets the rest.
+ * Display transform (SOMEWHAT_BORING).  c = max(c, 0); y = luma(c); cb = dot(c, (-0.1146, -0.3854, 0.5)), cr = dot(c, (0.5, -0.4542,
+ * -0.0458)); curve(v) = 1 - expf(-v); bt = curve(sqrtf(cb cb + cr cr) * 2.4); desat = max((bt - 0.7) * 0.8, 0) squared; desat_col =
+ * lerp(c, (y, y, y), desat); tm0 = c * max(0, curve(y) / max(1e-5, y)); tm1 = curve(desat_col); out = lerp(tm0, tm1, bt * bt) * 0.97.
+ * NONE passes max(c, 0) through.
+ * Encode.  v = clamp(out, 0, 1), v <= 0.0031308 ? 12.92 v : 1.055 powf(v, 1 / 2.4) - 0.055, byte = floor(v * 255 + 0.5); alpha:
+ * floor(clamp(a, 0, 1) * 255 + 0.5); a NaN encodes as 0.
+ * Left out of the displayed picture, here and in every section above: the pitch-name text, MSAA, the deband dither, colour grading
+ * (the reference leaves it at identity) and a draw of the chroma boxes in display space — they stay where the overlay stage blends
+ * them, in the linear target, and so pass through the transform. */
+enum { PVQ_PRESENT_ENERGY_CONSERVING = 0, PVQ_PRESENT_ADDITIVE = 1 };          /* composite_mode */
+enum { PVQ_PRESENT_TONEMAP_NONE = 0, PVQ_PRESENT_TONEMAP_SOMEWHAT_BORING = 1 }; /* tonemapping */
+typedef struct pvq_present_settings {
+    float low_frequency_boost, low_frequency_boost_curvature, high_pass_frequency, threshold, threshold_softness;
+    int composite_mode;
+    uint32_t max_mip_dimension;   /* 0: 512, else 4 .. 4096 */
+    int tonemapping;
+} pvq_present_settings;
+void pvq_present_default_settings(pvq_present_settings *s);   /* 1.0, 1.0, 0.52, 0.17, 0.82, ADDITIVE, 512, SOMEWHAT_BORING */
+/* the mip sizes of a width x height picture (1 .. 4096 each): *out_count = n_mips (at most 11), out_sizes [n_mips][2] as (w, h);
+ * either may be NULL.  PVQ_ERR_UNSUPPORTED where mip 0 would be wider than 16384 texels (a picture far wider than high). */
+pvq_status pvq_present_mips(uint32_t width, uint32_t height, uint32_t max_mip_dimension, uint32_t *out_count, uint32_t *out_sizes);
+/* B_0 .. B_{n_mips - 1} (n_mips 1 .. 11) at an intensity; settings NULL: the defaults.  The settings are checked wherever they are
+ * given: every float finite, high_pass_frequency > 0, the enums and max_mip_dimension in range. */
+pvq_status pvq_present_blend_factors(const pvq_present_settings *settings, float intensity, uint32_t n_mips, float *out);
+/* one picture on the host: image [height][width][4] -> out_rgba8 [height][width][4] bytes and, unless NULL, out_hdr
+ * [height][width][4], the bloomed linear picture before the display transform (it may be `image`) */
+pvq_status pvq_present_frame(const pvq_present_settings *settings, uint32_t width, uint32_t height, const float *image, float intensity,
+                             uint8_t *out_rgba8, float *out_hdr);
+
+/* The same for MANY pictures on the GPU.  Stateless; the handle owns one grow-only workspace for the mip chains of a piece of a
+ * call's rows (the sum of w_k h_k * 16 bytes a row: 9.9 MB at 1280 x 720 and 512). */
+typedef struct pvq_present_batch pvq_present_batch;
+/* The arguments are checked before any device is touched.  device_id < 0: a host-only handle whose device call returns
+ * PVQ_ERR_NO_DEVICE after its argument checks. */
+pvq_status pvq_present_batch_create(int device_id, const pvq_present_settings *settings, uint32_t width, uint32_t height,
+                                    pvq_present_batch **out);
+void pvq_present_batch_destroy(pvq_present_batch *b);
+/* upper bound of the workspace in bytes (default 1 GiB): a call whose rows need more runs in pieces of rows, with the same bits;
+ * one row's chains are always allocated */
+pvq_status pvq_present_batch_set_workspace_limit(pvq_present_batch *b, uint64_t bytes);
+/* d_image [n_rows][height][width][4] f32, 16-byte aligned, never written; d_intensity [n_rows] f32 — pvq_scene_outputs.bloom as it
+ * lies —, NULL: no bloom in any row; d_rgba8 [n_rows][height][width][4] bytes, 4-byte aligned; d_hdr NULL or
+ * [n_rows][height][width][4] f32, 16-byte aligned, which may be d_image (a picture pixel is read only by the lane that writes it).
+ * A row's result depends neither on its place in the call nor on the cut into pieces.  n_rows at most 2^31 - 1.  Asynchronous on
+ * `stream`; one handle's calls are stream-ordered. */
+pvq_status pvq_present_batch_rows_device(pvq_present_batch *b, size_t n_rows, const float *d_image, const float *d_intensity,
+                                         uint8_t *d_rgba8, float *d_hdr, void *stream);
 
 /* The note model the dataset of pitchvis_train exists for (pitchvis_train/train.py:67-99), which the viewer runs per rendered frame
  * through TorchScript on a CUDA device (pitchvis_viewer/src/ml_system.rs:24-69): a window of t_frames consecutive dB frames,

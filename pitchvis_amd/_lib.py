@@ -49,6 +49,8 @@ EXPORTS = [
     "pvq_overlay_quad", "pvq_overlay_state_create", "pvq_overlay_state_destroy", "pvq_overlay_state_push", "pvq_overlay_state_texture",
     "pvq_overlay_frame", "pvq_overlay_batch_create", "pvq_overlay_batch_destroy", "pvq_overlay_batch_frames_device",
     "pvq_overlay_batch_get_texture",
+    "pvq_present_default_settings", "pvq_present_mips", "pvq_present_blend_factors", "pvq_present_frame", "pvq_present_batch_create",
+    "pvq_present_batch_destroy", "pvq_present_batch_set_workspace_limit", "pvq_present_batch_rows_device",
     "pvq_note_model_create", "pvq_note_model_destroy", "pvq_note_model_sizes", "pvq_note_model_infer", "pvq_note_model_rows_device",
     "pvq_note_model_set_workspace_limit",
     "pvq_note_trainer_hyper_default", "pvq_note_trainer_create", "pvq_note_trainer_destroy", "pvq_note_trainer_step", "pvq_note_trainer_steps",
@@ -146,6 +148,12 @@ class CBackdropInputs(C.Structure):   # pvq_backdrop_inputs (device pointers)
                 ("hist_pos", C.c_void_p), ("hist_rgba", C.c_void_p), ("graph_pos", C.c_void_p), ("graph_rgba", C.c_void_p),
                 ("graph_capacity", C.c_uint32), ("spectrum_transform", C.c_float * 4), ("histogram_transform", C.c_float * 4),
                 ("graph_transform", C.c_float * 4), ("background", C.c_void_p)]
+
+
+class CPresentSettings(C.Structure):   # pvq_present_settings
+    _fields_ = [(n, C.c_float) for n in ("low_frequency_boost", "low_frequency_boost_curvature", "high_pass_frequency", "threshold",
+                                         "threshold_softness")] + \
+               [("composite_mode", C.c_int), ("max_mip_dimension", C.c_uint32), ("tonemapping", C.c_int)]
 
 
 class CNoteModelParams(C.Structure):   # pvq_note_model_params
@@ -390,6 +398,15 @@ def load():
     L.pvq_overlay_batch_destroy.argtypes = [vp]; L.pvq_overlay_batch_destroy.restype = None
     L.pvq_overlay_batch_frames_device.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]; L.pvq_overlay_batch_frames_device.restype = C.c_int
     L.pvq_overlay_batch_get_texture.argtypes = [vp, C.c_uint32, bp, up]; L.pvq_overlay_batch_get_texture.restype = C.c_int
+    psp = C.POINTER(CPresentSettings)
+    L.pvq_present_default_settings.argtypes = [psp]; L.pvq_present_default_settings.restype = None
+    L.pvq_present_mips.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, up, up]; L.pvq_present_mips.restype = C.c_int
+    L.pvq_present_blend_factors.argtypes = [psp, C.c_float, C.c_uint32, fp]; L.pvq_present_blend_factors.restype = C.c_int
+    L.pvq_present_frame.argtypes = [psp, C.c_uint32, C.c_uint32, fp, C.c_float, bp, fp]; L.pvq_present_frame.restype = C.c_int
+    L.pvq_present_batch_create.argtypes = [C.c_int, psp, C.c_uint32, C.c_uint32, C.POINTER(vp)]; L.pvq_present_batch_create.restype = C.c_int
+    L.pvq_present_batch_destroy.argtypes = [vp]; L.pvq_present_batch_destroy.restype = None
+    L.pvq_present_batch_set_workspace_limit.argtypes = [vp, C.c_uint64]; L.pvq_present_batch_set_workspace_limit.restype = C.c_int
+    L.pvq_present_batch_rows_device.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp]; L.pvq_present_batch_rows_device.restype = C.c_int
     L.pvq_note_model_create.argtypes = [C.c_int, C.POINTER(CNoteModelParams), C.POINTER(CNoteModelWeights), C.POINTER(vp)]
     L.pvq_note_model_create.restype = C.c_int
     L.pvq_note_model_destroy.argtypes = [vp]
