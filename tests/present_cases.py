@@ -6,7 +6,12 @@ Sizes: 1 x 1, 2 x 3, 5 x 4, 17 x 9, 129 x 33 (no multiple of the 16 x 16 tile or
 the default 512 (mip 0 is 994 x 512: the picture is magnified) and 1 x 1 at 16.  Content: a single lit pixel at a corner, on an edge
 and in the middle, a constant, a checkerboard of 0.1 / 4.0 either side of the threshold's knee, an HDR ramp 0 .. 50, pixels that are
 NaN, +-inf and negative, alpha 0, 0.5, 2 and NaN.  Both composite modes, both tone-mapping values, threshold 0, curvature 1 (the
-infinite exponent) and 0.5."""
+infinite exponent) and 0.5.
+
+Chain length and odd sides: 1 x 64 at 4096 (11 mips, 64 x 4096 down to 1 x 4: every table filled to MAX_MIPS) and at 4095 (10 mips of odd
+heights), 40 x 24 at 100 (a ratio that is no integer, sides that halve unevenly), 4096 x 1 at 4 (one mip of 16 384 x 4, the widest the plan
+admits: 1 024 tiles along x).  `forms` restates which kernel form the host picks for a picture's two passes; `stride_rows` makes the 61
+patterns of the row-stride test (STRIDE_SHAPES)."""
 import numpy as np
 
 import present_model as M
@@ -85,8 +90,58 @@ CASES = [
     ("33x17-d512-middle", lit(33, 17, "middle"), 0.5, dict()),
     ("5x4-d8-no-bloom", specials(5, 4, 41), 0.0, dict(max_mip_dimension=8)),
     ("17x9-d16-nan-intensity-none", random_hdr(17, 9, 42), float("nan"), dict(max_mip_dimension=16, **NONE)),
+    ("1x64-d4096-random", random_hdr(1, 64, 51), 0.6, dict(max_mip_dimension=4096)),
+    ("1x64-d4095-random", random_hdr(1, 64, 51), 0.6, dict(max_mip_dimension=4095)),
+    ("40x24-d100-specials-ec", specials(40, 24, 52), 0.7, dict(max_mip_dimension=100, **EC)),
+    ("4096x1-d4-ramp", ramp(4096, 1), 0.8, dict(max_mip_dimension=4)),
 ]
 IDS = [c[0] for c in CASES]
+
+
+# ---- the row-stride test's rows (tests/test_present_gpu.py) ----
+# (W, H, max_mip_dimension, rows): every workgroup of the first makes 3 trips and rows 0 .. 2 a fourth; of the second 2 and a third
+STRIDE_SHAPES = [(5, 4, 8, 3 * 65535 + 3), (24, 10, 8, 2 * 65535 + 3)]
+STRIDE_PATTERNS = 61    # 65 535 % 61 = 21: a workgroup that starts on pattern p goes on to p + 21, then p + 42 (mod 61)
+# pattern p's intensity is STRIDE_CYCLE[p % 9]: 0 and NaN skip bloom (14 of the 61 patterns), the rest are spread over (0, 1].  9 and 21
+# share the factor 3, so the residues a workgroup meets are r, r + 3, r + 6: with the skips at 2 and 6 every run of three has at most
+# one, and 8 -> 2 -> 5 and 3 -> 6 -> 0 are bloom -> skip -> bloom.
+STRIDE_CYCLE = (0.3, 1.0, 0.0, 0.65, 0.12, 0.85, float("nan"), 0.5, 0.02)
+
+
+def stride_rows(W, H, seed):
+    """(images [61][H][W][4], intensities [61]): pattern p is random_hdr, specials at every fifth p, at STRIDE_CYCLE[p % 9]"""
+    imgs = np.stack([(specials if p % 5 == 0 else random_hdr)(W, H, seed + p) for p in range(STRIDE_PATTERNS)])
+    return imgs, np.asarray([STRIDE_CYCLE[p % len(STRIDE_CYCLE)] for p in range(STRIDE_PATTERNS)], f32)
+
+
+# ---- which kernel form the host picks ----
+TILE, FOOT = 16, 44 * 44    # present_batch.hip: a workgroup's target tile, the texels of its LDS footprint array
+
+
+def _footprint(i0, wt, ws, margin):
+    """present::footprint along one axis, in float32: the number of source texels that targets i0 .. i0 + 15 can sample"""
+    last = min(i0 + TILE, wt) - 1
+    a = (f32(i0) + f32(0.5)) / f32(wt) * f32(ws)
+    b = (f32(last) + f32(0.5)) / f32(wt) * f32(ws)
+    lo = int(np.floor(a - f32(margin))) - 2
+    hi = int(np.floor(b + f32(margin))) + 2
+    return min(max(hi, 0), ws - 1) - min(max(lo, 0), ws - 1) + 1
+
+
+def _fit(wt, ht, ws, hs, mx, my):
+    """footprints_fit: the widest and the highest footprint of any tile together"""
+    fw = max(_footprint(i0, wt, ws, mx) for i0 in range(0, wt, TILE))
+    fh = max(_footprint(j0, ht, hs, my) for j0 in range(0, ht, TILE))
+    return fw * fh <= FOOT
+
+
+def forms(W, H, d=512):
+    """(first_staged, last_staged): whether the picture -> mip 0 pass and the mip 0 -> picture pass stage their footprints in LDS.
+    Restates present::footprint, footprints_fit, tent_x and tent_reach (present_math.hpp, present_batch.hip) in NumPy float32."""
+    w0, h0 = M.mips(W, H, d)[0]
+    x = f32(0.004) / (f32(W) / f32(H))
+    return _fit(w0, h0, W, H, 2.0, 2.0), _fit(W, H, w0, h0, x * f32(w0), f32(0.004) * f32(h0))
+
 
 _models = {}
 

@@ -193,8 +193,40 @@ def test_mips_known_answers():
     assert P.present_mips(1, 1, 16) == [(16, 16), (8, 8), (4, 4)]
     assert [len(P.present_mips(64, 64, d)) for d in (4, 7, 8, 16, 64, 512, 4096)] == [1, 1, 2, 3, 5, 8, 11]
     assert P.present_mips(1, 4096, 4) == [(1, 4)]                    # round(1 * 4 / 4096) = 0: at least one texel
-    for W, H, d in ((1280, 720, 512), (4, 130, 64), (129, 33, 16), (33, 17, 512), (5, 4, 8)):
+    # 11 mips, every table filled to MAX_MIPS; 10 mips of odd heights; a ratio that is no integer; the widest mip 0 the plan admits
+    assert P.present_mips(1, 64, 4096) == [(64, 4096), (32, 2048), (16, 1024), (8, 512), (4, 256), (2, 128), (1, 64), (1, 32), (1, 16), (1, 8), (1, 4)]
+    assert P.present_mips(1, 64, 4095) == [(64, 4095), (32, 2047), (16, 1023), (8, 511), (4, 255), (2, 127), (1, 63), (1, 31), (1, 15), (1, 7)]
+    assert P.present_mips(40, 24, 100) == [(167, 100), (83, 50), (41, 25), (20, 12), (10, 6)]
+    assert P.present_mips(4096, 1, 4) == [(16384, 4)]
+    assert P.present_mips(5, 4, 8) == [(10, 8), (5, 4)] and P.present_mips(24, 10, 8) == [(19, 8), (9, 4)]   # the stride shapes
+    for W, H, d in ((1280, 720, 512), (4, 130, 64), (129, 33, 16), (33, 17, 512), (5, 4, 8), (24, 10, 8), (1, 64, 4096), (1, 64, 4095),
+                    (40, 24, 100), (4096, 1, 4)):
         assert P.present_mips(W, H, d) == M.mips(W, H, d)
+
+
+def test_every_kernel_form_has_a_case():
+    """The host picks each of the picture's two passes from two forms, staged in LDS or sampling device memory, by whether every tile's
+    footprint fits 44 x 44 texels.  present_cases.forms restates that rule; this test holds the crafted cases and the stride shapes to
+    it, so that a change to the footprint rule which leaves a form without a case fails here.  It is a mirror of the library and no
+    more: it cannot see which kernel a call launched, only say which one the rule, as restated, picks."""
+    shapes = {name: (img.shape[1], img.shape[0], kw.get("max_mip_dimension", 512)) for name, img, _, kw in PC.CASES}
+    shapes.update({f"stride {W}x{H}-d{d}": (W, H, d) for W, H, d, _ in PC.STRIDE_SHAPES})
+    got = {name: PC.forms(*s) for name, s in shapes.items()}
+    for name, f in got.items():
+        print(f"{name}: first pass {'staged' if f[0] else 'unstaged'}, last pass {'staged' if f[1] else 'unstaged'}")
+    # A picture cannot have both passes unstaged: the first needs a mip 0 far smaller than the picture, the last one far larger.
+    assert set(got.values()) == {(True, True), (False, True), (True, False)}
+    for first_staged in (True, False):
+        assert any(f[0] == first_staged for f in got.values())
+    for last_staged in (True, False):
+        assert any(f[1] == last_staged for f in got.values())
+    named = {(64, 64, 4): (False, True), (64, 64, 8): (False, True), (129, 33, 4): (False, True),
+             (33, 17, 512): (True, False), (40, 24, 100): (True, False), (1, 64, 4096): (True, False),
+             (5, 4, 8): (True, True), (24, 10, 8): (True, True), (17, 9, 16): (True, True)}
+    for s, want in named.items():
+        assert s in shapes.values(), s
+        assert PC.forms(*s) == want, (s, PC.forms(*s), want)
+    assert all(PC.forms(W, H, d) == (True, True) for W, H, d, _ in PC.STRIDE_SHAPES)
 
 
 @pytest.mark.parametrize("intensity", [0.0, 0.3, 1.0])
