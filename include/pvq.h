@@ -664,7 +664,8 @@ pvq_status pvq_scene_batch_get_state(pvq_scene_batch *b, uint32_t stream_index, 
  * bytes are the present stage further down, which takes that target.
  * Left out: noisy_color_2d.wgsl, which nothing references.  The spider net, the bass spiral and the debug panels are the backdrop stage further down, which draws the picture the
  * balls go over, the spectrogram quad and the chroma boxes the overlay stage after it, which draws in front of the balls; the
- * pitch-name text and the other parts the backdrop section lists stay left out. */
+ * pitch-name text the text stage between the two, which draws over the balls and under the overlay; the other parts the backdrop
+ * section lists stay left out. */
 /* one fragment: rgba linear, params = (calmness, time, pitch_accuracy, pitch_deviation) */
 pvq_status pvq_raster_shade(const float *rgba, const float *params, float u, float v, float *out4);
 /* the time update of one frame: every entry of the list sets time[trunc(center)] = elapsed (keys >= n_bins are ignored, as the
@@ -829,11 +830,11 @@ pvq_status pvq_panels_batch_get_history(pvq_panels_batch *b, uint32_t stream_ind
  * non-finite vertex (after its transform) or a non-finite colour draws nothing.  Pixel boxes are an acceleration only and err
  * outwards.
  *
- * Left out: the pitch-name text (it needs a font); MSAA; a ball whose z has fallen below -12.7, which in the
+ * Left out: MSAA; a ball whose z has fallen below -12.7, which in the
  * reference would go under the bass spiral — here the balls are always on top (at keying z >= -12.625, and the fade lowers it by
- * 0.03 per second while the ball lives).  The spectrogram quad at z = 5 and the chroma boxes are the overlay stage below, bloom and
- * tone mapping the present stage after it (which names what stays out of the displayed picture: the text, MSAA, the deband dither
- * and a draw of the boxes in display space). */
+ * 0.03 per second while the ball lives).  The pitch-name text at z = -0.02 is the text stage below (the caller brings the font),
+ * the spectrogram quad at z = 5 and the chroma boxes are the overlay stage after it, bloom and tone mapping the present stage after
+ * that (which names what stays out of the displayed picture: MSAA, the deband dither and a draw of the boxes in display space). */
 enum { PVQ_BACKDROP_NET_SPIRAL = 0, PVQ_BACKDROP_NET_RAYS = 1, PVQ_BACKDROP_BASS = 2 };
 /* the static quads of one layer: quads_out [n][4][2] (v0 .. v3 as x, y; triangles (2, 1, 0), (2, 0, 3)), n_out: their number —
  * 72 octaves - 1, 12, min(72 octaves, 168) - 1.  Either may be NULL.  octaves 1 .. 1024. */
@@ -965,6 +966,106 @@ pvq_status pvq_overlay_batch_frames_device(pvq_overlay_batch *b, size_t n_frames
  * write_index may be NULL */
 pvq_status pvq_overlay_batch_get_texture(pvq_overlay_batch *b, uint32_t stream_index, uint8_t *out, uint32_t *write_index);
 
+/* ---- the text: pitch-name labels from font outlines, over the balls and under the overlay ----------------------------
+ * The twelve Text2d labels of the viewer (pitchvis_viewer/src/display_system/setup.rs:386-416; names pitchvis_colors/src/lib.rs:36-38)
+ * sit at z = -0.02: above every ball (z <= -0.125) and below the spectrogram quad (z = 5) and the UI.  So the stage is an in-place
+ * blend over a finished image of the raster section's camera, run after pvq_backdrop_balls_over_device and before
+ * pvq_overlay_batch_frames_device, and only in the Full and Performance visuals modes (update.rs:871-885 hides the labels in the
+ * others: there the caller does not call it).  Bevy's text pipeline (shaping, rasteriser, glyph atlas, sampling of the scaled
+ * quad) is not in the reference tree; the rule below is this library's own, and DESIGN.md 6i lists what it assumes.  The library
+ * embeds no font: the caller brings one (the viewer's is DejaVuSans).
+ *
+ * Font.  Per codepoint a TrueType outline — contours of on- and off-curve points in font units, y upwards, an implied on-curve
+ * point between two consecutive off-curve points — and an advance; units per em, hhea ascent and hhea descent (negative below the
+ * baseline).  From TrueType bytes the reader takes head, maxp, hhea, hmtx, cmap (a Unicode subtable of format 12, else 4), loca
+ * (both formats) and glyf, simple glyphs only: a composite glyph, or a font without glyf (CFF), is PVQ_ERR_UNSUPPORTED when a label
+ * asks for it.  Hinting instructions are skipped, never interpreted; kern and GPOS are ignored; there is no shaping (one glyph per
+ * codepoint, left to right).  Every offset and count is checked against the bytes before use: bad bytes are PVQ_ERR_INVALID_ARG
+ * with a text that names the table.
+ *
+ * Layout of a label, in font pixels with y downwards about the label's position: k = font_px / units_per_em; the pen advances by
+ * advance * k; the block's width is the sum of the advances, its height the line height 1.2 font_px; the block is centred on
+ * (x, y), so left = -width / 2 and top = -0.6 font_px; baseline = top + (line height - (ascent - descent) k) / 2 + ascent k.  A
+ * point (gx, gy) of the glyph at pen p lies at (left + p + gx k, baseline - gy k); times scale (world units per font pixel) about
+ * (x, y) it is a world position, which the raster section's camera maps to output pixel coordinates (pixel (i, j) is the square
+ * [i, i + 1] x [j, j + 1]): px = wx / s + width / 2, py = height / 2 - wy / s, s = viewport_height / height in f32.  All of this in
+ * double, rounded once to f32.  A codepoint the font lacks is PVQ_ERR_INVALID_ARG naming it (Bevy would draw a replacement box).
+ *
+ * Outline to segments.  A quadratic p0 p1 p2 (output pixels, double) is cut into n = max(1, ceil(sqrt(|p0 - 2 p1 + p2| / (4 tol))))
+ * chords of equal parameter, tol = 1 / 64 pixel; the chord ends are rounded once to f32.  A label's outline is one list of
+ * directed segments, glyph by glyph, contour by contour; horizontal segments, segments that meet no pixel row of the image and
+ * segments left of the image are dropped (they add nothing).
+ *
+ * Coverage of pixel (X, Y) by a label: for each segment in list order, clip it to the pixel's rows Y .. Y + 1 and integrate
+ * clamp(x(y) - X, 0, 1) over y — piecewise linear after the cuts at x = X and x = X + 1 —, positive where the segment runs to
+ * larger y; the coverage is min(|sum|, 1): the exact area of the outline inside the pixel square for a winding number of 0 or +-1
+ * (overlapping contours of one sense count once where they fill the pixel).  f32 without FMA contraction, so the host face and the
+ * device carry the same bits.  A label's pixel box is the pixel squares its outline's bounding box meets; outside it the coverage
+ * is 0.  No hinting, no grid fitting, no MSAA on top.
+ *
+ * Blend.  Colour srgb_to_linear(rgb) (the curve of the scene section), alpha the coverage, the raster section's blend; a pixel
+ * whose coverage is exactly 0 is not touched.  Labels blend in label order where they overlap.
+ *
+ * Limits: 1 .. 64 labels of 1 .. 8 codepoints; width, height 1 .. 4096; an em (font_px * scale / s) of at most 1024 output
+ * pixels; at most 65536 segments a label; units per em 16 .. 16384; coordinates within +-65536 font units; a batch handle's
+ * coverage layer (1 KB per tile a label's box meets) at most 256 MiB, PVQ_ERR_UNSUPPORTED beyond.  A font handle caches the glyphs
+ * it has read and is not to be used from two threads at once. */
+typedef struct pvq_text_font pvq_text_font;
+pvq_status pvq_text_font_from_ttf(const uint8_t *bytes, size_t n_bytes, pvq_text_font **out);
+/* The same data given directly: codepoints, advances, n_contours and n_points are [n_glyphs]; contour_ends holds, glyph after
+ * glyph, the index of each contour's last point among the glyph's own points (ascending, the last one n_points - 1); points
+ * [total][2] and on_curve [total] hold the glyphs' points one after the other. */
+pvq_status pvq_text_font_from_outlines(uint32_t n_glyphs, const uint32_t *codepoints, const float *advances, const uint32_t *n_contours,
+                                       const uint32_t *contour_ends, const uint32_t *n_points, const float *points, const uint8_t *on_curve,
+                                       uint32_t units_per_em, float ascent, float descent, pvq_text_font **out);
+void pvq_text_font_destroy(pvq_text_font *f);
+/* any of the three may be NULL */
+pvq_status pvq_text_font_metrics(const pvq_text_font *f, uint32_t *units_per_em, float *ascent, float *descent);
+/* A glyph as the font holds it.  advance, n_contours, n_points may be NULL; contour_ends [cap_contours], points [cap_points][2] and
+ * on_curve [cap_points] are filled where given and large enough (PVQ_ERR_INVALID_ARG where given and too small): ask for the
+ * counts first. */
+pvq_status pvq_text_font_glyph(pvq_text_font *f, uint32_t codepoint, float *advance, uint32_t *n_contours, uint32_t *n_points,
+                               uint32_t cap_contours, uint32_t cap_points, uint32_t *contour_ends, float *points, uint8_t *on_curve);
+typedef struct pvq_text_label {
+    char text[36];          /* NUL-terminated UTF-8, 1 .. 8 codepoints */
+    float x, y;             /* the block's centre, world units */
+    float font_px, scale;   /* the viewer's 40 and 0.02: an em of 0.8 world units */
+    float rgb[3];           /* sRGB, 0 .. 1 */
+} pvq_text_label;
+/* The reference's twelve: the last twelve of calculate_spiral_points(octaves, 12), each times 0.85 + 0.025 |x|, named
+ * PITCH_NAMES[(idx + 12 - 3) % 12] and coloured colors[that] (12 RGB triples, NULL: pitchvis_colors::COLORS), font_px 40, scale
+ * 0.02.  octaves 1 .. 255. */
+pvq_status pvq_text_pitch_labels(uint32_t octaves, const float *colors, pvq_text_label *out12);
+/* what the layout makes of a label on a width x height image */
+typedef struct pvq_text_layout {
+    uint32_t on_image;          /* 0: nothing of the label lies on the image; the box and n_tiles are 0 */
+    uint32_t x0, y0, x1, y1;    /* its pixel box: first and last column and row */
+    uint32_t n_segments;        /* of its list, after the drops */
+    uint32_t n_tiles;           /* the 16 x 16 tiles the box meets: columns x0 / 16 .. x1 / 16, rows y0 / 16 .. y1 / 16 */
+    float origin_x, baseline_y; /* the first glyph's origin, output pixel coordinates */
+} pvq_text_layout;
+pvq_status pvq_text_layout_query(pvq_text_font *font, const pvq_text_label *labels, uint32_t n, uint32_t width, uint32_t height,
+                                 float viewport_height, pvq_text_layout *out_n);
+/* One picture on the host: the labels over image_inout [height][width][4] in place, and / or every label's coverage to
+ * coverage_out [n][height][width]; either may be NULL, both NULL is PVQ_ERR_INVALID_ARG.  viewport_height 0: the viewer's. */
+pvq_status pvq_text_frame(pvq_text_font *font, const pvq_text_label *labels, uint32_t n, uint32_t width, uint32_t height,
+                          float viewport_height, float *image_inout, float *coverage_out);
+
+/* The same for MANY rows on the GPU.  The text is the same for every row, so the handle owns a compact coverage layer, computed on
+ * the device once at create: one f32 per pixel of each (tile, label) pair, over the 16 x 16 tiles the labels' boxes meet only. */
+typedef struct pvq_text_batch pvq_text_batch;
+/* The arguments are checked, and the labels laid out, before any device is touched; the font is not needed after the call.
+ * device_id < 0: a host-only handle whose device calls return PVQ_ERR_NO_DEVICE after their argument checks. */
+pvq_status pvq_text_batch_create(int device_id, pvq_text_font *font, const pvq_text_label *labels, uint32_t n, float viewport_height,
+                                 uint32_t width, uint32_t height, pvq_text_batch **out);
+void pvq_text_batch_destroy(pvq_text_batch *b);
+/* The labels over each of n_rows pictures d_image_inout [n_rows][height][width][4] (16-byte aligned), in place: a pixel is read and
+ * written by the same lane, and a pixel no label covers is not touched.  A handle whose labels all lie off the image launches
+ * nothing.  n_rows at most 2^31 - 1.  Asynchronous on `stream`; one handle's calls are stream-ordered. */
+pvq_status pvq_text_batch_rows_device(pvq_text_batch *b, size_t n_rows, float *d_image_inout, void *stream);
+/* the layer copied back as a full image out [height][width] (synchronises): label 0 .. n - 1, or -1: the largest over the labels */
+pvq_status pvq_text_batch_get_coverage(pvq_text_batch *b, int label, float *out);
+
 /* ---- the present stage: bloom, display transform and sRGB bytes ----------------------------------------------------
  * What turns the linear HDR target [H][W][4] of the sections above into something a screen, a PNG or a video encoder takes: the
  * camera's Bloom, its Tonemapping::SomewhatBoringDisplayTransform and the surface's sRGB encode.  The reference fixes the settings
@@ -1001,7 +1102,7 @@ pvq_status pvq_overlay_batch_get_texture(pvq_overlay_batch *b, uint32_t stream_i
  * NONE passes max(c, 0) through.
  * Encode.  v = clamp(out, 0, 1), v <= 0.0031308 ? 12.92 v : 1.055 powf(v, 1 / 2.4) - 0.055, byte = floor(v * 255 + 0.5); alpha:
  * floor(clamp(a, 0, 1) * 255 + 0.5); a NaN encodes as 0.
- * Left out of the displayed picture, here and in every section above: the pitch-name text, MSAA, the deband dither, colour grading
+ * Left out of the displayed picture, here and in every section above: MSAA, the deband dither, colour grading
  * (the reference leaves it at identity) and a draw of the chroma boxes in display space — they stay where the overlay stage blends
  * them, in the linear target, and so pass through the transform. */
 enum { PVQ_PRESENT_ENERGY_CONSERVING = 0, PVQ_PRESENT_ADDITIVE = 1 };          /* composite_mode */

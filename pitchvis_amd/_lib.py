@@ -49,6 +49,9 @@ EXPORTS = [
     "pvq_overlay_quad", "pvq_overlay_state_create", "pvq_overlay_state_destroy", "pvq_overlay_state_push", "pvq_overlay_state_texture",
     "pvq_overlay_frame", "pvq_overlay_batch_create", "pvq_overlay_batch_destroy", "pvq_overlay_batch_frames_device",
     "pvq_overlay_batch_get_texture",
+    "pvq_text_font_from_ttf", "pvq_text_font_from_outlines", "pvq_text_font_destroy", "pvq_text_font_metrics", "pvq_text_font_glyph",
+    "pvq_text_pitch_labels", "pvq_text_layout_query", "pvq_text_frame", "pvq_text_batch_create", "pvq_text_batch_destroy",
+    "pvq_text_batch_rows_device", "pvq_text_batch_get_coverage",
     "pvq_present_default_settings", "pvq_present_mips", "pvq_present_blend_factors", "pvq_present_frame", "pvq_present_batch_create",
     "pvq_present_batch_destroy", "pvq_present_batch_set_workspace_limit", "pvq_present_batch_rows_device",
     "pvq_note_model_create", "pvq_note_model_destroy", "pvq_note_model_sizes", "pvq_note_model_infer", "pvq_note_model_rows_device",
@@ -154,6 +157,15 @@ class CPresentSettings(C.Structure):   # pvq_present_settings
     _fields_ = [(n, C.c_float) for n in ("low_frequency_boost", "low_frequency_boost_curvature", "high_pass_frequency", "threshold",
                                          "threshold_softness")] + \
                [("composite_mode", C.c_int), ("max_mip_dimension", C.c_uint32), ("tonemapping", C.c_int)]
+
+
+class CTextLabel(C.Structure):   # pvq_text_label
+    _fields_ = [("text", C.c_char * 36), ("x", C.c_float), ("y", C.c_float), ("font_px", C.c_float), ("scale", C.c_float), ("rgb", C.c_float * 3)]
+
+
+class CTextLayout(C.Structure):   # pvq_text_layout
+    _fields_ = [("on_image", C.c_uint32), ("x0", C.c_uint32), ("y0", C.c_uint32), ("x1", C.c_uint32), ("y1", C.c_uint32), ("n_segments", C.c_uint32),
+                ("n_tiles", C.c_uint32), ("origin_x", C.c_float), ("baseline_y", C.c_float)]
 
 
 class CNoteModelParams(C.Structure):   # pvq_note_model_params
@@ -398,6 +410,22 @@ def load():
     L.pvq_overlay_batch_destroy.argtypes = [vp]; L.pvq_overlay_batch_destroy.restype = None
     L.pvq_overlay_batch_frames_device.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]; L.pvq_overlay_batch_frames_device.restype = C.c_int
     L.pvq_overlay_batch_get_texture.argtypes = [vp, C.c_uint32, bp, up]; L.pvq_overlay_batch_get_texture.restype = C.c_int
+    tlp = C.POINTER(CTextLabel)
+    L.pvq_text_font_from_ttf.argtypes = [bp, C.c_size_t, C.POINTER(vp)]; L.pvq_text_font_from_ttf.restype = C.c_int
+    L.pvq_text_font_from_outlines.argtypes = [C.c_uint32, up, fp, up, up, up, fp, bp, C.c_uint32, C.c_float, C.c_float, C.POINTER(vp)]
+    L.pvq_text_font_from_outlines.restype = C.c_int
+    L.pvq_text_font_destroy.argtypes = [vp]; L.pvq_text_font_destroy.restype = None
+    L.pvq_text_font_metrics.argtypes = [vp, up, fp, fp]; L.pvq_text_font_metrics.restype = C.c_int
+    L.pvq_text_font_glyph.argtypes = [vp, C.c_uint32, fp, up, up, C.c_uint32, C.c_uint32, up, fp, bp]; L.pvq_text_font_glyph.restype = C.c_int
+    L.pvq_text_pitch_labels.argtypes = [C.c_uint32, fp, tlp]; L.pvq_text_pitch_labels.restype = C.c_int
+    L.pvq_text_layout_query.argtypes = [vp, tlp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(CTextLayout)]
+    L.pvq_text_layout_query.restype = C.c_int
+    L.pvq_text_frame.argtypes = [vp, tlp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, fp, fp]; L.pvq_text_frame.restype = C.c_int
+    L.pvq_text_batch_create.argtypes = [C.c_int, vp, tlp, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.pvq_text_batch_create.restype = C.c_int
+    L.pvq_text_batch_destroy.argtypes = [vp]; L.pvq_text_batch_destroy.restype = None
+    L.pvq_text_batch_rows_device.argtypes = [vp, C.c_size_t, vp, vp]; L.pvq_text_batch_rows_device.restype = C.c_int
+    L.pvq_text_batch_get_coverage.argtypes = [vp, C.c_int, fp]; L.pvq_text_batch_get_coverage.restype = C.c_int
     psp = C.POINTER(CPresentSettings)
     L.pvq_present_default_settings.argtypes = [psp]; L.pvq_present_default_settings.restype = None
     L.pvq_present_mips.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, up, up]; L.pvq_present_mips.restype = C.c_int

@@ -31,6 +31,8 @@
 #include "scene_batch.hpp"
 #include "scene_host.hpp"
 #include "stage_plan.hpp"
+#include "text_batch.hpp"
+#include "text_host.hpp"
 #include "vqt_engine.hpp"
 
 struct pvq_vqt {
@@ -68,6 +70,12 @@ struct pvq_overlay_state {
 };
 struct pvq_overlay_batch {
     std::unique_ptr<pvq::OverlayBatch> impl;
+};
+struct pvq_text_font {
+    std::unique_ptr<pvq::TextFont> impl;
+};
+struct pvq_text_batch {
+    std::unique_ptr<pvq::TextBatch> impl;
 };
 struct pvq_present_batch {
     std::unique_ptr<pvq::PresentBatch> impl;
@@ -1652,6 +1660,166 @@ pvq_status pvq_overlay_batch_get_texture(pvq_overlay_batch* b, uint32_t stream_i
     try {
         if (!b) return null_handle();
         return b->impl->get_texture(stream_index, out, write_index);
+    } catch (...) { return translate_exception(); }
+}
+
+// The pitch-name labels over the balls and under the overlay (setup.rs:386-416): a font the caller brings, one picture on the host
+// (text_host.hpp) and many rows on the device (text_batch.hpp)
+pvq_status pvq_text_font_from_ttf(const uint8_t* bytes, size_t n_bytes, pvq_text_font** out) {
+    try {
+        if (!out) return null_handle();
+        *out = nullptr;
+        std::unique_ptr<pvq::TextFont> impl;
+        std::string err;
+        const pvq_status st = pvq::TextFont::from_ttf(bytes, n_bytes, impl, err);
+        if (st != PVQ_OK) {
+            pvq::set_last_error(err);
+            return st;
+        }
+        *out = new pvq_text_font{std::move(impl)};
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_text_font_from_outlines(uint32_t n_glyphs, const uint32_t* codepoints, const float* advances, const uint32_t* n_contours,
+                                       const uint32_t* contour_ends, const uint32_t* n_points, const float* points, const uint8_t* on_curve,
+                                       uint32_t units_per_em, float ascent, float descent, pvq_text_font** out) {
+    try {
+        if (!out) return null_handle();
+        *out = nullptr;
+        std::unique_ptr<pvq::TextFont> impl;
+        std::string err;
+        const pvq_status st = pvq::TextFont::from_outlines(n_glyphs, codepoints, advances, n_contours, contour_ends, n_points, points, on_curve,
+                                                           units_per_em, ascent, descent, impl, err);
+        if (st != PVQ_OK) {
+            pvq::set_last_error(err);
+            return st;
+        }
+        *out = new pvq_text_font{std::move(impl)};
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+void pvq_text_font_destroy(pvq_text_font* f) {
+    try {
+        delete f;
+    } catch (...) { (void)translate_exception(); }
+}
+pvq_status pvq_text_font_metrics(const pvq_text_font* f, uint32_t* units_per_em, float* ascent, float* descent) {
+    try {
+        if (!f) return null_handle();
+        if (units_per_em) *units_per_em = f->impl->units_per_em();
+        if (ascent) *ascent = f->impl->ascent();
+        if (descent) *descent = f->impl->descent();
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_text_font_glyph(pvq_text_font* f, uint32_t codepoint, float* advance, uint32_t* n_contours, uint32_t* n_points,
+                               uint32_t cap_contours, uint32_t cap_points, uint32_t* contour_ends, float* points, uint8_t* on_curve) {
+    try {
+        if (!f) return null_handle();
+        const pvq::TextGlyph* g = nullptr;
+        std::string err;
+        const pvq_status st = f->impl->glyph(codepoint, g, err);
+        if (st != PVQ_OK) {
+            pvq::set_last_error(err);
+            return st;
+        }
+        if (advance) *advance = g->advance;
+        if (n_contours) *n_contours = static_cast<uint32_t>(g->contour_ends.size());
+        if (n_points) *n_points = static_cast<uint32_t>(g->on_curve.size());
+        if ((contour_ends && cap_contours < g->contour_ends.size()) || ((points || on_curve) && cap_points < g->on_curve.size())) {
+            pvq::set_last_error("text font glyph: an array is smaller than the glyph; ask for the counts first");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        if (contour_ends) std::copy(g->contour_ends.begin(), g->contour_ends.end(), contour_ends);
+        if (points) std::copy(g->points.begin(), g->points.end(), points);
+        if (on_curve) std::copy(g->on_curve.begin(), g->on_curve.end(), on_curve);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_text_pitch_labels(uint32_t octaves, const float* colors, pvq_text_label* out12) {
+    try {
+        if (!out12 || octaves == 0 || octaves > 255) {
+            pvq::set_last_error("text pitch labels: octaves is 1 .. 255 and out12 is needed");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        pvq::text_pitch_labels(octaves, colors, out12);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+namespace {
+pvq_status text_plans(const char* who, pvq_text_font* font, const pvq_text_label* labels, uint32_t n, uint32_t width, uint32_t height,
+                      float viewport_height, std::vector<pvq::TextLabelPlan>& plans) {
+    std::string err;
+    if (!pvq::stage_image_ok(who, width, height, viewport_height, err)) {
+        pvq::set_last_error(err);
+        return PVQ_ERR_INVALID_ARG;
+    }
+    const pvq_status st = pvq::text_plan(who, *font->impl, labels, n, width, height,
+                                         viewport_height == 0.0f ? pvq::raster::VIEWPORT_HEIGHT : viewport_height, plans, err);
+    if (st != PVQ_OK) pvq::set_last_error(err);
+    return st;
+}
+}  // namespace
+pvq_status pvq_text_layout_query(pvq_text_font* font, const pvq_text_label* labels, uint32_t n, uint32_t width, uint32_t height,
+                                 float viewport_height, pvq_text_layout* out_n) {
+    try {
+        if (!font) return null_handle();
+        if (!out_n) {
+            pvq::set_last_error("text layout: out_n is needed");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        std::vector<pvq::TextLabelPlan> plans;
+        if (pvq_status st = text_plans("text layout", font, labels, n, width, height, viewport_height, plans)) return st;
+        for (uint32_t l = 0; l < n; ++l) {
+            const pvq::TextLabelPlan& p = plans[l];
+            out_n[l] = pvq_text_layout{p.on_image ? 1u : 0u, p.x0, p.y0, p.x1, p.y1, p.on_image ? static_cast<uint32_t>(p.segments.size()) : 0u,
+                                       p.n_tiles(), p.origin_x, p.baseline_y};
+        }
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_text_frame(pvq_text_font* font, const pvq_text_label* labels, uint32_t n, uint32_t width, uint32_t height, float viewport_height,
+                          float* image_inout, float* coverage_out) {
+    try {
+        if (!font) return null_handle();
+        if (!image_inout && !coverage_out) {
+            pvq::set_last_error("text frame: image_inout or coverage_out is needed");
+            return PVQ_ERR_INVALID_ARG;
+        }
+        std::vector<pvq::TextLabelPlan> plans;
+        if (pvq_status st = text_plans("text frame", font, labels, n, width, height, viewport_height, plans)) return st;
+        pvq::text_frame(plans, width, height, image_inout, coverage_out);
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_text_batch_create(int device_id, pvq_text_font* font, const pvq_text_label* labels, uint32_t n, float viewport_height,
+                                 uint32_t width, uint32_t height, pvq_text_batch** out) {
+    try {
+        if (!out) return null_handle();
+        *out = nullptr;
+        if (!font) return null_handle();
+        std::unique_ptr<pvq::TextBatch> impl;
+        const pvq_status st = pvq::TextBatch::create(device_id, *font->impl, labels, n, viewport_height, width, height, impl);
+        if (st != PVQ_OK) return st;
+        *out = new pvq_text_batch{std::move(impl)};
+        return PVQ_OK;
+    } catch (...) { return translate_exception(); }
+}
+void pvq_text_batch_destroy(pvq_text_batch* b) {
+    try {
+        delete b;
+    } catch (...) { (void)translate_exception(); }
+}
+pvq_status pvq_text_batch_rows_device(pvq_text_batch* b, size_t n_rows, float* d_image_inout, void* stream) {
+    try {
+        if (!b) return null_handle();
+        return b->impl->rows_device(n_rows, d_image_inout, static_cast<hipStream_t>(stream));
+    } catch (...) { return translate_exception(); }
+}
+pvq_status pvq_text_batch_get_coverage(pvq_text_batch* b, int label, float* out) {
+    try {
+        if (!b) return null_handle();
+        return b->impl->get_coverage(label, out);
     } catch (...) { return translate_exception(); }
 }
 
