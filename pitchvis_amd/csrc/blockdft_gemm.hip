@@ -76,6 +76,9 @@ struct GemmTreeArgs {
     const float4* E16R;           // per group and column tile: [k < rem / 2][n < 16], as E16
     const float2* gen_tw;         // per group: phi_c = e^{-2 pi i c hop / W} and tau_c (see the kernel), n_tiles * 32 columns each
     int gen_kind;                 // 1: remainder tiles (R' -> Y, or -> X for windows shorter than the hop); 2: whole-block tiles (Q', combined, + tau R' -> X)
+#ifdef PVQ_DEV_KNOBS
+    int tree_tail;                // developer knob PVQ_TREE_TAIL: 0 = a tile's last tree levels as an LDS pass of their own before the store (the former epilogue)
+#endif
 };
 
 // which (group, row tile, column tile) a workgroup of the fused kernels owns
@@ -180,26 +183,18 @@ __device__ __forceinline__ void fused_tree_register_levels(float2 (*A)[CB_C + 1]
     __syncthreads();
 }
 
-template <int BM = FT_BM>   // BM rows, 2 * BM threads
-__device__ __forceinline__ void fused_tree_levels(float* smem, const float2 (*tw)[CB_C], const FusedTile& t, const GemmTreeArgs& a, int tid, int stamp_slot) {
-    float2 (*A)[FT_LDP] = reinterpret_cast<float2 (*)[FT_LDP]>(smem);  // [BM][33]
+constexpr int FT_REGL = 4;   // tree levels evaluated in registers; a tile has at most FT_MAXL - FT_REGL = 2 more (CB_MAX_NB = 64 blocks)
+#ifdef PVQ_DEV_KNOBS
+// PVQ_TREE_TAIL=0 (A/B, bit identity): the former epilogue — the levels past the register ones (strides >= 16) as a pass of their own
+// through LDS: read, barrier, write back, barrier; two levels in one pass, outputs in groups of four to bound the registers.  The
+// store then only copies.
+template <int BM>
+__device__ __forceinline__ void fused_tree_lds_levels(float2 (*A)[CB_C + 1], const float2 (*tw)[CB_C], int l, int levels, int tid) {
     const int c = tid & (CB_C - 1);
     constexpr int THREADS = 2 * BM;
     constexpr int PER = BM * CB_C / THREADS;  // 16
     auto cmadd = [](float2 lo, float2 w, float2 hi) { return tree_cmadd(lo, w, hi); };
-    const int levels = t.G.levels_f;
-    int l = levels < 4 ? levels : 4;
-    switch (l) {   // wave-uniform
-        case 1: fused_tree_register_levels<1, BM>(A, tw, tid); break;
-        case 2: fused_tree_register_levels<2, BM>(A, tw, tid); break;
-        case 3: fused_tree_register_levels<3, BM>(A, tw, tid); break;
-        case 4: fused_tree_register_levels<4, BM>(A, tw, tid); break;
-        default: break;
-    }
-    PVQ_STAMP(6);
     int valid = BM - ((1 << l) - 1);
-    // remaining levels (strides >= 16) through LDS, two per pass where possible: evaluated exactly as two radix-2
-    // levels (same operations in the same order), outputs in groups of four to bound the registers
     for (; l + 1 < levels; l += 2) {
         const int st = 1 << l;
         const float2 w1 = tw[l][c], w2 = tw[l + 1][c];
@@ -244,11 +239,40 @@ __device__ __forceinline__ void fused_tree_levels(float* smem, const float2 (*tw
         }
         __syncthreads();
     }
-    PVQ_STAMP(2);
 }
-// the tile's S complete frames to X (or Y): lanes walk the frames of one column: 512-byte runs in memory, conflict-free LDS reads
+#endif
+
+// the tree levels that leave their results in LDS: the register levels.  Returns how many levels (0, 1 or 2) the store still has to evaluate
+template <int BM = FT_BM>   // BM rows, 2 * BM threads
+__device__ __forceinline__ int fused_tree_levels(float* smem, const float2 (*tw)[CB_C], const FusedTile& t, const GemmTreeArgs& a, int tid, int stamp_slot) {
+    float2 (*A)[FT_LDP] = reinterpret_cast<float2 (*)[FT_LDP]>(smem);  // [BM][33]
+    const int levels = t.G.levels_f;
+    const int l = levels < FT_REGL ? levels : FT_REGL;
+    switch (l) {   // wave-uniform
+        case 1: fused_tree_register_levels<1, BM>(A, tw, tid); break;
+        case 2: fused_tree_register_levels<2, BM>(A, tw, tid); break;
+        case 3: fused_tree_register_levels<3, BM>(A, tw, tid); break;
+        case 4: fused_tree_register_levels<4, BM>(A, tw, tid); break;
+        default: break;
+    }
+    PVQ_STAMP(6);
+    int tail = levels - l;
+#ifdef PVQ_DEV_KNOBS
+    if (!a.tree_tail) {
+        fused_tree_lds_levels<BM>(A, tw, l, levels, tid);
+        tail = 0;
+    }
+#endif
+    PVQ_STAMP(2);
+    return tail;
+}
+// the tile's S complete frames to X (or Y): lanes walk the frames of one column: 512-byte runs in memory, conflict-free LDS reads.
+// The tile's last `tail` tree levels (strides 16, 32) are evaluated here, on the way from LDS to memory: row j of the result needs
+// rows j, j + 16 (, j + 32, j + 48) of the register levels' output in its own column, so no value has to change threads — no
+// write-back, no barrier and no second read.  The same calls in the same order as a level-by-level pass (two levels: exactly as two
+// radix-2 levels), the twiddles wave-uniform.  j < S = BM - nb_f + 1 keeps every read inside the tile's BM rows.
 template <int BM = FT_BM>
-__device__ __forceinline__ void fused_store_x(float* smem, const FusedTile& t, const GemmTreeArgs& a, int tid) {
+__device__ __forceinline__ void fused_store_x(float* smem, const float2 (*tw)[CB_C], const FusedTile& t, const GemmTreeArgs& a, int tid, int tail) {
     float2 (*A)[FT_LDP] = reinterpret_cast<float2 (*)[FT_LDP]>(smem);  // [BM][33]
     const int j = tid % BM;
     const int f = t.f0 + j;
@@ -257,17 +281,30 @@ __device__ __forceinline__ void fused_store_x(float* smem, const FusedTile& t, c
         const bool to_y = t.G.nb > t.G.nb_f;
         float2* dst = (to_y ? a.Y : a.X) + ((size_t)((f >> 6) + (to_y ? t.yt0 : t.xt0)) * a.xcp + t.nt * CB_C) * 64 + (f & 63);
         const int ncv = t.G.n_cols - t.ntl * CB_C < CB_C ? t.G.n_cols - t.ntl * CB_C : CB_C;   // the tile's real columns: the padding of a group's last tile is never read with a non-zero coefficient and never written (X starts out zeroed)
+        // streamed out (non-temporal): the kernel-product stage that reads X back runs 5 % faster for it
+        auto put = [&](int cc, float2 val) { __builtin_nontemporal_store((f32x2){val.x, val.y}, reinterpret_cast<f32x2*>(&dst[cc * 64])); };   // one 8-byte store
+        constexpr int st = 1 << FT_REGL;
+        if (tail == 2) {   // wave-uniform
 #pragma unroll 4
-        for (int cc = tid / BM; cc < ncv; cc += 2) {   // streamed out (non-temporal): the kernel-product stage that reads X back runs 5 % faster for it
-            const float2 val = A[j][cc];
-            __builtin_nontemporal_store((f32x2){val.x, val.y}, reinterpret_cast<f32x2*>(&dst[cc * 64]));   // one 8-byte store
+            for (int cc = tid / BM; cc < ncv; cc += 2) {
+                const float2 w1 = tw[FT_REGL][cc], w2 = tw[FT_REGL + 1][cc];
+                const float2 t0 = tree_cmadd(A[j][cc], w1, A[j + st][cc]);
+                const float2 t1 = tree_cmadd(A[j + 2 * st][cc], w1, A[j + 3 * st][cc]);
+                put(cc, tree_cmadd(t0, w2, t1));
+            }
+        } else if (tail == 1) {
+#pragma unroll 4
+            for (int cc = tid / BM; cc < ncv; cc += 2) put(cc, tree_cmadd(A[j][cc], tw[FT_REGL][cc], A[j + st][cc]));
+        } else {
+#pragma unroll 4
+            for (int cc = tid / BM; cc < ncv; cc += 2) put(cc, A[j][cc]);
         }
     }
 }
 template <int BM = FT_BM>
 __device__ __forceinline__ void fused_tree_store(float* smem, const float2 (*tw)[CB_C], const FusedTile& t, const GemmTreeArgs& a, int tid, int stamp_slot) {
-    fused_tree_levels<BM>(smem, tw, t, a, tid, stamp_slot);
-    fused_store_x<BM>(smem, t, a, tid);
+    const int tail = fused_tree_levels<BM>(smem, tw, t, a, tid, stamp_slot);
+    fused_store_x<BM>(smem, tw, t, a, tid, tail);
     if (a.stamps) {
         __builtin_amdgcn_s_waitcnt(0);   // stores issued and acknowledged
         __syncthreads();
@@ -1317,6 +1354,10 @@ pvq_status Vqt::launch_blockdft_gemm_fused(BlockLaunch& L, hipStream_t stream) {
     fa.E16R = t->d_E16R;
     fa.gen_tw = t->d_gen_tw;
     fa.gen_kind = 0;
+#ifdef PVQ_DEV_KNOBS
+    static const int tree_tail_env = dev_knob("PVQ_TREE_TAIL", 1);   // 0: the former epilogue (A/B, bit identity)
+    fa.tree_tail = tree_tail_env;
+#endif
     static const char* stamps_env = dev_knob_str("PVQ_STAMPS");   // dump per-tile phase stamps of the first launch
     static bool stamps_done = false;
     static int stamps_skip = dev_knob("PVQ_STAMPS_SKIP", 0);         // ... of launch n + 1 (a warm one)
