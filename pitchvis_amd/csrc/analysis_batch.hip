@@ -399,7 +399,7 @@ __global__ __launch_bounds__(256, NK <= 6 ? 4 : (NK <= 12 ? 3 : 2)) void ab_fram
     const float bpo_f = (float)a.bpo, n_f = (float)n;
 
     // one (stream, frame) row per wave, no loop over rows (the host launches a workgroup per 4 rows): a loop's hoisted invariants cost the
-    // lean peak kernel half its registers (vqt_engine.hip, peaks_frames_lean)
+    // lean peak kernel half its registers (peaks_frames.hip, peaks_frames_lean)
     const long long fr = (long long)blockIdx.x * 4 + wave;
     if (fr < rows) {
         const int s = (int)(fr / a.n_frames), f = (int)(fr - (long long)s * a.n_frames);
@@ -865,10 +865,8 @@ pvq_status AnalysisBatch::preprocess_device(const float* d_db, size_t n_frames, 
 #undef PVQ_AB_LAUNCH
         if (lst != PVQ_OK) return lst;
     }
-    // 3. the tuning inaccuracy's EMA, a thread per stream
+    // 3. the tuning inaccuracy's EMA, a wave per stream
     hipLaunchKernelGGL(ab_tuning, dim3((n_streams_ + 3) / 4), dim3(256), 0, stream, a);
-    pvq_status lst = PVQ_OK;
-    if (lst != PVQ_OK) return lst;
     PVQ_HIP(hipGetLastError());
     return PVQ_OK;
 }

@@ -5,7 +5,7 @@
 // preprocess() is a recurrence over frames — bin EMAs, calmness EMAs and the scene calmness feed the
 // next frame's smoothing horizons (analysis.rs:295-319, calmness.rs:23-95) — so it is sequential per
 // stream and lives on the host, consuming dB frames the GPU produced.  The batch-parallel, stateless
-// part of it (peaks of a frame with smoothing off) is the GPU peak kernel (peaks_device.hpp).
+// part of it (peaks of a frame with smoothing off) is the GPU peak kernels (peaks_frames.hip, peaks_device.hpp).
 #pragma once
 
 #include <cstddef>

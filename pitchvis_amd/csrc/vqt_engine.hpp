@@ -48,7 +48,7 @@ struct AnalysisParameters {
 struct DeviceTables;   // opaque (device_tables.hpp)
 struct PeakParamsDev;  // peaks_device.hpp
 struct BlockLaunch;    // blockdft_device.hpp
-struct FftArgs;        // vqt_engine.hip
+struct FftArgs;        // fft_path.hpp
 
 class Vqt {
    public:
@@ -117,6 +117,7 @@ class Vqt {
     // this call waits for `stream`, returns PVQ_ERR_NONFINITE_INPUT if the flag is up and clears it.  The synchronous
     // host-buffer entry points call it themselves.
     pvq_status input_status(hipStream_t stream);
+    pvq_status multi_buffers(const size_t (&bytes)[6], void* (&out)[6], hipStream_t* st);   // (used by analyze_batch_multi's workers)
 
     enum KernelSlot { SLOT_FFT_FRAMES = 0, SLOT_BLOCKDFT_GEMM = 1, SLOT_BLOCKDFT_COMBINE = 2, SLOT_BLOCKDFT_DOTS = 3, SLOT_PEAKS = 4, N_SLOTS = 5 };
     static const char* slot_name(uint32_t s);
@@ -131,7 +132,7 @@ class Vqt {
     pvq_status launch_fft_path(const float* d_pcm, size_t n_lead, size_t hop, size_t n_frames, float* d_out_db,
                                float* d_out_cplx, const PeakParamsDev* pk, hipStream_t stream);
     pvq_status launch_fft_streams(const void* st_table, size_t n_st, const float* d_pcm, size_t n_lead, size_t hop, size_t n_frames, size_t rows_total,
-                                  float* d_out_db, float* d_out_cplx, const PeakParamsDev* pk, hipStream_t stream);   // st_table: FftStream[n_st] (vqt_engine.hip) or null
+                                  float* d_out_db, float* d_out_cplx, const PeakParamsDev* pk, hipStream_t stream);   // st_table: FftStream[n_st] (fft_path.hpp) or null
     pvq_status launch_fft_groups(FftArgs& a, size_t n_frames, hipStream_t stream);   // the two forms of one launch of the FFT path
     pvq_status launch_fft_walk(FftArgs& a, int T, int grid, size_t lds, bool split, size_t n_frames, hipStream_t stream);
     bool blockdft_applicable(size_t hop) const;
@@ -152,12 +153,12 @@ class Vqt {
                                     float* d_out_db, float* d_out_cplx, const PeakParamsDev* pk, hipStream_t stream);
     pvq_status peaks_stage(const float* d_db, size_t n_frames, const PeakParamsDev& p, hipStream_t s);   // the peak kernels as the timed SLOT_PEAKS stage
     void slot_begin(int slot, hipStream_t s);
+    void slot_end(int slot, hipStream_t s);
     // One handle's calls are ORDERED: the workspaces (X, the group-split rows, staging buffers, tile-list slots, the peak kernels' redo
     // flags) belong to the handle, so a call on another stream than the previous call's — the single-frame route's own stream after an
     // asynchronous batch on the caller's, a pvq_stream's stream, a second user stream — first makes its stream wait (on the device, the
     // host does not block) for everything the previous call queued.  Calls that stay on one stream pay nothing.
     pvq_status order_on(hipStream_t s);
-    void slot_end(int slot, hipStream_t s);
 
     HostPlan plan_;
     int device_id_ = -1;
@@ -192,9 +193,6 @@ class Vqt {
     // the multi-device driver's per-handle shard buffers (PCM, dB, mask, count, center, size) and stream, grow-only
     DeviceBuffer multi_buf_[6];
     hipStream_t multi_stream_ = nullptr;
-   public:
-    pvq_status multi_buffers(const size_t (&bytes)[6], void* (&out)[6], hipStream_t* st);   // (used by analyze_batch_multi's workers)
-   private:
 };
 
 // One stream of host PCM analysed on several handles at once (one host thread per handle; handles may sit on different devices
@@ -205,7 +203,7 @@ pvq_status analyze_batch_multi(Vqt* const* handles, uint32_t n_handles, const fl
                                const AnalysisParameters& a, float* out_db, uint32_t* peak_mask, uint32_t* peak_count, float* center,
                                float* size, uint32_t max_peaks);
 
-// find_peaks over n_frames independent dB rows [n_frames][a.n_bins] (vqt_engine.hip; redo: n_frames bytes of device scratch)
+// find_peaks over n_frames independent dB rows [n_frames][a.n_bins] (peaks_frames.hip; redo: n_frames bytes of device scratch)
 pvq_status launch_peaks_frames(const float* d_db, size_t n_frames, const PeakParamsDev& a, uint8_t* redo, hipStream_t stream);
 
 }  // namespace pvq

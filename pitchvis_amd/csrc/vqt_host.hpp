@@ -2,7 +2,7 @@
 // VQT kernel.  Mirrors the public surface of pitchvis_analysis::vqt (reference file
 // pitchvis_analysis/src/vqt.rs): VqtRange / VqtParameters / VqtError / WindowGroup / VqtKernel.
 // Construction runs once per parameter set on one CPU thread (as in the reference); everything
-// per-frame runs on the GPU (vqt_engine.hip).
+// per-frame runs on the GPU (fft_path.hip, vqt_blockdft.hip, peaks_frames.hip; the handle that routes a call: vqt_engine.hip).
 #pragma once
 
 #include <cstddef>

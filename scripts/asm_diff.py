@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the compiled device code of two source trees, kernel by kernel (no GPU needed).
 
-    scripts/asm_diff.py OLD_TREE NEW_TREE [UNIT.hip ...]
+    scripts/asm_diff.py [--by-name] OLD_TREE NEW_TREE [UNIT.hip ...]
 
 The units are every *.hip under pitchvis_amd/csrc that either tree has, or the ones named (the block-DFT path alone:
 vqt_blockdft.hip blockdft_gemm.hip blockdft_dots.hip).  Each is compiled with the
@@ -10,7 +10,11 @@ function bodies as tests/test_kernel_resources.py cuts it (label `_ZN3pvq...:` t
 labels (.LBB<n>_, .Ltmp<n>, .Lfunc_begin<n>, and the BB<n>_ of the loop comments) are replaced by a fixed string — they move when a
 kernel before this one leaves the unit — together with the padding between a label and its comment, which follows the counter's
 width; nothing else is normalised.  Prints, per flavour, the (unit, name) pairs on either side and whether each body is equal;
-exits 1 if any body that both trees have differs, or if the two sides' names differ."""
+exits 1 if any body that both trees have differs, or if the two sides' names differ.
+
+--by-name keys a body by its mangled name alone, for a change that moves kernels from one unit to another (a unit split): keyed by
+(unit, name) a moved kernel shows up as "only in old" and "only in new" and is never compared.  In that mode a name that occurs in
+two units of one tree is an error (which of the two bodies would be the kernel's?); the unit printed is the new tree's."""
 import hashlib
 import os
 import re
@@ -60,15 +64,33 @@ def bodies(tree, units, dev, tmp):
     return out
 
 
+def by_name(tree, out):
+    """(unit, name) -> body as name -> (unit, body); exits if two units of the tree hold one name"""
+    named = {}
+    for (unit, name), body in sorted(out.items()):
+        if name in named:
+            sys.exit("%s: kernel %s occurs in two units, %s and %s" % (tree, name, named[name][0], unit))
+        named[name] = (unit, body)
+    return named
+
+
 def main():
-    old, new = sys.argv[1:3]
-    units = sys.argv[3:] or sorted({f for t in (old, new) for f in os.listdir(csrc_of(t)) if f.endswith(".hip")})
+    args = sys.argv[1:]
+    named = "--by-name" in args
+    args = [a for a in args if a != "--by-name"]
+    old, new = args[:2]
+    units = args[2:] or sorted({f for t in (old, new) for f in os.listdir(csrc_of(t)) if f.endswith(".hip")})
     differ = 0
     with tempfile.TemporaryDirectory() as tmp:
         for dev in (False, True):
             a, b = bodies(old, units, dev, tmp), bodies(new, units, dev, tmp)
+            if named:   # both sides under the unit the new tree has the kernel in (the old tree's, for a name only the old tree has)
+                an, bn = by_name(old, a), by_name(new, b)
+                a = {((bn.get(n) or an[n])[0], n): body for n, (_, body) in an.items()}
+                b = {(unit, n): body for n, (unit, body) in bn.items()}
             differ += set(a) != set(b)
             print("== %s build: old %d kernels, new %d kernels" % ("dev (-DPVQ_DEV_KNOBS)" if dev else "prod", len(a), len(b)))
+            print("new tree, kernels per unit: %s" % ", ".join("%s %d" % (u, sum(k[0] == u for k in b)) for u in units if os.path.exists(os.path.join(csrc_of(new), u))))
             print("only in old: %s" % sorted(set(a) - set(b)))
             print("only in new: %s" % sorted(set(b) - set(a)))
             for k in sorted(set(a) & set(b)):

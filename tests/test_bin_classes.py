@@ -181,7 +181,7 @@ def test_kernel_product_thresholds_match_the_restatement():
 
 
 def test_peak_thresholds_match_the_restatement():
-    s = _src("vqt_engine.hip")
+    s = _src("peaks_frames.hip")
     body = s[s.index("pvq_status launch_peaks_frames("):]
     body = body[:body.index("\n}\n")]
     for flag in ("true", "false"):
@@ -217,7 +217,7 @@ def test_analysis_batch_thresholds_match_the_restatement():
 def test_fft_epilogue_thresholds_match_the_restatement():
     """the dB epilogue of T threads holds max(4, 1024 / T) bins per thread; above 1 024 bins the FFT path takes 512 or 1 024
     threads per frame (db_rows_batch<1024> behind the batch kernels), beyond 4 096 it refuses"""
-    s = _src("vqt_engine.hip")
+    s = _src("fft_path.hip")
     assert "constexpr int PER = 1024 / T < 4 ? 4 : 1024 / T;" in s
     m = re.search(r"constexpr int FFT_MAX_BINS = (\d+);", s)
     assert m and int(m.group(1)) == FFT_DB[-1][0]

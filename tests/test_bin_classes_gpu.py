@@ -6,7 +6,7 @@ fixed register count, `__builtin_assume`):
   kernel product + dB, block-DFT fp32   blockdft_dots.hip  <= 256 lds260 | 257-304 lds308 | 305-368 lds372 | 369-592 lds596 |
                                                            593-848 lds852 | 849-1020 lds1028 | 1021-1024 db1x8 (banddots_db<1, 8>)
   the same, split-bf16 GEMM             blockdft_dots.hip  <= 256 bf2x4 | 257-1024 bf1x4
-  peaks (launch_peaks_frames)           vqt_engine.hip     lean kernel NK in {4, 5, 6, 8, 10, 12, 16} x DENSE (n > 64 (NK - 1)) x DIST
+  peaks (launch_peaks_frames)           peaks_frames.hip   lean kernel NK in {4, 5, 6, 8, 10, 12, 16} x DENSE (n > 64 (NK - 1)) x DIST
                                                            (min_distance > 1); the generic kernel behind it <4/8/12/16>
   AnalysisBatch                         analysis_batch.hip ab_recurrence<NK, DENSE>, ab_frames<NK, DIST, DENSE>, NK in {4, 6, 8, 10, 12, 16}
 

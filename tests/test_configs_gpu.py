@@ -357,7 +357,7 @@ def test_tile_shapes_bit_identical_in_subprocesses():
 def test_fft_batch_kernels_equal_the_walk_in_subprocesses():
     """The FFT path's batch form (vqt_fft_group: one kernel instantiation per window size, round 5) against the walk (vqt_fft_frames, which the
     developer library keeps for batches too with PVQ_FFT_CT=0): the same bits on every test geometry, at a power-of-two hop and at an odd one
-    (735 = pitchvis_serial's cadence at 22 050 Hz), stream start included.  Both forms share every arithmetic helper and vqt_engine.hip
+    (735 = pitchvis_serial's cadence at 22 050 Hz), stream start included.  Both forms share every arithmetic helper and fft_path.hip
     compiles with FMA contraction off (fused multiply-adds are written where wanted), so this holds by construction; the test keeps it so.
     (tests/test_handles_gpu.py::test_few_frames_on_the_fft_path_equal_the_same_frames_of_a_batch compares the few-frames forms of the walk with
     the batch form in one process.)"""
