@@ -1359,6 +1359,101 @@ float pvq_vqt_last_sclk_mhz(pvq_vqt *v);
 uint32_t pvq_vqt_last_frames_per_launch(const pvq_vqt *v);
 const char *pvq_vqt_kernel_name(uint32_t slot);
 
+/* ---- the synth stage: SoundFont voices rendered for many streams ---------------------------------------------------
+ * The first link of the trainer's chain (pitchvis_train/src/train.rs:252-351): MIDI-style events -> rustysynth_fork -> left / right
+ * PCM and the active voices whose keys become the targets.  The work splits at the 64-sample block.  The CONTROL rate (once per
+ * voice and block: both envelopes, both LFOs, pitch, filter coefficients, mix gains, and every decision about which voices exist)
+ * runs on the host and emits a PLAN: per block the records of the voices that sound, in the reference's active-list order, which is
+ * the order of the sum.  The AUDIO rate (oscillator.rs:112-176, bi_quad_filter.rs:77-99, synthesizer.rs:478-495) replays the plan,
+ * on the host (pvq_synth_state_render) and on the device (pvq_synth_batch_render_device) with one copy of the arithmetic: integer
+ * ops and unfused IEEE f32 in the written order, so both give the same bits.
+ * Left out: reverb and chorus (synthesizer.rs:393-475) — this is the reference with enable_reverb_and_chorus = false, while
+ * train.rs:264 uses the default (on), so the dry rows are not yet the trainer's exact PCM; SF2 and MIDI file parsing (arrays in);
+ * play_loop; polyphony above 64; block sizes other than 64; the control rate on the device. */
+#define PVQ_SYNTH_GENERATORS 61 /* generator_type.rs:71 */
+#define PVQ_SYNTH_BLOCK 64      /* SynthesizerSettings::DEFAULT_BLOCK_SIZE */
+/* One sounding voice in one block (64 bytes).  flags: 1 started since its last record (position := start, filter memory cleared),
+ * 2 looping, 4 filter active, 8 a sample without a loop ends inside this block. */
+typedef struct pvq_synth_record {
+    uint32_t voice;              /* the voice object 0 .. maximum_polyphony - 1 */
+    uint32_t flags;
+    uint32_t ratio_lo, ratio_hi; /* pitch_ratio_fp, i64 (oscillator.rs:103) */
+    float a[5];                  /* BiQuadFilter a0 .. a4 */
+    float gain[4];               /* previous left, current left, previous right, current right, times master_volume */
+    uint32_t desc;               /* the instrument region whose sample points a started voice reads */
+    int32_t key;
+    uint32_t stage;              /* volume envelope stage 0 delay 1 attack 2 hold 3 decay 4 release */
+} pvq_synth_record;
+/* replaces SoundFont::new (soundfont.rs) after parsing.  wave_data [n_wave] int16; samples [n_samples][7] = start, end, start_loop,
+ * end_loop, sample_rate, original_pitch, pitch_correction (sample_header.rs); instrument_gs [n_instrument_regions][61]: a region's
+ * generators after the defaults and its zones (instrument_region.rs:39-66), instrument_sample [n_instrument_regions] its sample;
+ * instruments [n_instruments][2] = first region, regions; preset_gs [n_preset_regions][61] (preset_region.rs:32-42),
+ * preset_instrument its instrument; presets [n_presets][4] = bank, patch, first region, regions.  PVQ_ERR_INVALID_ARG names the
+ * first bad index: a sample or instrument id out of range (the reference's InvalidSampleId / InvalidInstrumentId), a region range
+ * past its array, a sample point (with the region's address offsets) outside 0 .. n_wave, a sample rate that is not positive, an original pitch
+ * outside 0 .. 255 or a pitch correction outside -128 .. 127 (the file's u8 and i8). */
+typedef struct pvq_synth_bank pvq_synth_bank;
+pvq_status pvq_synth_bank_create(const int16_t *wave_data, size_t n_wave, const int32_t *samples, uint32_t n_samples,
+                                 const int16_t *instrument_gs, const uint32_t *instrument_sample, uint32_t n_instrument_regions,
+                                 const uint32_t *instruments, uint32_t n_instruments, const int16_t *preset_gs,
+                                 const uint32_t *preset_instrument, uint32_t n_preset_regions, const int32_t *presets, uint32_t n_presets,
+                                 pvq_synth_bank **out);
+void pvq_synth_bank_destroy(pvq_synth_bank *b);   /* handles made from it keep their own reference */
+/* out4: wave values, instrument regions, preset regions, presets */
+pvq_status pvq_synth_bank_counts(const pvq_synth_bank *b, uint64_t *out4);
+/* replaces Synthesizer::new + MidiFileSequencer (synthesizer.rs:58-174, midifile_sequencer.rs) for ONE stream on the host.
+ * sample_rate 16 000 .. 192 000 and maximum_polyphony 8 .. 256 as synthesizer_settings.rs:35-57 (its texts); above 64:
+ * PVQ_ERR_UNSUPPORTED. */
+typedef struct pvq_synth_state pvq_synth_state;
+pvq_status pvq_synth_state_create(const pvq_synth_bank *bank, int32_t sample_rate, uint32_t maximum_polyphony, pvq_synth_state **out);
+void pvq_synth_state_destroy(pvq_synth_state *s);
+/* replaces MidiFileSequencer::render (midifile_sequencer.rs:52-104) over n_blocks blocks: left / right [n_blocks * 64].  The five
+ * event arrays [n_events] are the stream's WHOLE list (times in seconds, ascending; channel, command, data1, data2 each 0 .. 255,
+ * Synthesizer::process_midi_message's arguments, synthesizer.rs:176-213); the state keeps how many it has consumed, so calls
+ * continue one another and a render in several calls equals one call.  Before each block every event with time <= current_time is
+ * applied, and current_time grows by the repeated f64 addition of 64 / sample_rate.  snapshot_blocks [n_snapshots] (ascending
+ * block numbers of this call, may be NULL with 0): the active voices after that block, for pvq_synth_state_get_snapshots.
+ * Where the reference would panic on a read outside wave_data (a loop shorter than the pitch step: oscillator.rs:155-172), the call
+ * ends with PVQ_ERR_INVALID_ARG naming stream, block and key before a sample is made; the state is then no longer usable. */
+pvq_status pvq_synth_state_render(pvq_synth_state *s, const double *time_s, const int32_t *channel, const int32_t *command,
+                                  const int32_t *data1, const int32_t *data2, size_t n_events, size_t n_blocks,
+                                  const uint32_t *snapshot_blocks, size_t n_snapshots, float *left, float *right);
+/* replaces Synthesizer::get_active_voices (synthesizer.rs:525; key, current_mix_gain_left, current_mix_gain_right of voice.rs:38-48)
+ * after each snapshot block of the last render: out_counts [0] snapshots taken, [1] voices in all.  voice_ptr [ptr_capacity] (at
+ * least snapshots + 1) indexes key / gain_left / gain_right [capacity]; any of them may be NULL to ask for the counts alone.
+ * These are pvq_train_rows' voice arrays. */
+pvq_status pvq_synth_state_get_snapshots(const pvq_synth_state *s, uint32_t *out_counts, uint32_t *voice_ptr, size_t ptr_capacity,
+                                         int32_t *key, float *gain_left, float *gain_right, size_t capacity);
+/* the plan of the last render: out_counts [0] blocks, [1] records.  block_ptr [ptr_capacity] (at least blocks + 1) indexes
+ * records [capacity]; NULL to ask for the counts alone. */
+pvq_status pvq_synth_state_get_plan(const pvq_synth_state *s, uint32_t *out_counts, uint32_t *block_ptr, size_t ptr_capacity,
+                                    pvq_synth_record *records, size_t capacity);
+uint32_t pvq_synth_state_active_voices(const pvq_synth_state *s);   /* VoiceCollection::active_voice_count */
+/* The same for MANY streams: the planner on the host (at most 16 threads), the audio rate on the device, a wavefront per stream
+ * and a lane per voice object.  device_id < 0: a host-only handle whose render returns PVQ_ERR_NO_DEVICE after its argument checks. */
+typedef struct pvq_synth_batch pvq_synth_batch;
+pvq_status pvq_synth_batch_create(int device_id, const pvq_synth_bank *bank, uint32_t n_streams, int32_t sample_rate,
+                                  uint32_t maximum_polyphony, pvq_synth_batch **out);
+void pvq_synth_batch_destroy(pvq_synth_batch *b);
+/* pvq_synth_state_render for every stream: event_ptr [n_streams + 1] indexes the five event arrays (stream s owns
+ * [event_ptr[s], event_ptr[s + 1]), its whole list); n_blocks [n_streams]; d_left / d_right are HOST arrays of n_streams DEVICE
+ * pointers to rows of n_blocks[s] * 64 floats (4-byte aligned; nothing past them is written; a stream without events gets zeros):
+ * what pvq_agc_batch_condition_device takes.  snapshot_blocks is shared by the streams.  Every lane's position and filter memory
+ * stay on the device and every stream's control state on the host between calls.  The planner runs before anything is launched:
+ * its PVQ_ERR_INVALID_ARG (see pvq_synth_state_render) leaves the rows untouched and the handle unusable.  Asynchronous on
+ * `stream`; the calls of one handle go to one stream. */
+pvq_status pvq_synth_batch_render_device(pvq_synth_batch *b, const uint64_t *event_ptr, const double *time_s, const int32_t *channel,
+                                         const int32_t *command, const int32_t *data1, const int32_t *data2, const size_t *n_blocks,
+                                         float *const *d_left, float *const *d_right, const uint32_t *snapshot_blocks,
+                                         size_t n_snapshots, void *stream);
+/* What the last render cost, in ms: out_ms4 [0] the planner's host time, [1] the host time spent laying the plan out for the upload,
+ * [2] the device time of the upload, [3] of the replay kernel (waits for the call's end); out_records (may be NULL): the
+ * voice-blocks it replayed. */
+pvq_status pvq_synth_batch_last_times(pvq_synth_batch *b, float *out_ms4, uint64_t *out_records);
+/* pvq_synth_state_get_snapshots for stream `stream_index` of the last render (host data: does not synchronise) */
+pvq_status pvq_synth_batch_get_snapshots(const pvq_synth_batch *b, uint32_t stream_index, uint32_t *out_counts, uint32_t *voice_ptr,
+                                         size_t ptr_capacity, int32_t *key, float *gain_left, float *gain_right, size_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,9 @@ EXPORTS = [
     "pvq_text_batch_rows_device", "pvq_text_batch_get_coverage",
     "pvq_present_default_settings", "pvq_present_mips", "pvq_present_blend_factors", "pvq_present_frame", "pvq_present_batch_create",
     "pvq_present_batch_destroy", "pvq_present_batch_set_workspace_limit", "pvq_present_batch_rows_device",
+    "pvq_synth_bank_create", "pvq_synth_bank_destroy", "pvq_synth_bank_counts", "pvq_synth_state_create", "pvq_synth_state_destroy",
+    "pvq_synth_state_render", "pvq_synth_state_get_snapshots", "pvq_synth_state_get_plan", "pvq_synth_state_active_voices",
+    "pvq_synth_batch_create", "pvq_synth_batch_destroy", "pvq_synth_batch_render_device", "pvq_synth_batch_get_snapshots", "pvq_synth_batch_last_times",
     "pvq_note_model_create", "pvq_note_model_destroy", "pvq_note_model_sizes", "pvq_note_model_infer", "pvq_note_model_rows_device",
     "pvq_note_model_set_workspace_limit",
     "pvq_note_trainer_hyper_default", "pvq_note_trainer_create", "pvq_note_trainer_destroy", "pvq_note_trainer_step", "pvq_note_trainer_steps",
@@ -166,6 +169,11 @@ class CTextLabel(C.Structure):   # pvq_text_label
 class CTextLayout(C.Structure):   # pvq_text_layout
     _fields_ = [("on_image", C.c_uint32), ("x0", C.c_uint32), ("y0", C.c_uint32), ("x1", C.c_uint32), ("y1", C.c_uint32), ("n_segments", C.c_uint32),
                 ("n_tiles", C.c_uint32), ("origin_x", C.c_float), ("baseline_y", C.c_float)]
+
+
+class CSynthRecord(C.Structure):   # pvq_synth_record
+    _fields_ = [("voice", C.c_uint32), ("flags", C.c_uint32), ("ratio_lo", C.c_uint32), ("ratio_hi", C.c_uint32), ("a", C.c_float * 5),
+                ("gain", C.c_float * 4), ("desc", C.c_uint32), ("key", C.c_int32), ("stage", C.c_uint32)]
 
 
 class CNoteModelParams(C.Structure):   # pvq_note_model_params
@@ -435,6 +443,26 @@ def load():
     L.pvq_present_batch_destroy.argtypes = [vp]; L.pvq_present_batch_destroy.restype = None
     L.pvq_present_batch_set_workspace_limit.argtypes = [vp, C.c_uint64]; L.pvq_present_batch_set_workspace_limit.restype = C.c_int
     L.pvq_present_batch_rows_device.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp]; L.pvq_present_batch_rows_device.restype = C.c_int
+    i16p, i32p, u64p, dp_ = C.POINTER(C.c_int16), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_double)
+    L.pvq_synth_bank_create.argtypes = [i16p, C.c_size_t, i32p, C.c_uint32, i16p, up, C.c_uint32, up, C.c_uint32, i16p, up, C.c_uint32, i32p, C.c_uint32,
+                                        C.POINTER(vp)]
+    L.pvq_synth_bank_create.restype = C.c_int
+    L.pvq_synth_bank_destroy.argtypes = [vp]; L.pvq_synth_bank_destroy.restype = None
+    L.pvq_synth_bank_counts.argtypes = [vp, u64p]; L.pvq_synth_bank_counts.restype = C.c_int
+    L.pvq_synth_state_create.argtypes = [vp, C.c_int32, C.c_uint32, C.POINTER(vp)]; L.pvq_synth_state_create.restype = C.c_int
+    L.pvq_synth_state_destroy.argtypes = [vp]; L.pvq_synth_state_destroy.restype = None
+    L.pvq_synth_state_render.argtypes = [vp, dp_, i32p, i32p, i32p, i32p, C.c_size_t, C.c_size_t, up, C.c_size_t, fp, fp]
+    L.pvq_synth_state_render.restype = C.c_int
+    L.pvq_synth_state_get_snapshots.argtypes = [vp, up, up, C.c_size_t, i32p, fp, fp, C.c_size_t]; L.pvq_synth_state_get_snapshots.restype = C.c_int
+    L.pvq_synth_state_get_plan.argtypes = [vp, up, up, C.c_size_t, C.POINTER(CSynthRecord), C.c_size_t]; L.pvq_synth_state_get_plan.restype = C.c_int
+    L.pvq_synth_state_active_voices.argtypes = [vp]; L.pvq_synth_state_active_voices.restype = C.c_uint32
+    L.pvq_synth_batch_create.argtypes = [C.c_int, vp, C.c_uint32, C.c_int32, C.c_uint32, C.POINTER(vp)]; L.pvq_synth_batch_create.restype = C.c_int
+    L.pvq_synth_batch_destroy.argtypes = [vp]; L.pvq_synth_batch_destroy.restype = None
+    L.pvq_synth_batch_render_device.argtypes = [vp, u64p, dp_, i32p, i32p, i32p, i32p, szp, C.POINTER(vp), C.POINTER(vp), up, C.c_size_t, vp]
+    L.pvq_synth_batch_render_device.restype = C.c_int
+    L.pvq_synth_batch_get_snapshots.argtypes = [vp, C.c_uint32, up, up, C.c_size_t, i32p, fp, fp, C.c_size_t]
+    L.pvq_synth_batch_get_snapshots.restype = C.c_int
+    L.pvq_synth_batch_last_times.argtypes = [vp, fp, u64p]; L.pvq_synth_batch_last_times.restype = C.c_int
     L.pvq_note_model_create.argtypes = [C.c_int, C.POINTER(CNoteModelParams), C.POINTER(CNoteModelWeights), C.POINTER(vp)]
     L.pvq_note_model_create.restype = C.c_int
     L.pvq_note_model_destroy.argtypes = [vp]

@@ -3,6 +3,7 @@
 * ``MonoAgc``                        — dagc_fork/src/lib.rs:19-87
 * ``train_dataset`` / ``write_npy``  — pitchvis_train/src/train.rs:252-351, 443-460, 192-208 (frames on the GPU)
 * ``AgcBatch`` / ``train_dataset_streams`` — the same for many rendered streams at once (train.rs:146-163), conditioned on the device
+* ``train_dataset_from_events``      — the same from MIDI-style events on: the voices rendered on the device too (synth.py)
 * ``Stream``                         — the pitchvis_audio RingBuffer contract with a device-resident ring
 * ``calculate_color`` / ``led_frame``— pitchvis_colors/src/lib.rs:86-117, pitchvis_serial/src/main.rs:122-175
 * ``spectrogram_row`` / ``chroma_row`` — pitchvis_viewer/src/display_system/update.rs:961-1065, 1102-1131 (one AnalysisState, host)
@@ -199,6 +200,44 @@ def train_dataset_streams(vqt, lefts, rights, voices, step: int = STEP_SIZE_IN_C
         vqt.input_status()   # (waits; raises on a non-finite sample like pvq_train_frames_db)
         db = d_db.cpu().numpy()
         gains = d_gain.cpu().numpy()
+    return [_train_rows(L, vqt.n_bins, np.ascontiguousarray(db[s, :n_frames[s]]), gains[s, :n_chunks[s]], voices[s], step) for s in range(n)]
+
+
+def train_dataset_from_events(vqt, bank, events, n_chunks, step: int = STEP_SIZE_IN_CHUNKS, maximum_polyphony: int = 64):
+    """``train_dataset_streams`` with the first link on the device too (train.rs:252-351 from the MIDI events on): every stream's
+    events are planned on the host and its voices rendered on the device (``SynthBatch``, the synthesizer's dry path) into left /
+    right rows that go straight to ``AgcBatch.condition_device``; the active voices after every analysed chunk (train.rs:317-337)
+    become the targets.  No PCM crosses to the host.  ``events[s]``: stream s's ``(time_s, channel, command, data1, data2)``;
+    ``n_chunks``: chunks to render, one count or one per stream.  Returns one flat row array per stream, laid out as
+    ``train_dataset``'s."""
+    import torch
+    from .synth import BLOCK, SynthBatch
+    L = _lib.load()
+    n = len(events)
+    if n == 0:
+        return []
+    chunk = train_chunk_samples(vqt)
+    assert chunk % BLOCK == 0   # train.rs:128-129
+    n_chunks = [int(n_chunks)] * n if np.isscalar(n_chunks) else [int(x) for x in n_chunks]
+    n_frames = [nc // step for nc in n_chunks]
+    max_chunks, max_frames = max(max(n_chunks), 1), max(max(n_frames), 1)
+    per_chunk = chunk // BLOCK
+    dev = torch.device("cuda", vqt.device)
+    with torch.cuda.device(dev):
+        synth = SynthBatch(bank, n, int(vqt.params().sr), maximum_polyphony, device=vqt.device)
+        d_l = [torch.empty(max(nc * chunk, 1), dtype=torch.float32, device=dev) for nc in n_chunks]
+        d_r = [torch.empty(max(nc * chunk, 1), dtype=torch.float32, device=dev) for nc in n_chunks]
+        snapshot_blocks = [(f + 1) * step * per_chunk - 1 for f in range(max_frames)]
+        synth.render(events, [nc * per_chunk for nc in n_chunks], d_l, d_r, snapshot_blocks=snapshot_blocks)
+        agc = AgcBatch(n, 0.07, 0.001, device=vqt.device)   # train.rs:265
+        d_gain = torch.zeros((n, max_chunks), dtype=torch.float32, device=dev)
+        agc.condition_device(d_l, d_r, n_chunks, chunk, d_gain_out=d_gain)   # in place: d_l now holds the conditioned mono streams
+        d_db = torch.empty((n, max_frames, vqt.n_bins), dtype=torch.float32, device=dev)
+        vqt.batch_streams_device(d_l, chunk * step, n_frames, d_db, out_stride_frames=max_frames)
+        vqt.input_status()
+        db = d_db.cpu().numpy()
+        gains = d_gain.cpu().numpy()
+    voices = [synth.snapshots(s)[:n_frames[s]] for s in range(n)]
     return [_train_rows(L, vqt.n_bins, np.ascontiguousarray(db[s, :n_frames[s]]), gains[s, :n_chunks[s]], voices[s], step) for s in range(n)]
 
 
