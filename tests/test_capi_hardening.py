@@ -4,6 +4,7 @@ instead of aborting the host process; std::bad_alloc / std::length_error / anyth
 is caught at the boundary and becomes PVQ_ERR_INTERNAL."""
 import ctypes as C
 import os
+import re
 import subprocess
 import sys
 import textwrap
@@ -56,6 +57,65 @@ def test_exceptions_stop_at_the_abi(what, text):
     assert r.returncode == 0, r.stderr[-1500:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("STATUS")][0]
     assert line.startswith(f"STATUS {_lib.PVQ_ERR_INTERNAL} |") and text in line and line.endswith("False")
+
+
+def _declarations():
+    """(return type, name, [parameter texts]) of every function include/pvq.h declares, and the opaque handle types."""
+    text = open(os.path.join(ROOT, "include", "pvq.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    handles = set(re.findall(r"typedef\s+struct\s+(pvq_\w+)\s+\1\s*;", text))
+    decls = []
+    for ret, name, params in re.findall(r"^((?:const\s+)?\w+\s*\**)\s*\b(pvq_\w+)\s*\(([^;{}]*)\)\s*;", text, flags=re.M):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        decls.append(("".join(ret.split()), name, [] if params == ["void"] else params))
+    return decls, handles
+
+
+def _zeros(fn):
+    assert fn.argtypes is not None, "every declared function has a ctypes prototype"
+    return [t() for t in fn.argtypes]
+
+
+def test_constructors_refuse_a_null_out_and_destructors_take_null():
+    """Every constructor tests `out` before anything else: with a zero for every argument it answers PVQ_ERR_INVALID_ARG and
+    "null handle".  Every destructor takes NULL, as free() does."""
+    L = _lib.load()
+    decls, _ = _declarations()
+    makers = [n for _, n, _ in decls if n.endswith("_create") or n in ("pvq_text_font_from_ttf", "pvq_text_font_from_outlines")]
+    breakers = [n for _, n, _ in decls if n.endswith("_destroy")]
+    assert len(makers) >= 24 and len(breakers) >= 23, (len(makers), len(breakers))
+    for name in makers:
+        fn = getattr(L, name)
+        assert fn(*_zeros(fn)) == _lib.PVQ_ERR_INVALID_ARG, name
+        assert L.pvq_last_error() == b"null handle", name
+    for name in breakers:
+        fn = getattr(L, name)
+        fn(*_zeros(fn))
+
+
+def test_every_function_refuses_a_null_handle():
+    """Every function whose first parameter is a handle tests it first: with NULL there and zeros elsewhere a pvq_status function
+    answers PVQ_ERR_INVALID_ARG, a getter its zero (PVQ_ALGO_AUTO for the two pvq_algo ones), a void function returns."""
+    L = _lib.load()
+    decls, handles = _declarations()
+    assert len(handles) == 23, sorted(handles)
+    n = 0
+    for ret, name, params in decls:
+        m = params and re.fullmatch(r"(?:const )?(pvq_\w+) ?\* ?\w+", params[0])
+        if not m or m.group(1) not in handles:
+            continue
+        fn = getattr(L, name)
+        got = fn(*_zeros(fn))
+        n += 1
+        if ret == "pvq_status":
+            assert got == _lib.PVQ_ERR_INVALID_ARG, name
+        elif ret == "pvq_algo":
+            assert got == P.ALGO_AUTO, name
+        elif ret != "void":
+            assert ret in ("uint32_t", "uint64_t", "size_t", "int", "float", "double"), (name, ret)
+            assert got == 0, name
+    assert n >= 130, n
 
 
 def test_null_and_range_arguments_return_statuses():
