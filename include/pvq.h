@@ -1367,11 +1367,18 @@ const char *pvq_vqt_kernel_name(uint32_t slot);
  * the order of the sum.  The AUDIO rate (oscillator.rs:112-176, bi_quad_filter.rs:77-99, synthesizer.rs:478-495) replays the plan,
  * on the host (pvq_synth_state_render) and on the device (pvq_synth_batch_render_device) with one copy of the arithmetic: integer
  * ops and unfused IEEE f32 in the written order, so both give the same bits.
- * Left out: reverb and chorus (synthesizer.rs:393-475) — this is the reference with enable_reverb_and_chorus = false, while
- * train.rs:264 uses the default (on), so the dry rows are not yet the trainer's exact PCM; SF2 and MIDI file parsing (arrays in);
- * play_loop; polyphony above 64; block sizes other than 64; the control rate on the device. */
+ * The plain create entries give the reference with enable_reverb_and_chorus = false (the dry path).  train.rs:264 uses the
+ * reference's default (on): the _ex entries with PVQ_SYNTH_EFFECTS add reverb and chorus (synthesizer.rs:393-475, reverb.rs,
+ * chorus.rs), and the rows are then the trainer's exact PCM.  With effects the control rate also gives every record its chorus and
+ * reverb gains (pvq_synth_sends), and the audio rate adds three more sums per block (chorus input left / right, reverb input), the
+ * chorus (no feedback: a function of present and past inputs), the reverb (8 combs in parallel, whose filter_store is the one
+ * recurrence from sample to sample, then 4 all-passes in series, per channel) and dry + 0.5 chorus + 0.5 reverb.  The effect state
+ * of a stream (24 reverb buffers, 2 chorus rings: 51 KB at 22 050 Hz, 443 KB at 192 000) starts at zero and lives in the handle.
+ * Left out: SF2 and MIDI file parsing (arrays in); play_loop; polyphony above 64; block sizes other than 64; the control rate on
+ * the device. */
 #define PVQ_SYNTH_GENERATORS 61 /* generator_type.rs:71 */
 #define PVQ_SYNTH_BLOCK 64      /* SynthesizerSettings::DEFAULT_BLOCK_SIZE */
+#define PVQ_SYNTH_EFFECTS 1u    /* flag of the _ex create entries: enable_reverb_and_chorus (synthesizer_settings.rs) */
 /* One sounding voice in one block (64 bytes).  flags: 1 started since its last record (position := start, filter memory cleared),
  * 2 looping, 4 filter active, 8 a sample without a loop ends inside this block. */
 typedef struct pvq_synth_record {
@@ -1384,6 +1391,13 @@ typedef struct pvq_synth_record {
     int32_t key;
     uint32_t stage;              /* volume envelope stage 0 delay 1 attack 2 hold 3 decay 4 release */
 } pvq_synth_record;
+/* The effect gains of one record (32 bytes), parallel to the records of a plan made with PVQ_SYNTH_EFFECTS.  The mix gains in them
+ * are NOT times master_volume (synthesizer.rs:404-415, 449-454). */
+typedef struct pvq_synth_sends {
+    float chorus[4];             /* previous left, current left, previous right, current right: chorus send * mix gain */
+    float reverb[2];             /* previous, current: (0.015 * reverb send) * (mix gain left + mix gain right) */
+    uint32_t pad[2];
+} pvq_synth_sends;
 /* replaces SoundFont::new (soundfont.rs) after parsing.  wave_data [n_wave] int16; samples [n_samples][7] = start, end, start_loop,
  * end_loop, sample_rate, original_pitch, pitch_correction (sample_header.rs); instrument_gs [n_instrument_regions][61]: a region's
  * generators after the defaults and its zones (instrument_region.rs:39-66), instrument_sample [n_instrument_regions] its sample;
@@ -1406,6 +1420,10 @@ pvq_status pvq_synth_bank_counts(const pvq_synth_bank *b, uint64_t *out4);
  * PVQ_ERR_UNSUPPORTED. */
 typedef struct pvq_synth_state pvq_synth_state;
 pvq_status pvq_synth_state_create(const pvq_synth_bank *bank, int32_t sample_rate, uint32_t maximum_polyphony, pvq_synth_state **out);
+/* the same with flags: 0 is exactly pvq_synth_state_create; PVQ_SYNTH_EFFECTS adds reverb and chorus; any other bit:
+ * PVQ_ERR_INVALID_ARG */
+pvq_status pvq_synth_state_create_ex(const pvq_synth_bank *bank, int32_t sample_rate, uint32_t maximum_polyphony, uint32_t flags,
+                                     pvq_synth_state **out);
 void pvq_synth_state_destroy(pvq_synth_state *s);
 /* replaces MidiFileSequencer::render (midifile_sequencer.rs:52-104) over n_blocks blocks: left / right [n_blocks * 64].  The five
  * event arrays [n_events] are the stream's WHOLE list (times in seconds, ascending; channel, command, data1, data2 each 0 .. 255,
@@ -1428,12 +1446,20 @@ pvq_status pvq_synth_state_get_snapshots(const pvq_synth_state *s, uint32_t *out
  * records [capacity]; NULL to ask for the counts alone. */
 pvq_status pvq_synth_state_get_plan(const pvq_synth_state *s, uint32_t *out_counts, uint32_t *block_ptr, size_t ptr_capacity,
                                     pvq_synth_record *records, size_t capacity);
+/* the sends of the last render's plan, shaped like pvq_synth_state_get_plan: out_counts [0] blocks, [1] sends (one per record).
+ * A state made without PVQ_SYNTH_EFFECTS has none: both counts are 0. */
+pvq_status pvq_synth_state_get_sends(const pvq_synth_state *s, uint32_t *out_counts, uint32_t *block_ptr, size_t ptr_capacity,
+                                     pvq_synth_sends *sends, size_t capacity);
 uint32_t pvq_synth_state_active_voices(const pvq_synth_state *s);   /* VoiceCollection::active_voice_count */
 /* The same for MANY streams: the planner on the host (at most 16 threads), the audio rate on the device, a wavefront per stream
  * and a lane per voice object.  device_id < 0: a host-only handle whose render returns PVQ_ERR_NO_DEVICE after its argument checks. */
 typedef struct pvq_synth_batch pvq_synth_batch;
 pvq_status pvq_synth_batch_create(int device_id, const pvq_synth_bank *bank, uint32_t n_streams, int32_t sample_rate,
                                   uint32_t maximum_polyphony, pvq_synth_batch **out);
+/* the same with flags, as pvq_synth_state_create_ex.  With PVQ_SYNTH_EFFECTS the handle also owns every stream's effect state on
+ * the device, zeroed here, and its render replays the plan with a second kernel. */
+pvq_status pvq_synth_batch_create_ex(int device_id, const pvq_synth_bank *bank, uint32_t n_streams, int32_t sample_rate,
+                                     uint32_t maximum_polyphony, uint32_t flags, pvq_synth_batch **out);
 void pvq_synth_batch_destroy(pvq_synth_batch *b);
 /* pvq_synth_state_render for every stream: event_ptr [n_streams + 1] indexes the five event arrays (stream s owns
  * [event_ptr[s], event_ptr[s + 1]), its whole list); n_blocks [n_streams]; d_left / d_right are HOST arrays of n_streams DEVICE
@@ -1453,6 +1479,19 @@ pvq_status pvq_synth_batch_last_times(pvq_synth_batch *b, float *out_ms4, uint64
 /* pvq_synth_state_get_snapshots for stream `stream_index` of the last render (host data: does not synchronise) */
 pvq_status pvq_synth_batch_get_snapshots(const pvq_synth_batch *b, uint32_t stream_index, uint32_t *out_counts, uint32_t *voice_ptr,
                                          size_t ptr_capacity, int32_t *key, float *gain_left, float *gain_right, size_t capacity);
+/* Reverb + Chorus alone (Reverb::new, Chorus::new(sample_rate, 0.002, 0.0019, 0.4): synthesizer.rs:102-126) on the host, fed with
+ * chosen inputs: the code the host face's effect path runs.  sample_rate as pvq_synth_state_create's. */
+typedef struct pvq_synth_effects_s pvq_synth_effects;
+pvq_status pvq_synth_effects_create(int32_t sample_rate, pvq_synth_effects **out);
+void pvq_synth_effects_destroy(pvq_synth_effects *e);
+/* Chorus::process and Reverb::process over n_blocks * 64 samples: the chorus inputs left / right and the (mono) reverb input in,
+ * the chorus outputs left / right and the reverb outputs left / right out.  The state goes on from call to call. */
+pvq_status pvq_synth_effects_process(pvq_synth_effects *e, size_t n_blocks, const float *chorus_in_left, const float *chorus_in_right,
+                                     const float *reverb_in, float *chorus_out_left, float *chorus_out_right, float *reverb_out_left,
+                                     float *reverb_out_right);
+/* the chorus delay table (chorus.rs:24-29): returns its length, round(sample_rate / 0.4), and fills out [capacity] when it is
+ * large enough (out may be NULL); 0 for a sample rate outside 16 000 .. 192 000 */
+uint32_t pvq_synth_chorus_table(int32_t sample_rate, float *out, size_t capacity);
 
 #ifdef __cplusplus
 }

@@ -638,7 +638,7 @@ class AnalysisState:
         return float(self._L.pvq_analysis_state_tuning_grid_inaccuracy(self._h))
 
 from .consumers import AgcBatch, MonoAgc, PinnedArray, RenderBatch, Stream, calculate_color, chroma_row, led_frame, spectrogram_row, train_chunk_samples, train_dataset, train_dataset_from_events, train_dataset_streams, write_npy  # noqa: E402,F401
-from .synth import SynthBank, SynthBatch, SynthState  # noqa: E402,F401
+from .synth import SynthBank, SynthBatch, SynthEffects, SynthState, chorus_table  # noqa: E402,F401
 from .scene import SceneBatch, SceneState  # noqa: E402,F401
 from .raster import RasterBatch, raster_frame, raster_shade, raster_touch  # noqa: E402,F401
 from .backdrop import BackdropBatch, backdrop_draw_mesh, backdrop_frame, backdrop_geometry, panel_transforms  # noqa: E402,F401

@@ -57,6 +57,8 @@ EXPORTS = [
     "pvq_synth_bank_create", "pvq_synth_bank_destroy", "pvq_synth_bank_counts", "pvq_synth_state_create", "pvq_synth_state_destroy",
     "pvq_synth_state_render", "pvq_synth_state_get_snapshots", "pvq_synth_state_get_plan", "pvq_synth_state_active_voices",
     "pvq_synth_batch_create", "pvq_synth_batch_destroy", "pvq_synth_batch_render_device", "pvq_synth_batch_get_snapshots", "pvq_synth_batch_last_times",
+    "pvq_synth_state_create_ex", "pvq_synth_batch_create_ex", "pvq_synth_state_get_sends", "pvq_synth_effects_create", "pvq_synth_effects_destroy",
+    "pvq_synth_effects_process", "pvq_synth_chorus_table",
     "pvq_note_model_create", "pvq_note_model_destroy", "pvq_note_model_sizes", "pvq_note_model_infer", "pvq_note_model_rows_device",
     "pvq_note_model_set_workspace_limit",
     "pvq_note_trainer_hyper_default", "pvq_note_trainer_create", "pvq_note_trainer_destroy", "pvq_note_trainer_step", "pvq_note_trainer_steps",
@@ -174,6 +176,10 @@ class CTextLayout(C.Structure):   # pvq_text_layout
 class CSynthRecord(C.Structure):   # pvq_synth_record
     _fields_ = [("voice", C.c_uint32), ("flags", C.c_uint32), ("ratio_lo", C.c_uint32), ("ratio_hi", C.c_uint32), ("a", C.c_float * 5),
                 ("gain", C.c_float * 4), ("desc", C.c_uint32), ("key", C.c_int32), ("stage", C.c_uint32)]
+
+
+class CSynthSends(C.Structure):   # pvq_synth_sends
+    _fields_ = [("chorus", C.c_float * 4), ("reverb", C.c_float * 2), ("pad", C.c_uint32 * 2)]
 
 
 class CNoteModelParams(C.Structure):   # pvq_note_model_params
@@ -463,6 +469,14 @@ def load():
     L.pvq_synth_batch_get_snapshots.argtypes = [vp, C.c_uint32, up, up, C.c_size_t, i32p, fp, fp, C.c_size_t]
     L.pvq_synth_batch_get_snapshots.restype = C.c_int
     L.pvq_synth_batch_last_times.argtypes = [vp, fp, u64p]; L.pvq_synth_batch_last_times.restype = C.c_int
+    L.pvq_synth_state_create_ex.argtypes = [vp, C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(vp)]; L.pvq_synth_state_create_ex.restype = C.c_int
+    L.pvq_synth_batch_create_ex.argtypes = [C.c_int, vp, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.pvq_synth_batch_create_ex.restype = C.c_int
+    L.pvq_synth_state_get_sends.argtypes = [vp, up, up, C.c_size_t, C.POINTER(CSynthSends), C.c_size_t]; L.pvq_synth_state_get_sends.restype = C.c_int
+    L.pvq_synth_effects_create.argtypes = [C.c_int32, C.POINTER(vp)]; L.pvq_synth_effects_create.restype = C.c_int
+    L.pvq_synth_effects_destroy.argtypes = [vp]; L.pvq_synth_effects_destroy.restype = None
+    L.pvq_synth_effects_process.argtypes = [vp, C.c_size_t, fp, fp, fp, fp, fp, fp, fp]; L.pvq_synth_effects_process.restype = C.c_int
+    L.pvq_synth_chorus_table.argtypes = [C.c_int32, fp, C.c_size_t]; L.pvq_synth_chorus_table.restype = C.c_uint32
     L.pvq_note_model_create.argtypes = [C.c_int, C.POINTER(CNoteModelParams), C.POINTER(CNoteModelWeights), C.POINTER(vp)]
     L.pvq_note_model_create.restype = C.c_int
     L.pvq_note_model_destroy.argtypes = [vp]

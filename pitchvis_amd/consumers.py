@@ -203,13 +203,13 @@ def train_dataset_streams(vqt, lefts, rights, voices, step: int = STEP_SIZE_IN_C
     return [_train_rows(L, vqt.n_bins, np.ascontiguousarray(db[s, :n_frames[s]]), gains[s, :n_chunks[s]], voices[s], step) for s in range(n)]
 
 
-def train_dataset_from_events(vqt, bank, events, n_chunks, step: int = STEP_SIZE_IN_CHUNKS, maximum_polyphony: int = 64):
+def train_dataset_from_events(vqt, bank, events, n_chunks, step: int = STEP_SIZE_IN_CHUNKS, maximum_polyphony: int = 64, effects: bool = False):
     """``train_dataset_streams`` with the first link on the device too (train.rs:252-351 from the MIDI events on): every stream's
     events are planned on the host and its voices rendered on the device (``SynthBatch``, the synthesizer's dry path) into left /
     right rows that go straight to ``AgcBatch.condition_device``; the active voices after every analysed chunk (train.rs:317-337)
     become the targets.  No PCM crosses to the host.  ``events[s]``: stream s's ``(time_s, channel, command, data1, data2)``;
     ``n_chunks``: chunks to render, one count or one per stream.  Returns one flat row array per stream, laid out as
-    ``train_dataset``'s."""
+    ``train_dataset``'s.  ``effects=True``: the synthesizer's reverb and chorus too, the trainer's own setting (train.rs:264)."""
     import torch
     from .synth import BLOCK, SynthBatch
     L = _lib.load()
@@ -224,7 +224,7 @@ def train_dataset_from_events(vqt, bank, events, n_chunks, step: int = STEP_SIZE
     per_chunk = chunk // BLOCK
     dev = torch.device("cuda", vqt.device)
     with torch.cuda.device(dev):
-        synth = SynthBatch(bank, n, int(vqt.params().sr), maximum_polyphony, device=vqt.device)
+        synth = SynthBatch(bank, n, int(vqt.params().sr), maximum_polyphony, device=vqt.device, effects=effects)
         d_l = [torch.empty(max(nc * chunk, 1), dtype=torch.float32, device=dev) for nc in n_chunks]
         d_r = [torch.empty(max(nc * chunk, 1), dtype=torch.float32, device=dev) for nc in n_chunks]
         snapshot_blocks = [(f + 1) * step * per_chunk - 1 for f in range(max_frames)]

@@ -32,6 +32,7 @@ class TextBatch;
 class SynthBank;
 class SynthState;
 class SynthBatch;
+class SynthEffects;
 class PresentBatch;
 class PanelsBatch;
 class NoteModel;
@@ -91,6 +92,9 @@ struct pvq_synth_state {
 };
 struct pvq_synth_batch {
     std::unique_ptr<pvq::SynthBatch> impl;
+};
+struct pvq_synth_effects_s {
+    std::unique_ptr<pvq::SynthEffects> impl;
 };
 struct pvq_present_batch {
     std::unique_ptr<pvq::PresentBatch> impl;

@@ -9,10 +9,41 @@
 
 extern "C" {
 
-// The synthesizer (rustysynth_fork, dry path): the bank, one stream on the host (synth_host.hpp) and many on the device
-// (synth_batch.hpp)
+// The synthesizer (rustysynth_fork; the dry path, or with PVQ_SYNTH_EFFECTS its reverb and chorus too): the bank, one stream on the
+// host (synth_host.hpp) and many on the device (synth_batch.hpp), and the effects alone on the host
 namespace {
 static_assert(sizeof(pvq_synth_record) == sizeof(pvq::synth::Record), "one layout");
+static_assert(sizeof(pvq_synth_sends) == sizeof(pvq::synth::Sends), "one layout");
+pvq_status synth_flags(uint32_t flags, bool& effects) {
+    if (flags & ~static_cast<uint32_t>(PVQ_SYNTH_EFFECTS)) return invalid_arg("synth: unknown flag bits (PVQ_SYNTH_EFFECTS is the only flag)");
+    effects = (flags & PVQ_SYNTH_EFFECTS) != 0;
+    return PVQ_OK;
+}
+pvq_status synth_state_make(const pvq_synth_bank* bank, int32_t sample_rate, uint32_t maximum_polyphony, uint32_t flags, pvq_synth_state** out) {
+    if (!out) return null_handle();
+    *out = nullptr;
+    if (!bank) return null_handle();
+    bool effects = false;
+    if (pvq_status st = synth_flags(flags, effects)) return st;
+    std::unique_ptr<pvq::SynthState> impl;
+    std::string err;
+    const pvq_status st = pvq::SynthState::create(bank->impl, sample_rate, maximum_polyphony, impl, err, effects);   // synthesizer.rs:58-174
+    if (st != PVQ_OK) {
+        pvq::set_last_error(err);
+        return st;
+    }
+    *out = new pvq_synth_state{std::move(impl)};
+    return PVQ_OK;
+}
+pvq_status synth_batch_make(int device_id, const pvq_synth_bank* bank, uint32_t n_streams, int32_t sample_rate, uint32_t maximum_polyphony, uint32_t flags,
+                            pvq_synth_batch** out) {
+    return make_handle(out, [&](auto& impl) {
+        if (!bank) return null_handle();
+        bool effects = false;
+        if (pvq_status st = synth_flags(flags, effects)) return st;
+        return pvq::SynthBatch::create(device_id, bank->impl, n_streams, sample_rate, maximum_polyphony, impl, effects);   // synthesizer.rs:58-174
+    });
+}
 pvq_status synth_snapshots_out(const pvq::SynthPlan& p, uint32_t* out_counts, uint32_t* voice_ptr, size_t ptr_capacity, int32_t* key, float* gain_left,
                                float* gain_right, size_t capacity) {
     const size_t n_snap = p.snapshot_ptr.empty() ? 0 : p.snapshot_ptr.size() - 1, n_voices = p.snapshots.size();
@@ -64,20 +95,10 @@ pvq_status pvq_synth_bank_counts(const pvq_synth_bank* b, uint64_t* out4) {
     });
 }
 pvq_status pvq_synth_state_create(const pvq_synth_bank* bank, int32_t sample_rate, uint32_t maximum_polyphony, pvq_synth_state** out) {
-    return guarded([&] {
-        if (!out) return null_handle();
-        *out = nullptr;
-        if (!bank) return null_handle();
-        std::unique_ptr<pvq::SynthState> impl;
-        std::string err;
-        const pvq_status st = pvq::SynthState::create(bank->impl, sample_rate, maximum_polyphony, impl, err);   // synthesizer.rs:58-174
-        if (st != PVQ_OK) {
-            pvq::set_last_error(err);
-            return st;
-        }
-        *out = new pvq_synth_state{std::move(impl)};
-        return PVQ_OK;
-    });
+    return guarded([&] { return synth_state_make(bank, sample_rate, maximum_polyphony, 0, out); });
+}
+pvq_status pvq_synth_state_create_ex(const pvq_synth_bank* bank, int32_t sample_rate, uint32_t maximum_polyphony, uint32_t flags, pvq_synth_state** out) {
+    return guarded([&] { return synth_state_make(bank, sample_rate, maximum_polyphony, flags, out); });
 }
 void pvq_synth_state_destroy(pvq_synth_state* s) { destroy(s); }
 pvq_status pvq_synth_state_render(pvq_synth_state* s, const double* time_s, const int32_t* channel, const int32_t* command, const int32_t* data1,
@@ -117,6 +138,25 @@ pvq_status pvq_synth_state_get_plan(const pvq_synth_state* s, uint32_t* out_coun
         return PVQ_OK;
     });
 }
+pvq_status pvq_synth_state_get_sends(const pvq_synth_state* s, uint32_t* out_counts, uint32_t* block_ptr, size_t ptr_capacity, pvq_synth_sends* sends,
+                                     size_t capacity) {
+    return guarded([&] {
+        if (!s) return null_handle();
+        const pvq::SynthPlan& p = s->impl->last_plan();
+        const bool fx = s->impl->effects();
+        const size_t n_blocks = !fx || p.block_ptr.empty() ? 0 : p.block_ptr.size() - 1, n_sends = fx ? p.sends.size() : 0;
+        if (out_counts) {
+            out_counts[0] = static_cast<uint32_t>(n_blocks);
+            out_counts[1] = static_cast<uint32_t>(n_sends);
+        }
+        if (!block_ptr && !sends) return PVQ_OK;
+        if (!block_ptr || !sends || ptr_capacity < n_blocks + 1 || capacity < n_sends)
+            return invalid_arg("synth sends: block_ptr of blocks + 1 entries and sends of as many as the plan holds are needed");
+        for (size_t k = 0; k <= n_blocks; ++k) block_ptr[k] = fx && !p.block_ptr.empty() ? p.block_ptr[k] : 0u;
+        if (n_sends) std::memcpy(sends, p.sends.data(), n_sends * sizeof(pvq_synth_sends));
+        return PVQ_OK;
+    });
+}
 uint32_t pvq_synth_state_active_voices(const pvq_synth_state* s) {
     return guarded(0, [&] {
         return s ? s->impl->active_voice_count() : 0;   // voice_collection.rs:11
@@ -124,12 +164,11 @@ uint32_t pvq_synth_state_active_voices(const pvq_synth_state* s) {
 }
 pvq_status pvq_synth_batch_create(int device_id, const pvq_synth_bank* bank, uint32_t n_streams, int32_t sample_rate, uint32_t maximum_polyphony,
                                   pvq_synth_batch** out) {
-    return guarded([&] {
-        return make_handle(out, [&](auto& impl) {
-            if (!bank) return null_handle();
-            return pvq::SynthBatch::create(device_id, bank->impl, n_streams, sample_rate, maximum_polyphony, impl);   // synthesizer.rs:58-174
-        });
-    });
+    return guarded([&] { return synth_batch_make(device_id, bank, n_streams, sample_rate, maximum_polyphony, 0, out); });
+}
+pvq_status pvq_synth_batch_create_ex(int device_id, const pvq_synth_bank* bank, uint32_t n_streams, int32_t sample_rate, uint32_t maximum_polyphony,
+                                     uint32_t flags, pvq_synth_batch** out) {
+    return guarded([&] { return synth_batch_make(device_id, bank, n_streams, sample_rate, maximum_polyphony, flags, out); });
 }
 void pvq_synth_batch_destroy(pvq_synth_batch* b) { destroy(b); }
 pvq_status pvq_synth_batch_render_device(pvq_synth_batch* b, const uint64_t* event_ptr, const double* time_s, const int32_t* channel,
@@ -163,6 +202,40 @@ pvq_status pvq_synth_batch_get_snapshots(const pvq_synth_batch* b, uint32_t stre
         const pvq::SynthPlan* p = b->impl->plan_of(stream_index);
         if (!p) return invalid_arg("synth batch: stream_index is 0 .. n_streams - 1");
         return synth_snapshots_out(*p, out_counts, voice_ptr, ptr_capacity, key, gain_left, gain_right, capacity);   // synthesizer.rs:525
+    });
+}
+pvq_status pvq_synth_effects_create(int32_t sample_rate, pvq_synth_effects** out) {
+    return guarded([&] {
+        return make_handle(out, [&](auto& impl) {
+            std::string err;
+            const pvq_status st = pvq::SynthEffects::create(sample_rate, impl, err);   // Reverb::new, Chorus::new (synthesizer.rs:102-126)
+            if (st != PVQ_OK) pvq::set_last_error(err);
+            return st;
+        });
+    });
+}
+void pvq_synth_effects_destroy(pvq_synth_effects* e) { destroy(e); }
+pvq_status pvq_synth_effects_process(pvq_synth_effects* e, size_t n_blocks, const float* chorus_in_left, const float* chorus_in_right, const float* reverb_in,
+                                     float* chorus_out_left, float* chorus_out_right, float* reverb_out_left, float* reverb_out_right) {
+    return guarded([&] {
+        if (!e) return null_handle();
+        if (n_blocks > 0x7fffffffull / pvq::synth::BLOCK) return invalid_arg("synth effects: too many blocks in one call");
+        if (n_blocks && !(chorus_in_left && chorus_in_right && reverb_in && chorus_out_left && chorus_out_right && reverb_out_left && reverb_out_right))
+            return invalid_arg("synth effects: the three inputs and the four outputs are needed");
+        e->impl->process(n_blocks, chorus_in_left, chorus_in_right, reverb_in, chorus_out_left, chorus_out_right, reverb_out_left,
+                         reverb_out_right);   // Chorus::process, Reverb::process
+        return PVQ_OK;
+    });
+}
+uint32_t pvq_synth_chorus_table(int32_t sample_rate, float* out, size_t capacity) {
+    return guarded(0u, [&]() -> uint32_t {
+        if (sample_rate < 16000 || sample_rate > 192000) {
+            pvq::set_last_error("The sample rate must be between 16000 and 192000, but was " + std::to_string(sample_rate) + ".");
+            return 0;
+        }
+        const std::vector<float> table = pvq::synth_chorus_table(sample_rate);   // chorus.rs:24-29
+        if (out && capacity >= table.size()) std::memcpy(out, table.data(), table.size() * sizeof(float));
+        return static_cast<uint32_t>(table.size());
     });
 }
 

@@ -11,7 +11,12 @@
 //      write_block skips (synthesizer.rs:485), which is the host replay's sum; one coalesced 256-byte store per row and channel.
 // No lane walks a global row: rows are only ever written 64 consecutive dwords at a time.  FMA contraction is off (synth_math.hpp),
 // f32 subnormals are kept, the i64 -> f32 conversion is the correctly rounded one on both sides.
+//
+// With effects the plan and its sends are replayed by synth_replay_fx, a unit of its own (synth_fx_batch.hip): this unit keeps its
+// one kernel, its code path and its resources.
 #include "synth_batch.hpp"
+
+#include "synth_device.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -21,24 +26,6 @@
 namespace pvq {
 
 namespace {
-constexpr int LDT = synth::BLOCK + 1;   // dwords of a tile row
-
-struct SynthStream {
-    float* left;
-    float* right;
-    uint32_t n_blocks;
-    uint32_t ptr_base;   // the stream's first entry of block_ptr
-};
-
-struct SynthArgs {
-    const SynthStream* tab;         // [gridDim.x]
-    const uint32_t* block_ptr;      // per stream [n_blocks + 1]: indices into records
-    const uint4* records;           // four pieces a record
-    const int16_t* wave;
-    const synth::SampleDesc* descs;
-    uint4* lanes;                   // [gridDim.x][2][64]
-};
-
 __global__ __launch_bounds__(64) void synth_replay(SynthArgs a) {
 #pragma clang fp contract(off)
     __shared__ uint4 s_rec[64 * 4];
@@ -108,7 +95,7 @@ SynthBatch::~SynthBatch() {
 }
 
 pvq_status SynthBatch::create(int device_id, std::shared_ptr<const SynthBank> bank, uint32_t n_streams, int32_t sample_rate, uint32_t maximum_polyphony,
-                              std::unique_ptr<SynthBatch>& out) {
+                              std::unique_ptr<SynthBatch>& out, bool effects) {
     out.reset();
     if (n_streams == 0) {
         set_last_error("synth batch: zero streams");
@@ -118,15 +105,24 @@ pvq_status SynthBatch::create(int device_id, std::shared_ptr<const SynthBank> ba
     b->device_id_ = device_id < 0 ? -1 : device_id;
     b->n_streams_ = n_streams;
     b->bank_ = bank;
+    b->effects_ = effects;
     b->states_.resize(n_streams);
     b->plans_.resize(n_streams);
     std::string err;
     for (uint32_t s = 0; s < n_streams; ++s) {
-        if (pvq_status st = SynthState::create(bank, sample_rate, maximum_polyphony, b->states_[s], err)) {
+        if (pvq_status st = SynthState::create(bank, sample_rate, maximum_polyphony, b->states_[s], err, effects, true)) {
             set_last_error(err);
             return st;
         }
         b->plans_[s].clear();
+    }
+    std::unique_ptr<SynthEffects> fx;   // the layout and the table, and the check of the table's bounds: before any device is touched
+    if (effects) {
+        if (pvq_status st = SynthEffects::create(sample_rate, fx, err)) {
+            set_last_error(err);
+            return st;
+        }
+        b->master_volume_ = b->states_[0]->master_volume();
     }
     if (device_id >= 0) {
         PVQ_HIP(hipSetDevice(device_id));
@@ -138,6 +134,18 @@ pvq_status SynthBatch::create(int device_id, std::shared_ptr<const SynthBank> ba
         if (pvq_status st = b->lanes_.reserve(lane_bytes)) return st;
         PVQ_HIP(hipMemset(b->lanes_.as<void>(), 0, lane_bytes));
         if (pvq_status st = b->tab_.reserve(n_streams * sizeof(SynthStream))) return st;
+        if (effects) {
+            const synth::FxLayout& l = fx->layout();
+            if (pvq_status st = b->fx_layout_.upload(&l, sizeof l)) return st;
+            if (pvq_status st = b->fx_table_.upload(fx->table().data(), fx->table().size() * sizeof(float))) return st;
+            const size_t sizes[4] = {static_cast<size_t>(n_streams) * l.total * sizeof(float), static_cast<size_t>(n_streams) * 2 * synth::FX_COMBS * sizeof(float),
+                                     static_cast<size_t>(n_streams) * 2 * l.ring * sizeof(float), static_cast<size_t>(n_streams) * sizeof(unsigned long long)};
+            DeviceBuffer* const bufs[4] = {&b->fx_reverb_, &b->fx_store_, &b->fx_ring_, &b->fx_count_};
+            for (int k = 0; k < 4; ++k) {
+                if (pvq_status st = bufs[k]->reserve(sizes[k])) return st;
+                PVQ_HIP(hipMemset(bufs[k]->as<void>(), 0, sizes[k]));
+            }
+        }
         PVQ_HIP(hipDeviceSynchronize());
     }
     out = std::move(b);
@@ -217,6 +225,9 @@ pvq_status SynthBatch::render_device(const SynthEvents* events, const size_t* n_
     std::vector<synth::Record>& records = h_records_;
     records.clear();
     records.reserve(std::max<size_t>(total_records, 1));
+    std::vector<synth::Sends>& sends = h_sends_;
+    sends.clear();
+    if (effects_) sends.reserve(std::max<size_t>(total_records, 1));
     for (uint32_t s = 0; s < n_streams_; ++s) {
         const SynthPlan& p = plans_[s];
         tab[s] = SynthStream{d_left[s], d_right[s], static_cast<uint32_t>(n_blocks[s]), static_cast<uint32_t>(block_ptr.size())};
@@ -229,8 +240,18 @@ pvq_status SynthBatch::render_device(const SynthEvents* events, const size_t* n_
             block_ptr.push_back(base + p.block_ptr[b]);
         }
         records.insert(records.end(), p.records.begin(), p.records.end());
+        if (effects_) {
+            if (p.sends.size() != p.records.size()) {
+                set_last_error("synth batch: a plan whose sends do not match its records");
+                return PVQ_ERR_INTERNAL;
+            }
+            sends.insert(sends.end(), p.sends.begin(), p.sends.end());
+        }
     }
     if (records.empty()) records.push_back(synth::Record{});
+    if (effects_ && sends.empty()) sends.push_back(synth::Sends{});
+    if (effects_)
+        if (pvq_status st = sends_.reserve(sends.size() * sizeof(synth::Sends))) return st;
     if (pvq_status st = block_ptr_.reserve(block_ptr.size() * sizeof(uint32_t))) return st;
     if (pvq_status st = records_.reserve(records.size() * sizeof(synth::Record))) return st;
     stage_ms_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
@@ -246,8 +267,23 @@ pvq_status SynthBatch::render_device(const SynthEvents* events, const size_t* n_
     a.wave = wave_.as<int16_t>();
     a.descs = descs_.as<synth::SampleDesc>();
     a.lanes = lanes_.as<uint4>();
+    if (effects_) PVQ_HIP(hipMemcpyAsync(sends_.as<void>(), sends.data(), sends.size() * sizeof(synth::Sends), hipMemcpyHostToDevice, stream));
     PVQ_HIP(hipEventRecord(uploaded_, stream));
-    hipLaunchKernelGGL(synth_replay, dim3(n_streams_), dim3(64), 0, stream, a);
+    if (effects_) {
+        SynthFxArgs fa{};
+        fa.dry = a;
+        fa.sends = sends_.as<uint4>();
+        fa.layout = fx_layout_.as<uint32_t>();
+        fa.table = fx_table_.as<float>();
+        fa.reverb = fx_reverb_.as<float>();
+        fa.store = fx_store_.as<float>();
+        fa.ring = fx_ring_.as<float>();
+        fa.count = fx_count_.as<unsigned long long>();
+        fa.master_volume = master_volume_;
+        launch_synth_replay_fx(fa, n_streams_, stream);
+    } else {
+        hipLaunchKernelGGL(synth_replay, dim3(n_streams_), dim3(64), 0, stream, a);
+    }
     PVQ_HIP(hipGetLastError());
     PVQ_HIP(hipEventRecord(ended_, stream));
     timed_ = true;

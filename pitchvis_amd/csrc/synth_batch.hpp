@@ -4,6 +4,8 @@
 // record order, so left / right rows carry the bits of SynthState::render.  The rows stay in device memory: they are what
 // AgcBatch::condition_device takes.  Between calls the handle keeps every lane's position and filter memory on the device and every
 // stream's control state on the host: a render in two calls equals one call.
+// With effects (enable_reverb_and_chorus: synth_fx_math.hpp) a second kernel replays the plan and its sends, and the handle also owns
+// every stream's effect state on the device: the 24 reverb buffers, the 16 filter stores, the two chorus rings and a sample count.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -24,7 +26,7 @@ class SynthBatch {
     // The arguments are checked before any device is touched (SynthState::create's checks and texts; n_streams >= 1).
     // device_id < 0: a host-only object whose render_device returns PVQ_ERR_NO_DEVICE after the argument checks.
     static pvq_status create(int device_id, std::shared_ptr<const SynthBank> bank, uint32_t n_streams, int32_t sample_rate, uint32_t maximum_polyphony,
-                             std::unique_ptr<SynthBatch>& out);
+                             std::unique_ptr<SynthBatch>& out, bool effects = false);
     ~SynthBatch();
     uint32_t n_streams() const { return n_streams_; }
     // events / n_blocks [n_streams]; d_left / d_right: HOST arrays of n_streams device pointers to rows of n_blocks[s] * 64 floats
@@ -45,12 +47,15 @@ class SynthBatch {
     int device_id_ = -1;
     uint32_t n_streams_ = 0;
     bool broken_ = false;
+    bool effects_ = false;
+    float master_volume_ = 0.5f;
     std::shared_ptr<const SynthBank> bank_;
     std::vector<std::unique_ptr<SynthState>> states_;
     std::vector<SynthPlan> plans_;
     std::vector<unsigned char> h_tab_;        // what the running call uploads: alive until the next call has waited for `uploaded_`
     std::vector<uint32_t> h_block_ptr_;
     std::vector<synth::Record> h_records_;
+    std::vector<synth::Sends> h_sends_;
     hipEvent_t uploaded_ = nullptr, began_ = nullptr, ended_ = nullptr;   // around the upload and the kernel of the running call
     float plan_ms_ = 0.0f, stage_ms_ = 0.0f;
     bool timed_ = false;
@@ -61,6 +66,14 @@ class SynthBatch {
     DeviceBuffer tab_;       // [n_streams] stream descriptors of the running call
     DeviceBuffer block_ptr_; // grow-only: every stream's [n_blocks + 1] record indices
     DeviceBuffer records_;   // grow-only: every stream's records
+    DeviceBuffer sends_;     // grow-only: every stream's sends (effects)
+    // effects: one allocation per kind, zeroed at create
+    DeviceBuffer fx_layout_; // synth::FxLayout
+    DeviceBuffer fx_table_;  // the chorus delay table
+    DeviceBuffer fx_reverb_; // [n_streams][layout.total]
+    DeviceBuffer fx_store_;  // [n_streams][16]
+    DeviceBuffer fx_ring_;   // [n_streams][2][layout.ring]
+    DeviceBuffer fx_count_;  // [n_streams] uint64: samples rendered
 };
 
 }  // namespace pvq

@@ -1,5 +1,5 @@
 // synth_host.cpp — rustysynth_fork's control rate restated (synth_host.hpp): every f32 / f64 expression is the reference's, in its
-// order, file:line cited; built with -ffp-contract=off.  The audio rate is synth_math.hpp's.
+// order, file:line cited; built with -ffp-contract=off.  The audio rate is synth_math.hpp's, the effects' synth_fx_math.hpp's.
 #include "synth_host.hpp"
 
 #include <algorithm>
@@ -136,6 +136,8 @@ struct Channel {
     float get_pitch_bend_range() const { return static_cast<float>(pitch_bend_range >> 7) + 0.01f * static_cast<float>(pitch_bend_range & 0x7F); }
     float get_tune() const { return static_cast<float>(coarse_tune) + (1.0f / 8192.0f) * static_cast<float>(fine_tune - 8192); }
     float get_pitch_bend() const { return get_pitch_bend_range() * pitch_bend; }
+    float get_reverb_send() const { return (1.0f / 127.0f) * static_cast<float>(reverb_send); }
+    float get_chorus_send() const { return (1.0f / 127.0f) * static_cast<float>(chorus_send); }
 };
 
 // volume_envelope.rs
@@ -309,6 +311,7 @@ struct Voice {
     bool filter_active = false;
     float a[5] = {0, 0, 0, 0, 0};
     float previous_mix_gain_left = 0, previous_mix_gain_right = 0, current_mix_gain_left = 0, current_mix_gain_right = 0;
+    float previous_reverb_send = 0, previous_chorus_send = 0, current_reverb_send = 0, current_chorus_send = 0, instrument_reverb = 0, instrument_chorus = 0;
     int32_t exclusive_class = 0, channel = 0, key = 0, velocity = 0;
     float note_gain = 0, cutoff = 0, resonance = 0, vib_lfo_to_pitch = 0, mod_lfo_to_pitch = 0, mod_env_to_pitch = 0;
     int32_t mod_lfo_to_cutoff = 0, mod_env_to_cutoff = 0;
@@ -363,6 +366,8 @@ struct Voice {
         mod_lfo_to_volume = 0.1f * region.gf(MODULATION_LFO_TO_VOLUME);
         dynamic_volume = mod_lfo_to_volume > 0.05f;
         instrument_pan = sf_clamp(0.1f * region.gf(PAN), -50.0f, 50.0f);
+        instrument_reverb = 0.01f * (0.1f * region.gf(REVERB_EFFECTS_SEND));   // voice.rs:159-160, region_pair.rs:89-95
+        instrument_chorus = 0.01f * (0.1f * region.gf(CHORUS_EFFECTS_SEND));
         {   // region_ex.rs:41-65
             const float delay = region.timecents(DELAY_VOLUME_ENVELOPE), attack = region.timecents(ATTACK_VOLUME_ENVELOPE);
             const float hold = region.timecents(HOLD_VOLUME_ENVELOPE) * key_number_to_multiplying_factor(region.gs(KEY_NUMBER_TO_VOLUME_ENVELOPE_HOLD), key);
@@ -450,8 +455,8 @@ struct Voice {
         return OscStep::Sounds;
     }
 
-    // voice.rs:186-278; fills `rec` when the voice sounds
-    OscStep process(const Channel* channels, int64_t n_wave, float master_volume, synth::Record& rec) {
+    // voice.rs:186-278; fills `rec` and `snd` when the voice sounds
+    OscStep process(const Channel* channels, int64_t n_wave, float master_volume, synth::Record& rec, synth::Sends& snd) {
         if (note_gain < NON_AUDIBLE) return OscStep::Ended;
         const Channel& channel_info = channels[channel];
         if (voice_length >= min_voice_length) {   // release_if_necessary, voice.rs:280-292
@@ -488,6 +493,8 @@ struct Voice {
         }
         previous_mix_gain_left = current_mix_gain_left;
         previous_mix_gain_right = current_mix_gain_right;
+        previous_reverb_send = current_reverb_send;
+        previous_chorus_send = current_chorus_send;
         const float ve = channel_info.get_volume() * channel_info.get_expression();
         const float channel_gain = ve * ve;
         float mix_gain = note_gain * channel_gain * vol_env.value;
@@ -506,9 +513,13 @@ struct Voice {
             current_mix_gain_left = mix_gain * cosf(angle);
             current_mix_gain_right = mix_gain * sinf(angle);
         }
+        current_reverb_send = sf_clamp(channel_info.get_reverb_send() + instrument_reverb, 0.0f, 1.0f);   // voice.rs:257-266
+        current_chorus_send = sf_clamp(channel_info.get_chorus_send() + instrument_chorus, 0.0f, 1.0f);
         if (voice_length == 0) {
             previous_mix_gain_left = current_mix_gain_left;
             previous_mix_gain_right = current_mix_gain_right;
+            previous_reverb_send = current_reverb_send;
+            previous_chorus_send = current_chorus_send;
         }
         voice_length += synth::BLOCK;
         rec.voice = id;
@@ -523,6 +534,12 @@ struct Voice {
         rec.desc = desc_index;
         rec.key = key;
         rec.stage = static_cast<uint32_t>(vol_env.stage);
+        snd.chorus[0] = previous_chorus_send * previous_mix_gain_left;   // synthesizer.rs:404-415: not times master_volume
+        snd.chorus[1] = current_chorus_send * current_mix_gain_left;
+        snd.chorus[2] = previous_chorus_send * previous_mix_gain_right;
+        snd.chorus[3] = current_chorus_send * current_mix_gain_right;
+        snd.reverb[0] = synth::FX_REVERB_GAIN * previous_reverb_send * (previous_mix_gain_left + previous_mix_gain_right);   // synthesizer.rs:449-454
+        snd.reverb[1] = synth::FX_REVERB_GAIN * current_reverb_send * (current_mix_gain_left + current_mix_gain_right);
         started = false;
         return OscStep::Sounds;
     }
@@ -720,8 +737,87 @@ pvq_status SynthBank::create(const int16_t* wave, size_t n_wave, const int32_t* 
 
 SynthState::~SynthState() = default;
 
+std::vector<float> synth_chorus_table(int32_t sample_rate) {   // chorus.rs:24-29
+    const synth::FxLayout l = synth::fx_layout(sample_rate);
+    std::vector<float> table(l.table);
+    for (size_t t = 0; t < table.size(); ++t) {
+        const double phase = 2.0 * 3.14159265358979323846 * static_cast<double>(t) / static_cast<double>(table.size());
+        table[t] = static_cast<float>(static_cast<double>(sample_rate) * (synth::FX_CHORUS_DELAY + synth::FX_CHORUS_DEPTH * sin(phase)));
+    }
+    return table;
+}
+
+pvq_status SynthEffects::create(int32_t sample_rate, std::unique_ptr<SynthEffects>& out, std::string& err) {
+    out.reset();
+    if (sample_rate < 16000 || sample_rate > 192000) {   // synthesizer_settings.rs:35-41
+        err = "The sample rate must be between 16000 and 192000, but was " + std::to_string(sample_rate) + ".";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    std::unique_ptr<SynthEffects> e(new SynthEffects());
+    e->layout_ = synth::fx_layout(sample_rate);
+    e->k_ = synth::reverb_constants();
+    e->table_ = synth_chorus_table(sample_rate);
+    const synth::FxLayout& l = e->layout_;
+    for (uint32_t i = 0; i < synth::FX_BUFFERS; ++i)
+        if (l.len[i] <= static_cast<uint32_t>(synth::BLOCK)) {
+            err = "synth effects: a reverb buffer no longer than a block";
+            return PVQ_ERR_INTERNAL;
+        }
+    if (l.ring < static_cast<uint32_t>(synth::BLOCK) || l.table < 4 * static_cast<uint32_t>(synth::BLOCK)) {
+        err = "synth effects: a chorus ring shorter than a block, or a delay table shorter than four";
+        return PVQ_ERR_INTERNAL;
+    }
+    for (size_t t = 0; t < e->table_.size(); ++t)
+        if (!(e->table_[t] >= 1.0f && e->table_[t] < static_cast<float>(l.ring - 1))) {
+            err = "synth effects: delay table entry " + std::to_string(t) + " lies outside 1 <= delay < ring - 1";
+            return PVQ_ERR_INTERNAL;
+        }
+    e->reverb_.assign(l.total, 0.0f);
+    e->ring_.assign(2 * static_cast<size_t>(l.ring), 0.0f);
+    e->table_index_[1] = l.table / 4;   // chorus.rs:35
+    out = std::move(e);
+    return PVQ_OK;
+}
+
+void SynthEffects::process(size_t n_blocks, const float* chorus_in_left, const float* chorus_in_right, const float* reverb_in, float* chorus_out_left,
+                           float* chorus_out_right, float* reverb_out_left, float* reverb_out_right) {
+    const synth::FxLayout& l = layout_;
+    const float* chorus_in[2] = {chorus_in_left, chorus_in_right};
+    float* chorus_out[2] = {chorus_out_left, chorus_out_right};
+    for (size_t t = 0; t < n_blocks * synth::BLOCK; ++t) {
+        for (int c = 0; c < 2; ++c) {   // chorus.rs:59-117
+            float* ring = ring_.data() + static_cast<size_t>(c) * l.ring;
+            const synth::ChorusTap tap = synth::chorus_tap(ring_index_, table_[table_index_[c]], l.ring);
+            chorus_out[c][t] = synth::chorus_mix(tap, ring[tap.index1], ring[tap.index2]);
+            ring[ring_index_] = chorus_in[c][t];
+            if (++table_index_[c] == l.table) table_index_[c] = 0;
+        }
+        if (++ring_index_ == l.ring) ring_index_ = 0;
+        float out[2];
+        for (int c = 0; c < 2; ++c) {   // reverb.rs:161-182
+            float* const buf = reverb_.data();
+            const uint32_t first = c * synth::FX_COMBS;
+            float x = synth::comb_output_sum([&](int i) { return buf[l.off[first + i] + pos_[first + i]]; });
+            for (int i = 0; i < synth::FX_COMBS; ++i) {
+                float& slot = buf[l.off[first + i] + pos_[first + i]];
+                slot = synth::comb_step(slot, reverb_in[t], store_[first + i], k_);
+            }
+            for (int k = 0; k < synth::FX_ALLPASSES; ++k) {
+                const uint32_t b = synth::FX_FIRST_ALLPASS + c * synth::FX_ALLPASSES + k;
+                x = synth::allpass_step(buf[l.off[b] + pos_[b]], x);
+            }
+            out[c] = x;
+        }
+        synth::reverb_wet_mix(out[0], out[1], k_);
+        reverb_out_left[t] = out[0];
+        reverb_out_right[t] = out[1];
+        for (uint32_t i = 0; i < synth::FX_BUFFERS; ++i)
+            if (++pos_[i] == l.len[i]) pos_[i] = 0;
+    }
+}
+
 pvq_status SynthState::create(std::shared_ptr<const SynthBank> bank, int32_t sample_rate, uint32_t maximum_polyphony, std::unique_ptr<SynthState>& out,
-                              std::string& err) {
+                              std::string& err, bool effects, bool plan_only) {
     out.reset();
     if (!bank) {
         err = "synth state: a bank is needed";
@@ -756,6 +852,9 @@ pvq_status SynthState::create(std::shared_ptr<const SynthBank> bank, int32_t sam
         v.sample_rate = v.vol_env.sample_rate = v.mod_env.sample_rate = v.vib_lfo.sample_rate = v.mod_lfo.sample_rate = sample_rate;
         v.min_voice_length = static_cast<size_t>(sample_rate / 500);
     }
+    s->effects_ = effects;
+    if (effects && !plan_only)
+        if (pvq_status st = SynthEffects::create(sample_rate, s->fx_, err)) return st;
     s->last_plan_.clear();
     out = std::move(s);
     return PVQ_OK;
@@ -817,9 +916,11 @@ pvq_status SynthState::plan(const SynthEvents& events, size_t n_blocks, const ui
         size_t i = 0;   // voice_collection.rs:72-87
         while (i != m.active_voice_count) {
             synth::Record rec{};
-            const OscStep st = m.voices[i].process(m.channels, n_wave, master_volume_, rec);
+            synth::Sends snd{};
+            const OscStep st = m.voices[i].process(m.channels, n_wave, master_volume_, rec, snd);
             if (st == OscStep::Sounds) {
                 out.records.push_back(rec);
+                if (effects_) out.sends.push_back(snd);
                 ++i;
             } else if (st == OscStep::Ended) {
                 m.active_voice_count -= 1;
@@ -843,13 +944,39 @@ pvq_status SynthState::plan(const SynthEvents& events, size_t n_blocks, const ui
     return PVQ_OK;
 }
 
-void synth_replay(const SynthBank& bank, const SynthPlan& plan, size_t n_blocks, synth::Lane* lanes, uint32_t* lane_desc, float* left, float* right) {
+void synth_replay(const SynthBank& bank, const SynthPlan& plan, size_t n_blocks, synth::Lane* lanes, uint32_t* lane_desc, float* left, float* right,
+                  SynthEffects* fx, float master_volume) {
     const int16_t* wave = bank.wave.data();
     for (size_t b = 0; b < n_blocks; ++b) {
         float* l = left + b * synth::BLOCK;
         float* r = right + b * synth::BLOCK;
         std::fill(l, l + synth::BLOCK, 0.0f);   // synthesizer.rs:367-370
         std::fill(r, r + synth::BLOCK, 0.0f);
+        if (fx) {   // synthesizer.rs:393-475: the five sums in one walk (each is a sum over the same records in the same order)
+            float in[3][synth::BLOCK] = {}, out[4][synth::BLOCK];
+            float* const sum[synth::FX_CHANNELS] = {l, r, in[0], in[1], in[2]};
+            for (uint32_t k = plan.block_ptr[b]; k < plan.block_ptr[b + 1]; ++k) {
+                const synth::Record& rec = plan.records[k];
+                if (rec.flags & synth::F_START) lane_desc[rec.voice] = rec.desc;
+                const synth::SampleDesc& d = bank.descs[lane_desc[rec.voice]];
+                synth::MixGain g[synth::FX_CHANNELS];
+                synth::fx_gains(rec, plan.sends[k], g);
+                bool add[synth::FX_CHANNELS];
+                for (int c = 0; c < synth::FX_CHANNELS; ++c) add[c] = g[c].mode != synth::MIX_SKIP;
+                synth::Walk w = synth::walk_begin(rec, d, lanes[rec.voice]);
+                synth::walk_span<synth::FX_CHANNELS>(rec, d, wave, lanes[rec.voice], w, g, 0, synth::BLOCK, [&](int t, const float (&p)[synth::FX_CHANNELS]) {
+                    for (int c = 0; c < synth::FX_CHANNELS; ++c)
+                        if (add[c]) sum[c][t] += p[c];
+                });
+                synth::walk_end(rec, lanes[rec.voice], w);
+            }
+            fx->process(1, in[0], in[1], in[2], out[0], out[1], out[2], out[3]);
+            for (int t = 0; t < synth::BLOCK; ++t) {
+                l[t] = synth::fx_final(l[t], out[0][t], out[2][t], master_volume);
+                r[t] = synth::fx_final(r[t], out[1][t], out[3][t], master_volume);
+            }
+            continue;
+        }
         for (uint32_t k = plan.block_ptr[b]; k < plan.block_ptr[b + 1]; ++k) {   // synthesizer.rs:372-391
             const synth::Record& rec = plan.records[k];
             if (rec.flags & synth::F_START) lane_desc[rec.voice] = rec.desc;
@@ -870,7 +997,11 @@ pvq_status SynthState::render(const SynthEvents& events, size_t n_blocks, const 
     }
     last_plan_.clear();
     if (pvq_status st = plan(events, n_blocks, snapshot_blocks, n_snapshots, 0, last_plan_, err)) return st;
-    synth_replay(*bank_, last_plan_, n_blocks, lanes_, lane_desc_, left, right);
+    if (effects_ && !fx_) {
+        err = "synth state: a state made for planning alone has no effect state to render with";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    synth_replay(*bank_, last_plan_, n_blocks, lanes_, lane_desc_, left, right, fx_.get(), master_volume_);
     return PVQ_OK;
 }
 

@@ -90,23 +90,33 @@ PVQ_SYNTH_FLAT float biquad_step(const float a[5], Lane& s, float input) {
     return output;
 }
 
-// A record's 64 samples: oscillator, filter, and the two products a_left * x and a_right * x that write_block adds, a stepped by
-// repeated addition (array_math.rs:16-24).  sink(t, left product, right product); a channel whose mode is MIX_SKIP is not to be
-// added.  The reads of eight samples are issued before the first of them enters the filter chain: positions do not depend on data.
-template <class Sink>
-PVQ_SYNTH_FLAT void walk_block(const Record& r, const SampleDesc& d, const int16_t* wave, Lane& s, MixGain gl, MixGain gr, Sink&& sink) {
-    PVQ_FP_STRICT
-    const int64_t ratio_fp = static_cast<int64_t>((static_cast<uint64_t>(r.ratio_hi) << 32) | r.ratio_lo);
+// A record's walk in pieces, for a caller that cannot hold a whole block's products at once (synth_batch.hip's effects kernel walks
+// half a block at a time): walk_begin, walk_span over [t_begin, t_end) (multiples of 8) with N gains, walk_end.  What passes from
+// span to span is the Walk and the gains, which walk_span steps by the reference's repeated addition (array_math.rs:16-24).
+struct Walk {
+    int64_t pos;
+    float in1, in2;   // the block's last and last but one oscillator samples
+};
+PVQ_SYNTH_FLAT Walk walk_begin(const Record& r, const SampleDesc& d, Lane& s) {
     if (r.flags & F_START) {   // region_ex.rs:15-39 -> oscillator.rs:87; voice.rs:167
         s.position_fp = static_cast<int64_t>(d.start) << FRAC_BITS;
         s.x1 = s.x2 = s.y1 = s.y2 = 0.0f;
     }
+    return Walk{s.position_fp, 0.0f, 0.0f};
+}
+// sink(t, products[N]): products[c] = gain c * the voice's sample; a channel whose mode is MIX_SKIP is not to be added.  The reads
+// of eight samples are issued before the first of them enters the filter chain: positions do not depend on data.
+template <int N, class Sink>
+PVQ_SYNTH_FLAT void walk_span(const Record& r, const SampleDesc& d, const int16_t* wave, Lane& s, Walk& w, MixGain (&g)[N], int t_begin, int t_end,
+                              Sink&& sink) {
+    PVQ_FP_STRICT
+    const int64_t ratio_fp = static_cast<int64_t>((static_cast<uint64_t>(r.ratio_hi) << 32) | r.ratio_lo);
     const bool looping = (r.flags & F_LOOP) != 0, active = (r.flags & F_FILTER) != 0;
     const int64_t end_loop_fp = static_cast<int64_t>(d.end_loop) << FRAC_BITS;
     const int64_t loop_length = static_cast<int64_t>(d.end_loop) - d.start_loop, loop_length_fp = loop_length * FRAC_UNIT;
-    int64_t pos = s.position_fp;
-    float in1 = 0.0f, in2 = 0.0f;   // the block's last and last but one oscillator samples
-    for (int t0 = 0; t0 < BLOCK; t0 += 8) {
+    int64_t pos = w.pos;
+    float in1 = w.in1, in2 = w.in2;
+    for (int t0 = t_begin; t0 < t_end; t0 += 8) {
         int32_t w1[8], w2[8];
         int64_t a_fp[8];
         PVQ_SYNTH_UNROLL
@@ -135,18 +145,37 @@ PVQ_SYNTH_FLAT void walk_block(const Record& r, const SampleDesc& d, const int16
             in2 = in1;
             in1 = x;
             const float y = active ? biquad_step(r.a, s, x) : x;
-            sink(t0 + k, gl.a * y, gr.a * y);
-            gl.a += gl.step;
-            gr.a += gr.step;
+            float p[N];
+            PVQ_SYNTH_UNROLL
+            for (int c = 0; c < N; ++c) {
+                p[c] = g[c].a * y;
+                g[c].a += g[c].step;
+            }
+            sink(t0 + k, p);
         }
     }
-    s.position_fp = pos;
-    if (!active) {   // bi_quad_filter.rs:93-98
-        s.x2 = in2;
-        s.x1 = in1;
+    w.pos = pos;
+    w.in1 = in1;
+    w.in2 = in2;
+}
+PVQ_SYNTH_FLAT void walk_end(const Record& r, Lane& s, const Walk& w) {
+    s.position_fp = w.pos;
+    if (!(r.flags & F_FILTER)) {   // bi_quad_filter.rs:93-98
+        s.x2 = w.in2;
+        s.x1 = w.in1;
         s.y2 = s.x2;
         s.y1 = s.x1;
     }
+}
+
+// A record's 64 samples: oscillator, filter, and the two products a_left * x and a_right * x that write_block adds.
+// sink(t, left product, right product).
+template <class Sink>
+PVQ_SYNTH_FLAT void walk_block(const Record& r, const SampleDesc& d, const int16_t* wave, Lane& s, MixGain gl, MixGain gr, Sink&& sink) {
+    MixGain g[2] = {gl, gr};
+    Walk w = walk_begin(r, d, s);
+    walk_span<2>(r, d, wave, s, w, g, 0, BLOCK, [&](int t, const float (&p)[2]) { sink(t, p[0], p[1]); });
+    walk_end(r, s, w);
 }
 
 }  // namespace synth

@@ -1,10 +1,12 @@
-"""The synth stage (include/pvq.h, "the synth stage"): rustysynth_fork's voices — the dry path, ``enable_reverb_and_chorus = false`` —
-from a sound bank and MIDI-style event lists.
+"""The synth stage (include/pvq.h, "the synth stage"): rustysynth_fork's voices from a sound bank and MIDI-style event lists — by
+default the dry path, ``enable_reverb_and_chorus = false``; with ``effects=True`` its reverb and chorus too (reverb.rs, chorus.rs,
+synthesizer.rs:393-475), which is what pitchvis_train renders.
 
 * ``SynthBank.from_arrays``  — SoundFont::new after parsing (soundfont.rs, instrument_region.rs, preset_region.rs): arrays in
 * ``SynthState``             — Synthesizer + MidiFileSequencer for one stream on the host (synthesizer.rs, midifile_sequencer.rs:52-104)
 * ``SynthBatch``             — the same for many streams: the control rate planned on the host, the audio rate replayed on the GPU,
                                left / right rows left in device memory for ``AgcBatch.condition_device``
+* ``SynthEffects``           — Reverb + Chorus alone on the host, fed with chosen inputs; ``chorus_table`` is Chorus::new's delay table
 
 Events are a 5-tuple of arrays ``(time_s float64, channel, command, data1, data2)``, sorted by time: a stream's WHOLE list.  A handle
 keeps how many it has consumed, so successive calls continue one another.
@@ -25,6 +27,9 @@ F_START, F_LOOP, F_FILTER, F_ENDS = 1, 2, 4, 8   # pvq_synth_record.flags
 RECORD_DTYPE = np.dtype([("voice", "<u4"), ("flags", "<u4"), ("ratio_lo", "<u4"), ("ratio_hi", "<u4"), ("a", "<f4", (5,)), ("gain", "<f4", (4,)),
                          ("desc", "<u4"), ("key", "<i4"), ("stage", "<u4")])
 assert RECORD_DTYPE.itemsize == 64
+SENDS_DTYPE = np.dtype([("chorus", "<f4", (4,)), ("reverb", "<f4", (2,)), ("pad", "<u4", (2,))])   # pvq_synth_sends
+assert SENDS_DTYPE.itemsize == 32
+PVQ_SYNTH_EFFECTS = 1
 
 _i16p, _i32p, _u32p, _u64p = C.POINTER(C.c_int16), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 _fp, _dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
@@ -128,11 +133,15 @@ def _snapshots(getter) -> List[List[Tuple[int, float, float]]]:
 class SynthState:
     """One stream on the host (pvq_synth_state_*): the planner, then the replay of its plan."""
 
-    def __init__(self, bank: SynthBank, sample_rate: int, maximum_polyphony: int = 64):
+    def __init__(self, bank: SynthBank, sample_rate: int, maximum_polyphony: int = 64, effects: bool = False):
         self._L = _lib.load()
         self._bank = bank
+        self.effects = bool(effects)
         self._h = C.c_void_p()
-        _check(self._L.pvq_synth_state_create(bank._h, int(sample_rate), int(maximum_polyphony), C.byref(self._h)))
+        if effects:
+            _check(self._L.pvq_synth_state_create_ex(bank._h, int(sample_rate), int(maximum_polyphony), PVQ_SYNTH_EFFECTS, C.byref(self._h)))
+        else:
+            _check(self._L.pvq_synth_state_create(bank._h, int(sample_rate), int(maximum_polyphony), C.byref(self._h)))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -166,6 +175,17 @@ class SynthState:
                                                 C.cast(rec.ctypes.data, C.POINTER(_lib.CSynthRecord)), rec.size))
         return ptr, rec[:int(counts[1])]
 
+    def sends(self) -> Tuple[np.ndarray, np.ndarray]:
+        """the last render's effect gains: (block_ptr uint32 [n_blocks + 1], sends SENDS_DTYPE, one per record of ``plan()``); a state
+        without effects has none: ([0], empty)"""
+        counts = (C.c_uint32 * 2)()
+        _check(self._L.pvq_synth_state_get_sends(self._h, counts, None, 0, None, 0))
+        ptr = np.zeros(int(counts[0]) + 1, np.uint32)
+        snd = np.zeros(max(int(counts[1]), 1), SENDS_DTYPE)
+        _check(self._L.pvq_synth_state_get_sends(self._h, counts, ptr.ctypes.data_as(_u32p), ptr.size,
+                                                 C.cast(snd.ctypes.data, C.POINTER(_lib.CSynthSends)), snd.size))
+        return ptr, snd[:int(counts[1])]
+
     @property
     def active_voices(self) -> int:
         return int(self._L.pvq_synth_state_active_voices(self._h))
@@ -175,14 +195,20 @@ class SynthBatch:
     """Many streams (pvq_synth_batch_*): a wavefront per stream, a lane per voice object.  ``device=None``: a host-only handle (the
     argument checks work; rendering raises: no CPU fallback)."""
 
-    def __init__(self, bank: SynthBank, n_streams: int, sample_rate: int, maximum_polyphony: int = 64, device: Optional[int] = 0):
+    def __init__(self, bank: SynthBank, n_streams: int, sample_rate: int, maximum_polyphony: int = 64, device: Optional[int] = 0,
+                 effects: bool = False):
         self._L = _lib.load()
         self._bank = bank
         self.n_streams = int(n_streams)
         self.device = device
+        self.effects = bool(effects)
         self._h = C.c_void_p()
-        _check(self._L.pvq_synth_batch_create(-1 if device is None else int(device), bank._h, self.n_streams, int(sample_rate),
-                                              int(maximum_polyphony), C.byref(self._h)))
+        if effects:   # the handle then owns every stream's reverb buffers and chorus rings on the device
+            _check(self._L.pvq_synth_batch_create_ex(-1 if device is None else int(device), bank._h, self.n_streams, int(sample_rate),
+                                                     int(maximum_polyphony), PVQ_SYNTH_EFFECTS, C.byref(self._h)))
+        else:
+            _check(self._L.pvq_synth_batch_create(-1 if device is None else int(device), bank._h, self.n_streams, int(sample_rate),
+                                                  int(maximum_polyphony), C.byref(self._h)))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -225,3 +251,40 @@ class SynthBatch:
     def snapshots(self, stream_index: int) -> List[List[Tuple[int, float, float]]]:
         """``SynthState.snapshots`` for one stream of the last render (host data: does not wait for the device)"""
         return _snapshots(lambda *a: self._L.pvq_synth_batch_get_snapshots(self._h, int(stream_index), *a))
+
+
+def chorus_table(sample_rate: int) -> np.ndarray:
+    """Chorus::new's delay table (chorus.rs:24-29): float32 ``[round(sample_rate / 0.4)]``, delays in samples"""
+    L = _lib.load()
+    n = int(L.pvq_synth_chorus_table(int(sample_rate), None, 0))
+    if n == 0:
+        raise ValueError((L.pvq_last_error() or b"").decode())
+    out = np.zeros(n, np.float32)
+    L.pvq_synth_chorus_table(int(sample_rate), out.ctypes.data_as(_fp), out.size)
+    return out
+
+
+class SynthEffects:
+    """Reverb + Chorus alone on the host (pvq_synth_effects_*), fed with chosen inputs: the code ``SynthState(effects=True)`` runs."""
+
+    def __init__(self, sample_rate: int):
+        self._L = _lib.load()
+        self._h = C.c_void_p()
+        _check(self._L.pvq_synth_effects_create(int(sample_rate), C.byref(self._h)))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._L.pvq_synth_effects_destroy(h)
+            self._h = None
+
+    def process(self, chorus_in_left, chorus_in_right, reverb_in) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """three inputs of ``n_blocks * 64`` float32 -> (chorus out left, chorus out right, reverb out left, reverb out right); the
+        state goes on from call to call"""
+        ins = [np.ascontiguousarray(a, np.float32).reshape(-1) for a in (chorus_in_left, chorus_in_right, reverb_in)]
+        n = ins[0].size
+        if n % BLOCK or any(a.size != n for a in ins):
+            raise ValueError("three inputs of one length, a multiple of 64")
+        outs = [np.zeros(max(n, 1), np.float32) for _ in range(4)]
+        _check(self._L.pvq_synth_effects_process(self._h, n // BLOCK, *[a.ctypes.data_as(_fp) for a in ins], *[a.ctypes.data_as(_fp) for a in outs]))
+        return tuple(a[:n] for a in outs)
