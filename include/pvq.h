@@ -830,11 +830,13 @@ pvq_status pvq_panels_batch_get_history(pvq_panels_batch *b, uint32_t stream_ind
  * non-finite vertex (after its transform) or a non-finite colour draws nothing.  Pixel boxes are an acceleration only and err
  * outwards.
  *
- * Left out: MSAA; a ball whose z has fallen below -12.7, which in the
+ * Left out: MSAA other than the backdrop's own (the pvq_msaa_ entries below, samples = 4; the border pixels of the overlay's
+ * spectrogram quad stay one-sample); a ball whose z has fallen below -12.7, which in the
  * reference would go under the bass spiral — here the balls are always on top (at keying z >= -12.625, and the fade lowers it by
  * 0.03 per second while the ball lives).  The pitch-name text at z = -0.02 is the text stage below (the caller brings the font),
  * the spectrogram quad at z = 5 and the chroma boxes are the overlay stage after it, bloom and tone mapping the present stage after
- * that (which names what stays out of the displayed picture: MSAA, the deband dither and a draw of the boxes in display space). */
+ * that (which names what stays out of the displayed picture: MSAA of the overlay quad's border, the deband dither and a draw of
+ * the boxes in display space). */
 enum { PVQ_BACKDROP_NET_SPIRAL = 0, PVQ_BACKDROP_NET_RAYS = 1, PVQ_BACKDROP_BASS = 2 };
 /* the static quads of one layer: quads_out [n][4][2] (v0 .. v3 as x, y; triangles (2, 1, 0), (2, 0, 3)), n_out: their number —
  * 72 octaves - 1, 12, min(72 octaves, 168) - 1.  Either may be NULL.  octaves 1 .. 1024. */
@@ -899,6 +901,61 @@ pvq_status pvq_backdrop_batch_frames_device(pvq_backdrop_batch *b, size_t n_fram
  * row (in place: a pixel is read and written by the same lane).  in->background must be NULL and d_image_inout is needed. */
 pvq_status pvq_backdrop_balls_over_device(pvq_raster_batch *b, size_t n_frames, const pvq_raster_inputs *in, const float *elapsed_s,
                                           float *d_image_inout, float *d_ball_time, void *stream);
+
+/* ---- the backdrop multisampled: four samples a pixel, resolved at the end of the stage --------------------------------
+ * The reference sets Msaa::Off under target_os = "android" only (setup.rs:379-382); its desktop and wasm builds keep Bevy's
+ * default, Msaa::Sample4.  The backdrop's triangles are almost all thin (0.05 world units: 2.3 pixels at 1280 x 720, 0.8 at
+ * 256 x 256), so nearly every pixel they cover is an edge pixel.  The entries here are the backdrop's faces with a sample count in
+ * front; samples is 1 or 4, anything else is PVQ_ERR_INVALID_ARG before anything else is looked at and before any device is
+ * touched.  With samples = 1 they give the bits of the one-sample faces above.
+ *
+ * The rule, samples = 4.  A pixel (i, j) has four samples at these positions, in pixel units from its top-left corner, in this order:
+ *     0: (0.375, 0.125)   1: (0.875, 0.375)   2: (0.125, 0.625)   3: (0.625, 0.875)        (samples = 1: (0.5, 0.5))
+ * Sample k's world position is the raster section's pixel position with 0.5 replaced by the fractions, f32 without FMA contraction:
+ *     s = vh / (float)H;  wx = ((float)i + fx_k - 0.5f * (float)W) * s;  wy = (0.5f * (float)H - ((float)j + fy_k)) * s
+ * (i + fx_k is exact: sides <= 4096, fractions in eighths; with (0.5, 0.5) this is the pixel centre bit for bit).  Every sample has a
+ * destination of its own, which starts from the clear colour or from the shared background's pixel.  Each sample runs the coverage
+ * rule of the section above unchanged at its own position — canonical edges, a tie e == 0 going to the triangle whose sign is
+ * positive, so an edge through a sample goes to exactly one of the two triangles beside it — and a covered sample is blended with
+ * the triangle's flat colour against its own destination, in list order.  After layer 6 the pixel is resolved, per channel
+ *     ((s0 + s1) + (s2 + s3)) * 0.25f
+ * in that order: four equal finite samples x with |x| < 2^126 resolve to exactly x; pictures with channels beyond that bound are
+ * not promised.  The pixel boxes are those of the one-sample rule: widened by a whole pixel, they hold every pixel with a covered
+ * sample, none of which is further than 0.375 pixel from its centre.  No per-sample picture leaves the stage.
+ *
+ * What is assumed:
+ *   sample positions   the standard four-sample pattern; wgpu does not expose the positions, but Vulkan's standard sample
+ *                      locations, D3D and Metal share them                                        (confidence: high for desktop)
+ *   shading            once per pixel in the reference, per covered sample here: the same for a flat colour
+ *   resolve            an unweighted mean of the linear target before bloom: Bevy resolves the main pass's texture before
+ *                      post-processing; its target is 16-bit float, ours f32
+ *   not multisampled   the balls — the fragment's alpha is exactly 0 at and beyond the unit radius, so the edge of a ball's quad
+ *                      never shows; the text, whose coverage is analytic; the chroma boxes, which are UI and which Bevy does not
+ *                      multisample.  A layer that covers all four samples of a pixel with one colour and one alpha blends every
+ *                      sample by the same affine map, and the mean commutes with an affine map: blending it over the resolved
+ *                      picture equals resolving after it, up to rounding.  So the later stages run on the resolved picture as they are.
+ *   left out           the border pixels of the overlay's spectrogram quad, the one partial coverage outside the backdrop;
+ *                      sample counts other than 1 and 4; a per-sample picture kept after the backdrop; centroid or per-sample
+ *                      shading; the deband dither; the UI boxes in display space */
+/* xy_out [samples][2]: the positions above */
+pvq_status pvq_msaa_sample_positions(uint32_t samples, float *xy_out /* [samples][2] */);
+/* The one-mesh face.  image_inout is a resolved picture: every sample starts from its pixel, the mesh is drawn, and the result is
+ * resolved back.  The other arguments and their checks are the one-sample face's. */
+pvq_status pvq_msaa_draw_mesh(uint32_t samples, uint32_t width, uint32_t height, float viewport_height, size_t n_triangles, const float *pos,
+                              const float *rgba, const float *transform, float *image_inout);
+/* One frame on the host: layers 0 - 6, resolved.  The other arguments and their checks are the one-frame host face's.  The four
+ * sample planes are host memory of 4 x the picture's size for the length of the call. */
+pvq_status pvq_msaa_frame(uint32_t samples, uint32_t octaves, uint32_t buckets_per_octave, uint32_t width, uint32_t height,
+                          float viewport_height, int visuals_mode, uint32_t bass_lit, const float *bass_rgba,
+                          const pvq_backdrop_panels *panels, const float *background, float *image_out);
+/* Many streams on the GPU.  The handle is an ordinary backdrop batch handle: the batched backdrop's frames call draws it — with
+ * samples = 4 through a tile kernel that keeps a pixel's four samples in registers and stores the resolved pixel, the output bytes
+ * being the one-sample call's — and its destroy frees it.  The other arguments and their checks are the batched create's;
+ * device_id < 0 makes a host-only handle as there. */
+pvq_status pvq_msaa_batch_create(uint32_t samples, int device_id, uint32_t octaves, uint32_t buckets_per_octave, int visuals_mode,
+                                 float viewport_height, uint32_t n_streams, uint32_t width, uint32_t height, pvq_backdrop_batch **out);
+/* the sample count a backdrop batch handle was made with (1 for one from the one-sample create); 0 for NULL */
+uint32_t pvq_msaa_batch_samples(const pvq_backdrop_batch *b);
 
 /* ---- the overlay: scrolling spectrogram quad and chroma boxes, in front of the balls -------------------------------
  * The last two parts of the DisplayMode::Debugging picture (pitchvis_viewer/src/display_system/setup.rs:418-541, update.rs:929-1172,
@@ -1102,7 +1159,8 @@ pvq_status pvq_text_batch_get_coverage(pvq_text_batch *b, int label, float *out)
  * NONE passes max(c, 0) through.
  * Encode.  v = clamp(out, 0, 1), v <= 0.0031308 ? 12.92 v : 1.055 powf(v, 1 / 2.4) - 0.055, byte = floor(v * 255 + 0.5); alpha:
  * floor(clamp(a, 0, 1) * 255 + 0.5); a NaN encodes as 0.
- * Left out of the displayed picture, here and in every section above: MSAA, the deband dither, colour grading
+ * Left out of the displayed picture, here and in every section above: MSAA beyond the backdrop's (which the pvq_msaa_ entries
+ * draw with samples = 4; the overlay quad's border pixels are left out), the deband dither, colour grading
  * (the reference leaves it at identity) and a draw of the chroma boxes in display space — they stay where the overlay stage blends
  * them, in the linear target, and so pass through the transform. */
 enum { PVQ_PRESENT_ENERGY_CONSERVING = 0, PVQ_PRESENT_ADDITIVE = 1 };          /* composite_mode */

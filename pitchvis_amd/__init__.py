@@ -641,7 +641,7 @@ from .consumers import AgcBatch, MonoAgc, PinnedArray, RenderBatch, Stream, calc
 from .synth import SynthBank, SynthBatch, SynthEffects, SynthState, chorus_table  # noqa: E402,F401
 from .scene import SceneBatch, SceneState  # noqa: E402,F401
 from .raster import RasterBatch, raster_frame, raster_shade, raster_touch  # noqa: E402,F401
-from .backdrop import BackdropBatch, backdrop_draw_mesh, backdrop_frame, backdrop_geometry, panel_transforms  # noqa: E402,F401
+from .backdrop import BackdropBatch, backdrop_draw_mesh, backdrop_frame, backdrop_geometry, msaa_sample_positions, panel_transforms  # noqa: E402,F401
 from .overlay import OverlayBatch, OverlayState, overlay_frame, overlay_quad  # noqa: E402,F401
 from .text import TextBatch, TextFont, TextLabel, pitch_name_labels, text_frame, text_layout  # noqa: E402,F401
 from .present import PresentBatch, present_blend_factors, present_frame, present_mips, present_settings  # noqa: E402,F401

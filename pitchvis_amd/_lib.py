@@ -46,6 +46,7 @@ EXPORTS = [
     "pvq_raster_batch_frames_device", "pvq_raster_batch_get_times",
     "pvq_backdrop_geometry", "pvq_backdrop_panel_transforms", "pvq_backdrop_draw_mesh", "pvq_backdrop_frame", "pvq_backdrop_batch_create",
     "pvq_backdrop_batch_destroy", "pvq_backdrop_batch_frames_device", "pvq_backdrop_balls_over_device",
+    "pvq_msaa_sample_positions", "pvq_msaa_draw_mesh", "pvq_msaa_frame", "pvq_msaa_batch_create", "pvq_msaa_batch_samples",
     "pvq_overlay_quad", "pvq_overlay_state_create", "pvq_overlay_state_destroy", "pvq_overlay_state_push", "pvq_overlay_state_texture",
     "pvq_overlay_frame", "pvq_overlay_batch_create", "pvq_overlay_batch_destroy", "pvq_overlay_batch_frames_device",
     "pvq_overlay_batch_get_texture",
@@ -412,6 +413,12 @@ def load():
     L.pvq_backdrop_batch_destroy.argtypes = [vp]; L.pvq_backdrop_batch_destroy.restype = None
     L.pvq_backdrop_batch_frames_device.argtypes = [vp, C.c_size_t, C.POINTER(CBackdropInputs), vp, vp]; L.pvq_backdrop_batch_frames_device.restype = C.c_int
     L.pvq_backdrop_balls_over_device.argtypes = [vp, C.c_size_t, C.POINTER(CRasterInputs), fp, vp, vp, vp]; L.pvq_backdrop_balls_over_device.restype = C.c_int
+    if not _dev or _dev == "1" or hasattr(L, "pvq_msaa_frame"):   # (a library of older sources kept for an A/B, PVQ_DEV_LIB=<name>, may predate them)
+        L.pvq_msaa_sample_positions.argtypes = [C.c_uint32, fp]; L.pvq_msaa_sample_positions.restype = C.c_int
+        L.pvq_msaa_draw_mesh.argtypes = [C.c_uint32] + L.pvq_backdrop_draw_mesh.argtypes; L.pvq_msaa_draw_mesh.restype = C.c_int
+        L.pvq_msaa_frame.argtypes = [C.c_uint32] + L.pvq_backdrop_frame.argtypes; L.pvq_msaa_frame.restype = C.c_int
+        L.pvq_msaa_batch_create.argtypes = [C.c_uint32] + L.pvq_backdrop_batch_create.argtypes; L.pvq_msaa_batch_create.restype = C.c_int
+        L.pvq_msaa_batch_samples.argtypes = [vp]; L.pvq_msaa_batch_samples.restype = C.c_uint32
     L.pvq_overlay_quad.argtypes = [C.c_uint32, C.c_uint32, fp]; L.pvq_overlay_quad.restype = C.c_int
     L.pvq_overlay_state_create.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(vp)]; L.pvq_overlay_state_create.restype = C.c_int
     L.pvq_overlay_state_destroy.argtypes = [vp]; L.pvq_overlay_state_destroy.restype = None

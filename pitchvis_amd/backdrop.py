@@ -7,6 +7,9 @@ balls on it.
   placement of the three panels; ``backdrop_draw_mesh`` — the rule's one-mesh face; ``backdrop_frame`` — one frame on the host
 * ``BackdropBatch`` — many streams on the GPU (pvq_backdrop_batch_*), fed with what ``SceneBatch.frames_device``,
   ``PanelsBatch.rows_device`` and ``PanelsBatch.graph_device(first_emitted=0)`` leave in device memory
+* ``samples=4`` on ``backdrop_draw_mesh``, ``backdrop_frame`` and ``BackdropBatch`` draws with four samples a pixel, resolved at the
+  end of the stage (pvq_msaa_*; the reference's desktop setting, Msaa::Sample4); ``samples=1``, the default, is the one-sample rule
+  through the one-sample entry points; ``msaa_sample_positions`` — where the samples lie
 """
 from __future__ import annotations
 
@@ -43,6 +46,20 @@ def panel_transforms(n_bins: int, width: int, height: int, viewport_height: floa
     return out
 
 
+def _samples(samples) -> int:
+    if samples not in (1, 4):
+        raise ValueError("samples is 1 or 4")
+    return int(samples)
+
+
+def msaa_sample_positions(samples: int) -> np.ndarray:
+    """[samples][2]: (x, y) of every sample in pixel units from the pixel's top-left corner"""
+    L = _lib.load()
+    out = np.empty((_samples(samples), 2), np.float32)
+    _checked(L, L.pvq_msaa_sample_positions(int(samples), _f(out)))
+    return out
+
+
 def _transform(t):
     t = np.ascontiguousarray(IDENTITY if t is None else t, np.float32)
     if t.shape != (4,):
@@ -50,17 +67,19 @@ def _transform(t):
     return t
 
 
-def backdrop_draw_mesh(image, pos, rgba, *, viewport_height: float = 0.0, transform=None) -> np.ndarray:
+def backdrop_draw_mesh(image, pos, rgba, *, viewport_height: float = 0.0, transform=None, samples: int = 1) -> np.ndarray:
     """``image`` [height][width][4] with the triangles ``pos`` [n][3][2] of linear colours ``rgba`` [n][4] blended over it in index
-    order (a new array)"""
+    order (a new array).  ``samples=4``: every sample of a pixel starts from the pixel, and the result is resolved."""
     L = _lib.load()
+    samples = _samples(samples)
     img = np.array(image, np.float32)
     p, c = np.ascontiguousarray(pos, np.float32), np.ascontiguousarray(rgba, np.float32)
     if img.ndim != 3 or img.shape[2] != 4 or p.shape[1:] != (3, 2) or c.shape != (p.shape[0], 4):
         raise ValueError("image [height][width][4], pos [n][3][2], rgba [n][4]")
     t = None if transform is None else _transform(transform)
-    _checked(L, L.pvq_backdrop_draw_mesh(img.shape[1], img.shape[0], float(viewport_height), p.shape[0], _f(p) if p.size else None,
-                                         _f(c) if c.size else None, _f(t) if t is not None else None, _f(img)))
+    args = (img.shape[1], img.shape[0], float(viewport_height), p.shape[0], _f(p) if p.size else None, _f(c) if c.size else None,
+            _f(t) if t is not None else None, _f(img))
+    _checked(L, L.pvq_backdrop_draw_mesh(*args) if samples == 1 else L.pvq_msaa_draw_mesh(samples, *args))
     return img
 
 
@@ -96,9 +115,11 @@ def _host_panels(n_bins: int, panels: dict, keep: list) -> _lib.CBackdropPanels:
 
 
 def backdrop_frame(octaves: int, buckets_per_octave: int, width: int, height: int, *, viewport_height: float = 0.0, visuals_mode: int = FULL,
-                   bass_lit: int = 0, bass_rgba=None, panels: Optional[dict] = None, background=None) -> np.ndarray:
-    """One frame on the host: clear colour or ``background``, net, panels (see ``_host_panels``), lit bass segments"""
+                   bass_lit: int = 0, bass_rgba=None, panels: Optional[dict] = None, background=None, samples: int = 1) -> np.ndarray:
+    """One frame on the host: clear colour or ``background``, net, panels (see ``_host_panels``), lit bass segments; with
+    ``samples=4`` drawn per sample and resolved"""
     L = _lib.load()
+    samples = _samples(samples)
     if not (1 <= width <= 4096 and 1 <= height <= 4096):
         raise ValueError("width and height are 1 .. 4096")
     bg = None
@@ -114,29 +135,31 @@ def backdrop_frame(octaves: int, buckets_per_octave: int, width: int, height: in
     keep: list = []
     o = _host_panels(int(octaves) * int(buckets_per_octave), panels, keep) if panels is not None else None
     out = np.empty((height, width, 4), np.float32)
-    _checked(L, L.pvq_backdrop_frame(int(octaves), int(buckets_per_octave), width, height, float(viewport_height), int(visuals_mode),
-                                     int(bass_lit), _f(col) if col is not None else None, C.byref(o) if o is not None else None,
-                                     _f(bg) if bg is not None else None, _f(out)))
+    args = (int(octaves), int(buckets_per_octave), width, height, float(viewport_height), int(visuals_mode), int(bass_lit),
+            _f(col) if col is not None else None, C.byref(o) if o is not None else None, _f(bg) if bg is not None else None, _f(out))
+    _checked(L, L.pvq_backdrop_frame(*args) if samples == 1 else L.pvq_msaa_frame(samples, *args))
     return out
 
 
 class BackdropBatch:
     """The backdrop for MANY streams on the GPU; stateless.  ``device=None``: a host-only handle (the argument checks work;
-    ``frames`` raises: no CPU fallback)."""
+    ``frames`` raises: no CPU fallback).  ``samples=4``: four samples a pixel, kept in registers and resolved by the tile kernel;
+    the image ``frames`` returns has the shape and the meaning it has with one sample."""
 
     INPUTS = ("bass_lit", "bass_rgba", "line_pos", "line_rgba", "disc_pos", "disc_rgba", "peak_count", "hist_pos", "hist_rgba", "graph_pos",
               "graph_rgba")
 
     def __init__(self, range, n_streams: int, width: int, height: int, visuals_mode: int = FULL, viewport_height: float = 0.0,
-                 device: Optional[int] = 0):
+                 device: Optional[int] = 0, samples: int = 1):
         self._L = _lib.load()
+        self.samples = _samples(samples)
         self.range, self.n_streams, self.device = range, int(n_streams), device
         self.width, self.height = int(width), int(height)
         self.n_bins = range.octaves * range.buckets_per_octave
         self._h = C.c_void_p()
-        _checked(self._L, self._L.pvq_backdrop_batch_create(-1 if device is None else int(device), range.octaves, range.buckets_per_octave,
-                                                            int(visuals_mode), float(viewport_height), self.n_streams, self.width,
-                                                            self.height, C.byref(self._h)))
+        args = (-1 if device is None else int(device), range.octaves, range.buckets_per_octave, int(visuals_mode), float(viewport_height),
+                self.n_streams, self.width, self.height, C.byref(self._h))
+        _checked(self._L, self._L.pvq_backdrop_batch_create(*args) if self.samples == 1 else self._L.pvq_msaa_batch_create(self.samples, *args))
 
     def __del__(self):
         h = getattr(self, "_h", None)

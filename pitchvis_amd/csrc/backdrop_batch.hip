@@ -9,7 +9,9 @@
 // lane per pixel): per 64 records each lane loads one record's box word (16 bytes, a record apart; four such loads in flight) and
 // tests it against the wave's block; a ballot gives the hit mask, the wave visits the set bits in ascending order — the list's
 // order — reading the record at a wave-uniform address, and every lane evaluates the rule for its pixel and blends.  The colour
-// stays in four registers and leaves in one 16-byte store.
+// stays in four registers and leaves in one 16-byte store.  The kernels' argument block and the walk over a list are
+// backdrop_device.hpp's, shared with the four-sample tile kernel of backdrop_msaa.hip, which frames_device launches in this
+// kernel's place for a handle made with samples = 4.
 //
 // FMA contraction is off and `/` is the correctly rounded one, as in raster_batch.hip.
 #include "backdrop_batch.hpp"
@@ -18,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "backdrop_device.hpp"
 #include "stage_device.hpp"
 #include "stage_plan.hpp"
 #include "vqt_engine.hpp"
@@ -29,28 +32,7 @@ constexpr uint32_t MAX_BINS = 1024;
 constexpr size_t WORKSPACE_LIMIT = 256ull << 20;   // the lists of one piece of a call
 constexpr int LIST_THREADS = 256;
 constexpr int TILE = stage::TILE;
-constexpr uint32_t WORDS = sizeof(backdrop::Tri) / 16;   // 16-byte words a record
-
-struct BackdropArgs {
-    const uint32_t* bass_lit;    // [rows] or null
-    const float* bass_rgba;      // [rows][4]
-    const float *line_pos, *line_rgba, *disc_pos, *disc_rgba, *hist_pos, *hist_rgba, *graph_pos, *graph_rgba;
-    const uint32_t* peak_count;
-    uint32_t max_peaks, line_quads, graph_quads;
-    float t_spec[4], t_hist[4], t_graph[4];
-    const float* background;     // [H][W][4] or null
-    const float* bass_quads;     // [n_bass][4][2]
-    const uint4* net;            // [n_net] records
-    uint32_t n_bass, n_net;
-    uint32_t n_streams, n_frames, f0, pf;   // the call's frames; this piece is frames f0 .. f0 + pf
-    uint32_t cap;                // records a row of the workspace holds
-    uint32_t W, H;
-    float vh;
-    float clear[4];
-    uint4* list;                 // [n_streams * pf][cap] records
-    uint32_t* counts;            // [n_streams * pf]
-    float* image;                // [n_streams][n_frames][H][W][4]
-};
+constexpr uint32_t WORDS = BACKDROP_WORDS;
 
 __global__ __launch_bounds__(LIST_THREADS) __attribute__((flatten)) void backdrop_lists(BackdropArgs a) {
 #pragma clang fp contract(off)
@@ -136,49 +118,11 @@ __global__ __launch_bounds__(LIST_THREADS) __attribute__((flatten)) void backdro
     }
 }
 
-// m records, in order, over the pixel (wx, wy) of the wave's block at (bx0, by0).  A wave that hits nothing — most waves, most of
-// the time: the layers are thin lines — waits for one load per round, so a round takes the box words of DEPTH x 64 records at once.
-__device__ __forceinline__ void walk(const uint4* list, uint32_t m, uint32_t lane, uint32_t bx0, uint32_t by0, float wx, float wy, float dst[4]) {
-#pragma clang fp contract(off)
-    constexpr uint32_t DEPTH = 4;
-    for (uint32_t c0 = 0; c0 < m; c0 += 64u * DEPTH) {   // (m is the wave's)
-        unsigned long long masks[DEPTH];
-#pragma unroll
-        for (uint32_t d = 0; d < DEPTH; ++d) {
-            const uint32_t idx = c0 + 64u * d + lane;
-            bool hit = false;
-            if (idx < m) {
-                const uint4 b = list[static_cast<size_t>(idx) * WORDS];
-                hit = !((b.x & 0xFFFFu) > bx0 + 7u || (b.x >> 16) < bx0 || (b.y & 0xFFFFu) > by0 + 7u || (b.y >> 16) < by0);
-            }
-            masks[d] = __ballot(hit);
-        }
-#pragma unroll
-        for (uint32_t d = 0; d < DEPTH; ++d) {
-            unsigned long long mask = masks[d];
-            while (mask) {
-                const uint32_t k = static_cast<uint32_t>(__builtin_ctzll(mask));        // ascending: the list's order
-                mask &= mask - 1ull;
-                const uint4* rec = list + static_cast<size_t>(c0 + 64u * d + k) * WORDS;   // wave-uniform, < m
-                const uint4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4];
-                backdrop::Tri t;
-                t.positive = q0.z;
-                t.edge[0][0] = __uint_as_float(q1.x); t.edge[0][1] = __uint_as_float(q1.y); t.edge[0][2] = __uint_as_float(q1.z); t.edge[0][3] = __uint_as_float(q1.w);
-                t.edge[1][0] = __uint_as_float(q2.x); t.edge[1][1] = __uint_as_float(q2.y); t.edge[1][2] = __uint_as_float(q2.z); t.edge[1][3] = __uint_as_float(q2.w);
-                t.edge[2][0] = __uint_as_float(q3.x); t.edge[2][1] = __uint_as_float(q3.y); t.edge[2][2] = __uint_as_float(q3.z); t.edge[2][3] = __uint_as_float(q3.w);
-                if (backdrop::covers(t, wx, wy)) {
-                    const float src[4] = {__uint_as_float(q4.x), __uint_as_float(q4.y), __uint_as_float(q4.z), __uint_as_float(q4.w)};
-                    raster::blend(src, dst);
-                }
-            }
-        }
-    }
-}
-
 __global__ __launch_bounds__(256) __attribute__((flatten)) void backdrop_tiles(BackdropArgs a) {
 #pragma clang fp contract(off)
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const stage::TilePixel px = stage::tile_pixel(wave, lane, a.W, a.H, a.vh);
+    const float wx[1] = {px.wx}, wy[1] = {px.wy};   // one sample, at the centre
     const uint32_t rows = a.n_streams * a.pf;
     for (uint32_t r = blockIdx.y; r < rows; r += gridDim.y) {
         const size_t g = stage::piece_row(r, a.pf, a.n_frames, a.f0);
@@ -187,16 +131,20 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void backdrop_tiles(B
             const float4 bg = reinterpret_cast<const float4*>(a.background)[px.pixel];
             dst[0] = bg.x; dst[1] = bg.y; dst[2] = bg.z; dst[3] = bg.w;
         }
-        walk(a.net, a.n_net, lane, px.bx0, px.by0, px.wx, px.wy, dst);
-        walk(a.list + static_cast<size_t>(r) * a.cap * WORDS, a.counts[r], lane, px.bx0, px.by0, px.wx, px.wy, dst);
+        backdrop::walk<1>(a.net, a.n_net, lane, px.bx0, px.by0, wx, wy, dst);
+        backdrop::walk<1>(a.list + static_cast<size_t>(r) * a.cap * WORDS, a.counts[r], lane, px.bx0, px.by0, wx, wy, dst);
         if (px.inside) reinterpret_cast<float4*>(a.image)[g * a.W * a.H + px.pixel] = make_float4(dst[0], dst[1], dst[2], dst[3]);
     }
 }
 }  // namespace
 
 pvq_status BackdropBatch::create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, int visuals_mode, float viewport_height,
-                                 uint32_t n_streams, uint32_t width, uint32_t height, std::unique_ptr<BackdropBatch>& out) {
+                                 uint32_t n_streams, uint32_t width, uint32_t height, std::unique_ptr<BackdropBatch>& out, uint32_t samples) {
     out.reset();
+    if (!backdrop::samples_ok(samples)) {
+        set_last_error("backdrop batch: samples is 1 or 4");
+        return PVQ_ERR_INVALID_ARG;
+    }
     if (octaves == 0 || buckets_per_octave == 0 || n_streams == 0) {
         set_last_error("backdrop batch: octaves, buckets_per_octave and n_streams must be positive");
         return PVQ_ERR_INVALID_ARG;
@@ -223,6 +171,7 @@ pvq_status BackdropBatch::create(int device_id, uint32_t octaves, uint32_t bucke
     b->height_ = height;
     b->vh_ = viewport_height == 0.0f ? raster::VIEWPORT_HEIGHT : viewport_height;
     b->galaxy_ = visuals_mode == scene::GALAXY;
+    b->samples_ = samples;
     raster::clear_color(visuals_mode, b->clear_);
     if (device_id >= 0) {
         PVQ_HIP(hipSetDevice(device_id));
@@ -344,7 +293,9 @@ pvq_status BackdropBatch::frames_device(size_t n_frames, const pvq_backdrop_inpu
         a.pf = static_cast<uint32_t>(std::min(pf, n_frames - f0));
         const size_t rows_here = static_cast<size_t>(n_streams_) * a.pf;
         hipLaunchKernelGGL(backdrop_lists, dim3(static_cast<unsigned>(std::min<size_t>(rows_here, 256 * 32))), dim3(LIST_THREADS), 0, stream, a);
-        hipLaunchKernelGGL(backdrop_tiles, dim3(tiles, static_cast<unsigned>(std::min<size_t>(rows_here, 65535))), dim3(256), 0, stream, a);
+        const dim3 grid(tiles, static_cast<unsigned>(std::min<size_t>(rows_here, 65535)));
+        if (samples_ == 4u) launch_backdrop_tiles_msaa(a, grid, stream);
+        else hipLaunchKernelGGL(backdrop_tiles, grid, dim3(256), 0, stream, a);
     }
     PVQ_HIP(hipGetLastError());
     return PVQ_OK;

@@ -14,6 +14,13 @@
 // vertex.  p is inside when, for all three edges, e has the triangle's sign, or e == 0 and the triangle's sign is positive: an edge
 // through a pixel centre goes to exactly one of the two triangles beside it.  Both windings are drawn.  A triangle with a zero or
 // non-finite sign, a non-finite vertex or a non-finite colour draws nothing.
+//
+// Multisampling (samples = 4; the reference's desktop and wasm builds, Msaa::Sample4).  A pixel has four samples at the standard
+// positions (sample_fraction below), each with a destination of its own that starts from the clear colour or the background's
+// pixel.  Every sample runs the rule above unchanged at its own position — a tie e == 0 still goes to the triangle whose sign is
+// positive, and two triangles that share an edge still compute the same number for it at every sample — and a covered sample is
+// blended with the triangle's flat colour, in list order.  At the end of the backdrop the pixel is the unweighted mean of its
+// samples (resolve4).  samples = 1 is the rule above: one sample at (0.5, 0.5).
 #pragma once
 
 #include <cstddef>
@@ -129,6 +136,13 @@ PVQ_HD int make_edge(float ax, float ay, float bx, float by, float cx, float cy,
 // pixel.  false: nothing of the triangle is on the image.  The arithmetic is double precision and not held to one evaluation order
 // (the device may contract it): the host's and the device's box of a triangle need not be equal, and nothing may rely on that —
 // both contain every pixel the rule covers, which is all the pictures depend on.
+//
+// With four samples the same box holds every pixel that has a covered sample.  For the left side: a covered sample lies at
+// x >= xmin - slack (the argument above is about a position, not about a centre), and the sample of column i lies at
+// (i + fx - 0.5 W) s with fx <= 0.875, so i >= A + 0.5 - fx >= A - 0.375 with A = (xmin - slack) / s + 0.5 W - 0.5, and since i is
+// a whole number i >= floor(A) > floor(A) - 1, the box's first column.  No sample is further than 0.375 pixel from its centre and
+// the box is widened by a whole pixel on every side, so the other three sides go the same way.  The multisampled parity tests,
+// whose model uses no boxes, are the check.
 PVQ_HD bool tri_box(const float v[6], uint32_t W, uint32_t H, float vh, uint32_t& box_x, uint32_t& box_y) {
     const double s = static_cast<double>(vh / static_cast<float>(H));
     const double x0 = v[0], y0 = v[1], x1 = v[2], y1 = v[3], x2 = v[4], y2 = v[5];
@@ -188,6 +202,40 @@ PVQ_HD bool covers(const Tri& t, float px, float py) {
         in = in && (((t.positive >> k) & 1u) ? e >= 0.0f : e < 0.0f);
     }
     return in;
+}
+
+// ---- multisampling: the sample positions, a sample's world position, the resolve ----
+constexpr uint32_t MAX_SAMPLES = 4;
+PVQ_HD bool samples_ok(uint32_t samples) { return samples == 1u || samples == 4u; }
+
+// sample k of `samples` (1 or 4), in pixel units from the pixel's top-left corner: the standard four-sample pattern that Vulkan's
+// standard sample locations, D3D and Metal share, in their order; one sample sits at the centre
+PVQ_HD void sample_fraction(uint32_t samples, uint32_t k, float& fx, float& fy) {
+    if (samples == 1u) {
+        fx = 0.5f;
+        fy = 0.5f;
+        return;
+    }
+    fx = k == 0u ? 0.375f : (k == 1u ? 0.875f : (k == 2u ? 0.125f : 0.625f));
+    fy = k == 0u ? 0.125f : (k == 1u ? 0.375f : (k == 2u ? 0.625f : 0.875f));
+}
+
+// The world position of the point (fx, fy) of pixel (i, j): raster::pixel_world with 0.5 replaced by the fractions, and with
+// (0.5, 0.5) that function bit for bit (the same expressions in the same order).  i + fx and j + fy are exact for every admitted
+// image: the sides are <= 4096 = 2^12 and the fractions are eighths, so the sum needs 15 of f32's 24 bits.
+PVQ_HD void sample_world(uint32_t i, uint32_t j, uint32_t W, uint32_t H, float vh, float fx, float fy, float& wx, float& wy) {
+    PVQ_FP_STRICT
+    const float s = vh / static_cast<float>(H);
+    wx = (static_cast<float>(i) + fx - 0.5f * static_cast<float>(W)) * s;
+    wy = (0.5f * static_cast<float>(H) - (static_cast<float>(j) + fy)) * s;
+}
+
+// The resolve of one channel: the unweighted mean, in this order.  Four equal finite samples x with |x| < 2^126 resolve to
+// exactly x: x + x = 2x and 2x + 2x = 4x are exact below the overflow threshold (|4x| < 2^128), and * 0.25 is exact for a normal
+// result and for a subnormal x too (4x / 4 is x again, representable).  Pictures with channels at or beyond 2^126 are not promised.
+PVQ_HD float resolve4(float s0, float s1, float s2, float s3) {
+    PVQ_FP_STRICT
+    return ((s0 + s1) + (s2 + s3)) * 0.25f;
 }
 
 // the vertex numbers of triangle t of a mesh of quads (4 vertices each) or of discs (13 each)

@@ -99,37 +99,48 @@ pvq_status pvq_backdrop_panel_transforms(uint32_t n_bins, uint32_t width, uint32
         return PVQ_OK;
     });
 }
+namespace {
+// the one-mesh face and the one-frame face behind their one-sample and multisampled entry points: `who` heads the messages
+pvq_status backdrop_mesh(const std::string& who, uint32_t samples, uint32_t width, uint32_t height, float viewport_height, size_t n_triangles,
+                         const float* pos, const float* rgba, const float* transform, float* image_inout) {
+    if (!pvq::backdrop::samples_ok(samples)) return invalid_arg(who + ": samples is 1 or 4");
+    if (!image_inout || (n_triangles && (!pos || !rgba))) return invalid_arg(who + ": image_inout is needed, and pos and rgba with n_triangles > 0");
+    std::string err;
+    if (!pvq::stage_image_ok(who.c_str(), width, height, viewport_height, err)) return invalid_arg(err);
+    pvq::backdrop_draw_mesh(width, height, viewport_or_default(viewport_height), n_triangles, pos, rgba, transform, image_inout, samples);
+    return PVQ_OK;
+}
+pvq_status backdrop_one_frame(const std::string& who, uint32_t samples, uint32_t octaves, uint32_t buckets_per_octave, uint32_t width,
+                              uint32_t height, float viewport_height, int visuals_mode, uint32_t bass_lit, const float* bass_rgba,
+                              const pvq_backdrop_panels* panels, const float* background, float* image_out) {
+    if (!pvq::backdrop::samples_ok(samples)) return invalid_arg(who + ": samples is 1 or 4");
+    if (!image_out || (bass_lit && !bass_rgba)) return invalid_arg(who + ": image_out is needed, and bass_rgba with bass_lit > 0");
+    const uint64_t n = static_cast<uint64_t>(octaves) * buckets_per_octave;
+    if (octaves == 0 || buckets_per_octave == 0 || octaves > 1024 || n < 2 || n > 0x7FFFFFFFull)
+        return invalid_arg(who + ": octaves 1 .. 1024, buckets_per_octave positive, at least two bins");
+    std::string err;
+    if (!pvq::stage_image_ok(who.c_str(), width, height, viewport_height, err) || !pvq::stage_mode_ok(who.c_str(), visuals_mode, err))
+        return invalid_arg(err);
+    if (panels && (!panels->line_pos != !panels->line_rgba || !panels->disc_pos != !panels->disc_rgba ||
+                   !panels->hist_pos != !panels->hist_rgba || !panels->graph_pos != !panels->graph_rgba ||
+                   (panels->graph_pos && panels->graph_capacity < 2))) {
+        return invalid_arg(who + ": a mesh needs its positions and its colours, the graph its graph_capacity >= 2");
+    }
+    pvq::backdrop_frame(octaves, buckets_per_octave, width, height, viewport_or_default(viewport_height), visuals_mode, bass_lit, bass_rgba, panels,
+                        background, image_out, samples);
+    return PVQ_OK;
+}
+}  // namespace
 pvq_status pvq_backdrop_draw_mesh(uint32_t width, uint32_t height, float viewport_height, size_t n_triangles, const float* pos, const float* rgba,
                                   const float* transform, float* image_inout) {
-    return guarded([&] {
-        if (!image_inout || (n_triangles && (!pos || !rgba)))
-            return invalid_arg("backdrop draw mesh: image_inout is needed, and pos and rgba with n_triangles > 0");
-        std::string err;
-        if (!pvq::stage_image_ok("backdrop draw mesh", width, height, viewport_height, err)) return invalid_arg(err);
-        pvq::backdrop_draw_mesh(width, height, viewport_or_default(viewport_height), n_triangles, pos, rgba,
-                                transform, image_inout);
-        return PVQ_OK;
-    });
+    return guarded([&] { return backdrop_mesh("backdrop draw mesh", 1, width, height, viewport_height, n_triangles, pos, rgba, transform, image_inout); });
 }
 pvq_status pvq_backdrop_frame(uint32_t octaves, uint32_t buckets_per_octave, uint32_t width, uint32_t height, float viewport_height,
                               int visuals_mode, uint32_t bass_lit, const float* bass_rgba, const pvq_backdrop_panels* panels,
                               const float* background, float* image_out) {
     return guarded([&] {
-        if (!image_out || (bass_lit && !bass_rgba)) return invalid_arg("backdrop frame: image_out is needed, and bass_rgba with bass_lit > 0");
-        const uint64_t n = static_cast<uint64_t>(octaves) * buckets_per_octave;
-        if (octaves == 0 || buckets_per_octave == 0 || octaves > 1024 || n < 2 || n > 0x7FFFFFFFull)
-            return invalid_arg("backdrop frame: octaves 1 .. 1024, buckets_per_octave positive, at least two bins");
-        std::string err;
-        if (!pvq::stage_image_ok("backdrop frame", width, height, viewport_height, err) || !pvq::stage_mode_ok("backdrop frame", visuals_mode, err))
-            return invalid_arg(err);
-        if (panels && (!panels->line_pos != !panels->line_rgba || !panels->disc_pos != !panels->disc_rgba ||
-                       !panels->hist_pos != !panels->hist_rgba || !panels->graph_pos != !panels->graph_rgba ||
-                       (panels->graph_pos && panels->graph_capacity < 2))) {
-            return invalid_arg("backdrop frame: a mesh needs its positions and its colours, the graph its graph_capacity >= 2");
-        }
-        pvq::backdrop_frame(octaves, buckets_per_octave, width, height, viewport_or_default(viewport_height),
-                            visuals_mode, bass_lit, bass_rgba, panels, background, image_out);
-        return PVQ_OK;
+        return backdrop_one_frame("backdrop frame", 1, octaves, buckets_per_octave, width, height, viewport_height, visuals_mode, bass_lit, bass_rgba,
+                                  panels, background, image_out);
     });
 }
 pvq_status pvq_backdrop_batch_create(int device_id, uint32_t octaves, uint32_t buckets_per_octave, int visuals_mode, float viewport_height,
@@ -156,6 +167,41 @@ pvq_status pvq_backdrop_balls_over_device(pvq_raster_batch* b, size_t n_frames, 
         const pvq_raster_inputs no_in{};
         return b->impl->frames_device(n_frames, in ? *in : no_in, elapsed_s, d_image_inout, d_ball_time, static_cast<hipStream_t>(stream), true);
     });
+}
+
+// The backdrop multisampled (backdrop_math.hpp: four samples a pixel, resolved at the end of the stage): the faces above with a
+// sample count in front.  samples is checked first, before any device is touched; 1 gives the one-sample faces' bits.
+pvq_status pvq_msaa_sample_positions(uint32_t samples, float* xy_out) {
+    return guarded([&] {
+        if (!pvq::backdrop::samples_ok(samples)) return invalid_arg("msaa sample positions: samples is 1 or 4");
+        if (!xy_out) return invalid_arg("msaa sample positions: xy_out is needed");
+        for (uint32_t k = 0; k < samples; ++k) pvq::backdrop::sample_fraction(samples, k, xy_out[2 * k], xy_out[2 * k + 1]);
+        return PVQ_OK;
+    });
+}
+pvq_status pvq_msaa_draw_mesh(uint32_t samples, uint32_t width, uint32_t height, float viewport_height, size_t n_triangles, const float* pos,
+                              const float* rgba, const float* transform, float* image_inout) {
+    return guarded([&] { return backdrop_mesh("msaa draw mesh", samples, width, height, viewport_height, n_triangles, pos, rgba, transform, image_inout); });
+}
+pvq_status pvq_msaa_frame(uint32_t samples, uint32_t octaves, uint32_t buckets_per_octave, uint32_t width, uint32_t height, float viewport_height,
+                          int visuals_mode, uint32_t bass_lit, const float* bass_rgba, const pvq_backdrop_panels* panels, const float* background,
+                          float* image_out) {
+    return guarded([&] {
+        return backdrop_one_frame("msaa frame", samples, octaves, buckets_per_octave, width, height, viewport_height, visuals_mode, bass_lit, bass_rgba,
+                                  panels, background, image_out);
+    });
+}
+pvq_status pvq_msaa_batch_create(uint32_t samples, int device_id, uint32_t octaves, uint32_t buckets_per_octave, int visuals_mode,
+                                 float viewport_height, uint32_t n_streams, uint32_t width, uint32_t height, pvq_backdrop_batch** out) {
+    return guarded([&] {
+        return make_handle(out, [&](auto& impl) {
+            return pvq::BackdropBatch::create(device_id, octaves, buckets_per_octave, visuals_mode, viewport_height, n_streams, width, height, impl,
+                                              samples);
+        });
+    });
+}
+uint32_t pvq_msaa_batch_samples(const pvq_backdrop_batch* b) {
+    return guarded(0u, [&] { return b ? b->impl->samples() : 0u; });
 }
 
 // The spectrogram quad and the chroma boxes in front of the balls (setup.rs:418-541, update.rs:929-1172, spectrogram_scroll.wgsl):
