@@ -1123,6 +1123,88 @@ pvq_status pvq_text_batch_rows_device(pvq_text_batch *b, size_t n_rows, float *d
 /* the layer copied back as a full image out [height][width] (synchronises): label 0 .. n - 1, or -1: the largest over the labels */
 pvq_status pvq_text_batch_get_coverage(pvq_text_batch *b, int label, float *out);
 
+/* ---- the readout: the tuning-drift text, formatted and drawn row by row ----------------------------------------------
+ * The bottom-right readout "Tuning drift: NNN" of the viewer's Debugging display mode (pitchvis_viewer/src/app/common.rs:348-432:
+ * setup_analysis_text, update_analysis_text_system, analysis_text_showhide): a half-transparent black box, a white prefix, and the
+ * rounded smoothed tuning-grid inaccuracy coloured green -> yellow -> red.  The stage is an in-place blend over a finished linear
+ * image, run after pvq_overlay_batch_frames_device and before the present stage, in the Debugging display mode only (in the others
+ * the caller does not call it).  Like the chroma boxes it is UI and stays in the linear target.  The value is one f32 a row,
+ * laid out as pvq_analysis_batch_* writes tuning_grid_inaccuracy.  Bevy's UI text pipeline is not in the reference tree; the rule
+ * below is this library's own, and DESIGN.md 6k lists what it assumes.  The font is the caller's (a pvq_text_font).  The FPS
+ * counter (wall clock) and the bottom-left dump of settings are not drawn.
+ *
+ * Text.  r = roundf(v) (half away from zero, f32::round); the value text is Rust's format!("{r:>3.0}"): the integer's decimal
+ * digits, '-' for a negative r, spaces on the left up to three characters.  Negative zero counts as negative (-0.4 gives " -0");
+ * NaN gives "NaN", +inf "inf", -inf "-inf".  A finite |r| above 2 147 483 520 (the largest f32 below 2^31) is formatted as that
+ * bound, so the value text has at most 11 characters: a deviation from the reference, which would print up to 39 digits; the
+ * analysis cannot produce such a value.  The string is "Tuning drift: " and the value text: at most 25 glyph slots.
+ *
+ * Colour of the value text (common.rs:404-413), a = |r|, in f32 in the reference's order: a <= 10: (0, 1, 0); a <= 20:
+ * ((a - 10) / 10, 1, 0); a <= 30: (1, 1 - (a - 20) / 10, 0); otherwise, NaN included, (1, 0, 0).  sRGB; each channel goes through
+ * the scene section's srgb_to_linear.  The prefix is white.
+ *
+ * Atlas.  s = ui_scale (0: 1), the font size is F = 16 s output pixels (f32), k = F / units_per_em (double).  Each codepoint the
+ * stage can emit — T u n i g d r f t, the space, ':', 0-9, '-', N, a — is rasterised once: its origin at pixel column 0, its
+ * baseline on pixel row 0, a point (gx, gy) at (gx k, -gy k) in double; flattened as the text section's (tolerance 1 / 64 pixel,
+ * chord ends rounded once to f32, horizontal chords dropped); coverage of a pixel by the text section's rule, unchanged.  A glyph's
+ * cell is the pixel box its outline's bounding box meets, relative to (origin column, baseline row): a left bearing makes it
+ * start at a negative column.  A codepoint the font lacks is PVQ_ERR_INVALID_ARG naming it, at create.
+ *
+ * Layout, f32 in this order, pixel coordinates from the top left: adv[c] = (float)(advance_c k), rounded once; the pen is the
+ * sequential left fold p_0 = 0, p_(i+1) = p_i + adv[c_i], the text's width Wt = p_n; the node's box xr = W - 0.01f W,
+ * yb = H - 0.01f H, xl = xr - Wt, yt = yb - 1.2f F; glyph i's origin column is floorf(xl + p_i + 0.5f), the baseline row
+ * floorf(yt + b + 0.5f), b = (float)((1.2f F - (ascent - descent) k) / 2 + ascent k) in double: the text section's baseline inside
+ * a line.  There is no sub-pixel glyph positioning: that is what makes an atlas valid.
+ *
+ * Blend.  First the box: the pixels whose centre (i + 0.5, j + 0.5) lies in [xl, xr) x [yt, yb), black at alpha 0.5, the raster
+ * section's blend.  Then the glyphs in string order, each its span's colour at alpha = the atlas coverage; a coverage of exactly
+ * 0 is not blended.  A pixel that neither the box nor a glyph covers is neither read nor written; glyph cells may reach outside
+ * the box and are drawn there.  Everything is clipped to the image.  f32 without FMA contraction: the host face and the device
+ * carry the same bits.
+ *
+ * Limits: width, height 1 .. 4096; ui_scale 0 or positive and finite with F at most 1024; at most 65536 chords a glyph; an atlas of
+ * at most 256 MiB, PVQ_ERR_UNSUPPORTED beyond; n_rows at most 2^31 - 1; the image 16-byte aligned. */
+#define PVQ_READOUT_MAX_SLOTS 25
+/* The value text of `value` (NUL-terminated, at most 11 characters) and its sRGB colour; either may be NULL. */
+pvq_status pvq_readout_text(float value, char text_out[12], float srgb_out[3]);
+/* what the layout makes of a value on a width x height image */
+typedef struct pvq_readout_layout {
+    float xl, xr, yt, yb;                        /* the node's box */
+    float text_width, font_px, baseline;         /* Wt, F, b */
+    int32_t baseline_row;
+    uint32_t n_slots;                            /* glyph slots of the string, 17 .. 25 */
+    char text[PVQ_READOUT_MAX_SLOTS + 3];        /* the whole string, NUL-terminated */
+    int32_t origin_x[PVQ_READOUT_MAX_SLOTS];     /* each slot's origin column */
+    int32_t cell_x0[PVQ_READOUT_MAX_SLOTS];      /* each slot's placed cell on the image (not clipped): first column and row, */
+    int32_t cell_y0[PVQ_READOUT_MAX_SLOTS];
+    uint32_t cell_w[PVQ_READOUT_MAX_SLOTS];      /* width and height; 0 x 0: no outline (the space) */
+    uint32_t cell_h[PVQ_READOUT_MAX_SLOTS];
+    float value_srgb[3], value_linear[3];        /* the value text's colour */
+} pvq_readout_layout;
+pvq_status pvq_readout_layout_query(pvq_text_font *font, float value, uint32_t width, uint32_t height, float ui_scale,
+                                    pvq_readout_layout *out);
+/* One picture on the host: the readout of `value` over image_inout [height][width][4], in place. */
+pvq_status pvq_readout_frame(pvq_text_font *font, float value, uint32_t width, uint32_t height, float ui_scale, float *image_inout);
+
+/* The same for MANY rows on the GPU, each row its own value: the device formats the value, lays the string out and draws it.  The
+ * handle owns the glyph atlas, computed on the device once at create. */
+typedef struct pvq_readout_batch_s pvq_readout_batch;
+/* The arguments are checked, and the atlas laid out, before any device is touched; the font is not needed after the call.
+ * device_id < 0: a host-only handle whose rows_device returns PVQ_ERR_NO_DEVICE after its argument checks, and whose atlas is the
+ * host face's. */
+pvq_status pvq_readout_batch_create(int device_id, pvq_text_font *font, uint32_t width, uint32_t height, float ui_scale,
+                                    pvq_readout_batch **out);
+void pvq_readout_batch_destroy(pvq_readout_batch *b);
+/* The readout of d_values[row] over each of n_rows pictures d_image_inout [n_rows][height][width][4] (16-byte aligned), in place:
+ * a pixel is read and written by the same lane.  d_values [n_rows] f32 in device memory, as pvq_analysis_batch_* leaves
+ * tuning_grid_inaccuracy [stream][frame].  Asynchronous on `stream`; one handle's calls are stream-ordered. */
+pvq_status pvq_readout_batch_rows_device(pvq_readout_batch *b, size_t n_rows, const float *d_values, float *d_image_inout, void *stream);
+/* A codepoint's atlas cell: its box relative to (origin column, baseline row), its advance in pixels, and its coverages to
+ * out [h][w] where out is given (cap_floats at least w h; ask for the size first).  Any pointer may be NULL.  Synchronises.  A
+ * codepoint the readout never emits is PVQ_ERR_INVALID_ARG. */
+pvq_status pvq_readout_batch_get_atlas(pvq_readout_batch *b, uint32_t codepoint, int32_t *x0, int32_t *y0, uint32_t *w, uint32_t *h,
+                                       float *advance, size_t cap_floats, float *out);
+
 /* ---- the present stage: bloom, display transform and sRGB bytes ----------------------------------------------------
  * What turns the linear HDR target [H][W][4] of the sections above into something a screen, a PNG or a video encoder takes: the
  * camera's Bloom, its Tonemapping::SomewhatBoringDisplayTransform and the surface's sRGB encode.  The reference fixes the settings
@@ -1162,7 +1244,8 @@ pvq_status pvq_text_batch_get_coverage(pvq_text_batch *b, int label, float *out)
  * Left out of the displayed picture, here and in every section above: MSAA beyond the backdrop's (which the pvq_msaa_ entries
  * draw with samples = 4; the overlay quad's border pixels are left out), the deband dither, colour grading
  * (the reference leaves it at identity) and a draw of the chroma boxes in display space — they stay where the overlay stage blends
- * them, in the linear target, and so pass through the transform. */
+ * them, in the linear target, and so pass through the transform.  The Debugging mode's tuning-drift text is drawn: the readout
+ * section above, also in the linear target; the FPS counter and the dump of settings are not. */
 enum { PVQ_PRESENT_ENERGY_CONSERVING = 0, PVQ_PRESENT_ADDITIVE = 1 };          /* composite_mode */
 enum { PVQ_PRESENT_TONEMAP_NONE = 0, PVQ_PRESENT_TONEMAP_SOMEWHAT_BORING = 1 }; /* tonemapping */
 typedef struct pvq_present_settings {

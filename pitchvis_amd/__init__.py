@@ -644,6 +644,7 @@ from .raster import RasterBatch, raster_frame, raster_shade, raster_touch  # noq
 from .backdrop import BackdropBatch, backdrop_draw_mesh, backdrop_frame, backdrop_geometry, msaa_sample_positions, panel_transforms  # noqa: E402,F401
 from .overlay import OverlayBatch, OverlayState, overlay_frame, overlay_quad  # noqa: E402,F401
 from .text import TextBatch, TextFont, TextLabel, pitch_name_labels, text_frame, text_layout  # noqa: E402,F401
+from .readout import ReadoutBatch, readout_frame, readout_layout, readout_text  # noqa: E402,F401
 from .present import PresentBatch, present_blend_factors, present_frame, present_mips, present_settings  # noqa: E402,F401
 from .panels import CalmnessGraph, PanelsBatch, calmness_histogram_mesh, panel_topology, spectrum_mesh  # noqa: E402,F401
 from .note_model import NoteModel, NoteModelParams  # noqa: E402,F401

@@ -53,6 +53,8 @@ EXPORTS = [
     "pvq_text_font_from_ttf", "pvq_text_font_from_outlines", "pvq_text_font_destroy", "pvq_text_font_metrics", "pvq_text_font_glyph",
     "pvq_text_pitch_labels", "pvq_text_layout_query", "pvq_text_frame", "pvq_text_batch_create", "pvq_text_batch_destroy",
     "pvq_text_batch_rows_device", "pvq_text_batch_get_coverage",
+    "pvq_readout_text", "pvq_readout_layout_query", "pvq_readout_frame", "pvq_readout_batch_create", "pvq_readout_batch_destroy",
+    "pvq_readout_batch_rows_device", "pvq_readout_batch_get_atlas",
     "pvq_present_default_settings", "pvq_present_mips", "pvq_present_blend_factors", "pvq_present_frame", "pvq_present_batch_create",
     "pvq_present_batch_destroy", "pvq_present_batch_set_workspace_limit", "pvq_present_batch_rows_device",
     "pvq_synth_bank_create", "pvq_synth_bank_destroy", "pvq_synth_bank_counts", "pvq_synth_state_create", "pvq_synth_state_destroy",
@@ -172,6 +174,17 @@ class CTextLabel(C.Structure):   # pvq_text_label
 class CTextLayout(C.Structure):   # pvq_text_layout
     _fields_ = [("on_image", C.c_uint32), ("x0", C.c_uint32), ("y0", C.c_uint32), ("x1", C.c_uint32), ("y1", C.c_uint32), ("n_segments", C.c_uint32),
                 ("n_tiles", C.c_uint32), ("origin_x", C.c_float), ("baseline_y", C.c_float)]
+
+
+READOUT_MAX_SLOTS = 25   # PVQ_READOUT_MAX_SLOTS
+
+
+class CReadoutLayout(C.Structure):   # pvq_readout_layout
+    _fields_ = [(n, C.c_float) for n in ("xl", "xr", "yt", "yb", "text_width", "font_px", "baseline")] + \
+               [("baseline_row", C.c_int32), ("n_slots", C.c_uint32), ("text", C.c_char * (READOUT_MAX_SLOTS + 3))] + \
+               [(n, C.c_int32 * READOUT_MAX_SLOTS) for n in ("origin_x", "cell_x0", "cell_y0")] + \
+               [(n, C.c_uint32 * READOUT_MAX_SLOTS) for n in ("cell_w", "cell_h")] + \
+               [("value_srgb", C.c_float * 3), ("value_linear", C.c_float * 3)]
 
 
 class CSynthRecord(C.Structure):   # pvq_synth_record
@@ -447,6 +460,15 @@ def load():
     L.pvq_text_batch_destroy.argtypes = [vp]; L.pvq_text_batch_destroy.restype = None
     L.pvq_text_batch_rows_device.argtypes = [vp, C.c_size_t, vp, vp]; L.pvq_text_batch_rows_device.restype = C.c_int
     L.pvq_text_batch_get_coverage.argtypes = [vp, C.c_int, fp]; L.pvq_text_batch_get_coverage.restype = C.c_int
+    ip = C.POINTER(C.c_int32)
+    L.pvq_readout_text.argtypes = [C.c_float, C.c_char_p, fp]; L.pvq_readout_text.restype = C.c_int
+    L.pvq_readout_layout_query.argtypes = [vp, C.c_float, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(CReadoutLayout)]
+    L.pvq_readout_layout_query.restype = C.c_int
+    L.pvq_readout_frame.argtypes = [vp, C.c_float, C.c_uint32, C.c_uint32, C.c_float, fp]; L.pvq_readout_frame.restype = C.c_int
+    L.pvq_readout_batch_create.argtypes = [C.c_int, vp, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(vp)]; L.pvq_readout_batch_create.restype = C.c_int
+    L.pvq_readout_batch_destroy.argtypes = [vp]; L.pvq_readout_batch_destroy.restype = None
+    L.pvq_readout_batch_rows_device.argtypes = [vp, C.c_size_t, vp, vp, vp]; L.pvq_readout_batch_rows_device.restype = C.c_int
+    L.pvq_readout_batch_get_atlas.argtypes = [vp, C.c_uint32, ip, ip, up, up, fp, C.c_size_t, fp]; L.pvq_readout_batch_get_atlas.restype = C.c_int
     psp = C.POINTER(CPresentSettings)
     L.pvq_present_default_settings.argtypes = [psp]; L.pvq_present_default_settings.restype = None
     L.pvq_present_mips.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, up, up]; L.pvq_present_mips.restype = C.c_int

@@ -11,6 +11,8 @@
 #include "overlay_host.hpp"
 #include "raster_batch.hpp"
 #include "raster_host.hpp"
+#include "readout_batch.hpp"
+#include "readout_host.hpp"
 #include "stage_plan.hpp"
 #include "text_batch.hpp"
 #include "text_host.hpp"
@@ -413,6 +415,89 @@ pvq_status pvq_text_batch_get_coverage(pvq_text_batch* b, int label, float* out)
     return guarded([&] {
         if (!b) return null_handle();
         return b->impl->get_coverage(label, out);
+    });
+}
+
+// The tuning-drift readout over the finished picture (common.rs:348-432): the value's text and colour, one picture on the host
+// (readout_host.hpp) and many rows, each its own value, on the device (readout_batch.hpp)
+pvq_status pvq_readout_text(float value, char text_out[12], float srgb_out[3]) {
+    return guarded([&] {
+        uint64_t text;
+        float r;
+        const uint32_t n = pvq::readout::value_glyphs(value, text, r);
+        if (text_out) {
+            for (uint32_t k = 0; k < n; ++k) text_out[k] = static_cast<char>(pvq::readout::codepoint_of(pvq::readout::slot_glyph(text, pvq::readout::N_PREFIX + k)));
+            text_out[n] = 0;
+        }
+        if (srgb_out) pvq::readout::value_srgb(r, srgb_out);
+        return PVQ_OK;
+    });
+}
+namespace {
+pvq_status readout_plan_of(const char* who, pvq_text_font* font, uint32_t width, uint32_t height, float ui_scale, pvq::ReadoutPlan& plan) {
+    std::string err;
+    const pvq_status st = pvq::readout_plan(who, *font->impl, width, height, ui_scale, plan, err);
+    if (st != PVQ_OK) pvq::set_last_error(err);
+    return st;
+}
+}  // namespace
+pvq_status pvq_readout_layout_query(pvq_text_font* font, float value, uint32_t width, uint32_t height, float ui_scale, pvq_readout_layout* out) {
+    return guarded([&] {
+        if (!font) return null_handle();
+        if (!out) return invalid_arg("readout layout: out is needed");
+        pvq::ReadoutPlan plan;
+        if (pvq_status st = readout_plan_of("readout layout", font, width, height, ui_scale, plan)) return st;
+        pvq::ReadoutRow row;
+        pvq::readout_row(plan, value, row);
+        std::memset(out, 0, sizeof(*out));
+        out->xl = row.box.xl, out->xr = row.box.xr, out->yt = row.box.yt, out->yb = row.box.yb;
+        out->text_width = row.text_width, out->font_px = plan.font_px, out->baseline = plan.baseline;
+        out->baseline_row = row.baseline_row;
+        out->n_slots = row.n_slots;
+        for (uint32_t s = 0; s < row.n_slots; ++s) {
+            const pvq::readout::Cell& c = plan.cells[row.glyph[s]];
+            out->text[s] = static_cast<char>(pvq::readout::codepoint_of(row.glyph[s]));
+            out->origin_x[s] = row.origin_x[s];
+            out->cell_x0[s] = row.origin_x[s] + c.x0;
+            out->cell_y0[s] = row.baseline_row + c.y0;
+            out->cell_w[s] = c.w;
+            out->cell_h[s] = c.h;
+        }
+        for (int c = 0; c < 3; ++c) out->value_srgb[c] = row.value_srgb[c], out->value_linear[c] = row.value_linear[c];
+        return PVQ_OK;
+    });
+}
+pvq_status pvq_readout_frame(pvq_text_font* font, float value, uint32_t width, uint32_t height, float ui_scale, float* image_inout) {
+    return guarded([&] {
+        if (!font) return null_handle();
+        if (!image_inout) return invalid_arg("readout frame: image_inout is needed");
+        pvq::ReadoutPlan plan;
+        if (pvq_status st = readout_plan_of("readout frame", font, width, height, ui_scale, plan)) return st;
+        pvq::readout_cover(plan);
+        pvq::readout_frame(plan, value, image_inout);
+        return PVQ_OK;
+    });
+}
+pvq_status pvq_readout_batch_create(int device_id, pvq_text_font* font, uint32_t width, uint32_t height, float ui_scale, pvq_readout_batch** out) {
+    return guarded([&] {
+        return make_handle(out, [&](auto& impl) {
+            if (!font) return null_handle();
+            return pvq::ReadoutBatch::create(device_id, *font->impl, width, height, ui_scale, impl);
+        });
+    });
+}
+void pvq_readout_batch_destroy(pvq_readout_batch* b) { destroy(b); }
+pvq_status pvq_readout_batch_rows_device(pvq_readout_batch* b, size_t n_rows, const float* d_values, float* d_image_inout, void* stream) {
+    return guarded([&] {
+        if (!b) return null_handle();
+        return b->impl->rows_device(n_rows, d_values, d_image_inout, static_cast<hipStream_t>(stream));
+    });
+}
+pvq_status pvq_readout_batch_get_atlas(pvq_readout_batch* b, uint32_t codepoint, int32_t* x0, int32_t* y0, uint32_t* w, uint32_t* h, float* advance,
+                                       size_t cap_floats, float* out) {
+    return guarded([&] {
+        if (!b) return null_handle();
+        return b->impl->get_atlas(codepoint, x0, y0, w, h, advance, cap_floats, out);
     });
 }
 

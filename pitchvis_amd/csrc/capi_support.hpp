@@ -29,6 +29,7 @@ class BackdropBatch;
 class OverlayBatch;
 class TextFont;
 class TextBatch;
+class ReadoutBatch;
 class SynthBank;
 class SynthState;
 class SynthBatch;
@@ -83,6 +84,9 @@ struct pvq_text_font {
 };
 struct pvq_text_batch {
     std::unique_ptr<pvq::TextBatch> impl;
+};
+struct pvq_readout_batch_s {
+    std::unique_ptr<pvq::ReadoutBatch> impl;
 };
 struct pvq_synth_bank {
     std::shared_ptr<const pvq::SynthBank> impl;

@@ -76,9 +76,7 @@ std::string name_of(uint32_t cp) {
     return t;
 }
 
-struct Pt {
-    double x, y;
-};
+using Pt = TextPoint;
 }  // namespace
 
 // ---- the font -------------------------------------------------------------------------------------------------------------------
@@ -376,6 +374,16 @@ bool flatten_contour(const std::vector<Pt>& pts, const std::vector<uint8_t>& on,
 }
 }  // namespace
 
+bool text_contour_chords(const TextGlyph& g, uint32_t first, uint32_t last, const TextMap& map, std::vector<TextPoint>& poly) {
+    std::vector<Pt> contour;
+    std::vector<uint8_t> on;
+    for (uint32_t q = first; q <= last; ++q) {
+        contour.push_back(map(g.points[2 * q], g.points[2 * q + 1]));
+        on.push_back(g.on_curve[q]);
+    }
+    return flatten_contour(contour, on, poly);
+}
+
 pvq_status text_plan(const char* who, TextFont& font, const pvq_text_label* labels, uint32_t n, uint32_t W, uint32_t H, float vh,
                      std::vector<TextLabelPlan>& out, std::string& err) {
     out.clear();
@@ -386,8 +394,7 @@ pvq_status text_plan(const char* who, TextFont& font, const pvq_text_label* labe
     const double s = static_cast<double>(vh / static_cast<float>(H));   // raster::pixel_world's world units per pixel
     const double upem = font.units_per_em();
     out.resize(n);
-    std::vector<Pt> contour, poly;
-    std::vector<uint8_t> on;
+    std::vector<Pt> poly;
     for (uint32_t l = 0; l < n; ++l) {
         const pvq_text_label& lab = labels[l];
         TextLabelPlan& plan = out[l];
@@ -446,23 +453,20 @@ pvq_status text_plan(const char* who, TextFont& font, const pvq_text_label* labe
             const double wx = lab.x + fx * lab.scale, wy = lab.y - fy_down * lab.scale;
             return Pt{wx / s + 0.5 * W, 0.5 * H - wy / s};
         };
+        double pen = 0.0;
+        const TextMap glyph_to_pixel = [&](double gx, double gy) { return to_pixel(left + pen + gx * k_px, baseline - gy * k_px); };
         const Pt origin = to_pixel(left, baseline);
         plan.origin_x = static_cast<float>(origin.x);
         plan.baseline_y = static_cast<float>(origin.y);
-        double pen = 0.0, lo_x = 1e300, lo_y = 1e300, hi_x = -1e300, hi_y = -1e300;
+        double lo_x = 1e300, lo_y = 1e300, hi_x = -1e300, hi_y = -1e300;
         std::vector<text::Segment> segs;
         for (uint32_t k = 0; k < n_cp; ++k) {
             const TextGlyph& g = *glyphs[k];
             uint32_t first = 0;
             for (uint32_t e : g.contour_ends) {
-                contour.clear();
-                on.clear();
-                for (uint32_t q = first; q <= e; ++q) {
-                    contour.push_back(to_pixel(left + pen + g.points[2 * q] * k_px, baseline - g.points[2 * q + 1] * k_px));
-                    on.push_back(g.on_curve[q]);
-                }
+                const bool fits = text_contour_chords(g, first, e, glyph_to_pixel, poly);
                 first = e + 1;
-                if (!flatten_contour(contour, on, poly) || segs.size() + poly.size() > text::MAX_SEGMENTS + 1u) {
+                if (!fits || segs.size() + poly.size() > text::MAX_SEGMENTS + 1u) {
                     err = tag + ": its outline takes more than 65536 line segments";
                     return PVQ_ERR_INVALID_ARG;
                 }

@@ -6,6 +6,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -57,6 +58,16 @@ class TextFont {
     uint32_t n_glyphs_ = 0, n_hmetrics_ = 0, cmap_format_ = 0;
     bool long_loca_ = false, from_bytes_ = false;
 };
+
+// One contour of a glyph (its points first .. last) as a closed polygon in output pixels: every point through `map` (font units, y
+// upwards, to output pixels, doubles), implied on-curve points added, lines kept and each quadratic cut into chords within
+// text::FLATTEN_TOL of it.  The readout stage (readout_host.cpp) flattens its atlas glyphs with it.  false: more chords than a
+// label may have.
+struct TextPoint {
+    double x, y;
+};
+using TextMap = std::function<TextPoint(double gx, double gy)>;
+bool text_contour_chords(const TextGlyph& g, uint32_t first, uint32_t last, const TextMap& map, std::vector<TextPoint>& poly);
 
 // A label laid out and flattened for a W x H image.
 struct TextLabelPlan {
