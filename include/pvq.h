@@ -1290,9 +1290,25 @@ pvq_status pvq_present_batch_rows_device(pvq_present_batch *b, size_t n_rows, co
  * flattened to L = t_frames * n_bins values -> Conv1d(1, 16, kernel 5, stride 2, no padding) -> ReLU -> max_pool1d(2) -> flatten
  * (channel-major: feature c * O_pool + p) -> Linear(n_features, mlp_size) -> ReLU -> mlp_layers x (Linear(mlp_size, mlp_size) ->
  * ReLU) -> Linear(mlp_size, 128) -> sigmoid.  O_conv = (L - 5) / 2 + 1, O_pool = O_conv / 2 (integer divisions: an odd O_conv
- * loses its last position, as max_pool1d does), n_features = 16 * O_pool.  All arithmetic is f32 (the reference's "TODO: Half"
- * is not taken up). */
+ * loses its last position, as max_pool1d does), n_features = 16 * O_pool.  A handle made by pvq_note_model_create computes all of
+ * it in f32.  The reference's "TODO: Half" (ml_system.rs:26) is an option of the handle, pvq_note_model_create_precision, under
+ * one rule for PVQ_NOTE_BF16 and PVQ_NOTE_F16:
+ *   - the conv, its ReLU and the pool are f32, the fmaf chain of the f32 path, so the pooled features are the same f32 values;
+ *   - each pooled feature is rounded to the type once;
+ *   - every dense weight (fc1, layers, output) is rounded to the type once, at create;
+ *   - every product accumulates in f32; bias and ReLU are f32;
+ *   - a hidden activation is rounded to the type when it is stored;
+ *   - logits, the sigmoid and the mask are f32, as on an f32 handle.
+ * Every rounding is to nearest, ties to even (pvq_note_round).  Subnormals: the 16-bit matrix instructions take their A and B
+ * operands as they are, f16 subnormals included (only f32 / f64 matrix operands follow the wave's denormal mode, and the kernels
+ * are built with the mode that keeps them in any case), so a value below 2^-14 in magnitude rounds to a multiple of 2^-24 and is
+ * not flushed; pvq_note_round and pvq_note_model_infer do the same.  bf16 has f32's exponent range: an f32 subnormal rounds to a
+ * bf16 subnormal.
+ * f16 range: a dense weight beyond +-65504 is refused at create (PVQ_ERR_INVALID_ARG, the layer named).  A row in which a pooled
+ * feature or a hidden activation leaves the f16 range (rounds to infinity) has unspecified values in that row only, as a row with
+ * a non-finite dB value has.  bf16 has no such case. */
 typedef struct pvq_note_model pvq_note_model;
+typedef enum { PVQ_NOTE_F32 = 0, PVQ_NOTE_BF16 = 1, PVQ_NOTE_F16 = 2 } pvq_note_precision;
 /* replaces the constructor arguments of train.py:67-75 (kernel_size 5, stride 2, 16 channels, pool 2 and 128 outputs are fixed, as
  * in train.py:75,90 and ml_system.rs:7).  n_bins 3 .. 1024; t_frames 1 .. 8 with t_frames * n_bins >= 8; mlp_size a multiple of 16
  * in 16 .. 4096; mlp_layers 0 .. 8 */
@@ -1328,12 +1344,26 @@ typedef struct pvq_note_model_outputs {
  * (pvq_note_model_infer works, pvq_note_model_rows_device returns PVQ_ERR_NO_DEVICE after its argument checks). */
 pvq_status pvq_note_model_create(int device_id, const pvq_note_model_params *params, const pvq_note_model_weights *weights,
                                  pvq_note_model **out);
+/* The same with the precision of the dense layers chosen (the rule above); pvq_note_model_create is this with PVQ_NOTE_F32, and a
+ * PVQ_NOTE_F32 handle made here gives that one's bits.  A value that is none of the enum's is PVQ_ERR_INVALID_ARG.  Every other
+ * entry point takes a handle of any precision; the outputs stay f32. */
+pvq_status pvq_note_model_create_precision(int device_id, const pvq_note_model_params *params, const pvq_note_model_weights *weights,
+                                           pvq_note_precision precision, pvq_note_model **out);
+/* the precision a handle was made with */
+pvq_status pvq_note_model_precision(const pvq_note_model *m, pvq_note_precision *out);
+/* The rounding of that rule as a pure host function: out[i] = in[i] rounded to nearest even to the type, returned as f32
+ * (PVQ_NOTE_F32: the identity).  bf16: beyond the largest finite value to infinity.  f16: magnitudes of 65520 and above to
+ * infinity, below 2^-14 to multiples of 2^-24 (subnormals are kept), below or at 2^-25 to a signed zero.  NaN stays NaN.  in may
+ * be out. */
+pvq_status pvq_note_round(pvq_note_precision precision, const float *in, size_t n, float *out);
 void pvq_note_model_destroy(pvq_note_model *m);
 /* the derived sizes: out4 = { L, O_conv, O_pool, n_features } */
 pvq_status pvq_note_model_sizes(const pvq_note_model *m, uint32_t out4[4]);
 /* replaces ml_system.rs::infer (ml_system.rs:24-69) for one row, on the host in plain f32: window_host [L] (t_frames frames, oldest
  * first) -> out_prob [128].  Works on a host-only handle.  The one-row face beside pvq_note_model_rows_device, as
- * pvq_spectrogram_row is beside pvq_render_batch_rows_device. */
+ * pvq_spectrogram_row is beside pvq_render_batch_rows_device.  On a PVQ_NOTE_BF16 / PVQ_NOTE_F16 handle it rounds where the rule
+ * above says (pvq_note_round) and sums in f32 in ascending index order, so a host-only handle predicts the device to within
+ * what the type itself costs. */
 pvq_status pvq_note_model_infer(const pvq_note_model *m, const float *window_host, float out_prob[128]);
 /* The same for MANY rows on the GPU.  d_db is [n_streams][stride_frames][n_bins] (DEVICE), exactly what
  * pvq_vqt_calculate_batch_db_streams writes; n_frames is a HOST array of n_streams frame counts (each <= stride_frames; NULL: every
@@ -1341,11 +1371,14 @@ pvq_status pvq_note_model_infer(const pvq_note_model *m, const float *window_hos
  * train.py:120-131's window_data with the label aligned to the last frame.  Rows with f < t_frames - 1 or f >= n_frames[s] are
  * written as zeros in every output.  A row whose window holds a non-finite dB value has unspecified values in that row only.
  * Asynchronous on `stream`; hidden activations live in a grow-only workspace of the handle (no allocation on the call path once
- * it has grown), so one handle serves one stream at a time. */
+ * it has grown), so one handle serves one stream at a time.  A PVQ_NOTE_BF16 / PVQ_NOTE_F16 handle stores four values at a time:
+ * its d_prob and d_logits must be 16-byte aligned (PVQ_ERR_INVALID_ARG otherwise). */
 pvq_status pvq_note_model_rows_device(pvq_note_model *m, const float *d_db, const size_t *n_frames, uint32_t n_streams,
                                       size_t stride_frames, const pvq_note_model_outputs *outs, void *stream);
 /* Upper bound in bytes for that workspace (default 256 MiB): a call processes its rows in chunks of whole 128-row tiles that fit;
- * results do not depend on the chunking.  One tile (1 KiB * mlp_size + its table entry) is the least a call works with. */
+ * results do not depend on the chunking.  One tile (1 KiB * mlp_size + its table entry) is the least a call works with.  A
+ * PVQ_NOTE_BF16 / PVQ_NOTE_F16 handle keeps, per tile, the 128 rounded feature rows and two hidden rows each, every row padded
+ * to whole chunks of 32 values: 256 * (pad32(n_features) + 2 * pad32(mlp_size)) bytes + its table entry. */
 pvq_status pvq_note_model_set_workspace_limit(pvq_note_model *m, uint64_t bytes);
 
 /* The trainer's optimisation step for that model (pitchvis_train/train.py:108-162): forward in training mode, BCELoss, backward,

@@ -63,7 +63,7 @@ EXPORTS = [
     "pvq_synth_state_create_ex", "pvq_synth_batch_create_ex", "pvq_synth_state_get_sends", "pvq_synth_effects_create", "pvq_synth_effects_destroy",
     "pvq_synth_effects_process", "pvq_synth_chorus_table",
     "pvq_note_model_create", "pvq_note_model_destroy", "pvq_note_model_sizes", "pvq_note_model_infer", "pvq_note_model_rows_device",
-    "pvq_note_model_set_workspace_limit",
+    "pvq_note_model_set_workspace_limit", "pvq_note_model_create_precision", "pvq_note_model_precision", "pvq_note_round",
     "pvq_note_trainer_hyper_default", "pvq_note_trainer_create", "pvq_note_trainer_destroy", "pvq_note_trainer_step", "pvq_note_trainer_steps",
     "pvq_note_trainer_param_count", "pvq_note_trainer_read", "pvq_note_trainer_dropout_keep", "pvq_note_trainer_test", "pvq_note_test_metrics",
     "pvq_vqt_input_status", "pvq_vqt_last_gemm_flop", "pvq_vqt_last_sclk_mhz",
@@ -514,6 +514,10 @@ def load():
     L.pvq_note_model_rows_device.argtypes = [vp, vp, szp, C.c_uint32, C.c_size_t, C.POINTER(CNoteModelOutputs), vp]
     L.pvq_note_model_rows_device.restype = C.c_int
     L.pvq_note_model_set_workspace_limit.argtypes = [vp, C.c_uint64]; L.pvq_note_model_set_workspace_limit.restype = C.c_int
+    L.pvq_note_model_create_precision.argtypes = [C.c_int, C.POINTER(CNoteModelParams), C.POINTER(CNoteModelWeights), C.c_int, C.POINTER(vp)]
+    L.pvq_note_model_create_precision.restype = C.c_int
+    L.pvq_note_model_precision.argtypes = [vp, C.POINTER(C.c_int)]; L.pvq_note_model_precision.restype = C.c_int
+    L.pvq_note_round.argtypes = [C.c_int, fp, C.c_size_t, fp]; L.pvq_note_round.restype = C.c_int
     L.pvq_note_trainer_hyper_default.argtypes = [C.POINTER(CNoteTrainerHyper)]; L.pvq_note_trainer_hyper_default.restype = None
     L.pvq_note_trainer_create.argtypes = [C.c_int, C.POINTER(CNoteModelParams), C.POINTER(CNoteModelWeights), C.POINTER(CNoteTrainerHyper), C.c_uint32,
                                           C.POINTER(vp)]

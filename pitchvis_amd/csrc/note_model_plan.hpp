@@ -47,13 +47,49 @@ inline uint32_t note_model_stages(uint32_t chunks) { return (chunks + NM_PC - 1)
 // the tile list of a call, stream by stream (n_frames null: every stream has stride_frames)
 std::vector<NmTile> note_model_tiles(const NoteModelDims& d, const size_t* n_frames, uint32_t n_streams, size_t stride_frames);
 
-// the host copy of the weights and the one-row forward (ml_system.rs:24-69) in plain f32, sums in ascending index order
+// the host copy of the weights and the one-row forward (ml_system.rs:24-69) in plain f32, sums in ascending index order.  With a
+// 16-bit precision the dense weights are rounded once in assign and infer follows the rule of include/pvq.h: the conv as the fmaf
+// chain the kernels run, features and hidden activations rounded by note_round, f32 sums in ascending index order.
 struct NoteModelHost {
     NoteModelDims d;
+    pvq_note_precision precision = PVQ_NOTE_F32;
     std::vector<float> conv_w, conv_b, fc1_w, fc1_b, out_w, out_b;
     std::vector<std::vector<float>> layer_w, layer_b;
-    void assign(const NoteModelDims& dims, const pvq_note_model_weights& w);
+    void assign(const NoteModelDims& dims, const pvq_note_model_weights& w, pvq_note_precision prec = PVQ_NOTE_F32);
     void infer(const float* window, float* out_prob) const;
 };
+
+// ---- the 16-bit path (note_model_half.hip) ----
+constexpr int NM_KC16 = 32;   // K of a chunk there: one v_mfma_f32_16x16x32_{bf16,f16}; a stage is NM_PC chunks, 16 KiB as above
+inline uint32_t note_model_pad32(uint32_t k) { return (k + NM_KC16 - 1) / NM_KC16 * NM_KC16; }
+
+// x rounded to nearest even to the type, as f32 (include/pvq.h pvq_note_round); PVQ_NOTE_F32: x
+float note_round(pvq_note_precision prec, float x);
+inline bool note_precision_known(int prec) { return prec == PVQ_NOTE_F32 || prec == PVQ_NOTE_BF16 || prec == PVQ_NOTE_F16; }
+// the 16 bits of a value note_round returned (bf16: the upper half of the f32; f16: the IEEE binary16 encoding)
+uint16_t note_bits16(pvq_note_precision prec, float rounded);
+// PVQ_NOTE_F16: a dense weight beyond +-65504 is refused with the layer named; else PVQ_OK
+pvq_status note_model_check_range(const NoteModelDims& d, const pvq_note_model_weights& w, pvq_note_precision prec, std::string& err);
+
+// W [n][k] row-major -> the packed operand of nmh_dense, 16-bit twin of note_model_pack_b:
+//   packed[column tile ct][chunk kc][strip s][lane l][j] = bits16(round(W[col][kmap(32 kc + 8 (l >> 4) + j)])), j = 0 .. 7,
+//   col = 64 ct + 16 ((l & 15) >> 2) + 4 s + (l & 3)
+// The kernel gives W as the instruction's A operand (lane l: matrix row l & 15, k = 8 (l >> 4) .. + 7) and the activations as B,
+// so lane l's accumulator register r of strip s is activation row l & 15, matrix row 4 (l >> 4) + r: with the column numbering
+// above, column 64 ct + 16 (l >> 4) + 4 s + r, and a lane holds 16 consecutive columns of one row.  k' past k (a half chunk when
+// k is an odd multiple of 16), chunks past the last up to whole stages of NM_PC, and columns past n are zero.
+// conv_order: k' = 16 p + c stands for feature c * o_pool + p (fc1); else k' = k.
+std::vector<uint16_t> note_model_pack_b16(const float* W, uint32_t n, uint32_t k, bool conv_order, uint32_t o_pool, pvq_note_precision prec);
+inline uint32_t note_model_stages16(uint32_t k) { return (note_model_pad32(k) / NM_KC16 + NM_PC - 1) / NM_PC; }
+
+// the workspace of a 16-bit call: the tile table, then per chunk of tiles the rounded features [rows][pad32(n_features)] and two
+// hidden buffers [rows][pad32(mlp)], 2 bytes a value.  chunk_tiles: the whole tiles that fit `limit`, at least one, at most n_tiles
+// and what a launch's grid takes.
+struct NmHalfWorkspace {
+    size_t tab_bytes = 0, tile_bytes = 0, chunk_tiles = 0;
+    size_t feat_at = 0, h_at[2] = {0, 0}, total = 0;   // byte offsets
+    uint32_t kf_pad = 0, mlp_pad = 0;
+};
+NmHalfWorkspace note_model_half_workspace(const NoteModelDims& d, size_t n_tiles, uint64_t limit);
 
 }  // namespace pvq

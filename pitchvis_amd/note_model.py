@@ -70,6 +70,24 @@ def _c_weights(params: "NoteModelParams", weights):
     return cw, (w, lw, lb)
 
 
+PRECISIONS = {"f32": 0, "bf16": 1, "f16": 2}   # pvq_note_precision
+
+
+def _precision(precision) -> int:
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision: one of {sorted(PRECISIONS)}, not {precision!r}")
+    return PRECISIONS[precision]
+
+
+def note_round(x, precision: str) -> np.ndarray:
+    """pvq_note_round: ``x`` rounded to nearest even to "bf16" or "f16" ("f32": unchanged), as an f32 array of its shape"""
+    from . import _check
+    a = np.ascontiguousarray(x, np.float32)
+    out = np.empty_like(a)
+    _check(_lib.load().pvq_note_round(_precision(precision), a.ctypes.data_as(_fp), a.size, out.ctypes.data_as(_fp)))
+    return out
+
+
 class NoteModel:
     """``weights``: PyTorch ``state_dict`` names -> arrays (conv1.weight [16][1][5], conv1.bias, fc1.weight [mlp][n_features],
     fc1.bias, layers.i.weight / .bias, output.weight [128][mlp], output.bias).  ``device=None``: a host-only handle (``infer`` works;
@@ -77,15 +95,22 @@ class NoteModel:
 
     OUTPUTS = ("d_prob", "d_logits", "d_mask")
 
-    def __init__(self, params: NoteModelParams, weights, device: Optional[int] = 0):
+    def __init__(self, params: NoteModelParams, weights, device: Optional[int] = 0, precision: str = "f32"):
+        """``precision``: "f32" (the default, pvq_note_model_create), "bf16" or "f16": the dense layers on the 16-bit matrix
+        instructions under the rule of include/pvq.h (pvq_note_model_create_precision); the outputs stay f32."""
         from . import _check
         self._L = _lib.load()
         self.params = params
         self.device = device
+        self.precision = str(precision)
         self._h = C.c_void_p()
         cw, keep = _c_weights(params, weights)   # (keep: alive until the library has copied them)
         cp = _lib.CNoteModelParams(params.n_bins, params.t_frames, params.mlp_size, params.mlp_layers)
-        st = self._L.pvq_note_model_create(-1 if device is None else int(device), C.byref(cp), C.byref(cw), C.byref(self._h))
+        dev = -1 if device is None else int(device)
+        if self.precision == "f32":
+            st = self._L.pvq_note_model_create(dev, C.byref(cp), C.byref(cw), C.byref(self._h))
+        else:
+            st = self._L.pvq_note_model_create_precision(dev, C.byref(cp), C.byref(cw), _precision(self.precision), C.byref(self._h))
         del keep
         if st == _lib.PVQ_ERR_INVALID_ARG:
             raise ValueError((self._L.pvq_last_error() or b"").decode())
@@ -95,7 +120,7 @@ class NoteModel:
         self.window_len, self.o_conv, self.o_pool, self.n_features = (int(x) for x in s4)
 
     @classmethod
-    def from_state_dict(cls, sd, n_bins: int, t_frames: int, device: Optional[int] = 0) -> "NoteModel":
+    def from_state_dict(cls, sd, n_bins: int, t_frames: int, device: Optional[int] = 0, precision: str = "f32") -> "NoteModel":
         """mlp_size and mlp_layers are read off the shapes.  Takes the module's ``state_dict()`` as well as
         ``torch.jit.load(path).state_dict()``, what train.py:205-208 saves."""
         w = _weights_dict(sd)
@@ -104,7 +129,7 @@ class NoteModel:
         layers = 0
         while f"layers.{layers}.weight" in w:
             layers += 1
-        return cls(NoteModelParams(int(n_bins), int(t_frames), int(w["fc1.weight"].shape[0]), layers), w, device)
+        return cls(NoteModelParams(int(n_bins), int(t_frames), int(w["fc1.weight"].shape[0]), layers), w, device, precision)
 
     def __del__(self):
         h = getattr(self, "_h", None)
