@@ -1442,6 +1442,32 @@ void pvq_note_trainer_hyper_default(pvq_note_trainer_hyper *h);
  * fallback). */
 pvq_status pvq_note_trainer_create(int device_id, const pvq_note_model_params *params, const pvq_note_model_weights *weights,
                                    const pvq_note_trainer_hyper *hyper, uint32_t max_batch, pvq_note_trainer **out);
+/* The same with the precision of the dense products chosen.  PVQ_NOTE_F32 is exactly pvq_note_trainer_create (its bits).
+ * PVQ_NOTE_F16 and any value that is none of the enum's are refused before a device is touched (PVQ_ERR_INVALID_ARG, the reason in
+ * pvq_last_error): dZ = (sigmoid(z) - y) / (128 * batch) is about 1e-5 and underflows f16 without loss scaling, which is not offered.
+ * PVQ_NOTE_BF16 is mixed-precision training: bf16 operands on the 16-bit matrix instructions, f32 accumulation, f32 master
+ * weights, gradients and Adam moments, under this rule (every rounding is pvq_note_round's: nearest, ties to even, subnormals kept):
+ *   Kept in f32.  The four arrays of pvq_note_trainer_read stay f32 in state_dict order and layout; pvq_note_trainer_read, the
+ *     step's loss and logits, the test pass and Adam are those of an f32 handle.
+ *   Forward.  Conv, ReLU and pool in f32 by the fmaf chain of the f32 path; each pooled feature rounded once (the point of the
+ *     inference rule above).  Each dense weight is rounded once per step from its f32 master value: the handle keeps a 16-bit
+ *     shadow of the dense weights, written at create and refreshed after every Adam update.  A hidden activation is bias + ReLU +
+ *     (dropout keep * 1 / (1 - p)) in f32 on the f32 accumulator, then rounded once and stored in 16 bits; the backward gate
+ *     [H > 0] reads the stored value.  Logits, loss and the output layer's (sigmoid(z) - y) / (batch * 128) are f32.
+ *   Backward.  Every back-propagated dZ is rounded once when it is stored: the output layer's, and each hidden layer's and fc1's
+ *     after gate and scale were applied in f32.  The weight gradient, the bias gradient and the data gradient of a layer all read
+ *     that one rounded value.  The gradient with respect to the pooled features is the exception: it stays f32, and the conv
+ *     gradients are computed from it as on an f32 handle.
+ *   Sums.  Every product accumulates in f32; partial sums and every stored gradient are f32; every order is fixed by the shapes,
+ *     nothing is accumulated atomically: equal inputs give equal bits, as in f32.
+ * The handle holds in addition, in 16 bits: both orientations of every dense weight, and per row of max_batch both orientations of
+ * the features, the hidden activations and the back-propagated gradients, rows padded to whole chunks of 32 values. */
+pvq_status pvq_note_trainer_create_precision(int device_id, const pvq_note_model_params *params, const pvq_note_model_weights *weights,
+                                             const pvq_note_trainer_hyper *hyper, uint32_t max_batch, pvq_note_precision precision,
+                                             pvq_note_trainer **out);
+/* the precision a handle was made with, a pvq_note_precision value (0, PVQ_NOTE_F32, for a null handle, as every getter answers
+ * its zero); a pure query */
+int pvq_note_trainer_precision(const pvq_note_trainer *t);
 void pvq_note_trainer_destroy(pvq_note_trainer *t);
 /* One step of `mode` (a pvq_train_mode) on the batch idx[0 .. batch) of the dataset (d_db, d_targets, n_rows), as laid out above.
  * d_loss (DEVICE, one float, may be NULL) receives the mean loss, d_logits (DEVICE, [batch][128], may be NULL) the logits; nothing

@@ -66,6 +66,7 @@ EXPORTS = [
     "pvq_note_model_set_workspace_limit", "pvq_note_model_create_precision", "pvq_note_model_precision", "pvq_note_round",
     "pvq_note_trainer_hyper_default", "pvq_note_trainer_create", "pvq_note_trainer_destroy", "pvq_note_trainer_step", "pvq_note_trainer_steps",
     "pvq_note_trainer_param_count", "pvq_note_trainer_read", "pvq_note_trainer_dropout_keep", "pvq_note_trainer_test", "pvq_note_test_metrics",
+    "pvq_note_trainer_create_precision", "pvq_note_trainer_precision",
     "pvq_vqt_input_status", "pvq_vqt_last_gemm_flop", "pvq_vqt_last_sclk_mhz",
     "pvq_vqt_bandwidths_3db", "pvq_vqt_warning_count", "pvq_vqt_warning",
 ]
@@ -522,6 +523,10 @@ def load():
     L.pvq_note_trainer_create.argtypes = [C.c_int, C.POINTER(CNoteModelParams), C.POINTER(CNoteModelWeights), C.POINTER(CNoteTrainerHyper), C.c_uint32,
                                           C.POINTER(vp)]
     L.pvq_note_trainer_create.restype = C.c_int
+    L.pvq_note_trainer_create_precision.argtypes = [C.c_int, C.POINTER(CNoteModelParams), C.POINTER(CNoteModelWeights), C.POINTER(CNoteTrainerHyper),
+                                                    C.c_uint32, C.c_int, C.POINTER(vp)]
+    L.pvq_note_trainer_create_precision.restype = C.c_int
+    L.pvq_note_trainer_precision.argtypes = [vp]; L.pvq_note_trainer_precision.restype = C.c_int
     L.pvq_note_trainer_destroy.argtypes = [vp]; L.pvq_note_trainer_destroy.restype = None
     L.pvq_note_trainer_step.argtypes = [vp, C.c_int, vp, vp, C.c_size_t, up, C.c_uint32, vp, vp, vp]; L.pvq_note_trainer_step.restype = C.c_int
     L.pvq_note_trainer_steps.argtypes = [vp]; L.pvq_note_trainer_steps.restype = C.c_uint64

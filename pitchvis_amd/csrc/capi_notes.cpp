@@ -103,6 +103,20 @@ pvq_status pvq_note_trainer_create(int device_id, const pvq_note_model_params* p
         });
     });
 }
+// the same with the dense products in bf16 under the rule of include/pvq.h (note_trainer_half.hpp); PVQ_NOTE_F32 is the entry above
+pvq_status pvq_note_trainer_create_precision(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
+                                             const pvq_note_trainer_hyper* hyper, uint32_t max_batch, pvq_note_precision precision,
+                                             pvq_note_trainer** out) {
+    if (precision == PVQ_NOTE_F32) return pvq_note_trainer_create(device_id, params, weights, hyper, max_batch, out);
+    return guarded([&] {
+        return make_handle(out, [&](auto& impl) {
+            return pvq::NoteTrainer::create(device_id, params, weights, hyper, max_batch, precision, impl);
+        });
+    });
+}
+int pvq_note_trainer_precision(const pvq_note_trainer* t) {
+    return guarded(0, [&] { return t ? static_cast<int>(t->impl->precision()) : 0; });
+}
 void pvq_note_trainer_destroy(pvq_note_trainer* t) { destroy(t); }
 pvq_status pvq_note_trainer_step(pvq_note_trainer* t, int mode, const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx,
                                  uint32_t batch, float* d_loss, float* d_logits, void* stream) {

@@ -465,12 +465,30 @@ NoteTrainer::~NoteTrainer() {
     if (h_test_out_) (void)hipHostFree(h_test_out_);
 }
 
+NthContext NoteTrainer::half_context() const {
+    NthContext c;
+    c.lay = &lay_;
+    c.plan = &half_;
+    c.arena = arena_.as<float>();
+    c.shadow = shadow_.as<uint16_t>();
+    c.ws16 = ws16_.as<uint16_t>();
+    c.part = ws(ws_part_);
+    c.d_idx = reinterpret_cast<const uint32_t*>(ws(ws_idx_));
+    c.Z = ws(ws_z_);
+    c.dZ = ws(ws_dz_);
+    c.dfeat = ws(ws_dfeat_);
+    c.hyper = hyper_;
+    c.steps = steps_;
+    return c;
+}
+
 pvq_status NoteTrainer::create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
-                               const pvq_note_trainer_hyper* hyper, uint32_t max_batch, std::unique_ptr<NoteTrainer>& out) {
+                               const pvq_note_trainer_hyper* hyper, uint32_t max_batch, pvq_note_precision precision, std::unique_ptr<NoteTrainer>& out) {
     out.reset();
     NoteModelDims d;
     std::string err;
-    pvq_status st = note_model_check(params, weights, d, err);
+    pvq_status st = note_trainer_check_precision(static_cast<int>(precision), err);
+    if (st == PVQ_OK) st = note_model_check(params, weights, d, err);
     if (st == PVQ_OK) st = note_trainer_check_hyper(hyper, max_batch, err);
     if (st != PVQ_OK) {
         set_last_error(err);
@@ -481,6 +499,8 @@ pvq_status NoteTrainer::create(int device_id, const pvq_note_model_params* param
     t->lay_ = note_trainer_layout(d);
     t->hyper_ = *hyper;
     t->max_batch_ = max_batch;
+    t->precision_ = precision;
+    if (precision == PVQ_NOTE_BF16) t->half_ = note_trainer_half_plan(t->lay_, max_batch);
     if (device_id >= 0) {
         PVQ_HIP(hipSetDevice(device_id));
         const size_t n = t->lay_.n_params;
@@ -511,6 +531,16 @@ pvq_status NoteTrainer::create(int device_id, const pvq_note_model_params* param
             PVQ_HIP(hipHostMalloc(reinterpret_cast<void**>(&t->h_idx_[s]), B * sizeof(uint32_t), hipHostMallocDefault));
             PVQ_HIP(hipEventCreateWithFlags(&t->idx_copied_[s], hipEventDisableTiming));
         }
+        if (precision == PVQ_NOTE_BF16) {
+            // the shadow weights and the 16-bit workspace; zeroed once, so no product ever meets a padding that is no number
+            if (pvq_status s = t->shadow_.reserve(t->half_.shadow_total * sizeof(uint16_t))) return s;
+            if (pvq_status s = t->ws16_.reserve(t->half_.ws_total * sizeof(uint16_t))) return s;
+            PVQ_HIP(hipMemset(t->shadow_.as<void>(), 0, t->half_.shadow_total * sizeof(uint16_t)));
+            PVQ_HIP(hipMemset(t->ws16_.as<void>(), 0, t->half_.ws_total * sizeof(uint16_t)));
+            nth_refresh_shadow(t->half_context(), nullptr);
+            PVQ_HIP(hipGetLastError());
+            PVQ_HIP(hipDeviceSynchronize());
+        }
     }
     out = std::move(t);
     return PVQ_OK;
@@ -530,6 +560,10 @@ pvq_status NoteTrainer::upload_idx(const uint32_t* idx, uint32_t rows, hipStream
 
 // forward (train.py:87-99)
 void NoteTrainer::forward(const float* d_db, uint32_t batch, bool train, hipStream_t stream) {
+    if (precision_ == PVQ_NOTE_BF16) {
+        nth_forward(half_context(), d_db, batch, train, stream);
+        return;
+    }
     const NoteModelDims& d = lay_.d;
     const float* w = arena_.as<float>();
     const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(ws(ws_idx_));
@@ -605,8 +639,9 @@ pvq_status NoteTrainer::step(int mode, const float* d_db, const float* d_targets
     hipLaunchKernelGGL(nt_loss, dim3(batch), dim3(NM_OUT), 0, stream, Z, d_targets, d_idx, static_cast<float>(inv_n), dZ, d_logits, row_loss);
     if (d_loss) hipLaunchKernelGGL(nt_loss_final, dim3(1), dim3(NT_THREADS), 0, stream, row_loss, batch, inv_n, d_loss);
 
-    if (train) {
-        // backward: the output layer, the hidden layers from the last to the first, fc1, the conv
+    if (train && precision_ == PVQ_NOTE_BF16) nth_backward(half_context(), batch, stream);
+    if (train && precision_ == PVQ_NOTE_F32) {
+        // backward: the output layer, the hidden layers from the last to the first, fc1
         Epi raw{};
         raw.kind = E_RAW;
         Epi gate{};
@@ -628,6 +663,9 @@ pvq_status NoteTrainer::step(int mode, const float* d_db, const float* d_targets
         gemm(G_TN, dA[cur], feat, grad + lay_.fc1_w.at, mlp, F, batch, mlp, F, raw, part, stream);
         hipLaunchKernelGGL(nt_bias_grad, dim3((mlp + 63) / 64), dim3(NT_THREADS), 0, stream, dA[cur], grad + lay_.fc1_b.at, batch, mlp);
         gemm(G_NN, dA[cur], w + lay_.fc1_w.at, dfeat, batch, F, mlp, mlp, F, raw, part, stream);
+    }
+    if (train) {
+        // the conv from dfeat, then Adam
         float* conv_part = ws(ws_convpart_);
         hipLaunchKernelGGL(nt_conv_grad, dim3(batch), dim3(NT_THREADS), x_bytes, stream, d_db, d_idx, w + lay_.conv_w.at, dfeat, conv_part, d.n_bins, d.t_frames,
                            d.L, d.o_pool);
@@ -638,6 +676,7 @@ pvq_status NoteTrainer::step(int mode, const float* d_db, const float* d_targets
                                reinterpret_cast<f32x4*>(arena_.as<float>()), reinterpret_cast<const f32x4*>(grad), reinterpret_cast<f32x4*>(arena_.as<float>() + 2 * n),
                                reinterpret_cast<f32x4*>(arena_.as<float>() + 3 * n), n4, note_trainer_adam_step(hyper_, steps_ + 1));
             ++steps_;
+            if (precision_ == PVQ_NOTE_BF16) nth_refresh_shadow(half_context(), stream);
         }
     }
     PVQ_HIP(hipGetLastError());

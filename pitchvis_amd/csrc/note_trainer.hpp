@@ -14,6 +14,8 @@
 //   nt_bias_grad    column sums in a fixed order
 //   nt_conv_grad, nt_conv_reduce   dFeat through pool and ReLU to the 96 conv gradients: per row, then over rows, fixed order
 //   nt_adam         one launch over the arena
+// A handle created with PVQ_NOTE_BF16 runs nt_features, nt_gemm and nt_bias_grad's work in note_trainer_half.hip instead (bf16 operands,
+// f32 sums; the arenas, nt_loss, the conv gradient, nt_adam and the test pass's kernels are shared), picked by precision_ in forward and step.
 // The test pass (train.py:164-198) runs the same forward without dropout over chunks of at most max_batch rows, then
 //   nt_test_rows    per row: the 128-bit masks of prediction (z > 0) and label (y > 0.5) by wave ballots, tp / fp / fn / correct by
 //                   popcount, the row's loss as nt_loss's tree in double, the logits when asked; indexed by the position in idx
@@ -29,6 +31,7 @@
 
 #include "../../include/pvq.h"
 #include "device_support.hpp"
+#include "note_trainer_half.hpp"
 #include "note_trainer_plan.hpp"
 
 namespace pvq {
@@ -38,8 +41,14 @@ class NoteTrainer {
     // every check runs before any device is touched.  device_id < 0: a host-only object (step returns PVQ_ERR_NO_DEVICE after its
     // argument checks, read returns it at once).
     static pvq_status create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
-                             const pvq_note_trainer_hyper* hyper, uint32_t max_batch, std::unique_ptr<NoteTrainer>& out);
+                             const pvq_note_trainer_hyper* hyper, uint32_t max_batch, std::unique_ptr<NoteTrainer>& out) {
+        return create(device_id, params, weights, hyper, max_batch, PVQ_NOTE_F32, out);
+    }
+    // precision: PVQ_NOTE_F32 (the entry above) or PVQ_NOTE_BF16 (note_trainer_half.hpp); anything else is refused with the other checks
+    static pvq_status create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
+                             const pvq_note_trainer_hyper* hyper, uint32_t max_batch, pvq_note_precision precision, std::unique_ptr<NoteTrainer>& out);
     ~NoteTrainer();
+    pvq_note_precision precision() const { return precision_; }
     const NoteModelDims& dims() const { return lay_.d; }
     size_t n_params() const { return lay_.n_params; }
     uint64_t steps() const { return steps_; }
@@ -59,8 +68,14 @@ class NoteTrainer {
     pvq_status upload_idx(const uint32_t* idx, uint32_t rows, hipStream_t stream);
     // train.py:87-99 on the rows the workspace's index array names: features, fc1, the hidden layers, the logits Z.  Queues only.
     void forward(const float* d_db, uint32_t batch, bool train, hipStream_t stream);
+    // the buffers of a bf16 step (precision_ == PVQ_NOTE_BF16)
+    NthContext half_context() const;
     int device_id_ = -1;
+    pvq_note_precision precision_ = PVQ_NOTE_F32;
     NoteTrainerLayout lay_;
+    NoteTrainerHalfPlan half_;   // bf16 only
+    DeviceBuffer shadow_;        //   the 16-bit copies of the dense weights, refreshed after every nt_adam
+    DeviceBuffer ws16_;          //   the 16-bit workspace, sized once from max_batch
     pvq_note_trainer_hyper hyper_{};
     uint32_t max_batch_ = 0;
     uint64_t steps_ = 0;     // completed PVQ_TRAIN_STEP calls: Adam's t - 1, and the step the dropout mask is keyed by

@@ -127,6 +127,67 @@ uint32_t nt_splits(uint32_t m, uint32_t n, uint32_t k) {
     return static_cast<uint32_t>(std::max<uint64_t>(s, 1));
 }
 
+pvq_status note_trainer_check_precision(int precision, std::string& err) {
+    if (precision == PVQ_NOTE_F32 || precision == PVQ_NOTE_BF16) return PVQ_OK;
+    if (precision == PVQ_NOTE_F16)
+        err = "note trainer: precision f16 is not offered: dZ = (sigmoid(z) - y) / (128 * batch) is about 1e-5 and underflows f16 without loss "
+              "scaling; train in bf16 or f32";
+    else
+        err = "note trainer: precision is none of pvq_note_precision";
+    return PVQ_ERR_INVALID_ARG;
+}
+
+uint32_t nth_splits(uint32_t m, uint32_t n, uint32_t k) {
+    const uint64_t blocks = static_cast<uint64_t>((m + NTH_BM - 1) / NTH_BM) * ((n + NTH_BN - 1) / NTH_BN);
+    const uint32_t stages = (k + NTH_BK - 1) / NTH_BK;
+    uint64_t s = std::min<uint64_t>({512 / blocks, stages / 4, 8});
+    while (s > 1 && s * m * n > NT_PART_FLOATS) --s;
+    return static_cast<uint32_t>(std::max<uint64_t>(s, 1));
+}
+
+NoteTrainerHalfPlan note_trainer_half_plan(const NoteTrainerLayout& lay, uint32_t max_batch) {
+    const NoteModelDims& d = lay.d;
+    NoteTrainerHalfPlan p;
+    auto round64 = [](size_t n) { return (n + 63) & ~static_cast<size_t>(63); };
+    size_t at = 0;
+    auto take = [&at, &round64](size_t n) {
+        const size_t here = at;
+        at += round64(n);
+        return here;
+    };
+    auto dense = [&](const NtTensor& t, uint32_t n, uint32_t k) {
+        NthShadow s;
+        s.src_at = t.at;
+        s.n = n;
+        s.k = k;
+        s.w_at = take(static_cast<size_t>(n) * nth_pad32(k));
+        s.wt_at = take(static_cast<size_t>(k) * nth_pad32(n));
+        p.shadow.push_back(s);
+    };
+    dense(lay.fc1_w, d.mlp, d.n_features);
+    for (uint32_t i = 0; i < d.layers; ++i) dense(lay.layer_w[i], d.mlp, d.mlp);
+    dense(lay.out_w, NM_OUT, d.mlp);
+    p.shadow_total = at;
+
+    at = 0;
+    const size_t B = max_batch;
+    p.f_pad = nth_pad32(d.n_features);
+    p.mlp_pad = nth_pad32(d.mlp);
+    p.b_pad = nth_pad32(max_batch);
+    p.h_stride = round64(B * p.mlp_pad);
+    p.ht_stride = round64(static_cast<size_t>(d.mlp) * p.b_pad);
+    p.feat_at = take(B * p.f_pad);
+    p.featt_at = take(static_cast<size_t>(d.n_features) * p.b_pad);
+    p.h_at = take((d.layers + 1) * p.h_stride);
+    p.ht_at = take((d.layers + 1) * p.ht_stride);
+    p.dz_at = take(B * NM_OUT);
+    p.dzt_at = take(static_cast<size_t>(NM_OUT) * p.b_pad);
+    p.da_at = take(2 * p.h_stride);
+    p.dat_at = take(2 * p.ht_stride);
+    p.ws_total = at;
+    return p;
+}
+
 NoteTrainerTestPlan note_trainer_test_plan(size_t n_idx, uint32_t max_batch, uint32_t batch) {
     NoteTrainerTestPlan p;
     if (n_idx == 0 || max_batch == 0 || batch == 0) return p;

@@ -79,6 +79,37 @@ NtAdamStep note_trainer_adam_step(const pvq_note_trainer_hyper& h, uint64_t t);
 // splits * m * n within NT_PART_FLOATS.  1: no split, the GEMM writes its result itself.
 uint32_t nt_splits(uint32_t m, uint32_t n, uint32_t k);
 
+// The bf16 step (note_trainer_half.hpp; the rule: include/pvq.h, pvq_note_trainer_create_precision).  f32 and bf16 are admitted;
+// f16 is refused with the reason, any other value as unknown.  err receives the text
+pvq_status note_trainer_check_precision(int precision, std::string& err);
+constexpr int NTH_BM = 64;   // nth_gemm's workgroup tile: 2 x 2 waves of 32 x 32
+constexpr int NTH_BN = 64;
+constexpr int NTH_BK = 64;   // K of a stage: two chunks of 32, one v_mfma_f32_16x16x32_bf16 each
+inline uint32_t nth_pad32(uint32_t n) { return (n + 31u) & ~31u; }
+// nt_splits for nth_gemm (k: the padded K): the same fixed 512 workgroups, at least 4 stages (256 k) per split, at most 8 splits,
+// splits * m * n within NT_PART_FLOATS
+uint32_t nth_splits(uint32_t m, uint32_t n, uint32_t k);
+// One dense weight W [n][k] of the arena (at float offset src_at) and its two 16-bit copies in the shadow buffer: w_at [n][pad32(k)]
+// and wt_at [k][pad32(n)], the padding zeros.  Offsets in 16-bit elements, multiples of 64.
+struct NthShadow {
+    size_t src_at = 0, w_at = 0, wt_at = 0;
+    uint32_t n = 0, k = 0;
+};
+// The shadow weights (fc1, layers 0 .., output: in that order) and the 16-bit workspace of a handle, sized once from max_batch.  Every
+// matrix is kept both ways round, [row][pad32(col)] and [col][pad32(row)], so that every product reads both operands along k; rows of a
+// call are laid out densely with the strides of ITS batch (pad32(n_features), pad32(mlp), pad32(batch)), so values do not depend on
+// max_batch.  Offsets in 16-bit elements, multiples of 64; h_at and ht_at hold layers + 1 matrices of h_stride and ht_stride each,
+// da_at and dat_at two.
+struct NoteTrainerHalfPlan {
+    std::vector<NthShadow> shadow;
+    size_t shadow_total = 0;
+    uint32_t f_pad = 0, mlp_pad = 0, b_pad = 0;   // pad32 of n_features, mlp, max_batch
+    size_t feat_at = 0, featt_at = 0, h_at = 0, ht_at = 0, dz_at = 0, dzt_at = 0, da_at = 0, dat_at = 0;
+    size_t h_stride = 0, ht_stride = 0;
+    size_t ws_total = 0;
+};
+NoteTrainerHalfPlan note_trainer_half_plan(const NoteTrainerLayout& lay, uint32_t max_batch);
+
 // The test pass (train.py:164-198).  Dropout is off, so a row's forward depends on no other row: the forward runs in chunks of at
 // most max_batch consecutive entries of idx, a function of n_idx and max_batch alone; `batch` shapes only the counting.
 constexpr size_t NT_TEST_MAX_IDX = size_t(1) << 25;   // rows of a pass: 128 * rows, the most a count can reach, stays below 2^32

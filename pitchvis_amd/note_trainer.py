@@ -129,9 +129,16 @@ class NoteTrainer:
     """``weights``: the initial ``state_dict`` (names as for ``NoteModel``).  ``device=None``: a host-only handle (argument checks
     work; ``step`` raises: no CPU fallback).  ``max_batch`` sizes the workspace once."""
 
-    def __init__(self, params: NoteModelParams, weights, hyper: Optional[NoteTrainerHyper] = None, max_batch: int = 300, device: Optional[int] = 0):
+    def __init__(self, params: NoteModelParams, weights, hyper: Optional[NoteTrainerHyper] = None, max_batch: int = 300, device: Optional[int] = 0,
+                 precision: str = "f32"):
+        """``precision``: "f32" (the default, pvq_note_trainer_create) or "bf16": mixed-precision training under the rule of
+        include/pvq.h (pvq_note_trainer_create_precision): bf16 operands, f32 sums, f32 master weights, gradients and moments.
+        "f16" is refused: the gradients underflow it without loss scaling."""
         from . import _check
+        from .note_model import _precision
         self._L = _lib.load()
+        self.precision = str(precision)
+        code = _precision(self.precision)
         self.params = params
         self.hyper = hyper or NoteTrainerHyper()
         self.max_batch = int(max_batch)
@@ -140,8 +147,11 @@ class NoteTrainer:
         cw, keep = _c_weights(params, weights)   # (keep: alive until the library has copied them)
         cp = _lib.CNoteModelParams(params.n_bins, params.t_frames, params.mlp_size, params.mlp_layers)
         ch = self.hyper._c()
-        st = self._L.pvq_note_trainer_create(-1 if device is None else int(device), C.byref(cp), C.byref(cw), C.byref(ch), self.max_batch,
-                                             C.byref(self._h))
+        dev = -1 if device is None else int(device)
+        if self.precision == "f32":
+            st = self._L.pvq_note_trainer_create(dev, C.byref(cp), C.byref(cw), C.byref(ch), self.max_batch, C.byref(self._h))
+        else:
+            st = self._L.pvq_note_trainer_create_precision(dev, C.byref(cp), C.byref(cw), C.byref(ch), self.max_batch, code, C.byref(self._h))
         del keep
         if st == _lib.PVQ_ERR_INVALID_ARG:
             raise ValueError((self._L.pvq_last_error() or b"").decode())
