@@ -3,7 +3,6 @@
 
 #include "capi_support.hpp"
 #include "note_model.hpp"
-#include "note_model_half.hpp"
 #include "note_trainer.hpp"
 
 extern "C" {
@@ -16,25 +15,20 @@ pvq_status pvq_note_model_create(int device_id, const pvq_note_model_params* par
         });
     });
 }
-// the same model with its dense layers in bf16 or f16 (note_model_half.hpp); PVQ_NOTE_F32 is the entry above
+// the same model at any precision: its dense layers in f32 as above, or in bf16 or f16 (note_model_half.hpp)
 pvq_status pvq_note_model_create_precision(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
                                            pvq_note_precision precision, pvq_note_model** out) {
-    if (precision == PVQ_NOTE_F32) return pvq_note_model_create(device_id, params, weights, out);
     return guarded([&] {
-        if (!out) return null_handle();
-        *out = nullptr;
-        if (!pvq::note_precision_known(static_cast<int>(precision))) return invalid_arg("note model: precision is none of pvq_note_precision");
-        std::unique_ptr<pvq::NoteModelHalf> half;
-        const pvq_status st = pvq::NoteModelHalf::create(device_id, params, weights, precision, half);
-        if (st != PVQ_OK) return st;
-        *out = new pvq_note_model{nullptr, std::move(half)};
-        return PVQ_OK;
+        return make_handle(out, [&](auto& impl) {
+            if (!pvq::note_precision_known(static_cast<int>(precision))) return invalid_arg("note model: precision is none of pvq_note_precision");
+            return pvq::NoteModel::create(device_id, params, weights, precision, impl);
+        });
     });
 }
 pvq_status pvq_note_model_precision(const pvq_note_model* m, pvq_note_precision* out) {
     return guarded([&] {
         if (!m || !out) return null_handle();
-        *out = m->half ? m->half->precision() : PVQ_NOTE_F32;
+        *out = m->impl->precision();
         return PVQ_OK;
     });
 }
@@ -50,7 +44,7 @@ void pvq_note_model_destroy(pvq_note_model* m) { destroy(m); }
 pvq_status pvq_note_model_sizes(const pvq_note_model* m, uint32_t out4[4]) {
     return guarded([&] {
         if (!m || !out4) return null_handle();
-        const pvq::NoteModelDims& d = m->half ? m->half->dims() : m->impl->dims();
+        const pvq::NoteModelDims& d = m->impl->dims();
         out4[0] = d.L; out4[1] = d.o_conv; out4[2] = d.o_pool; out4[3] = d.n_features;
         return PVQ_OK;
     });
@@ -59,8 +53,7 @@ pvq_status pvq_note_model_infer(const pvq_note_model* m, const float* window_hos
     return guarded([&] {
         if (!m) return null_handle();
         if (!window_host || !out_prob) return invalid_arg("note model: null window or output");
-        if (m->half) m->half->infer(window_host, out_prob);
-        else m->impl->infer(window_host, out_prob);   // ml_system.rs:24-69
+        m->impl->infer(window_host, out_prob);   // ml_system.rs:24-69
         return PVQ_OK;
     });
 }
@@ -69,15 +62,13 @@ pvq_status pvq_note_model_rows_device(pvq_note_model* m, const float* d_db, cons
     return guarded([&] {
         if (!m) return null_handle();
         const pvq_note_model_outputs none{};
-        if (m->half) return m->half->rows_device(d_db, n_frames, n_streams, stride_frames, outs ? *outs : none, static_cast<hipStream_t>(stream));
         return m->impl->rows_device(d_db, n_frames, n_streams, stride_frames, outs ? *outs : none, static_cast<hipStream_t>(stream));
     });
 }
 pvq_status pvq_note_model_set_workspace_limit(pvq_note_model* m, uint64_t bytes) {
     return guarded([&] {
         if (!m) return null_handle();
-        if (m->half) m->half->set_workspace_limit(bytes);
-        else m->impl->set_workspace_limit(bytes);
+        m->impl->set_workspace_limit(bytes);
         return PVQ_OK;
     });
 }

@@ -37,7 +37,6 @@ class SynthEffects;
 class PresentBatch;
 class PanelsBatch;
 class NoteModel;
-class NoteModelHalf;
 class NoteTrainer;
 }  // namespace pvq
 
@@ -111,8 +110,7 @@ struct pvq_panels_batch {
     std::unique_ptr<pvq::PanelsBatch> impl;
 };
 struct pvq_note_model {
-    std::unique_ptr<pvq::NoteModel> impl;       // a PVQ_NOTE_F32 handle, or
-    std::unique_ptr<pvq::NoteModelHalf> half;   // a PVQ_NOTE_BF16 / PVQ_NOTE_F16 one
+    std::unique_ptr<pvq::NoteModel> impl;
 };
 struct pvq_note_trainer {
     std::unique_ptr<pvq::NoteTrainer> impl;

@@ -17,6 +17,8 @@
 #include <algorithm>
 #include <string>
 
+#include "note_device.hpp"
+#include "note_model_half.hpp"
 #include "vqt_engine.hpp"
 
 namespace pvq {
@@ -295,12 +297,49 @@ __global__ __launch_bounds__(NM_THREADS, 2) void nm_dense(const NmArgs a) {
     if (active) epilogue<ACT>(a, tile, tile_local, ct, wave, lane, acc);
 }
 
-pvq_status upload(const std::vector<float>& packed, const float* bias, uint32_t n_bias, DeviceBuffer& d, size_t& bias_at) {
-    bias_at = packed.size();
-    if (pvq_status s = d.reserve((packed.size() + n_bias) * sizeof(float))) return s;
-    PVQ_HIP(hipMemcpy(d.as<float>(), packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-    PVQ_HIP(hipMemcpy(d.as<float>() + bias_at, bias, n_bias * sizeof(float), hipMemcpyHostToDevice));
-    return PVQ_OK;
+// the f32 launches of the tiles d_tiles[0 .. nt): fc1 over the fused conv, the hidden layers, the output layer into `outs`
+void nm_chunk(const NmContext& c, const NmTile* d_tiles, uint32_t nt, const float* d_db, size_t stride_frames, const pvq_note_model_outputs& outs,
+              hipStream_t stream) {
+    const NoteModelDims& d = c.d;
+    float* buf[2] = {reinterpret_cast<float*>(c.ws + c.at.h_at[0]), reinterpret_cast<float*>(c.ws + c.at.h_at[1])};
+    NmArgs a{};
+    a.tiles = d_tiles;
+    a.stride_frames = stride_frames;
+    a.n_bins = d.n_bins;
+    a.t_frames = d.t_frames;
+    a.L = d.L;
+    // fc1 over the fused conv
+    a.db = d_db;
+    a.conv = c.conv;
+    a.b_packed = static_cast<const float4*>(c.w[0]);
+    a.bias = c.bias[0];
+    a.h_out = buf[0];
+    a.chunks = d.o_pool;
+    a.k = d.n_features;
+    a.n = d.mlp;
+    a.n_ct = (d.mlp + NM_BN - 1) / NM_BN;
+    hipLaunchKernelGGL(nm_conv_fc1, dim3(nt * a.n_ct), dim3(NM_THREADS), 0, stream, a);
+    int cur = 0;
+    a.chunks = d.mlp / NM_KC;
+    a.k = d.mlp;
+    for (uint32_t i = 1; i <= d.layers; ++i) {
+        a.a_in = buf[cur];
+        a.h_out = buf[cur ^ 1];
+        a.b_packed = static_cast<const float4*>(c.w[i]);
+        a.bias = c.bias[i];
+        hipLaunchKernelGGL(nm_dense<0>, dim3(nt * a.n_ct), dim3(NM_THREADS), 0, stream, a);
+        cur ^= 1;
+    }
+    a.a_in = buf[cur];
+    a.h_out = nullptr;
+    a.b_packed = static_cast<const float4*>(c.w[d.layers + 1]);
+    a.bias = c.bias[d.layers + 1];
+    a.n = NM_OUT;
+    a.n_ct = NM_OUT / NM_BN;
+    a.prob = outs.d_prob;
+    a.logits = outs.d_logits;
+    a.mask = outs.d_mask;
+    hipLaunchKernelGGL(nm_dense<1>, dim3(nt * a.n_ct), dim3(NM_THREADS), 0, stream, a);
 }
 }  // namespace
 
@@ -308,30 +347,51 @@ NoteModel::~NoteModel() {
     if (device_id_ >= 0) (void)hipSetDevice(device_id_);   // the buffers go after this body, with their device set
 }
 
+// a dense layer as its precision's kernel reads it (note_model_pack_b, note_model_pack_b16), then its f32 bias
+pvq_status NoteModel::upload(const float* W, const float* bias, uint32_t n, uint32_t k, bool conv_order, Layer& l) {
+    std::vector<float> p32;
+    std::vector<uint16_t> p16;
+    const void* packed;
+    if (host_.precision == PVQ_NOTE_F32) {
+        p32 = note_model_pack_b(W, n, k, conv_order, host_.d.o_pool);
+        packed = p32.data();
+        l.bias_at = p32.size() * sizeof(float);
+    } else {
+        p16 = note_model_pack_b16(W, n, k, conv_order, host_.d.o_pool, host_.precision);
+        packed = p16.data();
+        l.bias_at = p16.size() * sizeof(uint16_t);
+    }
+    // (whole chunks of 4 KiB: the bias is 16-byte aligned)
+    if (pvq_status s = l.buf.reserve(l.bias_at + n * sizeof(float))) return s;
+    PVQ_HIP(hipMemcpy(l.buf.as<char>(), packed, l.bias_at, hipMemcpyHostToDevice));
+    PVQ_HIP(hipMemcpy(l.buf.as<char>() + l.bias_at, bias, n * sizeof(float), hipMemcpyHostToDevice));
+    return PVQ_OK;
+}
+
 pvq_status NoteModel::create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
-                             std::unique_ptr<NoteModel>& out) {
+                             pvq_note_precision precision, std::unique_ptr<NoteModel>& out) {
     out.reset();
     NoteModelDims d;
     std::string err;
-    const pvq_status st = note_model_check(params, weights, d, err);
+    pvq_status st = note_model_check(params, weights, d, err);
+    if (st == PVQ_OK) st = note_model_check_range(d, *weights, precision, err);
     if (st != PVQ_OK) {
         set_last_error(err);
         return st;
     }
     std::unique_ptr<NoteModel> m(new NoteModel());
     m->device_id_ = device_id < 0 ? -1 : device_id;
-    m->host_.assign(d, *weights);
+    m->host_.assign(d, *weights, precision);
     if (device_id >= 0) {
         PVQ_HIP(hipSetDevice(device_id));
         const NoteModelHost& h = m->host_;
         std::vector<float> conv(h.conv_w);
-        size_t at = 0;
-        pvq_status s = upload(conv, h.conv_b.data(), NM_CH, m->conv_, at);
-        if (s == PVQ_OK) s = upload(note_model_pack_b(h.fc1_w.data(), d.mlp, d.n_features, true, d.o_pool), h.fc1_b.data(), d.mlp, m->fc1_, m->fc1_bias_at_);
-        m->layer_ = std::vector<DeviceBuffer>(d.layers);
-        for (uint32_t i = 0; s == PVQ_OK && i < d.layers; ++i)
-            s = upload(note_model_pack_b(h.layer_w[i].data(), d.mlp, d.mlp, false, 0), h.layer_b[i].data(), d.mlp, m->layer_[i], m->layer_bias_at_);
-        if (s == PVQ_OK) s = upload(note_model_pack_b(h.out_w.data(), NM_OUT, d.mlp, false, 0), h.out_b.data(), NM_OUT, m->out_, m->out_bias_at_);
+        conv.insert(conv.end(), h.conv_b.begin(), h.conv_b.end());
+        pvq_status s = m->conv_.upload(conv.data(), NOTE_CONV_VALUES * sizeof(float));
+        if (s == PVQ_OK) s = m->upload(h.fc1_w.data(), h.fc1_b.data(), d.mlp, d.n_features, true, m->fc1_);
+        m->layer_ = std::vector<Layer>(d.layers);
+        for (uint32_t i = 0; s == PVQ_OK && i < d.layers; ++i) s = m->upload(h.layer_w[i].data(), h.layer_b[i].data(), d.mlp, d.mlp, false, m->layer_[i]);
+        if (s == PVQ_OK) s = m->upload(h.out_w.data(), h.out_b.data(), NM_OUT, d.mlp, false, m->out_);
         if (s != PVQ_OK) return s;
     }
     out = std::move(m);
@@ -341,12 +401,17 @@ pvq_status NoteModel::create(int device_id, const pvq_note_model_params* params,
 pvq_status NoteModel::rows_device(const float* d_db, const size_t* n_frames, uint32_t n_streams, size_t stride_frames,
                                   const pvq_note_model_outputs& outs, hipStream_t stream) {
     const NoteModelDims& d = host_.d;
+    const bool half = host_.precision != PVQ_NOTE_F32;
     if (!d_db) {
         set_last_error("note model: d_db is null");
         return PVQ_ERR_INVALID_ARG;
     }
     if (reinterpret_cast<uintptr_t>(outs.d_mask) & 3) {
         set_last_error("note model: d_mask must be 4-byte aligned");
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (half && ((reinterpret_cast<uintptr_t>(outs.d_prob) | reinterpret_cast<uintptr_t>(outs.d_logits)) & 15)) {   // nmh_dense stores float4
+        set_last_error("note model: d_prob and d_logits of a 16-bit handle must be 16-byte aligned");
         return PVQ_ERR_INVALID_ARG;
     }
     if (stride_frames > 0x7fffffffull || (n_streams && stride_frames > (~0ull >> 12) / n_streams)) {
@@ -372,59 +437,28 @@ pvq_status NoteModel::rows_device(const float* d_db, const size_t* n_frames, uin
     const std::vector<NmTile> tiles = note_model_tiles(d, n_frames, n_streams, stride_frames);
     if (tiles.empty()) return PVQ_OK;
 
-    // workspace: the tile table, then two activation buffers of chunk_tiles * 128 rows
-    const size_t tab_bytes = (tiles.size() * sizeof(NmTile) + 255) & ~static_cast<size_t>(255);
-    const size_t tile_bytes = 2 * static_cast<size_t>(NM_BM) * d.mlp * sizeof(float);
-    const uint32_t n_ct_mlp = (d.mlp + NM_BN - 1) / NM_BN;
-    size_t chunk_tiles = ws_limit_ > tab_bytes ? (ws_limit_ - tab_bytes) / tile_bytes : 0;
-    chunk_tiles = std::max<size_t>(1, std::min<size_t>({chunk_tiles, tiles.size(), 0x7fffffffull / std::max<uint32_t>(n_ct_mlp, NM_OUT / NM_BN)}));
-    if (pvq_status s = ws_.reserve(tab_bytes + chunk_tiles * tile_bytes)) return s;
+    NmContext c;
+    c.d = d;
+    c.precision = host_.precision;
+    c.at = note_model_workspace(d, host_.precision, tiles.size(), ws_limit_);
+    if (pvq_status s = ws_.reserve(c.at.total)) return s;
+    c.ws = ws_.as<char>();
+    c.conv = conv_.as<float>();
+    const auto put = [&c](uint32_t i, const Layer& l) {
+        c.w[i] = l.buf.as<char>();
+        c.bias[i] = reinterpret_cast<const float*>(l.buf.as<char>() + l.bias_at);
+    };
+    put(0, fc1_);
+    for (uint32_t i = 0; i < d.layers; ++i) put(1 + i, layer_[i]);
+    put(1 + d.layers, out_);
     NmTile* d_tiles = ws_.as<NmTile>();
-    float* buf[2];
-    buf[0] = reinterpret_cast<float*>(ws_.as<char>() + tab_bytes);
-    buf[1] = buf[0] + chunk_tiles * NM_BM * d.mlp;
     PVQ_HIP(hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(NmTile), hipMemcpyHostToDevice, stream));   // (pageable source: staged before the call returns)
 
+    const size_t chunk_tiles = c.at.chunk_tiles;
     for (size_t t0 = 0; t0 < tiles.size(); t0 += chunk_tiles) {
         const uint32_t nt = static_cast<uint32_t>(std::min(chunk_tiles, tiles.size() - t0));
-        NmArgs a{};
-        a.tiles = d_tiles + t0;
-        a.stride_frames = stride_frames;
-        a.n_bins = d.n_bins;
-        a.t_frames = d.t_frames;
-        a.L = d.L;
-        // fc1 over the fused conv
-        a.db = d_db;
-        a.conv = conv_.as<float>();
-        a.b_packed = fc1_.as<float4>();
-        a.bias = fc1_.as<float>() + fc1_bias_at_;
-        a.h_out = buf[0];
-        a.chunks = d.o_pool;
-        a.k = d.n_features;
-        a.n = d.mlp;
-        a.n_ct = n_ct_mlp;
-        hipLaunchKernelGGL(nm_conv_fc1, dim3(nt * a.n_ct), dim3(NM_THREADS), 0, stream, a);
-        int cur = 0;
-        a.chunks = d.mlp / NM_KC;
-        a.k = d.mlp;
-        for (uint32_t i = 0; i < d.layers; ++i) {
-            a.a_in = buf[cur];
-            a.h_out = buf[cur ^ 1];
-            a.b_packed = layer_[i].as<float4>();
-            a.bias = layer_[i].as<float>() + layer_bias_at_;
-            hipLaunchKernelGGL(nm_dense<0>, dim3(nt * a.n_ct), dim3(NM_THREADS), 0, stream, a);
-            cur ^= 1;
-        }
-        a.a_in = buf[cur];
-        a.h_out = nullptr;
-        a.b_packed = out_.as<float4>();
-        a.bias = out_.as<float>() + out_bias_at_;
-        a.n = NM_OUT;
-        a.n_ct = NM_OUT / NM_BN;
-        a.prob = outs.d_prob;
-        a.logits = outs.d_logits;
-        a.mask = outs.d_mask;
-        hipLaunchKernelGGL(nm_dense<1>, dim3(nt * a.n_ct), dim3(NM_THREADS), 0, stream, a);
+        if (half) nmh_chunk(c, d_tiles + t0, nt, d_db, stride_frames, outs, stream);
+        else nm_chunk(c, d_tiles + t0, nt, d_db, stride_frames, outs, stream);
     }
     PVQ_HIP(hipGetLastError());
     return PVQ_OK;

@@ -6,7 +6,10 @@
 //   nm_conv_fc1   conv + ReLU + pool computed in registers as the A operand of the first Linear; the [rows][n_features]
 //                 activation never exists in memory
 //   nm_dense<ACT> one launch per further Linear; the output layer writes logits, sigmoid and the 128-bit mask in its epilogue
-// Hidden activations go through a grow-only workspace of the handle; rows are processed in chunks of whole tiles that fit its limit.
+// A handle created with PVQ_NOTE_BF16 or PVQ_NOTE_F16 runs the kernels of note_model_half.hip instead (note_model_half.hpp).  Either
+// way NoteModel::rows_device is the one driver: the argument checks, the zeroed outputs, the tile list, the planned workspace
+// (note_model_workspace), the loop over chunks of whole tiles that fit its limit.  Two things are per precision: how a dense layer
+// is packed when it is uploaded, and the launches of one chunk.
 // NoteModelHost (note_model_plan.hpp) is the one-row host face.
 #pragma once
 
@@ -25,12 +28,18 @@ namespace pvq {
 
 class NoteModel {
    public:
-    // sizes and pointers are checked before any device is touched.  device_id < 0: a host-only object (infer works, rows_device
-    // returns PVQ_ERR_NO_DEVICE after its argument checks).
+    // sizes and pointers are checked before any device is touched, then (PVQ_NOTE_F16) the range of the dense weights.  device_id < 0:
+    // a host-only object (infer works, rows_device returns PVQ_ERR_NO_DEVICE after its argument checks).
     static pvq_status create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
-                             std::unique_ptr<NoteModel>& out);
+                             std::unique_ptr<NoteModel>& out) {
+        return create(device_id, params, weights, PVQ_NOTE_F32, out);
+    }
+    // precision: one of pvq_note_precision (the caller has checked that)
+    static pvq_status create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
+                             pvq_note_precision precision, std::unique_ptr<NoteModel>& out);
     ~NoteModel();
     const NoteModelDims& dims() const { return host_.d; }
+    pvq_note_precision precision() const { return host_.precision; }
     int device() const { return device_id_; }
     void infer(const float* window, float* out_prob) const { host_.infer(window, out_prob); }
     // n_frames: HOST array or null.  Asynchronous on `stream`; uses the handle's workspace, so one stream at a time.
@@ -40,15 +49,18 @@ class NoteModel {
 
    private:
     NoteModel() = default;
+    struct Layer {
+        DeviceBuffer buf;     // the operand packed for the precision's kernel, then the f32 bias
+        size_t bias_at = 0;   // byte offset of the bias, a multiple of 16
+    };
+    pvq_status upload(const float* W, const float* bias, uint32_t n, uint32_t k, bool conv_order, Layer& l);
     int device_id_ = -1;
     NoteModelHost host_;
     uint64_t ws_limit_ = 256ull << 20;
-    DeviceBuffer conv_;                    // floats: conv weights [16][5], then bias [16]
-    DeviceBuffer fc1_;                     // floats: packed B operand, then bias [mlp]
-    std::vector<DeviceBuffer> layer_;      // floats: packed B operand, then bias [mlp], per hidden layer
-    DeviceBuffer out_;                     // floats: packed B operand, then bias [128]
-    size_t fc1_bias_at_ = 0, layer_bias_at_ = 0, out_bias_at_ = 0;   // float offsets of the biases
-    DeviceBuffer ws_;                      // grow-only: tile table, then two [chunk rows][mlp] activation buffers
+    DeviceBuffer conv_;          // floats: conv weights [16][5], then bias [16]
+    Layer fc1_, out_;
+    std::vector<Layer> layer_;   // the hidden layers
+    DeviceBuffer ws_;            // grow-only: NmWorkspace
 };
 
 }  // namespace pvq

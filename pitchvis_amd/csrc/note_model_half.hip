@@ -15,10 +15,7 @@
 // A row's result depends on its window alone: equal windows give equal bits wherever the row sits.
 #include "note_model_half.hpp"
 
-#include <algorithm>
-#include <string>
-
-#include "vqt_engine.hpp"
+#include "note_device.hpp"
 
 namespace pvq {
 
@@ -88,13 +85,8 @@ __global__ __launch_bounds__(64) void nmh_features(const NmhArgs a) {
         for (int j = 0; j < NM_KW + 2; ++j) x[j] = xrow[j];   // 4 p + 6 <= L - 1 for p < o_pool
 #pragma unroll
         for (int c = 0; c < NM_CH; ++c) {
-            float e = a.conv[NM_CH * NM_KW + c], o = e;   // conv positions 2 p and 2 p + 1
-#pragma unroll
-            for (int j = 0; j < NM_KW; ++j) {
-                const float w = a.conv[c * NM_KW + j];
-                e = fmaf(w, x[j], e);
-                o = fmaf(w, x[2 + j], o);
-            }
+            float e, o;   // conv positions 2 p and 2 p + 1
+            conv_pair(a.conv + c * NM_KW, a.conv[NM_CH * NM_KW + c], x, e, o);
             const T v = static_cast<T>(fmaxf(fmaxf(e, o), 0.0f));
             if (c < 8) lo[c] = v;
             else hi[c - 8] = v;
@@ -253,143 +245,53 @@ constexpr Kernels kernels_of() {
 }
 }  // namespace
 
-NoteModelHalf::~NoteModelHalf() {
-    if (device_id_ >= 0) (void)hipSetDevice(device_id_);   // the buffers go after this body, with their device set
-}
-
-pvq_status NoteModelHalf::upload(const float* W, const float* bias, uint32_t n, uint32_t k, bool conv_order, Layer& l) {
-    const std::vector<uint16_t> packed = note_model_pack_b16(W, n, k, conv_order, host_.d.o_pool, host_.precision);
-    l.bias_at = packed.size() * sizeof(uint16_t);   // whole 4 KiB chunks: the bias is 16-byte aligned
-    if (pvq_status s = l.buf.reserve(l.bias_at + n * sizeof(float))) return s;
-    PVQ_HIP(hipMemcpy(l.buf.as<char>(), packed.data(), l.bias_at, hipMemcpyHostToDevice));
-    PVQ_HIP(hipMemcpy(l.buf.as<char>() + l.bias_at, bias, n * sizeof(float), hipMemcpyHostToDevice));
-    return PVQ_OK;
-}
-
-pvq_status NoteModelHalf::create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
-                                 pvq_note_precision precision, std::unique_ptr<NoteModelHalf>& out) {
-    out.reset();
-    NoteModelDims d;
-    std::string err;
-    pvq_status st = note_model_check(params, weights, d, err);
-    if (st == PVQ_OK) st = note_model_check_range(d, *weights, precision, err);
-    if (st != PVQ_OK) {
-        set_last_error(err);
-        return st;
-    }
-    std::unique_ptr<NoteModelHalf> m(new NoteModelHalf());
-    m->device_id_ = device_id < 0 ? -1 : device_id;
-    m->host_.assign(d, *weights, precision);
-    if (device_id >= 0) {
-        PVQ_HIP(hipSetDevice(device_id));
-        const NoteModelHost& h = m->host_;
-        std::vector<float> conv(h.conv_w);
-        conv.insert(conv.end(), h.conv_b.begin(), h.conv_b.end());
-        pvq_status s = m->conv_.upload(conv.data(), conv.size() * sizeof(float));
-        if (s == PVQ_OK) s = m->upload(h.fc1_w.data(), h.fc1_b.data(), d.mlp, d.n_features, true, m->fc1_);
-        m->layer_ = std::vector<Layer>(d.layers);
-        for (uint32_t i = 0; s == PVQ_OK && i < d.layers; ++i) s = m->upload(h.layer_w[i].data(), h.layer_b[i].data(), d.mlp, d.mlp, false, m->layer_[i]);
-        if (s == PVQ_OK) s = m->upload(h.out_w.data(), h.out_b.data(), NM_OUT, d.mlp, false, m->out_);
-        if (s != PVQ_OK) return s;
-    }
-    out = std::move(m);
-    return PVQ_OK;
-}
-
-pvq_status NoteModelHalf::rows_device(const float* d_db, const size_t* n_frames, uint32_t n_streams, size_t stride_frames,
-                                      const pvq_note_model_outputs& outs, hipStream_t stream) {
-    const NoteModelDims& d = host_.d;
-    // the checks of NoteModel::rows_device, in its order
-    if (!d_db) {
-        set_last_error("note model: d_db is null");
-        return PVQ_ERR_INVALID_ARG;
-    }
-    if (reinterpret_cast<uintptr_t>(outs.d_mask) & 3) {
-        set_last_error("note model: d_mask must be 4-byte aligned");
-        return PVQ_ERR_INVALID_ARG;
-    }
-    if ((reinterpret_cast<uintptr_t>(outs.d_prob) | reinterpret_cast<uintptr_t>(outs.d_logits)) & 15) {
-        set_last_error("note model: d_prob and d_logits of a 16-bit handle must be 16-byte aligned");
-        return PVQ_ERR_INVALID_ARG;
-    }
-    if (stride_frames > 0x7fffffffull || (n_streams && stride_frames > (~0ull >> 12) / n_streams)) {
-        set_last_error("note model: too many frames in one call");
-        return PVQ_ERR_INVALID_ARG;
-    }
-    for (uint32_t s = 0; n_frames && s < n_streams; ++s)
-        if (n_frames[s] > stride_frames) {
-            set_last_error("note model: n_frames of stream " + std::to_string(s) + " exceeds stride_frames");
-            return PVQ_ERR_INVALID_ARG;
-        }
-    if (device_id_ < 0) {
-        set_last_error("the batched note model runs on a GPU; this handle has none (pvq_note_model_infer is the host face)");
-        return PVQ_ERR_NO_DEVICE;
-    }
-    const size_t rows_all = static_cast<size_t>(n_streams) * stride_frames;
-    if (rows_all == 0 || !(outs.d_prob || outs.d_logits || outs.d_mask)) return PVQ_OK;
-    PVQ_HIP(hipSetDevice(device_id_));
-    // every row that is no model row is zero; the model rows are overwritten below
-    if (outs.d_prob) PVQ_HIP(hipMemsetAsync(outs.d_prob, 0, rows_all * NM_OUT * sizeof(float), stream));
-    if (outs.d_logits) PVQ_HIP(hipMemsetAsync(outs.d_logits, 0, rows_all * NM_OUT * sizeof(float), stream));
-    if (outs.d_mask) PVQ_HIP(hipMemsetAsync(outs.d_mask, 0, rows_all * 4 * sizeof(uint32_t), stream));
-    const std::vector<NmTile> tiles = note_model_tiles(d, n_frames, n_streams, stride_frames);
-    if (tiles.empty()) return PVQ_OK;
-
-    const NmHalfWorkspace w = note_model_half_workspace(d, tiles.size(), ws_limit_);
-    if (pvq_status s = ws_.reserve(w.total)) return s;
-    NmTile* d_tiles = ws_.as<NmTile>();
-    PVQ_HIP(hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(NmTile), hipMemcpyHostToDevice, stream));   // (pageable source: staged before the call returns)
-    const Kernels kern = host_.precision == PVQ_NOTE_BF16 ? kernels_of<PVQ_NOTE_BF16>() : kernels_of<PVQ_NOTE_F16>();
-    const auto bias_of = [](const Layer& l) { return reinterpret_cast<const float*>(l.buf.as<char>() + l.bias_at); };
-    char* ws = ws_.as<char>();
-
-    for (size_t t0 = 0; t0 < tiles.size(); t0 += w.chunk_tiles) {
-        const uint32_t nt = static_cast<uint32_t>(std::min(w.chunk_tiles, tiles.size() - t0));
-        NmhArgs a{};
-        a.tiles = d_tiles + t0;
-        a.stride_frames = stride_frames;
-        a.n_bins = d.n_bins;
-        a.t_frames = d.t_frames;
-        a.o_pool = d.o_pool;
-        // the features, once per row
-        a.db = d_db;
-        a.conv = conv_.as<float>();
-        a.h_out = ws + w.feat_at;
-        a.k_pad = w.kf_pad;
-        a.p_blocks = (w.kf_pad / NM_CH + 63) / 64;
-        hipLaunchKernelGGL(kern.features, dim3(nt * NM_BM * a.p_blocks), dim3(64), 0, stream, a);
-        // fc1
-        a.x_in = ws + w.feat_at;
-        a.w_packed = fc1_.buf.as<u32x4>();
-        a.bias = bias_of(fc1_);
-        a.h_out = ws + w.h_at[0];
-        a.n = d.mlp;
-        a.n_pad = w.mlp_pad;
-        a.n_ct = (d.mlp + NM_BN - 1) / NM_BN;
+void nmh_chunk(const NmContext& c, const NmTile* d_tiles, uint32_t nt, const float* d_db, size_t stride_frames,
+               const pvq_note_model_outputs& outs, hipStream_t stream) {
+    const NoteModelDims& d = c.d;
+    const NmWorkspace& w = c.at;
+    const Kernels kern = c.precision == PVQ_NOTE_BF16 ? kernels_of<PVQ_NOTE_BF16>() : kernels_of<PVQ_NOTE_F16>();
+    NmhArgs a{};
+    a.tiles = d_tiles;
+    a.stride_frames = stride_frames;
+    a.n_bins = d.n_bins;
+    a.t_frames = d.t_frames;
+    a.o_pool = d.o_pool;
+    // the features, once per row
+    a.db = d_db;
+    a.conv = c.conv;
+    a.h_out = c.ws + w.feat_at;
+    a.k_pad = w.kf_pad;
+    a.p_blocks = (w.kf_pad / NM_CH + 63) / 64;
+    hipLaunchKernelGGL(kern.features, dim3(nt * NM_BM * a.p_blocks), dim3(64), 0, stream, a);
+    // fc1
+    a.x_in = c.ws + w.feat_at;
+    a.w_packed = static_cast<const u32x4*>(c.w[0]);
+    a.bias = c.bias[0];
+    a.h_out = c.ws + w.h_at[0];
+    a.n = d.mlp;
+    a.n_pad = w.mlp_pad;
+    a.n_ct = (d.mlp + NM_BN - 1) / NM_BN;
+    hipLaunchKernelGGL(kern.hidden, dim3(nt * a.n_ct), dim3(NMH_THREADS), 0, stream, a);
+    int cur = 0;
+    a.k_pad = w.mlp_pad;
+    for (uint32_t i = 1; i <= d.layers; ++i) {
+        a.x_in = c.ws + w.h_at[cur];
+        a.h_out = c.ws + w.h_at[cur ^ 1];
+        a.w_packed = static_cast<const u32x4*>(c.w[i]);
+        a.bias = c.bias[i];
         hipLaunchKernelGGL(kern.hidden, dim3(nt * a.n_ct), dim3(NMH_THREADS), 0, stream, a);
-        int cur = 0;
-        a.k_pad = w.mlp_pad;
-        for (const Layer& l : layer_) {
-            a.x_in = ws + w.h_at[cur];
-            a.h_out = ws + w.h_at[cur ^ 1];
-            a.w_packed = l.buf.as<u32x4>();
-            a.bias = bias_of(l);
-            hipLaunchKernelGGL(kern.hidden, dim3(nt * a.n_ct), dim3(NMH_THREADS), 0, stream, a);
-            cur ^= 1;
-        }
-        a.x_in = ws + w.h_at[cur];
-        a.h_out = nullptr;
-        a.w_packed = out_.buf.as<u32x4>();
-        a.bias = bias_of(out_);
-        a.n = a.n_pad = NM_OUT;
-        a.n_ct = NM_OUT / NM_BN;
-        a.prob = outs.d_prob;
-        a.logits = outs.d_logits;
-        a.mask = outs.d_mask;
-        hipLaunchKernelGGL(kern.output, dim3(nt * a.n_ct), dim3(NMH_THREADS), 0, stream, a);
+        cur ^= 1;
     }
-    PVQ_HIP(hipGetLastError());
-    return PVQ_OK;
+    a.x_in = c.ws + w.h_at[cur];
+    a.h_out = nullptr;
+    a.w_packed = static_cast<const u32x4*>(c.w[d.layers + 1]);
+    a.bias = c.bias[d.layers + 1];
+    a.n = a.n_pad = NM_OUT;
+    a.n_ct = NM_OUT / NM_BN;
+    a.prob = outs.d_prob;
+    a.logits = outs.d_logits;
+    a.mask = outs.d_mask;
+    hipLaunchKernelGGL(kern.output, dim3(nt * a.n_ct), dim3(NMH_THREADS), 0, stream, a);
 }
 
 }  // namespace pvq

@@ -5,50 +5,35 @@
 // Two kernels (note_model_half.hip), one template parameter for the type:
 //   nmh_features    conv + ReLU + pool once per row, rounded, written as [rows][pad32(n_features)] in the order k' = 16 p + c
 //   nmh_dense<ACT>  one launch per Linear, fc1 included; the output layer writes logits, sigmoid and the 128-bit mask
-// The workspace is note_model_half_workspace's (note_model_plan.hpp); rows are processed in chunks of whole tiles that fit its limit.
+// NoteModel owns the buffers and drives a call; a PVQ_NOTE_BF16 / PVQ_NOTE_F16 handle calls nmh_chunk below for every chunk of tiles
+// where an f32 handle launches nm_conv_fc1 / nm_dense.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
-#include <memory>
-#include <vector>
 
 #include "../../include/pvq.h"
-#include "device_support.hpp"
 #include "note_model_plan.hpp"
 
 namespace pvq {
 
-class NoteModelHalf {
-   public:
-    // precision: PVQ_NOTE_BF16 or PVQ_NOTE_F16.  Checks as NoteModel::create, then the f16 weight range; device_id < 0: host-only
-    static pvq_status create(int device_id, const pvq_note_model_params* params, const pvq_note_model_weights* weights,
-                             pvq_note_precision precision, std::unique_ptr<NoteModelHalf>& out);
-    ~NoteModelHalf();
-    const NoteModelDims& dims() const { return host_.d; }
-    pvq_note_precision precision() const { return host_.precision; }
-    void infer(const float* window, float* out_prob) const { host_.infer(window, out_prob); }
-    // the contract of NoteModel::rows_device
-    pvq_status rows_device(const float* d_db, const size_t* n_frames, uint32_t n_streams, size_t stride_frames,
-                           const pvq_note_model_outputs& outs, hipStream_t stream);
-    void set_workspace_limit(uint64_t bytes) { ws_limit_ = bytes; }
+constexpr int NM_MAX_DENSE = 10;   // dense layers of a model: fc1, up to 8 hidden layers (note_model_check), the output layer
 
-   private:
-    NoteModelHalf() = default;
-    struct Layer {
-        DeviceBuffer buf;     // the packed 16-bit operand, then the f32 bias
-        size_t bias_at = 0;   // byte offset of the bias
-    };
-    pvq_status upload(const float* W, const float* bias, uint32_t n, uint32_t k, bool conv_order, Layer& l);
-    int device_id_ = -1;
-    NoteModelHost host_;
-    uint64_t ws_limit_ = 256ull << 20;
-    DeviceBuffer conv_;          // floats: conv weights [16][5], then bias [16]
-    Layer fc1_, out_;
-    std::vector<Layer> layer_;
-    DeviceBuffer ws_;            // grow-only: NmHalfWorkspace
+// what the launches of one chunk of tiles work on, either path: the handle's buffers, nothing owned
+struct NmContext {
+    NoteModelDims d;
+    pvq_note_precision precision = PVQ_NOTE_F32;
+    const float* conv = nullptr;                // conv weights [16][5], then bias [16]
+    const void* w[NM_MAX_DENSE] = {};           // the packed operand of fc1, of the d.layers hidden layers, of the output layer
+    const float* bias[NM_MAX_DENSE] = {};       //   and their biases
+    char* ws = nullptr;                         // the workspace
+    NmWorkspace at;                             //   and where its pieces lie
 };
+
+// the 16-bit launches of the tiles d_tiles[0 .. nt): features, fc1, the hidden layers, the output layer into `outs`.  Queues only.
+void nmh_chunk(const NmContext& c, const NmTile* d_tiles, uint32_t nt, const float* d_db, size_t stride_frames,
+               const pvq_note_model_outputs& outs, hipStream_t stream);
 
 }  // namespace pvq

@@ -165,19 +165,24 @@ std::vector<uint16_t> note_model_pack_b16(const float* W, uint32_t n, uint32_t k
     return out;
 }
 
-NmHalfWorkspace note_model_half_workspace(const NoteModelDims& d, size_t n_tiles, uint64_t limit) {
-    NmHalfWorkspace w;
-    w.kf_pad = note_model_pad32(d.n_features);
-    w.mlp_pad = note_model_pad32(d.mlp);
+NmWorkspace note_model_workspace(const NoteModelDims& d, pvq_note_precision precision, size_t n_tiles, uint64_t limit) {
+    NmWorkspace w;
+    const bool half = precision != PVQ_NOTE_F32;
+    if (half) {
+        w.kf_pad = note_model_pad32(d.n_features);
+        w.mlp_pad = note_model_pad32(d.mlp);
+    }
+    const size_t row_bytes = half ? 2 * static_cast<size_t>(w.mlp_pad) : sizeof(float) * static_cast<size_t>(d.mlp);   // of a hidden buffer
+    const size_t feat_bytes = 2 * static_cast<size_t>(w.kf_pad);                                                       // of the features: 16-bit only
     w.tab_bytes = (n_tiles * sizeof(NmTile) + 255) & ~static_cast<size_t>(255);
-    w.tile_bytes = static_cast<size_t>(NM_BM) * 2 * (static_cast<size_t>(w.kf_pad) + 2 * static_cast<size_t>(w.mlp_pad));
-    // a launch's grid: the features kernel has a block per row and 64 pooled positions, the dense kernel one per tile and column tile
+    w.tile_bytes = static_cast<size_t>(NM_BM) * (feat_bytes + 2 * row_bytes);
+    // a launch's grid: the features kernel has a block per row and 64 pooled positions, a dense kernel one per tile and column tile
     const size_t per_tile = std::max<size_t>({static_cast<size_t>(NM_BM) * ((w.kf_pad / NM_CH + 63) / 64), (d.mlp + NM_BN - 1) / NM_BN, NM_OUT / NM_BN});
-    size_t fit = limit > w.tab_bytes ? static_cast<size_t>((limit - w.tab_bytes) / w.tile_bytes) : 0;
+    const size_t fit = limit > w.tab_bytes ? static_cast<size_t>((limit - w.tab_bytes) / w.tile_bytes) : 0;
     w.chunk_tiles = std::max<size_t>(1, std::min<size_t>({fit, n_tiles, 0x7fffffffull / per_tile}));
-    w.feat_at = w.tab_bytes;
-    w.h_at[0] = w.feat_at + w.chunk_tiles * NM_BM * 2 * w.kf_pad;
-    w.h_at[1] = w.h_at[0] + w.chunk_tiles * NM_BM * 2 * w.mlp_pad;
+    if (half) w.feat_at = w.tab_bytes;
+    w.h_at[0] = w.tab_bytes + w.chunk_tiles * NM_BM * feat_bytes;
+    w.h_at[1] = w.h_at[0] + w.chunk_tiles * NM_BM * row_bytes;
     w.total = w.tab_bytes + w.chunk_tiles * w.tile_bytes;
     return w;
 }

@@ -82,14 +82,21 @@ pvq_status note_model_check_range(const NoteModelDims& d, const pvq_note_model_w
 std::vector<uint16_t> note_model_pack_b16(const float* W, uint32_t n, uint32_t k, bool conv_order, uint32_t o_pool, pvq_note_precision prec);
 inline uint32_t note_model_stages16(uint32_t k) { return (note_model_pad32(k) / NM_KC16 + NM_PC - 1) / NM_PC; }
 
-// the workspace of a 16-bit call: the tile table, then per chunk of tiles the rounded features [rows][pad32(n_features)] and two
-// hidden buffers [rows][pad32(mlp)], 2 bytes a value.  chunk_tiles: the whole tiles that fit `limit`, at least one, at most n_tiles
-// and what a launch's grid takes.
-struct NmHalfWorkspace {
+// ---- the workspace of a call, every precision ----
+// The tile table (rounded up to 256 bytes), then per chunk of tiles two hidden buffers: PVQ_NOTE_F32 [rows][mlp] floats; 16-bit
+// [rows][pad32(mlp)] of 2 bytes a value, behind the rounded features [rows][pad32(n_features)].  chunk_tiles: the whole tiles that
+// fit `limit`, at least one, at most n_tiles and what a launch's grid takes.  feat_at, kf_pad and mlp_pad are the 16-bit path's and
+// stay zero for PVQ_NOTE_F32.
+struct NmWorkspace {
     size_t tab_bytes = 0, tile_bytes = 0, chunk_tiles = 0;
     size_t feat_at = 0, h_at[2] = {0, 0}, total = 0;   // byte offsets
     uint32_t kf_pad = 0, mlp_pad = 0;
 };
-NmHalfWorkspace note_model_half_workspace(const NoteModelDims& d, size_t n_tiles, uint64_t limit);
+NmWorkspace note_model_workspace(const NoteModelDims& d, pvq_note_precision precision, size_t n_tiles, uint64_t limit);
+// the 16-bit cut under the name it had before the f32 cut joined it (bf16 and f16 share it): a program written against that name keeps building
+using NmHalfWorkspace = NmWorkspace;
+inline NmHalfWorkspace note_model_half_workspace(const NoteModelDims& d, size_t n_tiles, uint64_t limit) {
+    return note_model_workspace(d, PVQ_NOTE_BF16, n_tiles, limit);
+}
 
 }  // namespace pvq

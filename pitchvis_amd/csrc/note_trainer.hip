@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "note_device.hpp"
 #include "vqt_engine.hpp"
 
 namespace pvq {
@@ -27,21 +28,9 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int NT_THREADS = 256;
 constexpr int NT_LD = NT_BK + 4;   // LDS row: 36 floats, 16-byte aligned rows, 16-byte reads of neighbouring rows on different banks
-constexpr int NT_CONV_OUT = NM_CH * NM_KW + NM_CH;   // 96 conv gradients: weights [16][5], then bias [16]
 
 enum { G_NT = 0, G_NN = 1, G_TN = 2 };
-enum { E_RAW = 0, E_BIAS = 1, E_HIDDEN = 2, E_GATE = 3 };
-
-// what happens to an element of a product before it is stored
-struct Epi {
-    int kind;            // E_RAW: nothing.  E_BIAS: + bias[col].  E_HIDDEN: ReLU(+ bias[col]), then dropout.  E_GATE: * (gate > 0 ? scale : 0)
-    const float* bias;   // [N]
-    const float* gate;   // E_GATE: [M][N], the activation this gradient flows back through (as stored: after ReLU and dropout)
-    float scale;         // 1 / (1 - p) where dropout applies, else 1
-    int drop;            // E_HIDDEN: apply the mask
-    uint32_t threshold;  // keep when the 24-bit draw >= threshold
-    uint64_t key;        // nt_layer_key(seed, step, layer)
-};
+using Epi = NoteEpi<float>;   // the gate is an f32 activation [M][N]: gemm() sets its row length
 
 struct GemmArgs {
     const float* A;
@@ -53,17 +42,6 @@ struct GemmArgs {
     uint32_t stages, stages_per_split, splits;
     Epi e;
 };
-
-__device__ __forceinline__ float epi_apply(const Epi& e, float v, uint32_t row, uint32_t col, uint32_t N) {
-    if (e.kind == E_BIAS) return v + e.bias[col];
-    if (e.kind == E_HIDDEN) {
-        v = fmaxf(v + e.bias[col], 0.0f);
-        if (e.drop) v = nt_keep(e.key, row, col, e.threshold) ? v * e.scale : 0.0f;
-        return v;
-    }
-    if (e.kind == E_GATE) return e.gate[static_cast<size_t>(row) * N + col] > 0.0f ? v * e.scale : 0.0f;
-    return v;
-}
 
 // k along the rows of src: tile rows r0 .. r0 + 63 (bound R), k0 .. k0 + 31 (bound K, a multiple of 4) -> two 16-byte pieces per thread
 __device__ __forceinline__ void fetch_rows(const float* __restrict__ src, uint32_t ld, uint32_t R, uint32_t r0, uint32_t K, uint32_t k0, f32x4 (&r)[2]) {
@@ -166,7 +144,7 @@ __global__ __launch_bounds__(NT_THREADS) void nt_gemm(const GemmArgs a) {
             const uint32_t col = n0 + 16 * s + c;
             if (col >= a.N) continue;
             const float v = acc[s][reg];
-            dst[static_cast<size_t>(row) * a.N + col] = a.splits > 1 ? v : epi_apply(a.e, v, row, col, a.N);
+            dst[static_cast<size_t>(row) * a.N + col] = a.splits > 1 ? v : epi_apply(a.e, v, row, col);
         }
     }
 }
@@ -178,29 +156,18 @@ __global__ __launch_bounds__(NT_THREADS) void nt_gemm_finish(const float* __rest
     if (i >= mn) return;
     float v = part[i];
     for (uint32_t z = 1; z < splits; ++z) v += part[z * mn + i];
-    C[i] = epi_apply(e, v, static_cast<uint32_t>(i / N), static_cast<uint32_t>(i % N), N);
-}
-
-// the two conv positions a pooled position covers (train.py:89-90), as nm_conv_fc1 evaluates them: bias first, taps in order, fused
-__device__ __forceinline__ void conv_pair(const float* w5, float cb, const float* x, float& e, float& o) {
-    e = cb;
-    o = cb;
-#pragma unroll
-    for (int j = 0; j < NM_KW; ++j) {
-        e = fmaf(w5[j], x[j], e);
-        o = fmaf(w5[j], x[2 + j], o);
-    }
+    C[i] = epi_apply(e, v, static_cast<uint32_t>(i / N), static_cast<uint32_t>(i % N));
 }
 
 // feat[b][c * o_pool + p] = max(conv[c][2 p], conv[c][2 p + 1], 0) of the window that ends at row idx[b] (train.py:17-21,46,89-91)
 __global__ __launch_bounds__(NT_THREADS) void nt_features(const float* __restrict__ db, const uint32_t* __restrict__ idx, const float* __restrict__ conv,
                                                           float* __restrict__ feat, uint32_t n_bins, uint32_t t_frames, uint32_t L, uint32_t o_pool) {
     extern __shared__ float s_x[];   // the window, L floats
-    __shared__ float s_w[NT_CONV_OUT];
+    __shared__ float s_w[NOTE_CONV_VALUES];
     const uint32_t b = blockIdx.x;
     const float* x = db + (static_cast<size_t>(idx[b]) - (t_frames - 1)) * n_bins;
     for (uint32_t i = threadIdx.x; i < L; i += NT_THREADS) s_x[i] = x[i];
-    if (threadIdx.x < NT_CONV_OUT) s_w[threadIdx.x] = conv[threadIdx.x];
+    if (threadIdx.x < NOTE_CONV_VALUES) s_w[threadIdx.x] = conv[threadIdx.x];
     __syncthreads();
     const uint32_t F = NM_CH * o_pool;
     float* dst = feat + static_cast<size_t>(b) * F;
@@ -219,12 +186,12 @@ __global__ __launch_bounds__(NT_THREADS) void nt_conv_grad(const float* __restri
                                                            const float* __restrict__ dfeat, float* __restrict__ part, uint32_t n_bins, uint32_t t_frames,
                                                            uint32_t L, uint32_t o_pool) {
     extern __shared__ float s_x[];
-    __shared__ float s_w[NT_CONV_OUT];
+    __shared__ float s_w[NOTE_CONV_VALUES];
     __shared__ float s_red[NT_THREADS][NM_KW + 1];
     const uint32_t b = blockIdx.x;
     const float* x = db + (static_cast<size_t>(idx[b]) - (t_frames - 1)) * n_bins;
     for (uint32_t i = threadIdx.x; i < L; i += NT_THREADS) s_x[i] = x[i];
-    if (threadIdx.x < NT_CONV_OUT) s_w[threadIdx.x] = conv[threadIdx.x];
+    if (threadIdx.x < NOTE_CONV_VALUES) s_w[threadIdx.x] = conv[threadIdx.x];
     __syncthreads();
     const uint32_t ch = threadIdx.x >> 4, q = threadIdx.x & 15;
     const float* g_row = dfeat + static_cast<size_t>(b) * NM_CH * o_pool + static_cast<size_t>(ch) * o_pool;
@@ -246,18 +213,18 @@ __global__ __launch_bounds__(NT_THREADS) void nt_conv_grad(const float* __restri
 #pragma unroll
     for (int j = 0; j <= NM_KW; ++j) s_red[threadIdx.x][j] = acc[j];
     __syncthreads();
-    if (threadIdx.x < NT_CONV_OUT) {
+    if (threadIdx.x < NOTE_CONV_VALUES) {
         const uint32_t c2 = threadIdx.x / (NM_KW + 1), j = threadIdx.x % (NM_KW + 1);
         float s = 0.0f;
         for (int k = 0; k < 16; ++k) s += s_red[16 * c2 + k][j];
-        part[static_cast<size_t>(b) * NT_CONV_OUT + (j < NM_KW ? c2 * NM_KW + j : NM_CH * NM_KW + c2)] = s;
+        part[static_cast<size_t>(b) * NOTE_CONV_VALUES + (j < NM_KW ? c2 * NM_KW + j : NM_CH * NM_KW + c2)] = s;
     }
 }
 // grad[i] = part[0][i] + part[1][i] + ... in row order
 __global__ __launch_bounds__(128) void nt_conv_reduce(const float* __restrict__ part, float* __restrict__ grad, uint32_t batch) {
-    if (threadIdx.x >= NT_CONV_OUT) return;
+    if (threadIdx.x >= NOTE_CONV_VALUES) return;
     float s = 0.0f;
-    for (uint32_t b = 0; b < batch; ++b) s += part[static_cast<size_t>(b) * NT_CONV_OUT + threadIdx.x];
+    for (uint32_t b = 0; b < batch; ++b) s += part[static_cast<size_t>(b) * NOTE_CONV_VALUES + threadIdx.x];
     grad[threadIdx.x] = s;
 }
 
@@ -442,6 +409,7 @@ void gemm(int mode, const float* A, const float* B, float* C, uint32_t M, uint32
     a.splits = (a.stages + a.stages_per_split - 1) / a.stages_per_split;   // no empty split
     a.C = a.splits > 1 ? part : C;
     a.e = e;
+    a.e.ldg = N;
     const dim3 grid(((M + NT_BM - 1) / NT_BM) * a.n_ct, a.splits);
     if (mode == G_NT) hipLaunchKernelGGL(nt_gemm<G_NT>, grid, dim3(NT_THREADS), 0, stream, a);
     else if (mode == G_NN) hipLaunchKernelGGL(nt_gemm<G_NN>, grid, dim3(NT_THREADS), 0, stream, a);
@@ -449,7 +417,7 @@ void gemm(int mode, const float* A, const float* B, float* C, uint32_t M, uint32
     if (a.splits > 1) {
         const size_t mn = static_cast<size_t>(M) * N;
         hipLaunchKernelGGL(nt_gemm_finish, dim3(static_cast<uint32_t>((mn + NT_THREADS - 1) / NT_THREADS)), dim3(NT_THREADS), 0, stream, part, C, M, N,
-                           a.splits, e);
+                           a.splits, a.e);
     }
 }
 }  // namespace
@@ -522,7 +490,7 @@ pvq_status NoteTrainer::create(int device_id, const pvq_note_model_params* param
         t->ws_da_ = take(2 * round64(B * d.mlp));
         t->ws_z_ = take(B * NM_OUT);
         t->ws_dz_ = take(B * NM_OUT);
-        t->ws_convpart_ = take(B * NT_CONV_OUT);
+        t->ws_convpart_ = take(B * NOTE_CONV_VALUES);
         t->ws_rowloss_ = take(2 * B);   // doubles
         t->ws_part_ = take(NT_PART_FLOATS);
         t->ws_idx_ = take(B);           // uint32
@@ -598,6 +566,48 @@ void NoteTrainer::forward(const float* d_db, uint32_t batch, bool train, hipStre
     gemm(G_NT, H(d.layers), w + lay_.out_w.at, Z, batch, NM_OUT, mlp, mlp, mlp, e, part, stream);
 }
 
+// backward from nt_loss's dZ: the output layer, the hidden layers from the last to the first, fc1 -> every dense gradient, dfeat
+void NoteTrainer::backward(uint32_t batch, hipStream_t stream) {
+    if (precision_ == PVQ_NOTE_BF16) {
+        nth_backward(half_context(), batch, stream);
+        return;
+    }
+    const NoteModelDims& d = lay_.d;
+    const float* w = arena_.as<float>();
+    float* grad = arena_.as<float>() + lay_.n_params;
+    const size_t h_stride = round64(static_cast<size_t>(max_batch_) * d.mlp);
+    auto H = [&](uint32_t i) { return ws(ws_h_) + i * h_stride; };
+    float* dA[2] = {ws(ws_da_), ws(ws_da_) + h_stride};
+    float* dZ = ws(ws_dz_);
+    float* part = ws(ws_part_);
+    const uint32_t F = d.n_features, mlp = d.mlp;
+    const bool drop = nt_keep_threshold(hyper_.dropout) > 0;
+    const float scale = drop ? static_cast<float>(1.0 / (1.0 - hyper_.dropout)) : 1.0f;
+
+    Epi raw{};
+    raw.kind = E_RAW;
+    Epi gate{};
+    gate.kind = E_GATE;
+    gemm(G_TN, dZ, H(d.layers), grad + lay_.out_w.at, NM_OUT, mlp, batch, NM_OUT, mlp, raw, part, stream);
+    hipLaunchKernelGGL(nt_bias_grad, dim3((NM_OUT + 63) / 64), dim3(NT_THREADS), 0, stream, dZ, grad + lay_.out_b.at, batch, static_cast<uint32_t>(NM_OUT));
+    int cur = 0;
+    gate.gate = H(d.layers);
+    gate.scale = d.layers > 0 ? scale : 1.0f;   // (fc1 has no dropout behind it, train.py:93)
+    gemm(G_NN, dZ, w + lay_.out_w.at, dA[cur], batch, mlp, NM_OUT, NM_OUT, mlp, gate, part, stream);
+    for (uint32_t i = d.layers; i >= 1; --i) {
+        gemm(G_TN, dA[cur], H(i - 1), grad + lay_.layer_w[i - 1].at, mlp, mlp, batch, mlp, mlp, raw, part, stream);
+        hipLaunchKernelGGL(nt_bias_grad, dim3((mlp + 63) / 64), dim3(NT_THREADS), 0, stream, dA[cur], grad + lay_.layer_b[i - 1].at, batch, mlp);
+        gate.gate = H(i - 1);
+        gate.scale = i - 1 > 0 ? scale : 1.0f;
+        gemm(G_NN, dA[cur], w + lay_.layer_w[i - 1].at, dA[cur ^ 1], batch, mlp, mlp, mlp, mlp, gate, part, stream);
+        cur ^= 1;
+    }
+    gemm(G_TN, dA[cur], ws(ws_feat_), grad + lay_.fc1_w.at, mlp, F, batch, mlp, F, raw, part, stream);
+    hipLaunchKernelGGL(nt_bias_grad, dim3((mlp + 63) / 64), dim3(NT_THREADS), 0, stream, dA[cur], grad + lay_.fc1_b.at, batch, mlp);
+    gemm(G_NN, dA[cur], w + lay_.fc1_w.at, ws(ws_dfeat_), batch, F, mlp, mlp, F, raw, part, stream);
+}
+
+// upload, forward, loss; when training: backward, the conv gradient; PVQ_TRAIN_STEP: Adam, the shadow refresh of a bf16 handle
 pvq_status NoteTrainer::step(int mode, const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx, uint32_t batch, float* d_loss,
                              float* d_logits, hipStream_t stream) {
     const NoteModelDims& d = lay_.d;
@@ -615,66 +625,28 @@ pvq_status NoteTrainer::step(int mode, const float* d_db, const float* d_targets
     const pvq_status up = upload_idx(idx, batch, stream);
     if (up != PVQ_OK) return up;
     const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(ws(ws_idx_));
-
     const size_t n = lay_.n_params;
-    const float* w = arena_.as<float>();
-    float* grad = arena_.as<float>() + n;
-    float* feat = ws(ws_feat_);
-    float* dfeat = ws(ws_dfeat_);
-    const size_t h_stride = round64(static_cast<size_t>(max_batch_) * d.mlp);
-    auto H = [&](uint32_t i) { return ws(ws_h_) + i * h_stride; };
-    float* dA[2] = {ws(ws_da_), ws(ws_da_) + h_stride};
-    float* Z = ws(ws_z_);
-    float* dZ = ws(ws_dz_);
-    float* part = ws(ws_part_);
+    float* arena = arena_.as<float>();
+    float* grad = arena + n;
     double* row_loss = reinterpret_cast<double*>(ws(ws_rowloss_));
-    const uint32_t F = d.n_features, mlp = d.mlp;
     const bool train = mode != PVQ_TRAIN_EVAL;
-    const bool drop = train && nt_keep_threshold(hyper_.dropout) > 0;
-    const float scale = drop ? static_cast<float>(1.0 / (1.0 - hyper_.dropout)) : 1.0f;
-    const size_t x_bytes = static_cast<size_t>(d.L) * sizeof(float);
 
     forward(d_db, batch, train, stream);
     const double inv_n = 1.0 / (static_cast<double>(batch) * NM_OUT);
-    hipLaunchKernelGGL(nt_loss, dim3(batch), dim3(NM_OUT), 0, stream, Z, d_targets, d_idx, static_cast<float>(inv_n), dZ, d_logits, row_loss);
+    hipLaunchKernelGGL(nt_loss, dim3(batch), dim3(NM_OUT), 0, stream, ws(ws_z_), d_targets, d_idx, static_cast<float>(inv_n), ws(ws_dz_), d_logits, row_loss);
     if (d_loss) hipLaunchKernelGGL(nt_loss_final, dim3(1), dim3(NT_THREADS), 0, stream, row_loss, batch, inv_n, d_loss);
-
-    if (train && precision_ == PVQ_NOTE_BF16) nth_backward(half_context(), batch, stream);
-    if (train && precision_ == PVQ_NOTE_F32) {
-        // backward: the output layer, the hidden layers from the last to the first, fc1
-        Epi raw{};
-        raw.kind = E_RAW;
-        Epi gate{};
-        gate.kind = E_GATE;
-        gemm(G_TN, dZ, H(d.layers), grad + lay_.out_w.at, NM_OUT, mlp, batch, NM_OUT, mlp, raw, part, stream);
-        hipLaunchKernelGGL(nt_bias_grad, dim3((NM_OUT + 63) / 64), dim3(NT_THREADS), 0, stream, dZ, grad + lay_.out_b.at, batch, static_cast<uint32_t>(NM_OUT));
-        int cur = 0;
-        gate.gate = H(d.layers);
-        gate.scale = d.layers > 0 ? scale : 1.0f;   // (fc1 has no dropout behind it, train.py:93)
-        gemm(G_NN, dZ, w + lay_.out_w.at, dA[cur], batch, mlp, NM_OUT, NM_OUT, mlp, gate, part, stream);
-        for (uint32_t i = d.layers; i >= 1; --i) {
-            gemm(G_TN, dA[cur], H(i - 1), grad + lay_.layer_w[i - 1].at, mlp, mlp, batch, mlp, mlp, raw, part, stream);
-            hipLaunchKernelGGL(nt_bias_grad, dim3((mlp + 63) / 64), dim3(NT_THREADS), 0, stream, dA[cur], grad + lay_.layer_b[i - 1].at, batch, mlp);
-            gate.gate = H(i - 1);
-            gate.scale = i - 1 > 0 ? scale : 1.0f;
-            gemm(G_NN, dA[cur], w + lay_.layer_w[i - 1].at, dA[cur ^ 1], batch, mlp, mlp, mlp, mlp, gate, part, stream);
-            cur ^= 1;
-        }
-        gemm(G_TN, dA[cur], feat, grad + lay_.fc1_w.at, mlp, F, batch, mlp, F, raw, part, stream);
-        hipLaunchKernelGGL(nt_bias_grad, dim3((mlp + 63) / 64), dim3(NT_THREADS), 0, stream, dA[cur], grad + lay_.fc1_b.at, batch, mlp);
-        gemm(G_NN, dA[cur], w + lay_.fc1_w.at, dfeat, batch, F, mlp, mlp, F, raw, part, stream);
-    }
     if (train) {
+        backward(batch, stream);
         // the conv from dfeat, then Adam
         float* conv_part = ws(ws_convpart_);
-        hipLaunchKernelGGL(nt_conv_grad, dim3(batch), dim3(NT_THREADS), x_bytes, stream, d_db, d_idx, w + lay_.conv_w.at, dfeat, conv_part, d.n_bins, d.t_frames,
-                           d.L, d.o_pool);
+        hipLaunchKernelGGL(nt_conv_grad, dim3(batch), dim3(NT_THREADS), static_cast<size_t>(d.L) * sizeof(float), stream, d_db, d_idx, arena + lay_.conv_w.at,
+                           ws(ws_dfeat_), conv_part, d.n_bins, d.t_frames, d.L, d.o_pool);
         hipLaunchKernelGGL(nt_conv_reduce, dim3(1), dim3(128), 0, stream, conv_part, grad + lay_.conv_w.at, batch);
         if (mode == PVQ_TRAIN_STEP) {
             const size_t n4 = n / 4;
             hipLaunchKernelGGL(nt_adam, dim3(static_cast<uint32_t>((n4 + NT_THREADS - 1) / NT_THREADS)), dim3(NT_THREADS), 0, stream,
-                               reinterpret_cast<f32x4*>(arena_.as<float>()), reinterpret_cast<const f32x4*>(grad), reinterpret_cast<f32x4*>(arena_.as<float>() + 2 * n),
-                               reinterpret_cast<f32x4*>(arena_.as<float>() + 3 * n), n4, note_trainer_adam_step(hyper_, steps_ + 1));
+                               reinterpret_cast<f32x4*>(arena), reinterpret_cast<const f32x4*>(grad), reinterpret_cast<f32x4*>(arena + 2 * n),
+                               reinterpret_cast<f32x4*>(arena + 3 * n), n4, note_trainer_adam_step(hyper_, steps_ + 1));
             ++steps_;
             if (precision_ == PVQ_NOTE_BF16) nth_refresh_shadow(half_context(), stream);
         }

@@ -15,7 +15,7 @@
 //   nt_conv_grad, nt_conv_reduce   dFeat through pool and ReLU to the 96 conv gradients: per row, then over rows, fixed order
 //   nt_adam         one launch over the arena
 // A handle created with PVQ_NOTE_BF16 runs nt_features, nt_gemm and nt_bias_grad's work in note_trainer_half.hip instead (bf16 operands,
-// f32 sums; the arenas, nt_loss, the conv gradient, nt_adam and the test pass's kernels are shared), picked by precision_ in forward and step.
+// f32 sums; the arenas, nt_loss, the conv gradient, nt_adam and the test pass's kernels are shared), picked by precision_ in forward and backward.
 // The test pass (train.py:164-198) runs the same forward without dropout over chunks of at most max_batch rows, then
 //   nt_test_rows    per row: the 128-bit masks of prediction (z > 0) and label (y > 0.5) by wave ballots, tp / fp / fn / correct by
 //                   popcount, the row's loss as nt_loss's tree in double, the logits when asked; indexed by the position in idx
@@ -68,6 +68,8 @@ class NoteTrainer {
     pvq_status upload_idx(const uint32_t* idx, uint32_t rows, hipStream_t stream);
     // train.py:87-99 on the rows the workspace's index array names: features, fc1, the hidden layers, the logits Z.  Queues only.
     void forward(const float* d_db, uint32_t batch, bool train, hipStream_t stream);
+    // backward from nt_loss's dZ: every dense gradient of the arena and dfeat.  Queues only.
+    void backward(uint32_t batch, hipStream_t stream);
     // the buffers of a bf16 step (precision_ == PVQ_NOTE_BF16)
     NthContext half_context() const;
     int device_id_ = -1;

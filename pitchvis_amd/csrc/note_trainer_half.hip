@@ -19,6 +19,8 @@
 
 #include <algorithm>
 
+#include "note_device.hpp"
+
 namespace pvq {
 
 namespace {
@@ -31,23 +33,10 @@ using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 constexpr int NTH_THREADS = 256;
 constexpr int NTH_PIECES = NTH_BK / 8;               // 16-byte pieces of an operand row per stage
 constexpr int NTH_LD = NTH_BM * NTH_PIECES / NTH_THREADS;   // pieces per thread, operand and stage
-constexpr int NTH_CONV_OUT = NM_CH * NM_KW + NM_CH;
 constexpr int NTH_MAX_JOBS = 10;                     // dense weights of a model: fc1, up to 8 hidden layers, output
 static_assert(NTH_BM == NTH_BN && NTH_BM * NTH_PIECES % NTH_THREADS == 0 && NTH_PIECES == 8, "the stage copy and the slot XOR");
 
-enum { E_RAW = 0, E_BIAS = 1, E_HIDDEN = 2, E_GATE = 3 };
-
-// note_trainer.hip's Epi; the gate is the stored 16-bit activation
-struct NthEpi {
-    int kind;
-    const float* bias;   // [N]
-    const bf16* gate;    // E_GATE: [M][ldg]
-    uint32_t ldg;
-    float scale;
-    int drop;
-    uint32_t threshold;
-    uint64_t key;
-};
+using NthEpi = NoteEpi<bf16>;   // the gate is the stored 16-bit activation [M][ldg]
 
 struct NthGemm {
     const bf16* A;   // [M][K]
@@ -62,17 +51,6 @@ struct NthGemm {
     uint32_t stages, stages_per_split, splits;
     NthEpi e;
 };
-
-__device__ __forceinline__ float epi_apply(const NthEpi& e, float v, uint32_t row, uint32_t col) {
-    if (e.kind == E_BIAS) return v + e.bias[col];
-    if (e.kind == E_HIDDEN) {
-        v = fmaxf(v + e.bias[col], 0.0f);
-        if (e.drop) v = nt_keep(e.key, row, col, e.threshold) ? v * e.scale : 0.0f;
-        return v;
-    }
-    if (e.kind == E_GATE) return static_cast<float>(e.gate[static_cast<size_t>(row) * e.ldg + col]) > 0.0f ? v * e.scale : 0.0f;
-    return v;
-}
 
 // rows r0 .. r0 + 3 (r0 a multiple of 4) of column col: the epilogue, then every copy the product keeps
 __device__ __forceinline__ void store4(const NthGemm& a, const f32x4 v, uint32_t r0, uint32_t col) {
@@ -209,11 +187,11 @@ __global__ __launch_bounds__(NTH_THREADS) void nth_gemm_finish(const NthGemm a) 
 __global__ __launch_bounds__(NTH_THREADS) void nth_features(const float* __restrict__ db, const uint32_t* __restrict__ idx, const float* __restrict__ conv,
                                                             bf16* __restrict__ feat, uint32_t n_bins, uint32_t t_frames, uint32_t L, uint32_t o_pool, uint32_t f_pad) {
     extern __shared__ float s_x[];   // the window, L floats
-    __shared__ float s_w[NTH_CONV_OUT];
+    __shared__ float s_w[NOTE_CONV_VALUES];
     const uint32_t b = blockIdx.x;
     const float* x = db + (static_cast<size_t>(idx[b]) - (t_frames - 1)) * n_bins;
     for (uint32_t i = threadIdx.x; i < L; i += NTH_THREADS) s_x[i] = x[i];
-    if (threadIdx.x < NTH_CONV_OUT) s_w[threadIdx.x] = conv[threadIdx.x];
+    if (threadIdx.x < NOTE_CONV_VALUES) s_w[threadIdx.x] = conv[threadIdx.x];
     __syncthreads();
     const uint32_t F = NM_CH * o_pool;
     bf16* dst = feat + static_cast<size_t>(b) * f_pad;
@@ -221,14 +199,8 @@ __global__ __launch_bounds__(NTH_THREADS) void nth_features(const float* __restr
         float v = 0.0f;
         if (i < F) {
             const uint32_t ch = i / o_pool, p = i - ch * o_pool;
-            const float* w5 = s_w + ch * NM_KW;
-            const float* xs = s_x + 4 * p;   // reads x[4 p .. 4 p + 6] <= x[L - 1]
-            float e = s_w[NM_CH * NM_KW + ch], o = e;
-#pragma unroll
-            for (int j = 0; j < NM_KW; ++j) {
-                e = fmaf(w5[j], xs[j], e);
-                o = fmaf(w5[j], xs[2 + j], o);
-            }
+            float e, o;
+            conv_pair(s_w + ch * NM_KW, s_w[NM_CH * NM_KW + ch], s_x + 4 * p, e, o);   // reads x[4 p .. 4 p + 6] <= x[L - 1]
             v = fmaxf(fmaxf(e, o), 0.0f);
         }
         dst[i] = static_cast<bf16>(v);

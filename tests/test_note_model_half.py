@@ -235,9 +235,11 @@ def test_pack_b16_puts_every_element_where_its_lane_reads_it(name, precision, ha
         assert int((got != 0).sum()) == n * k                  # every element of W exactly once (fill16 is never zero)
 
 
-def _ws(tool, shape_name, limit, stride, *n_frames):
+def _ws(tool, shape_name, limit, stride, *n_frames, precision=None):
+    """the 16-bit layout ("ws"), or that of the precision named ("wsp")"""
     n_bins, T, mlp, layers, _ = R.shape(shape_name)
-    lines = note_plan_tool.run(tool, "ws", n_bins, T, mlp, layers, limit, stride, *n_frames).splitlines()
+    cmd = ("ws",) if precision is None else ("wsp", PREC[precision])
+    lines = note_plan_tool.run(tool, *cmd, n_bins, T, mlp, layers, limit, stride, *n_frames).splitlines()
     head = lines[0].split()
     return dict(zip(head[0::2], map(int, head[1::2]))), [tuple(map(int, x.split())) for x in lines[1:]]
 
@@ -261,6 +263,34 @@ def test_workspace_cut_of_three_tiles_in_one_stream(half_tool):
         assert (w["tiles"], w["kf_pad"], w["mlp_pad"], w["tile"]) == (4, kf, mp, 256 * (kf + 2 * mp)) and chunks == [(0, 4)]
     hdr = re.sub(r"\s*\n \*\s*", " ", open(os.path.join(ROOT, "include", "pvq.h")).read())
     assert "256 * (pad32(n_features) + 2 * pad32(mlp_size)) bytes" in hdr
+
+
+def test_f32_workspace_cut_of_three_tiles_in_one_stream(half_tool):
+    """the same call for an f32 handle: shape I (mlp 112), one stream of T + 256 frames, tiles of 128, 128 and 1 rows.  A tile is two
+    hidden buffers of 128 rows x 112 floats = 114 688 bytes; the table takes 256 bytes; the 16-bit path's fields stay zero."""
+    T = R.shape("I")[1]
+    tile = 2 * 128 * 112 * 4
+    assert tile == 114688
+    for limit, cut in ((0, [(0, 1), (1, 1), (2, 1)]), (256 + tile, [(0, 1), (1, 1), (2, 1)]), (256 + 2 * tile - 1, [(0, 1), (1, 1), (2, 1)]),
+                       (256 + 2 * tile, [(0, 2), (2, 1)]), (256 + 3 * tile, [(0, 3)]), (256 << 20, [(0, 3)])):
+        w, chunks = _ws(half_tool, "I", limit, T + 260, T + 256, precision="f32")
+        ct = cut[0][1]
+        assert chunks == cut, (limit, chunks)
+        assert (w["tiles"], w["tab"], w["tile"], w["chunk_tiles"]) == (3, 256, tile, ct)
+        assert w["total"] == 256 + ct * tile
+        assert (w["h0_at"], w["h1_at"]) == (256, 256 + ct * tile // 2)      # the two buffers, back to back behind the table
+        assert (w["feat_at"], w["kf_pad"], w["mlp_pad"]) == (0, 0, 0)
+
+
+def test_workspace_grid_cap(half_tool):
+    """shape K (mlp 4096: 64 column tiles; 32 features -> pad32 32, two pooled positions: one block per row, 128 per tile), 40 000 000
+    tiles under no limit: a chunk is what a launch's grid of 2^31 - 1 blocks takes.  Planning only."""
+    n_bins, T, mlp, layers, _ = R.shape("K")
+    cap = {name: int(note_plan_tool.run(half_tool, "cap", PREC[name], n_bins, T, mlp, layers, 40_000_000)) for name in PREC}
+    print(cap)
+    assert cap["f32"] == 0x7fffffff // 64 == 33_554_431
+    assert cap["bf16"] == 0x7fffffff // 128 == 16_777_215
+    assert cap["f16"] == cap["bf16"]
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")

@@ -181,6 +181,31 @@ def test_f32_handle_of_the_new_entry_equals_the_old_entry():
     assert a["d_logits"].cpu().numpy().any()
 
 
+def test_handles_of_three_precisions_share_no_state():
+    """shape I, one stream of T + 130 frames (two tiles): an f32, a bf16 and an f16 handle called in turn, twice, give each the bits of
+    its own first call, and those of a handle of its precision that no other call came between"""
+    n_bins, T, mlp, layers, _ = R.shape("I")
+    par, w = P.NoteModelParams(n_bins, T, mlp, layers), R.weights("I")
+    stride = T + 130
+    d_db = torch.from_numpy(R.db_like((1, stride, n_bins), seed=77)).cuda()
+    keys = ("d_prob", "d_logits", "d_mask")
+
+    def call(m):
+        o = m.rows_device(d_db, [stride], stride)
+        torch.cuda.synchronize()
+        return [o[k].cpu().numpy().view(np.uint32) for k in keys]
+
+    alone = {p: call(P.NoteModel(par, w, device=0, precision=p)) for p in ("f32", "bf16", "f16")}
+    models = {p: P.NoteModel(par, w, device=0, precision=p) for p in alone}
+    rounds = [{p: call(m) for p, m in models.items()} for _ in range(2)]
+    for p in alone:
+        assert alone[p][1].any()
+        for k, first, second, single in zip(keys, rounds[0][p], rounds[1][p], alone[p]):
+            assert np.array_equal(second, first), (p, k)
+            assert np.array_equal(first, single), (p, k)
+    assert not np.array_equal(alone["f32"][1], alone["bf16"][1]) and not np.array_equal(alone["bf16"][1], alone["f16"][1])
+
+
 @pytest.mark.parametrize("precision", PRECISIONS)
 @pytest.mark.parametrize("name", ["G", "J"])
 def test_host_infer_predicts_the_device_rows(name, precision):
