@@ -77,7 +77,9 @@ struct BlockDftTables {
     } tile_lists[8];   // eight slots: a batch's first, middle and last sub-batch alternate without rebuilding; a general hop takes two lists per launch shape
     int tile_list_next = 0;
     unsigned long long* d_clk = nullptr; size_t clk_cap = 0; int clk_n = 0;   // K-loop clock samples of the last profiled launch: 4 slots per sampled tile
-    float4* d_E16 = nullptr;       // E in the B-operand order of the 16x16x4 GEMM: [column tile][k < hop / 2][n < 16]
+    float4* d_E16 = nullptr;       // E in the B-operand order of the 16x16x4 GEMM: [column tile][k < hop / 2][n < 16]; behind the n_tiles column tiles
+                                   // the merged slices of the mixed tiles, one per pair of `mixed`
+    std::vector<MixedPair> mixed;  // the pairs of groups whose last column tiles share a mixed tile (blockdft_plan.hpp)
     bool general = false;          // the hop does not divide the windows: blockdft_gemm_gen (whole hop blocks + the window's remainder)
     float4* d_E16R = nullptr;      // general hops: per group and column tile [k < rem / 2][n < 16]
     float2* d_gen_tw = nullptr;    // general hops: per group phi, tau (n_tiles * 32 columns each)

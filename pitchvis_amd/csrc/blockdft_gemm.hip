@@ -160,10 +160,17 @@ __device__ __forceinline__ float2 tree_cmadd(float2 lo, float2 w, float2 hi) {
 // reads them plus the 2^R - 1 rows above once; every A_{l+1}[j] = A_l[j] + w_l A_l[j + 2^l] is evaluated exactly as
 // the level-by-level form would, without a pass through LDS per level.  Rows past the tile read as zero: they only
 // feed outputs that are themselves incomplete.
-template <int R, int BM>
-__device__ __forceinline__ void fused_tree_register_levels(float2 (*A)[CB_C + 1], const float2 (*tw)[CB_C], int tid) {
+// MIXED (a mixed tile: columns [0, n1) of one window group, the rest of another with its own twiddle table tw2 and r2 <= R register
+// levels): a column of the second part takes the levels l < r2 and keeps its values past them — by select, never by a zero twiddle
+// (0 * Inf must not appear where the group's own tree has none).
+template <int R, int BM, bool MIXED = false>
+__device__ __forceinline__ void fused_tree_register_levels(float2 (*A)[CB_C + 1], const float2 (*tw)[CB_C], int tid, int n1 = 0, int r2 = 0,
+                                                           const float2 (*tw2)[CB_C] = nullptr) {
     constexpr int H = (1 << R) - 1;
     const int c = tid & (CB_C - 1), j0 = (tid >> 5) * 16;
+    const bool p2 = MIXED && c >= n1;
+    const float2* twc = p2 ? &tw2[0][c - n1] : &tw[0][c];   // level l: + l * CB_C
+    const int rc = p2 ? r2 : R;
     float2 v[16 + H];
 #pragma unroll
     for (int i = 0; i < 16 + H; ++i) v[i] = A[j0 + i][c];   // rows BM .. BM + 14 are spare rows of the tile (zeroed by the caller)
@@ -171,11 +178,15 @@ __device__ __forceinline__ void fused_tree_register_levels(float2 (*A)[CB_C + 1]
 #pragma unroll
     for (int l = 0; l < R; ++l) {
         const int st = 1 << l;
-        const float2 w = tw[l][c];
+        const float2 w = MIXED ? twc[l * CB_C] : tw[l][c];
+        const bool on = !MIXED || l < rc;
         len -= st;
 #pragma unroll
         for (int i = 0; i < 16 + H; ++i)
-            if (i < len) v[i] = tree_cmadd(v[i], w, v[i + st]);
+            if (i < len) {
+                const float2 t = tree_cmadd(v[i], w, v[i + st]);
+                v[i] = on ? t : v[i];
+            }
     }
     __syncthreads();   // every thread has read its halo
 #pragma unroll
@@ -271,9 +282,31 @@ __device__ __forceinline__ int fused_tree_levels(float* smem, const float2 (*tw)
 // rows j, j + 16 (, j + 32, j + 48) of the register levels' output in its own column, so no value has to change threads — no
 // write-back, no barrier and no second read.  The same calls in the same order as a level-by-level pass (two levels: exactly as two
 // radix-2 levels), the twiddles wave-uniform.  j < S = BM - nb_f + 1 keeps every read inside the tile's BM rows.
+// (the column loop: row j of the tile's columns col0 .. col0 + ncv - 1 to dst, dst[cc * 64] taking column col0 + cc; tw: the twiddles of those columns)
+template <int BM>
+__device__ __forceinline__ void fused_store_cols(float* smem, const float2 (*tw)[CB_C], float2* dst, int col0, int ncv, int j, int tid, int tail) {
+    float2 (*A)[FT_LDP] = reinterpret_cast<float2 (*)[FT_LDP]>(smem);  // [BM][33]
+    // streamed out (non-temporal): the kernel-product stage that reads X back runs 5 % faster for it
+    auto put = [&](int cc, float2 val) { __builtin_nontemporal_store((f32x2){val.x, val.y}, reinterpret_cast<f32x2*>(&dst[cc * 64])); };   // one 8-byte store
+    constexpr int st = 1 << FT_REGL;
+    if (tail == 2) {   // wave-uniform
+#pragma unroll 4
+        for (int cc = tid / BM; cc < ncv; cc += 2) {
+            const float2 w1 = tw[FT_REGL][cc], w2 = tw[FT_REGL + 1][cc];
+            const float2 t0 = tree_cmadd(A[j][col0 + cc], w1, A[j + st][col0 + cc]);
+            const float2 t1 = tree_cmadd(A[j + 2 * st][col0 + cc], w1, A[j + 3 * st][col0 + cc]);
+            put(cc, tree_cmadd(t0, w2, t1));
+        }
+    } else if (tail == 1) {
+#pragma unroll 4
+        for (int cc = tid / BM; cc < ncv; cc += 2) put(cc, tree_cmadd(A[j][col0 + cc], tw[FT_REGL][cc], A[j + st][col0 + cc]));
+    } else {
+#pragma unroll 4
+        for (int cc = tid / BM; cc < ncv; cc += 2) put(cc, A[j][col0 + cc]);
+    }
+}
 template <int BM = FT_BM>
 __device__ __forceinline__ void fused_store_x(float* smem, const float2 (*tw)[CB_C], const FusedTile& t, const GemmTreeArgs& a, int tid, int tail) {
-    float2 (*A)[FT_LDP] = reinterpret_cast<float2 (*)[FT_LDP]>(smem);  // [BM][33]
     const int j = tid % BM;
     const int f = t.f0 + j;
     if (j < t.S && f < t.nfr) {
@@ -281,30 +314,47 @@ __device__ __forceinline__ void fused_store_x(float* smem, const float2 (*tw)[CB
         const bool to_y = t.G.nb > t.G.nb_f;
         float2* dst = (to_y ? a.Y : a.X) + ((size_t)((f >> 6) + (to_y ? t.yt0 : t.xt0)) * a.xcp + t.nt * CB_C) * 64 + (f & 63);
         const int ncv = t.G.n_cols - t.ntl * CB_C < CB_C ? t.G.n_cols - t.ntl * CB_C : CB_C;   // the tile's real columns: the padding of a group's last tile is never read with a non-zero coefficient and never written (X starts out zeroed)
-        // streamed out (non-temporal): the kernel-product stage that reads X back runs 5 % faster for it
-        auto put = [&](int cc, float2 val) { __builtin_nontemporal_store((f32x2){val.x, val.y}, reinterpret_cast<f32x2*>(&dst[cc * 64])); };   // one 8-byte store
-        constexpr int st = 1 << FT_REGL;
-        if (tail == 2) {   // wave-uniform
-#pragma unroll 4
-            for (int cc = tid / BM; cc < ncv; cc += 2) {
-                const float2 w1 = tw[FT_REGL][cc], w2 = tw[FT_REGL + 1][cc];
-                const float2 t0 = tree_cmadd(A[j][cc], w1, A[j + st][cc]);
-                const float2 t1 = tree_cmadd(A[j + 2 * st][cc], w1, A[j + 3 * st][cc]);
-                put(cc, tree_cmadd(t0, w2, t1));
-            }
-        } else if (tail == 1) {
-#pragma unroll 4
-            for (int cc = tid / BM; cc < ncv; cc += 2) put(cc, tree_cmadd(A[j][cc], tw[FT_REGL][cc], A[j + st][cc]));
-        } else {
-#pragma unroll 4
-            for (int cc = tid / BM; cc < ncv; cc += 2) put(cc, A[j][cc]);
-        }
+        fused_store_cols<BM>(smem, tw, dst, 0, ncv, j, tid, tail);
     }
 }
 template <int BM = FT_BM>
 __device__ __forceinline__ void fused_tree_store(float* smem, const float2 (*tw)[CB_C], const FusedTile& t, const GemmTreeArgs& a, int tid, int stamp_slot) {
     const int tail = fused_tree_levels<BM>(smem, tw, t, a, tid, stamp_slot);
     fused_store_x<BM>(smem, tw, t, a, tid, tail);
+    if (a.stamps) {
+        __builtin_amdgcn_s_waitcnt(0);   // stores issued and acknowledged
+        __syncthreads();
+        PVQ_STAMP(3);
+    }
+}
+
+// A MIXED tile's epilogue (blockdft_plan.hpp: MixedPair): columns [0, n1) of the P tile are the last column tile of t's group, columns
+// [n1, n1 + n2) the last column tile of a second group t2 of fewer hop blocks, whose frame t2.f0 + j sits in row j; tw[0] / tw[1] hold
+// the two parts' twiddles.  Each column runs its own group's levels — the same tree_cmadd calls as in a tile of its own — and each part
+// goes to the X columns it always had.  The rows advance by t's stride, so the second part stores rows j < t.S too, those of its frames
+// that exist (its first frame index is negative where its windows begin later than t's at a stream's start).
+template <int BM>
+__device__ __forceinline__ void fused_tree_store_mixed(float* smem, const float2 (*tw)[FT_MAXL][CB_C], const FusedTile& t, const FusedTile& t2, int n1, int n2,
+                                                       const GemmTreeArgs& a, int tid, int stamp_slot) {
+    float2 (*A)[FT_LDP] = reinterpret_cast<float2 (*)[FT_LDP]>(smem);  // [BM][33]
+    const int l1 = t.G.levels_f < FT_REGL ? t.G.levels_f : FT_REGL, l2 = t2.G.levels_f < FT_REGL ? t2.G.levels_f : FT_REGL;   // l2 <= l1
+    switch (l1) {   // wave-uniform
+        case 1: fused_tree_register_levels<1, BM, true>(A, tw[0], tid, n1, l2, tw[1]); break;
+        case 2: fused_tree_register_levels<2, BM, true>(A, tw[0], tid, n1, l2, tw[1]); break;
+        case 3: fused_tree_register_levels<3, BM, true>(A, tw[0], tid, n1, l2, tw[1]); break;
+        case 4: fused_tree_register_levels<4, BM, true>(A, tw[0], tid, n1, l2, tw[1]); break;
+        default: break;
+    }
+    PVQ_STAMP(6);
+    PVQ_STAMP(2);
+    const int j = tid % BM;
+    if (j < t.S) {
+        const int f1 = t.f0 + j, f2 = t2.f0 + j;
+        if (f1 < t.nfr)
+            fused_store_cols<BM>(smem, tw[0], a.X + ((size_t)((f1 >> 6) + t.xt0) * a.xcp + t.nt * CB_C) * 64 + (f1 & 63), 0, n1, j, tid, t.G.levels_f - l1);
+        if (f2 >= 0 && f2 < t2.nfr)
+            fused_store_cols<BM>(smem, tw[1], a.X + ((size_t)((f2 >> 6) + t2.xt0) * a.xcp + t2.nt * CB_C) * 64 + (f2 & 63), n1, n2, j, tid, t2.G.levels_f - l2);
+    }
     if (a.stamps) {
         __builtin_amdgcn_s_waitcnt(0);   // stores issued and acknowledged
         __syncthreads();
@@ -410,7 +460,8 @@ template <int BM, bool HALF>   // tiles that lie wholly inside the stream (all b
 // depth: samples of a row the DFT runs over (the hop; the general-hop kernel's second GEMM runs over the first `rem` samples of rows that
 // still lie a.K = hop samples apart)
 __device__ __forceinline__ void fused_f32_kloop16(const GemmTreeArgs& a, const float* pcm_base, unsigned pcm_bytes, float* smem, long long tile_lo, const float4* e_tile, int tid,
-                                                  f32x4a (&accR)[2][2], f32x4a (&accI)[2][2], const float* tw_src, float* tw_dst, int tw_levels, int tw_stride, int stamp_slot, int depth) {
+                                                  f32x4a (&accR)[2][2], f32x4a (&accI)[2][2], const float* tw_src, float* tw_dst, int tw_levels, int tw_stride, int stamp_slot, int depth,
+                                                  const float* tw_src2 = nullptr, int tw_levels2 = 0, int tw_stride2 = 0) {   // (a mixed tile: its second part's twiddles, into the second table)
     constexpr int THREADS = 2 * BM;
     const int lane = tid & 63, wave = tid >> 6, m16 = lane & 15, kq = lane >> 4;
     const unsigned long long pcm_addr = reinterpret_cast<unsigned long long>(pcm_base);
@@ -500,6 +551,8 @@ __device__ __forceinline__ void fused_f32_kloop16(const GemmTreeArgs& a, const f
     stage_e(0, K2 < FR_KC ? K2 : FR_KC);
     for (int l = wave; l < tw_levels; l += THREADS / 64)   // the tile's combine twiddles: one level (32 complex = 64 floats) per wave instruction
         lds_dma4(tw_src + (size_t)l * tw_stride, tw_dst + l * (2 * CB_C));
+    for (int l = wave; l < tw_levels2; l += THREADS / 64)
+        lds_dma4(tw_src2 + (size_t)l * tw_stride2, tw_dst + (FT_MAXL + l) * (2 * CB_C));
     load_dgroup(0, 0);
     // (one wait for everything the prologue fetched.  Waiting only for the DMA pieces — s_waitcnt vmcnt(8) + a raw s_barrier — lets a
     // wave start on its own first operands, but hipcc does not credit a hand-written wait: with an LDS-DMA "possibly in flight" it
@@ -710,15 +763,31 @@ __device__ __forceinline__ void fused_dump_p(float* smem, const f32x4a (&accR)[2
 }
 
 // one 32-column tile from the K loop to the store
+// mixed_x: the entry's .x if it is a MIXED one (the host emits them for tiles inside the stream only), else 0; n_frames: the frames of the tile's segment
 template <int BM>
-__device__ __forceinline__ void fused_f32_narrow_tile(const GemmTreeArgs& a, const float* pcm_base, unsigned pcm_bytes, float* smem, float2 (*tw_lds)[CB_C], const FusedTile& T, bool inside,
-                                                      long long tile_lo, int tid, int stamp_slot) {
+__device__ __forceinline__ void fused_f32_narrow_tile(const GemmTreeArgs& a, const float* pcm_base, unsigned pcm_bytes, float* smem, float2 (*tw_lds)[FT_MAXL][CB_C], const FusedTile& T, bool inside,
+                                                      long long tile_lo, int tid, int stamp_slot, int mixed_x, int n_frames) {
     const int lane = tid & 63;
     // the tile's combine twiddles (levels x 32 complex columns = 64 floats per level): a wave copies a level, a dword per lane
     const float* tw_src = reinterpret_cast<const float*>(a.comb_tw + T.G.tw_off + T.ntl * CB_C) + lane;   // level l: + l * tw_stride floats
-    float* tw_dst = reinterpret_cast<float*>(&tw_lds[0][0]);
+    float* tw_dst = reinterpret_cast<float*>(&tw_lds[0][0][0]);
     const int tw_levels = T.G.levels_f, tw_stride = 2 * T.G.n_tiles * CB_C;
-    const float4* e_tile = a.E16 + (size_t)T.nt * (a.K / 2) * 16;
+    const bool mixed = mixed_x != 0;   // workgroup-uniform
+    const float4* e_tile = a.E16 + (size_t)(mixed ? a.ld / FT_BN + ((mixed_x >> TILE_MIXED_PAIR_SHIFT) & 7) : T.nt) * (a.K / 2) * 16;   // (a pair's merged slice: behind the regular column tiles)
+    // a mixed tile's second part: the last column tile of group g2, frame T.f0 + j + d in row j (K is a power of two on this path)
+    FusedTile T2 = T;
+    int n1 = 0, n2 = 0;
+    if (mixed) {
+        T2.G = a.gv[(mixed_x >> TILE_MIXED_G2_SHIFT) & 7];
+        T2.ntl = T2.G.n_tiles - 1;
+        T2.nt = T2.G.tile0 + T2.ntl;
+        T2.f0 = T.f0 + (int)((T.G.s_rel - T2.G.s_rel) >> __builtin_ctz(a.K));
+        T2.nfr = n_frames;
+        n1 = T.G.n_cols - T.ntl * CB_C;
+        n2 = T2.G.n_cols - T2.ntl * CB_C;
+    }
+    const float* tw_src2 = reinterpret_cast<const float*>(a.comb_tw + T2.G.tw_off + T2.ntl * CB_C) + lane;
+    const int tw_levels2 = mixed ? T2.G.levels_f : 0, tw_stride2 = 2 * T2.G.n_tiles * CB_C;
     f32x4a accR[2][2], accI[2][2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
@@ -736,13 +805,14 @@ __device__ __forceinline__ void fused_f32_narrow_tile(const GemmTreeArgs& a, con
         a.clk[(blockIdx.x >> 6) * 4 + 1] = __builtin_amdgcn_s_memrealtime();
     }
     // a group's last column tile may hold 16 columns or fewer (3 of the 21 tiles at 48 kHz / 252 bins): half the MFMAs
-    const bool half = T.ntl == T.G.n_tiles - 1 && T.G.n_cols - T.ntl * CB_C <= 16;
-    if (!inside)
+    // (a mixed tile: both parts together)
+    const bool half = mixed ? n1 + n2 <= 16 : T.ntl == T.G.n_tiles - 1 && T.G.n_cols - T.ntl * CB_C <= 16;
+    if (__builtin_expect(!inside, 0))   // (a handful of tiles per launch)
         fused_f32_kloop16_edge<BM>(a, pcm_base, pcm_bytes, smem, tile_lo, e_tile, tid, accR, accI, tw_src, tw_dst, tw_levels, tw_stride, stamp_slot, a.K);
     else if (half)
-        fused_f32_kloop16<BM, true>(a, pcm_base, pcm_bytes, smem, tile_lo, e_tile, tid, accR, accI, tw_src, tw_dst, tw_levels, tw_stride, stamp_slot, a.K);
+        fused_f32_kloop16<BM, true>(a, pcm_base, pcm_bytes, smem, tile_lo, e_tile, tid, accR, accI, tw_src, tw_dst, tw_levels, tw_stride, stamp_slot, a.K, tw_src2, tw_levels2, tw_stride2);
     else
-        fused_f32_kloop16<BM, false>(a, pcm_base, pcm_bytes, smem, tile_lo, e_tile, tid, accR, accI, tw_src, tw_dst, tw_levels, tw_stride, stamp_slot, a.K);
+        fused_f32_kloop16<BM, false>(a, pcm_base, pcm_bytes, smem, tile_lo, e_tile, tid, accR, accI, tw_src, tw_dst, tw_levels, tw_stride, stamp_slot, a.K, tw_src2, tw_levels2, tw_stride2);
     if (a.clk != nullptr && (blockIdx.x & 63) == 0 && tid == 0) {
         a.clk[(blockIdx.x >> 6) * 4 + 2] = __builtin_amdgcn_s_memtime();
         a.clk[(blockIdx.x >> 6) * 4 + 3] = __builtin_amdgcn_s_memrealtime();
@@ -753,7 +823,10 @@ __device__ __forceinline__ void fused_f32_narrow_tile(const GemmTreeArgs& a, con
     fused_dump_p<BM, 2, 0>(smem, accR, accI, tid);
     __syncthreads();
     PVQ_STAMP(5);
-    fused_tree_store<BM>(smem, tw_lds, T, a, tid, stamp_slot);
+    if (mixed)
+        fused_tree_store_mixed<BM>(smem, tw_lds, T, T2, n1, n2, a, tid, stamp_slot);
+    else
+        fused_tree_store<BM>(smem, tw_lds[0], T, a, tid, stamp_slot);
 }
 
 
@@ -828,7 +901,7 @@ __global__ __launch_bounds__(2 * BM, 4) void blockdft_gemm_tree(GemmTreeArgs a) 
         return;
     }
     // (the host pairs only tiles that lie inside the stream — same test, same numbers, launch(): the range-checked loop takes one tile)
-    fused_f32_narrow_tile<BM>(a, ts.pcm_base, ts.pcm_bytes, smem, tw_lds[0], T, inside, tile_lo, tid, stamp_slot);
+    fused_f32_narrow_tile<BM>(a, ts.pcm_base, ts.pcm_bytes, smem, tw_lds, T, inside, tile_lo, tid, stamp_slot, WIDE && inside && (entry.x & TILE_MIXED) ? entry.x : 0, ts.n_frames);
     PVQ_END_STAMPS
 }
 
@@ -1255,10 +1328,11 @@ __global__ __launch_bounds__(256) void blockdft_combine(CombineArgs a) {
 static pvq_status get_tile_list(BlockDftTables* t, const BlockLaunch& L, int kind, int bm, int wide_mode, const TileListOptions& opt,
                                 hipStream_t stream, BlockDftTables::TileList** out) {
     const LaunchShape& sh = *L.shape;
+    const int list_mode = wide_mode | (opt.mixed.empty() ? 0 : 4);   // (a list with mixed entries is a list of its own)
     std::vector<SegKey> key = sh.segs;
     if (!L.multi) key[0].pcm_off = key[0].out_row0 = key[0].fbeg = 0;
     for (auto& c : t->tile_lists)
-        if (c.bm == bm && c.wide == wide_mode && c.multi == L.multi && c.kind == kind && c.key == key && c.slot_data == sh.slot_data) {
+        if (c.bm == bm && c.wide == list_mode && c.multi == L.multi && c.kind == kind && c.key == key && c.slot_data == sh.slot_data) {
             *out = &c;
             return PVQ_OK;
         }
@@ -1281,7 +1355,7 @@ static pvq_status get_tile_list(BlockDftTables* t, const BlockLaunch& L, int kin
     tl->key = key;
     tl->slot_data = sh.slot_data;
     tl->bm = bm;
-    tl->wide = wide_mode;
+    tl->wide = list_mode;
     tl->multi = L.multi;
     tl->kind = kind;
     tl->blocks = (int)h.list.size();
@@ -1320,15 +1394,20 @@ pvq_status Vqt::launch_blockdft_gemm_fused(BlockLaunch& L, hipStream_t stream) {
     }();
     static const int wide_env = dev_knob("PVQ_WIDE", 1);         // 0: narrow tiles only; 2: wide tiles to the very end of every queue
     const int wide_mode = !use_bf && fused_bm == 256 && !t->general ? wide_env : 0;   // (the split-bf16 kernel, the 128-row form and the general-hop kernel take 32-column tiles only)
+    // mixed tiles (two window groups' partial last column tiles in one tile: blockdft_plan.hpp, MixedPair): the fp32 256-row kernel only.
+    // Developer library: PVQ_MIXED_TILES=0 takes the former list (A/B, bit identity), and so does the former epilogue (PVQ_TREE_TAIL=0).
+    static const bool mixed_env = dev_knob("PVQ_MIXED_TILES", 1) != 0 && dev_knob("PVQ_TREE_TAIL", 1) != 0;
+    TileListOptions lopt = opt;
+    if (mixed_env && !use_bf && fused_bm == 256 && !t->general) lopt.mixed = t->mixed;
     BlockDftTables::TileList* tl = nullptr;
     BlockDftTables::TileList* tl_r = nullptr;   // general hops: the remainder tiles
     pvq_status ls;
     if (t->general) {
-        if ((ls = get_tile_list(t, L, 1, fused_bm, wide_mode, opt, stream, &tl_r)) != PVQ_OK) return ls;
-        if ((ls = get_tile_list(t, L, 2, fused_bm, wide_mode, opt, stream, &tl)) != PVQ_OK) return ls;
+        if ((ls = get_tile_list(t, L, 1, fused_bm, wide_mode, lopt, stream, &tl_r)) != PVQ_OK) return ls;
+        if ((ls = get_tile_list(t, L, 2, fused_bm, wide_mode, lopt, stream, &tl)) != PVQ_OK) return ls;
         // (the second lookup may have evicted the first — the slots are handed out round robin — look it up again)
-        if ((ls = get_tile_list(t, L, 1, fused_bm, wide_mode, opt, stream, &tl_r)) != PVQ_OK) return ls;
-    } else if ((ls = get_tile_list(t, L, 0, fused_bm, wide_mode, opt, stream, &tl)) != PVQ_OK)
+        if ((ls = get_tile_list(t, L, 1, fused_bm, wide_mode, lopt, stream, &tl_r)) != PVQ_OK) return ls;
+    } else if ((ls = get_tile_list(t, L, 0, fused_bm, wide_mode, lopt, stream, &tl)) != PVQ_OK)
         return ls;
     L.d_xmap = L.multi ? tl->d_xmap : nullptr;
     const int n_wg = tl->blocks;   // list entries = workgroups of the non-persistent forms = rows of the stamp dump

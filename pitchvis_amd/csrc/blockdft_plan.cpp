@@ -179,6 +179,37 @@ void deal_blocks(size_t n_blocks, int waves, int per_wave, int* rows) {
 
 }  // namespace
 
+std::vector<MixedPair> plan_mixed_pairs(const std::vector<BlockGroup>& groups, size_t hop, bool general) {
+    std::vector<MixedPair> pairs;
+    if (general || groups.size() > 8) return pairs;   // (a tile list entry names a group in 3 bits: the fused path's limit)
+    // a group's last tile is a candidate if it is partial and a single entry of the tile list whatever the wide mode: at most 16
+    // columns (never paired up), or the odd tile of its group
+    auto last_cols = [](const BlockGroup& G) { return G.n_cols - (G.n_tiles - 1) * CB_C; };
+    auto candidate = [&](const BlockGroup& G) {
+        const int n = last_cols(G);
+        return G.n_tiles > 0 && G.nb == G.nb_f && n < CB_C && (n <= 16 || G.n_tiles % 2 == 1);
+    };
+    struct Cand { int a, b, dist, nb; };
+    std::vector<Cand> cands;
+    for (size_t i = 0; i < groups.size(); ++i)
+        for (size_t k = i + 1; k < groups.size(); ++k) {
+            const BlockGroup &A = groups[i], &B = groups[k];
+            if (!candidate(A) || !candidate(B) || last_cols(A) + last_cols(B) > CB_C) continue;
+            if ((A.s_rel - B.s_rel) % (long long)hop != 0) continue;
+            cands.push_back(Cand{(int)i, (int)k, std::abs(A.levels - B.levels), std::max(A.nb, B.nb)});
+        }
+    std::stable_sort(cands.begin(), cands.end(), [](const Cand& x, const Cand& y) { return x.dist != y.dist ? x.dist < y.dist : x.nb > y.nb; });
+    std::vector<char> used(groups.size(), 0);
+    for (const Cand& c : cands) {
+        if (used[c.a] || used[c.b] || (int)pairs.size() == MIXED_MAX_PAIRS) continue;
+        used[c.a] = used[c.b] = 1;
+        const bool a_first = groups[c.a].nb >= groups[c.b].nb;
+        const int g1 = a_first ? c.a : c.b, g2 = a_first ? c.b : c.a;
+        pairs.push_back(MixedPair{g1, g2, last_cols(groups[g1]), last_cols(groups[g2]), (int)((groups[g1].s_rel - groups[g2].s_rel) / (long long)hop)});
+    }
+    return pairs;
+}
+
 bool build_blockdft_tables(const HostPlan& plan, size_t hop, bool twiddle_fp16, BlockDftHostTables& t, std::string* err) {
     t = BlockDftHostTables();
     const auto& groups = plan.kernel.window_groups;
@@ -351,6 +382,23 @@ bool build_blockdft_tables(const HostPlan& plan, size_t hop, bool twiddle_fp16, 
                     t.E16[((size_t)tt * K2 + m) * 16 + n] = Float4{e[2 * n], e[2 * (n + 16)], e[2 * n + 1], e[2 * (n + 16) + 1]};
                 }
     }
+    {   // mixed tiles: per pair one merged slice, g1's last column tile and then g2's, columns taken from E as E16 takes them
+        const size_t K2 = hop / 2;
+        t.mixed = plan_mixed_pairs(t.groups, hop, t.general);
+        t.E16M.assign(t.mixed.size() * K2 * 16, Float4{0.0f, 0.0f, 0.0f, 0.0f});
+        for (size_t p = 0; p < t.mixed.size(); ++p) {
+            const MixedPair& mp = t.mixed[p];
+            for (int c = 0; c < mp.n1 + mp.n2; ++c) {
+                const BlockGroup& B = t.groups[c < mp.n1 ? mp.g1 : mp.g2];
+                const size_t col = ((size_t)(B.tile0 + B.n_tiles - 1) * CB_C + (c < mp.n1 ? c : c - mp.n1)) * 2;   // float index of the column's cosine in a row of E
+                for (size_t m = 0; m < K2; ++m) {
+                    Float4& dst = t.E16M[(p * K2 + m) * 16 + (c & 15)];
+                    const float er = t.E[m * ntot + col], ei = t.E[m * ntot + col + 1];
+                    if (c < 16) { dst.x = er; dst.z = ei; } else { dst.y = er; dst.w = ei; }
+                }
+            }
+        }
+    }
     t.E16R.assign((size_t)std::max(e16r_off, 1), Float4{0.0f, 0.0f, 0.0f, 0.0f});
     t.gen_tw.assign((size_t)std::max(gtw_off, 1), Float2{1.0f, 0.0f});
     if (t.general) {
@@ -487,16 +535,26 @@ void build_segment_map(const BdStream* st, const std::vector<BdRun>& runs, const
 // ------------------------------------------------------------------------------------------------
 // tile lists of the fused kernels
 // ------------------------------------------------------------------------------------------------
-double fused_tile_count(const std::vector<BlockGroup>& groups, const std::vector<SegKey>& segs, int bm, bool split_bf16) {
+double fused_tile_count(const std::vector<BlockGroup>& groups, const std::vector<SegKey>& segs, int bm, bool split_bf16,
+                        const std::vector<MixedPair>* mixed) {
     double n = 0.0;
     for (const SegKey& k : segs)
-        for (const BlockGroup& G : groups) {
+        for (size_t g = 0; g < groups.size(); ++g) {
+            const BlockGroup& G = groups[g];
             const int S = bm - G.nb_f + 1;
             const int rows_g = k.nf + G.nb - G.nb_f;
             // a last tile of at most 16 columns runs half the MFMAs (fp32 kernel; the few tiles at the stream's ends run the full
             // loop: counted as half all the same)
             const bool half_last = !split_bf16 && G.n_cols - (G.n_tiles - 1) * CB_C <= 16;
-            n += (G.n_tiles - (half_last ? 0.5 : 0.0)) * ((rows_g + S - 1) / S);
+            double last = half_last ? 0.5 : 1.0;
+            // mixed tiles: g1's last tile carries g2's (a whole tile, or half of one up to 16 columns together); g2's last tile issues
+            // nothing of its own (its few cover entries at the streams' ends are not counted)
+            if (mixed && !split_bf16)
+                for (const MixedPair& mp : *mixed) {
+                    if (mp.g1 == (int)g) last = mp.n1 + mp.n2 <= 16 ? 0.5 : 1.0;
+                    if (mp.g2 == (int)g) last = 0.0;
+                }
+            n += (G.n_tiles - 1 + last) * ((rows_g + S - 1) / S);
         }
     return n;
 }
@@ -528,10 +586,20 @@ HostTileList build_tile_list(const std::vector<BlockGroup>& groups, const std::v
     auto is_wide = [](const Int4& e) { return ((e.x >> 8) & 1) != 0; };
     auto seg_of = [](const Int4& e) { return (int)((unsigned)e.x >> 16); };
     auto inside = [&](const Int4& e) { return tile_inside_stream(groups[grp(e)], segs[seg_of(e)], e.z, hop, bm, kind); };
-    auto half_tile = [&](const Int4& e) {   // a group's last tile of at most 16 columns: half the K loop
+    auto is_mixed = [](const Int4& e) { return (e.x & TILE_MIXED) != 0; };
+    auto pair_of = [&](const Int4& e) -> const MixedPair& { return opt.mixed[(e.x >> TILE_MIXED_PAIR_SHIFT) & 7]; };
+    auto half_tile = [&](const Int4& e) {   // a group's last tile of at most 16 columns (a mixed tile: both parts together): half the K loop
+        if (is_mixed(e)) return pair_of(e).n1 + pair_of(e).n2 <= 16;
         const BlockGroup& G = groups[grp(e)];
         return e.y == G.n_tiles - 1 && G.n_cols - e.y * CB_C <= 16;
     };
+    // mixed tiles (kind 0): the pair a group is the first / the second member of
+    std::vector<int> as_g1(groups.size(), -1), as_g2(groups.size(), -1);
+    if (kind == 0)
+        for (size_t p = 0; p < opt.mixed.size(); ++p) {
+            as_g1[opt.mixed[p].g1] = (int)p;
+            as_g2[opt.mixed[p].g2] = (int)p;
+        }
     std::vector<std::vector<Int4>> q(8);
     for (size_t u = 0; u < segs.size(); ++u)
         for (size_t g = 0; g < groups.size(); ++g) {
@@ -540,8 +608,41 @@ HostTileList build_tile_list(const std::vector<BlockGroup>& groups, const std::v
             const int S = kind == 0 ? bm - G.nb_f + 1 : kind == 1 ? bm : bm - (G.nq > 1 ? G.nq - 1 : 0);
             const int rows_g = kind == 0 ? segs[u].nf + G.nb - G.nb_f : segs[u].nf;
             const bool half_last = G.n_cols - (G.n_tiles - 1) * CB_C <= 16;
+            auto stripe_of = [&](int f0) { return (segs[u].x_tile0 * 64 + f0) / opt.fs; };   // position in the launch's frame order
+            if (as_g2[g] >= 0) {
+                // The second member of a pair: its last column tile rides in g1's mixed entries, which lie on g1's row grid and exist
+                // where g1's tile is inside the stream.  Row j < S1 of the mixed tile at f1 is this group's frame f1 + j + d; the frames
+                // those leave uncovered (next to g1's range-checked edge tiles, before the offset at the segment's start, the last
+                // frames) get ordinary entries of the last tile at the first uncovered frame (S frames each: they may overlap what a
+                // mixed entry or another cover entry stores — the same bits).
+                const MixedPair& mp = opt.mixed[as_g2[g]];
+                const BlockGroup& G1 = groups[mp.g1];
+                const int S1 = bm - G1.nb_f + 1, nf = segs[u].nf;
+                auto cover = [&](int from, int to) {   // ordinary entries over the frames [from, to)
+                    for (int f = from; f < to; f += S) {
+                        const int s = stripe_of(f);
+                        q[s & 7].push_back(Int4{(int)g | (int)((unsigned)u << 16), G.n_tiles - 1, f, s});
+                    }
+                };
+                int done = 0;   // frames [0, done) are stored
+                for (int f1 = 0; f1 < nf; f1 += S1) {
+                    if (!tile_inside_stream(G1, segs[u], f1, hop, bm, kind)) continue;
+                    const int lo = std::max(f1 + mp.d, 0), hi = std::min(f1 + mp.d + S1, nf);
+                    if (lo >= hi) continue;
+                    if (done < lo) cover(done, lo);
+                    done = std::max(done, hi);
+                }
+                if (done < nf) cover(done, nf);
+            }
             for (int f0 = 0; f0 < rows_g; f0 += S)
                 for (int ntl = 0; ntl < G.n_tiles; ++ntl) {
+                    if (ntl == G.n_tiles - 1 && as_g2[g] >= 0) continue;   // (above)
+                    if (ntl == G.n_tiles - 1 && as_g1[g] >= 0 && tile_inside_stream(G, segs[u], f0, hop, bm, kind)) {
+                        const MixedPair& mp = opt.mixed[as_g1[g]];
+                        const int s = stripe_of(f0);
+                        q[s & 7].push_back(Int4{(int)g | TILE_MIXED | (mp.g2 << TILE_MIXED_G2_SHIFT) | (as_g1[g] << TILE_MIXED_PAIR_SHIFT) | (int)((unsigned)u << 16), ntl, f0, s});
+                        continue;
+                    }
                     // two neighbouring column tiles as one WIDE entry (.x bit 8; fp32 kernel, 256-row tiles)
                     // (a last tile of at most 16 columns keeps its own entry and its half-depth loop: pairing it up too was measured
                     // at the same time for more MFMAs)

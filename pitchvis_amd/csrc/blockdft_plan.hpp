@@ -101,6 +101,19 @@ struct SegKey {
     }
 };
 
+// Two window groups whose partial last column tiles share one MIXED tile of the fp32 fused kernel: one 32-column tile whose columns
+// [0, n1) are the last column tile of g1 and whose columns [n1, n1 + n2) are the last column tile of g2 — one K loop over the PCM
+// rows both groups read, one epilogue, instead of a workgroup life each.  A pair forms only where both groups run the fused
+// power-of-two path without Y partial sums (nb == nb_f), their windows begin a whole number of hops apart and n1 + n2 <= 32.
+struct MixedPair {
+    int g1, g2;   // g1: the group of more hop blocks, on whose row grid (stride 257 - nb_1) the mixed tile lives
+    int n1, n2;   // columns the two last tiles hold
+    int d;        // (s_rel_1 - s_rel_2) / hop: row j of a mixed tile at f0 is frame f0 + j of g1 and frame f0 + j + d of g2
+};
+constexpr int MIXED_MAX_PAIRS = 4;        // (the fused path takes at most 8 window groups)
+constexpr int TILE_MIXED = 1 << 9;        // tile list entry .x: bit 9 a mixed entry, bits 10..12 its second group, bits 13..15 the pair
+constexpr int TILE_MIXED_G2_SHIFT = 10, TILE_MIXED_PAIR_SHIFT = 13;
+
 // ---- tables ----------------------------------------------------------------------------------------------------------------------
 bool blockdft_plan_applicable(const HostPlan& plan, size_t hop);   // whether the path's kernels take this geometry at this hop
 
@@ -113,6 +126,9 @@ struct BlockDftHostTables {
     std::vector<float> E;          // [hop][Ntot], (cos, sin) interleaved per column
     std::vector<Float4> E16;       // E in the B-operand order of the 16x16x4 GEMM: [column tile][k < hop / 2][n < 16]
     std::vector<Float4> E16R;      // general hops: per group and column tile [k < rem / 2][n < 16]
+    std::vector<MixedPair> mixed;  // the pairs of groups whose last column tiles may share a mixed tile (plan_mixed_pairs)
+    std::vector<Float4> E16M;      // per pair one merged slice in the format of E16: its columns [0, n1) g1's last tile, [n1, n1 + n2) g2's, zeros
+                                   // behind them; on the device it follows the regular column tiles of E16 (pair m is column tile n_tiles + m)
     std::vector<Float2> comb_tw;   // tree twiddles: per group [level][n_tiles * 32]
     std::vector<Float2> gen_tw;    // general hops: per group phi, tau (n_tiles * 32 columns each)
     std::vector<int> tile_group;   // [n_tiles]
@@ -138,6 +154,9 @@ struct BlockDftHostTables {
 };
 // false (with the text in *err): the geometry has too many spectrum columns for the path
 bool build_blockdft_tables(const HostPlan& plan, size_t hop, bool twiddle_fp16, BlockDftHostTables& out, std::string* err);
+// Which groups pair up (MixedPair), greedily among the partial last tiles that stay single entries of the tile list (at most 16 columns,
+// or the odd tile of a group), nearest block counts first and of those the longer windows first; nothing for a general hop
+std::vector<MixedPair> plan_mixed_pairs(const std::vector<BlockGroup>& groups, size_t hop, bool general);
 // hi / mid / lo bf16 planes of E^T, [3][Ntot][hop] (the split-bf16 GEMM's operand)
 std::vector<uint16_t> build_Et_bf16x3(const std::vector<float>& E, int ntot, size_t hop);
 
@@ -170,9 +189,10 @@ struct TileListOptions {
     int fs = 2048;       // frames per stripe
     int balance = 1;     // 0: queues as the stripes fall
     int tail = 128;      // narrow entries at the end of every queue (wide_mode 1)
+    std::vector<MixedPair> mixed;   // the pairs whose last tiles share mixed entries (kind 0, 256-row fp32 kernel only); empty: none
 };
 struct HostTileList {
-    std::vector<Int4> list;    // (group | wide << 8 | segment << 16, column tile, first frame, position); length a multiple of 8
+    std::vector<Int4> list;    // (group | wide << 8 | mixed bits 9..15 | segment << 16, column tile, first frame, position); length a multiple of 8
     double eff_tiles = 0.0;    // MFMA work of the list in whole 32-column tiles
     double eff_flop = 0.0;     // ... in flop (general hops: the depth differs by tile kind and group)
 };
@@ -180,7 +200,9 @@ struct HostTileList {
 bool tile_inside_stream(const BlockGroup& G, const SegKey& seg, int f0, size_t hop, int bm, int kind);
 HostTileList build_tile_list(const std::vector<BlockGroup>& groups, const std::vector<SegKey>& segs, size_t hop, int bm, int wide_mode, int kind,
                              const TileListOptions& opt);
-// matrix work of a launch of the fused GEMM + tree kernels in whole-tile units, for tiles of bm rows
-double fused_tile_count(const std::vector<BlockGroup>& groups, const std::vector<SegKey>& segs, int bm, bool split_bf16);
+// matrix work of a launch of the fused GEMM + tree kernels in whole-tile units, for tiles of bm rows (mixed: the pairs whose last
+// tiles share mixed entries — g2's last tile then issues nothing of its own, g1's a whole tile, or half of one up to 16 columns)
+double fused_tile_count(const std::vector<BlockGroup>& groups, const std::vector<SegKey>& segs, int bm, bool split_bf16,
+                        const std::vector<MixedPair>* mixed = nullptr);
 
 }  // namespace pvq

@@ -121,6 +121,8 @@ pvq_status Vqt::prepare_blockdft(size_t hop) {
     t->band_per_wave8 = h.band_per_wave8;
     t->band_stage_stride8 = h.band_stage_stride8;
     std::copy(h.band_stage_count8, h.band_stage_count8 + 8, t->band_stage_count8);
+    h.E16.insert(h.E16.end(), h.E16M.begin(), h.E16M.end());   // the mixed tiles' merged slices: column tiles n_tiles ... of the device's E16
+    t->mixed = h.mixed;
     const bool ok = up(&t->d_E16R, h.E16R) && up(&t->d_gen_tw, h.gen_tw) && up(&t->d_E, h.E) && up(&t->d_tile_group, h.tile_group) && up(&t->d_tile_s, h.tile_s) &&
                     up(&t->d_groups, h.groups) && up(&t->d_comb_tw, h.comb_tw) && up(&t->d_band, h.band) && up(&t->d_band_B, h.band_B) && up(&t->d_band_list, h.band_list) &&
                     up(&t->d_band8, h.band8) && up(&t->d_band_B4, h.band_B4) && up(&t->d_band_list8, h.band_list8) && up(&t->d_band_stages8, h.band_stages8) && up(&t->d_band_B3, h.band_B3) && up(&t->d_E16, h.E16);

@@ -2,6 +2,7 @@
 usage: dev_ab_knob.py KNOB v1,v2,... [rounds] [iters]
 knobs with two code forms kept in the developer library for this:
   PVQ_TREE_TAIL 1,0    fused GEMM epilogue: the tile's last tree levels evaluated by the store (1) / as an LDS pass before it (0)
+  PVQ_MIXED_TILES 1,0  fused GEMM tile list: two window groups' partial last column tiles in one mixed tile (1) / the former list (0)
   PVQ_DOTS_BLOCKS 0,1  kernel product: one stage stream per wave (0) / the block loop (1)
   PVQ_DEV_LIB 1,<name> two code versions: lib/libpvq_dev.so against lib/libpvq_<name>.so (pitchvis_amd/_lib.py)"""
 import os, subprocess, sys, statistics
