@@ -563,8 +563,15 @@ pvq_status pvq_render_batch_rows_device(pvq_render_batch *r, size_t n_rows, cons
  *     c = center / bpo * 12; nothing is lit if round(c) * 6 >= n_segments; otherwise segments [0, (round(c) * 6) as usize) are lit, all
  *     in one colour: calculate_color at (round(c) * bpo / 12 + (bpo - 3 (bpo / 12))) % bpo with alpha 1 - (1 - size / max_size)^2 — a
  *     Color, not converted to linear.  The visible state is (lit count, rgba); rgba keeps its last value while nothing is lit.
- * Left out: the `ml` branch (update.rs:247-255; it reads an AnalysisState field that no longer exists), params.time (the caller's
- * clock).  The debug meshes (update_spectrum, the calmness histogram and graph) are the panels stage below.
+ *  6. The `ml` branch (update.rs:247-255, display_system/util.rs:23-31), only through the pvq_ml_ entry points below with a non-NULL
+ *     probability row (AnalysisState::ml_midi_base_pitches [128], what pvq_note_model_outputs.d_prob holds).  For a ball the frame
+ *     keys (idx = trunc(center) < n_bins, the later list entry winning as in step 3): m = (uint) round((idx as f32 / bpo as f32) *
+ *     12.0) + 33, the division and the product each rounded to f32, round half away from zero, 33 = FREQ_A1_MIDI_KEY_ID.  m <= 127:
+ *     alpha = prob[m] > 0.35 ? 1.0 : color_coefficient * 0.1 (one f32 product; a NaN probability takes the dim side).  m > 127 (the
+ *     reference's None): alpha stays color_coefficient.  Nothing else changes: the bass spiral's alpha, scale, z, the hide pass and
+ *     the fade are as above — so the fade's max(alpha * dropoff, 0.7) lifts a dim ball to 0.7 on its next frame, as in the viewer.
+ *     A row of zeros reads as "nothing inferred", like the reference's initial vec![0.0; 128].
+ * Left out: params.time (the caller's clock).  The debug meshes (update_spectrum, the calmness histogram and graph) are the panels stage below.
  * Every libm call of steps 3 and 5 is the double-precision function rounded once to f32, on the host and on the device (DESIGN.md
  * 6c); the fade's powf is the host's, also for the device stage. */
 typedef enum pvq_visuals_mode { PVQ_VISUALS_FULL = 0, PVQ_VISUALS_ZEN = 1, PVQ_VISUALS_PERFORMANCE = 2, PVQ_VISUALS_GALAXY = 3 } pvq_visuals_mode;
@@ -590,6 +597,14 @@ uint32_t pvq_scene_state_n_segments(const pvq_scene_state *s);   /* min(octaves 
 pvq_status pvq_scene_state_update(pvq_scene_state *s, const float *center, const float *size, uint32_t n_peaks,
                                   const float *calmness, const float *pitch_accuracy, const float *pitch_deviation,
                                   float scene_calmness, uint64_t frame_time_ns);
+/* The same frame with step 6: ml_prob [128] (HOST), the frame's ml_midi_base_pitches.  ml_prob NULL: pvq_scene_state_update, bit
+ * for bit. */
+pvq_status pvq_ml_scene_state_update(pvq_scene_state *s, const float *center, const float *size, uint32_t n_peaks,
+                                     const float *calmness, const float *pitch_accuracy, const float *pitch_deviation,
+                                     float scene_calmness, uint64_t frame_time_ns, const float *ml_prob);
+/* step 6's pitch of a bin (util.rs:23-31 bin_to_midi_pitch): PVQ_OK and *out_pitch <= 127, or *out_pitch = UINT32_MAX for None.
+ * PVQ_ERR_INVALID_ARG for buckets_per_octave 0 or a NULL out_pitch. */
+pvq_status pvq_ml_midi_pitch(uint32_t buckets_per_octave, uint32_t bin, uint32_t *out_pitch);
 /* the scene as it stands; any pointer may be NULL.  ball_xyzs [n_bins][4]: x, y, z, scale; ball_rgba [n_bins][4] (linear r, g, b and
  * alpha); ball_params [n_bins][3]: calmness, pitch_accuracy, pitch_deviation; ball_visible [ceil(n_bins / 32)]: bit bin % 32 of word
  * bin / 32 (the bit order of peak_mask); bass_lit: the number of lit segments; bass_rgba [4]; bloom: Bloom::intensity */
@@ -633,6 +648,14 @@ uint32_t pvq_scene_batch_n_segments(const pvq_scene_batch *b);
  * call's, or that brings per-frame times, first waits for `stream` (the fade table, built with the host's libm, is replaced). */
 pvq_status pvq_scene_batch_frames_device(pvq_scene_batch *b, size_t n_frames, const pvq_scene_inputs *in, uint64_t frame_time_ns,
                                          const uint64_t *frame_times_ns, const pvq_scene_outputs *outs, void *stream);
+/* The same frames with step 6.  d_ml_prob (DEVICE) is [n_streams][ml_stride_frames][128]: row (s, f) reads
+ * d_ml_prob[(s * ml_stride_frames + f) * 128 + m], so the d_prob buffer pvq_note_model_rows_device or
+ * pvq_note_model_rows_carry_device wrote is taken where it lies, whatever its stride_frames.  ml_stride_frames < n_frames is
+ * PVQ_ERR_INVALID_ARG; rows f >= n_frames are never read.  d_ml_prob NULL: pvq_scene_batch_frames_device, bit for bit (the stride is
+ * not looked at).  Alpha carries the bits of pvq_ml_scene_state_update. */
+pvq_status pvq_ml_scene_batch_frames_device(pvq_scene_batch *b, size_t n_frames, const pvq_scene_inputs *in,
+                                            const float *d_ml_prob, size_t ml_stride_frames, uint64_t frame_time_ns,
+                                            const uint64_t *frame_times_ns, const pvq_scene_outputs *outs, void *stream);
 /* the state of one stream after the last call (synchronises), laid out as pvq_scene_state_get */
 pvq_status pvq_scene_batch_get_state(pvq_scene_batch *b, uint32_t stream_index, float *ball_xyzs, float *ball_rgba,
                                      float *ball_params, uint32_t *ball_visible, uint32_t *bass_lit, float *bass_rgba, float *bloom);
@@ -1375,6 +1398,43 @@ pvq_status pvq_note_model_infer(const pvq_note_model *m, const float *window_hos
  * its d_prob and d_logits must be 16-byte aligned (PVQ_ERR_INVALID_ARG otherwise). */
 pvq_status pvq_note_model_rows_device(pvq_note_model *m, const float *d_db, const size_t *n_frames, uint32_t n_streams,
                                       size_t stride_frames, const pvq_note_model_outputs *outs, void *stream);
+/* Windows that continue from call to call: what a caller needs who feeds frames as they arrive (one frame per call is the
+ * viewer's cadence, ml_system.rs:50-69), where pvq_note_model_rows_device starts afresh at every call and gives rows
+ * f < t_frames - 1 as zeros.  A carry keeps, per stream, the last t_frames - 1 frames it was given (on the device) and
+ * seen[s], the number of frames stream s has been given since create or reset — a HOST counter, as n_frames is a host array.
+ * It belongs to the model's n_bins, t_frames and device, and to n_streams streams (n_streams 0: PVQ_ERR_INVALID_ARG); a
+ * host-only model gives a host-only carry.
+ *
+ * pvq_note_model_rows_carry_device: d_db, n_frames, stride_frames and outs as for pvq_note_model_rows_device, but n_frames[s]
+ * (NULL: stride_frames each) counts the NEW frames of stream s, which continue its sequence.  Row (s, f), f < n_frames[s], is the
+ * model on the last t_frames frames of the stream's whole sequence ending at that frame, and is a model row exactly when
+ * seen[s] + f >= t_frames - 1; every other row of every output is written as zeros.  Afterwards the carry holds the stream's last
+ * min(t_frames - 1, seen + n) frames and seen += n: a call with n_frames[s] < t_frames - 1 merges old and new frames, one with
+ * n_frames[s] == 0 leaves the stream alone.  d_db rows f >= n_frames[s] are never read.  t_frames == 1: nothing is carried, the
+ * rows are still packed.
+ * The model rows of ALL streams are packed into tiles of 128 (a tile is 128 consecutive rows of the call's row list, whatever
+ * streams they come from): a call of R model rows launches ceil(R / 128) tiles' worth of workgroups per layer, where
+ * pvq_note_model_rows_device spends a tile per stream.  A row's logits, probability and mask carry the bits
+ * pvq_note_model_rows_device gives the same window, at every precision.
+ * Asynchronous on `stream`, with no host synchronisation and no device-to-host copy (the per-stream descriptors of a call go out
+ * from pinned host memory, one of 8 slots in turn: only a host that has queued 8 calls the device has not begun waits, for the
+ * oldest one's descriptor copy); no allocation on the call path once the
+ * carry's row table and the model's workspace have grown (the table is 16 bytes a model row and outside the workspace limit,
+ * which cuts the call into chunks of whole tiles with the same bits).  Every frame the call or a later one needs is copied inside
+ * the call, so d_db may be overwritten in stream order right after it.  One carry, like one model, serves one stream at a time.
+ * All argument checks of pvq_note_model_rows_device apply, the 16-byte alignment of a 16-bit handle's outputs included; a carry
+ * made for another n_streams, for a model of other n_bins or t_frames, or on another device is PVQ_ERR_INVALID_ARG; 2^31 model
+ * rows or more in one call too.  On host-only handles the call returns PVQ_ERR_NO_DEVICE after these checks.
+ * pvq_note_carry_reset: stream_index < 0: every stream; else that stream (>= n_streams: PVQ_ERR_INVALID_ARG).  seen returns to 0
+ * at once, the kept frames are cleared in stream order. */
+struct pvq_note_carry;   /* opaque; named by its tag: the set of handle typedefs of this header stays as it was */
+pvq_status pvq_note_carry_create(const pvq_note_model *m, uint32_t n_streams, struct pvq_note_carry **out);
+void pvq_note_carry_destroy(struct pvq_note_carry *c);
+pvq_status pvq_note_carry_reset(struct pvq_note_carry *c, int64_t stream_index, void *stream);
+pvq_status pvq_note_carry_frames_seen(const struct pvq_note_carry *c, uint32_t stream_index, uint64_t *out);
+pvq_status pvq_note_model_rows_carry_device(pvq_note_model *m, struct pvq_note_carry *c, const float *d_db, const size_t *n_frames,
+                                            uint32_t n_streams, size_t stride_frames, const pvq_note_model_outputs *outs,
+                                            void *stream);
 /* Upper bound in bytes for that workspace (default 256 MiB): a call processes its rows in chunks of whole 128-row tiles that fit;
  * results do not depend on the chunking.  One tile (1 KiB * mlp_size + its table entry) is the least a call works with.  A
  * PVQ_NOTE_BF16 / PVQ_NOTE_F16 handle keeps, per tile, the 128 rounded feature rows and two hidden rows each, every row padded

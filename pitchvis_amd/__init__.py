@@ -647,5 +647,5 @@ from .text import TextBatch, TextFont, TextLabel, pitch_name_labels, text_frame,
 from .readout import ReadoutBatch, readout_frame, readout_layout, readout_text  # noqa: E402,F401
 from .present import PresentBatch, present_blend_factors, present_frame, present_mips, present_settings  # noqa: E402,F401
 from .panels import CalmnessGraph, PanelsBatch, calmness_histogram_mesh, panel_topology, spectrum_mesh  # noqa: E402,F401
-from .note_model import NoteModel, NoteModelParams, note_round  # noqa: E402,F401
+from .note_model import NoteCarry, NoteModel, NoteModelParams, note_round  # noqa: E402,F401
 from .note_trainer import NoteTestResult, NoteTrainer, NoteTrainerHyper, dropout_keep, epoch, random_split, note_test_metrics  # noqa: E402,F401

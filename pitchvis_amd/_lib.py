@@ -39,6 +39,7 @@ EXPORTS = [
     "pvq_scene_default_settings", "pvq_scene_state_create", "pvq_scene_state_destroy", "pvq_scene_state_n_bins", "pvq_scene_state_n_segments",
     "pvq_scene_state_update", "pvq_scene_state_get", "pvq_scene_batch_create", "pvq_scene_batch_destroy", "pvq_scene_batch_n_segments",
     "pvq_scene_batch_frames_device", "pvq_scene_batch_get_state",
+    "pvq_ml_scene_state_update", "pvq_ml_midi_pitch", "pvq_ml_scene_batch_frames_device",
     "pvq_spectrum_mesh", "pvq_calmness_histogram_mesh", "pvq_calmness_graph_create", "pvq_calmness_graph_destroy", "pvq_calmness_graph_capacity",
     "pvq_calmness_graph_push", "pvq_calmness_graph_mesh", "pvq_panel_topology", "pvq_panels_batch_create", "pvq_panels_batch_destroy",
     "pvq_panels_batch_graph_capacity", "pvq_panels_batch_rows_device", "pvq_panels_batch_graph_device", "pvq_panels_batch_get_history",
@@ -64,6 +65,7 @@ EXPORTS = [
     "pvq_synth_effects_process", "pvq_synth_chorus_table",
     "pvq_note_model_create", "pvq_note_model_destroy", "pvq_note_model_sizes", "pvq_note_model_infer", "pvq_note_model_rows_device",
     "pvq_note_model_set_workspace_limit", "pvq_note_model_create_precision", "pvq_note_model_precision", "pvq_note_round",
+    "pvq_note_carry_create", "pvq_note_carry_destroy", "pvq_note_carry_reset", "pvq_note_carry_frames_seen", "pvq_note_model_rows_carry_device",
     "pvq_note_trainer_hyper_default", "pvq_note_trainer_create", "pvq_note_trainer_destroy", "pvq_note_trainer_step", "pvq_note_trainer_steps",
     "pvq_note_trainer_param_count", "pvq_note_trainer_read", "pvq_note_trainer_dropout_keep", "pvq_note_trainer_test", "pvq_note_test_metrics",
     "pvq_note_trainer_create_precision", "pvq_note_trainer_precision",
@@ -392,6 +394,12 @@ def load():
     L.pvq_scene_batch_frames_device.argtypes = [vp, C.c_size_t, C.POINTER(CSceneInputs), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(CSceneOutputs), vp]
     L.pvq_scene_batch_frames_device.restype = C.c_int
     L.pvq_scene_batch_get_state.argtypes = [vp, C.c_uint32, fp, fp, fp, up, up, fp, fp]; L.pvq_scene_batch_get_state.restype = C.c_int
+    if not _dev or _dev == "1" or hasattr(L, "pvq_ml_midi_pitch"):   # (as for pvq_msaa_frame below)
+        L.pvq_ml_scene_state_update.argtypes = [vp, fp, fp, C.c_uint32, fp, fp, fp, C.c_float, C.c_uint64, fp]; L.pvq_ml_scene_state_update.restype = C.c_int
+        L.pvq_ml_midi_pitch.argtypes = [C.c_uint32, C.c_uint32, up]; L.pvq_ml_midi_pitch.restype = C.c_int
+        L.pvq_ml_scene_batch_frames_device.argtypes = [vp, C.c_size_t, C.POINTER(CSceneInputs), vp, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint64),
+                                                       C.POINTER(CSceneOutputs), vp]
+        L.pvq_ml_scene_batch_frames_device.restype = C.c_int
     L.pvq_spectrum_mesh.argtypes = [C.c_uint32, C.c_uint16, fp, fp, fp, C.c_uint32, fp, C.c_float, fp, fp, fp, fp]; L.pvq_spectrum_mesh.restype = C.c_int
     L.pvq_calmness_histogram_mesh.argtypes = [C.c_uint32, fp, fp, fp]; L.pvq_calmness_histogram_mesh.restype = C.c_int
     L.pvq_calmness_graph_create.argtypes = [C.c_uint32, C.POINTER(vp)]; L.pvq_calmness_graph_create.restype = C.c_int
@@ -515,6 +523,13 @@ def load():
     L.pvq_note_model_rows_device.argtypes = [vp, vp, szp, C.c_uint32, C.c_size_t, C.POINTER(CNoteModelOutputs), vp]
     L.pvq_note_model_rows_device.restype = C.c_int
     L.pvq_note_model_set_workspace_limit.argtypes = [vp, C.c_uint64]; L.pvq_note_model_set_workspace_limit.restype = C.c_int
+    if not _dev or _dev == "1" or hasattr(L, "pvq_note_carry_create"):   # (a library of older sources kept for an A/B may predate them)
+        L.pvq_note_carry_create.argtypes = [vp, C.c_uint32, C.POINTER(vp)]; L.pvq_note_carry_create.restype = C.c_int
+        L.pvq_note_carry_destroy.argtypes = [vp]; L.pvq_note_carry_destroy.restype = None
+        L.pvq_note_carry_reset.argtypes = [vp, C.c_int64, vp]; L.pvq_note_carry_reset.restype = C.c_int
+        L.pvq_note_carry_frames_seen.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint64)]; L.pvq_note_carry_frames_seen.restype = C.c_int
+        L.pvq_note_model_rows_carry_device.argtypes = [vp, vp, vp, szp, C.c_uint32, C.c_size_t, C.POINTER(CNoteModelOutputs), vp]
+        L.pvq_note_model_rows_carry_device.restype = C.c_int
     L.pvq_note_model_create_precision.argtypes = [C.c_int, C.POINTER(CNoteModelParams), C.POINTER(CNoteModelWeights), C.c_int, C.POINTER(vp)]
     L.pvq_note_model_create_precision.restype = C.c_int
     L.pvq_note_model_precision.argtypes = [vp, C.POINTER(C.c_int)]; L.pvq_note_model_precision.restype = C.c_int

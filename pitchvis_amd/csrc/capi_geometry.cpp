@@ -95,6 +95,27 @@ pvq_status pvq_scene_state_update(pvq_scene_state* s, const float* center, const
         return PVQ_OK;
     });
 }
+// the same frame with the `ml` branch (update.rs:247-255); ml_prob null: the call above
+pvq_status pvq_ml_scene_state_update(pvq_scene_state* s, const float* center, const float* size, uint32_t n_peaks, const float* calmness,
+                                     const float* pitch_accuracy, const float* pitch_deviation, float scene_calmness, uint64_t frame_time_ns,
+                                     const float* ml_prob) {
+    return guarded([&] {
+        if (!s) return null_handle();
+        if (n_peaks && (!center || !size || !calmness || !pitch_accuracy || !pitch_deviation))
+            return invalid_arg("scene: a frame with peaks needs center, size, calmness, pitch_accuracy and pitch_deviation");
+        s->impl->update(center, size, n_peaks, calmness, pitch_accuracy, pitch_deviation, scene_calmness, frame_time_ns, ml_prob);
+        return PVQ_OK;
+    });
+}
+// display_system/util.rs:23-31
+pvq_status pvq_ml_midi_pitch(uint32_t buckets_per_octave, uint32_t bin, uint32_t* out_pitch) {
+    return guarded([&] {
+        if (!out_pitch || buckets_per_octave == 0) return invalid_arg("scene: midi pitch needs buckets_per_octave > 0 and an output");
+        const uint32_t m = pvq::scene::midi_pitch(buckets_per_octave, bin);
+        *out_pitch = m < pvq::scene::MIDI_PITCHES ? m : UINT32_MAX;
+        return PVQ_OK;
+    });
+}
 pvq_status pvq_scene_state_get(const pvq_scene_state* s, float* ball_xyzs, float* ball_rgba, float* ball_params, uint32_t* ball_visible,
                                uint32_t* bass_lit, float* bass_rgba, float* bloom) {
     return guarded([&] {
@@ -134,6 +155,18 @@ pvq_status pvq_scene_batch_frames_device(pvq_scene_batch* b, size_t n_frames, co
         const pvq_scene_outputs none{};
         return b->impl->frames_device(n_frames, in ? *in : no_in, frame_time_ns, frame_times_ns, outs ? *outs : none,
                                       static_cast<hipStream_t>(stream));
+    });
+}
+// the same frames with the `ml` branch: row (s, f) reads d_ml_prob[(s * ml_stride_frames + f) * 128 + pitch]; null: the call above
+pvq_status pvq_ml_scene_batch_frames_device(pvq_scene_batch* b, size_t n_frames, const pvq_scene_inputs* in, const float* d_ml_prob,
+                                            size_t ml_stride_frames, uint64_t frame_time_ns, const uint64_t* frame_times_ns,
+                                            const pvq_scene_outputs* outs, void* stream) {
+    return guarded([&] {
+        if (!b) return null_handle();
+        const pvq_scene_inputs no_in{};
+        const pvq_scene_outputs none{};
+        return b->impl->frames_device(n_frames, in ? *in : no_in, frame_time_ns, frame_times_ns, outs ? *outs : none,
+                                      static_cast<hipStream_t>(stream), d_ml_prob, ml_stride_frames);
     });
 }
 pvq_status pvq_scene_batch_get_state(pvq_scene_batch* b, uint32_t stream_index, float* ball_xyzs, float* ball_rgba, float* ball_params,

@@ -2,6 +2,7 @@
 #include <string>
 
 #include "capi_support.hpp"
+#include "note_carry.hpp"
 #include "note_model.hpp"
 #include "note_trainer.hpp"
 
@@ -63,6 +64,36 @@ pvq_status pvq_note_model_rows_device(pvq_note_model* m, const float* d_db, cons
         if (!m) return null_handle();
         const pvq_note_model_outputs none{};
         return m->impl->rows_device(d_db, n_frames, n_streams, stride_frames, outs ? *outs : none, static_cast<hipStream_t>(stream));
+    });
+}
+// windows that continue across calls, rows of many streams in one tile (note_carry.hpp); ml_system.rs:50-69 feeds a frame per call
+pvq_status pvq_note_carry_create(const pvq_note_model* m, uint32_t n_streams, pvq_note_carry** out) {
+    return guarded([&] {
+        return make_handle(out, [&](auto& impl) {
+            if (!m) return null_handle();
+            return pvq::NoteCarry::create(m->impl->dims(), m->impl->device(), n_streams, impl);
+        });
+    });
+}
+void pvq_note_carry_destroy(pvq_note_carry* c) { destroy(c); }
+pvq_status pvq_note_carry_reset(pvq_note_carry* c, int64_t stream_index, void* stream) {
+    return guarded([&] {
+        if (!c) return null_handle();
+        return c->impl->reset(stream_index, static_cast<hipStream_t>(stream));
+    });
+}
+pvq_status pvq_note_carry_frames_seen(const pvq_note_carry* c, uint32_t stream_index, uint64_t* out) {
+    return guarded([&] {
+        if (!c) return null_handle();
+        return c->impl->frames_seen(stream_index, out);
+    });
+}
+pvq_status pvq_note_model_rows_carry_device(pvq_note_model* m, pvq_note_carry* c, const float* d_db, const size_t* n_frames, uint32_t n_streams,
+                                            size_t stride_frames, const pvq_note_model_outputs* outs, void* stream) {
+    return guarded([&] {
+        if (!m || !c) return null_handle();
+        const pvq_note_model_outputs none{};
+        return m->impl->rows_carry_device(*c->impl, d_db, n_frames, n_streams, stride_frames, outs ? *outs : none, static_cast<hipStream_t>(stream));
     });
 }
 pvq_status pvq_note_model_set_workspace_limit(pvq_note_model* m, uint64_t bytes) {

@@ -37,6 +37,7 @@ class SynthEffects;
 class PresentBatch;
 class PanelsBatch;
 class NoteModel;
+class NoteCarry;
 class NoteTrainer;
 }  // namespace pvq
 
@@ -111,6 +112,9 @@ struct pvq_panels_batch {
 };
 struct pvq_note_model {
     std::unique_ptr<pvq::NoteModel> impl;
+};
+struct pvq_note_carry {
+    std::unique_ptr<pvq::NoteCarry> impl;
 };
 struct pvq_note_trainer {
     std::unique_ptr<pvq::NoteTrainer> impl;

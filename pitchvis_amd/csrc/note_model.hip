@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <string>
 
+#include "note_carry.hpp"
 #include "note_device.hpp"
 #include "note_model_half.hpp"
 #include "vqt_engine.hpp"
@@ -37,6 +38,8 @@ static_assert(sizeof(NmTile) == 16, "NmTile is read as laid out in note_model_pl
 
 struct NmArgs {
     const NmTile* tiles;     // this launch's tiles
+    const NmRow* rows;       // null: a tile is n_valid frames of one stream from f0.  Else the launch's row table, entry 128 * tile_local + r:
+                             //   row r's window and output row (note_carry.hip; the tile's stream and f0 are unread)
     const float* db;         // nm_conv_fc1: [n_streams][stride_frames][n_bins]
     const float* conv;       // nm_conv_fc1: conv weights [16][5], bias [16]
     const float* a_in;       // nm_dense: [tiles * 128][k]
@@ -120,7 +123,8 @@ __device__ __forceinline__ void epilogue(const NmArgs& a, const NmTile tile, uin
                     bal[s] = __ballot(logit[s] > 0.0f);   // bits 16 g' .. 16 g' + 15: row 4 g' + reg, the strip's 16 columns
                 }
                 if (r < tile.n_valid) {
-                    const size_t row = static_cast<size_t>(tile.stream) * a.stride_frames + tile.f0 + r;
+                    const size_t row = a.rows ? a.rows[static_cast<size_t>(tile_local) * NM_BM + r].out_row
+                                              : static_cast<size_t>(tile.stream) * a.stride_frames + tile.f0 + r;
 #pragma unroll
                     for (int s = 0; s < 4; ++s) {
                         const size_t at = row * NM_OUT + NM_BN * ct + 16 * s + c;
@@ -160,7 +164,8 @@ __global__ __launch_bounds__(NM_THREADS, 2) void nm_conv_fc1(const NmArgs a) {
     for (int t = 0; t < 2; ++t) {
         uint32_t r = 32 * wave + 16 * t + (lane & 15);
         if (r >= tile.n_valid) r = 0;
-        xrow[t] = a.db + (static_cast<size_t>(tile.stream) * a.stride_frames + tile.f0 + r - (a.t_frames - 1)) * a.n_bins;
+        xrow[t] = a.rows ? a.rows[static_cast<size_t>(tile_local) * NM_BM + r].x   // (uniform choice)
+                         : a.db + (static_cast<size_t>(tile.stream) * a.stride_frames + tile.f0 + r - (a.t_frames - 1)) * a.n_bins;
     }
     const uint32_t last = a.L - 1;   // every position a real chunk reads is <= last; the clamp serves the padded chunks of the last stage
     float x[2][X_REGS], xn[2][X_STAGE];
@@ -298,12 +303,13 @@ __global__ __launch_bounds__(NM_THREADS, 2) void nm_dense(const NmArgs a) {
 }
 
 // the f32 launches of the tiles d_tiles[0 .. nt): fc1 over the fused conv, the hidden layers, the output layer into `outs`
-void nm_chunk(const NmContext& c, const NmTile* d_tiles, uint32_t nt, const float* d_db, size_t stride_frames, const pvq_note_model_outputs& outs,
-              hipStream_t stream) {
+void nm_chunk(const NmContext& c, const NmTile* d_tiles, const NmRow* d_rows, uint32_t nt, const float* d_db, size_t stride_frames,
+              const pvq_note_model_outputs& outs, hipStream_t stream) {
     const NoteModelDims& d = c.d;
     float* buf[2] = {reinterpret_cast<float*>(c.ws + c.at.h_at[0]), reinterpret_cast<float*>(c.ws + c.at.h_at[1])};
     NmArgs a{};
     a.tiles = d_tiles;
+    a.rows = d_rows;
     a.stride_frames = stride_frames;
     a.n_bins = d.n_bins;
     a.t_frames = d.t_frames;
@@ -398,9 +404,9 @@ pvq_status NoteModel::create(int device_id, const pvq_note_model_params* params,
     return PVQ_OK;
 }
 
-pvq_status NoteModel::rows_device(const float* d_db, const size_t* n_frames, uint32_t n_streams, size_t stride_frames,
-                                  const pvq_note_model_outputs& outs, hipStream_t stream) {
-    const NoteModelDims& d = host_.d;
+// the argument checks of both row calls, before any device is touched
+pvq_status NoteModel::check_rows(const float* d_db, const size_t* n_frames, uint32_t n_streams, size_t stride_frames,
+                                 const pvq_note_model_outputs& outs) const {
     const bool half = host_.precision != PVQ_NOTE_F32;
     if (!d_db) {
         set_last_error("note model: d_db is null");
@@ -423,24 +429,24 @@ pvq_status NoteModel::rows_device(const float* d_db, const size_t* n_frames, uin
             set_last_error("note model: n_frames of stream " + std::to_string(s) + " exceeds stride_frames");
             return PVQ_ERR_INVALID_ARG;
         }
-    if (device_id_ < 0) {
-        set_last_error("the batched note model runs on a GPU; this handle has none (pvq_note_model_infer is the host face)");
-        return PVQ_ERR_NO_DEVICE;
-    }
-    const size_t rows_all = static_cast<size_t>(n_streams) * stride_frames;
-    if (rows_all == 0 || !(outs.d_prob || outs.d_logits || outs.d_mask)) return PVQ_OK;
-    PVQ_HIP(hipSetDevice(device_id_));
-    // every row that is no model row is zero; the model rows are overwritten below
+    return PVQ_OK;
+}
+
+// every row of every output is zero before the model rows are written
+pvq_status NoteModel::zero_outputs(size_t rows_all, const pvq_note_model_outputs& outs, hipStream_t stream) {
+    if (rows_all == 0) return PVQ_OK;
     if (outs.d_prob) PVQ_HIP(hipMemsetAsync(outs.d_prob, 0, rows_all * NM_OUT * sizeof(float), stream));
     if (outs.d_logits) PVQ_HIP(hipMemsetAsync(outs.d_logits, 0, rows_all * NM_OUT * sizeof(float), stream));
     if (outs.d_mask) PVQ_HIP(hipMemsetAsync(outs.d_mask, 0, rows_all * 4 * sizeof(uint32_t), stream));
-    const std::vector<NmTile> tiles = note_model_tiles(d, n_frames, n_streams, stride_frames);
-    if (tiles.empty()) return PVQ_OK;
+    return PVQ_OK;
+}
 
-    NmContext c;
+// the workspace for n_tiles tiles and what the launches of a chunk work on; the tile table lies at the workspace's start
+pvq_status NoteModel::prepare(size_t n_tiles, NmContext& c) {
+    const NoteModelDims& d = host_.d;
     c.d = d;
     c.precision = host_.precision;
-    c.at = note_model_workspace(d, host_.precision, tiles.size(), ws_limit_);
+    c.at = note_model_workspace(d, host_.precision, n_tiles, ws_limit_);
     if (pvq_status s = ws_.reserve(c.at.total)) return s;
     c.ws = ws_.as<char>();
     c.conv = conv_.as<float>();
@@ -451,17 +457,72 @@ pvq_status NoteModel::rows_device(const float* d_db, const size_t* n_frames, uin
     put(0, fc1_);
     for (uint32_t i = 0; i < d.layers; ++i) put(1 + i, layer_[i]);
     put(1 + d.layers, out_);
-    NmTile* d_tiles = ws_.as<NmTile>();
-    PVQ_HIP(hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(NmTile), hipMemcpyHostToDevice, stream));   // (pageable source: staged before the call returns)
+    return PVQ_OK;
+}
 
+// the launches of n_tiles tiles, in chunks of whole tiles that fit the workspace; d_rows: null or their row table
+pvq_status NoteModel::run(const NmContext& c, size_t n_tiles, const NmRow* d_rows, const float* d_db, size_t stride_frames,
+                          const pvq_note_model_outputs& outs, hipStream_t stream) {
+    const NmTile* d_tiles = ws_.as<NmTile>();
     const size_t chunk_tiles = c.at.chunk_tiles;
-    for (size_t t0 = 0; t0 < tiles.size(); t0 += chunk_tiles) {
-        const uint32_t nt = static_cast<uint32_t>(std::min(chunk_tiles, tiles.size() - t0));
-        if (half) nmh_chunk(c, d_tiles + t0, nt, d_db, stride_frames, outs, stream);
-        else nm_chunk(c, d_tiles + t0, nt, d_db, stride_frames, outs, stream);
+    for (size_t t0 = 0; t0 < n_tiles; t0 += chunk_tiles) {
+        const uint32_t nt = static_cast<uint32_t>(std::min(chunk_tiles, n_tiles - t0));
+        const NmRow* rows = d_rows ? d_rows + t0 * NM_BM : nullptr;
+        if (host_.precision != PVQ_NOTE_F32) nmh_chunk(c, d_tiles + t0, rows, nt, d_db, stride_frames, outs, stream);
+        else nm_chunk(c, d_tiles + t0, rows, nt, d_db, stride_frames, outs, stream);
     }
     PVQ_HIP(hipGetLastError());
     return PVQ_OK;
+}
+
+pvq_status NoteModel::rows_device(const float* d_db, const size_t* n_frames, uint32_t n_streams, size_t stride_frames,
+                                  const pvq_note_model_outputs& outs, hipStream_t stream) {
+    const NoteModelDims& d = host_.d;
+    if (pvq_status s = check_rows(d_db, n_frames, n_streams, stride_frames, outs)) return s;
+    if (device_id_ < 0) {
+        set_last_error("the batched note model runs on a GPU; this handle has none (pvq_note_model_infer is the host face)");
+        return PVQ_ERR_NO_DEVICE;
+    }
+    const size_t rows_all = static_cast<size_t>(n_streams) * stride_frames;
+    if (rows_all == 0 || !(outs.d_prob || outs.d_logits || outs.d_mask)) return PVQ_OK;
+    PVQ_HIP(hipSetDevice(device_id_));
+    // every row that is no model row is zero; the model rows are overwritten below
+    if (pvq_status s = zero_outputs(rows_all, outs, stream)) return s;
+    const std::vector<NmTile> tiles = note_model_tiles(d, n_frames, n_streams, stride_frames);
+    if (tiles.empty()) return PVQ_OK;
+
+    NmContext c;
+    if (pvq_status s = prepare(tiles.size(), c)) return s;
+    NmTile* d_tiles = ws_.as<NmTile>();
+    PVQ_HIP(hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(NmTile), hipMemcpyHostToDevice, stream));   // (pageable source: staged before the call returns)
+    return run(c, tiles.size(), nullptr, d_db, stride_frames, outs, stream);
+}
+
+pvq_status NoteModel::rows_carry_device(NoteCarry& carry, const float* d_db, const size_t* n_frames, uint32_t n_streams, size_t stride_frames,
+                                        const pvq_note_model_outputs& outs, hipStream_t stream) {
+    const NoteModelDims& d = host_.d;
+    if (pvq_status s = check_rows(d_db, n_frames, n_streams, stride_frames, outs)) return s;
+    if (!carry.fits(d, device_id_) || carry.n_streams() != n_streams) {
+        set_last_error("note carry: made for another n_streams, or for a model of other sizes or on another device");
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (device_id_ < 0) {
+        set_last_error("the batched note model runs on a GPU; this handle has none (pvq_note_model_infer is the host face)");
+        return PVQ_ERR_NO_DEVICE;
+    }
+    if (pvq_status s = carry.plan(d, n_frames, stride_frames)) return s;
+    const NcPlan& plan = carry.planned();
+    PVQ_HIP(hipSetDevice(device_id_));
+    if (pvq_status s = zero_outputs(static_cast<size_t>(n_streams) * stride_frames, outs, stream)) return s;
+    if (plan.max_n == 0) return PVQ_OK;   // no stream gets a frame
+    const size_t n_tiles = static_cast<size_t>(plan.tiles);
+    NmContext c;
+    if (pvq_status s = prepare(std::max<size_t>(1, n_tiles), c)) return s;   // (the tile list nc_rows writes lies in the workspace)
+    // every frame a row needs is copied or read by the kernels queued here: the caller may overwrite d_db in stream order behind them
+    if (pvq_status s = carry.stage(d_db, stride_frames, ws_.as<NmTile>(), stream)) return s;
+    if (n_tiles && (outs.d_prob || outs.d_logits || outs.d_mask))   // (without an output the frames are still taken in)
+        if (pvq_status s = run(c, n_tiles, carry.rows(), d_db, stride_frames, outs, stream)) return s;
+    return carry.commit(d_db, stride_frames, stream);
 }
 
 }  // namespace pvq

@@ -10,7 +10,8 @@
 // way NoteModel::rows_device is the one driver: the argument checks, the zeroed outputs, the tile list, the planned workspace
 // (note_model_workspace), the loop over chunks of whole tiles that fit its limit.  Two things are per precision: how a dense layer
 // is packed when it is uploaded, and the launches of one chunk.
-// NoteModelHost (note_model_plan.hpp) is the one-row host face.
+// NoteModelHost (note_model_plan.hpp) is the one-row host face.  rows_carry_device is the same driver over a row table that
+// note_carry.hip builds on the device: the four places of the kernels that name a row's window or output row read the table instead.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -22,9 +23,12 @@
 
 #include "../../include/pvq.h"
 #include "device_support.hpp"
+#include "note_model_half.hpp"
 #include "note_model_plan.hpp"
 
 namespace pvq {
+
+class NoteCarry;
 
 class NoteModel {
    public:
@@ -45,6 +49,10 @@ class NoteModel {
     // n_frames: HOST array or null.  Asynchronous on `stream`; uses the handle's workspace, so one stream at a time.
     pvq_status rows_device(const float* d_db, const size_t* n_frames, uint32_t n_streams, size_t stride_frames,
                            const pvq_note_model_outputs& outs, hipStream_t stream);
+    // The same with windows that continue from the carry's last call (note_carry.hpp): n_frames[s] NEW frames per stream, row (s, f)
+    // a model row when the stream has seen t_frames - 1 frames before it, the rows of all streams packed into shared tiles.
+    pvq_status rows_carry_device(NoteCarry& carry, const float* d_db, const size_t* n_frames, uint32_t n_streams, size_t stride_frames,
+                                 const pvq_note_model_outputs& outs, hipStream_t stream);
     void set_workspace_limit(uint64_t bytes) { ws_limit_ = bytes; }
 
    private:
@@ -54,6 +62,12 @@ class NoteModel {
         size_t bias_at = 0;   // byte offset of the bias, a multiple of 16
     };
     pvq_status upload(const float* W, const float* bias, uint32_t n, uint32_t k, bool conv_order, Layer& l);
+    // the pieces of a row call (note_model.hip)
+    pvq_status check_rows(const float* d_db, const size_t* n_frames, uint32_t n_streams, size_t stride_frames, const pvq_note_model_outputs& outs) const;
+    pvq_status zero_outputs(size_t rows_all, const pvq_note_model_outputs& outs, hipStream_t stream);
+    pvq_status prepare(size_t n_tiles, NmContext& c);
+    pvq_status run(const NmContext& c, size_t n_tiles, const NmRow* d_rows, const float* d_db, size_t stride_frames,
+                   const pvq_note_model_outputs& outs, hipStream_t stream);
     int device_id_ = -1;
     NoteModelHost host_;
     uint64_t ws_limit_ = 256ull << 20;

@@ -48,6 +48,7 @@ struct Type16<PVQ_NOTE_F16> {
 
 struct NmhArgs {
     const NmTile* tiles;     // this launch's tiles
+    const NmRow* rows;       // null, or the launch's row table as in note_model.hip's NmArgs
     const float* db;         // nmh_features: [n_streams][stride_frames][n_bins]
     const float* conv;       // nmh_features: conv weights [16][5], bias [16]
     const void* x_in;        // nmh_dense: [tiles * 128][k_pad], 16-bit
@@ -79,7 +80,8 @@ __global__ __launch_bounds__(64) void nmh_features(const NmhArgs a) {
 #pragma unroll
     for (int c = 0; c < 8; ++c) lo[c] = hi[c] = static_cast<T>(0.0f);
     if (r < tile.n_valid && p < a.o_pool) {
-        const float* xrow = a.db + (static_cast<size_t>(tile.stream) * a.stride_frames + tile.f0 + r - (a.t_frames - 1)) * a.n_bins + 4 * p;
+        const float* xrow = (a.rows ? a.rows[row_local].x   // (uniform choice; row_local = 128 * tile_local + r)
+                                    : a.db + (static_cast<size_t>(tile.stream) * a.stride_frames + tile.f0 + r - (a.t_frames - 1)) * a.n_bins) + 4 * p;
         float x[NM_KW + 2];
 #pragma unroll
         for (int j = 0; j < NM_KW + 2; ++j) x[j] = xrow[j];   // 4 p + 6 <= L - 1 for p < o_pool
@@ -215,7 +217,8 @@ __global__ __launch_bounds__(NMH_THREADS, 2) void nmh_dense(const NmhArgs a) {
             }
             const uint32_t upper = __shfl_xor(bits, 16);   // the row's next 16 columns (lane group g ^ 1); every lane takes part
             if (r < tile.n_valid) {
-                const size_t row = static_cast<size_t>(tile.stream) * a.stride_frames + tile.f0 + r;
+                const size_t row = a.rows ? a.rows[static_cast<size_t>(tile_local) * NM_BM + r].out_row
+                                          : static_cast<size_t>(tile.stream) * a.stride_frames + tile.f0 + r;
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
                     const size_t at = row * NM_OUT + cb + 4 * s;
@@ -245,13 +248,14 @@ constexpr Kernels kernels_of() {
 }
 }  // namespace
 
-void nmh_chunk(const NmContext& c, const NmTile* d_tiles, uint32_t nt, const float* d_db, size_t stride_frames,
+void nmh_chunk(const NmContext& c, const NmTile* d_tiles, const NmRow* d_rows, uint32_t nt, const float* d_db, size_t stride_frames,
                const pvq_note_model_outputs& outs, hipStream_t stream) {
     const NoteModelDims& d = c.d;
     const NmWorkspace& w = c.at;
     const Kernels kern = c.precision == PVQ_NOTE_BF16 ? kernels_of<PVQ_NOTE_BF16>() : kernels_of<PVQ_NOTE_F16>();
     NmhArgs a{};
     a.tiles = d_tiles;
+    a.rows = d_rows;
     a.stride_frames = stride_frames;
     a.n_bins = d.n_bins;
     a.t_frames = d.t_frames;

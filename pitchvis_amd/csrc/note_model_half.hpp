@@ -32,8 +32,16 @@ struct NmContext {
     NmWorkspace at;                             //   and where its pieces lie
 };
 
+// one row of a gathered call (note_carry.hip builds the table on the device): where its window of L floats begins, and the row of
+// the outputs it writes.  Read by the kernels of both paths as laid out here.
+struct alignas(16) NmRow {
+    const float* x;
+    uint64_t out_row;
+};
+
 // the 16-bit launches of the tiles d_tiles[0 .. nt): features, fc1, the hidden layers, the output layer into `outs`.  Queues only.
-void nmh_chunk(const NmContext& c, const NmTile* d_tiles, uint32_t nt, const float* d_db, size_t stride_frames,
+// d_rows: null, or the row table of these tiles (128 entries a tile).
+void nmh_chunk(const NmContext& c, const NmTile* d_tiles, const NmRow* d_rows, uint32_t nt, const float* d_db, size_t stride_frames,
                const pvq_note_model_outputs& outs, hipStream_t stream);
 
 }  // namespace pvq

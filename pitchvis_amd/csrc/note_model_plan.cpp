@@ -86,6 +86,35 @@ std::vector<NmTile> note_model_tiles(const NoteModelDims& d, const size_t* n_fra
     return tiles;
 }
 
+pvq_status note_carry_plan(const NoteModelDims& d, const uint64_t* seen, const size_t* n_frames, uint32_t n_streams, size_t stride_frames,
+                           NcPlan& out, std::string& err) {
+    out.streams.resize(n_streams);
+    out.total_rows = out.tiles = 0;
+    out.max_rows = out.max_n = 0;
+    const uint64_t lead = d.t_frames - 1u;   // frames a stream needs before its first model row
+    for (uint32_t s = 0; s < n_streams; ++s) {
+        const uint64_t n = n_frames ? n_frames[s] : stride_frames;
+        const uint64_t missing = seen[s] < lead ? lead - seen[s] : 0u;
+        const uint64_t f_first = std::min(missing, n);
+        NcStream& st = out.streams[s];
+        st.first_row = static_cast<uint32_t>(out.total_rows);
+        st.f_first = static_cast<uint32_t>(f_first);
+        st.rows = static_cast<uint32_t>(n - f_first);
+        st.head = static_cast<uint32_t>(std::min(n, lead) - std::min(f_first, lead));
+        st.n = static_cast<uint32_t>(n);
+        st.pad[0] = st.pad[1] = st.pad[2] = 0u;
+        out.total_rows += st.rows;
+        out.max_rows = std::max(out.max_rows, st.rows);
+        out.max_n = std::max(out.max_n, st.n);
+        if (out.total_rows > 0x7fffffffull) {
+            err = "note carry: too many model rows in one call";
+            return PVQ_ERR_INVALID_ARG;
+        }
+    }
+    out.tiles = (out.total_rows + NM_BM - 1) / NM_BM;
+    return PVQ_OK;
+}
+
 namespace {
 uint32_t f32_bits(float x) {
     uint32_t u;

@@ -6,6 +6,7 @@
 // layers x (Linear -> ReLU) -> Linear(., 128) -> sigmoid, over a window of t_frames dB frames.
 #pragma once
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -81,6 +82,52 @@ pvq_status note_model_check_range(const NoteModelDims& d, const pvq_note_model_w
 // conv_order: k' = 16 p + c stands for feature c * o_pool + p (fc1); else k' = k.
 std::vector<uint16_t> note_model_pack_b16(const float* W, uint32_t n, uint32_t k, bool conv_order, uint32_t o_pool, pvq_note_precision prec);
 inline uint32_t note_model_stages16(uint32_t k) { return (note_model_pad32(k) / NM_KC16 + NM_PC - 1) / NM_PC; }
+
+// ---- windows that continue across calls (note_carry.hip): the plan of one call ----
+// A stream has been given seen[s] frames before the call and gets n now.  Frame f of the call is a model row when seen + f >=
+// t_frames - 1; the model rows of all streams are numbered stream by stream, frame by frame, and 128 consecutive numbers are a
+// tile, whatever streams they come from.  One descriptor per stream goes to the device, where note_carry_row expands it.
+#if defined(__HIPCC__)
+#define PVQ_NC_HD __host__ __device__ inline
+#else
+#define PVQ_NC_HD inline
+#endif
+struct alignas(16) NcStream {
+    uint32_t first_row;   // table row of the stream's first model row
+    uint32_t f_first;     // the call's frame that row stands for: max(0, t_frames - 1 - seen), at most n
+    uint32_t rows;        // model rows: n - f_first
+    uint32_t head;        // how many of them are head rows, f < t_frames - 1: their window begins before the call
+    uint32_t n;           // frames given in this call
+    uint32_t pad[3];
+};
+struct NcPlan {
+    std::vector<NcStream> streams;
+    uint64_t total_rows = 0, tiles = 0;   // tiles = ceil(total_rows / 128)
+    uint32_t max_rows = 0, max_n = 0;     // the largest of a stream
+};
+// n_frames null: every stream gets stride_frames.  The caller has checked n_frames[s] <= stride_frames <= 2^31 - 1.
+// PVQ_ERR_INVALID_ARG (text in err) when the call has 2^31 model rows or more.  `out` is reused: no allocation once it has n_streams entries.
+pvq_status note_carry_plan(const NoteModelDims& d, const uint64_t* seen, const size_t* n_frames, uint32_t n_streams, size_t stride_frames,
+                           NcPlan& out, std::string& err);
+// The stitched buffer of a stream holds 2 (t_frames - 1) frames: the tail (the last frames before the call, right-aligned) in the
+// first half, then the call's first min(n, t_frames - 1) frames.  Model row i of stream s stands for frame f = f_first + i:
+//   in_stitch  f < t_frames - 1: the window is floats [at, at + L) of the stream's stitched buffer (at = f * n_bins);
+//              else floats [at, at + L) of d_db, at = (s * stride_frames + f - (t_frames - 1)) * n_bins
+//   out_row    s * stride_frames + f
+struct NcRow {
+    bool in_stitch;
+    uint64_t at, out_row;
+};
+PVQ_NC_HD NcRow note_carry_row(const NcStream& st, uint32_t s, uint32_t i, uint32_t t_frames, uint32_t n_bins, uint64_t stride_frames) {
+    const uint64_t f = static_cast<uint64_t>(st.f_first) + i;
+    NcRow r;
+    r.in_stitch = f < t_frames - 1u;
+    r.at = (r.in_stitch ? f : s * stride_frames + f - (t_frames - 1u)) * n_bins;
+    r.out_row = s * stride_frames + f;
+    return r;
+}
+// after the call: the frames a stream's tail holds, min(t_frames - 1, seen + n)
+inline uint64_t note_carry_tail_frames(const NoteModelDims& d, uint64_t seen_after) { return std::min<uint64_t>(d.t_frames - 1u, seen_after); }
 
 // ---- the workspace of a call, every precision ----
 // The tile table (rounded up to 256 bytes), then per chunk of tiles two hidden buffers: PVQ_NOTE_F32 [rows][mlp] floats; 16-bit

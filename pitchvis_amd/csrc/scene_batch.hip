@@ -3,7 +3,8 @@
 // scene_peaks (frame-parallel, a wavefront per (stream, frame) row, a lane per peak): util::arg_max of the row's sizes, then
 // scene::peak_record for every entry of the list — colour, spiral position, alpha, z, scale, the three params, key bin, hide range
 // (update.rs:199-302, :310-315) — and, once per row, the bloom and the bass spiral's (lit count, colour) (update.rs:336-425).  None
-// of it reads the scene's state, and all the libm of a frame sits here.  The records go to a workspace of the handle.
+// of it reads the scene's state, and all the libm of a frame sits here.  The records go to a workspace of the handle.  With a
+// probability buffer (the note model's d_prob, its own frame stride) a record's alpha follows the `ml` branch (update.rs:247-255).
 //
 // scene_frames<NK> (a wavefront per stream, frames in order; lane l owns bins l, l + 64, ...; NK: the bin count's 64-chunk): what
 // recurs.  Per bin the fade (update.rs:151-177: two multiplies, a max, a subtract, two compares), then the frame's records are
@@ -53,6 +54,8 @@ struct SceneArgs {
     const float* accuracy;
     const float* deviation;
     const float* scene_calmness;
+    const float* ml_prob;             // [n_streams][ml_stride][128] or null: no `ml` branch
+    size_t ml_stride;
     uint32_t max_peaks, n_streams;
     uint32_t n_frames, f0, pf;        // the call's frames; this piece is frames f0 .. f0 + pf
     int n_bins;
@@ -107,9 +110,11 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void scene_peaks(Scene
         }
         const float max_size = best > scene::F32_MIN ? best : z_row[0];
         const size_t bins = g * static_cast<size_t>(a.n_bins);
+        // the row's probabilities: stream r / pf, frame f0 + r % pf of a buffer with its own frame stride (so not row g)
+        const float* ml = a.ml_prob ? a.ml_prob + (static_cast<size_t>(r / a.pf) * a.ml_stride + a.f0 + r % a.pf) * scene::MIDI_PITCHES : nullptr;
         for (uint32_t p = lane; p < cnt; p += 64) {
             scene::PeakRecord q;
-            scene::peak_record(s_set, c_row[p], z_row[p], max_size, a.calmness + bins, a.accuracy + bins, a.deviation + bins, q);
+            scene::peak_record(s_set, c_row[p], z_row[p], max_size, a.calmness + bins, a.accuracy + bins, a.deviation + bins, q, ml);
             uint4* dst = reinterpret_cast<uint4*>(a.rec + static_cast<size_t>(r) * a.max_peaks + p);
             dst[0] = make_uint4(__float_as_uint(q.x), __float_as_uint(q.y), __float_as_uint(q.z), __float_as_uint(q.scale));
             dst[1] = make_uint4(__float_as_uint(q.r), __float_as_uint(q.g), __float_as_uint(q.b), __float_as_uint(q.a));
@@ -339,7 +344,7 @@ pvq_status SceneBatch::create(int device_id, uint32_t octaves, uint32_t buckets_
 }
 
 pvq_status SceneBatch::frames_device(size_t n_frames, const pvq_scene_inputs& in, uint64_t frame_time_ns, const uint64_t* frame_times_ns,
-                                     const pvq_scene_outputs& outs, hipStream_t stream) {
+                                     const pvq_scene_outputs& outs, hipStream_t stream, const float* d_ml_prob, size_t ml_stride_frames) {
     if (!in.center || !in.size || !in.peak_count || in.max_peaks == 0) {
         set_last_error("scene batch: center, size and peak_count are needed, with max_peaks > 0");
         return PVQ_ERR_INVALID_ARG;
@@ -356,6 +361,10 @@ pvq_status SceneBatch::frames_device(size_t n_frames, const pvq_scene_inputs& in
     std::string err;
     if (!stage_frames_ok("scene batch", n_frames, n_streams_, err)) {
         set_last_error(err);
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (d_ml_prob && (ml_stride_frames < n_frames || ml_stride_frames > (~0ull >> 12) / n_streams_)) {
+        set_last_error("scene batch: ml_stride_frames must be at least n_frames");
         return PVQ_ERR_INVALID_ARG;
     }
     if (device_id_ < 0) {
@@ -402,6 +411,8 @@ pvq_status SceneBatch::frames_device(size_t n_frames, const pvq_scene_inputs& in
     a.accuracy = in.pitch_accuracy;
     a.deviation = in.pitch_deviation;
     a.scene_calmness = in.scene_calmness;
+    a.ml_prob = d_ml_prob;
+    a.ml_stride = ml_stride_frames;
     a.max_peaks = in.max_peaks;
     a.n_streams = n_streams_;
     a.n_frames = static_cast<uint32_t>(n_frames);

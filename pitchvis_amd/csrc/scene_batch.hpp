@@ -29,9 +29,10 @@ class SceneBatch {
     uint32_t n_streams() const { return n_streams_; }
     uint32_t n_segments() const { return s_.n_segments; }
     // Every stream advances by n_frames frames.  Inputs [n_streams][n_frames][...] (device), frame_times_ns: host array or null.
+    // d_ml_prob: [n_streams][ml_stride_frames][128] (device) for the `ml` branch, or null: the branch is off and the stride unread.
     // Asynchronous on `stream`; one handle's calls are stream-ordered.
     pvq_status frames_device(size_t n_frames, const pvq_scene_inputs& in, uint64_t frame_time_ns, const uint64_t* frame_times_ns,
-                             const pvq_scene_outputs& outs, hipStream_t stream);
+                             const pvq_scene_outputs& outs, hipStream_t stream, const float* d_ml_prob = nullptr, size_t ml_stride_frames = 0);
     // one stream's state after the last call (synchronises the device); any pointer may be null
     pvq_status get_state(uint32_t stream_index, float* ball_xyzs, float* ball_rgba, float* ball_params, uint32_t* ball_visible,
                          uint32_t* bass_lit, float* bass_rgba, float* bloom);

@@ -68,7 +68,7 @@ SceneState::SceneState(const scene::Settings& s) : s_(s), dropoff_(s.n_bins), ow
 }
 
 void SceneState::update(const float* center, const float* size, uint32_t n_peaks, const float* calmness, const float* pitch_accuracy,
-                        const float* pitch_deviation, float scene_calmness, uint64_t frame_time_ns) {
+                        const float* pitch_deviation, float scene_calmness, uint64_t frame_time_ns, const float* ml_prob) {
     const uint32_t n = s_.n_bins;
     if (frame_time_ns != table_ns_) {
         scene_fade_table(n, frame_time_ns, dropoff_.data(), z_step_);
@@ -95,7 +95,7 @@ void SceneState::update(const float* center, const float* size, uint32_t n_peaks
     std::fill(hide_.begin(), hide_.end(), 0);
     std::vector<scene::PeakRecord> rec(n_peaks);
     for (uint32_t p = 0; p < n_peaks; ++p) {
-        scene::peak_record(s_, center[p], size[p], max_size, calmness, pitch_accuracy, pitch_deviation, rec[p]);
+        scene::peak_record(s_, center[p], size[p], max_size, calmness, pitch_accuracy, pitch_deviation, rec[p], ml_prob);
         if (rec[p].key < n) owner_[rec[p].key] = p + 1u;
     }
     for (uint32_t idx = 0; idx < n; ++idx) {   // update.rs:214-304

@@ -12,8 +12,8 @@
 //
 // Bloom intensity starts at 0 here; the reference leaves Bevy's default on the camera until the first frame with peaks.
 // A peak whose trunc(center) is >= n_bins is ignored (the reference would index out of range); it still counts for max_size.
-// Left out: the `ml` branch (update.rs:247-255: it reads an AnalysisState field that no longer exists), params.time (the caller's
-// clock).  The debug meshes (update_spectrum, the calmness histogram and graph) are panels_host.hpp's.
+// The `ml` branch (update.rs:247-255) takes the probabilities as an argument of update: a keyed ball whose MIDI pitch is inferred
+// (probability > 0.35) becomes opaque, any other nearly transparent (scene_math.hpp).  Left out: params.time (the caller's clock).  The debug meshes (update_spectrum, the calmness histogram and graph) are panels_host.hpp's.
 #pragma once
 
 #include <cstdint>
@@ -39,9 +39,10 @@ class SceneState {
    public:
     explicit SceneState(const scene::Settings& s);
     const scene::Settings& settings() const { return s_; }
-    // update_display (update.rs:80-107) for one frame; calmness / pitch_accuracy / pitch_deviation [n_bins]
+    // update_display (update.rs:80-107) for one frame; calmness / pitch_accuracy / pitch_deviation [n_bins].  ml_prob: the frame's
+    // AnalysisState::ml_midi_base_pitches [128] for the `ml` branch (update.rs:247-255), or null: the branch is off.
     void update(const float* center, const float* size, uint32_t n_peaks, const float* calmness, const float* pitch_accuracy,
-                const float* pitch_deviation, float scene_calmness, uint64_t frame_time_ns);
+                const float* pitch_deviation, float scene_calmness, uint64_t frame_time_ns, const float* ml_prob = nullptr);
     const SceneBalls& balls() const { return b_; }
     uint32_t bass_lit() const { return bass_lit_; }
     const float* bass_rgba() const { return bass_rgba_; }

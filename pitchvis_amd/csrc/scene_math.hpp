@@ -89,9 +89,22 @@ struct PeakRecord {
     uint32_t pad;
 };
 
-// calm / acc / dev: the frame's per-bin fields (only entry `key` is read)
+// The MIDI pitch of a bin as the `ml` branch names it (update.rs:248, util.rs:23-31 bin_to_midi_pitch): round(bin / bpo * 12) + 33,
+// the division and the product each rounded to f32, roundf half away from zero; 33 is FREQ_A1_MIDI_KEY_ID.  A pitch above 127 is
+// the reference's None.
+constexpr uint32_t FREQ_A1_MIDI_KEY_ID = 33;
+constexpr uint32_t MIDI_PITCHES = 128;
+constexpr float ML_THRESHOLD = 0.35f;   // update.rs:250
+PVQ_HD uint32_t midi_pitch(uint32_t bpo, uint32_t bin) {
+    PVQ_FP_STRICT
+    const float q = static_cast<float>(bin) / static_cast<float>(bpo);
+    return sat_u32(roundf(q * 12.0f)) + FREQ_A1_MIDI_KEY_ID;   // (sat_u32 stops at 4294967040: the sum does not wrap)
+}
+
+// calm / acc / dev: the frame's per-bin fields (only entry `key` is read).  ml_prob: the frame's ml_midi_base_pitches [128], or
+// null: no `ml` branch.
 PVQ_HD_FLAT void peak_record(const Settings& s, float center, float size, float max_size, const float* calm, const float* acc, const float* dev,
-                        PeakRecord& o) {
+                        PeakRecord& o, const float* ml_prob = nullptr) {
     PVQ_FP_STRICT
     const uint32_t n = s.n_bins;
     o.key = sat_u32(truncf(center));
@@ -108,6 +121,10 @@ PVQ_HD_FLAT void peak_record(const Settings& s, float center, float size, float 
     o.g = color::clampf(srgb_to_linear(rgb[1]), 0.0f, 1.0f);
     o.b = color::clampf(srgb_to_linear(rgb[2]), 0.0f, 1.0f);
     o.a = color_coefficient;
+    if (ml_prob && !ignored) {   // update.rs:247-255: an inferred pitch is opaque, any other nearly transparent
+        const uint32_t m = midi_pitch(s.bpo, o.key);
+        if (m < MIDI_PITCHES) o.a = ml_prob[m] > ML_THRESHOLD ? 1.0f : color_coefficient * 0.1f;   // (a NaN takes the dim side)
+    }
     o.calmness = color::clampf(calm[at] - 0.27f, 0.0f, 1.0f);                       // update.rs:262-263
     o.accuracy = acc[at];
     o.deviation = dev[at];

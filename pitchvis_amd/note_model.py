@@ -1,7 +1,8 @@
 """The trainer's note model (pitchvis_train/train.py:67-99), which the viewer runs per rendered frame through TorchScript
 (pitchvis_viewer/src/ml_system.rs:24-69): pvq_note_model_* of include/pvq.h.  ``NoteModel.infer`` is the one-row host face,
 ``NoteModel.rows_device`` runs every frame of many streams on the GPU, reading the ``[n_streams][stride_frames][n_bins]`` dB buffer
-``Vqt.batch_streams_device`` writes, in place."""
+``Vqt.batch_streams_device`` writes, in place.  With a ``NoteCarry`` the windows continue from call to call (pvq_note_carry_*): a
+caller that feeds frames as they arrive gets a model row per frame, and the rows of all streams share tiles."""
 from __future__ import annotations
 
 import ctypes as C
@@ -157,8 +158,10 @@ class NoteModel:
                 "d_mask": ((n_streams, stride_frames, 4), np.uint32)}[name]
 
     def rows_device(self, d_db, n_frames=None, stride_frames: Optional[int] = None, outputs=None, *, n_streams: Optional[int] = None,
-                    stream=None) -> dict:
-        """Every row of every stream.  ``d_db``: device tensor ``[n_streams][stride_frames][n_bins]`` (or a raw pointer, with
+                    stream=None, carry: Optional["NoteCarry"] = None) -> dict:
+        """Every row of every stream.  With ``carry`` (pvq_note_model_rows_carry_device) ``n_frames`` counts the NEW frames of each
+        stream, which continue what the carry has seen: row (s, f) is a model row once the stream has seen ``t_frames - 1`` frames
+        before it, and carries the bits this call without a carry gives the same window.  ``d_db``: device tensor ``[n_streams][stride_frames][n_bins]`` (or a raw pointer, with
         ``n_streams`` and ``stride_frames``); ``n_frames``: one count per stream (default: ``stride_frames`` each).  ``outputs``: a
         dict name -> device tensor to fill, or a sequence of names to allocate (default: all three; ``d_mask`` is an int32 tensor
         holding the uint32 words).  Returns the dict of output tensors.  Asynchronous on ``stream``."""
@@ -200,8 +203,52 @@ class NoteModel:
                 if t.numel() != int(np.prod(shape)) or not t.is_contiguous() or t.element_size() != 4:
                     raise ValueError(f"output {name!r} must be a contiguous 32-bit tensor of shape {shape}")
             setattr(o, name, _ptr(t))
-        st = self._L.pvq_note_model_rows_device(self._h, _ptr(d_db), nf, int(n_streams), int(stride_frames), C.byref(o), _stream_handle(stream))
+        if carry is not None:
+            st = self._L.pvq_note_model_rows_carry_device(self._h, carry._h, _ptr(d_db), nf, int(n_streams), int(stride_frames), C.byref(o),
+                                                          _stream_handle(stream))
+        else:
+            st = self._L.pvq_note_model_rows_device(self._h, _ptr(d_db), nf, int(n_streams), int(stride_frames), C.byref(o), _stream_handle(stream))
         if st == _lib.PVQ_ERR_INVALID_ARG:
             raise ValueError((self._L.pvq_last_error() or b"").decode())
         _check(st)
         return outputs
+
+
+class NoteCarry:
+    """What continues a model's windows across ``NoteModel.rows_device(..., carry=...)`` calls for ``n_streams`` streams: the last
+    ``t_frames - 1`` frames of each on the device, and the host count of the frames each has been given.  Belongs to the model's
+    ``n_bins``, ``t_frames`` and device; a host-only model gives a host-only carry."""
+
+    def __init__(self, model: NoteModel, n_streams: int):
+        from . import _check
+        self._L = _lib.load()
+        self.model, self.n_streams = model, int(n_streams)
+        self._h = C.c_void_p()
+        st = self._L.pvq_note_carry_create(model._h, self.n_streams, C.byref(self._h))
+        if st == _lib.PVQ_ERR_INVALID_ARG:
+            raise ValueError((self._L.pvq_last_error() or b"").decode())
+        _check(st)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._L.pvq_note_carry_destroy(h)
+            self._h = None
+
+    def reset(self, stream_index: Optional[int] = None, stream=None) -> None:
+        """forget one stream's frames, or (``None``) every stream's"""
+        from . import _check, _stream_handle
+        st = self._L.pvq_note_carry_reset(self._h, -1 if stream_index is None else int(stream_index), _stream_handle(stream))
+        if st == _lib.PVQ_ERR_INVALID_ARG:
+            raise ValueError((self._L.pvq_last_error() or b"").decode())
+        _check(st)
+
+    def frames_seen(self, s: int) -> int:
+        """frames stream ``s`` has been given since create or reset"""
+        from . import _check
+        out = C.c_uint64()
+        st = self._L.pvq_note_carry_frames_seen(self._h, int(s), C.byref(out))
+        if st == _lib.PVQ_ERR_INVALID_ARG:
+            raise ValueError((self._L.pvq_last_error() or b"").decode())
+        _check(st)
+        return int(out.value)

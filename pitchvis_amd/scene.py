@@ -20,6 +20,16 @@ _up = C.POINTER(C.c_uint32)
 INPUTS = ("center", "size", "peak_count", "calmness", "pitch_accuracy", "pitch_deviation", "scene_calmness")
 
 
+def midi_pitch(buckets_per_octave: int, bin: int) -> Optional[int]:
+    """The MIDI pitch the ``ml`` branch looks a bin's ball up at (display_system/util.rs:23-31), ``None`` above 127"""
+    out = C.c_uint32()
+    st = _lib.load().pvq_ml_midi_pitch(int(buckets_per_octave), int(bin), C.byref(out))
+    if st == _lib.PVQ_ERR_INVALID_ARG:
+        raise ValueError((_lib.load().pvq_last_error() or b"").decode())
+    _check(st)
+    return None if out.value == 0xFFFFFFFF else int(out.value)
+
+
 def _settings(visuals_mode, enable_bloom, colors, gray_level, easing_pow):
     pal = None if colors is None else np.ascontiguousarray(colors, np.float32)
     if pal is not None and pal.shape != (12, 3):
@@ -67,15 +77,24 @@ class SceneState:
             self._L.pvq_scene_state_destroy(h)
             self._h = None
 
-    def update(self, peaks_continuous, calmness, pitch_accuracy, pitch_deviation, scene_calmness: float, frame_time: float) -> None:
+    def update(self, peaks_continuous, calmness, pitch_accuracy, pitch_deviation, scene_calmness: float, frame_time: float,
+               ml_prob=None) -> None:
         """One frame: ``peaks_continuous`` (center, size) pairs in list order, three per-bin fields, the smoothed scene calmness and
-        the frame's duration in seconds (``frame_time``; an int is taken as nanoseconds)."""
+        the frame's duration in seconds (``frame_time``; an int is taken as nanoseconds).  ``ml_prob``: the frame's 128 note
+        probabilities for the viewer's ``ml`` branch (update.rs:247-255, pvq_ml_scene_state_update); ``None``: the branch is off."""
         ctr = np.asarray([p[0] for p in peaks_continuous] or [0.0], np.float32)
         sz = np.asarray([p[1] for p in peaks_continuous] or [0.0], np.float32)
         per_bin = [np.ascontiguousarray(a, np.float32) for a in (calmness, pitch_accuracy, pitch_deviation)]
         if any(a.size != self.n_bins for a in per_bin):
             raise ValueError("calmness, pitch_accuracy and pitch_deviation must hold n_bins values")
         ns = frame_time if isinstance(frame_time, (int, np.integer)) else int(round(frame_time * 1e9))
+        if ml_prob is not None:
+            ml = np.ascontiguousarray(ml_prob, np.float32)
+            if ml.size != 128:
+                raise ValueError("ml_prob must hold 128 values")
+            _check(self._L.pvq_ml_scene_state_update(self._h, _f(ctr), _f(sz), len(peaks_continuous), _f(per_bin[0]), _f(per_bin[1]),
+                                                     _f(per_bin[2]), float(scene_calmness), int(ns), _f(ml)))
+            return
         _check(self._L.pvq_scene_state_update(self._h, _f(ctr), _f(sz), len(peaks_continuous), _f(per_bin[0]), _f(per_bin[1]), _f(per_bin[2]),
                                               float(scene_calmness), int(ns)))
 
@@ -120,12 +139,15 @@ class SceneBatch:
                 "bloom": ((s, f), np.float32)}[name]
 
     def frames_device(self, fields=None, outputs=None, *, frame_time: float = 1.0 / 30.0, frame_times=None, n_frames: Optional[int] = None,
-                      max_peaks: Optional[int] = None, stream=None, **inputs) -> dict:
+                      max_peaks: Optional[int] = None, stream=None, ml_prob=None, ml_stride_frames: Optional[int] = None, **inputs) -> dict:
         """Advance every stream.  Inputs: torch device tensors [n_streams][n_frames][...], by keyword or as the dict
         ``AnalysisBatch.preprocess_device(outputs=...)`` filled (``fields``; the keys of ``scene.INPUTS``).  ``outputs``: a dict
         name -> device tensor to fill, or a sequence of names to allocate (default: all of ``OUTPUTS``).  ``frame_time`` in seconds,
         or ``frame_times``: per-frame seconds (host sequence).  ``n_frames`` / ``max_peaks`` default to what the tensors' shapes
-        say (raw pointers need them).  Returns the dict of output tensors.  Asynchronous on ``stream``."""
+        say (raw pointers need them).  ``ml_prob``: the note probabilities ``[n_streams][ml_stride_frames][128]`` for the viewer's
+        ``ml`` branch, a device tensor (``NoteModel.rows_device``'s ``d_prob``, taken where it lies) or a raw pointer;
+        ``ml_stride_frames`` defaults to the tensor's second dimension; ``None``: the branch is off.  Returns the dict of output
+        tensors.  Asynchronous on ``stream``."""
         from . import _ptr, _stream_handle
         f = dict(fields or {})
         f.update({k: v for k, v in inputs.items() if v is not None})
@@ -171,8 +193,22 @@ class SceneBatch:
             if len(frame_times) != n_frames:
                 raise ValueError("frame_times: one entry per frame")
             ft = (C.c_uint64 * n_frames)(*[int(round(x * 1e9)) for x in frame_times])
-        st = self._L.pvq_scene_batch_frames_device(self._h, int(n_frames), C.byref(i), int(round(frame_time * 1e9)), ft, C.byref(o),
-                                                   _stream_handle(stream))
+        if ml_prob is not None:
+            if hasattr(ml_prob, "shape"):
+                if ml_prob.dim() != 3 or ml_prob.shape[0] != self.n_streams or ml_prob.shape[2] != 128 or not ml_prob.is_contiguous() \
+                        or ml_prob.element_size() != 4:
+                    raise ValueError("ml_prob must be a contiguous f32 tensor [n_streams][ml_stride_frames][128]")
+                if ml_stride_frames is None:
+                    ml_stride_frames = int(ml_prob.shape[1])
+                if ml_stride_frames > ml_prob.shape[1]:
+                    raise ValueError("ml_prob is smaller than n_streams * ml_stride_frames rows")
+            if ml_stride_frames is None:
+                raise ValueError("ml_stride_frames is needed with a raw pointer")
+            st = self._L.pvq_ml_scene_batch_frames_device(self._h, int(n_frames), C.byref(i), _ptr(ml_prob), int(ml_stride_frames),
+                                                          int(round(frame_time * 1e9)), ft, C.byref(o), _stream_handle(stream))
+        else:
+            st = self._L.pvq_scene_batch_frames_device(self._h, int(n_frames), C.byref(i), int(round(frame_time * 1e9)), ft, C.byref(o),
+                                                       _stream_handle(stream))
         if st == _lib.PVQ_ERR_INVALID_ARG:
             raise ValueError((self._L.pvq_last_error() or b"").decode())
         _check(st)
