@@ -1592,6 +1592,50 @@ pvq_status pvq_note_trainer_test(pvq_note_trainer *t, const float *d_db, const f
 pvq_status pvq_note_test_metrics(const pvq_note_test_batch *b, size_t n_batches,
                                  double *mean_f1, double *accuracy, double *mean_loss);
 
+/* The epoch loop of the trainer (pitchvis_train/train.py:147-162): DataLoader(train_dataset, batch_size, shuffle=True), one
+ * optimisation step per batch, running_loss / len(train_loader).
+ *
+ * Order.  The shuffle has no stateful generator either: the order of an epoch is a counter-based permutation of [0, n), a function
+ *   of (seed, epoch, n) evaluated per element.  With mix as for the dropout mask, 64-bit unsigned arithmetic modulo 2^64 and n the
+ *   number of samples:
+ *       n == 1:  order(0) = 0.  Otherwise
+ *       b      = max(2, bit_length(n - 1)) rounded up to an even number;  h = b / 2;  mask = 2^h - 1
+ *       base   = mix(mix(seed + 0x9E3779B97F4A7C15 * (epoch + 1)) ^ 0x45504F4348)
+ *       key_i  = mix(base ^ i)                                                      for i = 0 .. 3
+ *       pass(x), x < 2^b:  l = x >> h;  r = x & mask;  four rounds i = 0 .. 3 of  (l, r) = (r, l ^ (mix(key_i ^ r) & mask));
+ *                          the result is (l << h) | r
+ *       order(j), j < n:   x = pass(j);  while x >= n: x = pass(x)
+ *   pass is a four-round Feistel network, a bijection of [0, 2^b) whatever mix is; the walk along its cycle back below n makes order
+ *   a bijection of [0, n).  2^b <= 4 n for n >= 2, so a walk is a few passes long.  pvq_note_epoch_order evaluates it on the host.
+ * Batches.  idx is a HOST array of n_idx sample indices, the train split (1 <= n_idx <= 2^25; duplicates are legal).  Batch k is the
+ *   samples idx[order(k * batch + r)], r = 0 .. min(batch, n_idx - k * batch), with n = n_idx: the last batch may be short and still
+ *   counts, because the DataLoader keeps it (train.py:64).
+ * Steps.  Each batch is one PVQ_TRAIN_STEP, with the bits of pvq_note_trainer_step called with that batch as its host idx at that
+ *   counter: weights, gradients, moments, dropout keys, loss.  pvq_note_trainer_steps advances by ceil(n_idx / batch).
+ * Loss.  out_losses[k] is the float d_loss would receive for batch k; out_mean_loss their sum in double, in batch order, divided by
+ *   the number of batches (train.py:162). */
+/* One epoch over the dataset (d_db, d_targets, n_rows: DEVICE, as for a step, never written).  out_losses (HOST, ceil(n_idx / batch)
+ * floats) and out_mean_loss (HOST) may each be NULL.  Bad arguments (a null d_db, d_targets or idx, a batch outside 1 .. max_batch,
+ * n_idx outside 1 .. 2^25, an index outside [t_frames - 1, n_rows)) give PVQ_ERR_INVALID_ARG with a message, launch nothing and leave
+ * the counter; a host-only handle returns PVQ_ERR_NO_DEVICE after these checks.  idx goes to the device once per call; the split,
+ * its order and the batch losses (8 bytes per entry of idx, 4 per batch) live in a grow-only buffer of the handle.  The call is a
+ * loop of launches on `stream`, is synchronous with respect to its host outputs and waits on the stream once, at the end. */
+pvq_status pvq_note_trainer_epoch(pvq_note_trainer *t, const float *d_db, const float *d_targets, size_t n_rows,
+                                  const uint32_t *idx, size_t n_idx, uint32_t batch, uint64_t shuffle_seed, uint64_t epoch,
+                                  float *out_losses /* host, ceil(n_idx / batch), or NULL */, double *out_mean_loss /* host or NULL */,
+                                  void *stream);
+/* pure host: out[j] = order(first + j) for j in 0 .. count, the order above for (seed, epoch, n).  PVQ_ERR_INVALID_ARG for n outside
+ * 1 .. 2^32, first + count > n or a null out. */
+pvq_status pvq_note_epoch_order(uint64_t seed, uint64_t epoch, uint64_t n, uint64_t first, uint64_t count, uint32_t *out);
+/* The inverse of pvq_note_trainer_read: array `what` (a pvq_train_array) of the handle is replaced by host[0 .. count), in
+ * state_dict order and layout; count must equal pvq_note_trainer_param_count (PVQ_ERR_INVALID_ARG otherwise, as for an unknown
+ * array or a null host).  On a PVQ_NOTE_BF16 handle writing PVQ_TRAIN_WEIGHTS refreshes the 16-bit shadow, as a step's Adam does.
+ * Synchronises the device; a host-only handle returns PVQ_ERR_NO_DEVICE after the checks. */
+pvq_status pvq_note_trainer_write(pvq_note_trainer *t, int what, const float *host, size_t count);
+/* Sets the counter pvq_note_trainer_steps reports (Adam's t - 1, the `step` of the dropout mask); steps < 2^53.  The weights and both
+ * moments written back and the counter set make a handle continue a run with the bits of the handle they were read from. */
+pvq_status pvq_note_trainer_set_steps(pvq_note_trainer *t, uint64_t steps);
+
 /* Page-locked host memory for the host-buffer entry points (pvq_vqt_calculate_batch_db, pvq_analyze_batch,
  * pvq_train_frames_db): with pageable buffers those calls are bound by staged PCIe copies (~16 GB/s); buffers from
  * here are DMA-able directly.  NULL on failure (pvq_last_error). */

@@ -648,4 +648,4 @@ from .readout import ReadoutBatch, readout_frame, readout_layout, readout_text  
 from .present import PresentBatch, present_blend_factors, present_frame, present_mips, present_settings  # noqa: E402,F401
 from .panels import CalmnessGraph, PanelsBatch, calmness_histogram_mesh, panel_topology, spectrum_mesh  # noqa: E402,F401
 from .note_model import NoteCarry, NoteModel, NoteModelParams, note_round  # noqa: E402,F401
-from .note_trainer import NoteTestResult, NoteTrainer, NoteTrainerHyper, dropout_keep, epoch, random_split, note_test_metrics  # noqa: E402,F401
+from .note_trainer import NoteTestResult, NoteTrainer, NoteTrainerHyper, dropout_keep, epoch, epoch_order, random_split, note_test_metrics  # noqa: E402,F401

@@ -69,6 +69,7 @@ EXPORTS = [
     "pvq_note_trainer_hyper_default", "pvq_note_trainer_create", "pvq_note_trainer_destroy", "pvq_note_trainer_step", "pvq_note_trainer_steps",
     "pvq_note_trainer_param_count", "pvq_note_trainer_read", "pvq_note_trainer_dropout_keep", "pvq_note_trainer_test", "pvq_note_test_metrics",
     "pvq_note_trainer_create_precision", "pvq_note_trainer_precision",
+    "pvq_note_trainer_epoch", "pvq_note_epoch_order", "pvq_note_trainer_write", "pvq_note_trainer_set_steps",
     "pvq_vqt_input_status", "pvq_vqt_last_gemm_flop", "pvq_vqt_last_sclk_mhz",
     "pvq_vqt_bandwidths_3db", "pvq_vqt_warning_count", "pvq_vqt_warning",
 ]
@@ -553,6 +554,12 @@ def load():
     L.pvq_note_trainer_test.restype = C.c_int
     dp = C.POINTER(C.c_double)
     L.pvq_note_test_metrics.argtypes = [C.POINTER(CNoteTestBatch), C.c_size_t, dp, dp, dp]; L.pvq_note_test_metrics.restype = C.c_int
+    if not _dev or _dev == "1" or hasattr(L, "pvq_note_trainer_epoch"):   # (as the carry above)
+        L.pvq_note_trainer_epoch.argtypes = [vp, vp, vp, C.c_size_t, up, C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64, fp, dp, vp]
+        L.pvq_note_trainer_epoch.restype = C.c_int
+        L.pvq_note_epoch_order.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, up]; L.pvq_note_epoch_order.restype = C.c_int
+        L.pvq_note_trainer_write.argtypes = [vp, C.c_int, fp, C.c_size_t]; L.pvq_note_trainer_write.restype = C.c_int
+        L.pvq_note_trainer_set_steps.argtypes = [vp, C.c_uint64]; L.pvq_note_trainer_set_steps.restype = C.c_int
     L.pvq_host_alloc.argtypes = [C.c_size_t]; L.pvq_host_alloc.restype = C.c_void_p
     L.pvq_host_free.argtypes = [C.c_void_p]
     L.pvq_vqt_input_status.argtypes = [vp, vp]; L.pvq_vqt_input_status.restype = C.c_int

@@ -155,6 +155,35 @@ pvq_status pvq_note_trainer_read(pvq_note_trainer* t, int what, float* out_host,
         return t->impl->read(what, out_host, capacity);
     });
 }
+// the inverse of pvq_note_trainer_read, and the counter: a checkpoint restored
+pvq_status pvq_note_trainer_write(pvq_note_trainer* t, int what, const float* host, size_t count) {
+    return guarded([&] {
+        if (!t) return null_handle();
+        return t->impl->write(what, host, count);
+    });
+}
+pvq_status pvq_note_trainer_set_steps(pvq_note_trainer* t, uint64_t steps) {
+    return guarded([&] {
+        if (!t) return null_handle();
+        return t->impl->set_steps(steps);
+    });
+}
+// train.py:147-162, one epoch; its order on the host
+pvq_status pvq_note_trainer_epoch(pvq_note_trainer* t, const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx, size_t n_idx,
+                                  uint32_t batch, uint64_t shuffle_seed, uint64_t epoch, float* out_losses, double* out_mean_loss, void* stream) {
+    return guarded([&] {
+        if (!t) return null_handle();
+        return t->impl->epoch(d_db, d_targets, n_rows, idx, n_idx, batch, shuffle_seed, epoch, out_losses, out_mean_loss, static_cast<hipStream_t>(stream));
+    });
+}
+pvq_status pvq_note_epoch_order(uint64_t seed, uint64_t epoch, uint64_t n, uint64_t first, uint64_t count, uint32_t* out) {
+    return guarded([&] {
+        std::string err;
+        const pvq_status st = pvq::note_epoch_order(seed, epoch, n, first, count, out, err);
+        if (st != PVQ_OK) pvq::set_last_error(err);
+        return st;
+    });
+}
 // train.py:164-198, the test pass
 pvq_status pvq_note_trainer_test(pvq_note_trainer* t, const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx, size_t n_idx,
                                  uint32_t batch, pvq_note_test_batch* out_batches, uint32_t* out_pitch, float* d_logits, void* stream) {

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "note_device.hpp"
+#include "note_epoch.hpp"
 #include "vqt_engine.hpp"
 
 namespace pvq {
@@ -431,6 +432,7 @@ NoteTrainer::~NoteTrainer() {
         if (h_idx_[s]) (void)hipHostFree(h_idx_[s]);
     }
     if (h_test_out_) (void)hipHostFree(h_test_out_);
+    if (h_epoch_) (void)hipHostFree(h_epoch_);
 }
 
 NthContext NoteTrainer::half_context() const {
@@ -607,7 +609,7 @@ void NoteTrainer::backward(uint32_t batch, hipStream_t stream) {
     gemm(G_NN, dA[cur], w + lay_.fc1_w.at, ws(ws_dfeat_), batch, F, mlp, mlp, F, raw, part, stream);
 }
 
-// upload, forward, loss; when training: backward, the conv gradient; PVQ_TRAIN_STEP: Adam, the shadow refresh of a bf16 handle
+// the checks, the upload, then run_step
 pvq_status NoteTrainer::step(int mode, const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx, uint32_t batch, float* d_loss,
                              float* d_logits, hipStream_t stream) {
     const NoteModelDims& d = lay_.d;
@@ -624,6 +626,12 @@ pvq_status NoteTrainer::step(int mode, const float* d_db, const float* d_targets
     PVQ_HIP(hipSetDevice(device_id_));
     const pvq_status up = upload_idx(idx, batch, stream);
     if (up != PVQ_OK) return up;
+    return run_step(mode, d_db, d_targets, batch, d_loss, d_logits, stream);
+}
+
+// forward, loss; when training: backward, the conv gradient; PVQ_TRAIN_STEP: Adam, the shadow refresh of a bf16 handle
+pvq_status NoteTrainer::run_step(int mode,const float* d_db, const float* d_targets, uint32_t batch, float* d_loss, float* d_logits, hipStream_t stream) {
+    const NoteModelDims& d = lay_.d;
     const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(ws(ws_idx_));
     const size_t n = lay_.n_params;
     float* arena = arena_.as<float>();
@@ -708,6 +716,88 @@ pvq_status NoteTrainer::test(const float* d_db, const float* d_targets, size_t n
     PVQ_HIP(hipStreamSynchronize(stream));
     std::memcpy(out_batches, h_test_out_, batch_bytes);
     if (out_pitch) std::memcpy(out_pitch, static_cast<const char*>(h_test_out_) + batch_bytes, NT_TEST_PITCH_BYTES);
+    return PVQ_OK;
+}
+
+// The split up once, its gathered order by one kernel, then per batch: its slice of the order into the step's index array (device to
+// device) and the step's launches, the loss into the batch's slot.  One read-back, one wait.
+pvq_status NoteTrainer::epoch(const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx, size_t n_idx, uint32_t batch,
+                              uint64_t shuffle_seed, uint64_t epoch, float* out_losses, double* out_mean_loss, hipStream_t stream) {
+    std::string err;
+    const pvq_status st = note_trainer_check_epoch(lay_.d, max_batch_, d_db, d_targets, n_rows, idx, n_idx, batch, err);
+    if (st != PVQ_OK) {
+        set_last_error(err);
+        return st;
+    }
+    if (device_id_ < 0) {
+        set_last_error("the note trainer runs on a GPU; this handle has none");
+        return PVQ_ERR_NO_DEVICE;
+    }
+    PVQ_HIP(hipSetDevice(device_id_));
+    const NoteTrainerEpochPlan plan = note_trainer_epoch_plan(n_idx, batch);
+    if (pvq_status s = epoch_buf_.reserve(plan.device_bytes)) return s;
+    if (plan.host_bytes > h_epoch_bytes_) {
+        if (h_epoch_) PVQ_HIP(hipHostFree(h_epoch_));
+        h_epoch_ = nullptr;
+        h_epoch_bytes_ = 0;
+        PVQ_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_epoch_), plan.host_bytes, hipHostMallocDefault));
+        h_epoch_bytes_ = plan.host_bytes;
+    }
+    uint32_t* words = epoch_buf_.as<uint32_t>();
+    uint32_t* d_split = words + plan.idx_at;
+    uint32_t* d_order = words + plan.order_at;
+    float* d_losses = reinterpret_cast<float*>(words + plan.loss_at);
+    uint32_t* d_idx = reinterpret_cast<uint32_t*>(ws(ws_idx_));
+
+    std::memcpy(h_epoch_ + plan.h_idx_at, idx, n_idx * sizeof(uint32_t));
+    PVQ_HIP(hipMemcpyAsync(d_split, h_epoch_ + plan.h_idx_at, n_idx * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    note_epoch_gather(d_split, d_order, static_cast<uint32_t>(n_idx), shuffle_seed, epoch, stream);
+    for (size_t k = 0; k < plan.n_batches; ++k) {
+        const uint32_t rows = k + 1 < plan.n_batches ? batch : plan.last_rows;
+        PVQ_HIP(hipMemcpyAsync(d_idx, d_order + k * batch, rows * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        const pvq_status rs = run_step(PVQ_TRAIN_STEP, d_db, d_targets, rows, d_losses + k, nullptr, stream);
+        if (rs != PVQ_OK) return rs;
+    }
+    // the one read-back, the one wait
+    float* h_losses = reinterpret_cast<float*>(h_epoch_ + plan.h_loss_at);
+    PVQ_HIP(hipMemcpyAsync(h_losses, d_losses, plan.n_batches * sizeof(float), hipMemcpyDeviceToHost, stream));
+    PVQ_HIP(hipStreamSynchronize(stream));
+    if (out_losses) std::memcpy(out_losses, h_losses, plan.n_batches * sizeof(float));
+    if (out_mean_loss) *out_mean_loss = note_epoch_mean_loss(h_losses, plan.n_batches);
+    return PVQ_OK;
+}
+
+pvq_status NoteTrainer::write(int what, const float* host, size_t count) {
+    std::string err;
+    const pvq_status st = note_trainer_check_write(what, host, count, lay_.n_params, err);
+    if (st != PVQ_OK) {
+        set_last_error(err);
+        return st;
+    }
+    if (device_id_ < 0) {
+        set_last_error("the note trainer's state lives on a GPU; this handle has none");
+        return PVQ_ERR_NO_DEVICE;
+    }
+    PVQ_HIP(hipSetDevice(device_id_));
+    PVQ_HIP(hipDeviceSynchronize());
+    PVQ_HIP(hipMemcpy(arena_.as<float>() + static_cast<size_t>(what) * lay_.n_params, host, lay_.n_params * sizeof(float), hipMemcpyHostToDevice));
+    if (what == PVQ_TRAIN_WEIGHTS && precision_ == PVQ_NOTE_BF16) {
+        // the 16-bit shadow is a function of the weights: as after nt_adam
+        nth_refresh_shadow(half_context(), nullptr);
+        PVQ_HIP(hipGetLastError());
+        PVQ_HIP(hipDeviceSynchronize());
+    }
+    return PVQ_OK;
+}
+
+pvq_status NoteTrainer::set_steps(uint64_t steps) {
+    std::string err;
+    const pvq_status st = note_trainer_check_steps(steps, err);
+    if (st != PVQ_OK) {
+        set_last_error(err);
+        return st;
+    }
+    steps_ = steps;
     return PVQ_OK;
 }
 

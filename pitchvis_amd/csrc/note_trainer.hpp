@@ -21,6 +21,8 @@
 //                   popcount, the row's loss as nt_loss's tree in double, the logits when asked; indexed by the position in idx
 //   nt_test_batches one wave per test batch: its rows' records added, the loss in double in an order fixed by the row count
 //   nt_test_pitches tp / fp / fn per output over all rows, from the masks
+// An epoch (train.py:147-162) is a host loop of the step's launches on one stream: the split goes up once, note_epoch.hip writes its
+// gathered order, each batch's slice reaches the step's index array by a device-to-device copy, and the batch losses come back in one read.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -59,13 +61,23 @@ class NoteTrainer {
     // Leaves the counter, the weights, the gradients and the moments as they are.
     pvq_status test(const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx, size_t n_idx, uint32_t batch,
                     pvq_note_test_batch* out_batches, uint32_t* out_pitch, float* d_logits, hipStream_t stream);
+    // train.py:147-162, one epoch over idx[0 .. n_idx) (HOST) in the order of note_epoch_math.hpp: every batch one PVQ_TRAIN_STEP with the
+    // bits of step() on that batch at that counter.  Fills the HOST outputs (each may be null), so it waits on `stream` at its end.
+    pvq_status epoch(const float* d_db, const float* d_targets, size_t n_rows, const uint32_t* idx, size_t n_idx, uint32_t batch, uint64_t shuffle_seed,
+                     uint64_t epoch, float* out_losses, double* out_mean_loss, hipStream_t stream);
     // the arena `what` names, n_params floats in state_dict order -> host.  Synchronises the device.
     pvq_status read(int what, float* out, size_t capacity);
+    // host -> the arena `what` names, the inverse of read; a bf16 handle's shadow follows its weights.  Synchronises the device.
+    pvq_status write(int what, const float* host, size_t count);
+    pvq_status set_steps(uint64_t steps);
 
    private:
     NoteTrainer() = default;
     // rows -> pinned slot -> the workspace's index array, on `stream`
     pvq_status upload_idx(const uint32_t* idx, uint32_t rows, hipStream_t stream);
+    // what step() queues once the workspace's index array holds the batch: forward, loss, and by `mode` backward, Adam, the shadow
+    // refresh; PVQ_TRAIN_STEP advances the counter.  Shared by step() and epoch().
+    pvq_status run_step(int mode, const float* d_db, const float* d_targets, uint32_t batch, float* d_loss, float* d_logits, hipStream_t stream);
     // train.py:87-99 on the rows the workspace's index array names: features, fc1, the hidden layers, the logits Z.  Queues only.
     void forward(const float* d_db, uint32_t batch, bool train, hipStream_t stream);
     // backward from nt_loss's dZ: every dense gradient of the arena and dfeat.  Queues only.
@@ -92,6 +104,10 @@ class NoteTrainer {
     DeviceBuffer test_rows_, test_out_;
     void* h_test_out_ = nullptr;
     size_t h_test_out_bytes_ = 0;
+    // an epoch (NoteTrainerEpochPlan): the split, its gathered order and the batch losses (grow-only), the pinned staging of both ends
+    DeviceBuffer epoch_buf_;
+    uint32_t* h_epoch_ = nullptr;
+    size_t h_epoch_bytes_ = 0;
     // float offsets into the workspace
     size_t ws_feat_ = 0, ws_dfeat_ = 0, ws_h_ = 0, ws_da_ = 0, ws_z_ = 0, ws_dz_ = 0, ws_convpart_ = 0, ws_rowloss_ = 0, ws_part_ = 0, ws_idx_ = 0;
 };

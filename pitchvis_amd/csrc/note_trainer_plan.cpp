@@ -5,6 +5,8 @@
 #include <cmath>
 #include <cstring>
 
+#include "note_epoch_math.hpp"
+
 namespace pvq {
 
 NoteTrainerLayout note_trainer_layout(const NoteModelDims& d) {
@@ -81,6 +83,22 @@ pvq_status note_trainer_check_hyper(const pvq_note_trainer_hyper* h, uint32_t ma
     return PVQ_OK;
 }
 
+namespace {
+// the row count of a dataset and every index of a batch, a test pass or an epoch
+pvq_status check_rows(const NoteModelDims& d, size_t n_rows, const uint32_t* idx, size_t n, std::string& err) {
+    if (n_rows > 0xffffffffull) {
+        err = "note trainer: a dataset holds at most 2^32 - 1 rows";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    for (size_t i = 0; i < n; ++i)
+        if (idx[i] < d.t_frames - 1 || idx[i] >= n_rows) {
+            err = "note trainer: idx[" + std::to_string(i) + "] = " + std::to_string(idx[i]) + " is outside [t_frames - 1, n_rows)";
+            return PVQ_ERR_INVALID_ARG;
+        }
+    return PVQ_OK;
+}
+}  // namespace
+
 pvq_status note_trainer_check_step(const NoteModelDims& d, uint32_t max_batch, int mode, const void* d_db, const void* d_targets, size_t n_rows,
                                    const uint32_t* idx, uint32_t batch, std::string& err) {
     if (mode != PVQ_TRAIN_STEP && mode != PVQ_TRAIN_GRAD && mode != PVQ_TRAIN_EVAL) {
@@ -95,16 +113,7 @@ pvq_status note_trainer_check_step(const NoteModelDims& d, uint32_t max_batch, i
         err = "note trainer: batch must lie in 1 .. max_batch (" + std::to_string(max_batch) + ")";
         return PVQ_ERR_INVALID_ARG;
     }
-    if (n_rows > 0xffffffffull) {
-        err = "note trainer: a dataset holds at most 2^32 - 1 rows";
-        return PVQ_ERR_INVALID_ARG;
-    }
-    for (uint32_t i = 0; i < batch; ++i)
-        if (idx[i] < d.t_frames - 1 || idx[i] >= n_rows) {
-            err = "note trainer: idx[" + std::to_string(i) + "] = " + std::to_string(idx[i]) + " is outside [t_frames - 1, n_rows)";
-            return PVQ_ERR_INVALID_ARG;
-        }
-    return PVQ_OK;
+    return check_rows(d, n_rows, idx, batch, err);
 }
 
 NtAdamStep note_trainer_adam_step(const pvq_note_trainer_hyper& h, uint64_t t) {
@@ -221,16 +230,7 @@ pvq_status note_trainer_check_test(const NoteModelDims& d, const void* d_db, con
         err = "note trainer: n_idx must lie in 1 .. 2^25";
         return PVQ_ERR_INVALID_ARG;
     }
-    if (n_rows > 0xffffffffull) {
-        err = "note trainer: a dataset holds at most 2^32 - 1 rows";
-        return PVQ_ERR_INVALID_ARG;
-    }
-    for (size_t i = 0; i < n_idx; ++i)
-        if (idx[i] < d.t_frames - 1 || idx[i] >= n_rows) {
-            err = "note trainer: idx[" + std::to_string(i) + "] = " + std::to_string(idx[i]) + " is outside [t_frames - 1, n_rows)";
-            return PVQ_ERR_INVALID_ARG;
-        }
-    return PVQ_OK;
+    return check_rows(d, n_rows, idx, n_idx, err);
 }
 
 pvq_status note_test_metrics(const pvq_note_test_batch* b, size_t n_batches, double* mean_f1, double* accuracy, double* mean_loss, std::string& err) {
@@ -254,6 +254,86 @@ pvq_status note_test_metrics(const pvq_note_test_batch* b, size_t n_batches, dou
     if (mean_f1) *mean_f1 = f1 / static_cast<double>(n_batches);
     if (accuracy) *accuracy = static_cast<double>(correct) / (static_cast<double>(NM_OUT) * static_cast<double>(rows));
     if (mean_loss) *mean_loss = loss / static_cast<double>(n_batches);
+    return PVQ_OK;
+}
+
+NoteTrainerEpochPlan note_trainer_epoch_plan(size_t n_idx, uint32_t batch) {
+    NoteTrainerEpochPlan p;
+    if (n_idx == 0 || batch == 0) return p;
+    p.n_batches = (n_idx + batch - 1) / batch;
+    p.last_rows = static_cast<uint32_t>(n_idx - (p.n_batches - 1) * batch);
+    p.idx_at = 0;
+    p.order_at = n_idx;
+    p.loss_at = 2 * n_idx;
+    p.device_bytes = (2 * n_idx + p.n_batches) * 4;
+    p.h_idx_at = 0;
+    p.h_loss_at = n_idx;
+    p.host_bytes = (n_idx + p.n_batches) * 4;
+    return p;
+}
+
+pvq_status note_trainer_check_epoch(const NoteModelDims& d, uint32_t max_batch, const void* d_db, const void* d_targets, size_t n_rows,
+                                    const uint32_t* idx, size_t n_idx, uint32_t batch, std::string& err) {
+    if (!d_db || !d_targets || !idx) {
+        err = "note trainer: d_db, d_targets or idx is null";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (batch < 1 || batch > max_batch) {
+        err = "note trainer: batch must lie in 1 .. max_batch (" + std::to_string(max_batch) + ")";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (n_idx < 1 || n_idx > NT_EPOCH_MAX_IDX) {
+        err = "note trainer: n_idx must lie in 1 .. 2^25";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    return check_rows(d, n_rows, idx, n_idx, err);
+}
+
+double note_epoch_mean_loss(const float* losses, size_t n_batches) {
+    double s = 0.0;
+    for (size_t k = 0; k < n_batches; ++k) s += static_cast<double>(losses[k]);
+    return s / static_cast<double>(n_batches);
+}
+
+pvq_status note_epoch_order(uint64_t seed, uint64_t epoch, uint64_t n, uint64_t first, uint64_t count, uint32_t* out, std::string& err) {
+    if (n < 1 || n > NE_MAX_N) {
+        err = "note epoch order: n must lie in 1 .. 2^32";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (first > n || count > n - first) {
+        err = "note epoch order: first + count exceeds n";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (!out) {
+        err = "note epoch order: out is null";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    const NoteEpochKeys k = ne_keys(seed, epoch, n);
+    for (uint64_t j = 0; j < count; ++j) out[j] = static_cast<uint32_t>(ne_order(k, first + j));
+    return PVQ_OK;
+}
+
+pvq_status note_trainer_check_write(int what, const void* host, size_t count, size_t n_params, std::string& err) {
+    if (what < PVQ_TRAIN_WEIGHTS || what > PVQ_TRAIN_ADAM_V) {
+        err = "note trainer: unknown array";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (!host) {
+        err = "note trainer: the array to write is null";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    if (count != n_params) {
+        err = "note trainer: count is " + std::to_string(count) + ", the handle holds " + std::to_string(n_params) + " parameters";
+        return PVQ_ERR_INVALID_ARG;
+    }
+    return PVQ_OK;
+}
+
+pvq_status note_trainer_check_steps(uint64_t steps, std::string& err) {
+    if (steps >= NT_MAX_STEPS) {
+        err = "note trainer: steps must lie below 2^53";
+        return PVQ_ERR_INVALID_ARG;
+    }
     return PVQ_OK;
 }
 

@@ -1,9 +1,10 @@
 // note_trainer_plan.hpp — host side of the note trainer (note_trainer.hip): the layout of the parameter arena, the argument checks,
-// the per-step Adam constants, the split-K rule of the GEMMs, the dropout mask function, and the plan and the metrics of the test
-// pass.  Plain data in, plain data out: no HIP, no device pointer, no environment (the note_model_plan.cpp pattern).
+// the per-step Adam constants, the split-K rule of the GEMMs, the dropout mask function, the plan and the metrics of the test
+// pass, the plan of an epoch and the checks of a restored checkpoint.  Plain data in, plain data out: no HIP, no device pointer, no
+// environment (the note_model_plan.cpp pattern).
 //
 // The step is pitchvis_train/train.py:108-162: forward in training mode (train.py:87-99), BCELoss, backward, optim.Adam with weight
-// decay (train.py:141-144).  The test pass is train.py:164-198.
+// decay (train.py:141-144).  The test pass is train.py:164-198, the epoch loop train.py:147-162.
 #pragma once
 
 #include <cstddef>
@@ -132,5 +133,30 @@ pvq_status note_trainer_check_test(const NoteModelDims& d, const void* d_db, con
 // what train.py:185-198 prints, from the records: the plain mean of the batch F1 scores (2 tp / (2 tp + fp + fn), 0 when that
 // denominator is 0), sum of correct / (128 * sum of rows), the plain mean of the batch losses.  An output may be null.
 pvq_status note_test_metrics(const pvq_note_test_batch* b, size_t n_batches, double* mean_f1, double* accuracy, double* mean_loss, std::string& err);
+
+// One epoch (train.py:147-162): the DataLoader's shuffle is the order of note_epoch_math.hpp, batch k its entries k * batch ..; the
+// last batch may be short and still counts (train.py:64).  The handle keeps one grow-only device buffer and one pinned host buffer
+// for it, both laid out in 4-byte words: the split as given, its gathered order, one loss per batch.
+constexpr size_t NT_EPOCH_MAX_IDX = size_t(1) << 25;   // as a test pass
+struct NoteTrainerEpochPlan {
+    size_t n_batches = 0;      // ceil(n_idx / batch)
+    uint32_t last_rows = 0;    // rows of the last batch, 1 .. batch
+    size_t idx_at = 0, order_at = 0, loss_at = 0;   // device: word offsets of d_idx [n_idx], d_order [n_idx], d_losses [n_batches]
+    size_t device_bytes = 0;
+    size_t h_idx_at = 0, h_loss_at = 0;             // pinned host: the staged idx [n_idx], the losses read back [n_batches]
+    size_t host_bytes = 0;
+};
+NoteTrainerEpochPlan note_trainer_epoch_plan(size_t n_idx, uint32_t batch);
+// the checks of an epoch that need no device: pointers, batch, n_idx, n_rows, every index.  err receives the text
+pvq_status note_trainer_check_epoch(const NoteModelDims& d, uint32_t max_batch, const void* d_db, const void* d_targets, size_t n_rows,
+                                    const uint32_t* idx, size_t n_idx, uint32_t batch, std::string& err);
+// running_loss / len(train_loader) (train.py:162): the batch losses added in double in batch order, over their number
+double note_epoch_mean_loss(const float* losses, size_t n_batches);
+// out[j] = order(first + j) of note_epoch_math.hpp for j < count, on the host.  Refuses n outside 1 .. 2^32, first + count > n, a null out
+pvq_status note_epoch_order(uint64_t seed, uint64_t epoch, uint64_t n, uint64_t first, uint64_t count, uint32_t* out, std::string& err);
+// the checks of pvq_note_trainer_write and pvq_note_trainer_set_steps
+pvq_status note_trainer_check_write(int what, const void* host, size_t count, size_t n_params, std::string& err);
+constexpr uint64_t NT_MAX_STEPS = uint64_t(1) << 53;   // Adam's t = steps + 1 goes through a double (note_trainer_adam_step)
+pvq_status note_trainer_check_steps(uint64_t steps, std::string& err);
 
 }  // namespace pvq

@@ -2,7 +2,9 @@
 owns the parameters, their gradients and Adam's moments on the device and runs forward (training mode), BCE loss, backward and Adam on
 a batch of rows gathered by index from a dataset in device memory: the ``[n_rows][n_bins]`` dB rows and ``[n_rows][128]`` targets
 ``train_dataset_streams`` leaves there.  ``state_dict()`` is what ``NoteModel.from_state_dict`` takes.  ``NoteTrainer.test`` is the test
-pass that follows the last epoch (train.py:164-198): micro-F1 per batch, accuracy and loss, counted on the device."""
+pass that follows the last epoch (train.py:164-198): micro-F1 per batch, accuracy and loss, counted on the device.  ``NoteTrainer.epoch``
+and ``fit`` are the epoch loop (train.py:147-162) with its shuffle made on the device (``epoch_order`` is that order on the host);
+``checkpoint`` and ``load_checkpoint`` stop a run and continue it with the same bits."""
 from __future__ import annotations
 
 import ctypes as C
@@ -55,6 +57,24 @@ def epoch(indices, batch: int):
     idx = np.ascontiguousarray(indices, np.uint32)
     for at in range(0, idx.size, int(batch)):
         yield idx[at:at + int(batch)]
+
+
+def epoch_order(seed: int, epoch: int, n: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+    """``order(first) .. order(first + count - 1)`` (uint32) of the permutation of ``[0, n)`` in which ``NoteTrainer.epoch`` visits ``n``
+    samples at ``(seed, epoch)``: the counter-based rule of include/pvq.h, on the host by ``pvq_note_epoch_order``.  ``count`` defaults
+    to the rest of the order."""
+    n, first = int(n), int(first)
+    count = max(n - first, 0) if count is None else int(count)
+    if min(n, first, count) < 0:
+        raise ValueError("note epoch order: n, first and count must not be negative")
+    out = np.empty(max(count, 1), np.uint32)
+    m = 2 ** 64 - 1
+    st = _lib.load().pvq_note_epoch_order(int(seed) & m, int(epoch) & m, n, first, count, out.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if st == _lib.PVQ_ERR_INVALID_ARG:
+        raise ValueError((_lib.load().pvq_last_error() or b"").decode())
+    from . import _check
+    _check(st)
+    return out[:count]
 
 
 def random_split(n_rows: int, t_frames: int, train_fraction: float = 0.8, seed: int = 0):
@@ -229,6 +249,91 @@ class NoteTrainer:
             raise ValueError((self._L.pvq_last_error() or b"").decode())
         _check(st)
         return NoteTestResult.from_records(rec, counts)
+
+    def epoch(self, d_db, d_targets, idx, batch: int, shuffle_seed: int = 0, epoch: int = 0, *, n_rows: Optional[int] = None, stream=None):
+        """One epoch (train.py:147-162) over the train split ``idx`` (host sequence of sample indices): batch ``k`` is
+        ``idx[epoch_order(shuffle_seed, epoch, len(idx))[k * batch:(k + 1) * batch]]`` (the last may be short and still counts), each
+        batch one ``step`` in mode "step" with that call's bits.  ``idx`` goes to the device once; the order is made and every batch
+        gathered there.  Returns ``(losses, mean_loss)``: the f32 loss of every batch, and their sum in double over their number, what
+        train.py:162 prints.  Synchronous: waits on ``stream`` once.  ``steps`` advances by ``len(losses)``."""
+        from . import _check, _ptr, _stream_handle
+        n_rows = self._dataset_rows(d_db, d_targets, n_rows)
+        ix = np.ascontiguousarray(idx, np.uint32).reshape(-1)
+        batch = int(batch)
+        if not 0 <= batch < 2 ** 32:
+            raise ValueError("note trainer: batch must lie in 1 .. max_batch")
+        losses = np.zeros(-(-ix.size // batch) if batch > 0 and ix.size else 1, np.float32)
+        mean = C.c_double()
+        m = 2 ** 64 - 1
+        st = self._L.pvq_note_trainer_epoch(self._h, _ptr(d_db), _ptr(d_targets), n_rows, ix.ctypes.data_as(C.POINTER(C.c_uint32)), ix.size, batch,
+                                            int(shuffle_seed) & m, int(epoch) & m, losses.ctypes.data_as(_fp), C.byref(mean), _stream_handle(stream))
+        if st == _lib.PVQ_ERR_INVALID_ARG:
+            raise ValueError((self._L.pvq_last_error() or b"").decode())
+        _check(st)
+        return losses, mean.value
+
+    def fit(self, d_db, d_targets, train_idx, epochs: int, batch: int, shuffle_seed: int = 0, start_epoch: int = 0, *, n_rows: Optional[int] = None,
+            stream=None) -> np.ndarray:
+        """train.py:147-162: ``epochs`` epochs ``start_epoch ..`` over ``train_idx``, each in its own order.  Returns the mean loss of
+        every epoch (f64).  A run stopped after epoch ``e`` continues from ``checkpoint()`` with ``start_epoch=e + 1``."""
+        ix = np.ascontiguousarray(train_idx, np.uint32).reshape(-1)
+        return np.array([self.epoch(d_db, d_targets, ix, batch, shuffle_seed, e, n_rows=n_rows, stream=stream)[1]
+                         for e in range(int(start_epoch), int(start_epoch) + int(epochs))], np.float64)
+
+    def write_flat(self, what: str, flat) -> None:
+        """the inverse of ``read_flat``: one f32 array of ``n_params`` values in state_dict order becomes "weights", "grads", "adam_m" or
+        "adam_v" (``pvq_note_trainer_write``; a bf16 handle's 16-bit shadow follows its weights).  Synchronises."""
+        from . import _check
+        a = np.ascontiguousarray(flat, np.float32).reshape(-1)
+        st = self._L.pvq_note_trainer_write(self._h, _ARRAYS[what], a.ctypes.data_as(_fp), a.size)
+        if st == _lib.PVQ_ERR_INVALID_ARG:
+            raise ValueError((self._L.pvq_last_error() or b"").decode())
+        _check(st)
+
+    def set_steps(self, steps: int) -> None:
+        """sets ``steps``: Adam's t - 1 and the step the dropout mask is keyed by"""
+        from . import _check
+        steps = int(steps)
+        if not 0 <= steps < 2 ** 64:
+            raise ValueError("note trainer: steps must lie below 2^53")
+        st = self._L.pvq_note_trainer_set_steps(self._h, steps)
+        if st == _lib.PVQ_ERR_INVALID_ARG:
+            raise ValueError((self._L.pvq_last_error() or b"").decode())
+        _check(st)
+
+    def checkpoint(self) -> dict:
+        """What continues this run with the same bits: "weights", "adam_m", "adam_v" (flat f32 arrays in state_dict order), "steps",
+        "hyper" (the ``NoteTrainerHyper`` fields), "precision" and "params" (n_bins, t_frames, mlp_size, mlp_layers).  The gradients are
+        left out: every step writes them anew.  Arrays, ints, floats, strings and two flat dicts of them: ``pickle`` stores it."""
+        from dataclasses import asdict
+        p = self.params
+        return {"weights": self.read_flat("weights"), "adam_m": self.read_flat("adam_m"), "adam_v": self.read_flat("adam_v"), "steps": self.steps,
+                "hyper": asdict(self.hyper), "precision": self.precision,
+                "params": {"n_bins": p.n_bins, "t_frames": p.t_frames, "mlp_size": p.mlp_size, "mlp_layers": p.mlp_layers}}
+
+    def load_checkpoint(self, ck: dict) -> None:
+        """Puts a ``checkpoint()`` back: weights, both moments and ``steps``.  The handle must have been made with the checkpoint's
+        model sizes, hyper-parameters and precision (ValueError otherwise): they are fixed when a handle is made, and a run
+        continues with the same bits only under the same ones.  Checked in full before anything is written."""
+        from dataclasses import asdict
+        p = self.params
+        mine = {"n_bins": p.n_bins, "t_frames": p.t_frames, "mlp_size": p.mlp_size, "mlp_layers": p.mlp_layers}
+        if "params" in ck and {k: int(v) for k, v in dict(ck["params"]).items()} != mine:
+            raise ValueError(f"note trainer: the checkpoint is of a model {dict(ck['params'])}, the handle of {mine}")
+        if str(ck["precision"]) != self.precision:
+            raise ValueError(f"note trainer: the checkpoint is of precision {ck['precision']}, the handle of {self.precision}")
+        if dict(ck["hyper"]) != asdict(self.hyper):
+            raise ValueError(f"note trainer: the checkpoint's hyper-parameters {dict(ck['hyper'])} are not the handle's {asdict(self.hyper)}")
+        arrays = {k: np.ascontiguousarray(ck[k], np.float32).reshape(-1) for k in ("weights", "adam_m", "adam_v")}
+        for k, a in arrays.items():
+            if a.size != self.n_params:
+                raise ValueError(f"note trainer: the checkpoint's {k} holds {a.size} values, the handle {self.n_params} parameters")
+        steps = int(ck["steps"])
+        if not 0 <= steps < 2 ** 53:
+            raise ValueError("note trainer: steps must lie below 2^53")
+        for k, a in arrays.items():
+            self.write_flat(k, a)
+        self.set_steps(steps)
 
     def read_flat(self, what: str = "weights", out: Optional[np.ndarray] = None) -> np.ndarray:
         """"weights", "grads", "adam_m" or "adam_v" as one f32 array in state_dict order.  Synchronises."""
